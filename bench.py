@@ -25,6 +25,11 @@ weight-streaming kernel): algorithmic bytes per launch / its mean launch time fr
 on the engine's stream, measured in a second instrumented pass of the same K steps.
 `cpu_baseline` is the oracle's C restatement (oracle/c) timed on this box's host cores on a
 bounded sample (see the "sample" field); it is a reported baseline, not a target.
+
+`--dump-outputs DIR` (rank 0): after the timed steps, what the headline leg's LAST timed step returned to its caller
+(`Engine.step_wait`: tokens, logprobs, probs_row0; in `--mode mixed` the last fused step) as DIR/<name>.npy, token
+ids as float64 and the rest as float32, a few KB in all.  Weights, prompts and sampler seeds all derive from `--seed`,
+so the same arguments give the same inputs and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -131,6 +136,17 @@ def load_synthetic(engine, cfg, seed, quant_bits, rank, world, dist, stats=None,
     if stats is not None:
         stats.update(broadcast_seconds=round(bsec, 4), broadcast_bytes=int(bbytes), broadcast_buckets=len(buckets) if world > 1 else 0)
     return nbytes
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array; integer arrays (token ids) as float64, the rest as float32."""
+    import numpy as np
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(d / f"{name}.npy", a.astype(np.float64 if a.dtype.kind in "iub" else np.float32))
 
 
 def streamed_weight_bytes(cfg, quant_bits):
@@ -305,7 +321,15 @@ def parse_args(argv=None):
                     help="rehearse the multi-process protocol without an engine (launch, rendezvous, bucketed weight "
                          "broadcast, barrier / max-over-ranks timing) -- the only mode that runs without a GPU; "
                          "prints a line with value = null")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline leg returned (tokens, logprobs, probs_row0) as "
+                         "DIR/<name>.npy (float64 ids, float32 values), to compare two builds output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the engine (not --dry-run)")
+    return args
 
 
 def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap):
@@ -340,7 +364,7 @@ def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap):
     engine.sync()
     t0 = time.perf_counter()
     last = run_steps(K)
-    engine.step_wait(last, B)
+    outputs = engine.step_wait(last, B)             # what the caller of the last timed step receives (--dump-outputs)
     engine.sync()
     torch.cuda.synchronize()
     own = time.perf_counter() - t0                  # this rank's K steps, before it waits for the others
@@ -359,7 +383,8 @@ def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap):
     n_launch, total_ms = engine.profile_read()
     engine.profile_select(None)
     kv.close()
-    return dict(elapsed=elapsed, t_prefill=t_prefill, n_launch=n_launch, total_ms=total_ms, own_min=own_min, own_max=own_max)
+    return dict(elapsed=elapsed, t_prefill=t_prefill, n_launch=n_launch, total_ms=total_ms, own_min=own_min, own_max=own_max,
+                outputs=outputs)
 
 
 def mixed_leg(engine, cfg, args, sample, dist, world):
@@ -374,6 +399,7 @@ def mixed_leg(engine, cfg, args, sample, dist, world):
     rng = np.random.default_rng(args.seed + 5)
     V = cfg["vocab_size"]
     out = {}
+    last_res = {}
     for fused in (True, False):
         kv = engine.new_paged_kv(B, block_tokens=64, max_tokens_per_row=ctx + K + W + 2 * C + 64, kv_dtype=args.kv_dtype)
         # B - 1 live sequences with `ctx` tokens each (prefilled 8 rows at a time), row B - 1 is the arrival slot
@@ -394,6 +420,7 @@ def mixed_leg(engine, cfg, args, sample, dist, world):
             if fused:
                 t = engine.step_enqueue_mixed(kv, live + [arriving], [[int(last[r])] for r in live] + [chunk], [1] * len(live) + [int(done)], sample)
                 res = engine.step_wait(t, len(live) + int(done))
+                last_res["fused"] = res
                 last[live] = res["tokens"][:len(live)]
                 if done:
                     last[arriving] = res["tokens"][-1]
@@ -428,7 +455,8 @@ def mixed_leg(engine, cfg, args, sample, dist, world):
             tt = torch.tensor([el], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        out["fused" if fused else "unfused"] = dict(elapsed=el, prompt_tokens=ptoks, decode_tokens=(B - 1) * K, kv_stats=kv.stats())
+        out["fused" if fused else "unfused"] = dict(elapsed=el, prompt_tokens=ptoks, decode_tokens=(B - 1) * K, kv_stats=kv.stats(),
+                                                    outputs=last_res.get("fused") if fused else None)
         kv.close()
     return out
 
@@ -541,6 +569,8 @@ def main():
         m = mixed_leg(engine, cfg, args, greedy, dist, world)
         if rank == 0:
             f, u = m["fused"], m["unfused"]
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, f["outputs"])
             w_bytes, _ = streamed_weight_bytes(cfg, quant_bits)
             print(json.dumps({
                 "metric": "decode_tokens_per_sec", "value": round(world * f["decode_tokens"] / f["elapsed"], 2), "unit": "tokens/s",
@@ -675,6 +705,8 @@ def main():
             engine.close()
             engine = None
             out["other_configs"] = other_config_legs(args, args.seed)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, head["outputs"])
         print(json.dumps(out), flush=True)
     if engine is not None:
         engine.close()

@@ -130,9 +130,10 @@ def test_bench_self_launches_two_ranks_as_a_plain_command():
     tiny = 151936 * 64 + 8 * (4 * 64 * 64 + 3 * 128 * 64 + 2 * 64) + 64              # tied embedding: no lm_head
     assert j["broadcast_buckets"] == 1 and j["broadcast_bytes"] >= 2 * tiny
     assert j["rehearsal_barrier_seconds"] >= 0.02                                     # the slower rank (rank 1) sets the time
-    # a failing rank takes the launch down instead of leaving the others at a collective
+    # a failing rank takes the launch down instead of leaving the others at a collective; the ranks are shown no GPU
+    # (HIP_VISIBLE_DEVICES=-1), so that they fail the same way on a host that has one
     bad = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "tiny-bf16"],
-                         cwd=str(root), env=env, capture_output=True, text=True, timeout=600)
+                         cwd=str(root), env=dict(env, HIP_VISIBLE_DEVICES="-1"), capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0 and "needs an MI355X" in bad.stderr
 
 

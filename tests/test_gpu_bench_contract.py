@@ -32,6 +32,30 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == "tokens/s" and c["sample"]
 
 
+def test_bench_dump_outputs_is_the_same_for_the_same_arguments(tmp_path):
+    """--dump-outputs DIR: the last timed step's tokens / logprobs / probs_row0, one .npy each (float64 ids, float32
+    values); two runs with the same arguments dump the same arrays, and --steps is the number of timed steps."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny-bf16", "--steps", "5", "--warmup", "1",
+                              "--context", "64", "--batch", "2", "--no-cpu-baseline", "--no-second-leg", "--dump-outputs", str(d)],
+                             cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        j = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
+        assert j["steps"] == 5 and j["ms_per_step"] > 0
+        got = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert set(got) == {"tokens", "logprobs", "probs_row0"}
+        assert got["tokens"].dtype == np.float64 and got["logprobs"].dtype == np.float32
+        assert all(a.shape == (2,) and np.all(np.isfinite(a)) for a in got.values())
+        assert np.array_equal(got["tokens"], np.round(got["tokens"])) and got["tokens"].min() >= 0
+        runs.append(got)
+    assert np.array_equal(runs[0]["tokens"], runs[1]["tokens"])
+    for k in ("logprobs", "probs_row0"):
+        assert np.allclose(runs[0][k], runs[1][k], rtol=0, atol=1e-5), k
+
 def test_bench_gpus_2_as_a_plain_command_runs_two_ranks_with_engines():
     """`python bench.py --gpus 2` (no torchrun): self-launch, rendezvous, bucketed weight broadcast, two engines decoding
     their own shards, barrier + max-over-ranks timing, one JSON line.  On this one-GPU box the ranks share cuda:0 and
