@@ -389,13 +389,12 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
                  const char* prof, bool sq_was_valid) {
   const int KT = f0.W.K;                      // the true K: columns of x
   // Which kernel for a call that is not a pure decode step (prefill, mixed step)?  Measured on Mistral-7B shapes, one prompt
-  // of L tokens (tools/debug/prefill_sweep.py, ms for the whole call): dense 16-bit weights -- streaming kernel 4.2 / 5.1 /
+  // of L tokens (ms for the whole call): dense 16-bit weights -- streaming kernel 4.2 / 5.1 /
   // 6.1 / 6.9 at L = 32 / 64 / 96 / 128 against 5.2 / 5.5 / 5.6 / 5.8 on the K-split 128 x 128 tile: the hand-over is at ~80 rows;
   // int4 -- 3.0 / 5.0 / 6.9 (L <= 96) against 15.5 on the tile path, which first writes a [hi | lo] 16-bit copy of every
   // matrix (4 x 54 us per layer): the streaming kernel keeps the call, in two row slabs up to twice its row limit.
-  static const int dense_short = getenv("MI_SHORT_PREFILL_ROWS") ? atoi(getenv("MI_SHORT_PREFILL_ROWS")) : 64;
   const bool quant = wk_is_quant(f.W.wk);
-  const size_t short_rows = e->opt_short_prefill_skinny ? (quant ? 128 : (size_t)dense_short) : 0;
+  const size_t short_rows = e->opt_short_prefill_skinny ? (quant ? 128 : 64) : 0;
   if (e->opt_skinny_gemm && e->cur_L != 1 && quant && e->opt_short_prefill_skinny && rows > 64 && rows <= 256 &&
       !gemm_skinny_supported(f.W, c, rows)) {
     // quantised weights, a call just above the streaming kernel's row limit: two slabs of rows, two reads of W
@@ -438,8 +437,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
   }
   // decode steps: the streaming kernel up to 96 rows for dense weights -- above that the K-split tile GEMM is ahead
   // (Mistral-7B bf16, KV 512: 96 rows 7.18 vs 7.14 ms / step, 128 rows 8.71 vs 7.96)
-  static const int decode_max_env = getenv("MI_SKINNY_DECODE_MAX") ? atoi(getenv("MI_SKINNY_DECODE_MAX")) : 0;   // A/B
-  const size_t decode_max = decode_max_env > 0 ? (size_t)decode_max_env : (quant ? 128 : 96);
+  const size_t decode_max = quant ? 128 : 96;
   if (e->opt_skinny_gemm && ((e->cur_L == 1 && rows <= decode_max) || rows <= short_rows) && gemm_skinny_supported(f.W, c, rows)) {
     // the decode step of a batch of 9..128 sequences (int4 / int8 weights: any batch up to 128): W is streamed once, K split over workgroups (gemm_skinny.hip).
     // Also a prefill of up to 128 rows in all (a short prompt, a few short prompts): at that size the op is a weight
@@ -807,8 +805,6 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   auto rounds = [&](int n) { return ((mx - 1 + n - 1) / n + rk - 1) / rk; };     // (the cached keys; the new one is merged from registers)
   const int r0 = rounds(ns);
   while (ns > 1 && rounds(ns - 1) == r0) --ns;
-  static const int ns_env = getenv("MI_ATTN_NSPLIT") ? atoi(getenv("MI_ATTN_NSPLIT")) : 0;   // A/B
-  if (ns_env > 0) ns = std::min(ns_env, std::max(1, mx / 64));
   return std::max(1, std::min(ns, 16));
 }
 

@@ -32,9 +32,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef MI_GEMM_VARIANT
-#define MI_GEMM_VARIANT 0       // A/B experiments (tools/debug/gemm_ab.py); 0 = the shipped kernel
-#endif
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int LDA = 72;   // LDS row stride in elements (144 B)
 
@@ -335,12 +332,9 @@ constexpr int AFR = 4;                                  // A fragments in flight
 constexpr int SYNC_AT = 13;                             // the item in front of which the K step's barrier sits
 constexpr int STORE_AT = 11;                            // the item (of 16 per K step) after which the next tile is written to LDS
 
-// BD ("B direct", A/B variant behind MI_GEMM_B_DIRECT): the W fragments do not go through LDS -- in the tile-major
-// layout a fragment is one contiguous KiB, so each wave loads the 8 fragments of its four N tiles for the NEXT K step
-// straight into a second register set (two sets in turn, the K loop is unrolled by two); LDS then carries only the X
-// tile (16 instead of 24 fragment reads per wave and step, half the stores).  Measured 2 % SLOWER than both operands
-// in LDS (68.5 k vs 69.9 k prefill tok/s): the LDS pipe was not the limit, the instruction order was (below).
-template <typename AT, bool SWIGLU, bool BD>
+// W fragments loaded straight from global into registers instead of through LDS measured 2 % slower (68.5 k vs 69.9 k
+// prefill tok/s): removed in this commit; see git history.
+template <typename AT, bool SWIGLU>
 __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -372,38 +366,24 @@ __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
   // STRAIGHT-LINE loads (no exec mask, no branch): a load under a condition makes hipcc drain the vmcnt queue at the
   // join -- here that was an exposed L2 round trip per K step.  Rows past M read row M - 1 and are zeroed on the
   // way into LDS; the step after the last re-reads the last step.
-  constexpr int NB = BD ? 1 : 4;
-  u32x4 areg[4], breg[NB];
+  u32x4 areg[4], breg[4];
   const AT* arow[4];
-  const char* brow[NB];
+  const char* brow[4];
   bool aok[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = tid + 512 * i, row = c >> 3, kq = c & 7;
     aok[i] = m0 + row < p.M;
     arow[i] = x + (size_t)min(m0 + row, p.M - 1) * p.ldx + kq * 8;
-    if constexpr (!BD) {
-      const int s = c >> 7, kb = (c >> 6) & 1, l = c & 63;
-      brow[i] = (const char*)p.w + ((size_t)w_tile_of(s) * (p.kw / 32) + (size_t)kb) * 1024 + l * 16;
-    }
+    const int s = c >> 7, kb = (c >> 6) & 1, l = c & 63;
+    brow[i] = (const char*)p.w + ((size_t)w_tile_of(s) * (p.kw / 32) + (size_t)kb) * 1024 + l * 16;
   }
-  const char* bptr[4];                                   // BD: this wave's four N tiles, lane-linear
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) bptr[nt] = (const char*)p.w + (size_t)w_tile_of(wn * 4 + nt) * (p.kw / 32) * 1024 + lane * 16;
-  auto load_a = [&](int ks) {
+  auto load_ab = [&](int ks) {
     const int ka = (ks * BK) % p.ka;
 #pragma unroll
     for (int i = 0; i < 4; ++i) areg[i] = *(const u32x4*)(arow[i] + ka);
-    if constexpr (!BD) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) breg[i] = *(const u32x4*)(brow[i] + (size_t)(ks % nkw) * 2048);
-    }
-  };
-  auto load_bd = [&](int ks, u32x4 (&dst)[2][4]) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dst[kb][nt] = *(const u32x4*)(bptr[nt] + (size_t)((ks % nkw) * 2 + kb) * 1024);
+    for (int i = 0; i < 4; ++i) breg[i] = *(const u32x4*)(brow[i] + (size_t)(ks % nkw) * 2048);
   };
   auto store_ab = [&](int buf) {
     AT* A = a_img(buf);
@@ -412,14 +392,11 @@ __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
       const int c = tid + 512 * i, row = c >> 3, kq = c & 7;
       *(u32x4*)&A[row * LDA + kq * 8] = aok[i] ? areg[i] : u32x4{0u, 0u, 0u, 0u};
     }
-    if constexpr (!BD) {
-      unsigned char* B = b_img(buf);
+    unsigned char* B = b_img(buf);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) *(u32x4*)(B + (size_t)(tid + 512 * i) * 16) = breg[i];     // (slot, kb, lane) order = piece index
-    }
+    for (int i = 0; i < 4; ++i) *(u32x4*)(B + (size_t)(tid + 512 * i) * 16) = breg[i];     // (slot, kb, lane) order = piece index
   };
 
-  u32x4 bset0[2][4], bset1[2][4];                        // BD: the W fragments of the current / the next K step
   // The fragment pipeline runs ACROSS the K steps: 16 (k block, M tile) items of 4 MFMAs per step; the A fragment of
   // item i + 3 is read from LDS while item i multiplies (ring of AFR registers; 16 % AFR == 0, so the ring index carries
   // over), and for the last three items of a step "item i + 3" is item 0..2 of the NEXT step, read from the other
@@ -434,11 +411,9 @@ __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) dst[nt] = *(const u32x4*)(B + (size_t)(((wn * 4 + nt) * 2 + kb) * 64 + lane) * 16);
   };
-  // one K step: `bc` holds this step's W fragments (BD), `bn` receives the next step's
-  auto step = [&](int ks, u32x4 (&bc)[2][4], u32x4 (&bn)[2][4]) {
+  auto step = [&](int ks) {
     const int cur = ks & 1;
-    load_a(min(ks + 1, nk - 1));
-    if constexpr (BD) load_bd(min(ks + 1, nk - 1), bn);
+    load_ab(min(ks + 1, nk - 1));
     __builtin_amdgcn_sched_barrier(0);           // keep the loads HERE, a whole step of MFMAs ahead of their use (hipcc
                                                  // otherwise sinks them next to the LDS stores at the bottom of the step)
     const AT* A = a_img(cur);
@@ -452,23 +427,14 @@ __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
       }
       const int nx = it + AFR - 1;
       af[nx % AFR] = nx < 16 ? a_frag(A, nx) : a_frag(An, nx - 16);
-      if constexpr (!BD) {
-        if (it == 3) b_frags(b_img(cur), 1, bf[1]);
-        if (it == SYNC_AT) b_frags(b_img(cur ^ 1), 0, bf[0]);     // (bf[0] is dead since item 7)
-      }
-#if MI_GEMM_VARIANT == 1
-      __builtin_amdgcn_s_setprio(1);
-#endif
+      if (it == 3) b_frags(b_img(cur), 1, bf[1]);
+      if (it == SYNC_AT) b_frags(b_img(cur ^ 1), 0, bf[0]);     // (bf[0] is dead since item 7)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-        acc[it & 7][nt] = mfma16<AT>(af[it % AFR], BD ? bc[it >> 3][nt] : bf[it >> 3][nt], acc[it & 7][nt]);
-#if MI_GEMM_VARIANT == 1
-      __builtin_amdgcn_s_setprio(0);
-#endif
+      for (int nt = 0; nt < 4; ++nt) acc[it & 7][nt] = mfma16<AT>(af[it % AFR], bf[it >> 3][nt], acc[it & 7][nt]);
       // the order is imposed on hipcc's scheduler (sched_group_barrier: 0x100 = LDS read, 0x008 = MFMA); left alone
       // it bunches the fragment reads and waits for them in front of single MFMAs
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      if (!BD && (it == 3 || it == SYNC_AT)) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+      if (it == 3 || it == SYNC_AT) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
       if (it == STORE_AT) {
         // the next step's tile goes into the other buffer (its readers finished before the last barrier): the loads
@@ -480,19 +446,18 @@ __global__ __launch_bounds__(512) void gemm_tile256_kernel(GemmParams p) {
     }
   };
 
-  load_a(0);
-  if constexpr (BD) load_bd(0, bset0);
+  load_ab(0);
   store_ab(0);
   __syncthreads();
   // static priority for the younger wave of every SIMD (waves 4..7 lose every issue arbitration by age otherwise):
   // prefill 72.9 k -> 73.5 k tok/s, two runs each on one box.  (Priority flipped around every MFMA group: -1 %.)
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-  if constexpr (!BD) b_frags(b_img(0), 0, bf[0]);
+  b_frags(b_img(0), 0, bf[0]);
 #pragma unroll
   for (int i = 0; i < AFR - 1; ++i) af[i] = a_frag(a_img(0), i);
-  for (int ks = 0; ks < nk; ks += 2) {
-    step(ks, bset0, bset1);
-    if (ks + 1 < nk) step(ks + 1, bset1, bset0);
+  for (int ks = 0; ks < nk; ks += 2) {           // two steps per trip: each call's buffer index ks & 1 is a constant
+    step(ks);
+    if (ks + 1 < nk) step(ks + 1);
   }
 
   if constexpr (!SWIGLU) {
@@ -715,170 +680,8 @@ __global__ __launch_bounds__(512) void gemm_dma256_kernel(GemmParams p) {
 }
 
 
-// ---------------------------------------------------------------------------------------------------------------
-// The same 256 x 256 x 64 tile on v_mfma_f32_32x32x16: per wave and K step 32 MFMAs of 32 cycles instead of 64 of 16.
-// Why: a 16x16x32 MFMA leaves 8 of its 16 cycles for other instructions to issue, the loop has ~135 of them per 64 MFMAs
-// (24 LDS reads, 8 + 8 staging loads / stores, ~45 address VALU, the waits) -- more than one wave's MFMA shadow holds;
-// a 32x32x16 MFMA leaves 24 of 32 cycles, i.e. 6 issue slots per MFMA and ~190 per K step.  Same staging, same LDS images
-// (the A fragment of 32 rows x 16 k reads rows at the padded 144-byte stride: the 16 lanes of a read group hit 16
-// distinct 16-byte slots; the B fragment of 32 W rows x 16 k is two 256-byte runs of the tile-major image, 2 KiB apart:
-// conflict-free), same barrier placement.  Item (ks16, mt) = 2 MFMAs (the wave's two 32-column N tiles); SwiGLU: N tile 0
-// is the gate tile, N tile 1 the matching up tile.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T>
-__device__ __forceinline__ f32x16 mfma32(u32x4 a, u32x4 b, f32x16 c) {
-  if constexpr (std::is_same<T, bf16>::value)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-#ifdef MI_GEMM_M32_BUILD      // a debug build target (hipcc -DMI_GEMM_M32_BUILD, run with MI_GEMM_M32=1): measured 7 % slower than the 16 x 16 x 32 form, not in the shipped library
-template <typename AT, bool SWIGLU>
-__global__ __launch_bounds__(512) void gemm_tile256_m32_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 2, wn = wave & 3;              // 2 x 4 waves
-  const int c32 = lane & 31, h2 = lane >> 5;
-  const int bm = blockIdx.x, bn = blockIdx.y;
-  const int m0 = bm * BM2;
-  const int nk = p.K / BK, nkw = p.kw / BK;
-  const AT* x = (const AT*)p.x;
-  const int ntiles_w = p.N / 16;
-  auto a_img = [&](int buf) { return (AT*)(smem2 + (size_t)buf * A2_BYTES); };
-  auto b_img = [&](int buf) { return smem2 + 2 * (size_t)A2_BYTES + (size_t)buf * B2_BYTES; };
-  auto w_tile_of = [&](int s) -> int {
-    int t;
-    if constexpr (!SWIGLU) t = (bn * BN2) / 16 + s;
-    else t = (bn * 128 + (s >> 2) * 32 + (s & 1) * 16 + ((s >> 1) & 1) * p.pair_offset) / 16;
-    return min(t, ntiles_w - 1);
-  };
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  u32x4 areg[4], breg[4];
-  const AT* arow[4];
-  const char* brow[4];
-  bool aok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = tid + 512 * i, row = c >> 3, kq = c & 7;
-    aok[i] = m0 + row < p.M;
-    arow[i] = x + (size_t)min(m0 + row, p.M - 1) * p.ldx + kq * 8;
-    const int s = c >> 7, kb = (c >> 6) & 1, l = c & 63;
-    brow[i] = (const char*)p.w + ((size_t)w_tile_of(s) * (p.kw / 32) + (size_t)kb) * 1024 + l * 16;
-  }
-  auto load_ab = [&](int ks) {
-    const int ka = (ks * BK) % p.ka;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) areg[i] = *(const u32x4*)(arow[i] + ka);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) breg[i] = *(const u32x4*)(brow[i] + (size_t)(ks % nkw) * 2048);
-  };
-  auto store_ab = [&](int buf) {
-    AT* A = a_img(buf);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 512 * i, row = c >> 3, kq = c & 7;
-      *(u32x4*)&A[row * LDA + kq * 8] = aok[i] ? areg[i] : u32x4{0u, 0u, 0u, 0u};
-    }
-    unsigned char* B = b_img(buf);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *(u32x4*)(B + (size_t)(tid + 512 * i) * 16) = breg[i];
-  };
-
-  // item it = (ks16 = it >> 2, mt = it & 3): A fragment of rows wm*128 + 32 mt + c32, k = 16 ks16 + 8 h2
-  u32x4 af[AFR], bf[4][2];
-  auto a_frag = [&](const AT* A, int it) {
-    return *(const u32x4*)&A[(wm * 128 + (it & 3) * 32 + c32) * LDA + (it >> 2) * 16 + h2 * 8];
-  };
-  auto b_frags = [&](const unsigned char* B, int ks16, u32x4 (&dst)[2]) {
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const int slot = wn * 4 + nt * 2 + (c32 >> 4);
-      dst[nt] = *(const u32x4*)(B + (size_t)(((slot * 2 + (ks16 >> 1)) * 64) + (2 * (ks16 & 1) + h2) * 16 + (c32 & 15)) * 16);
-    }
-  };
-  auto step = [&](int ks) {
-    const int cur = ks & 1;
-    load_ab(min(ks + 1, nk - 1));
-    __builtin_amdgcn_sched_barrier(0);
-    const AT* A = a_img(cur);
-    const AT* An = a_img(cur ^ 1);
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      if (it == SYNC_AT) {
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const int nx = it + AFR - 1;
-      af[nx % AFR] = nx < 16 ? a_frag(A, nx) : a_frag(An, nx - 16);
-      if (it == 1) b_frags(b_img(cur), 1, bf[1]);
-      if (it == 5) b_frags(b_img(cur), 2, bf[2]);
-      if (it == 9) b_frags(b_img(cur), 3, bf[3]);
-      if (it == SYNC_AT) b_frags(b_img(cur ^ 1), 0, bf[0]);        // (bf[0] is dead since item 3)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) acc[it & 3][nt] = mfma32<AT>(af[it % AFR], bf[it >> 2][nt], acc[it & 3][nt]);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      if (it == 1 || it == 5 || it == 9 || it == SYNC_AT) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      if (it == STORE_AT) {
-        __builtin_amdgcn_sched_barrier(0);
-        store_ab(cur ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
-
-  load_ab(0);
-  store_ab(0);
-  __syncthreads();
-  b_frags(b_img(0), 0, bf[0]);
-#pragma unroll
-  for (int i = 0; i < AFR - 1; ++i) af[i] = a_frag(a_img(0), i);
-  for (int ks = 0; ks < nk; ++ks) step(ks);
-
-  // ---- epilogue: lane (c32, h2), register r holds C[m = (r & 3) + 8 (r >> 2) + 4 h2][n = c32] of every 32 x 32 tile
-  AT* out = (AT*)p.out;
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * 128 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h2;
-      if (m >= p.M) continue;
-      if constexpr (SWIGLU) {
-        const int n = bn * 128 + wn * 32 + c32;
-        if (n >= p.pair_offset) continue;
-        if (p.out32) { epi32_swiglu(p, m, n, acc[mt][0][r], acc[mt][1][r]); continue; }
-        const float gt = (float)(AT)acc[mt][0][r], up = (float)(AT)acc[mt][1][r];
-        const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-        const float sl = (float)(AT)(gt * sig);
-        out[(size_t)m * p.ldo + n] = (AT)(sl * up);
-      } else {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-          const int n = bn * BN2 + wn * 64 + nt * 32 + c32;
-          if (n >= p.N) continue;
-          if (p.out32) { epi32_plain(p, m, n, acc[mt][nt][r]); continue; }
-          const float y = (float)(AT)acc[mt][nt][r];
-          if (p.epi == EPI_STORE) out[(size_t)m * p.ldo + n] = (AT)y;
-          else {
-            AT* hh = (AT*)p.resid;
-            hh[(size_t)m * p.ldo + n] = (AT)((float)hh[(size_t)m * p.ldo + n] + y);
-          }
-        }
-      }
-    }
-}
-#endif  // MI_GEMM_M32_BUILD
+// The same tile on v_mfma_f32_32x32x16 (32 MFMAs of 32 cycles per wave and K step instead of 64 of 16) measured 7 %
+// slower: removed in this commit; see git history.
 
 // out[row][:] = w * cast_T(x32 * rsqrt(mean(x32^2) + eps))   (nn.RMSNorm); one wave per row
 template <typename AT>
@@ -1082,8 +885,7 @@ bool gemm_prefill_supported(const LinearW& W, const GemvCall& c, size_t rows) {
                   W.K % 128 == 0;                       // through a [hi | lo] 16-bit copy (launch_dequant_q4_hilo)
   const bool q8 = ((W.wk == WK_Q8_BF16 && c.act == MI_BF16) || (W.wk == WK_Q8_F16 && c.act == MI_F16)) && W.group == 64;
   // float32 activations on a bf16 model (PagedKVCache mode): x goes through launch_split3_rows first
-  static const bool f32_ok = getenv("MI_GEMM_NO_F32") == nullptr;
-  const bool x32 = f32_ok && c.act == MI_F32 && (W.wk == WK_BF16 || (W.wk == WK_Q4_BF16 && W.group == 64 && W.K % 128 == 0)) &&
+  const bool x32 = c.act == MI_F32 && (W.wk == WK_BF16 || (W.wk == WK_Q4_BF16 && W.group == 64 && W.K % 128 == 0)) &&
                    c.ldx % 4 == 0 && W.K % 4 == 0;
   if (!dense && !q4 && !q8 && !x32) return false;
   if (W.K % BK != 0 || (!x32 && c.ldx % 8 != 0)) return false;
@@ -1159,11 +961,9 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
   p.epi = c.epi; p.out = c.out; p.ldo = c.ldo; p.resid = c.resid; p.pair_offset = c.pair_offset;
   const bool sw = c.epi == EPI_SWIGLU;
   const int ncols = sw ? c.pair_offset : W.N;
-  static const bool small_only = getenv("MI_GEMM_TILE128") != nullptr;        // A/B: always the 128 x 128 kernel
-  static const bool b_in_lds = getenv("MI_GEMM_B_DIRECT") == nullptr;         // A/B: set = W fragments straight from global
   // The 256 x 256 tile only where its grid fills the chip: at 8 x 1024 rows every linear has >= 512 blocks, but one prompt
   // of 256..1024 tokens gives N/256 x (1..4) blocks -- 16..64 for N = 4096 -- and measured 25 / 25 / 30 ms for 256 / 512 /
-  // 1024 tokens against 14 / 17 / 23 ms on the 128 x 128 tile (Mistral-7B bf16; tools/debug/prefill_sweep.py).
+  // 1024 tokens against 14 / 17 / 23 ms on the 128 x 128 tile (Mistral-7B bf16).
   const long blocks256 = (long)(((int)rows + BM2 - 1) / BM2) * ((ncols + (sw ? 128 : BN2) - 1) / (sw ? 128 : BN2));
   const char* dma_env = getenv("MI_GEMM_DMA");         // A/B and the bit-equality test: 0 = the register-staged tile (read per call)
   const bool dma = dma_env == nullptr || atoi(dma_env) != 0;
@@ -1173,7 +973,7 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
   int ks256 = 1;
   const char* sk_env = getenv("MI_GEMM_DMA_SPLITK");     // (read per call: the tests switch it)
   const bool splitk256 = sk_env == nullptr || atoi(sk_env) != 0;
-  if (rows >= 256 && !small_only && dma && splitk256 && !sw && splitk_ws != nullptr && W.N % 4 == 0) {
+  if (rows >= 256 && dma && splitk256 && !sw && splitk_ws != nullptr && W.N % 4 == 0) {
     // one 128-KiB workgroup per CU: the launch runs in rounds of n_cu workgroups.  Pick the split whose last round is
     // fullest, charging 2 % per extra slice for its partial tile and its share of the reduce (q|k|v at 1024 rows: 96
     // tiles -> 5 slices = 480 workgroups, 1.9 rounds; o_proj: 64 tiles -> 4 slices = one full round)
@@ -1186,32 +986,18 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
       if (score > best + 1e-9) { best = score; ks256 = ks; }
     }
   }
-  if (rows >= 256 && !small_only && (blocks256 >= 192 || ks256 > 1)) {  // both operands through LDS (256 x 256 tile)
+  if (rows >= 256 && (blocks256 >= 192 || ks256 > 1)) {  // both operands through LDS (256 x 256 tile)
     const int bn = sw ? 128 : BN2;
     dim3 grid2(((int)rows + BM2 - 1) / BM2, (ncols + bn - 1) / bn), block2(512);
     if (ks256 > 1) { grid2.z = ks256; p.ksplit = ks256; p.ws = (float*)splitk_ws; }
-#ifdef MI_GEMM_M32_BUILD
-    static const bool m32 = getenv("MI_GEMM_M32") != nullptr;               // A/B: the 32x32x16 form of the tile
-#endif
     const bool use_dma = dma && p.K >= 2 * BK;
-#ifdef MI_GEMM_M32_BUILD
-#define GO256_M32(T, S) else if (m32) { auto k = gemm_tile256_m32_kernel<T, S>; \
-        MI_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES)); \
-        hipLaunchKernelGGL(k, grid2, block2, LDS2_BYTES, st, p); }
-#else
-#define GO256_M32(T, S)
-#endif
 #define GO256(T, S) do { \
       if (use_dma) { auto k = gemm_dma256_kernel<T, S>; \
         MI_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DMA_BUF)); \
         hipLaunchKernelGGL(k, grid2, block2, 2 * DMA_BUF, st, p); } \
-      GO256_M32(T, S) \
-      else if (b_in_lds) { auto k = gemm_tile256_kernel<T, S, false>; \
+      else { auto k = gemm_tile256_kernel<T, S>; \
         MI_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES)); \
-        hipLaunchKernelGGL(k, grid2, block2, LDS2_BYTES, st, p); } \
-      else { auto k = gemm_tile256_kernel<T, S, true>; \
-        MI_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * A2_BYTES)); \
-        hipLaunchKernelGGL(k, grid2, block2, 2 * A2_BYTES, st, p); } } while (0)
+        hipLaunchKernelGGL(k, grid2, block2, LDS2_BYTES, st, p); } } while (0)
     if (c.act == MI_BF16 || x32) { if (sw) GO256(bf16, true); else GO256(bf16, false); }
     else { if (sw) GO256(f16, true); else GO256(f16, false); }
 #undef GO256
@@ -1227,12 +1013,11 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
   }
   dim3 grid(((int)rows + BM - 1) / BM, (ncols + (sw ? 64 : BN) - 1) / (sw ? 64 : BN)), block(256);
   // too few (M, N) blocks for 256 CUs: split K (plain / residual epilogues; W.N % 4 == 0 for the reduce kernel)
-  static const bool no_splitk = getenv("MI_GEMM_NO_SPLITK") != nullptr;
   const long blocks = (long)grid.x * grid.y;
   // ~512 workgroups of 256 threads in all (two per CU): measured against a target of 256 -- 10.5 vs 11.6 ms at 384 rows,
   // 20.0 vs 21.4 at 768, 21.4 vs 22.4 at 1024 (Mistral-7B bf16, whole prefill call)
-  static const int target = getenv("MI_GEMM_SPLITK_TARGET") ? atoi(getenv("MI_GEMM_SPLITK_TARGET")) : 512;   // A/B
-  if (!sw && !no_splitk && splitk_ws != nullptr && blocks < target && W.N % 4 == 0) {
+  constexpr int target = 512;
+  if (!sw && splitk_ws != nullptr && blocks < target && W.N % 4 == 0) {
     int ks = (int)std::min<long>(8, std::max<long>(1, target / blocks));
     ks = std::min(ks, (p.K / BK) / 8);                       // at least 8 K steps per slice
     while (ks > 1 && (size_t)ks * rows * W.N * sizeof(float) > splitk_cap) --ks;

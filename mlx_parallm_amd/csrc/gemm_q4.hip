@@ -25,10 +25,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "gemv_phase.h"
 
@@ -52,8 +49,6 @@ struct Q4Params {
   int ksplit;         // K slices over workgroups
   int nslab, nunits;  // row slabs of 16 MT rows; units = tile groups x ksplit
   float* ws; unsigned* ctr;
-  unsigned long long* trace;   // MI_Q4_DBG & 8: [8 workgroups][12 waves][64] shader-clock stamps (debug)
-  int dbg;            // timing-only ablations (MI_Q4_DBG; results wrong on purpose): 1 = no MFMA / FMA work, 2 = no staging of x, 4 = no weight re-issue
   const float* lora_t; int lora_t_ld;
   const float* lora_b0; const float* lora_b1;
   int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
@@ -119,9 +114,6 @@ __global__ __launch_bounds__(256) void q4_prep_kernel(const AT* x, int ldx, int 
     if ((tid & 7) == 0) sx[(size_t)(k >> 6) * Mpad + row] = sum;
   }
 }
-
-#define Q4_STAMP(i) do { if (p.trace != nullptr && blockIdx.x < 8 && lane == 0 && (i) < 64) \
-    p.trace[((size_t)blockIdx.x * 12 + wave) * 64 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 
 template <typename AT, int MT, bool SWIGLU>
 __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) {
@@ -342,37 +334,28 @@ __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) 
   // ================= the slice.  Compute waves: chunk c is multiplied, the block UK chunks ahead is issued; staging waves:
   // chunk c + 1 goes into the other buffer (free since the barrier that closed chunk c - 1).  One barrier per chunk for all.
   const int nloop = (nch + UK - 1) / UK * UK;
-  Q4_STAMP(0);
   if (stager) {
     stage_chunk(cur);
     __syncthreads();
-    Q4_STAMP(1);
     for (int c = 0; c < nloop; ++c) {
-      if (!(p.dbg & 2)) stage_chunk(nxt);
-      Q4_STAMP(2 + 4 * c);
+      stage_chunk(nxt);
       __syncthreads();
-      Q4_STAMP(5 + 4 * c);
       unsigned char* t = cur; cur = nxt; nxt = t;
     }
   } else {
 #pragma unroll
     for (int u = 0; u < UK; ++u) issue(u);
     __syncthreads();
-    Q4_STAMP(1);
     for (int c = 0; c < nloop; c += UK) {
 #pragma unroll
       for (int ci = 0; ci < UK; ++ci) {
         const int cc = c + ci;
         landed(ci, std::integral_constant<int, (UK - 1) * 6>{});
-        Q4_STAMP(2 + 4 * cc);
-        if (cc < nch && b0 + cc * KW + kw < b1 && !(p.dbg & 1)) block_mfma(ci, cur);     // (uniform per wave)
+        if (cc < nch && b0 + cc * KW + kw < b1) block_mfma(ci, cur);     // (uniform per wave)
         __builtin_amdgcn_sched_barrier(0);
-        Q4_STAMP(3 + 4 * cc);
         issue(ci);
         __builtin_amdgcn_sched_barrier(0);
-        Q4_STAMP(4 + 4 * cc);
         __syncthreads();                                     // the next chunk is complete; this chunk's buffer is free
-        Q4_STAMP(5 + 4 * cc);
         unsigned char* t = cur; cur = nxt; nxt = t;
       }
     }
@@ -403,7 +386,6 @@ __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) 
       }
     }
   }
-  Q4_STAMP(62);
   const bool owner = kw == 0 && valid && !stager;            // the wave that holds the unit's sums
 
   // ================= K split over workgroups (narrow linears): as gemm_skinny.hip -- write-through partial tiles, every wave
@@ -519,12 +501,7 @@ __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) 
 
 struct Q4Plan { int mt, nslab, TW, KW, NS, ksplit, ntu, ntiles, ngroups, nblk; size_t prep_bytes, ws_bytes; };
 
-int q4_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-// test / A-B hook (mi_op_gemm_skinny with ksplit < 0): the next plans of this thread; a field of 0 = the cost model's choice
+// test hook (mi_op_gemm_skinny with ksplit < 0): the next plans of this thread; a field of 0 = the cost model's choice
 thread_local int q4_force_mt = 0, q4_force_tw = 0, q4_force_kw = 0, q4_force_ks = 0, q4_force_ns = 0;
 
 constexpr int Q4_PAD_BLOCKS = 64;       // padding of the preparation buffers, in 128-k blocks (clamp-free staging runs past a slice's end)
@@ -548,7 +525,7 @@ int gemv_cu_count();
 // 218 workgroups, ONE round on 256 CUs where 4 x 2 gives 272 = two rounds (85); lm_head 2 row tiles 254 (272); the narrow
 // linears stay on the split-K kernel (q|k|v 24.5 vs 23.4, o 24.1 vs 21.2, down 53 vs 37.5: 80-112 tile groups leave this
 // shape ~10 chunks per workgroup around a 2.5 us head and tail) -- gemm_q4_supported() routes only the wide ones here.
-static int q4_min_tiles() { static const int v = q4_env("MI_Q4_MIN_TILES", 1024); return v; }
+constexpr int Q4_MIN_TILES = 1024;
 
 static Q4Plan q4_plan(const LinearW& W, const GemvCall& c, size_t rows) {
   Q4Plan pl{};
@@ -558,20 +535,13 @@ static Q4Plan q4_plan(const LinearW& W, const GemvCall& c, size_t rows) {
   pl.nblk = W.K / 128;
   const int mt_all = (int)((rows + 15) / 16);
   double best = 1e30;
-  static const int e_mt = q4_env("MI_Q4_MT", 0), e_tw = q4_env("MI_Q4_TW", 0), e_kw = q4_env("MI_Q4_KW", 0),
-                   e_ks = q4_env("MI_Q4_KSPLIT", 0), e_ns = q4_env("MI_Q4_NS", 0);                       // A/B overrides
-  const int f_mt = q4_force_mt > 0 ? q4_force_mt : e_mt, f_tw = q4_force_tw > 0 ? q4_force_tw : e_tw,
-            f_kw = q4_force_kw > 0 ? q4_force_kw : e_kw, f_ks = q4_force_ks > 0 ? q4_force_ks : e_ks,
-            f_ns = q4_force_ns > 0 ? q4_force_ns : e_ns;
+  const int f_mt = q4_force_mt, f_tw = q4_force_tw, f_kw = q4_force_kw, f_ks = q4_force_ks, f_ns = q4_force_ns;
   const double cus = gemv_cu_count();
   const bool forced = f_mt > 0 || f_tw > 0 || f_kw > 0 || f_ks > 0 || f_ns > 0;
   if (!forced && pl.nblk >= 2) {                     // the measured choice (see above)
     pl.mt = std::min(mt_all, sw ? 4 : 2);
     pl.nslab = (mt_all + pl.mt - 1) / pl.mt;
     pl.TW = 5; pl.KW = 2; pl.NS = 2; pl.ksplit = 1;
-    // a narrow matrix behind an RMSNorm (q|k|v): few tile pairs, so two per workgroup and K over four waves (sweep on
-    // 7168 x 5120 at 64 rows: 20 us + the 4.5-us preparation pass that is ALSO the norm, against 23.4 + 4.7)
-    if (!sw && pl.ntiles < q4_min_tiles()) { pl.TW = 2; pl.KW = 4; pl.NS = 4; }
     pl.ngroups = (pl.ntu + pl.TW - 1) / pl.TW;
     best = 0.0;
   }
@@ -615,24 +585,20 @@ static Q4Plan q4_plan(const LinearW& W, const GemvCall& c, size_t rows) {
   return pl;
 }
 
-// int4 (group 64) weights, 16-bit activations, 17..128 rows (MI_Q4_MIN_ROWS moves the lower bound for A/B runs)
+// int4 (group 64) weights, 16-bit activations, 17..128 rows
 bool gemm_q4_supported(const LinearW& W, const GemvCall& c, size_t rows) {
-  static const int on = q4_env("MI_Q4", 1), min_rows = q4_env("MI_Q4_MIN_ROWS", 17);
-  if (!on || c.force_v1 || W.layout != 1 || c.rnd != RND_NONE) return false;
+  if (c.force_v1 || W.layout != 1 || c.rnd != RND_NONE) return false;
   const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.group == 64 &&
                   W.K % 128 == 0;
-  if (!q4 || (int)rows < min_rows || rows > 128 || c.ldx % 8 != 0) return false;
+  if (!q4 || rows < 17 || rows > 128 || c.ldx % 8 != 0) return false;
   const int n = c.epi == EPI_SWIGLU ? c.pair_offset : W.N;
   if (n % 16 != 0) return false;
   if (c.epi == EPI_SWIGLU_GU8) return false;
-  // wide matrices only (gate|up, lm_head: >= 1024 tiles), unless a plan is forced (tests, A/B): see q4_plan
-  // ... and, behind MI_Q4_NARROW=1 (A/B), the narrow matrix that has an RMSNorm in front (q|k|v), where the preparation pass
-  // replaces the norm launch: measured on the config-5 shard 7301 / 7309 tok/s against 7345 / 7342 without (same box,
-  // alternating) -- not taken
-  static const int narrow = q4_env("MI_Q4_NARROW", 0);
+  // wide matrices only (gate|up, lm_head: >= 1024 tiles), unless a plan is forced (tests): see q4_plan.  (The narrow
+  // q|k|v behind its RMSNorm, the preparation pass replacing the norm launch, measured 7301 / 7309 tok/s against 7345 / 7342
+  // on the config-5 shard: removed in this commit; see git history.)
   const bool forced = q4_force_mt > 0 || q4_force_tw > 0 || q4_force_kw > 0 || q4_force_ks > 0 || q4_force_ns > 0;
-  if (!forced && W.N / 16 < q4_min_tiles() && !(narrow && c.pro == PRO_NORM && W.N / 16 >= 256 && rows > 32)) return false;
-  return true;
+  return forced || W.N / 16 >= Q4_MIN_TILES;
 }
 
 size_t gemm_q4_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows) { return q4_plan(W, c, rows).ws_bytes; }
@@ -700,14 +666,6 @@ int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t
   p.ntu = pl.ntu; p.ntiles = pl.ntiles; p.TW = pl.TW; p.KW = pl.KW; p.NS = pl.NS; p.nblk = pl.nblk; p.ksplit = pl.ksplit;
   p.nslab = pl.nslab; p.nunits = pl.ngroups * pl.ksplit;
   p.ws = (float*)((char*)ws + pl.prep_bytes); p.ctr = ctr;
-  static const int dbg = q4_env("MI_Q4_DBG", 0);
-  p.dbg = dbg;
-  static unsigned long long* trace_buf = nullptr;
-  if (dbg & 8) {
-    if (!trace_buf) { MI_HIP(hipMalloc(&trace_buf, 8 * 12 * 64 * 8)); }
-    MI_HIP(hipMemsetAsync(trace_buf, 0, 8 * 12 * 64 * 8, st));
-    p.trace = trace_buf;
-  }
   p.lora_t = c.lora_t; p.lora_t_ld = c.lora_t_ld;
   p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
   p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
@@ -715,28 +673,8 @@ int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t
   const size_t lds = 2 * (size_t)(pl.KW * 4 * pl.mt + 2) * 1024;
   const int nthreads = (pl.TW * pl.KW + pl.NS) * 64;
   const int grid = pl.nslab > 1 ? (p.nunits + 7) / 8 * 8 * pl.nslab : p.nunits;
-  const int rc = c.act == MI_BF16 ? q4_launch_at<bf16>(p, pl.mt, c.epi == EPI_SWIGLU, grid, nthreads, lds, st)
-                                  : q4_launch_at<f16>(p, pl.mt, c.epi == EPI_SWIGLU, grid, nthreads, lds, st);
-  if ((dbg & 8) && rc == MI_OK) {               // debug: per-wave timeline of the first workgroups, cycles relative to the workgroup's first stamp
-    static int dumps = 0;
-    std::vector<unsigned long long> h(8 * 12 * 64);
-    hipStreamSynchronize(st);
-    hipMemcpy(h.data(), trace_buf, h.size() * 8, hipMemcpyDeviceToHost);
-    if (dumps++ == 2) {
-      fprintf(stderr, "q4 trace: N=%d K=%d M=%d mt=%d TW=%d KW=%d NS=%d ks=%d grid=%d\n", W.N, W.K, (int)rows, pl.mt, pl.TW, pl.KW, pl.NS, pl.ksplit, grid);
-      for (int wg = 0; wg < 2; ++wg) {
-        unsigned long long t0 = ~0ull;
-        for (int w = 0; w < 12; ++w) if (h[(wg * 12 + w) * 64]) t0 = std::min(t0, h[(wg * 12 + w) * 64]);
-        for (int w = 0; w < 12; ++w) {
-          if (!h[(wg * 12 + w) * 64]) continue;
-          fprintf(stderr, " wg%d w%-2d:", wg, w);
-          for (int i = 0; i < 64; ++i) { const unsigned long long v = h[(wg * 12 + w) * 64 + i]; if (v) fprintf(stderr, " %d:%llu", i, v - t0); }
-          fprintf(stderr, "\n");
-        }
-      }
-    }
-  }
-  return rc;
+  return c.act == MI_BF16 ? q4_launch_at<bf16>(p, pl.mt, c.epi == EPI_SWIGLU, grid, nthreads, lds, st)
+                           : q4_launch_at<f16>(p, pl.mt, c.epi == EPI_SWIGLU, grid, nthreads, lds, st);
 }
 
 }  // namespace mi

@@ -400,11 +400,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
           const int pb = ((i * 2 + sg) * 2) * 4 * MB + mt * 16;
           a0 = *(const u32x4*)(cur + lane_off[0] + pb * 16);
           a1 = *(const u32x4*)(cur + lane_off[1] + (pb + 4 * MB) * 16);
-#ifdef MI_ABL_NOSX
-          sv = f32x4{1.f, 1.f, 1.f, 1.f};
-#else
           sv = *(const f32x4*)(cur + NIMG * FRAG + ((i * 2 + sg) * MB + mt * 16 + g * 4) * 4);
-#endif
         };
         u32x4 c0, c1, n0, n1;
         f32x4 csx, nsx;
@@ -418,23 +414,14 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
           if (mt == 0) {
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-#ifdef MI_ABL_NOUNPACK      // timing-only ablation builds (tools/debug/build_ablation_libs.sh): results are wrong on purpose
-              wq[a][0] = u32x4{dw[a][sg * 2 + 0], dw[a][sg * 2 + 1], dw[a][sg * 2 + 0], dw[a][sg * 2 + 1]};
-              wq[a][1] = u32x4{dw[a][sg * 2 + 1], dw[a][sg * 2 + 0], dw[a][sg * 2 + 1], dw[a][sg * 2 + 0]};
-#else
               wq[a][0] = unpack_q4<AT>(dw[a][sg * 2 + 0]);
               wq[a][1] = unpack_q4<AT>(dw[a][sg * 2 + 1]);
-#endif
               sc[a] = (float)((const AT*)&sr[a][slot])[sg];
               bb[a] = (float)((const AT*)&br[a][slot])[sg] - Magic<AT>::offs * sc[a];
             }
           }
 #pragma unroll
           for (int a = 0; a < NA; ++a) {
-#ifdef MI_ABL_NOFMA
-            acc[a][mt] = mfma16<AT>(c0, wq[a][0], acc[a][mt]);
-            acc[a][mt] = mfma16<AT>(c1, wq[a][1], acc[a][mt]);
-#else
             f32x4 d = {0.f, 0.f, 0.f, 0.f};
             d = mfma16<AT>(c0, wq[a][0], d);
             d = mfma16<AT>(c1, wq[a][1], d);
@@ -442,7 +429,6 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
             acc[a][mt].y = fmaf(sc[a], d.y, fmaf(bb[a], csx.y, acc[a][mt].y));
             acc[a][mt].z = fmaf(sc[a], d.z, fmaf(bb[a], csx.z, acc[a][mt].z));
             acc[a][mt].w = fmaf(sc[a], d.w, fmaf(bb[a], csx.w, acc[a][mt].w));
-#endif
           }
           c0 = n0; c1 = n1; csx = nsx;
           __builtin_amdgcn_sched_barrier(0);
@@ -454,24 +440,15 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
         float sc[NA], bb[NA];
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-#ifdef MI_ABL_NOUNPACK      // timing-only ablation builds (tools/debug/build_ablation_libs.sh): results are wrong on purpose
-          wq[a][0] = u32x4{dw[a][sg * 2 + 0], dw[a][sg * 2 + 1], dw[a][sg * 2 + 0], dw[a][sg * 2 + 1]};
-          wq[a][1] = u32x4{dw[a][sg * 2 + 1], dw[a][sg * 2 + 0], dw[a][sg * 2 + 1], dw[a][sg * 2 + 0]};
-#else
           wq[a][0] = unpack_q4<AT>(dw[a][sg * 2 + 0]);
           wq[a][1] = unpack_q4<AT>(dw[a][sg * 2 + 1]);
-#endif
           sc[a] = (float)((const AT*)&sr[a][slot])[sg];
           bb[a] = (float)((const AT*)&br[a][slot])[sg] - Magic<AT>::offs * sc[a];
         }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const int pb = ((i * 2 + sg) * 2) * 4 * MB + mt * 16;
-#ifdef MI_ABL_NOSX
-          const f32x4 sxv = f32x4{1.f, 1.f, 1.f, 1.f};
-#else
           const f32x4 sxv = *(const f32x4*)(cur + NIMG * FRAG + ((i * 2 + sg) * MB + mt * 16 + g * 4) * 4);
-#endif
           f32x4 dq[NA];
 #pragma unroll
           for (int a = 0; a < NA; ++a) dq[a] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -481,18 +458,10 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
             const u32x4 af1 = *(const u32x4*)(cur + img * FRAG + lane_off[1] + (pb + 4 * MB) * 16);
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-#ifdef MI_ABL_NOFMA
-              acc[a][mt] = mfma16<AT>(af0, wq[a][0], acc[a][mt]);
-              acc[a][mt] = mfma16<AT>(af1, wq[a][1], acc[a][mt]);
-#else
               dq[a] = mfma16<AT>(af0, wq[a][0], dq[a]);
               dq[a] = mfma16<AT>(af1, wq[a][1], dq[a]);
-#endif
             }
           }
-#ifdef MI_ABL_NOFMA
-          continue;
-#endif
 #pragma unroll
           for (int a = 0; a < NA; ++a) {
             const f32x4 d = dq[a];
@@ -584,9 +553,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
         __builtin_amdgcn_sched_barrier(0);
         issue(slot, unit + UK);
         __builtin_amdgcn_sched_barrier(0);
-#ifndef MI_ABL_NOSTAGE
         if (i == UPC / 2) store_x(cn, nxt, cc + 1 < c1);   // (past the slice's end the last chunk is staged again, unused)
-#endif
       }
       __syncthreads();                            // the next chunk's fragments are complete; this chunk's are free
       unsigned char* t = cur; cur = nxt; nxt = t;
@@ -862,12 +829,7 @@ struct SkinnyPlan { int ntiles, ngroups, nchunks, ksplit, mt, na, nslab; size_t 
 // 32 rows, two workgroups per CU) gain ~6 % as slabs; the SwiGLU pair does not (148 VGPRs at 32 rows = one workgroup per
 // CU either way; capped at 128 it spills inside the loop): 76.9 us at 64 rows vs 82.9 (3 K slices) / 87.4 (2) / 92.1 (1) as
 // slabs.  So: slabs for the single-stream linears above 32 rows and for everything above 96 rows (where the 128-row
-// int4 SwiGLU instantiation would spill -- int4 used to stop at 96 rows).  MI_SKINNY_SLABS=0 / 2: never / always (A/B).
-static int skinny_slabs_mode() {
-  static const int v = [] { const char* e = getenv("MI_SKINNY_SLABS"); return e == nullptr ? 1 : atoi(e); }();
-  return v;
-}
-static bool skinny_slabs_on() { return skinny_slabs_mode() != 0; }
+// int4 SwiGLU instantiation would spill -- int4 used to stop at 96 rows).
 
 // ksplit: time of the launch ~ rounds x (bytes one workgroup moves) / (rate one CU gets), with the partial
 // tiles (written, then read once) counted as extra bytes.  A lone workgroup cannot pull more than ~40 GB/s
@@ -879,8 +841,7 @@ SkinnyPlan skinny_plan(const LinearW& W, const GemvCall& c, size_t rows) {
   pl.nslab = 1;
   {
     const bool q4w = wk_is_quant(W.wk) && !(W.wk == WK_Q8_BF16 || W.wk == WK_Q8_F16);
-    const bool want = skinny_slabs_mode() == 2 || (skinny_slabs_mode() == 1 && (pl.na == 1 || rows > 96));
-    if (q4w && c.act != MI_F32 && rows > 32 && want) { pl.mt = 2; pl.nslab = (int)((rows + 31) / 32); }
+    if (q4w && c.act != MI_F32 && rows > 32 && (pl.na == 1 || rows > 96)) { pl.mt = 2; pl.nslab = (int)((rows + 31) / 32); }
     // (16-bit weights as two 16-row slabs at 17..32 rows -- Qwen3-14B gate|up has 136 tile groups for 256 CUs -- was measured
     // and dropped: Qwen3-14B gate|up 72 -> 145 us, Mistral-7B 54.2 -> 51.7 us with the step unchanged.)
   }
@@ -918,16 +879,6 @@ SkinnyPlan skinny_plan(const LinearW& W, const GemvCall& c, size_t rows) {
     else if (q4_big) t = k * (unit_w / std::min(r1, share) + unit_pp / std::min(40e9, share));     // partial tiles move at the memory rate
     else t = k * std::max(std::min(units, cus) * unit / bw, unit / r1);
     if (s == 1 || t < best * 0.97) { best = t; pl.ksplit = s; }            // a larger split has to earn its partials
-  }
-  // A/B: MI_SKINNY_FORCE="N:K:ksplit,..." overrides the model for the linears named
-  static const char* force = getenv("MI_SKINNY_FORCE");
-  if (force != nullptr) {
-    for (const char* q = force; *q;) {
-      int fn = 0, fk = 0, fs = 0;
-      if (sscanf(q, "%d:%d:%d", &fn, &fk, &fs) == 3 && fn == W.N && fk == W.K && fs >= 1) pl.ksplit = std::min(fs, std::min(16, pl.nchunks));
-      while (*q && *q != ',') ++q;
-      if (*q == ',') ++q;
-    }
   }
   pl.ws_bytes = pl.ksplit > 1 ? (size_t)pl.nslab * pl.ksplit * pl.ntiles * pl.na * pl.mt * 1024 : 0;
   if (pl.ksplit > 1 && c.act == MI_F32 && c.pro == PRO_NORM)       // deferred RMSNorm: the K slices' row sums of squares
@@ -978,21 +929,16 @@ int launch_at(const SkinnyParams& p, int qb, bool swiglu, int mt, int grid, hipS
 // 16-bit / int4 weights: gemv_mfma.hip serves up to 8 rows, this kernel 9..64 (its 16-row instantiation beats the
 // M <= 16 form of gemv_mfma.hip, which stages all of x per workgroup: Mistral-7B bf16 B = 16 3557 -> 3835 tok/s, int4
 // 4181 -> 5973, Qwen3-14B bf16 1401 -> 2386; at 8 rows and below gemv_mfma.hip wins, 3.59 vs 3.95 ms/step).
-// MI_SKINNY_MIN_ROWS moves the hand-over (A/B).
-static int skinny_min_rows() {
-  static const int v = [] { const char* e = getenv("MI_SKINNY_MIN_ROWS"); return e ? std::max(1, atoi(e)) : 9; }();
-  return v;
-}
+constexpr int SKINNY_MIN_ROWS = 9;
 
 bool gemm_skinny_supported(const LinearW& W, const GemvCall& c, size_t rows) {
   if (c.force_v1 || W.layout != 1) return false;
   // float32 activations on 16-bit dense weights (PagedKVCache mode): the 16-row instantiation with x split three ways
   if (c.act == MI_F32) {
-    static const bool x32_ok = getenv("MI_SKINNY_NO_F32") == nullptr;
     const int n32 = c.epi == EPI_SWIGLU ? c.pair_offset : W.N;
     const bool wok = W.wk == WK_BF16 || (W.group == 64 && ((W.wk == WK_Q4_BF16 && W.K % 128 == 0) || (W.wk == WK_Q8_BF16 && W.K % 64 == 0)));
     const bool lora = W.lora_b[0] != nullptr || W.lora_b[1] != nullptr;      // (the term is added in the plain-store epilogue)
-    return x32_ok && wok && rows >= 1 && rows <= 32 && W.K % 32 == 0 && c.ldx % 4 == 0 && n32 % 16 == 0 &&
+    return wok && rows >= 1 && rows <= 32 && W.K % 32 == 0 && c.ldx % 4 == 0 && n32 % 16 == 0 &&
            (!lora || c.epi == EPI_STORE);
   }
   if (c.rnd != RND_NONE) return false;
@@ -1000,18 +946,14 @@ bool gemm_skinny_supported(const LinearW& W, const GemvCall& c, size_t rows) {
                   W.K % 64 == 0;                         // int8 has no M <= 16 kernel of its own: every decode step runs here
   // int4: this kernel also wins below 9 rows, on every linear (M = 8, Mistral-7B shapes, us: q|k|v 9.2 vs 12.4, o 9.8 vs
   // 9.8, gate|up 19.0 vs 24.3, down 14.8 vs 23.7, lm_head 17.7 vs 24.5 -- more than the two RMSNorm launches it adds)
-  static const bool q4_small = getenv("MI_SKINNY_Q4_MIN_ROWS") == nullptr;   // A/B: set = hand-over at skinny_min_rows() as for 16-bit
-  if (rows < 1 || rows > 128) return false;
-  if (wk_is_quant(W.wk) && !q8 && rows > (skinny_slabs_on() ? 128u : 96u)) return false;   // (the 128-row int4 SwiGLU instantiation would spill registers; as 32-row slabs it runs)
+  if (rows < 1 || rows > 128) return false;      // (int4 SwiGLU runs above 96 rows as 32-row slabs: its 128-row instantiation would spill)
   // 16-bit weights below the hand-over: only the linears without a norm in front (o_proj, down_proj) whose K leaves
   // gemv_mfma a short last activation chunk (K mod 4096 in 1..1024: Qwen3-14B's 5120 and 17408) -- M = 8, us: o 14.3 vs
   // 16.2, down 34.5 vs 45.5, in the bench 1134 -> 1236 tok/s; no RMSNorm launch is added.  (Mistral-7B's down_proj,
   // K = 14336 = 3.5 chunks, measured neutral: 2213 vs 2203 tok/s, and stays on gemv_mfma.)
-  static const bool ragged_small = getenv("MI_SKINNY_NO_RAGGED_K") == nullptr;
   const int rem = W.K % 4096;
-  const bool small_ok = q8 || (q4_small && wk_is_quant(W.wk)) ||
-                        (ragged_small && !wk_is_quant(W.wk) && c.pro == PRO_NONE && W.K > 4096 && rem > 0 && rem <= 1024);
-  if ((int)rows < skinny_min_rows() && !small_ok) return false;
+  const bool small_ok = wk_is_quant(W.wk) || (c.pro == PRO_NONE && W.K > 4096 && rem > 0 && rem <= 1024);   // (int8 and int4: every row count)
+  if ((int)rows < SKINNY_MIN_ROWS && !small_ok) return false;
   const bool dense = (W.wk == WK_BF16 && c.act == MI_BF16) || (W.wk == WK_F16 && c.act == MI_F16);
   const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.group == 64 &&
                   W.K % 128 == 0;

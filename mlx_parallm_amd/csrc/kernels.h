@@ -241,7 +241,7 @@ struct AttnDecodeCall {
   int nsplit;
   float* partial;          // [B*Hq][nsplit][D+2]
   int* counters;           // [B*Hkv] zero-initialised arrival tickets
-  int variant;             // 0: MFMA kernel where it applies (16-bit caches, D % 32 == 0); 1: VALU kernel
+  int variant;             // 0: MFMA kernel where it applies (16-bit caches, D % 32 == 0; float32, D 64 / 128); 1: VALU kernel
   int n_host_off;          // > 0: host_off[b] = offsets[cache row of b], host_row[b] = that cache row (B <= 32)
   int host_off[32];
   int host_row[32];

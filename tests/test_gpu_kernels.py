@@ -349,7 +349,7 @@ def test_fused_decode_attention(act, Hq, Hkv, D, qk_norm, variant):
     eight 256-key rounds, 1 / 3 / 4 / 8 splits; the cache must receive exactly the new K / V row."""
     # (float32 caches: variant 0 is the v_mfma_f32_16x16x4_f32 kernel for head_dim 64 / 128 -- exact float32 products, held to
     # a 10 x tighter bound below -- and the VALU kernel otherwise.  A form on two-term bf16 operands was built, passed this
-    # test as variant 0 and measured slower: attn_decode.hip, -DMI_ATTN_DECODE_SPLIT_BUILD.)
+    # test as variant 0, measured slower and was removed; see git history.)
     # 1023 / 1024 / 1100: the bench's regime (one full 4 x 256-key pass, then a second, nearly empty round per
     # workgroup); 2047: eight rounds
     B, cap, max_pos = 8, 2064, 2112

@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--generic", type=int, default=0)
     ap.add_argument("--tiled", type=int, default=1)
-    ap.add_argument("--skinny", action="store_true", help="time gemm_skinny also for batch <= 16 (set MI_SKINNY_MIN_ROWS=1 for batch <= 8)")
+    ap.add_argument("--skinny", action="store_true", help="time gemm_skinny also for batch <= 16 (below 9 rows it takes only int4 / int8 weights and the ragged-K linears)")
     ap.add_argument("--ksplit", default="0", help="batch > 16 (gemm_skinny): comma-separated K splits to time, 0 = cost model")
     ap.add_argument("--lib", default=None, help="A/B: load this build of libmi355_decode.so instead")
     args = ap.parse_args()

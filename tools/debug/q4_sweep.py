@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times gemm_q4.hip's plans on the linears of one decoder block (int4 g64, bf16 activations) next to the split-K kernel it
-replaces (gemm_skinny.hip with its cost model: run the same command with MI_Q4=0 for that column).
+replaces (gemm_skinny.hip: time that column with a K split > 0, e.g. tools/bench_kernels.py --ksplit).
 
     python tools/debug/q4_sweep.py [--model qwen3-14b] [--rows 64] [--iters 30] [--plans auto|all]
 """
