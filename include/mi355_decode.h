@@ -224,8 +224,6 @@ int mi_profile_read(mi_engine* e, int64_t* n_launches, double* total_ms);
  *   "force_generic_gemv"      1: every linear layer on the generic VALU kernel (default 0)
  *   "fused_decode_attention"  0: decode attention as rope/append + attention + combine launches (default 1)
  *   "prefill_gemm"            0: prefill through the chunked <= 16-row kernels instead of the tile GEMM (default 1)
- *   "fused_gemv_pairs"        bit 0: o_proj -> gate|up, bit 1: down_proj -> next layer's q|k|v as ONE launch
- *                             each with an in-launch seam (default 0: measured no faster than two launches)
  *   "decode_attention_mfma"   0: the VALU form of the fused decode attention also for 16-bit caches (default 1)
  *   "skinny_gemm"             0: decode steps of 9..128 rows (int4 / int8 weights: of any size) through <= 16-row
  *                             launches of the M <= 16 kernels instead of the split-K streaming GEMM (default 1)

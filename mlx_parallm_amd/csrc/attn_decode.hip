@@ -454,33 +454,18 @@ __host__ __device__ constexpr size_t attn_mfma_lds_bytes() {
 //     is d = 64 h + 4 c16' + e.  D/4 MFMAs per key tile for each product (32 + 32 at D = 128, 32 cycles each).
 __device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
-
+// (a call, not an assignment: the address is computed before the value, which the epilogue's schedule depends on)
 template <typename T>
-__device__ __forceinline__ void store_out(T* p, T v, bool write_through) {
-  if (write_through) {   // read by other workgroups of this same launch (attn_decode_o_kernel)
-    if constexpr (sizeof(T) == 2)
-      __hip_atomic_store((unsigned short*)p, __builtin_bit_cast(unsigned short, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-      __hip_atomic_store((unsigned*)p, __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    *p = v;
-  }
-}
+__device__ __forceinline__ void store_out(T* p, T v) { *p = v; }
 
-// The launch as a device function: `after_loads()` runs once the body's own first global loads are in flight;
-// WT: publish `out` write-through.  Every thread of the workgroup returns from it (no thread exits the kernel
-// inside).  The two hooks exist for hosting another phase in the same launch: o_proj + residual behind the
-// attention (its whole weight matrix fits the workgroups' prefetch registers) was built that way, bit-identical,
-// and measured SLOWER than two launches -- 36.7 us with the weights prefetched from `after_loads`, 33.7 us
-// prefetched after the attention, against 19.6 + 12.1 us: the per-CU memory queue is in order, so the 128 KiB
-// of weight loads per CU sit in front of every dependent load of the attention's latency chain.  Dropped.
+// The launch as a device function.  o_proj + residual hosted behind the attention in the same launch was built,
+// bit-identical, and measured SLOWER than two launches (36.7 / 33.7 us against 19.6 + 12.1 us): dropped, DESIGN 4.
 // A twelve-wave form (1536 keys in one round of four splits) measured 2251 vs 2257 tok/s (bf16) and 1928 vs 1962 (float32
 // caches) against eight waves: removed in this commit; see git history.
 // float32 caches on two-term bf16 operands (three v_mfma_f32_16x16x32_bf16 per product) measured 1913 / 1907 against
 // 1998 / 1987 tok/s for the exact form below: removed in this commit; see git history.
-template <typename T, int D, int G, bool NORM, bool WT, bool PAGED, class Hook>
-__device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, unsigned char* smem, Hook after_loads) {
+template <typename T, int D, int G, bool NORM, bool PAGED>
+__device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, unsigned char* smem) {
   constexpr bool F32 = sizeof(T) == 4;           // float32 q / caches / outputs, multiplied exactly on v_mfma_f32_16x16x4_f32
   static_assert(D % 32 == 0 && D <= 128 && G <= 8 && (!F32 || D % 64 == 0), "16-bit caches: head_dim 32/64/96/128; float32: 64/128");
   constexpr int EPL = D / 16, NW32 = EPL * (int)sizeof(T) / 4, NTH = NWV * 64;
@@ -581,8 +566,9 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   }
   uint32_t r0[NW32];
   if constexpr (NORM) load_raw<NW32>((const T*)(is_k ? c.k_norm_w : c.q_norm_w) + li * EPL, r0);
+  // every global load the prologue waits for is in the queue ahead of this.  (Two barriers: where a hook used to sit
+  // between them; with one, hipcc allocates the body's registers differently.)
   __builtin_amdgcn_sched_barrier(0);
-  after_loads();                                 // every global load the prologue waits for is in the queue ahead of this
   __builtin_amdgcn_sched_barrier(0);
   float x[EPL];
   raw_to_f32<T, EPL, NW32>(raw, x);
@@ -811,7 +797,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     }
     const int h = kh * G + g;
     if (c.nsplit == 1) {
-      store_out<T>(&out[(size_t)h * D + d], store_act<T>(O / L, c.rnd_out), WT);
+      store_out<T>(&out[(size_t)h * D + d], store_act<T>(O / L, c.rnd_out));
     } else {
       float* pp = c.partial + (((size_t)b * s.Hq + h) * c.nsplit + split) * (D + 2);
       __hip_atomic_store(&pp[2 + d], O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -835,14 +821,14 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   for (int idx = tid; idx < G * D; idx += NTH) {
     const int g = idx / D, d = idx % D, h = kh * G + g;
     const float* pp = c.partial + ((size_t)b * s.Hq + h) * c.nsplit * (D + 2);
-    store_out<T>(&out[(size_t)h * D + d], store_act<T>(combine_splits<D>(pp, c.nsplit, d), c.rnd_out), WT);
+    store_out<T>(&out[(size_t)h * D + d], store_act<T>(combine_splits<D>(pp, c.nsplit, d), c.rnd_out));
   }
 }
 
 template <typename T, int D, int G, bool NORM, bool PAGED>
 __global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_kernel(AttnDecodeCall c) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  attn_decode_mfma_body<T, D, G, NORM, false, PAGED>(c, smem, NoHook{});
+  attn_decode_mfma_body<T, D, G, NORM, PAGED>(c, smem);
 }
 
 template <typename T, int D, int G, bool NORM>

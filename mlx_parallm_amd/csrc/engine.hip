@@ -124,15 +124,7 @@ struct mi_engine {
   bool sq_valid = false; const void* sq_src = nullptr; int sq_parts = 0, sq_K = 0, sq_ld = 0;
   bool opt_gu8 = true;                   // decode GEMV of a dense gate|up matrix on its row-interleaved copy: 7 one-tile items per CU instead of 3.5 pairs (twice the matrix's bytes)
   bool opt_f16_hilo = true;              // f16 dense weights in the float32-activation mode through an exact [hi | lo] bf16 copy (matrix cores)
-  int opt_fused_pairs = 0;               // bit 0: o_proj -> gate|up, bit 1: down_proj -> next q|k|v as one launch each.
-                                         // Off: measured on Mistral-7B bf16 B=8 the in-launch seam costs what the kernel
-                                         // boundary it replaces costs (bit 0: +-0 %, bit 1: -2 %), DESIGN.md section 5
-  unsigned* d_seam_counter = nullptr;    // arrival counter of the in-launch seams (monotonic)
-  int* d_seam_error = nullptr;           // set by a workgroup that gave up waiting at a seam
-  int* h_seam_err = nullptr;             // pinned: [slot] = *d_seam_error behind that step's launches, [NSLOT] = synchronous reads
-  unsigned seam_spin_limit = 1u << 20;   // polls before a workgroup gives up (option "seam_spin_limit"; tests force 0)
-  unsigned seam_base = 0;
-  int last_n = 0;                        // rows of the last enqueued step (device-resident token feed)                // value of *d_seam_counter once every enqueued launch has run
+  int last_n = 0;                        // rows of the last enqueued step (device-resident token feed)
   void* xn = nullptr;            // [rows][max(H, I)] normalised activations of the prefill GEMMs
   void* xs = nullptr; size_t xs_cap = 0;   // [rows][3 K] bf16: float32 activations split three ways (float32-KV prefill)
   void* gk_ws = nullptr; size_t gk_cap = 0;   // float32 partial tiles of the K-split 128 x 128 tile GEMM
@@ -362,6 +354,42 @@ bool ensure_gu8(mi_engine* e, FusedLinear& f, int pair_offset) {
   return true;
 }
 
+// the split-K workspace of gemm_skinny.hip: at least `need` bytes of partial tiles and `groups` arrival counters (zeroed)
+int ensure_skinny_ws(mi_engine* e, size_t need, int groups) {
+  if (need <= e->sk_ws_cap && groups <= e->sk_ctr_cap) return MI_OK;
+  MI_HIP(hipStreamSynchronize(e->stream));
+  if (need > e->sk_ws_cap) {
+    hipFree(e->sk_ws); e->sk_ws = nullptr; e->sk_ws_cap = 0;
+    MI_HIP(hipMalloc(&e->sk_ws, need));
+    e->sk_ws_cap = need;
+  }
+  if (groups > e->sk_ctr_cap) {
+    hipFree(e->sk_ctr); e->sk_ctr = nullptr; e->sk_ctr_cap = 0;
+    const int cap = std::max(groups, 4096);
+    MI_HIP(hipMalloc(&e->sk_ctr, (size_t)cap * sizeof(unsigned)));
+    MI_HIP(hipMemsetAsync(e->sk_ctr, 0, (size_t)cap * sizeof(unsigned), e->stream));
+    e->sk_ctr_cap = cap;
+  }
+  return MI_OK;
+}
+
+// the call on rows [r, r + M) of its x / out / resid
+GemvCall row_slab(const GemvCall& c, size_t r, size_t M, size_t es_in, size_t es_out) {
+  GemvCall cc = c;
+  cc.M = (int)M;
+  cc.x = (const char*)c.x + r * (size_t)c.ldx * es_in;
+  if (c.out) cc.out = (char*)c.out + r * (size_t)c.ldo * es_out;
+  if (c.resid) cc.resid = (char*)c.resid + r * (size_t)c.ldo * es_in;
+  return cc;
+}
+
+// RMSNorm of the call's x into e->xn (one workgroup per row); the call then reads e->xn with no prologue
+int norm_into_xn(mi_engine* e, GemvCall& c, size_t rows, int K, int rnd) {
+  MI_TRY(launch_rmsnorm_rows(c.x, c.ldx, c.norm_w, e->xn, K, (int)rows, K, c.eps, c.act, e->stream, true, rnd));
+  c.x = e->xn; c.ldx = K; c.pro = PRO_NONE;
+  return MI_OK;
+}
+
 // y = W x for `rows` rows, split into launches of at most 16 (MFMA) / 8 (generic) rows
 int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, GemvCall c, size_t rows, size_t es_in, size_t es_out,
                  const char* prof, bool sq_was_valid);
@@ -402,34 +430,12 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     GemvCall probe = c; probe.pro = PRO_NONE;
     if (gemm_skinny_supported(f.W, probe, half) && f.W.lora_b[0] == nullptr && f.W.lora_b[1] == nullptr) {
       Prof pr(e, prof);
-      if (c.pro == PRO_NORM) {
-        MI_TRY(launch_rmsnorm_rows(c.x, c.ldx, c.norm_w, e->xn, KT, (int)rows, KT, c.eps, c.act, e->stream, true, c.rnd));
-        c.x = e->xn; c.ldx = KT; c.pro = PRO_NONE;
-      }
-      const char* x0 = (const char*)c.x; char* o0 = (char*)c.out; char* r0 = (char*)c.resid;
+      if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
       for (size_t r = 0; r < rows; r += half) {
-        GemvCall cc = c;
-        cc.M = (int)std::min(half, rows - r);
-        cc.x = x0 + r * (size_t)c.ldx * es_in;
-        if (o0) cc.out = o0 + r * (size_t)c.ldo * es_out;
-        if (r0) cc.resid = r0 + r * (size_t)c.ldo * es_in;
+        const GemvCall cc = row_slab(c, r, std::min(half, rows - r), es_in, es_out);
         const size_t need = gemm_skinny_ws_bytes(f.W, cc, (size_t)cc.M);
         const int groups = gemm_skinny_groups(f.W, cc, (size_t)cc.M);
-        if (need > e->sk_ws_cap || groups > e->sk_ctr_cap) {
-          MI_HIP(hipStreamSynchronize(e->stream));
-          if (need > e->sk_ws_cap) {
-            hipFree(e->sk_ws); e->sk_ws = nullptr; e->sk_ws_cap = 0;
-            MI_HIP(hipMalloc(&e->sk_ws, need));
-            e->sk_ws_cap = need;
-          }
-          if (groups > e->sk_ctr_cap) {
-            hipFree(e->sk_ctr); e->sk_ctr = nullptr; e->sk_ctr_cap = 0;
-            const int cap = std::max(groups, 4096);
-            MI_HIP(hipMalloc(&e->sk_ctr, (size_t)cap * sizeof(unsigned)));
-            MI_HIP(hipMemsetAsync(e->sk_ctr, 0, (size_t)cap * sizeof(unsigned), e->stream));
-            e->sk_ctr_cap = cap;
-          }
-        }
+        MI_TRY(ensure_skinny_ws(e, need, groups));
         MI_TRY(launch_gemm_skinny(f.W, cc, (size_t)cc.M, e->stream, e->sk_ws, e->sk_ctr));
       }
       return MI_OK;
@@ -461,10 +467,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     const bool defer = e->opt_defer_norm && c.pro == PRO_NORM && c.act == MI_F32 && c.rnd == RND_NONE && !handed;
     const bool q4_prep = gemm_q4_supported(f.W, c, rows);      // gemm_q4.hip: its preparation pass over x applies the RMSNorm
     if (handed) { c.sq_in = e->d_sq; c.sq_parts = e->sq_parts; }
-    else if (c.pro == PRO_NORM && !defer && !q4_prep) {
-      MI_TRY(launch_rmsnorm_rows(c.x, c.ldx, c.norm_w, e->xn, KT, (int)rows, KT, c.eps, c.act, e->stream, true, c.rnd));
-      c.x = e->xn; c.ldx = KT; c.pro = PRO_NONE;
-    }
+    else if (c.pro == PRO_NORM && !defer && !q4_prep) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
     const size_t need = gemm_skinny_ws_bytes(f.W, c, rows);
     const int groups = gemm_skinny_groups(f.W, c, rows);
     const int tgroups = gemm_skinny_tile_groups(f.W, c, rows);
@@ -474,21 +477,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       if (!e->d_sq) MI_HIP(hipMalloc(&e->d_sq, (size_t)4096 * 16 * sizeof(float)));     // (64 tile groups x <= 128 rows fit eight times)
       c.sq_out = e->d_sq;
     }
-    if (need > e->sk_ws_cap || groups > e->sk_ctr_cap) {
-      MI_HIP(hipStreamSynchronize(e->stream));
-      if (need > e->sk_ws_cap) {
-        hipFree(e->sk_ws); e->sk_ws = nullptr; e->sk_ws_cap = 0;
-        MI_HIP(hipMalloc(&e->sk_ws, need));
-        e->sk_ws_cap = need;
-      }
-      if (groups > e->sk_ctr_cap) {
-        hipFree(e->sk_ctr); e->sk_ctr = nullptr; e->sk_ctr_cap = 0;
-        const int cap = std::max(groups, 4096);
-        MI_HIP(hipMalloc(&e->sk_ctr, (size_t)cap * sizeof(unsigned)));
-        MI_HIP(hipMemsetAsync(e->sk_ctr, 0, (size_t)cap * sizeof(unsigned), e->stream));
-        e->sk_ctr_cap = cap;
-      }
-    }
+    MI_TRY(ensure_skinny_ws(e, need, groups));
     MI_TRY(launch_gemm_skinny(f.W, c, rows, e->stream, e->sk_ws, e->sk_ctr));
     if (produce) { e->sq_valid = true; e->sq_src = c.resid; e->sq_parts = tgroups; e->sq_K = f.W.N; e->sq_ld = leave_ld; }
     return MI_OK;
@@ -511,8 +500,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       MI_TRY(launch_split3_rows(c.x, c.ldx, c.pro == PRO_NORM ? c.norm_w : nullptr, c.eps, e->xs, (int)rows, KT, e->stream, terms));
       c.x = e->xs; c.ldx = terms * KT; c.pro = PRO_NONE;
     } else if (c.pro == PRO_NORM) {    // (one workgroup per row also here: one L2 round trip per row instead of a wave's 16)
-      MI_TRY(launch_rmsnorm_rows(c.x, c.ldx, c.norm_w, e->xn, KT, (int)rows, KT, c.eps, c.act, e->stream, true));
-      c.x = e->xn; c.ldx = KT; c.pro = PRO_NONE;
+      MI_TRY(norm_into_xn(e, c, rows, KT, RND_NONE));
     }
     void* scratch = nullptr;
     if (wk_is_quant(f.W.wk)) {               // int4: the GEMM multiplies by a [hi | lo] 16-bit copy made on the fly
@@ -546,10 +534,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     Prof pr(e, prof);
     const bool lora32 = f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr;
     if (lora32) { GemvCall cl = c; cl.M = (int)rows; MI_TRY(launch_lora_down(f0.W, cl, e->lora_t, 128, e->stream)); }
-    if (c.pro == PRO_NORM) {
-      MI_TRY(launch_rmsnorm_rows(c.x, c.ldx, c.norm_w, e->xn, KT, (int)rows, KT, c.eps, c.act, e->stream, true, c.rnd));
-      c.x = e->xn; c.ldx = KT; c.pro = PRO_NONE;
-    }
+    if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
     // workspace for every chunk size that is launched below: full 32-row chunks and the tail, whose plan (tile rows,
     // K split) is made for ITS row count and can need more partial-tile space than the 32-row plan
     GemvCall c16 = c; c16.M = 32;
@@ -561,28 +546,9 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       need = std::max(need, gemm_skinny_ws_bytes(f.W, ct, tail));
       groups = std::max(groups, gemm_skinny_groups(f.W, ct, tail));
     }
-    if (need > e->sk_ws_cap || groups > e->sk_ctr_cap) {
-      MI_HIP(hipStreamSynchronize(e->stream));
-      if (need > e->sk_ws_cap) {
-        hipFree(e->sk_ws); e->sk_ws = nullptr; e->sk_ws_cap = 0;
-        MI_HIP(hipMalloc(&e->sk_ws, need));
-        e->sk_ws_cap = need;
-      }
-      if (groups > e->sk_ctr_cap) {
-        hipFree(e->sk_ctr); e->sk_ctr = nullptr; e->sk_ctr_cap = 0;
-        const int cap = std::max(groups, 4096);
-        MI_HIP(hipMalloc(&e->sk_ctr, (size_t)cap * sizeof(unsigned)));
-        MI_HIP(hipMemsetAsync(e->sk_ctr, 0, (size_t)cap * sizeof(unsigned), e->stream));
-        e->sk_ctr_cap = cap;
-      }
-    }
-    const char* x0 = (const char*)c.x; char* o0 = (char*)c.out; char* r0 = (char*)c.resid;
+    MI_TRY(ensure_skinny_ws(e, need, groups));
     for (size_t r = 0; r < rows; r += 32) {
-      GemvCall cc = c;
-      cc.M = (int)std::min<size_t>(32, rows - r);
-      cc.x = x0 + r * (size_t)c.ldx * es_in;
-      if (o0) cc.out = o0 + r * (size_t)c.ldo * es_out;
-      if (r0) cc.resid = r0 + r * (size_t)c.ldo * es_in;
+      GemvCall cc = row_slab(c, r, std::min<size_t>(32, rows - r), es_in, es_out);
       if (lora32) { cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128; }
       MI_TRY(launch_gemm_skinny(f.W, cc, (size_t)cc.M, e->stream, e->sk_ws, e->sk_ctr));
     }
@@ -609,13 +575,8 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
   // here only if the option was switched on later; without it the paired-tile form below)
   const bool gu8 = mfma && c.epi == EPI_SWIGLU && gu8_wanted(e, f0, c.pair_offset) &&
                    ensure_gu8(e, const_cast<FusedLinear&>(f0), c.pair_offset);
-  const char* x0 = (const char*)c.x; char* o0 = (char*)c.out; char* r0 = (char*)c.resid;
   for (size_t r = 0; r < rows; r += step) {
-    GemvCall cc = c;
-    cc.M = (int)std::min(step, rows - r);
-    cc.x = x0 + r * (size_t)c.ldx * es_in;
-    if (o0) cc.out = o0 + r * (size_t)c.ldo * es_out;
-    if (r0) cc.resid = r0 + r * (size_t)c.ldo * es_in;
+    GemvCall cc = row_slab(c, r, std::min(step, rows - r), es_in, es_out);
     if (has_lora) {
       cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128;
       MI_TRY(launch_lora_down(f0.W, cc, e->lora_t + r * 128, 128, e->stream));
@@ -631,69 +592,6 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
   }
   return MI_OK;
 }
-
-// decode: two dependent GEMVs (b reads a's output) in one launch when the MFMA pair kernel supports them
-bool can_pair(mi_engine* e, const FusedLinear& fa, GemvCall a, const FusedLinear& fb, GemvCall b, size_t rows) {
-  if (!e->opt_fused_pairs || rows > 8) return false;
-  a.force_v1 = b.force_v1 = e->opt_force_v1;
-  a.M = b.M = (int)rows;
-  if (fa.W.lora_b[0] || fa.W.lora_b[1] || fb.W.lora_b[0] || fb.W.lora_b[1]) return false;
-  return gemv_pair_supported(fa.W, a, fb.W, b);
-}
-
-int ensure_seam(mi_engine* e) {          // arrival counter + error flag of the in-launch seams
-  if (e->d_seam_counter == nullptr) {
-    MI_HIP(hipMalloc(&e->d_seam_counter, sizeof(unsigned)));
-    MI_HIP(hipMalloc(&e->d_seam_error, sizeof(int)));
-    MI_HIP(hipMemsetAsync(e->d_seam_counter, 0, sizeof(unsigned), e->stream));
-    MI_HIP(hipMemsetAsync(e->d_seam_error, 0, sizeof(int), e->stream));
-    MI_HIP(hipHostMalloc(&e->h_seam_err, (NSLOT + 1) * sizeof(int)));
-    for (int i = 0; i <= NSLOT; ++i) e->h_seam_err[i] = 0;
-    e->seam_base = 0;
-  }
-  return MI_OK;
-}
-
-// The seam's error flag travels with every step's results (one 4-byte copy behind the step's launches, only once a
-// paired launch has ever run on this engine); a synchronous call reads it after its stream synchronisation.  A set
-// flag means some workgroup stopped waiting and computed phase B from incomplete inputs: the call fails, the flag
-// is cleared so that the engine stays usable.
-int seam_record(mi_engine* e, int64_t ticket) {
-  if (e->d_seam_counter == nullptr) return MI_OK;
-  MI_HIP(hipMemcpyAsync(&e->h_seam_err[ticket % NSLOT], e->d_seam_error, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  return MI_OK;
-}
-int seam_fail(mi_engine* e) {
-  hipMemsetAsync(e->d_seam_error, 0, sizeof(int), e->stream);
-  return fail(MI_ERR_RUNTIME, "a workgroup gave up waiting at an in-launch seam (fused_gemv_pairs): the results of this call are invalid");
-}
-int seam_check_sync(mi_engine* e) {        // the stream is idle
-  if (e->d_seam_counter == nullptr) return MI_OK;
-  MI_HIP(hipMemcpyAsync(&e->h_seam_err[NSLOT], e->d_seam_error, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  MI_HIP(hipStreamSynchronize(e->stream));
-  if (e->h_seam_err[NSLOT] == 0) return MI_OK;
-  e->h_seam_err[NSLOT] = 0;
-  return seam_fail(e);
-}
-
-int gemv_pair(mi_engine* e, const FusedLinear& fa, GemvCall a, const FusedLinear& fb, GemvCall b, size_t rows,
-              const char* prof) {
-  a.M = b.M = (int)rows;
-  MI_TRY(ensure_seam(e));
-  const bool selected = !e->prof_name.empty() && e->prof_name == prof;
-  Prof pr(e, selected ? "" : prof);
-  if (selected) {
-    hipEvent_t x = nullptr, y = nullptr;
-    hipEventCreate(&x); hipEventCreate(&y);
-    a.ev_start = x; a.ev_stop = y;
-    e->prof_events.emplace_back(x, y);
-  }
-  GemvSeam s{e->d_seam_counter, e->seam_base, e->d_seam_error, e->seam_spin_limit};
-  MI_TRY(launch_gemv_pair(fa.W, a, fb.W, b, s, e->stream));
-  e->seam_base += (unsigned)gemv_pair_grid();
-  return MI_OK;
-}
-
 
 // ---- block-paged KV: host-side block management (the device only sees the table) ------------------------------------
 uint64_t prefix_hash(uint64_t parent, const int32_t* toks, int n) {
@@ -808,12 +706,22 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   return std::max(1, std::min(ns, 16));
 }
 
-// the model forward for B*L tokens already in e->d_tokens; logits of the requested rows end
-// up in e->logits (float32, [B][V] or [B*L][V]).
-// `rows` (host, B distinct cache rows) = the call covers that subset of kv's rows, batch entry b <-> rows[b]
-int forward_device(mi_engine* e, mi_kv* kv, int B, int L, bool all_pos, bool want_logits, const int32_t* rows = nullptr) {
+// A group of cache rows that advance by the same number of tokens in one forward pass: entries [r0, r0 + B) of the
+// call's row list, L tokens each, the group's first token at position tok0 of the token buffer.
+struct AttnGroup { int r0, B, L; size_t tok0; };
+
+// Which hidden states feed the head: none; the last position of every row or every position (a call of ONE group);
+// the token positions listed in `gather` (mixed steps).
+enum class Head { NONE, LAST, ALL, GATHER };
+
+// The model forward for the tokens already in e->d_tokens (or at e->tok_src); logits of the head's rows end up in
+// e->logits (float32, [rows][V]).  `rows` (host) = the cache row of every entry of the call, in group order; null =
+// entry b is row b.  All linear layers run ONCE over the concatenated tokens of every group (a chunked prefill next to
+// the live decode rows reads the weights of a layer once for both); every group runs attention of its own.
+// cur_L: tokens per row as gemv_rows sees it (1 = the decode step's kernels).  `what` prefixes the error messages.
+int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<AttnGroup>& groups, int cur_L, Head head,
+            const std::vector<int32_t>& gather = {}, const char* what = "forward") {
   const mi_model_desc& d = e->d;
-  const size_t R = (size_t)B * L;
   const bool quirk = kv->quirk;
   const int act = quirk ? MI_F32 : d.act_dtype;
   const size_t es = dtype_size(act);
@@ -821,20 +729,23 @@ int forward_device(mi_engine* e, mi_kv* kv, int B, int L, bool all_pos, bool wan
   const int H = d.hidden_size, D = d.head_dim, Hq = d.num_heads, Hkv = d.num_kv_heads, I = d.intermediate_size;
   const int nqkv = (Hq + 2 * Hkv) * D;
   hipStream_t st = e->stream;
-  e->cur_L = L;
+  auto row_of = [&](const AttnGroup& g, int b) { return rows ? rows[g.r0 + b] : g.r0 + b; };
+  int n = 0; size_t R = 0;
+  for (const AttnGroup& g : groups) {
+    for (int b = 0; b < g.B; ++b)
+      if (kv->h_off[row_of(g, b)] + g.L > kv->cap || kv->h_off[row_of(g, b)] + g.L > d.max_positions)
+        return fail(MI_ERR_INVALID, std::string(what) + ": KV capacity / max_positions exceeded (call mi_kv_reserve)");
+    n += g.B; R += (size_t)g.B * g.L;
+  }
+  e->cur_L = cur_L;
   e->sq_valid = false;
-
-  auto row_of = [&](int b) { return rows ? rows[b] : b; };
-  for (int b = 0; b < B; ++b)
-    if (kv->h_off[row_of(b)] + L > kv->cap || kv->h_off[row_of(b)] + L > d.max_positions)
-      return fail(MI_ERR_INVALID, "forward: KV capacity / max_positions exceeded (call mi_kv_reserve)");
-  const int32_t* d_rows = nullptr;
   if (rows) {
     if (!kv->d_rows) MI_HIP(hipMalloc(&kv->d_rows, kv->B * sizeof(int32_t)));
-    MI_HIP(hipMemcpyAsync(kv->d_rows, rows, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    d_rows = kv->d_rows;
+    MI_HIP(hipMemcpyAsync(kv->d_rows, rows, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
-  for (int b = 0; b < B; ++b) MI_TRY(kv_ensure_blocks(kv, row_of(b), kv->h_off[row_of(b)] + L));
+  auto d_rows_of = [&](const AttnGroup& g) -> const int32_t* { return rows ? kv->d_rows + g.r0 : nullptr; };
+  for (const AttnGroup& g : groups)
+    for (int b = 0; b < g.B; ++b) MI_TRY(kv_ensure_blocks(kv, row_of(g, b), kv->h_off[row_of(g, b)] + g.L));
   MI_TRY(kv_upload_table(kv, st));
 
   { Prof pr(e, "embed");
@@ -843,220 +754,97 @@ int forward_device(mi_engine* e, mi_kv* kv, int B, int L, bool all_pos, bool wan
 
   const size_t layer_elems = kv_layer_elems(kv, d);
   const size_t kes = dtype_size(kv->dtype);
-  const int nsplit = choose_nsplit(kv, B, Hkv, L, rows);
-  if (nsplit > 1) {
-    const size_t need = R * Hq * nsplit * (D + 2);
-    if (kv->partial == nullptr || kv->partial_splits < nsplit) {
+  std::vector<int> nsplit(groups.size());
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    const AttnGroup& g = groups[gi];
+    nsplit[gi] = choose_nsplit(kv, g.B, Hkv, g.L, rows ? rows + g.r0 : nullptr);
+    if (nsplit[gi] > 1 && (kv->partial == nullptr || kv->partial_splits < nsplit[gi])) {
       MI_HIP(hipStreamSynchronize(st));
       hipFree(kv->partial);
       MI_HIP(hipMalloc(&kv->partial, (size_t)kv->B * Hq * 16 * (D + 2) * sizeof(float)));
       kv->partial_splits = 16;
     }
-    (void)need;
   }
 
-  bool qkv_done = false;     // this layer's q|k|v already ran behind the previous layer's down_proj
   for (int li = 0; li < d.num_layers; ++li) {
     LayerW& lw = e->layers[li];
     const bool w32 = quirk && d.act_dtype != MI_F32;     // norm weights must match the activation storage type
-    const void* in_norm = w32 ? lw.in_norm32 : lw.in_norm;
-    const void* post_norm = w32 ? lw.post_norm32 : lw.post_norm;
     const void* q_norm = w32 ? lw.q_norm32 : lw.q_norm;
     const void* k_norm = w32 ? lw.k_norm32 : lw.k_norm;
     // everything up to the layer-0 attention still rounds to the model dtype in quirk mode
     const int rnd = (quirk && li == 0) ? rndT : RND_NONE;
-    auto qkv_call = [&](int layer) {  // input_layernorm + q|k|v projections (llama.py:187,93)
-      const LayerW& l2 = e->layers[layer];
-      GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = (quirk && layer == 0) ? rndT : RND_NONE; c.pro = PRO_NORM;
-      c.norm_w = w32 ? l2.in_norm32 : l2.in_norm;
-      c.eps = d.rms_norm_eps; c.epi = EPI_STORE; c.out = e->qkv; c.ldo = nqkv;
-      return c;
-    };
-    (void)in_norm;
-    if (!qkv_done) MI_TRY(gemv_rows(e, lw.qkv, qkv_call(li), R, es, es, "gemv_qkv"));
-    qkv_done = false;
-    AttnShape s{B, L, Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, d_rows};
-    kv_shape(kv, s);
-    void* kc = (char*)kv->k + (size_t)li * layer_elems * kes;
-    void* vc = (char*)kv->v + (size_t)li * layer_elems * kes;
-    // o_proj + residual (llama.py:143,188)
-    GemvCall co; co.x = e->attn; co.ldx = Hq * D; co.act = act; co.rnd = RND_NONE; co.epi = EPI_RESID;
-    co.resid = e->h; co.ldo = H;
-    if (L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
-      // decode: norm + RoPE + append + attention + split combine in one launch
-      AttnDecodeCall ac{s, e->qkv, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
-                        e->attn, 1.0f / sqrtf((float)D), RND_NONE, nsplit, kv->partial, kv->counters,
-                        e->opt_attn_mfma ? 0 : 1};
-      if (B <= 32) {
-        ac.n_host_off = B;
-        for (int b = 0; b < B; ++b) { ac.host_row[b] = row_of(b); ac.host_off[b] = kv->h_off[row_of(b)]; }
-      }
-      Prof pr(e, "attn");
-      MI_TRY(launch_attention_decode(ac, st));
-    } else {
-      { Prof pr(e, "rope_append");
-        RopeAppendCall rc{s, e->qkv, e->q, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps,
-                          e->cos_tab, e->sin_tab, d.max_positions};
-        MI_TRY(launch_rope_append(rc, st)); }
-      { Prof pr(e, "attn");
-        AttnShape sa = s; sa.rnd = RND_NONE;  // SDPA output dtype = promote(q, kv): float32 in quirk mode
-        AttnCall ac{sa, e->q, kc, vc, kv->d_off, e->attn, 1.0f / sqrtf((float)D), nsplit, kv->partial,
-                    e->opt_attn_mfma ? 0 : 1};
-        MI_TRY(launch_attention(ac, st)); }
-    }
-    {
-      // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
-      GemvCall cg; cg.x = e->h; cg.ldx = H; cg.act = act; cg.rnd = RND_NONE; cg.pro = PRO_NORM; cg.norm_w = post_norm;
-      cg.eps = d.rms_norm_eps; cg.epi = EPI_SWIGLU; cg.out = e->act; cg.ldo = I; cg.pair_offset = I;
-      if ((e->opt_fused_pairs & 1) && can_pair(e, lw.o, co, lw.gate_up, cg, R)) {
-        MI_TRY(gemv_pair(e, lw.o, co, lw.gate_up, cg, R, "gemv_o_gate_up"));
-      } else {
-        MI_TRY(gemv_rows(e, lw.o, co, R, es, es, "gemv_o"));
-        MI_TRY(gemv_rows(e, lw.gate_up, cg, R, es, es, "gemv_gate_up"));
-      }
-    }
-    {  // down_proj + residual (llama.py:165,190); with the next layer's q|k|v behind it in the same launch
-      GemvCall c; c.x = e->act; c.ldx = I; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
-      if ((e->opt_fused_pairs & 2) && li + 1 < d.num_layers &&
-          can_pair(e, lw.down, c, e->layers[li + 1].qkv, qkv_call(li + 1), R)) {
-        MI_TRY(gemv_pair(e, lw.down, c, e->layers[li + 1].qkv, qkv_call(li + 1), R, "gemv_down_qkv"));
-        qkv_done = true;
-      } else {
-        MI_TRY(gemv_rows(e, lw.down, c, R, es, es, "gemv_down"));
-      }
-    }
-  }
-  if (want_logits) {  // final norm + lm_head / tied embedding (llama.py:231,249-252)
-    const FusedLinear& head = d.tie_word_embeddings ? e->embed : e->lm_head;
-    GemvCall c; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = (quirk && d.act_dtype != MI_F32) ? e->final_norm32 : e->final_norm; c.eps = d.rms_norm_eps;
-    c.epi = EPI_STORE_F32; c.out = e->logits; c.ldo = d.vocab_size;
-    if (all_pos) { c.x = e->h; c.ldx = H; MI_TRY(gemv_rows(e, head, c, R, es, sizeof(float), "gemv_head")); }
-    else { c.x = (char*)e->h + (size_t)(L - 1) * H * es; c.ldx = L * H; MI_TRY(gemv_rows(e, head, c, B, es, sizeof(float), "gemv_head")); }
-  }
-  MI_TRY(launch_advance_offsets(kv->d_off, d_rows, B, L, st));
-  for (int b = 0; b < B; ++b) kv->h_off[row_of(b)] += L;
-  return MI_OK;
-}
-
-
-// ---- one pass over the weights for rows that advance by DIFFERENT numbers of tokens (chunked prefill co-scheduled with
-// the live decode rows): segment i = lens[i] tokens of cache row rows[i].  The decode rows (lens == 1) come first in
-// the token buffer and share one decode-attention launch; every longer segment is one prefill-attention call on its
-// own row.  All linear layers run ONCE over the concatenated tokens (tile GEMM from 32 tokens up), which is the point:
-// the weights of a layer are read once for the 7 live sequences AND the 256-token chunk of an arriving prompt.
-// Logits are produced for the last token of the segments with want[i] != 0, in segment order.
-int forward_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const int32_t* lens, const int32_t* want, int n, int n_out) {
-  const mi_model_desc& d = e->d;
-  const bool quirk = kv->quirk;
-  const int act = quirk ? MI_F32 : d.act_dtype;
-  const size_t es = dtype_size(act);
-  const int rndT = quirk ? (d.act_dtype == MI_BF16 ? RND_BF16 : RND_F16) : RND_NONE;
-  const int H = d.hidden_size, D = d.head_dim, Hq = d.num_heads, Hkv = d.num_kv_heads, I = d.intermediate_size;
-  const int nqkv = (Hq + 2 * Hkv) * D;
-  hipStream_t st = e->stream;
-  int nd = 0;                                    // decode rows: the leading segments of length 1
-  while (nd < n && lens[nd] == 1) ++nd;
-  size_t R = 0;
-  std::vector<size_t> tok0(n);
-  for (int i = 0; i < n; ++i) {
-    if (i >= nd && lens[i] == 1) return fail(MI_ERR_INVALID, "mixed step: one-token segments must come first");
-    if (kv->h_off[rows[i]] + lens[i] > kv->cap || kv->h_off[rows[i]] + lens[i] > d.max_positions)
-      return fail(MI_ERR_INVALID, "mixed step: KV capacity / max_positions exceeded (call mi_kv_reserve)");
-    tok0[i] = R; R += (size_t)lens[i];
-  }
-  // Only decode rows: the decode step's kernels.  Otherwise the call is routed like a prefill of R rows (gemv_rows: the
-  // weight-streaming kernel for short calls, the K-split 128 x 128 tile for a few hundred rows, plain tiles above).
-  e->cur_L = R == (size_t)nd ? 1 : 2;
-  e->sq_valid = false;
-  if (!kv->d_rows) MI_HIP(hipMalloc(&kv->d_rows, kv->B * sizeof(int32_t)));
-  MI_HIP(hipMemcpyAsync(kv->d_rows, rows, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  for (int i = 0; i < n; ++i) MI_TRY(kv_ensure_blocks(kv, rows[i], kv->h_off[rows[i]] + lens[i]));
-  MI_TRY(kv_upload_table(kv, st));
-
-  { Prof pr(e, "embed");
-    EmbedCall ec{e->tok_src ? e->tok_src : e->d_tokens, (int)R, act, rndT, e->h};
-    MI_TRY(launch_embed(e->embed.W, ec, st)); }
-
-  const size_t layer_elems = kv_layer_elems(kv, d);
-  const size_t kes = dtype_size(kv->dtype);
-  const int nsplit = nd > 0 ? choose_nsplit(kv, nd, Hkv, 1, rows) : 1;
-  if (nsplit > 1 && (kv->partial == nullptr || kv->partial_splits < nsplit)) {
-    MI_HIP(hipStreamSynchronize(st));
-    hipFree(kv->partial);
-    MI_HIP(hipMalloc(&kv->partial, (size_t)kv->B * Hq * 16 * (D + 2) * sizeof(float)));
-    kv->partial_splits = 16;
-  }
-  for (int li = 0; li < d.num_layers; ++li) {
-    LayerW& lw = e->layers[li];
-    const bool w32 = quirk && d.act_dtype != MI_F32;
-    const void* post_norm = w32 ? lw.post_norm32 : lw.post_norm;
-    const void* q_norm = w32 ? lw.q_norm32 : lw.q_norm;
-    const void* k_norm = w32 ? lw.k_norm32 : lw.k_norm;
-    const int rnd = (quirk && li == 0) ? rndT : RND_NONE;
-    { GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = rnd; c.pro = PRO_NORM;
+    { // input_layernorm + q|k|v projections (llama.py:187,93)
+      GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = rnd; c.pro = PRO_NORM;
       c.norm_w = w32 ? lw.in_norm32 : lw.in_norm; c.eps = d.rms_norm_eps; c.epi = EPI_STORE; c.out = e->qkv; c.ldo = nqkv;
       MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv")); }
     void* kc = (char*)kv->k + (size_t)li * layer_elems * kes;
     void* vc = (char*)kv->v + (size_t)li * layer_elems * kes;
-    if (nd > 0) {                                // the decode rows: tokens [0, nd)
-      AttnShape s{nd, 1, Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, kv->d_rows};
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const AttnGroup& g = groups[gi];
+      AttnShape s{g.B, g.L, Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, d_rows_of(g)};
       kv_shape(kv, s);
-      if (e->opt_fused_attn && attention_decode_supported(s)) {
-        AttnDecodeCall ac{s, e->qkv, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
-                          e->attn, 1.0f / sqrtf((float)D), RND_NONE, nsplit, kv->partial, kv->counters,
+      const void* qkv_g = (const char*)e->qkv + g.tok0 * (size_t)nqkv * es;
+      void* q_g = (char*)e->q + g.tok0 * (size_t)Hq * D * es;
+      void* o_g = (char*)e->attn + g.tok0 * (size_t)Hq * D * es;
+      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
+        // decode: norm + RoPE + append + attention + split combine in one launch
+        AttnDecodeCall ac{s, qkv_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
+                          o_g, 1.0f / sqrtf((float)D), RND_NONE, nsplit[gi], kv->partial, kv->counters,
                           e->opt_attn_mfma ? 0 : 1};
-        if (nd <= 32) {
-          ac.n_host_off = nd;
-          for (int b = 0; b < nd; ++b) { ac.host_row[b] = rows[b]; ac.host_off[b] = kv->h_off[rows[b]]; }
+        if (g.B <= 32) {
+          ac.n_host_off = g.B;
+          for (int b = 0; b < g.B; ++b) { ac.host_row[b] = row_of(g, b); ac.host_off[b] = kv->h_off[row_of(g, b)]; }
         }
         Prof pr(e, "attn");
         MI_TRY(launch_attention_decode(ac, st));
       } else {
-        RopeAppendCall rc{s, e->qkv, e->q, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab, d.max_positions};
-        MI_TRY(launch_rope_append(rc, st));
-        AttnShape sa = s; sa.rnd = RND_NONE;
-        AttnCall ac{sa, e->q, kc, vc, kv->d_off, e->attn, 1.0f / sqrtf((float)D), nsplit, kv->partial, e->opt_attn_mfma ? 0 : 1};
-        MI_TRY(launch_attention(ac, st));
+        { Prof pr(e, "rope_append");
+          RopeAppendCall rc{s, qkv_g, q_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps,
+                            e->cos_tab, e->sin_tab, d.max_positions};
+          MI_TRY(launch_rope_append(rc, st)); }
+        { Prof pr(e, "attn");
+          AttnShape sa = s; sa.rnd = RND_NONE;  // SDPA output dtype = promote(q, kv): float32 in quirk mode
+          AttnCall ac{sa, q_g, kc, vc, kv->d_off, o_g, 1.0f / sqrtf((float)D), nsplit[gi], kv->partial,
+                      e->opt_attn_mfma ? 0 : 1};
+          MI_TRY(launch_attention(ac, st)); }
       }
     }
-    for (int i = nd; i < n; ++i) {               // every chunk: rope + append + causal attention on its own row
-      AttnShape s{1, lens[i], Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, kv->d_rows + i};
-      kv_shape(kv, s);
-      const void* qkv_i = (const char*)e->qkv + tok0[i] * (size_t)nqkv * es;
-      void* q_i = (char*)e->q + tok0[i] * (size_t)Hq * D * es;
-      void* o_i = (char*)e->attn + tok0[i] * (size_t)Hq * D * es;
-      RopeAppendCall rc{s, qkv_i, q_i, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab, d.max_positions};
-      MI_TRY(launch_rope_append(rc, st));
-      AttnShape sa = s; sa.rnd = RND_NONE;
-      AttnCall ac{sa, q_i, kc, vc, kv->d_off, o_i, 1.0f / sqrtf((float)D), 1, nullptr, e->opt_attn_mfma ? 0 : 1};
-      MI_TRY(launch_attention(ac, st));
-    }
-    { GemvCall co; co.x = e->attn; co.ldx = Hq * D; co.act = act; co.rnd = RND_NONE; co.epi = EPI_RESID; co.resid = e->h; co.ldo = H;
-      MI_TRY(gemv_rows(e, lw.o, co, R, es, es, "gemv_o"));
-      GemvCall cg; cg.x = e->h; cg.ldx = H; cg.act = act; cg.rnd = RND_NONE; cg.pro = PRO_NORM; cg.norm_w = post_norm;
-      cg.eps = d.rms_norm_eps; cg.epi = EPI_SWIGLU; cg.out = e->act; cg.ldo = I; cg.pair_offset = I;
-      MI_TRY(gemv_rows(e, lw.gate_up, cg, R, es, es, "gemv_gate_up"));
+    { // o_proj + residual (llama.py:143,188)
+      GemvCall c; c.x = e->attn; c.ldx = Hq * D; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
+      MI_TRY(gemv_rows(e, lw.o, c, R, es, es, "gemv_o")); }
+    { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
+      GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
+      c.eps = d.rms_norm_eps; c.epi = EPI_SWIGLU; c.out = e->act; c.ldo = I; c.pair_offset = I;
+      MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up")); }
+    { // down_proj + residual (llama.py:165,190)
       GemvCall c; c.x = e->act; c.ldx = I; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
       MI_TRY(gemv_rows(e, lw.down, c, R, es, es, "gemv_down")); }
   }
-  if (n_out > 0) {                               // hidden states of the wanted positions -> compact rows -> head
-    std::vector<int32_t> idx;
-    for (int i = 0; i < n; ++i) if (want[i]) idx.push_back((int32_t)(tok0[i] + lens[i] - 1));
-    if (!e->d_gather) MI_HIP(hipMalloc(&e->d_gather, 4096 * sizeof(int32_t)));
-    if (idx.size() > 4096) return fail(MI_ERR_INVALID, "mixed step: too many sampled rows");
-    MI_HIP(hipMemcpyAsync(e->d_gather, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    MI_TRY(launch_gather_rows(e->h, (size_t)H * es, e->d_gather, (int)idx.size(), e->xn, st));
-    const FusedLinear& head = d.tie_word_embeddings ? e->embed : e->lm_head;
-    GemvCall c; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = (quirk && d.act_dtype != MI_F32) ? e->final_norm32 : e->final_norm;
-    c.eps = d.rms_norm_eps; c.epi = EPI_STORE_F32; c.out = e->logits; c.ldo = d.vocab_size; c.x = e->xn; c.ldx = H;
-    const int keep_L = e->cur_L; e->cur_L = 1;   // the few sampled rows go through the decode step's head kernel
-    const int rc_head = gemv_rows(e, head, c, idx.size(), es, sizeof(float), "gemv_head");
-    e->cur_L = keep_L;
-    MI_TRY(rc_head);
+  if (head != Head::NONE) {  // final norm + lm_head / tied embedding (llama.py:231,249-252)
+    const FusedLinear& hw = d.tie_word_embeddings ? e->embed : e->lm_head;
+    GemvCall c; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = (quirk && d.act_dtype != MI_F32) ? e->final_norm32 : e->final_norm; c.eps = d.rms_norm_eps;
+    c.epi = EPI_STORE_F32; c.out = e->logits; c.ldo = d.vocab_size; c.x = e->h; c.ldx = H;
+    if (head == Head::ALL) {
+      MI_TRY(gemv_rows(e, hw, c, R, es, sizeof(float), "gemv_head"));
+    } else if (head == Head::LAST) {      // the last position of every row, read in place
+      const int L = groups[0].L;
+      c.x = (char*)e->h + (size_t)(L - 1) * H * es; c.ldx = L * H;
+      MI_TRY(gemv_rows(e, hw, c, groups[0].B, es, sizeof(float), "gemv_head"));
+    } else {                              // the wanted positions -> compact rows -> head
+      if (!e->d_gather) MI_HIP(hipMalloc(&e->d_gather, 4096 * sizeof(int32_t)));
+      if (gather.size() > 4096) return fail(MI_ERR_INVALID, std::string(what) + ": too many sampled rows");
+      MI_HIP(hipMemcpyAsync(e->d_gather, gather.data(), gather.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      MI_TRY(launch_gather_rows(e->h, (size_t)H * es, e->d_gather, (int)gather.size(), e->xn, st));
+      c.x = e->xn;
+      e->cur_L = 1;                       // the few sampled rows go through the decode step's head kernel
+      const int rc_head = gemv_rows(e, hw, c, gather.size(), es, sizeof(float), "gemv_head");
+      e->cur_L = cur_L;
+      MI_TRY(rc_head);
+    }
   }
-  if (nd > 0) MI_TRY(launch_advance_offsets(kv->d_off, kv->d_rows, nd, 1, st));
-  for (int i = nd; i < n; ++i) MI_TRY(launch_advance_offsets(kv->d_off, kv->d_rows + i, 1, lens[i], st));
-  for (int i = 0; i < n; ++i) kv->h_off[rows[i]] += lens[i];
+  for (const AttnGroup& g : groups) MI_TRY(launch_advance_offsets(kv->d_off, d_rows_of(g), g.B, g.L, st));
+  for (const AttnGroup& g : groups)
+    for (int b = 0; b < g.B; ++b) kv->h_off[row_of(g, b)] += g.L;
   return MI_OK;
 }
 
@@ -1125,6 +913,40 @@ int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* f
   return launch_sample(sc, st);
 }
 
+// The step's results -> a pinned slot (tokens | logprobs | row-0 probabilities: one copy, d_next and the slot's block
+// share the layout), then the event mi_step_wait waits for.
+int finish_step(mi_engine* e, int B, const mi_sample_params* sp, int64_t* ticket) {
+  hipStream_t st = e->stream;
+  const int64_t t = e->next_ticket++;
+  Slot& s = e->slots[t % NSLOT];
+  s.B = B; s.topk = sp ? sp->top_logprobs : 0; s.ticket = t;
+  if (B > 0) {
+    MI_HIP(hipMemcpyAsync(s.tokens, e->d_next, ((size_t)2 * e->maxB + B) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (s.topk > 0) {
+      MI_HIP(hipMemcpyAsync(s.topk_ids, e->d_topk_ids, (size_t)B * s.topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      MI_HIP(hipMemcpyAsync(s.topk_lp, e->d_topk_lp, (size_t)B * s.topk * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+  }
+  MI_HIP(hipEventRecord(s.ev, st));
+  *ticket = t;
+  return MI_OK;
+}
+
+// mi_step_enqueue / mi_step_enqueue_rows once their arguments are checked: n rows x L tokens (rows null = rows 0..n-1),
+// tokens_in null = the device-resident feed (the previous step's samples)
+int step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, const int32_t* tokens_in, int L,
+                 const mi_sample_params* sp, int64_t* ticket) {
+  MI_TRY(ensure_workspace(e, (size_t)n * L, (size_t)n, std::max(n, kv->B)));
+  if (tokens_in) MI_TRY(upload_tokens(e, tokens_in, n, L));
+  e->tok_src = tokens_in ? nullptr : e->d_next;            // (no copy: the sampler overwrites d_next only at the end of this step)
+  const int frc = forward(e, kv, rows, {{0, n, L, 0}}, L, Head::LAST);
+  e->tok_src = nullptr;
+  MI_TRY(frc);
+  MI_TRY(run_sample(e, n, sp));
+  e->last_n = n;
+  return finish_step(e, n, sp, ticket);
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -1184,7 +1006,7 @@ void mi_engine_destroy(mi_engine* e) {
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
   hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->d_forced); hipFree(e->d_gather);
-  hipFree(e->d_seam_counter); hipFree(e->d_seam_error); hipHostFree(e->h_seam_err); hipFree(e->d_rowpar); hipFree(e->deq_scratch);
+  hipFree(e->d_rowpar); hipFree(e->deq_scratch);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
   hipFree(e->d_uniforms); hipFree(e->d_topk_ids); hipFree(e->d_topk_lp); hipFree(e->d_bias_ids); hipFree(e->d_bias_vals);
@@ -1537,12 +1359,12 @@ int mi_forward(mi_engine* e, mi_kv* kv, const int32_t* tokens, int B, int L, flo
   const size_t R = (size_t)B * L;
   MI_TRY(ensure_workspace(e, R, all_pos ? R : (size_t)B, B));
   MI_TRY(upload_tokens(e, tokens, B, L));
-  MI_TRY(forward_device(e, kv, B, L, all_pos != 0, logits_out != nullptr));
+  MI_TRY(forward(e, kv, nullptr, {{0, B, L, 0}}, L, !logits_out ? Head::NONE : all_pos ? Head::ALL : Head::LAST));
   if (logits_out)
     MI_HIP(hipMemcpyAsync(logits_out, e->logits, (all_pos ? R : (size_t)B) * e->d.vocab_size * sizeof(float),
                           hipMemcpyDeviceToHost, e->stream));
   MI_HIP(hipStreamSynchronize(e->stream));
-  return seam_check_sync(e);
+  return MI_OK;
 }
 
 int mi_score_tokens(mi_engine* e, mi_kv* kv, const int32_t* tokens, const int32_t* targets, int B, int L,
@@ -1564,7 +1386,7 @@ int mi_score_tokens(mi_engine* e, mi_kv* kv, const int32_t* tokens, const int32_
   }
   MI_TRY(upload_tokens(e, tokens, B, L));
   MI_HIP(hipMemcpyAsync(e->d_forced, targets, R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  MI_TRY(forward_device(e, kv, B, L, true, true));
+  MI_TRY(forward(e, kv, nullptr, {{0, B, L, 0}}, L, Head::ALL));
   MI_TRY(run_sample(e, (int)R, sp, e->d_forced));
   MI_HIP(hipMemcpyAsync(logprob_out, e->d_logprob, R * sizeof(float), hipMemcpyDeviceToHost, st));
   if (k > 0) {
@@ -1572,7 +1394,7 @@ int mi_score_tokens(mi_engine* e, mi_kv* kv, const int32_t* tokens, const int32_
     MI_HIP(hipMemcpyAsync(topk_logprobs, e->d_topk_lp, R * k * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   MI_HIP(hipStreamSynchronize(st));
-  return seam_check_sync(e);
+  return MI_OK;
 }
 
 int mi_step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* tokens_in, int B, int L, const mi_sample_params* sp,
@@ -1582,27 +1404,7 @@ int mi_step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* tokens_in, int B, in
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (!tokens_in && L != 1) return fail(MI_ERR_INVALID, "device-resident token feed needs L == 1");
   if (!tokens_in && e->maxB < B) return fail(MI_ERR_INVALID, "no previous step to take tokens from");
-  MI_TRY(ensure_workspace(e, (size_t)B * L, (size_t)B, B));
-  hipStream_t st = e->stream;
-  if (tokens_in) MI_TRY(upload_tokens(e, tokens_in, B, L));
-  e->tok_src = tokens_in ? nullptr : e->d_next;            // (no copy: the sampler overwrites d_next only at the end of this step)
-  const int frc = forward_device(e, kv, B, L, false, true);
-  e->tok_src = nullptr;
-  MI_TRY(frc);
-  MI_TRY(run_sample(e, B, sp));
-  e->last_n = B;
-  const int64_t t = e->next_ticket++;
-  Slot& s = e->slots[t % NSLOT];
-  s.B = B; s.topk = sp ? sp->top_logprobs : 0; s.ticket = t;
-  MI_HIP(hipMemcpyAsync(s.tokens, e->d_next, ((size_t)2 * e->maxB + B) * sizeof(int32_t), hipMemcpyDeviceToHost, st));   // tokens | logprobs | row-0 probabilities
-  if (s.topk > 0) {
-    MI_HIP(hipMemcpyAsync(s.topk_ids, e->d_topk_ids, (size_t)B * s.topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MI_HIP(hipMemcpyAsync(s.topk_lp, e->d_topk_lp, (size_t)B * s.topk * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
-  MI_TRY(seam_record(e, t));
-  MI_HIP(hipEventRecord(s.ev, st));
-  *ticket = t;
-  return MI_OK;
+  return step_enqueue(e, kv, nullptr, B, tokens_in, L, sp, ticket);
 }
 
 int mi_step_enqueue_rows(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, const int32_t* tokens_in, int L,
@@ -1618,29 +1420,13 @@ int mi_step_enqueue_rows(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, co
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (!tokens_in && L != 1) return fail(MI_ERR_INVALID, "device-resident token feed needs L == 1");
   if (!tokens_in && e->last_n != n) return fail(MI_ERR_INVALID, "device-resident token feed needs the row set of the previous step");
-  MI_TRY(ensure_workspace(e, (size_t)n * L, (size_t)n, std::max(n, kv->B)));
-  hipStream_t st = e->stream;
-  if (tokens_in) MI_TRY(upload_tokens(e, tokens_in, n, L));
-  e->tok_src = tokens_in ? nullptr : e->d_next;
-  const int frc = forward_device(e, kv, n, L, false, true, rows);
-  e->tok_src = nullptr;
-  MI_TRY(frc);
-  MI_TRY(run_sample(e, n, sp));
-  e->last_n = n;
-  const int64_t t = e->next_ticket++;
-  Slot& s = e->slots[t % NSLOT];
-  s.B = n; s.topk = sp ? sp->top_logprobs : 0; s.ticket = t;
-  MI_HIP(hipMemcpyAsync(s.tokens, e->d_next, ((size_t)2 * e->maxB + n) * sizeof(int32_t), hipMemcpyDeviceToHost, st));   // tokens | logprobs | row-0 probabilities
-  if (s.topk > 0) {
-    MI_HIP(hipMemcpyAsync(s.topk_ids, e->d_topk_ids, (size_t)n * s.topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MI_HIP(hipMemcpyAsync(s.topk_lp, e->d_topk_lp, (size_t)n * s.topk * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
-  MI_TRY(seam_record(e, t));
-  MI_HIP(hipEventRecord(s.ev, st));
-  *ticket = t;
-  return MI_OK;
+  return step_enqueue(e, kv, rows, n, tokens_in, L, sp, ticket);
 }
 
+// One pass over the weights for rows that advance by DIFFERENT numbers of tokens (chunked prefill co-scheduled with the
+// live decode rows): segment i = lens[i] tokens of cache row rows[i].  The decode rows (lens == 1) come first in the
+// token buffer and form one attention group; every longer segment is a group of its own.  Logits are produced for the
+// last token of the segments with want[i] != 0, in segment order.
 int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const int32_t* lens, const int32_t* want, int n,
                           const int32_t* tokens, const mi_sample_params* sp, int64_t* ticket) {
   if (!e || !kv || !rows || !lens || !want || !tokens) return fail(MI_ERR_INVALID, "null argument");
@@ -1657,29 +1443,29 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (sp && (sp->row_temperature != nullptr) != (sp->row_top_p != nullptr)) return fail(MI_ERR_INVALID, "row_temperature and row_top_p come together");
   MI_TRY(ensure_workspace(e, R, (size_t)std::max(n_out, 1), std::max(n, kv->B)));
-  hipStream_t st = e->stream;
   for (size_t i = 0; i < R; ++i)
     if (tokens[i] < 0 || tokens[i] >= e->d.vocab_size) return fail(MI_ERR_INVALID, "token id out of range");
-  MI_HIP(hipMemcpyAsync(e->d_tokens, tokens, R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  MI_TRY(forward_mixed(e, kv, rows, lens, want, n, n_out));
-  const int64_t t = e->next_ticket++;
-  Slot& s = e->slots[t % NSLOT];
-  s.B = n_out; s.topk = sp ? sp->top_logprobs : 0; s.ticket = t;
-  if (n_out > 0) {
-    MI_TRY(run_sample(e, n_out, sp));
-    MI_HIP(hipMemcpyAsync(s.tokens, e->d_next, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MI_HIP(hipMemcpyAsync(s.logprob, e->d_logprob, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
-    MI_HIP(hipMemcpyAsync(s.prob0, e->d_prob0, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (s.topk > 0) {
-      MI_HIP(hipMemcpyAsync(s.topk_ids, e->d_topk_ids, (size_t)n_out * s.topk * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      MI_HIP(hipMemcpyAsync(s.topk_lp, e->d_topk_lp, (size_t)n_out * s.topk * sizeof(float), hipMemcpyDeviceToHost, st));
+  MI_HIP(hipMemcpyAsync(e->d_tokens, tokens, R * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  int nd = 0;                                    // decode rows: the leading segments of length 1
+  while (nd < n && lens[nd] == 1) ++nd;
+  std::vector<AttnGroup> groups;
+  std::vector<int32_t> gather;                   // token positions whose hidden state feeds the head
+  if (nd > 0) groups.push_back({0, nd, 1, 0});
+  size_t tok0 = 0;
+  for (int i = 0; i < n; ++i) {
+    if (i >= nd) {
+      if (lens[i] == 1) return fail(MI_ERR_INVALID, "mixed step: one-token segments must come first");
+      groups.push_back({i, 1, lens[i], tok0});
     }
+    if (want[i]) gather.push_back((int32_t)(tok0 + lens[i] - 1));
+    tok0 += (size_t)lens[i];
   }
+  // Only decode rows: the decode step's kernels.  Otherwise the call is routed like a prefill of R rows (gemv_rows: the
+  // weight-streaming kernel for short calls, the K-split 128 x 128 tile for a few hundred rows, plain tiles above).
+  MI_TRY(forward(e, kv, rows, groups, R == (size_t)nd ? 1 : 2, n_out > 0 ? Head::GATHER : Head::NONE, gather, "mixed step"));
+  if (n_out > 0) MI_TRY(run_sample(e, n_out, sp));
   e->last_n = -1;                                // the device-resident token feed does not survive a mixed step
-  MI_TRY(seam_record(e, t));
-  MI_HIP(hipEventRecord(s.ev, st));
-  *ticket = t;
-  return MI_OK;
+  return finish_step(e, n_out, sp, ticket);
 }
 
 int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logprob_out, float* prob_row0_out,
@@ -1690,10 +1476,6 @@ int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logpr
   if (s.ticket != ticket) return fail(MI_ERR_INVALID, "ticket expired (more than 4 steps in flight)");
   MI_HIP(hipSetDevice(e->device));
   MI_HIP(hipEventSynchronize(s.ev));
-  if (e->h_seam_err != nullptr && e->h_seam_err[ticket % NSLOT] != 0) {
-    e->h_seam_err[ticket % NSLOT] = 0;
-    return seam_fail(e);
-  }
   if (tokens_out) memcpy(tokens_out, s.tokens, s.B * sizeof(int32_t));
   if (logprob_out) memcpy(logprob_out, s.logprob, s.B * sizeof(float));
   if (prob_row0_out) memcpy(prob_row0_out, s.prob0, s.B * sizeof(float));
@@ -1748,13 +1530,8 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value) {
   if (k == "prefill_x_terms") { if (value != 2 && value != 3) return fail(MI_ERR_INVALID, "prefill_x_terms: 2 or 3"); e->opt_prefill_x_terms = (int)value; return MI_OK; }
   if (k == "short_prefill_skinny") { e->opt_short_prefill_skinny = value != 0; return MI_OK; }
   if (k == "decode_attention_mfma") { e->opt_attn_mfma = value != 0; return MI_OK; }
-  if (k == "fused_gemv_pairs") { e->opt_fused_pairs = (int)value; return MI_OK; }
   if (k == "f16_hilo") { e->opt_f16_hilo = value != 0; return MI_OK; }
   if (k == "gate_up_interleave") { e->opt_gu8 = value != 0; return MI_OK; }
-  if (k == "seam_spin_limit") {
-    if (value < 0 || value > (int64_t)0x7fffffff) return fail(MI_ERR_INVALID, "seam_spin_limit out of range");
-    e->seam_spin_limit = (unsigned)value; return MI_OK;
-  }
   if (k == "tile_weights") {
     if (e->finalized) return fail(MI_ERR_INVALID, "tile_weights must be set before mi_engine_finalize");
     e->opt_tile_weights = value != 0; return MI_OK;
@@ -1766,7 +1543,7 @@ int mi_engine_sync(mi_engine* e) {
   if (!e) return fail(MI_ERR_INVALID, "null engine");
   MI_HIP(hipSetDevice(e->device));
   MI_HIP(hipStreamSynchronize(e->stream));
-  return seam_check_sync(e);
+  return MI_OK;
 }
 
 }  // extern "C"

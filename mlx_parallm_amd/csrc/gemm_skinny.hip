@@ -586,10 +586,10 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
   }
 
   // ================= split K: publish the partial tile; the last workgroup of the group adds them up.
-  // Hand-off as in gemv_phase.h seam_arrive: partials are stored write-through (agent-scope atomics -> sc1, they do not
-  // stay dirty in this XCD's L2), every wave drains its stores, the workgroup is counted, and the reader uses
-  // agent-scope loads.  No release / acquire FENCES: on this part they write back / invalidate the whole L2 of the
-  // XCD per wave, which made the launch several times slower than the streaming itself.
+  // Hand-off: partials are stored write-through (agent-scope atomics -> sc1, they do not stay dirty in this XCD's L2),
+  // every wave drains its stores, the workgroup is counted, and the reader uses agent-scope loads (load16_agent).
+  // No release / acquire FENCES: on this part they write back / invalidate the whole L2 of the XCD per wave, which
+  // made the launch several times slower than the streaming itself.
   if (p.ksplit > 1) {
     if (valid) {
       unsigned long long* wp = (unsigned long long*)(p.ws + (((size_t)((slab * p.ksplit + s) * p.ntiles + tile) * (NA * MT)) * 64 + lane) * 4);

@@ -19,12 +19,8 @@
 // one step of the workgroup reads contiguous KiB blocks; partial tiles are summed through LDS.
 // Activations are staged (RMSNorm applied) as 16-bit MFMA A-fragments.
 //
-// One GEMV is a `Phase`.  gemv_mfma_kernel runs one phase; gemv_pair_kernel runs two dependent
-// phases (o_proj -> gate|up, down_proj -> next layer's q|k|v) in ONE launch: after its last tile of
-// phase A a workgroup publishes its outputs write-through (sc1), arrives on a device counter, issues
-// the first weight loads of phase B -- they do not depend on phase A -- and only then polls the
-// counter; phase B's activations are read with agent-scope (sc1) loads.  The seam costs a counter
-// round trip that overlaps the weight prefetch, instead of a kernel boundary + a cold prologue.
+// One GEMV is a `Phase` (gemv_phase.h), and one launch runs one phase.  Two dependent GEMVs in one launch,
+// joined by a device-wide arrival counter, were measured no faster than two launches and removed.
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -48,7 +44,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(MfmaParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Phase<AT, Q4, MB, SWIGLU, NW, J, DB> ph(p, smem_raw);
   if (ph.ntiles <= 0) return;
-  ph.template run<false, false, false>();
+  ph.run();
 }
 
 // The same body under its own symbol for the launches on a row-interleaved gate|up copy (EPI_SWIGLU_GU8): the dominant
@@ -58,24 +54,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_gu8_kernel(MfmaParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Phase<AT, false, MB, false, NW, J, DB> ph(p, smem_raw);
   if (ph.ntiles <= 0) return;
-  ph.template run<false, false, false>();
-}
-
-// Two dependent GEMVs in one launch: A (plain epilogue) then B (SwiGLU or plain), see the file header.
-// grid = number of CUs, every workgroup resident at once (one 8-wave workgroup per CU).
-template <typename AT, bool Q4, int MB, bool SWB, int NW, int JA, int JB>
-__global__ __launch_bounds__(NW * 64) void gemv_pair_kernel(MfmaParams pa, MfmaParams pb, SeamParams seam) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  {
-    Phase<AT, Q4, MB, false, NW, JA> A(pa, smem_raw);
-    A.template run<false, false, true>();
-  }
-  // ---- seam: publish, arrive, prefetch B's first weights, wait
-  seam_arrive(seam);
-  Phase<AT, Q4, MB, SWB, NW, JB> B(pb, smem_raw);
-  B.prefetch_weights();
-  seam_wait(seam);
-  B.template run<true, true, false>();
+  ph.run();
 }
 
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
@@ -145,36 +124,6 @@ int launch_at(bool q4, const MfmaParams& p, hipStream_t st) {
   return sw ? launch_one<AT, true, 16, true, 8>(p, st) : launch_one<AT, true, 16, false, 8>(p, st);
 }
 
-template <typename AT, bool Q4, int MB, bool SWB, int JA, int JB>
-int launch_pair_j(const MfmaParams& pa, const MfmaParams& pb, const SeamParams& seam, hipStream_t st) {
-  constexpr int NW = 8;
-  auto kern = gemv_pair_kernel<AT, Q4, MB, SWB, NW, JA, JB>;
-  const size_t lds = std::max(phase_lds_bytes<NW, 1, Q4>(pa.kc, MB, 1), phase_lds_bytes<NW, SWB ? 2 : 1, Q4>(pb.kc, MB, 1));
-  MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (g_ev_start != nullptr)
-    hipExtLaunchKernelGGL(kern, dim3(cu_count()), dim3(NW * 64), lds, st, g_ev_start, g_ev_stop, 0, pa, pb, seam);
-  else
-    hipLaunchKernelGGL(kern, dim3(cu_count()), dim3(NW * 64), lds, st, pa, pb, seam);
-  MI_HIP(hipGetLastError());
-  return MI_OK;
-}
-
-template <typename AT, bool Q4, int MB, bool SWB>
-int launch_pair_mb(const MfmaParams& pa, const MfmaParams& pb, const SeamParams& seam, hipStream_t st) {
-  const bool ja2 = pa.kc > 4096, jb2 = pb.kc > 4096;
-  if (!ja2 && !jb2) return launch_pair_j<AT, Q4, MB, SWB, 1, 1>(pa, pb, seam, st);
-  if (ja2 && jb2) return launch_pair_j<AT, Q4, MB, SWB, 2, 2>(pa, pb, seam, st);
-  if (ja2) return launch_pair_j<AT, Q4, MB, SWB, 2, 1>(pa, pb, seam, st);
-  return launch_pair_j<AT, Q4, MB, SWB, 1, 2>(pa, pb, seam, st);
-}
-
-template <typename AT>
-int launch_pair_at(bool q4, const MfmaParams& pa, const MfmaParams& pb, const SeamParams& seam, hipStream_t st) {
-  const bool sw = pb.epi == EPI_SWIGLU;
-  if (!q4) return sw ? launch_pair_mb<AT, false, 8, true>(pa, pb, seam, st) : launch_pair_mb<AT, false, 8, false>(pa, pb, seam, st);
-  return sw ? launch_pair_mb<AT, true, 8, true>(pa, pb, seam, st) : launch_pair_mb<AT, true, 8, false>(pa, pb, seam, st);
-}
-
 MfmaParams make_params(const LinearW& W, const GemvCall& c) {
   MfmaParams p{};
   p.x = c.x; p.ldx = c.ldx; p.M = c.M; p.pro = c.pro; p.norm_w = c.norm_w; p.eps = c.eps;
@@ -223,29 +172,5 @@ int launch_gemv_mfma(const LinearW& W, const GemvCall& c, hipStream_t st) {
   g_ev_start = g_ev_stop = nullptr;
   return rc;
 }
-
-// Two dependent GEMVs (B reads what A wrote) as one launch; see gemv_pair_kernel.
-bool gemv_pair_supported(const LinearW& WA, const GemvCall& a, const LinearW& WB, const GemvCall& b) {
-  if (!gemv_mfma_supported(WA, a) || !gemv_mfma_supported(WB, b)) return false;
-  if (a.M > 8 || b.M != a.M || a.act != b.act) return false;
-  if (wk_is_quant(WA.wk) != wk_is_quant(WB.wk)) return false;
-  if (a.epi != EPI_STORE && a.epi != EPI_RESID) return false;          // A's outputs are 16-bit activations
-  if (b.epi == EPI_STORE_F32) return false;
-  if (a.lora_t != nullptr || b.lora_t != nullptr) return false;        // the LoRA down-projection is a launch of its own
-  return true;
-}
-
-int launch_gemv_pair(const LinearW& WA, const GemvCall& a, const LinearW& WB, const GemvCall& b, const GemvSeam& s,
-                     hipStream_t st) {
-  const bool q4 = wk_is_quant(WA.wk);
-  const MfmaParams pa = make_params(WA, a), pb = make_params(WB, b);
-  SeamParams seam{s.counter, s.base + (unsigned)cu_count(), s.spin_limit, s.error};
-  g_ev_start = (hipEvent_t)a.ev_start; g_ev_stop = (hipEvent_t)a.ev_stop;
-  const int rc = (a.act == MI_BF16) ? launch_pair_at<bf16>(q4, pa, pb, seam, st) : launch_pair_at<f16>(q4, pa, pb, seam, st);
-  g_ev_start = g_ev_stop = nullptr;
-  return rc;
-}
-
-int gemv_pair_grid() { return cu_count(); }
 
 }  // namespace mi

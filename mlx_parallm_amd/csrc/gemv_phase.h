@@ -1,6 +1,5 @@
-// gemv_phase.h -- the weight-streaming skinny GEMM of gemv_mfma.hip as a device-side building block (`Phase`):
-// gemv_mfma_kernel runs one, gemv_pair_kernel two, attn_decode_o_kernel (attn_decode.hip) runs o_proj behind the
-// decode attention.  See gemv_mfma.hip for the design notes.
+// gemv_phase.h -- the weight-streaming skinny GEMM of gemv_mfma.hip as a device-side building block (`Phase`),
+// and the small device helpers the other skinny kernels share.  See gemv_mfma.hip for the design notes.
 #pragma once
 #include <type_traits>
 
@@ -38,17 +37,6 @@ struct MfmaParams {
 #define PH_STAMP(i) do { } while (0)
 #define PH_STAMP_WAVE(i) do { } while (0)
 #endif
-
-// in-launch seam of gemv_pair_kernel: every workgroup adds 1 to *counter after phase A; phase B starts
-// when the counter has reached `target`.  A workgroup that polls `spin_limit` times without seeing it
-// sets *error and carries on: never a hang, and never a silent wrong token -- the host copies *error back behind
-// every step and fails that step with MI_ERR_RUNTIME (engine.hip: seam_record, mi_step_wait, seam_check_sync).
-struct SeamParams {
-  unsigned* counter;
-  unsigned target;
-  unsigned spin_limit;
-  int* error;
-};
 
 template <typename T>
 __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
@@ -146,14 +134,9 @@ __device__ __forceinline__ uint32_t pack2(f32x2 f) {
   }
 }
 
+// (a call, not an assignment: the address is computed before the value, which the epilogue's schedule depends on)
 template <typename AT>
-__device__ __forceinline__ void store_elem(AT* p, AT v, bool write_through) {
-  if (write_through) {
-    __hip_atomic_store((unsigned short*)p, __builtin_bit_cast(unsigned short, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    *p = v;
-  }
-}
+__device__ __forceinline__ void store_elem(AT* p, AT v) { *p = v; }
 
 // nbuf = 2 when K spans several activation chunks: chunk c+1 is staged into the other buffer while chunk c's
 // MFMAs run (no staging bubble in the weight stream)
@@ -216,7 +199,7 @@ struct Phase {
     red2 = rs_sh + 16;
     tid = threadIdx.x; lane = tid & 63; wave = tid >> 6; c16 = lane & 15; g = lane >> 4;
     x = (const AT*)p.x;
-    G = gridDim.x * gridDim.y; w = blockIdx.y * gridDim.x + blockIdx.x;   // (the attention launch that hosts o_proj is 2-D)
+    G = gridDim.x * gridDim.y; w = blockIdx.y * gridDim.x + blockIdx.x;
     ntiles_all = p.N / 16;
     ntiles = w < ntiles_all ? (ntiles_all - w + G - 1) / G : 0;
     nbatch = (ntiles + TB - 1) / TB;
@@ -253,15 +236,7 @@ struct Phase {
       }
     }
   }
-  __device__ __forceinline__ void issue_w(int tbi, int k0, int kend) {
-#pragma unroll
-    for (int u = 0; u < UK; ++u) issue_u(u, tbi, k0, kend);
-  }
-  // the first batch's weights: independent of any activation, so a caller may issue them early
-  __device__ __forceinline__ void prefetch_weights() { issue_w(0, 0, ntiles > 0 ? klen0 : 0); }
 
-
-  template <bool COH>
   __device__ __forceinline__ void load_x(int kbase, int klen) {
     const int n8 = klen / 8;
 #pragma unroll
@@ -271,9 +246,7 @@ struct Phase {
         const int k8 = tid + j * NT;
         xv[m][j] = u32x4{0u, 0u, 0u, 0u};
         if (m < p.M && k8 < n8) {
-          const AT* src = x + (size_t)m * p.ldx + kbase + k8 * 8;
-          if constexpr (COH) xv[m][j] = load16_agent(src);
-          else xv[m][j] = *(const u32x4*)src;
+          xv[m][j] = *(const u32x4*)(x + (size_t)m * p.ldx + kbase + k8 * 8);
         }
       }
   }
@@ -392,9 +365,7 @@ struct Phase {
     }
   }
 
-  // ---- cross-wave reduction + epilogue of the TB tiles of batch tbi.  WT: the outputs are read by
-  // other workgroups of this same launch -> write-through stores
-  template <bool WT>
+  // ---- cross-wave reduction + epilogue of the TB tiles of batch tbi
   __device__ __forceinline__ void finish(int tbi) {
 #pragma unroll
     for (int t = 0; t < TB; ++t) {
@@ -419,7 +390,7 @@ struct Phase {
             const float gt = (float)(AT)y0, up = (float)(AT)y1;
             const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
             const float sl = (float)(AT)(gt * sig);
-            store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)(sl * up), WT);
+            store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)(sl * up));
           } else if (p.epi == EPI_SWIGLU_GU8) {
             // row-interleaved gate|up tile: columns 0..7 are gate, 8..15 the matching up rows (same reduction order as above)
             if ((el & 15) < 8) {
@@ -429,7 +400,7 @@ struct Phase {
               const float gt = (float)(AT)y0, up = (float)(AT)yu;
               const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
               const float sl = (float)(AT)(gt * sig);
-              store_elem<AT>(&out[(size_t)m * p.ldo + (n >> 4) * 8 + (el & 15)], (AT)(sl * up), WT);
+              store_elem<AT>(&out[(size_t)m * p.ldo + (n >> 4) * 8 + (el & 15)], (AT)(sl * up));
             }
           } else {
             float y = (float)(AT)y0;
@@ -448,12 +419,12 @@ struct Phase {
                 }
               }
             }
-            if (p.epi == EPI_STORE) store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)y, WT);
+            if (p.epi == EPI_STORE) store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)y);
             else if (p.epi == EPI_STORE_F32) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
             else {
               AT* h = (AT*)p.resid;
               const float h0 = (hpre_ok && tile == 0) ? hpre : (float)h[(size_t)m * p.ldo + n];
-              store_elem<AT>(&h[(size_t)m * p.ldo + n], (AT)(h0 + y), WT);
+              store_elem<AT>(&h[(size_t)m * p.ldo + n], (AT)(h0 + y));
             }
           }
         }
@@ -463,24 +434,21 @@ struct Phase {
 
   // with several activation chunks the NEXT chunk's x is fetched into registers while the current
   // chunk's MFMAs run, so that re-staging costs two barriers but no exposed L2 round trip
-  template <bool COH>
   __device__ __forceinline__ void prefetch_next_x(int c, int tbi) {
     if (nchunks == 1) return;
     const int nc = (c + 1) % nchunks;
     if (nc == 0 && tbi + 1 >= nbatch) return;
-    load_x<COH>(nc * p.kc, min(p.kc, p.K - nc * p.kc));
+    load_x(nc * p.kc, min(p.kc, p.K - nc * p.kc));
   }
 
-  // The whole phase.  PREFETCHED: prefetch_weights() has already been called.  COH: x was written by
-  // other workgroups of this launch.  WT: the outputs will be read by other workgroups of this launch.
-  // Every __syncthreads below is reached by the whole workgroup also when it owns no tile.
-  template <bool PREFETCHED, bool COH, bool WT>
+  // The whole phase.  Every __syncthreads below is reached by the whole workgroup also when it owns no tile.
   __device__ __forceinline__ void run() {
-    // ================= prologue: activations first (older in the vmcnt queue), then weights
+    // ================= prologue: activations first (older in the vmcnt queue), then the first batch's weights
     PH_STAMP(0);
-    if (ntiles > 0) load_x<COH>(0, klen0);
-    if constexpr (!PREFETCHED) prefetch_weights();
-    if constexpr (!COH && !SWIGLU) {
+    if (ntiles > 0) load_x(0, klen0);
+#pragma unroll
+    for (int u = 0; u < UK; ++u) issue_u(u, 0, 0, ntiles > 0 ? klen0 : 0);
+    if constexpr (!SWIGLU) {
       // residual epilogue: the h values of the first tile now -- only this workgroup writes them in this launch -- instead of
       // as a dependent load after the cross-wave reduction, at the very end of the chain (o_proj / down_proj: one tile per
       // workgroup).  Straight-line: the pointer is selected, the load is not under a branch.
@@ -514,9 +482,7 @@ struct Phase {
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
               if (m < p.M) {
-                u32x4 v;
-                if constexpr (COH) v = load16_agent(x + (size_t)m * p.ldx + k);
-                else v = *(const u32x4*)(x + (size_t)m * p.ldx + k);
+                const u32x4 v = *(const u32x4*)(x + (size_t)m * p.ldx + k);
                 const AT* e = (const AT*)&v;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { const float f = (float)e[i]; ss[m] = fmaf(f, f, ss[m]); }
@@ -544,7 +510,7 @@ struct Phase {
     PH_STAMP(2);
     if (ntiles <= 0) return;
     int staged = 0;
-    prefetch_next_x<COH>(0, 0);
+    prefetch_next_x(0, 0);
 
     // ================= this workgroup's tile batches
     int cur = 0;                                // nbuf == 2: the buffer that holds the chunk being multiplied
@@ -557,7 +523,7 @@ struct Phase {
           stage_x(cbase, kend - cbase);         // from the registers prefetched one chunk ago
           __syncthreads();
           staged = c;
-          prefetch_next_x<COH>(c, tb);
+          prefetch_next_x(c, tb);
         }
         // nbuf == 2: the chunk that follows this one (possibly chunk 0 of the next tile) is staged into the
         // other buffer in the middle of this chunk's first batch -- its x has been in registers since the
@@ -593,38 +559,16 @@ struct Phase {
           __syncthreads();                      // the next chunk's fragments are complete; this chunk's are free
           cur ^= 1;
           frag = cur ? frag_b[1] : frag_b[0]; sx = cur ? sx_b[1] : sx_b[0];
-          prefetch_next_x<COH>(nc, nc == 0 ? tb + 1 : tb);
+          prefetch_next_x(nc, nc == 0 ? tb + 1 : tb);
         }
       }
       if (tb == nbatch - 1) { PH_STAMP(3); PH_STAMP_WAVE(8); }
-      finish<WT>(tb);
+      finish(tb);
       __syncthreads();                          // `red` / fragments are reused
     }
     PH_STAMP(7);
   }
 };
-
-// ---- in-launch seam: every workgroup calls seam_arrive once it has published its outputs (write-through stores,
-// drained), may issue loads that do not depend on the other workgroups, then seam_wait.  Bounded: a workgroup
-// that gives up sets *error and carries on; the engine fails the step that contains the launch (see SeamParams).
-__device__ __forceinline__ void seam_arrive(const SeamParams& seam) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's write-through stores have left
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(seam.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void seam_wait(const SeamParams& seam) {
-  if (threadIdx.x == 0) {
-    unsigned spins = 0;
-    while ((int)(__hip_atomic_load(seam.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seam.target) < 0) {
-      __builtin_amdgcn_s_sleep(4);
-      if (++spins > seam.spin_limit) {
-        __hip_atomic_store(seam.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-  }
-  __syncthreads();
-}
 
 }  // namespace gemv
 
