@@ -15,16 +15,25 @@ batch shard; no collective inside the timed region except the bracketing barrier
 `python bench.py --gpus N` typed as a plain command (no torchrun environment) launches its own N rank processes
 before anything touches a GPU and relays rank 0's line (mlx_parallm_amd.distributed.self_launch).
 
-Rank 0 prints ONE JSON line.  The headline leg (`value`, `ms_per_step`, `roofline`, `prefill_tokens_per_sec`) runs the
+Rank 0 prints ONE JSON line.  The headline leg (`value`, `ms_per_step`, `prefill_tokens_per_sec`) runs the
 REFERENCE'S numerics: float32 KV = PagedKVCache semantics, what `generate_step` / `batch_generate` really run on
-(utils.py:392 + base.py:111-112), the mode in which ids bit-exact / logprobs <= 1e-3 against the oracle are asserted.  The
-same workload with KV in the model dtype (BatchedKVCache semantics, narrower arithmetic than the reference's on this path)
-is timed next to it and reported under `fast_mode` (`--kv-dtype model` swaps the two; the float32 leg then appears as
-`reference_numerics`).  `roofline` is for the dominant kernel (the fused gate|up SwiGLU
-weight-streaming kernel): algorithmic bytes per launch / its mean launch time from HIP events
-on the engine's stream, measured in a second instrumented pass of the same K steps.
-`cpu_baseline` is the oracle's C restatement (oracle/c) timed on this box's host cores on a
-bounded sample (see the "sample" field); it is a reported baseline, not a target.
+(utils.py:392 + base.py:111-112), the mode in which ids bit-exact / logprobs <= 1e-3 against the oracle are asserted.
+
+A plain run does only what the headline leg needs: set-up, the leg's prefill (both passes, so that the sampler's step
+counter, and with it every sampled token, is what it is under `--full`), W warm-up and K timed steps, the
+`--dump-outputs` arrays and the line.  Everything else the benchmark measures needs `--full` (each part can still be
+left out there with its `--no-...` switch):
+  - the same workload with KV in the model dtype (BatchedKVCache semantics, narrower arithmetic than the reference's on
+    this path), reported under `fast_mode` (`--kv-dtype model` swaps the two; the float32 leg then appears as
+    `reference_numerics`);
+  - `roofline` for the dominant kernel (the fused gate|up SwiGLU weight-streaming kernel): algorithmic bytes per launch /
+    its mean launch time from HIP events on the engine's stream, measured in a second instrumented pass of the same K
+    steps after the timed ones;
+  - `cpu_baseline`: the oracle's C restatement (oracle/c) timed on this box's host cores on a bounded sample (see the
+    "sample" field); it is a reported baseline, not a target;
+  - `other_configs` (default workload at N = 1): short legs of BASELINE configs 3 / 4 / 5;
+  - `--mode mixed`: the unfused schedule (`unfused_schedule`, `fused_over_unfused`).
+The extras run after the headline leg's timed steps, so its timing and outputs are the same with or without `--full`.
 
 `--dump-outputs DIR` (rank 0): after the timed steps, what the headline leg's LAST timed step returned to its caller
 (`Engine.step_wait`: tokens, logprobs, probs_row0; in `--mode mixed` the last fused step) as DIR/<name>.npy, token
@@ -180,8 +189,10 @@ def numbers(cfg, quant_bits, B, K, W, ctx, leg, kv_dtype, kern, world):
         "gemv_head": cfg["vocab_size"] * H * bpp + B * H * ab + B * cfg["vocab_size"] * 4,
     }.get(kern, 0.0)
     ms_per_step = leg["elapsed"] / K * 1e3
-    avg_ms = leg["total_ms"] / max(leg["n_launch"], 1)
-    achieved = kern_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    avg_ms = achieved = None                                # no instrumented pass (plain run)
+    if leg["n_launch"] is not None:
+        avg_ms = leg["total_ms"] / max(leg["n_launch"], 1)
+        achieved = kern_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
     # prefill: algorithmic flops = 2 W T + NL 2 S^2 Hq D per sequence (causal), whatever the implementation
     # spends on top (the float32 leg multiplies the exact three-way split of x: 3 x the MFMA work for the same flops)
     pf_flops = B * (2.0 * n_params * ctx + cfg["num_hidden_layers"] * 2.0 * ctx * ctx * nh * D)
@@ -253,7 +264,7 @@ def other_config_legs(args, seed):
         entry = {"config": oc["config"], "workload": oc["workload"], "batch_per_gpu": B, "context": ctx, "steps": K, "warmup": W,
                  "load_seconds": round(t_load, 2)}
         for kvm in oc["kv_modes"]:
-            leg = decode_leg(eng, cfg, a, kvm, prompts, sample, None, 1, cap)
+            leg = decode_leg(eng, cfg, a, kvm, prompts, sample, None, 1, cap, instrument=True)
             n = numbers(cfg, qb, B, K, W, ctx, leg, kvm, "gemv_gate_up", 1)
             entry["kv_" + ("model_dtype" if kvm == "model" else "float32")] = {
                 "value": round(n["value"], 2), "unit": "tokens/s", "ms_per_step": round(n["ms_per_step"], 4),
@@ -266,7 +277,7 @@ def other_config_legs(args, seed):
             }
         if oc["mixed"]:
             a.chunk, a.kv_dtype, a.mode = chunk, "model", "mixed"
-            m = mixed_leg(eng, cfg, a, sample, None, 1)
+            m = mixed_leg(eng, cfg, a, sample, None, 1, unfused=True)
             f, u = m["fused"], m["unfused"]
             entry["mixed_prefill_decode"] = {
                 "what": f"{B - 1} live sequences decoding at KV length ~{ctx} while the next request's prompt enters {chunk} tokens "
@@ -292,17 +303,21 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=8, help="sequences per GPU")
     ap.add_argument("--context", type=int, default=1024)
     ap.add_argument("--kv-dtype", default="float32", choices=["model", "float32"],
-                    help="KV mode of the HEADLINE leg: float32 = the reference's PagedKVCache numerics (default); the other mode is "
-                         "still timed and reported, under fast_mode (model-dtype KV) / reference_numerics (float32 KV)")
+                    help="KV mode of the HEADLINE leg: float32 = the reference's PagedKVCache numerics (default); with --full the "
+                         "other mode is timed and reported too, under fast_mode (model-dtype KV) / reference_numerics (float32 KV)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the leg in the other KV mode, the instrumented "
+                         "pass for `roofline`, the CPU baseline, the other BASELINE configs and, in --mode mixed, the "
+                         "unfused schedule (each after the headline leg's timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-prefill-timing", action="store_true")
-    ap.add_argument("--no-second-leg", action="store_true", help="skip the leg in the other KV mode")
+    ap.add_argument("--no-second-leg", action="store_true", help="--full: skip the leg in the other KV mode")
     ap.add_argument("--lora", type=int, default=0, metavar="LAYERS",
                     help="apply rank-16 LoRA adapters (scale 10) to q_proj / v_proj of the last LAYERS blocks "
                          "(BASELINE config 5 uses 8; SURVEY §8d)")
     ap.add_argument("--greedy", action="store_true", help="greedy decode also for the int4 workloads (A/B of the sampler)")
-    ap.add_argument("--profile-kernel", default="gemv_gate_up")
+    ap.add_argument("--profile-kernel", default="gemv_gate_up", help="--full: the linear that `roofline` times")
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value (A/B experiments)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo only to rehearse N > 1 on a single-GPU box or on CPU")
@@ -310,13 +325,14 @@ def parse_args(argv=None):
     ap.add_argument("--mode", default="decode", choices=["decode", "mixed"],
                     help="decode: the headline metric (K decode steps of a full batch).  mixed: BASELINE config 5's 'mixed "
                          "prefill + decode' -- every step decodes the live rows AND ingests a chunk of an arriving prompt in "
-                         "the same pass over the weights (mi_step_enqueue_mixed, block-paged KV), timed next to the unfused "
+                         "the same pass over the weights (mi_step_enqueue_mixed, block-paged KV); with --full also the unfused "
                          "schedule (decode step, then the chunk on its own)")
     ap.add_argument("--chunk", type=int, default=0,
                     help="--mode mixed: prompt tokens ingested per step; 0 = what the live rows leave of 256 rows per step (int4: "
                          "96, the row limit of its weight-streaming kernel)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, default workload only: skip the short legs of BASELINE configs 3 / 4 / 5 (`other_configs` of the line)")
+                    help="--full, N = 1, default workload only: skip the short legs of BASELINE configs 3 / 4 / 5 "
+                         "(`other_configs` of the line)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the multi-process protocol without an engine (launch, rendezvous, bucketed weight "
                          "broadcast, barrier / max-over-ranks timing) -- the only mode that runs without a GPU; "
@@ -332,10 +348,10 @@ def parse_args(argv=None):
     return args
 
 
-def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap):
+def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap, instrument=False):
     """Prefill (timed separately, after one untimed pass on a cache of its own) + W warm-up steps + EXACTLY K timed
-    steps bracketed by barrier + device sync, MAX over ranks; then K more steps with the dominant kernel's launches
-    bracketed by HIP events on the engine's own stream."""
+    steps bracketed by barrier + device sync, MAX over ranks; `instrument`: then K more steps with the dominant kernel's
+    launches bracketed by HIP events on the engine's own stream (n_launch / total_ms, else None)."""
     import torch
 
     B, K, W = args.batch, args.steps, args.warmup
@@ -377,21 +393,24 @@ def decode_leg(engine, cfg, args, kv_dtype, prompts, sample, dist, world, cap):
         tt = torch.tensor([elapsed, t_prefill, own, -own], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, t_prefill, own_max, own_min = float(tt[0].item()), float(tt[1].item()), float(tt[2].item()), -float(tt[3].item())
-    engine.profile_select(args.profile_kernel)
-    last = run_steps(K)
-    engine.step_wait(last, B)
-    n_launch, total_ms = engine.profile_read()
-    engine.profile_select(None)
+    n_launch = total_ms = None
+    if instrument:
+        engine.profile_select(args.profile_kernel)
+        last = run_steps(K)
+        engine.step_wait(last, B)
+        n_launch, total_ms = engine.profile_read()
+        engine.profile_select(None)
     kv.close()
     return dict(elapsed=elapsed, t_prefill=t_prefill, n_launch=n_launch, total_ms=total_ms, own_min=own_min, own_max=own_max,
                 outputs=outputs)
 
 
-def mixed_leg(engine, cfg, args, sample, dist, world):
+def mixed_leg(engine, cfg, args, sample, dist, world, unfused=False):
     """Steady state of a serving batch: B slots, B - 1 of them decoding at context ~args.context, one slot taking in
     the prompt of the next request `--chunk` tokens per step; when a prompt is complete it starts decoding and the
     oldest sequence leaves (its row is reset for the next arrival).  Returns timings of K such steps, fused (one
-    mi_step_enqueue_mixed per step) and unfused (a decode step of the live rows + the chunk as a step of its own)."""
+    mi_step_enqueue_mixed per step) and, if `unfused`, after it unfused (a decode step of the live rows + the chunk as a
+    step of its own)."""
     import numpy as np
     import torch
 
@@ -400,7 +419,7 @@ def mixed_leg(engine, cfg, args, sample, dist, world):
     V = cfg["vocab_size"]
     out = {}
     last_res = {}
-    for fused in (True, False):
+    for fused in ((True, False) if unfused else (True,)):
         kv = engine.new_paged_kv(B, block_tokens=64, max_tokens_per_row=ctx + K + W + 2 * C + 64, kv_dtype=args.kv_dtype)
         # B - 1 live sequences with `ctx` tokens each (prefilled 8 rows at a time), row B - 1 is the arrival slot
         live = list(range(B - 1))
@@ -566,12 +585,18 @@ def main():
     greedy = SampleArgs(temp=1.0, top_p=0.9, seed=args.seed) if (quant_bits and not args.greedy) else SampleArgs(temp=0.0)
 
     if args.mode == "mixed":
-        m = mixed_leg(engine, cfg, args, greedy, dist, world)
+        m = mixed_leg(engine, cfg, args, greedy, dist, world, unfused=args.full)
         if rank == 0:
-            f, u = m["fused"], m["unfused"]
+            f, u = m["fused"], m.get("unfused")
             if args.dump_outputs:
                 dump_outputs(args.dump_outputs, f["outputs"])
             w_bytes, _ = streamed_weight_bytes(cfg, quant_bits)
+            unfused_fields = {} if u is None else {
+                "unfused_schedule": {"what": "the same K steps as a decode step of the live rows followed by the chunk as a step of its own (two passes over the weights)",
+                                     "decode_tokens_per_sec": round(world * u["decode_tokens"] / u["elapsed"], 2),
+                                     "ms_per_step": round(u["elapsed"] / K * 1e3, 4)},
+                "fused_over_unfused": round(u["elapsed"] / f["elapsed"], 3),
+            }
             print(json.dumps({
                 "metric": "decode_tokens_per_sec", "value": round(world * f["decode_tokens"] / f["elapsed"], 2), "unit": "tokens/s",
                 "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(f["elapsed"] / K * 1e3, 4), "higher_is_better": True,
@@ -585,10 +610,7 @@ def main():
                            "batch_per_gpu": B, "global_batch": B * world, "context": ctx, "chunk_tokens": args.chunk,
                            "kv_dtype": args.kv_dtype, "parallelism": f"dp{world} (batch-sharded replicas, no collective in the step)"},
                 "prefill_tokens_per_sec_in_the_same_steps": round(world * f["prompt_tokens"] / f["elapsed"], 1),
-                "unfused_schedule": {"what": "the same K steps as a decode step of the live rows followed by the chunk as a step of its own (two passes over the weights)",
-                                     "decode_tokens_per_sec": round(world * u["decode_tokens"] / u["elapsed"], 2),
-                                     "ms_per_step": round(u["elapsed"] / K * 1e3, 4)},
-                "fused_over_unfused": round(u["elapsed"] / f["elapsed"], 3),
+                **unfused_fields,
                 "weight_bytes_per_step": int(w_bytes), "kv_arena": f["kv_stats"], "load_seconds": round(t_load, 2), "ranks_seen": ranks_seen,
             }), flush=True)
         engine.close()
@@ -596,9 +618,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    head = decode_leg(engine, cfg, args, args.kv_dtype, prompts, greedy, dist, world, cap)
+    head = decode_leg(engine, cfg, args, args.kv_dtype, prompts, greedy, dist, world, cap, instrument=args.full)
     other_mode = "float32" if args.kv_dtype == "model" else "model"
-    other = None if args.no_second_leg else decode_leg(engine, cfg, args, other_mode, prompts, greedy, dist, world, cap)
+    other = None
+    if args.full and not args.no_second_leg:
+        other = decode_leg(engine, cfg, args, other_mode, prompts, greedy, dist, world, cap, instrument=True)
 
     w_bytes, n_params = streamed_weight_bytes(cfg, quant_bits)
     H, I = cfg["hidden_size"], cfg["intermediate_size"]
@@ -657,10 +681,10 @@ def main():
                 "batch_per_gpu": B, "global_batch": B * world, "context": ctx,
                 "kv_dtype": kv_names[args.kv_dtype],
                 "numerics": ("the reference's (PagedKVCache float32; oracle parity asserted in this mode)" if args.kv_dtype == "float32"
-                             else "fast mode (16-bit KV and activations); the reference-numerics leg is under reference_numerics"),
+                             else "fast mode (16-bit KV and activations); with --full the reference-numerics leg is under reference_numerics"),
                 "parallelism": f"dp{world} (batch-sharded replicas, no collective in the decode step)",
             },
-            "roofline": dict(roofline_of(hn, args.kv_dtype), launches=head["n_launch"]),
+            **({"roofline": dict(roofline_of(hn, args.kv_dtype), launches=head["n_launch"])} if args.full else {}),
             "step_bytes": int(hn["step_bytes"]),
             "step_hbm_frac": round(hn["step_bytes"] / (hn["ms_per_step"] * 1e-3) / 8e12, 4),
             "step_hbm_frac_of_achievable": round(hn["step_bytes"] / (hn["ms_per_step"] * 1e-3) / 6.29e12, 4),
@@ -689,7 +713,7 @@ def main():
                 "step_hbm_frac": round(on["step_bytes"] / (on["ms_per_step"] * 1e-3) / 8e12, 4),
                 "roofline": dict(roofline_of(on, other_mode), launches=other["n_launch"]),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import c_ref
 
             nl_s, steps_s = 2, 6
@@ -701,7 +725,7 @@ def main():
                            f"{steps_s} decode steps at KV length {ctx}, batch {B}, bf16 weights; block time scaled "
                            f"x{cfg['num_hidden_layers']}/{nl_s}; not MLX (unavailable offline)"),
             }
-        if world == 1 and not args.no_other_configs and args.workload == "mistral-7b-bf16" and B == 8 and not args.lora:
+        if args.full and world == 1 and not args.no_other_configs and args.workload == "mistral-7b-bf16" and B == 8 and not args.lora:
             engine.close()
             engine = None
             out["other_configs"] = other_config_legs(args, args.seed)

@@ -11,6 +11,10 @@ def test_steps_must_be_positive():
         bench.parse_args(["--steps", "0"])
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True
+
 def test_dump_outputs_needs_the_engine():
     assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
     with pytest.raises(SystemExit):

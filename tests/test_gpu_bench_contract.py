@@ -1,5 +1,5 @@
-"""bench.py's output contract (-m gpu): ONE JSON line on stdout with the fields the driver reads, `roofline` for the
-dominant kernel and `cpu_baseline` from the oracle's C restatement.  Run on the tiny shape so that it takes seconds."""
+"""bench.py's output contract (-m gpu): ONE JSON line on stdout with the fields the driver reads; with --full also `roofline`
+for the dominant kernel and `cpu_baseline` from the oracle's C restatement.  Run on the tiny shape so that it takes seconds."""
 import json
 import subprocess
 import sys
@@ -13,7 +13,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny-bf16", "--steps", "6", "--warmup", "2",
-                          "--context", "64", "--batch", "2"], cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+                          "--context", "64", "--batch", "2", "--full"], cwd=str(ROOT), capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -31,6 +31,34 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     c = j["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == "tokens/s" and c["sample"]
 
+
+def test_plain_run_is_the_headline_leg_alone_and_computes_what_full_computes(tmp_path):
+    """Without --full the line has the headline fields and none of the extras (the leg in the other KV mode, the
+    instrumented pass, the CPU baseline), and the last timed step returns what it returns in a --full run."""
+    import numpy as np
+
+    lines, dumps = {}, {}
+    for full in (False, True):
+        d = tmp_path / ("full" if full else "plain")
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tiny-bf16", "--steps", "5", "--warmup", "1",
+                              "--context", "64", "--batch", "2", "--dump-outputs", str(d)] + (["--full"] if full else []),
+                             cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines[full] = json.loads(out[0])
+        dumps[full] = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+    plain, full = lines[False], lines[True]
+    assert plain["metric"] == "decode_tokens_per_sec" and plain["unit"] == "tokens/s" and plain["higher_is_better"] is True
+    assert plain["steps"] == 5 and plain["warmup"] == 1 and plain["dtype"] == full["dtype"] == "bf16"
+    assert plain["config"] == full["config"]
+    assert plain["value"] > 0 and abs(plain["value"] - 2 * 5 / (plain["ms_per_step"] * 5e-3)) / plain["value"] < 0.01
+    assert not {"roofline", "cpu_baseline", "fast_mode", "reference_numerics", "other_configs"} & set(plain)
+    assert {"roofline", "cpu_baseline", "fast_mode"} <= set(full)
+    assert set(dumps[False]) == set(dumps[True]) == {"tokens", "logprobs", "probs_row0"}
+    assert np.array_equal(dumps[False]["tokens"], dumps[True]["tokens"])
+    for k in ("logprobs", "probs_row0"):
+        assert np.allclose(dumps[False][k], dumps[True][k], rtol=0, atol=1e-5), k
 
 def test_bench_dump_outputs_is_the_same_for_the_same_arguments(tmp_path):
     """--dump-outputs DIR: the last timed step's tokens / logprobs / probs_row0, one .npy each (float64 ids, float32
@@ -62,7 +90,7 @@ def test_bench_gpus_2_as_a_plain_command_runs_two_ranks_with_engines():
     talk over gloo (--same-device --backend gloo); on a multi-GPU node the same command uses RCCL."""
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
                           "--workload", "tiny-bf16", "--steps", "6", "--warmup", "2", "--context", "64", "--batch", "2",
-                          "--no-cpu-baseline"], cwd=str(ROOT), capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], cwd=str(ROOT), capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -57,7 +57,7 @@ def main():
 
     import bench
 
-    argv = ["--workload", args.workload, "--no-cpu-baseline", "--steps", str(args.steps), "--warmup", "2", "--batch", str(args.batch),
+    argv = ["--workload", args.workload, "--full", "--no-cpu-baseline", "--steps", str(args.steps), "--warmup", "2", "--batch", str(args.batch),
             "--no-prefill-timing"]
     argv += ["--no-second-leg"] if args.kv == "model" else []
     for o in args.opt:

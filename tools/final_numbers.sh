@@ -1,8 +1,10 @@
 #!/bin/bash
-# The measurement set quoted in DESIGN.md / README.md, one box, final build.  Output: gpurun_out/final_<name>.json
+# The measurement set quoted in DESIGN.md / README.md, one box, final build.  Output: $OUT/final_<name>.json (default bench_out/)
 set -e
-b() { n=$1; shift; python bench.py --no-cpu-baseline "$@" > gpurun_out/final_$n.json 2>> gpurun_out/final.err; echo "$n done"; }
-python bench.py > gpurun_out/final_default.json 2>> gpurun_out/final.err; echo default done
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+b() { n=$1; shift; python bench.py --full --no-cpu-baseline "$@" > "$OUT/final_$n.json" 2>> "$OUT/final.err"; echo "$n done"; }
+python bench.py --full > "$OUT/final_default.json" 2>> "$OUT/final.err"; echo default done
 b int4 --workload mistral-7b-int4
 b int8 --workload mistral-7b-int8
 b q_bf16 --workload qwen3-14b-bf16

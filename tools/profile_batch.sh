@@ -21,8 +21,8 @@ OUT=$ROOT/gpurun_out/prof_b$B
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 $ROOT/bench.py --workload $WL --batch $B --steps 32 --warmup 4 --no-cpu-baseline --no-prefill-timing > "$OUT/bench.json" 2> "$OUT/stats.err"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 $ROOT/bench.py --workload $WL --batch $B --steps 32 --warmup 4 --full --no-cpu-baseline --no-prefill-timing > "$OUT/bench.json" 2> "$OUT/stats.err"
 python3 "$ROOT/tools/summarize_prof.py" stats "$OUT/stats" "$ROOT/gpurun_out/b${B}_${WL}_kernel_stats.csv" \
-  "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WL --batch $B --steps 32 --warmup 4 --no-prefill-timing"
+  "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WL --batch $B --steps 32 --warmup 4 --full --no-prefill-timing"
 grep '^{' "$OUT/bench.json" > "$ROOT/gpurun_out/b${B}_${WL}_bench.json"
 rm -rf "$OUT/stats"
