@@ -91,6 +91,12 @@ int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters,
  * -(row_tiles | tile_units << 3 | k_lanes << 7 | ksplit << 11 | staging_waves << 15), any field 0 = the cost model's choice. */
 int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int ksplit, int* ksplit_used, int iters,
                       float* avg_ms);
+/* the one-pass weight-streaming GEMV of the float32-KV decode step (gemv_f32.hip) on its own: float32 activations, outputs
+ * and norm weights, a->rnd = MI_RND_NONE, a->M in 1..8, tile-major dense bf16 weights, K % 32 == 0, N % 16 == 0.  Epilogues:
+ * MI_EPI_STORE / MI_EPI_STORE_F32 / MI_EPI_RESID, and MI_EPI_SWIGLU on a gate|up matrix of 2 x a->pair_offset rows (the
+ * row-interleaved copy the engine keeps is made inside the call).  a->pro may be MI_PRO_NORM: the row scale is applied in
+ * the epilogue.  iters >= 1 also times that many back-to-back launches into *avg_ms. */
+int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* gemm_prefill.hip on its own: the tile GEMM of the prefill call (generate_step's first model call, utils.py:243-262: every
  * nn.Linear over B x L rows at once).  a->M rows of 16-bit activations, tile-major dense 16-bit weights, a->pro =
  * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms. */

@@ -441,6 +441,25 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       return MI_OK;
     }
   }
+  // float32-KV decode step of <= 8 sequences, the WIDE linears (at least 4 tiles per CU: gate|up on its row-interleaved copy,
+  // lm_head): one pass over W with one workgroup per CU and no K split (gemv_f32.hip) instead of the 9..128-row kernel below,
+  // whose tile groups x K slices leave CUs idle at this shape and meet through a workspace.  RMSNorm is deferred to the
+  // epilogue there.  Narrow linears (q|k|v, o, down: 1-1.5 tiles per CU) stay below -- measured, DESIGN §8d.
+  if (e->opt_skinny_gemm && e->cur_L == 1 && rows <= 8 && c.act == MI_F32 && c.rnd == RND_NONE && c.kx == 0) {
+    GemvCall cw = c;
+    cw.M = (int)rows;
+    LinearW wv = f.W;                          // (a view: the interleaved copy stays owned by f0)
+    bool take = true;
+    if (c.epi == EPI_SWIGLU) {
+      take = gu8_wanted(e, f0, c.pair_offset) && ensure_gu8(e, const_cast<FusedLinear&>(f0), c.pair_offset);
+      if (take) { wv.w = f0.w_gu8; cw.epi = EPI_SWIGLU_GU8; }
+    }
+    if (take && wv.N / 16 >= 4 * gemv_cu_count() && gemv_f32_supported(wv, cw)) {
+      Prof pr(e, prof);
+      if (cw.pro == PRO_NORM && !e->opt_defer_norm) MI_TRY(norm_into_xn(e, cw, rows, KT, cw.rnd));
+      return launch_gemv_f32(wv, cw, e->stream);
+    }
+  }
   // decode steps: the streaming kernel up to 96 rows for dense weights -- above that the K-split tile GEMM is ahead
   // (Mistral-7B bf16, KV 512: 96 rows 7.18 vs 7.14 ms / step, 128 rows 8.71 vs 7.96)
   const size_t decode_max = quant ? 128 : 96;

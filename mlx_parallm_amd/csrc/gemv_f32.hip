@@ -1,0 +1,338 @@
+// gemv_f32.hip -- one-pass weight-streaming GEMV for FLOAT32 activations, <= 8 rows, on dense bf16 weights in the
+// tile-major layout (repack.hip): the wide linears (gate|up, lm_head) of a decode step in the float32-KV
+// ("PagedKVCache") mode of a bf16 model.
+//
+// Same operator and the same arithmetic contract as skinny_kernel<.., X32> (gemm_skinny.hip): x = hi + mid + lo exactly
+// (three bf16 terms), every product exact in the float32 accumulator -- a float32 dot product in another summation
+// order; outputs float32, no logical rounding.  What differs is the shape of the launch, which is that of gemv_mfma.hip:
+//
+//   * One 8-wave workgroup per CU, 16-row tiles of W dealt round-robin (tile = w + i G), NO K split over workgroups:
+//     no workspace, no arrival counter, no partial tiles, nothing that another workgroup of the launch reads.
+//   * Chunk-outer, tile-inner.  A workgroup walks K in chunks of 1024 and, inside a chunk, all the tiles of a "pass"
+//     (up to 8), with one float32 accumulator per tile held in registers for the whole pass.  A workgroup with more
+//     than 8 tiles runs several passes.
+//   * The eight waves split the 32 k-blocks (of 32) of a chunk round-robin, wave v owns blocks v, v + 8, v + 16, v + 24
+//     -- of EVERY tile.  So a wave only ever multiplies by the x of its own four blocks, and it needs no other wave's
+//     activations: each lane fetches the 8 floats of its own MFMA A-fragment position straight from x (L2), splits them
+//     in registers and keeps the fragments for all the tiles of the chunk.  There is no staging through LDS, no barrier
+//     inside the stream and nothing to double-buffer: a block's fragments are replaced by the next chunk's right after
+//     their last use (the chunk's last tile), from registers fetched two load positions earlier, so at most two blocks'
+//     raw x are live.  A workgroup reads x once per pass (32 KiB per chunk, L2 traffic).
+//   * No padded rows.  An MFMA A operand has 16 rows and the call at most 8: fragment rows 0..7 of the first image hold
+//     `hi`, rows 8..15 hold `mid`; the second image holds `lo` in rows 0..7 and zeros (a lane select) in rows 8..15.
+//     Two v_mfma_f32_16x16x32_bf16 per 1-KiB weight block; accumulator rows m and m + 8 are added once per tile in the
+//     epilogue.
+//   * The stream never drains inside a pass: every wave keeps D 16-byte non-temporal loads in flight, rolling across
+//     tile and chunk ends (and into the next pass when both are full), straight-line (no load under a branch; slots past
+//     the end re-load a cached block and are ignored).  D = 16 (128 KiB per CU) when a pass has 4 or 8 tiles; otherwise
+//     the largest of 14 / 12 / 10 that divides the 4 NT loads of a chunk, so that the slot of every load is static.
+//   * RMSNorm (PRO_NORM) is deferred and local: x is multiplied by the norm weight while it is split, the squares of the
+//     raw x are summed on the way (first pass only: each element once per launch), and rs[m] = rsqrt(mean + eps) scales
+//     the dot product in the epilogue.  Every workgroup sees all of x, so it owns the complete row sums.  In float32
+//     this differs from w * (x * rs) by one rounding per element (~6e-8), as `defer_norm` in gemm_skinny.hip.
+//
+// Every load is addressed as a wave-uniform 64-bit base plus a 32-bit lane offset: with one 64-bit address pair per load
+// position the loop spilled, and a spill reload drains the prefetch queue.
+//
+// Resources: 512 threads, 254 VGPRs (one workgroup per CU), no scratch.  LDS: 32.5 KiB static -- the cross-wave
+// reduction of a pass ([8 tiles][8 waves][32 lanes] float4 = 32 KiB, written once per pass after the last chunk) and
+// the waves' row sums of squares (8 x 8 floats).
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+
+#include "gemv_phase.h"
+
+namespace mi {
+
+namespace {
+
+using namespace gemv;
+
+constexpr int F32_NW = 8;                       // waves per workgroup
+constexpr int F32_TP = 8;                       // tiles per pass (one accumulator each)
+constexpr int F32_KB = 32;                      // k-blocks (of 32) per chunk: chunks of 1024
+constexpr int F32_UB = F32_KB / F32_NW;         // blocks per wave, tile and chunk
+
+struct F32Params {
+  const float* x; int ldx; int M;
+  int pro; const float* norm_w; float eps;
+  const void* w; int N, K;
+  int epi; float* out; int ldo; float* resid;
+};
+
+// loads per wave in flight for a pass of NT tiles (see the header)
+__host__ __device__ constexpr int f32_depth(int nt) {
+  const int l = nt * F32_UB;
+  return l < 16 ? l : l % 16 == 0 ? 16 : l % 14 == 0 ? 14 : l % 12 == 0 ? 12 : 10;
+}
+
+// base + off as a pointer the compiler keeps in scalar registers (both are wave-uniform): the loads below then take the
+// "scalar base + 32-bit lane offset" form, and no load of the stream carries a 64-bit address register pair of its own
+// (global address space spelled out: an integer turned pointer would otherwise be loaded through the flat path)
+typedef const __attribute__((address_space(1))) char* gptr;
+typedef const __attribute__((address_space(1))) u32x4* gptr16;
+__device__ __forceinline__ gptr uniform_ptr(const void* base, size_t off) {
+  const uint64_t a = (uint64_t)base + off;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return (gptr)(((uint64_t)hi << 32) | lo);
+}
+
+template <bool GU8>
+struct F32Body {
+  const F32Params& p;
+  float* red; float* sq_sh;
+  int tid, lane, wave, c16, g;
+  int G, w, ntiles_all, ntiles, nkb, nchunks;
+  uint32_t xoff;                // bytes from x to this lane's A-fragment position: row min(c16 & 7, M - 1), column 8 g
+  uint32_t noff;                // ... in the norm weights: column 8 g (without PRO_NORM x is loaded there and ignored)
+  bool norm;
+
+  u32x4 ring[16];
+  f32x4 acc[F32_TP];
+  u32x4 af[F32_UB][2];          // this lane's A fragments of the wave's four blocks of a chunk: [block][image]
+  u32x4 xr[F32_UB][2], nr[F32_UB][2];   // raw x / norm weights of a block on their way to af (at most two blocks are live)
+  float ss = 0.f;               // sum of squares of the raw x this lane has split (first pass)
+  float rs = 1.f;               // threads of the epilogue: the row scale of their row
+
+  __device__ __forceinline__ F32Body(const F32Params& pp, float* red_, float* sq_) : p(pp), red(red_), sq_sh(sq_) {
+    tid = threadIdx.x; lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6); c16 = lane & 15; g = lane >> 4;
+    G = gridDim.x; w = blockIdx.x;
+    ntiles_all = p.N / 16;
+    ntiles = w < ntiles_all ? (ntiles_all - w + G - 1) / G : 0;
+    nkb = p.K / 32;
+    nchunks = (nkb + F32_KB - 1) / F32_KB;
+    norm = p.pro == PRO_NORM;
+    xoff = ((uint32_t)min(c16 & 7, p.M - 1) * (uint32_t)p.ldx + 8u * g) * 4u;      // (<= 8 rows: far below 4 GiB)
+    noff = 32u * g;
+  }
+
+  __device__ __forceinline__ int tile_of(int i) const { return min(w + i * G, ntiles_all - 1); }
+
+  // STRAIGHT-LINE (gemv_phase.h issue_u): an invalid slot re-loads block 0 of this workgroup's first tile
+  __device__ __forceinline__ void issue(int slot, int i, int kb, bool valid) {
+    const int t = valid ? tile_of(i) : w, b = valid ? kb : 0;
+    // a uniform 64-bit tile base plus a 32-bit lane offset (a tile is K * 32 bytes): no per-position address registers
+    const gptr tb = uniform_ptr(p.w, ((size_t)t * nkb + b) * 1024);
+    ring[slot] = __builtin_nontemporal_load((gptr16)(tb + (uint32_t)lane * 16u));
+  }
+
+  // the x (and norm weights) of this wave's block u of chunk c, into registers
+  __device__ __forceinline__ void load_x(int c, int u) {
+    const int kb = c * F32_KB + u * F32_NW + wave;
+    const int k = kb < nkb ? kb * 32 : 0;
+    const gptr xb = uniform_ptr(p.x, (size_t)k * 4);
+    const gptr nb = uniform_ptr(norm ? p.norm_w : p.x, (size_t)k * 4);
+    xr[u][0] = *(gptr16)(xb + xoff);
+    xr[u][1] = *(gptr16)(xb + xoff + 16u);
+    nr[u][0] = *(gptr16)(nb + noff);
+    nr[u][1] = *(gptr16)(nb + noff + 16u);
+  }
+
+  // registers -> (x * w_norm) -> hi / mid / lo -> the two A-fragment images of this lane for block u of chunk c.
+  // `count`: the squares of the raw x go to the row sums
+  __device__ __forceinline__ void split_x(int c, int u, bool count) {
+    const bool low = c16 < 8;
+    const int kb = c * F32_KB + u * F32_NW + wave;
+    const uint32_t xd[8] = {xr[u][0].x, xr[u][0].y, xr[u][0].z, xr[u][0].w, xr[u][1].x, xr[u][1].y, xr[u][1].z, xr[u][1].w};
+    const uint32_t nd[8] = {nr[u][0].x, nr[u][0].y, nr[u][0].z, nr[u][0].w, nr[u][1].x, nr[u][1].y, nr[u][1].z, nr[u][1].w};
+    uint32_t a0[4], a1[4];
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x2 f = {__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])};
+      if (norm) {
+        const f32x2 wf = {__uint_as_float(nd[2 * j]), __uint_as_float(nd[2 * j + 1])};
+        sq = fmaf(f.x, f.x, sq); sq = fmaf(f.y, f.y, sq);
+        f = f * wf;
+      }
+      const uint32_t hi = pack2<bf16>(f);
+      const f32x2 r1 = f - unpack2<bf16>(hi);
+      const uint32_t mid = pack2<bf16>(r1);
+      const uint32_t lo = pack2<bf16>(r1 - unpack2<bf16>(mid));
+      a0[j] = low ? hi : mid;
+      a1[j] = low ? lo : 0u;
+    }
+    af[u][0] = u32x4{a0[0], a0[1], a0[2], a0[3]};
+    af[u][1] = u32x4{a1[0], a1[1], a1[2], a1[3]};
+    if (count && kb < nkb) ss += sq;
+  }
+
+  // One pass: tiles i0 .. i0 + NT - 1 of this workgroup over all of K.  `preloaded`: the previous pass has issued this
+  // pass's first D loads and split its first chunk's x; `roll`: this pass does so for the next one (both have 8 tiles).
+  template <int NT>
+  __device__ __forceinline__ void pass(int i0, bool preloaded, bool roll, bool first) {
+    constexpr int L = NT * F32_UB, D = f32_depth(NT);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!preloaded) {
+#pragma unroll
+      for (int s = 0; s < D; ++s) {
+        const int kb = (s % F32_UB) * F32_NW + wave;
+        issue(s, i0 + s / F32_UB, kb, kb < nkb);
+      }
+#pragma unroll
+      for (int u = 0; u < F32_UB; ++u) load_x(0, u);
+#pragma unroll
+      for (int u = 0; u < F32_UB; ++u) split_x(0, u, first);
+    }
+    for (int c = 0; c < nchunks; ++c) {
+      const bool last = c + 1 == nchunks;
+      const int nc = last ? 0 : c + 1;
+      const bool have_next = !last || roll;
+      // The next chunk's x.  Block u's fragments are last used at position L - 4 + u: they are replaced right there, from
+      // registers fetched XD positions earlier (an L2 round trip), so at most two blocks' raw x are live at a time.
+      // In the last chunk of a pass that does not roll (`last && !roll`) chunk 0's x is fetched and split all the same, unused:
+      // deliberate straight-line filler like the invalid weight slots (8 cached loads and 4 splits per wave at the tail of
+      // the pass; `count` is false, so the row sums are not touched) -- a branch around the loads would drain the queue.
+      constexpr int XD = 2;
+#pragma unroll
+      for (int u = 0; u < F32_UB; ++u)
+        if (L - F32_UB + u - XD < 0) load_x(nc, u);           // (a pass of one tile: no earlier position)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int u = 0; u < F32_UB; ++u) {
+          const int pos = t * F32_UB + u, slot = pos % D;
+          if (c * F32_KB + u * F32_NW + wave < nkb) {       // (wave-uniform; no load inside)
+            acc[t] = mfma16<bf16>(af[u][0], ring[slot], acc[t]);
+            acc[t] = mfma16<bf16>(af[u][1], ring[slot], acc[t]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          // the same registers are re-loaded with the load D positions ahead in this workgroup's sequence
+          const int q = pos + D;
+          if (q < L) {
+            const int kb = c * F32_KB + (q % F32_UB) * F32_NW + wave;
+            issue(slot, i0 + q / F32_UB, kb, kb < nkb);
+          } else {
+            const int q2 = q - L;
+            const int kb = nc * F32_KB + (q2 % F32_UB) * F32_NW + wave;
+            issue(slot, (last ? i0 + NT : i0) + q2 / F32_UB, kb, have_next && kb < nkb);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (pos >= L - F32_UB) split_x(nc, pos - (L - F32_UB), first && !last);
+          if (pos + XD >= L - F32_UB && pos + XD < L) load_x(nc, pos + XD - (L - F32_UB));
+        }
+      }
+    }
+
+    // ---- cross-wave reduction.  Lane (c16, g) holds D rows 4 g + r: rows 0..7 (hi and lo products) in g < 2, rows
+    // 8..15 (mid products) in g >= 2 -- added here, lanes 0..31 publish y[m = 4 (lane >> 4) + r][n = lane & 15]
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      f32x4 v = acc[t];
+      v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
+      if (lane < 32) *(f32x4*)&red[((t * F32_NW + wave) * 32 + lane) * 4] = v;
+    }
+    if (first && norm) {
+      float v = ss;                               // lanes c16 < 8: row c16, the four k-groups of the wave's blocks
+      v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+      if (lane < 8) sq_sh[wave * 8 + lane] = v;
+    }
+    __syncthreads();
+    // thread (t, m, c): columns c and c + 8 of row m of tile t
+    const int t = tid >> 6, m = (tid >> 3) & 7, cc = tid & 7;
+    if (first && norm) {
+      float tot = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < F32_NW; ++ww) tot += sq_sh[ww * 8 + m];
+      rs = 1.0f / sqrtf(tot / (float)p.K + p.eps);
+    }
+    if (t < NT && m < p.M) {
+      const int el = (m >> 2) * 16 + cc, r = m & 3;
+      float y0 = 0.f, y1 = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < F32_NW; ++ww) {
+        y0 += red[((t * F32_NW + ww) * 32 + el) * 4 + r];
+        y1 += red[((t * F32_NW + ww) * 32 + el + 8) * 4 + r];
+      }
+      y0 *= rs; y1 *= rs;
+      const int tile = w + (i0 + t) * G;          // (t < NT: one of this workgroup's tiles)
+      if constexpr (GU8) {
+        // row-interleaved gate|up tile: columns 0..7 are gate rows 8 tile .. + 7, columns 8..15 the matching up rows
+        const float sig = 1.0f / (1.0f + expf(-y0));
+        const float sl = y0 * sig;
+        p.out[(size_t)m * p.ldo + tile * 8 + cc] = sl * y1;
+      } else {
+        const size_t o = (size_t)m * p.ldo + tile * 16 + cc;
+        if (p.epi == EPI_RESID) {
+          const float h0 = p.resid[o], h1 = p.resid[o + 8];
+          p.resid[o] = h0 + y0; p.resid[o + 8] = h1 + y1;
+        } else {                                  // EPI_STORE and EPI_STORE_F32 coincide
+          p.out[o] = y0; p.out[o + 8] = y1;
+        }
+      }
+    }
+  }
+
+  __device__ __forceinline__ void run() {
+    int done = 0;
+    bool pre = false;
+    while (done < ntiles) {
+      const int nt = min(F32_TP, ntiles - done);
+      const bool roll = nt == F32_TP && ntiles - done - nt >= F32_TP;
+      const bool first = done == 0;
+      if (done > 0) __syncthreads();              // `red` is reused
+      switch (nt) {
+        case 8: pass<8>(done, pre, roll, first); break;
+        case 7: pass<7>(done, false, false, first); break;
+        case 6: pass<6>(done, false, false, first); break;
+        case 5: pass<5>(done, false, false, first); break;
+        case 4: pass<4>(done, false, false, first); break;
+        case 3: pass<3>(done, false, false, first); break;
+        case 2: pass<2>(done, false, false, first); break;
+        default: pass<1>(done, false, false, first); break;
+      }
+      pre = roll;
+      done += nt;
+    }
+  }
+};
+
+__global__ __launch_bounds__(F32_NW * 64) void gemv_f32_kernel(F32Params p) {
+  __shared__ __attribute__((aligned(16))) float red[F32_TP * F32_NW * 32 * 4];
+  __shared__ float sq_sh[F32_NW * 8];
+  F32Body<false> b(p, red, sq_sh);
+  b.run();
+}
+
+// The same stream under its own symbol for the launches on a row-interleaved gate|up copy (EPI_SWIGLU_GU8, float32
+// SwiGLU in the epilogue): the dominant kernel of a float32-KV decode step keeps a name of its own in traces.
+__global__ __launch_bounds__(F32_NW * 64) void gemv_f32_gu8_kernel(F32Params p) {
+  __shared__ __attribute__((aligned(16))) float red[F32_TP * F32_NW * 32 * 4];
+  __shared__ float sq_sh[F32_NW * 8];
+  F32Body<true> b(p, red, sq_sh);
+  b.run();
+}
+
+}  // namespace
+
+// float32 activations without logical rounding, <= 8 rows, dense bf16 tile-major weights, no LoRA, no [hi | lo] walk;
+// plain / residual stores and SwiGLU on the row-interleaved gate|up copy (EPI_SWIGLU_GU8: W is that copy, out has
+// W.N / 2 columns).  EPI_SWIGLU on a plain gate|up matrix is NOT taken: the caller passes the interleaved copy.
+bool gemv_f32_supported(const LinearW& W, const GemvCall& c) {
+  if (c.force_v1 || W.layout != 1 || W.wk != WK_BF16) return false;
+  if (c.act != MI_F32 || c.rnd != RND_NONE || c.kx != 0) return false;
+  if (c.M < 1 || c.M > 8) return false;
+  if (W.lora_b[0] != nullptr || W.lora_b[1] != nullptr || c.lora_t != nullptr) return false;
+  if (W.K < 32 || W.K % 32 != 0 || W.N < 16 || W.N % 16 != 0 || c.ldx % 4 != 0) return false;
+  if (c.pro != PRO_NONE && (c.pro != PRO_NORM || c.norm_w == nullptr)) return false;
+  return c.epi == EPI_STORE || c.epi == EPI_STORE_F32 || c.epi == EPI_RESID || c.epi == EPI_SWIGLU_GU8;
+}
+
+int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st) {
+  if (!gemv_f32_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "gemv_f32: call not supported by this kernel");
+  F32Params p{};
+  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
+  p.pro = c.pro; p.norm_w = (const float*)c.norm_w; p.eps = c.eps;
+  p.w = W.w; p.N = W.N; p.K = W.K;
+  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
+  if (c.epi == EPI_RESID ? p.resid == nullptr : p.out == nullptr) return fail(MI_ERR_INVALID, "gemv_f32: output buffer missing");
+  const int nwg = std::min(W.N / 16, gemv_cu_count());     // one workgroup per CU; tiles are dealt in-kernel
+  if (c.epi == EPI_SWIGLU_GU8) hipLaunchKernelGGL(gemv_f32_gu8_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
+  else hipLaunchKernelGGL(gemv_f32_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+}  // namespace mi

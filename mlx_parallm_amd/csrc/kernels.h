@@ -94,6 +94,13 @@ int gemm_skinny_tile_groups(const LinearW& W, const GemvCall& c, size_t rows);
 int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr,
                        int ksplit = 0);
 
+// float32 activations (no logical rounding), <= 8 rows, dense bf16 tile-major weights (gemv_f32.hip): one pass over W, one
+// workgroup per CU, no K split, no workspace; RMSNorm (c.pro = PRO_NORM) deferred to the epilogue.  Epilogues: EPI_STORE /
+// EPI_STORE_F32 / EPI_RESID in float32, EPI_SWIGLU_GU8 on the row-interleaved gate|up copy (W = the copy).
+bool gemv_f32_supported(const LinearW& W, const GemvCall& c);
+int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st);
+int gemv_cu_count();            // compute units of the current device (gemv_mfma.hip)
+
 // int4 (group 64) weights, 17..128 rows of 16-bit activations (gemm_q4.hip): x prepared once per launch (fragment-major,
 // with the RMSNorm of c.pro = PRO_NORM applied there), K split over the waves of a workgroup.  launch_gemm_skinny routes
 // to it; `ws` >= gemm_q4_ws_bytes() (preparation buffers + partial tiles), `ctr` >= gemm_q4_groups() zeroed words.

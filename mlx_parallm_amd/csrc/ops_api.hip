@@ -80,6 +80,41 @@ int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters,
   return finish();
 }
 
+// gemv_f32.hip on its own: float32 activations (a->rnd = MI_RND_NONE), a->M in 1..8, dense bf16 tile-major weights; plain,
+// float32 and residual stores; a->pro may be MI_PRO_NORM (float32 norm weights).  MI_EPI_SWIGLU: w is a gate|up matrix of
+// 2 x a->pair_offset rows -- its row-interleaved copy is made here, as mi_engine_finalize does, and the launch runs on it.
+// iters >= 1 additionally times `iters` back-to-back launches.
+int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  LinearW W = to_linear(w);
+  GemvCall c = to_call(a);
+  void* gu8 = nullptr;
+  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } guard{gu8};
+  if (c.epi == EPI_SWIGLU) {
+    if (W.wk != WK_BF16 || W.layout != 1) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32: call not supported by this kernel");
+    MI_HIP(hipMalloc(&gu8, (size_t)W.N * W.K * sizeof(uint16_t)));
+    MI_TRY(launch_gate_up_interleave(W, c.pair_offset, gu8, nullptr));
+    W.w = gu8; c.epi = EPI_SWIGLU_GU8;
+  }
+  if (!gemv_f32_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32: call not supported by this kernel");
+  int rc = launch_gemv_f32(W, c, nullptr);
+  if (rc == MI_OK && iters >= 1 && avg_ms) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32(W, c, nullptr);
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  const int rc2 = finish();
+  return rc != MI_OK ? rc : rc2;
+}
+
 // gemm_skinny.hip on its own: a->M in 9..128 (int4 / int8: 1..128), a->pro must be MI_PRO_NONE; ksplit 0 = the cost model's choice
 // (*ksplit_used returns it); iters >= 1 additionally times `iters` back-to-back launches.  int4 weights above 16 rows with
 // ksplit <= 0 run gemm_q4.hip (a->pro may then be MI_PRO_NORM); ksplit < 0 forces its plan: -(mt | TW << 3 | KW << 7 | ksplit << 11 | NS << 15).
