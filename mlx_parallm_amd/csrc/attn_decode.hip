@@ -19,6 +19,22 @@
 
 namespace mi {
 
+// Debug build (tools/debug/build_trace_lib.sh): wall-clock stamps of the MFMA decode attention, one 16-slot row per workgroup in
+// a buffer of their own (gemm_skinny.hip owns it): 0 entry, 1 every load of the prologue has landed (the first round's K / V
+// were issued in front of them and return in order), 2 prologue barrier, 3 last MFMA, 4 partial stored, 5 end.
+#ifdef MI_SK_TRACE
+unsigned long long* dbg_trace_slot(int N, int K, int grid, int epi, int M, int kind, int pro, int act);   // gemm_skinny.hip
+#define AT_TRACE_PARAM , unsigned long long* trace
+#define AT_TRACE_ARG , trace
+#define AT_STAMP(i) do { if (trace != nullptr && threadIdx.x == 0) trace[(size_t)((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 16 + (i)] = wall_clock64(); } while (0)
+#define AT_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else
+#define AT_TRACE_PARAM
+#define AT_TRACE_ARG
+#define AT_STAMP(i) do { } while (0)
+#define AT_LANDED() do { } while (0)
+#endif
+
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -77,30 +93,19 @@ __device__ __forceinline__ void raw_to_f32(const uint32_t (&r)[NW32], float (&o)
 // for 4 splits), then merged in split order -- deterministic whoever arrived last.
 template <int D>
 __device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int d) {
-  float mn = -1e30f, L = 0.f, O = 0.f;
+  float mn = -1e30f, L = 0.f, O[1] = {0.f};
   for (int i0 = 0; i0 < nsplit; i0 += 4) {
-    float mv[4], lv[4], ov[4];
+    float mv[4], lv[4], ov[4][1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float* q = pp + (size_t)min(i0 + j, nsplit - 1) * (D + 2);
       mv[j] = __hip_atomic_load(&q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       lv[j] = __hip_atomic_load(&q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ov[j] = __hip_atomic_load(&q[2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ov[j][0] = __hip_atomic_load(&q[2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    float bm = mn;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (i0 + j < nsplit) bm = fmaxf(bm, mv[j]);
-    const float cs = __builtin_amdgcn_exp2f(mn - bm);
-    L *= cs; O *= cs; mn = bm;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i0 + j < nsplit) {
-        const float cw = __builtin_amdgcn_exp2f(mv[j] - mn);
-        L = fmaf(lv[j], cw, L);
-        O = fmaf(ov[j], cw, O);
-      }
+    merge_splits4<1>(mn, L, O, mv, lv, ov, nsplit - i0);     // (common.h: the same lines serve o_proj's staging)
   }
-  return O / L;
+  return merged_out(O[0], L);
 }
 
 // D must be a multiple of 32 for 16-bit caches (two elements per dword per lane); float caches any D % 16 == 0
@@ -464,8 +469,14 @@ __device__ __forceinline__ void store_out(T* p, T v) { *p = v; }
 // caches) against eight waves: removed in this commit; see git history.
 // float32 caches on two-term bf16 operands (three v_mfma_f32_16x16x32_bf16 per product) measured 1913 / 1907 against
 // 1998 / 1987 tok/s for the exact form below: removed in this commit; see git history.
-template <typename T, int D, int G, bool NORM, bool PAGED>
-__device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, unsigned char* smem) {
+// QS (consumer_combine seam 1, float32 only): the q / k_new / v_new vectors are not read from c.qkv -- the q|k|v linear ran
+// publish-only (gemm_skinny.hip, skinny_kernel<bf16_publish, ..>) and each lane group adds the K slices' partial rows of ITS vector here,
+// at the place of its one load, with the arithmetic of that linear's last arriver (common.h: add_slice, rs_from_sumsq,
+// scale_row).  Up to 8 slices, all fetched in one round trip behind the first round's K/V loads.
+template <typename T, int D, int G, bool NORM, bool PAGED, bool QS = false>
+__device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, unsigned char* smem AT_TRACE_PARAM) {
+  AT_STAMP(0);
+  static_assert(!QS || sizeof(T) == 4, "partial q|k|v rows: float32 activations");
   constexpr bool F32 = sizeof(T) == 4;           // float32 q / caches / outputs, multiplied exactly on v_mfma_f32_16x16x4_f32
   static_assert(D % 32 == 0 && D <= 128 && G <= 8 && (!F32 || D % 64 == 0), "16-bit caches: head_dim 32/64/96/128; float32: 64/128");
   constexpr int EPL = D / 16, NW32 = EPL * (int)sizeof(T) / 4, NTH = NWV * 64;
@@ -556,7 +567,22 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   const T* src = row + (is_q ? (size_t)(kh * G + vi) * D : is_k ? (size_t)nq + (size_t)kh * D
                                                                : (size_t)nq + (size_t)(s.Hkv + kh) * D) + li * EPL;
   uint32_t raw[NW32];
-  load_raw<NW32>(src, raw);
+  constexpr int QSN = QS ? 8 : 1;                // K slices fetched per lane group (host: qkv_ksplit <= 8)
+  f32x4 qs_p[QSN][QS ? EPL / 4 : 1];
+  float qs_sq[QSN];
+  if constexpr (QS) {                            // straight-line: a slice past the last re-loads the last
+    const size_t ld = (size_t)nq + 2 * (size_t)s.Hkv * D, col = (size_t)(src - row);
+#pragma unroll
+    for (int j = 0; j < QSN; ++j) {
+      const int sl = min(j, c.qkv_ksplit - 1);
+      const float* pp = c.qkv_pub + ((size_t)sl * 8 + b) * ld + col;
+#pragma unroll
+      for (int i = 0; i < EPL / 4; ++i) qs_p[j][i] = *(const f32x4*)(pp + 4 * i);
+      qs_sq[j] = c.qkv_pub_sq[sl * 8 + b];
+    }
+  } else {
+    load_raw<NW32>(src, raw);
+  }
   float cs[EPL], sn[EPL];
   {
     const float* cp = c.cos_tab + (size_t)pos * (D / 2) + (li & 7) * EPL;
@@ -570,6 +596,21 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   // between them; with one, hipcc allocates the body's registers differently.)
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_sched_barrier(0);
+  AT_LANDED();
+  AT_STAMP(1);
+  if constexpr (QS) {                            // the q|k|v linear's combine and epilogue: slices in order from zero, then x rs
+    float tot = 0.f;
+#pragma unroll
+    for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) tot = add_slice(tot, qs_sq[j]);
+    const float rs = rs_from_sumsq(tot, c.hidden_k, c.qkv_eps);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+      float a = 0.f;
+#pragma unroll
+      for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) a = add_slice(a, qs_p[j][e >> 2][e & 3]);
+      raw[e] = __float_as_uint(scale_row(a, rs));
+    }
+  }
   float x[EPL];
   raw_to_f32<T, EPL, NW32>(raw, x);
   if constexpr (NORM) {
@@ -617,6 +658,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   }
   const float sc2 = c.scale * LOG2E;
   __syncthreads();
+  AT_STAMP(2);
   if (wave == NWV - 1) {                         // scores of the new key: q_sh rows 0..G-1 against row G
     uint32_t kn[NW32];
 #pragma unroll
@@ -764,6 +806,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     }
   }
   }
+  AT_STAMP(3);
   // ---- this wave's (m, l, O) for the heads in columns c16 < G
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
@@ -807,7 +850,8 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
       }
     }
   }
-  if (c.nsplit == 1 || c.counters == nullptr) return;
+  AT_STAMP(4);
+  if (c.nsplit == 1 || c.counters == nullptr) { AT_STAMP(5); return; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
@@ -817,29 +861,63 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     is_last_sh = last;
   }
   __syncthreads();
-  if (!is_last_sh) return;
+  if (!is_last_sh) { AT_STAMP(5); return; }
   for (int idx = tid; idx < G * D; idx += NTH) {
     const int g = idx / D, d = idx % D, h = kh * G + g;
     const float* pp = c.partial + ((size_t)b * s.Hq + h) * c.nsplit * (D + 2);
     store_out<T>(&out[(size_t)h * D + d], store_act<T>(combine_splits<D>(pp, c.nsplit, d), c.rnd_out));
   }
+  AT_STAMP(5);
 }
 
 template <typename T, int D, int G, bool NORM, bool PAGED>
-__global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_kernel(AttnDecodeCall c) {
+__global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_kernel(AttnDecodeCall c AT_TRACE_PARAM) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  attn_decode_mfma_body<T, D, G, NORM, PAGED>(c, smem);
+  attn_decode_mfma_body<T, D, G, NORM, PAGED>(c, smem AT_TRACE_ARG);
+}
+
+// consumer_combine seam 1: the same launch with the q|k|v partial rows added in the prologue (a kernel of its own: the
+// ordinary instantiations keep their code and registers)
+template <int D, int G, bool NORM, bool PAGED>
+__global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_qs_kernel(AttnDecodeCall c AT_TRACE_PARAM) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn_decode_mfma_body<float, D, G, NORM, PAGED, true>(c, smem AT_TRACE_ARG);
 }
 
 template <typename T, int D, int G, bool NORM>
 int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   const dim3 grid(c.nsplit, s.B * s.Hkv);
+#ifdef MI_SK_TRACE
+  // record: N = Hq D, K = keys of row 0, epi = splits, kind -2 (-3: the q|k|v slices are added here), pro = 1 when a last arriver combines
+  unsigned long long* trace = dbg_trace_slot(s.Hq * D, c.n_host_off > 0 ? c.host_off[0] : 0, c.nsplit * s.B * s.Hkv, c.nsplit, s.B,
+                                             c.qkv_pub != nullptr ? -3 : -2, c.counters != nullptr ? 1 : 0, s.act);
+#endif
+  if (c.qkv_pub != nullptr) {
+    if constexpr (sizeof(T) == 4) {
+      if (c.qkv_pub_sq == nullptr || c.qkv_ksplit < 2 || c.qkv_ksplit > 8 || s.B > 8 || c.hidden_k <= 0)
+        return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need 2..8 K slices and at most 8 sequences");
+      constexpr size_t lds = attn_mfma_lds_bytes<G, D, 4>();
+      if (s.btab) {
+        auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, true>;
+        MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
+      } else {
+        auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, false>;
+        MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
+      }
+      MI_HIP(hipGetLastError());
+      return MI_OK;
+    } else {
+      return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need float32 activations");
+    }
+  }
 #define LAUNCH_MFMA(PG) do { \
     auto kern = attn_decode_mfma_kernel<T, D, G, NORM, PG>; \
     constexpr size_t lds = attn_mfma_lds_bytes<G, D, (int)sizeof(T)>(); \
     MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c); } while (0)
+    hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG); } while (0)
   if (s.btab) LAUNCH_MFMA(true); else LAUNCH_MFMA(false);
 #undef LAUNCH_MFMA
   MI_HIP(hipGetLastError());
@@ -869,6 +947,7 @@ int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
   if constexpr (attn_mfma_ok<T, D>()) {
     if (c.variant != 1) return launch_mfma_gn<T, D, NORM>(c, st);
   }
+  if (c.qkv_pub != nullptr) return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows are read by the float32 MFMA kernel only");
   const dim3 grid(c.nsplit, s.B * s.Hkv), block(512);
 #define DK(GV) do { if (s.btab) hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, true>), grid, block, 0, st, c); \
                     else hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, false>), grid, block, 0, st, c); } while (0)

@@ -113,6 +113,38 @@ __device__ __forceinline__ float lora_dot(const float* tt, const float* lb_col, 
   return z;
 }
 
+// ---- arithmetic shared by a producer's last arriver and by a consumer that combines while it loads ("consumer_combine",
+// DESIGN §8e): ONE definition per expression, so both sides give the same bits.  Nothing here can be contracted differently
+// at two call sites: the multiply-adds are explicit fmaf calls, a product is never followed by an add of its own result.
+//
+// Split-KV merge: up to four splits' (max, sum, O[0..NO)) folded into the running (mn, L, O), in split order.
+template <int NO>
+__device__ __forceinline__ void merge_splits4(float& mn, float& L, float (&O)[NO], const float (&mv)[4], const float (&lv)[4],
+                                              const float (&ov)[4][NO], int cnt) {
+  float bm = mn;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) if (j < cnt) bm = fmaxf(bm, mv[j]);
+  const float cs = __builtin_amdgcn_exp2f(mn - bm);
+  L *= cs;
+#pragma unroll
+  for (int e = 0; e < NO; ++e) O[e] *= cs;
+  mn = bm;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (j < cnt) {
+      const float cw = __builtin_amdgcn_exp2f(mv[j] - mn);
+      L = fmaf(lv[j], cw, L);
+#pragma unroll
+      for (int e = 0; e < NO; ++e) O[e] = fmaf(ov[j][e], cw, O[e]);
+    }
+}
+__device__ __forceinline__ float merged_out(float O, float L) { return O / L; }
+// Deferred RMSNorm of a K-split linear: the row scale from the slices' sums of squares (added in slice order by the caller),
+// and a K slice's partial added to the running sum (slice order, from zero), then the scale.
+__device__ __forceinline__ float rs_from_sumsq(float tot, int K, float eps) { return 1.0f / sqrtf(tot / (float)K + eps); }
+__device__ __forceinline__ float add_slice(float acc, float part) { return acc + part; }
+__device__ __forceinline__ float scale_row(float acc, float rs) { return acc * rs; }
+
 __device__ __forceinline__ float wave_sum(float v) {
   v = row16_sum(v);
   const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));

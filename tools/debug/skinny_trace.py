@@ -53,13 +53,15 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--out", default="gpurun_out/skinny_trace.bin")
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value, passed on to bench.py")
+    ap.add_argument("--attention-side", action="store_true",
+                    help="float32-KV step: one row per distinct stamped launch (q|k|v, decode attention, o, down), attention stamps included")
     args = ap.parse_args()
 
     import bench
 
     argv = ["--workload", args.workload, "--full", "--no-cpu-baseline", "--steps", str(args.steps), "--warmup", "2", "--batch", str(args.batch),
             "--no-prefill-timing"]
-    argv += ["--no-second-leg"] if args.kv == "model" else []
+    argv += ["--kv-dtype", args.kv, "--no-second-leg", "--no-other-configs"] if args.attention_side else ["--no-second-leg"] if args.kv == "model" else []
     for o in args.opt:
         argv += ["--opt", o]
     sys.argv = ["bench.py"] + argv
@@ -73,7 +75,82 @@ def main():
     rc = lib.mi_debug_sk_trace_dump(str(args.out).encode())
     if rc:
         raise SystemExit(f"dump failed: {rc}")
-    report(args.out, args.steps)
+    if args.attention_side:
+        report_attention_side(args.out, args.steps)
+    else:
+        report(args.out, args.steps)
+
+
+def report_attention_side(path, steps):
+    """The float32-KV decode step as the stamps see it: gate|up and lm_head run on gemv_f32.hip (no stamps), so a layer is
+    q|k|v -> decode attention -> o -> down.  One row per distinct launch signature over the last `steps` steps, in the order
+    of first appearance.  Linears: stage = entry -> first chunk staged, stream = the K slice, tail = last MFMA -> the
+    workgroup's last stamp (publish-only: its stores; otherwise publish / count and, for the last arriver, combine + epilogue).
+    Attention (kind -2; -3 = it adds the q|k|v slices): landed = entry -> every prologue load has arrived (the first round's
+    K / V are in front of them), prologue = -> the barrier behind norm / RoPE / append, rounds = -> last MFMA, store = -> the
+    partial (or the output) is stored, tail = -> end (ticket, and for the last arriver the combine).  All in us, means over
+    workgroups and launches; total = first entry -> last end of the launch; to_next = -> first entry of the next stamped launch."""
+    import numpy as np
+
+    recs = read_dump(path)
+    sig = lambda h: (h[7], h[1], h[2], h[3], h[4], h[5], h[8], h[11], h[6])   # kind, N, K, ksplit, grid, epi, pro, cc form, M
+    lin = lambda h: (h[7], h[1], h[3], h[4], h[5], h[8], h[11], h[6])          # attention: without K (the context grows per step)
+    key_of = lambda h: lin(h) if h[7] in (-2, -3) else sig(h)
+    last = key_of(recs[-1][0])
+    ends = [i for i, (h, _) in enumerate(recs) if key_of(h) == last]
+    per = ends[-1] - ends[-2]                                  # stamped launches per layer
+    layers = 0
+    for i in range(len(ends) - 1, 0, -1):                     # layers per step: the run of equal distances from the end
+        if ends[i] - ends[i - 1] != per:
+            break
+        layers += 1
+    layers += 1
+    n = min(len(recs), steps * layers * per)
+    sel = recs[len(recs) - n:]
+    print(f"{len(recs)} launches in the dump; {per} stamped launches per layer, ~{layers} layers per step; analysing the last {n}")
+    acc, order = defaultdict(lambda: defaultdict(list)), []
+    for j, (h, st) in enumerate(sel):
+        k = key_of(h)
+        if k not in acc:
+            order.append(k)
+        a = acc[k]
+        s0 = st[:, 0].min()
+        if h[7] in (-2, -3):
+            a["landed"].append(np.mean(st[:, 1] - st[:, 0]) * TICK_US)
+            a["prologue"].append(np.mean(st[:, 2] - st[:, 1]) * TICK_US)
+            a["rounds"].append(np.mean(st[:, 3] - st[:, 2]) * TICK_US)
+            a["store"].append(np.mean(st[:, 4] - st[:, 3]) * TICK_US)
+            a["tail"].append(np.mean(st[:, 5] - st[:, 4]) * TICK_US)
+            end = st[:, 5].max()
+        else:
+            a["stage"].append(np.mean(st[:, 2] - st[:, 0]) * TICK_US)
+            a["stream"].append(np.mean(st[:, 3] - st[:, 2]) * TICK_US)
+            if h[11] == 1:                                     # publish-only: stamp 4 is the workgroup's end
+                wg_end = st[:, 4]
+            elif h[3] > 1:                                     # split K: everyone reaches 5, the last arriver 6 and 7
+                lastm = (st[:, 7] >= st[:, 5]) & (st[:, 5] >= s0)
+                wg_end = np.where(lastm, st[:, 7], st[:, 5])
+            else:
+                wg_end = st[:, 7]
+            a["tail"].append(np.mean(wg_end - st[:, 3]) * TICK_US)
+            a["last_tail"].append((wg_end.max() - st[:, 3].max()) * TICK_US)
+            end = wg_end.max()
+        a["ramp"].append((st[:, 0].max() - s0) * TICK_US)
+        a["total"].append((end - s0) * TICK_US)
+        if j + 1 < len(sel):
+            a["to_next"].append((sel[j + 1][1][:, 0].min() - end) * TICK_US)
+    f = lambda a, c: f"{np.mean(a[c]):>9.2f}" if a[c] else f"{'-':>9}"
+    cols = ["ramp", "stage", "stream", "tail", "last_tail", "landed", "prologue", "rounds", "store", "total", "to_next"]
+    print(f"{'kind':>5}{'N':>7}{'K':>7}{'split':>6}{'grid':>6}{'pro':>4}{'cc':>3}{'M':>3}{'count':>7} " + " ".join(f"{c:>9}" for c in cols))
+    for k in order:
+        a = acc[k]
+        if k[0] in (-2, -3):
+            kind, N, ks, grid, epi, pro, cc, M = k
+            K = "-"
+            ks = epi
+        else:
+            kind, N, K, ks, grid, epi, pro, cc, M = k
+        print(f"{kind:>5}{N:>7}{K:>7}{ks:>6}{grid:>6}{pro:>4}{cc:>3}{M:>3}{len(a['total']):>7} " + " ".join(f(a, c) for c in cols))
 
 
 def report(path, steps):
