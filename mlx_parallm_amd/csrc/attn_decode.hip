@@ -21,18 +21,21 @@ namespace mi {
 
 // Debug build (tools/debug/build_trace_lib.sh): wall-clock stamps of the MFMA decode attention, one 16-slot row per workgroup in
 // a buffer of their own (gemm_skinny.hip owns it): 0 entry, 1 every load of the prologue has landed (the first round's K / V
-// were issued in front of them and return in order), 2 prologue barrier, 3 last MFMA, 4 partial stored, 5 end.
+// were issued in front of them and return in order), 2 prologue barrier, 3 last MFMA, 4 partial stored, 5 end;
+// 6 + r: wave 0 enters round r of a float32 cache (r <= 9).
 #ifdef MI_SK_TRACE
 unsigned long long* dbg_trace_slot(int N, int K, int grid, int epi, int M, int kind, int pro, int act);   // gemm_skinny.hip
 #define AT_TRACE_PARAM , unsigned long long* trace
 #define AT_TRACE_ARG , trace
 #define AT_STAMP(i) do { if (trace != nullptr && threadIdx.x == 0) trace[(size_t)((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 16 + (i)] = wall_clock64(); } while (0)
 #define AT_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define AT_STAMP_ROUND(r) AT_STAMP(6 + min((int)(r), 9))       // float32 caches: wave 0 enters round r (slots 6..15)
 #else
 #define AT_TRACE_PARAM
 #define AT_TRACE_ARG
 #define AT_STAMP(i) do { } while (0)
 #define AT_LANDED() do { } while (0)
+#define AT_STAMP_ROUND(r) do { } while (0)
 #endif
 
 namespace {
@@ -446,6 +449,16 @@ __host__ __device__ constexpr size_t attn_mfma_lds_bytes() {
   return attn_mfma_vimg_bytes<G, D, ES>() + (size_t)(G + 1) * D * ES + (size_t)(NWV + 1) * G * D * 4 + (size_t)2 * (NWV + 1) * G * 4 + 16;
 }
 
+// float32 caches, G <= 4 (the 16-block MFMA loop): behind the above, 16-byte aligned, per wave [4 heads][16 keys] softmax
+// numerators of the current tile + the 4 heads' correction factors (+ padding: 80 floats)
+constexpr int PBLK_FLOATS = 80;
+template <int G, int D, int ES>
+__host__ __device__ constexpr size_t attn_mfma_pblk_offset() { return (attn_mfma_lds_bytes<G, D, ES>() + 15) / 16 * 16; }
+template <int G, int D, int ES>
+__host__ __device__ constexpr size_t attn_mfma_lds_total() {
+  return ES == 4 && G <= 4 ? attn_mfma_pblk_offset<G, D, ES>() + (size_t)NWV * PBLK_FLOATS * 4 : attn_mfma_lds_bytes<G, D, ES>();
+}
+
 // float32 caches (the PagedKVCache mode, base.py:104-140): v_mfma_f32_16x16x4_f32 -- exact float32 products, one float per
 // lane and operand.  The MFMA k index and the row index of the A operand are free labellings, which lets every operand
 // come straight from 16-byte global loads with no LDS image and no transpose:
@@ -458,6 +471,15 @@ __host__ __device__ constexpr size_t attn_mfma_lds_bytes() {
 //     each of 4 rows; element e of that load is row c16 of the A tile (h, e), so output tile (h, e) row c16' = 4 g4 + reg
 //     is d = 64 h + 4 c16' + e.  D/4 MFMAs per key tile for each product (32 + 32 at D = 128, 32 cycles each).
 __device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 x 1 blocks, block = lane >> 2; acc[i] of lane 4 blk + j += a(lane 4 blk + i) * b(lane 4 blk + j)
+__device__ __forceinline__ f32x4 mfma_blk(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ float row16_max(float v) {
+  v = fmaxf(v, __builtin_amdgcn_update_dpp(v, v, 0x128, 0xf, 0xf, false));   // row_ror:8
+  v = fmaxf(v, __builtin_amdgcn_update_dpp(v, v, 0x124, 0xf, 0xf, false));   // row_ror:4
+  v = fmaxf(v, __builtin_amdgcn_update_dpp(v, v, 0x122, 0xf, 0xf, false));   // row_ror:2
+  v = fmaxf(v, __builtin_amdgcn_update_dpp(v, v, 0x121, 0xf, 0xf, false));   // row_ror:1
+  return v;
+}
 
 // (a call, not an assignment: the address is computed before the value, which the epilogue's schedule depends on)
 template <typename T>
@@ -483,6 +505,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   constexpr int KK = D / 32, DT = D / 16, NV = (32 * D * 2) / (64 * 16);   // K steps, 16-d tiles, 16-B V loads per lane
   constexpr int KPW = F32 ? 16 : 32;             // keys per wave and round
   constexpr int NP = D / 16, NH = D / 64 > 0 ? D / 64 : 1;   // float32: 16-byte K pieces per lane and tile, 64-d halves of a V row
+  constexpr bool BLK = F32 && G <= 4;            // float32, at most 4 query heads per kv head: the 16-block MFMA loop
   constexpr float LOG2E = 1.4426950408889634f;
   const AttnShape& s = c.s;
   const int split = blockIdx.x, bh = blockIdx.y;
@@ -496,7 +519,8 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   const int pos = c.n_host_off > 0 ? c.host_off[b] : c.offsets[kb];
   // the pos cached keys are cut evenly over the splits (a 1024-key context = 4 x 256 = one round each); the
   // new key is merged by the last split from registers / LDS
-  const int chunk = (pos + c.nsplit - 1) / c.nsplit;
+  // (float32: in whole 16-key tiles -- a wave's unit of work -- so that at most one split ends in a ragged tile)
+  const int chunk = F32 ? ((pos + 16 * c.nsplit - 1) / (16 * c.nsplit)) * 16 : (pos + c.nsplit - 1) / c.nsplit;
   const int s0 = split * chunk;
   const bool owner = split == c.nsplit - 1;
   const int nq = s.Hq * D;
@@ -684,8 +708,9 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   if constexpr (F32) {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      qf32[i] = *(const f32x4*)(q_sh + (size_t)(c16 < G ? c16 : 0) * D + 16 * i + 4 * g4);
-      if (c16 >= G) qf32[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int hq = BLK ? (c16 & 3) : c16;      // (16-block form: lane j of a block supplies head j)
+      qf32[i] = *(const f32x4*)(q_sh + (size_t)(hq < G ? hq : 0) * D + 16 * i + 4 * g4);
+      if (hq >= G) qf32[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   } else {
 #pragma unroll
@@ -695,20 +720,89 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     }
   }
 
-  // ---- rounds of 256 keys per workgroup
-  float m_run = -1e30f, l_run = 0.f;             // of head c16 (lanes c16 < G), over this lane group's keys
+  // ---- rounds of 256 keys per workgroup (float32 caches: 128)
+  // m_run / l_run: of head c16 (lanes c16 < G) over this lane group's keys; in the 16-block float32 loop (BLK) of head g4
+  // over the keys of this lane (key c16 of every tile)
+  float m_run = -1e30f, l_run = 0.f;
   f32x4 accO[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) accO[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (F32) {
-    for (int base = s0; base < send; base += KPW * NWV) {       // uniform trip count; 16 keys per wave and round
+  if constexpr (BLK) {
+    // v_mfma_f32_4x4x1_16b_f32: the G <= 4 heads fill the 4 rows of each of the 16 blocks, where the 16x16x4 form gives them 4 of
+    // its 16 columns -- a quarter of the matrix time per key tile, from the same loads (lane (c16, g4), block = lane >> 2):
+    //   * S = Q K^T: b = kf32[i][e] = K[key c16][16 i + 4 g4 + e], a = q[head c16 & 3][same d]: register h accumulates
+    //     (head h, key c16) over the quarter of d that lane group g4 owns.  The four groups then add their quarters so
+    //     that group g4 is left with head g4 (a reduce-scatter: 3 exchanges), and runs that head's online softmax over
+    //     the 16 keys of its row (DPP); m_run / l_run are head g4's (l_run: this lane's keys, summed over the row at the end).
+    //   * O = P V: b = vv32[r][h][e] = V[key 4 g4 + r][64 h + 4 c16 + e], a = P[head c16 & 3][key 4 g4 + r].  P[head g4][key c16]
+    //     is in lane (c16, g4), so it goes through 256 B of LDS of the wave's own, with the four correction factors behind
+    //     it: one 4-byte write and two 16-byte reads per lane and tile.  Only this wave touches them (DS operations of a
+    //     wave execute in order): no workgroup barrier.  Register i of accO[4 h + e] = O[head i][64 h + 4 c16 + e] over
+    //     the keys of group g4; the groups are added once behind the loop.
+    // The trip count is the wave's own, as below.
+    float* p_sh = (float*)(smem + attn_mfma_pblk_offset<G, D, 4>()) + wave * PBLK_FLOATS;
+    const bool gb0 = (g4 & 1) != 0, gb1 = (g4 & 2) != 0;
+    for (int base = s0; base + KPW * wave < send; base += KPW * NWV) {
+      const bool more = base + KPW * NWV + KPW * wave < send;
+      AT_STAMP_ROUND((base - s0) / (KPW * NWV));
+      f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};          // two chains: the dependent latency is hidden
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        sa = mfma_blk(qf32[i][0], kf32[i][0], sa);
+        sb = mfma_blk(qf32[i][1], kf32[i][1], sb);
+        sa = mfma_blk(qf32[i][2], kf32[i][2], sa);
+        sb = mfma_blk(qf32[i][3], kf32[i][3], sb);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) issue_k(base + KPW * NWV);
+      __builtin_amdgcn_sched_barrier(0);
+      const f32x4 sc = sa + sb;
+      // groups {0, 1} keep heads {0, 1} and receive them from groups {2, 3}, and vice versa; then the same inside each pair
+      float k0v = gb1 ? sc[2] : sc[0], k1v = gb1 ? sc[3] : sc[1];
+      k0v += __shfl_xor(gb1 ? sc[0] : sc[2], 32, 64);
+      k1v += __shfl_xor(gb1 ? sc[1] : sc[3], 32, 64);
+      float sv = (gb0 ? k1v : k0v) + __shfl_xor(gb0 ? k0v : k1v, 16, 64);   // (head g4, key c16), all of d
+      sv = (base + KPW * wave + c16) < send ? sv * sc2 : -INFINITY;
+      const float mn = fmaxf(m_run, row16_max(sv));
+      const float corr = __builtin_amdgcn_exp2f(m_run - mn);
+      const float pv = __builtin_amdgcn_exp2f(sv - mn);
+      m_run = mn;
+      l_run = l_run * corr + pv;
+      p_sh[16 * g4 + c16] = pv;
+      if (c16 == 0) p_sh[64 + g4] = corr;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const f32x4 pa = *(const f32x4*)(p_sh + 16 * (c16 & 3) + 4 * g4);
+      const f32x4 cr = *(const f32x4*)(p_sh + 64);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) accO[dt] *= cr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) accO[h * 4 + e] = mfma_blk(pa[r], vv32[r][h][e], accO[h * 4 + e]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) issue_v(base + KPW * NWV);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (F32) {
+    // 16 keys per wave and round.  The trip count is the wave's own: nothing in the loop crosses waves, and a wave whose
+    // keys are exhausted neither loads nor multiplies for the others' last round (it would add p = 0 under a correction
+    // of 1: skipping is bit-identical; a wave with no keys at all merges as (-1e30, 0, 0)).
+    for (int base = s0; base + KPW * wave < send; base += KPW * NWV) {
+      const bool more = base + KPW * NWV + KPW * wave < send;   // wave-uniform: no prefetch of a round that is not computed
+      AT_STAMP_ROUND((base - s0) / (KPW * NWV));
       f32x4 sc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < NP; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) sc = mfma_f32(kf32[i][e], qf32[i][e], sc);
       __builtin_amdgcn_sched_barrier(0);
-      issue_k(base + KPW * NWV);                 // rolling prefetch: the next round's K into the registers just consumed
+      if (more) issue_k(base + KPW * NWV);       // rolling prefetch: the next round's K into the registers just consumed
       __builtin_amdgcn_sched_barrier(0);
       const int k0 = base + KPW * wave;
       float mx = -1e30f;
@@ -736,7 +830,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
 #pragma unroll
           for (int e = 0; e < 4; ++e) accO[h * 4 + e] = mfma_f32(vv32[r][h][e], p[r], accO[h * 4 + e]);
       __builtin_amdgcn_sched_barrier(0);
-      issue_v(base + KPW * NWV);                 // ... and the next round's V rows
+      if (more) issue_v(base + KPW * NWV);       // ... and the next round's V rows
       __builtin_amdgcn_sched_barrier(0);
     }
   } else {
@@ -808,6 +902,27 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   }
   AT_STAMP(3);
   // ---- this wave's (m, l, O) for the heads in columns c16 < G
+  if constexpr (BLK) {
+    // the same reduce-scatter over the lane groups for O: group g4 is left with O[head g4][64 h + 4 c16 + e], 16 bytes per h
+    const bool gb0 = (g4 & 1) != 0, gb1 = (g4 & 2) != 0;
+    l_run = row16_sum(l_run);
+    f32x4 oh[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const f32x4 a = accO[h * 4 + e];
+        float k0v = gb1 ? a[2] : a[0], k1v = gb1 ? a[3] : a[1];
+        k0v += __shfl_xor(gb1 ? a[0] : a[2], 32, 64);
+        k1v += __shfl_xor(gb1 ? a[1] : a[3], 32, 64);
+        oh[h][e] = (gb0 ? k1v : k0v) + __shfl_xor(gb0 ? k0v : k1v, 16, 64);
+      }
+    if (g4 < G) {
+      if (c16 == 0) { st_m[wave * G + g4] = m_run; st_l[wave * G + g4] = l_run; }
+#pragma unroll
+      for (int h = 0; h < NH; ++h) *(f32x4*)(st_o + (size_t)(wave * G + g4) * D + 64 * h + 4 * c16) = oh[h];
+    }
+  } else {
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
   if (c16 < G) {
@@ -823,6 +938,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
 #pragma unroll
         for (int r = 0; r < 4; ++r) st_o[(wave * G + c16) * D + 16 * dt + 4 * g4 + r] = accO[dt][r];
     }
+  }
   }
   __syncthreads();
   T* out = (T*)c.out + (size_t)b * nq;
@@ -897,7 +1013,7 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
     if constexpr (sizeof(T) == 4) {
       if (c.qkv_pub_sq == nullptr || c.qkv_ksplit < 2 || c.qkv_ksplit > 8 || s.B > 8 || c.hidden_k <= 0)
         return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need 2..8 K slices and at most 8 sequences");
-      constexpr size_t lds = attn_mfma_lds_bytes<G, D, 4>();
+      constexpr size_t lds = attn_mfma_lds_total<G, D, 4>();
       if (s.btab) {
         auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, true>;
         MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -915,7 +1031,7 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
   }
 #define LAUNCH_MFMA(PG) do { \
     auto kern = attn_decode_mfma_kernel<T, D, G, NORM, PG>; \
-    constexpr size_t lds = attn_mfma_lds_bytes<G, D, (int)sizeof(T)>(); \
+    constexpr size_t lds = attn_mfma_lds_total<G, D, (int)sizeof(T)>(); \
     MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG); } while (0)
   if (s.btab) LAUNCH_MFMA(true); else LAUNCH_MFMA(false);
@@ -933,12 +1049,13 @@ int launch_mfma_gn(const AttnDecodeCall& c, hipStream_t st) {
     switch (c.s.Hq / c.s.Hkv) {
       case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
       case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
+      case 3: if constexpr (sizeof(T) == 4) return launch_mfma_g<T, D, 3, NORM>(c, st); else break;   // (float32 caches only)
       case 4: return launch_mfma_g<T, D, 4, NORM>(c, st);
       case 5: return launch_mfma_g<T, D, 5, NORM>(c, st);
       case 8: return launch_mfma_g<T, D, 8, NORM>(c, st);
     }
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8");
+  return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8 (3: float32 caches, head_dim 64 / 128, matrix-core kernel only)");
 }
 
 template <typename T, int D, bool NORM>
@@ -957,7 +1074,7 @@ int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
     case 4: DK(4); break;
     case 5: DK(5); break;
     case 8: DK(8); break;
-    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8");
+    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8 (3: float32 caches, head_dim 64 / 128, matrix-core kernel only)");
   }
 #undef DK
   MI_HIP(hipGetLastError());
@@ -984,9 +1101,12 @@ int launch_d(const AttnDecodeCall& c, hipStream_t st) {
 
 }  // namespace
 
-bool attention_decode_supported(const AttnShape& s) {
+bool attention_decode_supported(const AttnShape& s, int variant) {
   if (s.L != 1 || s.act != s.kv) return false;
   const int G = s.Hkv > 0 ? s.Hq / s.Hkv : 0;
+  // G = 3: the float32 matrix-core kernel (variant 0) alone has it (no VALU, prefill or unfused kernel takes it: the geometry
+  // is reachable through mi_op_attention_decode only, not through a model)
+  if (G == 3) return variant != 1 && s.act == MI_F32 && (s.D == 64 || s.D == 128);
   if (!(G == 1 || G == 2 || G == 4 || G == 5 || G == 8)) return false;
   if (s.act == MI_F32) return s.D == 16 || s.D == 32 || s.D == 64 || s.D == 128;
   return s.D == 32 || s.D == 64 || s.D == 128;
@@ -994,7 +1114,7 @@ bool attention_decode_supported(const AttnShape& s) {
 
 int launch_attention_decode(const AttnDecodeCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
-  if (!attention_decode_supported(s)) return fail(MI_ERR_UNSUPPORTED, "attention_decode: shape / dtype not supported");
+  if (!attention_decode_supported(s, c.variant)) return fail(MI_ERR_UNSUPPORTED, "attention_decode: shape / dtype not supported by this variant");
   if (c.nsplit < 1 || (c.nsplit > 1 && c.partial == nullptr))
     return fail(MI_ERR_INVALID, "attention_decode: bad split configuration");
   if (s.act == MI_F32) return launch_d<float>(c, st);

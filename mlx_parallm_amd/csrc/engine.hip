@@ -717,6 +717,17 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   if (L != 1) return 1;
   int mx = 0;
   for (int b = 0; b < B; ++b) mx = std::max(mx, kv->h_off[rows ? rows[b] : b] + 1);
+  // float32 caches, at most one (sequence, kv head) pair per CU: the largest split count whose workgroups fit the CUs in one
+  // wave, with at least 64 keys per split up to 8 splits and at least 128 beyond, and no step-down.  From tools/bench_attn.py
+  // --kv float32 (Mistral-7B heads, B = 1 .. 6, 8, 16, 32, KV 256 .. 4096, 1 .. 16 splits): a launch of more
+  // workgroups than CUs falls off a cliff (B = 8, KV 1060: 4 splits 17.4 us, 5 splits 24.3; B = 3: 10 splits 12.2, 11 splits
+  // = 264 workgroups 15.8; B = 8, KV 4097: 4 splits 45.4, the 5 that the 1024-key limit below asks for 59.0); up to the CU
+  // count the stepped-down count is nowhere faster and 0.5 - 1.0 us slower at KV 256 .. 1060 (the waves walk their own
+  // keys and the splits are cut in whole tiles -- attn_decode.hip -- so a short last round costs two or three waves a tile
+  // each, not all eight a round); sixteen 69-key splits are 1.2 us slower than eight (B = 2, KV 1060: the merge).
+  const int cus = gemv_cu_count();
+  if (kv->dtype == MI_F32 && B * Hkv <= cus)
+    return std::max(1, std::min({cus / (B * Hkv), std::max(std::min(mx / 64, 8), mx / 128), 16}));
   int ns = (256 + B * Hkv - 1) / (B * Hkv);
   ns = std::min(ns, std::max(1, mx / 64));
   // long contexts: at most four 256-key rounds per workgroup -- eight when the batch alone fills the CUs (every extra
@@ -725,8 +736,8 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   ns = std::max(ns, (mx + per_wg - 1) / per_wg);
   ns = std::max(1, std::min(ns, 16));
   // a workgroup walks its keys in rounds of 256 (float32 caches: 128): the smallest split count with the SAME number of
-  // rounds has fewer workgroups to start and fewer partials to merge (KV length 1100, B = 8: 4 -> 3 splits, float32-KV
-  // 1968 -> 1995 tok/s, bf16 2238 -> 2252; more splits are slower: 5 / 6 / 8 splits 2175 / 2173 / 2155)
+  // rounds has fewer workgroups to start and fewer partials to merge (KV length 1100, B = 8, bf16: 4 -> 3 splits, 2238 ->
+  // 2252 tok/s; more splits are slower: 5 / 6 / 8 splits 2175 / 2173 / 2155)
   const int rk = kv->dtype == MI_F32 ? 128 : 256;
   auto rounds = [&](int n) { return ((mx - 1 + n - 1) / n + rk - 1) / rk; };     // (the cached keys; the new one is merged from registers)
   const int r0 = rounds(ns);
@@ -875,7 +886,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
       const void* qkv_g = (const char*)e->qkv + g.tok0 * (size_t)nqkv * es;
       void* q_g = (char*)e->q + g.tok0 * (size_t)Hq * D * es;
       void* o_g = (char*)e->attn + g.tok0 * (size_t)Hq * D * es;
-      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
+      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s, e->opt_attn_mfma ? 0 : 1)) {
         // decode: norm + RoPE + append + attention + split combine in one launch
         AttnDecodeCall ac{s, qkv_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
                           o_g, 1.0f / sqrtf((float)D), RND_NONE, nsplit[gi], kv->partial, kv->counters,

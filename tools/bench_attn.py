@@ -13,7 +13,7 @@ import torch
 from mlx_parallm_amd import _lib as L
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=1024)
@@ -25,22 +25,24 @@ def main():
     ap.add_argument("--splits", default="1,2,4,8,16")
     ap.add_argument("--variant", type=int, default=0, help="0: MFMA kernel, 1: VALU kernel")
     ap.add_argument("--no-combine", type=int, default=0, help="timing experiment: skip the ticket/combine tail")
-    a = ap.parse_args()
+    ap.add_argument("--kv", default="bfloat16", choices=["bfloat16", "float32"], help="element type of q|k|v, the caches and the output")
+    a = ap.parse_args(argv)
     B, S, Hq, Hkv, D = a.B, a.S, a.Hq, a.Hkv, a.D
     cap = S + 64
     dev = "cuda"
-    kcs = [torch.randn((B, Hkv, cap, D), device=dev, dtype=torch.float32).to(torch.bfloat16) for _ in range(a.layers)]
-    vcs = [torch.randn((B, Hkv, cap, D), device=dev, dtype=torch.float32).to(torch.bfloat16) for _ in range(a.layers)]
-    qkv = torch.randn((B, (Hq + 2 * Hkv) * D), device=dev, dtype=torch.float32).to(torch.bfloat16)
-    out = torch.zeros((B, Hq * D), device=dev, dtype=torch.bfloat16)
+    dt, mi_dt = (torch.float32, L.MI_F32) if a.kv == "float32" else (torch.bfloat16, L.MI_BF16)
+    kcs = [torch.randn((B, Hkv, cap, D), device=dev, dtype=torch.float32).to(dt) for _ in range(a.layers)]
+    vcs = [torch.randn((B, Hkv, cap, D), device=dev, dtype=torch.float32).to(dt) for _ in range(a.layers)]
+    qkv = torch.randn((B, (Hq + 2 * Hkv) * D), device=dev, dtype=torch.float32).to(dt)
+    out = torch.zeros((B, Hq * D), device=dev, dtype=dt)
     offs = torch.full((B,), S, device=dev, dtype=torch.int32)
     cos = torch.zeros((cap + 1, D // 2), device=dev, dtype=torch.float32)
     sin = torch.zeros_like(cos)
     torch.cuda.synchronize()
     L.check(L.lib().mi_op_rope_tables(C.c_void_p(cos.data_ptr()), C.c_void_p(sin.data_ptr()), cap + 1, D, 1e4, 1.0))
     sh = L.OpAttnShape()
-    sh.B, sh.L, sh.Hq, sh.Hkv, sh.D, sh.act, sh.kv, sh.rnd, sh.cap = B, 1, Hq, Hkv, D, L.MI_BF16, L.MI_BF16, 0, cap
-    kv_bytes = B * Hkv * (S + 1) * D * 2 * 2
+    sh.B, sh.L, sh.Hq, sh.Hkv, sh.D, sh.act, sh.kv, sh.rnd, sh.cap = B, 1, Hq, Hkv, D, mi_dt, mi_dt, 0, cap
+    kv_bytes = B * Hkv * (S + 1) * D * 2 * kcs[0].element_size()
     for ns in [int(x) for x in a.splits.split(",")]:
         part = torch.zeros((B * Hq * ns * (D + 2),), device=dev, dtype=torch.float32)
         ctr = torch.zeros((B * Hkv,), device=dev, dtype=torch.int32)

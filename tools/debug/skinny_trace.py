@@ -88,8 +88,9 @@ def report_attention_side(path, steps):
     workgroup's last stamp (publish-only: its stores; otherwise publish / count and, for the last arriver, combine + epilogue).
     Attention (kind -2; -3 = it adds the q|k|v slices): landed = entry -> every prologue load has arrived (the first round's
     K / V are in front of them), prologue = -> the barrier behind norm / RoPE / append, rounds = -> last MFMA, store = -> the
-    partial (or the output) is stored, tail = -> end (ticket, and for the last arriver the combine).  All in us, means over
-    workgroups and launches; total = first entry -> last end of the launch; to_next = -> first entry of the next stamped launch."""
+    partial (or the output) is stored, tail = -> end (ticket, and for the last arriver the combine).  A second table gives each
+    attention launch's stamps, one per round of a float32 cache included, for the median workgroup and for the one that
+    ends last.  All in us, means over workgroups and launches; total = first entry -> last end of the launch; to_next = -> first entry of the next stamped launch."""
     import numpy as np
 
     recs = read_dump(path)
@@ -122,6 +123,22 @@ def report_attention_side(path, steps):
             a["store"].append(np.mean(st[:, 4] - st[:, 3]) * TICK_US)
             a["tail"].append(np.mean(st[:, 5] - st[:, 4]) * TICK_US)
             end = st[:, 5].max()
+            # the workgroup's own timeline, from its entry: median workgroup and the one that ends last.  Round stamps
+            # (6 + r, float32 caches) are wave 0's; a slot the launch did not write holds an older launch's stamp.
+            rel = (st - st[:, :1]) * TICK_US
+            lastwg = int(np.argmax(st[:, 5]))
+            pts = [("landed", 1), ("barrier", 2)] + [(f"round{r}", 6 + r) for r in range(10)] + [("last_mfma", 3), ("stored", 4), ("end", 5)]
+            for name, col in pts:
+                okm = (st[:, col] >= st[:, 0]) & (st[:, col] <= st[:, 5])
+                if col >= 6 and okm.sum() * 2 < len(okm):                  # a round that fewer than half of the workgroups reach
+                    if okm[lastwg]:
+                        a["tl_last_" + name].append(rel[lastwg, col])
+                    continue
+                a["tl_med_" + name].append(float(np.median(rel[okm, col])))
+                if okm[lastwg]:
+                    a["tl_last_" + name].append(rel[lastwg, col])
+            a["tl_last_entry"].append((st[lastwg, 0] - s0) * TICK_US)
+            a["tl_med_entry"].append(float(np.median(st[:, 0] - s0)) * TICK_US)
         else:
             a["stage"].append(np.mean(st[:, 2] - st[:, 0]) * TICK_US)
             a["stream"].append(np.mean(st[:, 3] - st[:, 2]) * TICK_US)
@@ -151,6 +168,16 @@ def report_attention_side(path, steps):
         else:
             kind, N, K, ks, grid, epi, pro, cc, M = k
         print(f"{kind:>5}{N:>7}{K:>7}{ks:>6}{grid:>6}{pro:>4}{cc:>3}{M:>3}{len(a['total']):>7} " + " ".join(f(a, c) for c in cols))
+    for k in order:
+        if k[0] not in (-2, -3):
+            continue
+        a = acc[k]
+        names = ["entry", "landed", "barrier"] + [f"round{r}" for r in range(10)] + ["last_mfma", "stored", "end"]
+        names = [n for n in names if a["tl_med_" + n] or a["tl_last_" + n]]
+        print(f"attention kind {k[0]}, {k[4]} splits, grid {k[3]}: a workgroup's stamps in us from its own entry (entry: from the launch's first entry)")
+        print(f"{'':>10} " + " ".join(f"{n:>9}" for n in names))
+        print(f"{'median wg':>10} " + " ".join(f(a, "tl_med_" + n) for n in names))
+        print(f"{'last wg':>10} " + " ".join(f(a, "tl_last_" + n) for n in names))
 
 
 def report(path, steps):
