@@ -232,14 +232,13 @@ int mi_profile_read(mi_engine* e, int64_t* n_launches, double* total_ms);
  *                             staging of the next (default 1)
  *   "defer_norm"              0: float32-activation (PagedKVCache mode) decode steps run the RMSNorm as its own launch
  *                             instead of applying its row scale in the epilogue of the linear behind it (default 1)
- *   "consumer_combine"        bit mask for float32-KV decode steps of one group of <= 8 rows on dense bf16 weights without LoRA
- *                             (everything else runs as with 0; outputs are bit-identical for every value):
+ *   "consumer_combine"        0 / 1, for float32-KV decode steps of one group of <= 8 rows on dense bf16 weights without LoRA
+ *                             (everything else runs as with 0; outputs are bit-identical):
  *                             1: the q|k|v linear publishes its K slices' partial rows and ends; the decode attention's
- *                                prologue adds them (slice order) and applies the RMSNorm row scale;
- *                             2: the decode attention publishes its split partials and ends; o_proj merges them while it
- *                                stages its activations (measured slower: off).  0: the last workgroup to arrive
- *                                combines inside each launch.  Default 1.
- *   "consumer_combine_guard"  (a check, the value is ignored) MI_OK when the sentinels around the buffer of seam 1 are
+ *                                prologue adds them (slice order) and applies the RMSNorm row scale (default);
+ *                             0: the last workgroup to arrive combines inside the linear's launch.
+ *                             Any other value: MI_ERR_INVALID, the option keeps its value.
+ *   "consumer_combine_guard"  (a check, the value is ignored) MI_OK when the sentinels around the buffer of the q|k|v seam are
  *                             intact, MI_ERR_NOTFOUND when that seam has not run yet, MI_ERR_RUNTIME when one was overwritten
  *   "prefill_x_terms"         3: float32-activation (PagedKVCache mode) prefill multiplies an EXACT three-term 16-bit split of x
  *                             by dense bf16 weights (three walks of W); default 2: hi + lo, 16+ mantissa bits of x, two walks

@@ -106,7 +106,7 @@ __device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int
       lv[j] = __hip_atomic_load(&q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ov[j][0] = __hip_atomic_load(&q[2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    merge_splits4<1>(mn, L, O, mv, lv, ov, nsplit - i0);     // (common.h: the same lines serve o_proj's staging)
+    merge_splits4<1>(mn, L, O, mv, lv, ov, nsplit - i0);
   }
   return merged_out(O[0], L);
 }
@@ -491,7 +491,7 @@ __device__ __forceinline__ void store_out(T* p, T v) { *p = v; }
 // caches) against eight waves: removed in this commit; see git history.
 // float32 caches on two-term bf16 operands (three v_mfma_f32_16x16x32_bf16 per product) measured 1913 / 1907 against
 // 1998 / 1987 tok/s for the exact form below: removed in this commit; see git history.
-// QS (consumer_combine seam 1, float32 only): the q / k_new / v_new vectors are not read from c.qkv -- the q|k|v linear ran
+// QS (consumer_combine, float32 only): the q / k_new / v_new vectors are not read from c.qkv -- the q|k|v linear ran
 // publish-only (gemm_skinny.hip, skinny_kernel<bf16_publish, ..>) and each lane group adds the K slices' partial rows of ITS vector here,
 // at the place of its one load, with the arithmetic of that linear's last arriver (common.h: add_slice, rs_from_sumsq,
 // scale_row).  Up to 8 slices, all fetched in one round trip behind the first round's K/V loads.
@@ -992,7 +992,7 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_kernel(AttnDecodeCa
   attn_decode_mfma_body<T, D, G, NORM, PAGED>(c, smem AT_TRACE_ARG);
 }
 
-// consumer_combine seam 1: the same launch with the q|k|v partial rows added in the prologue (a kernel of its own: the
+// consumer_combine: the same launch with the q|k|v partial rows added in the prologue (a kernel of its own: the
 // ordinary instantiations keep their code and registers)
 template <int D, int G, bool NORM, bool PAGED>
 __global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_qs_kernel(AttnDecodeCall c AT_TRACE_PARAM) {

@@ -117,7 +117,8 @@ __device__ __forceinline__ float lora_dot(const float* tt, const float* lb_col, 
 // DESIGN §8e): ONE definition per expression, so both sides give the same bits.  Nothing here can be contracted differently
 // at two call sites: the multiply-adds are explicit fmaf calls, a product is never followed by an add of its own result.
 //
-// Split-KV merge: up to four splits' (max, sum, O[0..NO)) folded into the running (mn, L, O), in split order.
+// Split-KV merge (the decode attention's last arriver, combine_splits): up to four splits' (max, sum, O[0..NO)) folded into
+// the running (mn, L, O), in split order.
 template <int NO>
 __device__ __forceinline__ void merge_splits4(float& mn, float& L, float (&O)[NO], const float (&mv)[4], const float (&lv)[4],
                                               const float (&ov)[4][NO], int cnt) {

@@ -120,13 +120,10 @@ struct mi_engine {
   int opt_prefill_x_terms = 2;  // float32 activations, prefill tile GEMM on dense bf16 weights: 16-bit terms of x (2 or 3 = exact)
   int opt_defer_norm = 1;       // float32 activations: RMSNorm row scale applied in the split-K kernel's epilogue (no norm launch)
   int opt_short_prefill_skinny = 1;   // short prefill / mixed calls on the weight-streaming kernel instead of the tile GEMM (gemv_rows)
-  // consumer_combine, a bit mask: 1 = the q|k|v linear of a float32-KV decode step publishes its K slices'
-  // partial rows and the decode attention's prologue adds them; 2 = the decode attention publishes its split partials and
-  // o_proj merges them while it stages x.  0 = the last arriver of every launch combines, as before.  Bit-identical outputs.
-  // Measured (Mistral-7B bf16, B = 8, KV 1024 -> 1100, five alternating runs per setting, ms per step): 0 3.807, 1 3.748,
-  // 2 3.860, 3 3.810 against 3.814 for the commit before (spread 0.010): seam 1 is on, seam 2 stays an option (§8e).
+  // the q|k|v linear of a float32-KV decode step publishes its K slices' partial rows and the decode attention's prologue
+  // adds them (0: the linear's last arriver combines).  Bit-identical outputs; measurements and history: DESIGN §8e
   int opt_consumer_combine = 1;
-  float* cc_pub = nullptr; size_t cc_pub_floats = 0;   // seam 1: [guard][8 slices][8 rows][nqkv][guard][8 slices][8 rows][guard]
+  float* cc_pub = nullptr; size_t cc_pub_floats = 0;   // the q|k|v seam: [guard][8 slices][8 rows][nqkv][guard][8 slices][8 rows][guard]
   float* d_sq = nullptr;        // [4096 tile groups][16 rows]
   bool sq_valid = false; const void* sq_src = nullptr; int sq_parts = 0, sq_K = 0, sq_ld = 0;
   bool opt_gu8 = true;                   // decode GEMV of a dense gate|up matrix on its row-interleaved copy: 7 one-tile items per CU instead of 3.5 pairs (twice the matrix's bytes)
@@ -397,11 +394,44 @@ int norm_into_xn(mi_engine* e, GemvCall& c, size_t rows, int K, int rnd) {
   return MI_OK;
 }
 
-// y = W x for `rows` rows, split into launches of at most 16 (MFMA) / 8 (generic) rows
+constexpr size_t CC_GUARD = 64;                  // floats of sentinel around each part of the seam's buffer
+constexpr uint32_t CC_SENTINEL = 0x7fc0c0c0u;    // (a NaN: a read of it would not go unnoticed either)
+int ensure_cc_pub(mi_engine* e, int nqkv) {
+  const size_t need = 3 * CC_GUARD + (size_t)8 * 8 * nqkv + 8 * 8;
+  if (e->cc_pub != nullptr && e->cc_pub_floats >= need) return MI_OK;
+  MI_HIP(hipStreamSynchronize(e->stream));
+  hipFree(e->cc_pub); e->cc_pub = nullptr; e->cc_pub_floats = 0;
+  MI_HIP(hipMalloc(&e->cc_pub, need * sizeof(float)));
+  std::vector<uint32_t> fill(need, CC_SENTINEL);
+  MI_HIP(hipMemcpy(e->cc_pub, fill.data(), need * sizeof(float), hipMemcpyHostToDevice));
+  e->cc_pub_floats = need;
+  return MI_OK;
+}
+// the three sentinel runs of the seam's buffer (option "consumer_combine_guard"): intact -> MI_OK
+int check_cc_guards(mi_engine* e, int nqkv) {
+  if (e->cc_pub == nullptr) return fail(MI_ERR_NOTFOUND, "consumer_combine_guard: the q|k|v seam has not run");
+  MI_HIP(hipStreamSynchronize(e->stream));
+  const size_t body = (size_t)8 * 8 * nqkv, at[3] = {0, CC_GUARD + body, 2 * CC_GUARD + body + 64};
+  uint32_t g[CC_GUARD];
+  for (int i = 0; i < 3; ++i) {
+    MI_HIP(hipMemcpy(g, e->cc_pub + at[i], sizeof(g), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < CC_GUARD; ++j)
+      if (g[j] != CC_SENTINEL) return fail(MI_ERR_RUNTIME, "consumer_combine_guard: sentinel run " + std::to_string(i) + " was overwritten");
+  }
+  return MI_OK;
+}
+float* cc_pub_tiles(mi_engine* e) { return e->cc_pub + CC_GUARD; }                                     // [8 slices][8 rows][nqkv]
+float* cc_pub_sumsq(mi_engine* e, int nqkv) { return e->cc_pub + 2 * CC_GUARD + (size_t)8 * 8 * nqkv; }   // [8 slices][8 rows]
+
+// y = W x for `rows` rows, split into launches of at most 16 (MFMA) / 8 (generic) rows.
+// consumer_combine: `published` != null is an OFFER of the caller's -- "the next launch can add K slices published in the
+// seam buffer instead of reading c.out".  The router takes it on the one route whose kernel has the publish-only form, and
+// *published = the number of K slices it left there (0: declined, the ordinary launch wrote c.out).
 int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, GemvCall c, size_t rows, size_t es_in, size_t es_out,
-                 const char* prof, bool sq_was_valid);
+                 const char* prof, bool sq_was_valid, int* published);
 int gemv_rows(mi_engine* e, const FusedLinear& f0, GemvCall c, size_t rows, size_t es_in, size_t es_out,
-              const char* prof) {
+              const char* prof, int* published = nullptr) {
+  if (published != nullptr) *published = 0;
   c.force_v1 = e->opt_force_v1;
   const bool sq_was_valid = e->sq_valid;      // whatever runs now consumes or invalidates the hand-over
   e->sq_valid = false;
@@ -414,15 +444,16 @@ int gemv_rows(mi_engine* e, const FusedLinear& f0, GemvCall c, size_t rows, size
     FusedLinear fh = f0;                       // (a view: the pointers stay owned by f0)
     fh.W.wk = WK_BF16; fh.W.w = f0.w_hilo; fh.W.K = 2 * f0.W.K;
     c.kx = f0.W.K;
-    return gemv_rows_on(e, fh, f0, c, rows, es_in, es_out, prof, sq_was_valid);
+    return gemv_rows_on(e, fh, f0, c, rows, es_in, es_out, prof, sq_was_valid, published);
   }
-  return gemv_rows_on(e, f0, f0, c, rows, es_in, es_out, prof, sq_was_valid);
+  return gemv_rows_on(e, f0, f0, c, rows, es_in, es_out, prof, sq_was_valid, published);
 }
 
 // f: the matrix the matmul kernels stream (f0 itself, or its [hi | lo] view); f0: the linear as loaded (true K, LoRA)
 int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, GemvCall c, size_t rows, size_t es_in, size_t es_out,
-                 const char* prof, bool sq_was_valid) {
+                 const char* prof, bool sq_was_valid, int* published) {
   const int KT = f0.W.K;                      // the true K: columns of x
+  c.cc_pub = nullptr; c.cc_pub_sq = nullptr;     // (set below by the split-K decode branch alone)
   // Which kernel for a call that is not a pure decode step (prefill, mixed step)?  Measured on Mistral-7B shapes, one prompt
   // of L tokens (ms for the whole call): dense 16-bit weights -- streaming kernel 4.2 / 5.1 /
   // 6.1 / 6.9 at L = 32 / 64 / 96 / 128 against 5.2 / 5.5 / 5.6 / 5.8 on the K-split 128 x 128 tile: the hand-over is at ~80 rows;
@@ -462,7 +493,6 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       if (take) { wv.w = f0.w_gu8; cw.epi = EPI_SWIGLU_GU8; }
     }
     if (take && wv.N / 16 >= 4 * gemv_cu_count() && gemv_f32_supported(wv, cw)) {
-      if (c.cc_pub != nullptr || c.xs_partial != nullptr) return fail(MI_ERR_RUNTIME, "consumer_combine: the linear left the split-K kernel");
       Prof pr(e, prof);
       if (cw.pro == PRO_NORM && !e->opt_defer_norm) MI_TRY(norm_into_xn(e, cw, rows, KT, cw.rnd));
       return launch_gemv_f32(wv, cw, e->stream);
@@ -495,6 +525,17 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     const bool q4_prep = gemm_q4_supported(f.W, c, rows);      // gemm_q4.hip: its preparation pass over x applies the RMSNorm
     if (handed) { c.sq_in = e->d_sq; c.sq_parts = e->sq_parts; }
     else if (c.pro == PRO_NORM && !defer && !q4_prep) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
+    // consumer_combine: the offer is taken by the call that the publish-only instantiation covers (gemm_skinny.hip, CC) --
+    // <= 8 unrounded float32 rows with the RMSNorm deferred, a dense bf16 matrix as loaded, no LoRA, 2..8 K slices
+    if (published != nullptr && f.W.wk == WK_BF16 && c.kx == 0 && f0.W.lora_b[0] == nullptr && f0.W.lora_b[1] == nullptr &&
+        c.rnd == RND_NONE && defer && rows <= 8) {
+      const int ks = gemm_skinny_ksplit(f.W, c, rows);
+      if (ks >= 2 && ks <= 8) {
+        MI_TRY(ensure_cc_pub(e, f.W.N));
+        c.cc_pub = cc_pub_tiles(e); c.cc_pub_sq = cc_pub_sumsq(e, f.W.N);
+        *published = ks;
+      }
+    }
     const size_t need = gemm_skinny_ws_bytes(f.W, c, rows);
     const int groups = gemm_skinny_groups(f.W, c, rows);
     const int tgroups = gemm_skinny_tile_groups(f.W, c, rows);
@@ -509,7 +550,6 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     if (produce) { e->sq_valid = true; e->sq_src = c.resid; e->sq_parts = tgroups; e->sq_K = f.W.N; e->sq_ld = leave_ld; }
     return MI_OK;
   }
-  if (c.cc_pub != nullptr || c.xs_partial != nullptr) return fail(MI_ERR_RUNTIME, "consumer_combine: the linear left the split-K kernel");
   if (e->opt_prefill_gemm && gemm_prefill_supported(f.W, c, rows)) {
     // prefill: one MFMA tile GEMM over all rows (the RMSNorm runs as its own row-wise kernel)
     Prof pr(e, prof);
@@ -745,44 +785,6 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   return std::max(1, std::min(ns, 16));
 }
 
-// consumer_combine: will gemv_rows() run this decode-step call on the float32, 16-row, dense bf16 form of the split-K kernel
-// without LoRA (the one instantiation that has the publish-only and split-merge modes)?  Mirrors gemv_rows_on()'s routing;
-// should the two ever disagree, gemv_rows_on() / launch_gemm_skinny() fail the step rather than run another kernel.
-bool cc_linear_ok(mi_engine* e, const FusedLinear& f, GemvCall c, size_t rows) {
-  if (!e->opt_skinny_gemm || e->opt_force_v1 || e->cur_L != 1 || rows > 8 || c.act != MI_F32 || c.rnd != RND_NONE) return false;
-  if (f.W.wk != WK_BF16 || f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr) return false;
-  c.M = (int)rows;
-  if (f.W.N / 16 >= 4 * gemv_cu_count() && gemv_f32_supported(f.W, c)) return false;      // the one-pass kernel takes it
-  return gemm_skinny_supported(f.W, c, rows);
-}
-
-constexpr size_t CC_GUARD = 64;                  // floats of sentinel around each part of the seam-1 buffer
-constexpr uint32_t CC_SENTINEL = 0x7fc0c0c0u;    // (a NaN: a read of it would not go unnoticed either)
-int ensure_cc_pub(mi_engine* e, int nqkv) {
-  const size_t need = 3 * CC_GUARD + (size_t)8 * 8 * nqkv + 8 * 8;
-  if (e->cc_pub != nullptr && e->cc_pub_floats >= need) return MI_OK;
-  MI_HIP(hipStreamSynchronize(e->stream));
-  hipFree(e->cc_pub); e->cc_pub = nullptr; e->cc_pub_floats = 0;
-  MI_HIP(hipMalloc(&e->cc_pub, need * sizeof(float)));
-  std::vector<uint32_t> fill(need, CC_SENTINEL);
-  MI_HIP(hipMemcpy(e->cc_pub, fill.data(), need * sizeof(float), hipMemcpyHostToDevice));
-  e->cc_pub_floats = need;
-  return MI_OK;
-}
-// the three sentinel runs of the seam-1 buffer (option "consumer_combine_guard"): intact -> MI_OK
-int check_cc_guards(mi_engine* e, int nqkv) {
-  if (e->cc_pub == nullptr) return fail(MI_ERR_NOTFOUND, "consumer_combine_guard: the q|k|v seam has not run");
-  MI_HIP(hipStreamSynchronize(e->stream));
-  const size_t body = (size_t)8 * 8 * nqkv, at[3] = {0, CC_GUARD + body, 2 * CC_GUARD + body + 64};
-  uint32_t g[CC_GUARD];
-  for (int i = 0; i < 3; ++i) {
-    MI_HIP(hipMemcpy(g, e->cc_pub + at[i], sizeof(g), hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < CC_GUARD; ++j)
-      if (g[j] != CC_SENTINEL) return fail(MI_ERR_RUNTIME, "consumer_combine_guard: sentinel run " + std::to_string(i) + " was overwritten");
-  }
-  return MI_OK;
-}
-
 // A group of cache rows that advance by the same number of tokens in one forward pass: entries [r0, r0 + B) of the
 // call's row list, L tokens each, the group's first token at position tok0 of the token buffer.
 struct AttnGroup { int r0, B, L; size_t tok0; };
@@ -851,32 +853,19 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     // everything up to the layer-0 attention still rounds to the model dtype in quirk mode
     const int rnd = (quirk && li == 0) ? rndT : RND_NONE;
     // consumer_combine: a decode step of one group of at most 8 rows (every cache row, in order: not a row-subset step)
-    // whose attention runs on the float32 MFMA kernel
+    // whose attention runs on the float32 MFMA kernel can add published K slices of q|k|v in its prologue
     bool cc_attn = false;
     int qkv_ks = 0;                              // > 0: this layer's q|k|v ran publish-only with that many K slices
-    if (e->opt_consumer_combine != 0 && cur_L == 1 && rows == nullptr && groups.size() == 1 && groups[0].L == 1 && R <= 8 && act == MI_F32 &&
+    if (e->opt_consumer_combine && e->opt_defer_norm && cur_L == 1 && rows == nullptr && groups.size() == 1 && groups[0].L == 1 && R <= 8 && act == MI_F32 &&
         kv->dtype == MI_F32 && e->opt_fused_attn && e->opt_attn_mfma && D % 64 == 0 && D <= 128) {
       AttnShape s{groups[0].B, 1, Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, nullptr};
       cc_attn = attention_decode_supported(s);
     }
-    GemvCall c_o; c_o.x = e->attn; c_o.ldx = Hq * D; c_o.act = act; c_o.rnd = RND_NONE; c_o.epi = EPI_RESID; c_o.resid = e->h; c_o.ldo = H;
-    // seam 2: the attention's splits are merged by o_proj's staging (the attention then takes no ticket and combines nothing)
-    const bool cc_o = (e->opt_consumer_combine & 2) && cc_attn && nsplit[0] > 1 && cc_linear_ok(e, lw.o, c_o, R);
     { // input_layernorm + q|k|v projections (llama.py:187,93)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = rnd; c.pro = PRO_NORM;
       c.norm_w = w32 ? lw.in_norm32 : lw.in_norm; c.eps = d.rms_norm_eps; c.epi = EPI_STORE; c.out = e->qkv; c.ldo = nqkv;
-      // seam 1: 2..8 K slices published row-major, added by the attention's prologue (not the rounded layer-0 call)
-      if ((e->opt_consumer_combine & 1) && cc_attn && e->opt_defer_norm && cc_linear_ok(e, lw.qkv, c, R)) {
-        GemvCall cp = c; cp.M = (int)R;
-        const int ks = gemm_skinny_ksplit(lw.qkv.W, cp, R);
-        if (ks > 1 && ks <= 8) {
-          MI_TRY(ensure_cc_pub(e, nqkv));
-          qkv_ks = ks;
-          c.cc_pub = e->cc_pub + CC_GUARD;
-          c.cc_pub_sq = e->cc_pub + 2 * CC_GUARD + (size_t)8 * 8 * nqkv;
-        }
-      }
-      MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv")); }
+      // (the offer: gemv_rows takes it -- qkv_ks K slices published -- or runs the ordinary launch)
+      MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv", cc_attn ? &qkv_ks : nullptr)); }
     void* kc = (char*)kv->k + (size_t)li * layer_elems * kes;
     void* vc = (char*)kv->v + (size_t)li * layer_elems * kes;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
@@ -896,14 +885,13 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
           for (int b = 0; b < g.B; ++b) { ac.host_row[b] = row_of(g, b); ac.host_off[b] = kv->h_off[row_of(g, b)]; }
         }
         if (qkv_ks > 0) {
-          ac.qkv_pub = e->cc_pub + CC_GUARD; ac.qkv_pub_sq = e->cc_pub + 2 * CC_GUARD + (size_t)8 * 8 * nqkv;
+          ac.qkv_pub = cc_pub_tiles(e); ac.qkv_pub_sq = cc_pub_sumsq(e, nqkv);
           ac.qkv_ksplit = qkv_ks; ac.hidden_k = H; ac.qkv_eps = d.rms_norm_eps;
         }
-        if (cc_o) ac.counters = nullptr;         // publish and return: o_proj merges
         Prof pr(e, "attn");
         MI_TRY(launch_attention_decode(ac, st));
       } else {
-        if (qkv_ks > 0 || cc_o) return fail(MI_ERR_RUNTIME, "consumer_combine: the attention left the fused kernel");
+        if (qkv_ks > 0) return fail(MI_ERR_RUNTIME, "consumer_combine: the attention left the fused kernel");
         { Prof pr(e, "rope_append");
           RopeAppendCall rc{s, qkv_g, q_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps,
                             e->cos_tab, e->sin_tab, d.max_positions};
@@ -916,8 +904,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
       }
     }
     { // o_proj + residual (llama.py:143,188)
-      GemvCall c = c_o;
-      if (cc_o) { c.xs_partial = kv->partial; c.xs_nsplit = nsplit[0]; c.xs_hq = Hq; c.xs_d = D; }
+      GemvCall c; c.x = e->attn; c.ldx = Hq * D; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
       MI_TRY(gemv_rows(e, lw.o, c, R, es, es, "gemv_o")); }
     { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
@@ -1633,7 +1620,7 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value) {
   if (k == "prefill_gemm") { e->opt_prefill_gemm = value != 0; return MI_OK; }
   if (k == "skinny_gemm") { e->opt_skinny_gemm = value != 0; return MI_OK; }
   if (k == "norm_handover") { e->opt_norm_handover = value != 0; return MI_OK; }
-  if (k == "consumer_combine") { if (value < 0 || value > 3) return fail(MI_ERR_INVALID, "consumer_combine: a bit mask, 0..3"); e->opt_consumer_combine = (int)value; return MI_OK; }
+  if (k == "consumer_combine") { if (value != 0 && value != 1) return fail(MI_ERR_INVALID, "consumer_combine: 0 or 1"); e->opt_consumer_combine = (int)value; return MI_OK; }
   if (k == "consumer_combine_guard") return check_cc_guards(e, (e->d.num_heads + 2 * e->d.num_kv_heads) * e->d.head_dim);   // (a check, not a setting)
   if (k == "defer_norm") { e->opt_defer_norm = value != 0; return MI_OK; }
   if (k == "prefill_x_terms") { if (value != 2 && value != 3) return fail(MI_ERR_INVALID, "prefill_x_terms: 2 or 3"); e->opt_prefill_x_terms = (int)value; return MI_OK; }

@@ -93,10 +93,8 @@ struct SkinnyParams {
   int nchunks;       // ceil(K / 256)
   float* ws;         // [ksplit][ntiles][NA][MT][64 lanes][4] partial accumulators (ksplit > 1)
   unsigned* ctr;     // [tile groups] arrival counters, zero between launches
-  // consumer_combine (the CC instantiations below only):
-  float* pub; float* pub_sq;       // CC 1, publish-only producer: partial tiles row-major [ksplit][8][N], the slices' row sums of squares [ksplit][8]
-  const float* xs_partial;         // CC 2, x = the merge of the decode attention's split partials [M * xs_hq][xs_nsplit][xs_d + 2]
-  int xs_nsplit, xs_hq, xs_d;
+  // consumer_combine (the CC instantiation below only):
+  float* pub; float* pub_sq;       // publish-only producer: partial tiles row-major [ksplit][8][N], the slices' row sums of squares [ksplit][8]
   const float* lora_t; int lora_t_ld;
   const float* lora_b0; const float* lora_b1;
   int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
@@ -117,24 +115,20 @@ struct SkinnyParams {
 // terms, x = hi + mid + lo, staged as three fragment images and multiplied by three MFMAs per weight fragment -- every
 // product is exact in the float32 accumulator, so the result is a float32 dot product in another summation order.
 // Outputs stay float32 with the run-time logical rounding `rnd` (layer 0 of that mode still rounds like the model).
-// CC (consumer_combine, X32 / MT 1 / dense weights only; 0 everywhere else):
-//   1 = publish-only producer: every wave stores its partial tile row-major with plain stores and the workgroup ends -- no
-//       write-through, no ticket, no last arriver; the next launch (the decode attention's prologue) adds the slices;
-//   2 = x source: x[m][k] is merged from the decode attention's split partials while a chunk is staged (the attention
-//       then publishes and returns).
-// They are selected by a TAG in place of the activation type (bf16_publish / bf16_splitx, both bf16): the kernel keeps its
-// template signature, and every other instantiation its name, code and registers.
+// CC (consumer_combine, X32 / MT 1 / dense weights only; 0 everywhere else): 1 = publish-only producer -- every wave stores
+// its partial tile row-major with plain stores and the workgroup ends: no write-through, no ticket, no last arriver; the
+// next launch (the decode attention's prologue) adds the slices.
+// It is selected by a TAG in place of the activation type (bf16_publish, a bf16): the kernel keeps its template signature,
+// and every other instantiation its name, code and registers.
 struct bf16_publish {};
-struct bf16_splitx {};
 template <typename A> struct sk_act { using type = A; static constexpr int cc = 0; };
 template <> struct sk_act<bf16_publish> { using type = bf16; static constexpr int cc = 1; };
-template <> struct sk_act<bf16_splitx> { using type = bf16; static constexpr int cc = 2; };
 
 template <typename ATG, int QB, int MT, bool SWIGLU, bool X32 = false>
 __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT >= 5 || (X32 && QB == 8 && MT == 2)) ? 2 : 4) void skinny_kernel(const SkinnyParams p) {
   using AT = typename sk_act<ATG>::type;
   constexpr int CC = sk_act<ATG>::cc;
-  static_assert(CC == 0 || (X32 && QB == 0 && MT == 1 && !SWIGLU), "consumer_combine: the float32, 16-row, dense, plain instantiation");
+  static_assert(CC == 0 || (CC == 1 && X32 && QB == 0 && MT == 1 && !SWIGLU), "consumer_combine: 0, or 1 on the float32, 16-row, dense, plain instantiation");
   constexpr bool Q4 = QB == 4, Q8 = QB == 8, QUANT = QB != 0;
   static_assert(!X32 || MT <= 2, "float32 activations: 16- and 32-row instantiations");
   using XT = typename std::conditional<X32, float, AT>::type;
@@ -247,39 +241,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
 #pragma unroll
   for (int i = 0; i < (X32 ? MT : 1); ++i) sqacc[i] = 0.f;
   const bool dn = X32 && p.defer_norm != 0;
-  // CC 2: the piece's 8 elements belong to one head (8 | head_dim); per split (max, sum) and O[d .. d + 8) as 8-byte loads
-  // (a partial is (head_dim + 2) floats: 8-byte aligned).  Four splits per round trip, as in combine_splits.
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  u32x2 xs_ml[CC == 2 ? 4 : 1], xs_o[CC == 2 ? 4 : 1][CC == 2 ? 4 : 1];
-  auto xs_base = [&](int c, int& d) -> const float* {      // splits of (this piece's row, its head), and its first d
-    const int k = c * SK_KC + xk[0] < p.K ? c * SK_KC + xk[0] : 0;
-    const int hd = k / p.xs_d;
-    d = k - hd * p.xs_d;
-    return p.xs_partial + ((size_t)(row0 + min(xmi[0], Mloc - 1)) * p.xs_hq + hd) * p.xs_nsplit * (p.xs_d + 2);
-  };
-  auto xs_load4 = [&](int c, int i0) {                      // straight-line: a split past the last re-loads the last
-    int d;
-    const float* pp = xs_base(c, d);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float* q = pp + (size_t)min(i0 + j, p.xs_nsplit - 1) * (p.xs_d + 2);
-      xs_ml[j] = *(const u32x2*)q;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) xs_o[j][t] = *(const u32x2*)(q + 2 + d + 2 * t);
-    }
-  };
-  auto xs_merge4 = [&](float& mn, float& L, float (&O)[8], int i0) {
-    float mv[4], lv[4], ov[4][8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mv[j] = __uint_as_float(xs_ml[j].x); lv[j] = __uint_as_float(xs_ml[j].y);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { ov[j][2 * t] = __uint_as_float(xs_o[j][t].x); ov[j][2 * t + 1] = __uint_as_float(xs_o[j][t].y); }
-    }
-    merge_splits4<8>(mn, L, O, mv, lv, ov, p.xs_nsplit - i0);
-  };
   auto load_x = [&](int c) {
-    if constexpr (CC == 2) { xs_load4(c, 0); return; }
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       // ([hi | lo] weights, float32 activations only: the second half of K meets the same x again.  kx is a multiple of the
@@ -307,22 +269,9 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
       if constexpr (X32) {
         const u32x4 z4 = {0u, 0u, 0u, 0u};
         float xf[8];
-        if constexpr (CC != 2) {
-          const u32x4 f0 = ok ? xr[i] : z4, f1 = ok ? xr2[i] : z4;
-          xf[0] = __uint_as_float(f0.x); xf[1] = __uint_as_float(f0.y); xf[2] = __uint_as_float(f0.z); xf[3] = __uint_as_float(f0.w);
-          xf[4] = __uint_as_float(f1.x); xf[5] = __uint_as_float(f1.y); xf[6] = __uint_as_float(f1.z); xf[7] = __uint_as_float(f1.w);
-        } else {                                 // what the attention's last arriver would have stored (combine_splits)
-          float mn = -1e30f, L = 0.f, O[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) O[j] = 0.f;
-          xs_merge4(mn, L, O, 0);
-          for (int i0 = 4; i0 < p.xs_nsplit; i0 += 4) {     // (more than four splits: short batches on long contexts)
-            xs_load4(c, i0);
-            xs_merge4(mn, L, O, i0);
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xf[j] = ok ? merged_out(O[j], L) : 0.f;
-        }
+        const u32x4 f0 = ok ? xr[i] : z4, f1 = ok ? xr2[i] : z4;
+        xf[0] = __uint_as_float(f0.x); xf[1] = __uint_as_float(f0.y); xf[2] = __uint_as_float(f0.z); xf[3] = __uint_as_float(f0.w);
+        xf[4] = __uint_as_float(f1.x); xf[5] = __uint_as_float(f1.y); xf[6] = __uint_as_float(f1.z); xf[7] = __uint_as_float(f1.w);
         if (dn) {                                // deferred RMSNorm: squares of the raw x, then x * w_norm
           const float wf[8] = {__uint_as_float(xnw[i].x), __uint_as_float(xnw[i].y), __uint_as_float(xnw[i].z), __uint_as_float(xnw[i].w),
                                __uint_as_float(xnw2[i].x), __uint_as_float(xnw2[i].y), __uint_as_float(xnw2[i].z), __uint_as_float(xnw2[i].w)};
@@ -1065,7 +1014,7 @@ int gemm_skinny_groups(const LinearW& W, const GemvCall& c, size_t rows) {      
 // c.pro must be PRO_NONE (normalise first); `ws` holds gemm_skinny_ws_bytes(), `ctr` gemm_skinny_groups() zeroed words
 #ifdef MI_SK_TRACE
 namespace {
-struct SkTraceRec { int launch, N, K, ksplit, grid, epi, M, qb, pro, act, mt, pad; };     // pad: 1 = publish-only, 2 = split-merged x
+struct SkTraceRec { int launch, N, K, ksplit, grid, epi, M, qb, pro, act, mt, pad; };     // pad: 1 = publish-only
 constexpr int TR_LAUNCHES = 4096, TR_WG = 1024;
 unsigned long long* tr_buf = nullptr;
 SkTraceRec tr_rec[TR_LAUNCHES];
@@ -1141,23 +1090,20 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
 #ifdef MI_SK_TRACE
   if (!tr_buf) { MI_HIP(hipMalloc(&tr_buf, (size_t)TR_LAUNCHES * TR_WG * 128)); MI_HIP(hipMemset(tr_buf, 0, (size_t)TR_LAUNCHES * TR_WG * 128)); }
   tr_rec[tr_count % TR_LAUNCHES] = SkTraceRec{(int)tr_count, W.N, W.K, pl.ksplit, std::min(grid, TR_WG), c.epi, (int)rows, qb, c.pro, c.act, pl.mt,
-                                               c.cc_pub != nullptr ? 1 : c.xs_partial != nullptr ? 2 : 0};     // (pad = the consumer_combine form)
+                                               c.cc_pub != nullptr ? 1 : 0};     // (pad = 1: the publish-only form)
   p.trace = tr_buf + (size_t)(tr_count % TR_LAUNCHES) * TR_WG * 16;
   ++tr_count;
 #endif
-  // consumer_combine: the caller (the engine's forward pass) has checked that the call is one of these; anything else here
-  // is an error, never a silent return to the ordinary kernel -- the neighbouring launch already relies on the choice
-  const int cc = c.cc_pub != nullptr ? 1 : c.xs_partial != nullptr ? 2 : 0;
-  if (cc != 0) {
+  // consumer_combine: the caller (the engine's router, gemv_rows_on) asks for the publish-only form only where it applies;
+  // anything else here is an error, never a silent return to the ordinary kernel -- the next launch relies on the choice
+  const bool publish = c.cc_pub != nullptr;
+  if (publish) {
     const bool lora = c.lora_t != nullptr || W.lora_b[0] != nullptr || W.lora_b[1] != nullptr;
     if (c.act != MI_F32 || c.rnd != RND_NONE || qb != 0 || sw || pl.mt != 1 || pl.nslab != 1 || rows > 8 || p.kx != W.K || lora)
       return fail(MI_ERR_INVALID, "gemm_skinny: consumer_combine needs <= 8 rows of float32 on a dense bf16 linear without LoRA");
-    if (cc == 1 && !(defer_norm && pl.ksplit > 1 && pl.ksplit <= 8 && c.epi == EPI_STORE && c.cc_pub_sq != nullptr))
+    if (!(defer_norm && pl.ksplit > 1 && pl.ksplit <= 8 && c.epi == EPI_STORE && c.cc_pub_sq != nullptr))
       return fail(MI_ERR_INVALID, "gemm_skinny: publish-only mode needs the deferred RMSNorm, a plain store and 2..8 K slices");
-    if (cc == 2 && !(c.pro == PRO_NONE && c.xs_nsplit > 1 && c.xs_nsplit <= 16 && c.xs_d % 8 == 0 && c.xs_d > 0 && c.xs_hq * c.xs_d == W.K))
-      return fail(MI_ERR_INVALID, "gemm_skinny: split-merged x needs 2..16 splits of heads x head_dim = K");
     p.pub = c.cc_pub; p.pub_sq = c.cc_pub_sq;
-    p.xs_partial = c.xs_partial; p.xs_nsplit = c.xs_nsplit; p.xs_hq = c.xs_hq; p.xs_d = c.xs_d;
   }
   if (c.act == MI_F32) {
     p.sq_out = nullptr; p.sq_in = nullptr;
@@ -1171,8 +1117,7 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
 #define GO32(QBV) do { \
       if (pl.mt == 1) return sw ? launch32(skinny_kernel<bf16, QBV, 1, true, true>) : launch32(skinny_kernel<bf16, QBV, 1, false, true>); \
       return sw ? launch32(skinny_kernel<bf16, QBV, 2, true, true>) : launch32(skinny_kernel<bf16, QBV, 2, false, true>); } while (0)
-    if (cc == 1) return launch32(skinny_kernel<bf16_publish, 0, 1, false, true>);
-    if (cc == 2) return launch32(skinny_kernel<bf16_splitx, 0, 1, false, true>);
+    if (publish) return launch32(skinny_kernel<bf16_publish, 0, 1, false, true>);
     if (qb == 4) GO32(4);
     if (qb == 8) GO32(8);
     GO32(0);

@@ -56,14 +56,12 @@ struct GemvCall {
   float* sq_out = nullptr;
   const float* sq_in = nullptr;
   int sq_parts = 0;
-  // consumer_combine (gemm_skinny.hip, the bf16_publish / bf16_splitx forms; a decode step of <= 8 float32 rows on a dense bf16 linear without
-  // LoRA -- launch_gemm_skinny refuses anything else):
-  //   cc_pub / cc_pub_sq: publish only -- the K slices' partial tiles go row-major to cc_pub [ksplit][8][N] and their row sums
-  //     of squares to cc_pub_sq [ksplit][8]; nothing is combined and c.out is not written (the decode attention adds them);
-  //   xs_partial: x is not read -- x[m][h * xs_d + d] is merged from the decode attention's split partials
-  //     [M * xs_hq][xs_nsplit][xs_d + 2] while it is staged.
+  // consumer_combine (gemm_skinny.hip, the bf16_publish form; a decode step of <= 8 float32 rows on a dense bf16 linear without
+  // LoRA -- launch_gemm_skinny refuses anything else): publish only -- the K slices' partial tiles go row-major to cc_pub
+  // [ksplit][8][N] and their row sums of squares to cc_pub_sq [ksplit][8]; nothing is combined and c.out is not written (the
+  // decode attention adds them).  The engine's router (gemv_rows_on) takes the pointers as an OFFER: it clears them on every
+  // route but that one.
   float* cc_pub = nullptr; float* cc_pub_sq = nullptr;
-  const float* xs_partial = nullptr; int xs_nsplit = 0, xs_hq = 0, xs_d = 0;
   void* ev_start = nullptr;       // measurement: hipEvent_t pair stamped with this kernel's own begin / end
   void* ev_stop = nullptr;        // (hipExtLaunchKernelGGL); MFMA path only
 };
@@ -245,7 +243,7 @@ struct AttnDecodeCall {
   int n_host_off;          // > 0: host_off[b] = offsets[cache row of b], host_row[b] = that cache row (B <= 32)
   int host_off[32];
   int host_row[32];
-  // consumer_combine seam 1 (float32 MFMA kernel, B <= 8): qkv is not read -- row b of it is the sum of the qkv_ksplit
+  // consumer_combine (float32 MFMA kernel, B <= 8): qkv is not read -- row b of it is the sum of the qkv_ksplit
   // partial rows qkv_pub[s][b][:] (slice order, from zero) times the RMSNorm row scale from qkv_pub_sq[s][b] (sums of squares
   // of the hidden_k inputs).  qkv_pub == null: the ordinary launch.
   const float* qkv_pub = nullptr; const float* qkv_pub_sq = nullptr;
