@@ -99,8 +99,23 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
 int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* gemm_prefill.hip on its own: the tile GEMM of the prefill call (generate_step's first model call, utils.py:243-262: every
  * nn.Linear over B x L rows at once).  a->M rows of 16-bit activations, tile-major dense 16-bit weights, a->pro =
- * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms. */
+ * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms.
+ * Tile-major int4 / int8 (group 64) weights (nn.QuantizedLinear, llama.py:64-67) are taken too: their [hi | lo] 16-bit copy is
+ * made in a scratch buffer inside the call, as the engine does.  Float32 activations are refused: mi_op_gemm_prefill_f32. */
 int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
+/* the same tile GEMM on float32 activations, the PagedKVCache mode (base.py:111-112 promotes every activation behind layer 0
+ * to float32; the linears are llama.py:64-67,93,143,160-165 again): a->x float32 rows, a->act = MI_F32, a->rnd = MI_RND_NONE,
+ * float32 outputs and residual; a->pro may be MI_PRO_NORM with float32 norm weights (llama.py:187,189), applied inside the
+ * split.  The call splits x exactly into x_terms bf16 terms (mi_op_split_rows) and runs the tile GEMM over that image, as the
+ * engine's prefill does.  w is tile-major: dense bf16 (x_terms 2 or 3), int4-bf16 group 64 (x_terms 3; the [hi | lo] copy is
+ * made inside), or dense f16 with K % 64 == 0 (x_terms 3; its exact [hi | lo] bf16 copy is made inside).  Anything the tile
+ * GEMM does not take returns MI_ERR_UNSUPPORTED -- no other kernel runs.  iters >= 1 also times that many back-to-back
+ * launches of the GEMM (without the split) into *avg_ms. */
+int mi_op_gemm_prefill_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int x_terms, int iters, float* avg_ms);
+/* the split in front of it on its own: rows x K float32 (row stride ldx; K % 4 == 0, ldx % 4 == 0), RMS-normalised first when
+ * norm_w (float32 [K], nn.RMSNorm: llama.py:187,189) is not NULL -> out[rows][terms x K] bf16 = [hi | mid | lo] (terms 3) or
+ * [hi | mid] (terms 2) with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): hi + mid + lo == x exactly. */
+int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, int rows, int K, int terms, void* out);
 /* tile-major weight layout of the streaming kernels (what mi_engine_finalize applies to eligible
  * matrices): returns the size of the tiled buffer (0 if the matrix is not eligible) / fills `dst`. */
 uint64_t mi_op_tiled_bytes(const mi_op_linear* row_major);

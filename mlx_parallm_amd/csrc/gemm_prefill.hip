@@ -889,6 +889,9 @@ bool gemm_prefill_supported(const LinearW& W, const GemvCall& c, size_t rows) {
                    c.ldx % 4 == 0 && W.K % 4 == 0;
   if (!dense && !q4 && !q8 && !x32) return false;
   if (W.K % BK != 0 || (!x32 && c.ldx % 8 != 0)) return false;
+  // a [hi | lo] copy of an f16 matrix: the x terms are kx wide each and the walk wraps at whole K tiles of them (the engine
+  // makes the copy for K % 256 == 0 only)
+  if (c.kx > 0 && (!x32 || c.kx % BK != 0 || W.K != 2 * c.kx)) return false;
   if (c.epi == EPI_STORE_F32) return false;
   // an adapted matrix: the caller adds the LoRA term to the stored output afterwards (launch_lora_up_add)
   if ((W.lora_b[0] != nullptr || W.lora_b[1] != nullptr) && c.epi != EPI_STORE) return false;

@@ -156,22 +156,28 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
   return rc != MI_OK ? rc : rc2;
 }
 
+// gemm_prefill.hip on its own, 16-bit activations: dense 16-bit weights, or int4 / int8 (group 64) weights through the [hi | lo]
+// 16-bit copy that the launch makes in a scratch buffer allocated here (the engine's deq_scratch).
 int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
   if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
   MI_TRY(ready());
   const LinearW W = to_linear(w);
   const GemvCall c = to_call(a);
-  if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || wk_is_quant(W.wk) || c.act == MI_F32)
-    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit weights, 16-bit activations, no prologue");
+  if (c.act == MI_F32)
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: 16-bit activations only (float32 activations: mi_op_gemm_prefill_f32)");
+  if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || (wk_is_quant(W.wk) && !gemm_prefill_supported(W, c, (size_t)c.M)))
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int4 or int8 (group 64) weights, 16-bit activations, no prologue");
+  void* ws = nullptr; void* scratch = nullptr; size_t cap = 0;
+  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } g_ws{ws}, g_scratch{scratch};
+  if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, W.K)));
   // K-split workspace as the engine holds it (float32 partial tiles; prompts below 4096 rows)
-  void* ws = nullptr; size_t cap = 0;
   if (c.M < 4096) { cap = (size_t)128 << 20; MI_HIP(hipMalloc(&ws, cap)); }
-  int rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, nullptr, ws, cap);
+  int rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
   if (rc == MI_OK && iters >= 1 && avg_ms) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, nullptr, ws, cap);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
     hipEventRecord(e1, nullptr);
     hipEventSynchronize(e1);
     float ms = 0.f;
@@ -180,8 +186,60 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
     hipEventDestroy(e0); hipEventDestroy(e1);
   }
   const int rc2 = finish();
-  if (ws) hipFree(ws);
   return rc != MI_OK ? rc : rc2;
+}
+
+// gemm_prefill.hip on float32 activations, as gemv_rows_on (engine.hip) runs it: (norm +) launch_split3_rows into a buffer of
+// split3_bytes, then launch_gemm_prefill on that image with c.ldx = x_terms x K.  An f16 matrix is multiplied through its
+// [hi | lo] bf16 copy (launch_f16_to_hilo), presented as gemv_rows does: wk = WK_BF16, K = 2 K, c.kx = K.  Every buffer
+// is made here; the timed launches are the GEMM's alone.
+int mi_op_gemm_prefill_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int x_terms, int iters, float* avg_ms) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  LinearW W = to_linear(w);
+  GemvCall c = to_call(a);
+  const int KT = W.K;                                         // the true K: everything that is about x keeps it
+  if (c.M < 1 || c.act != MI_F32 || (x_terms != 2 && x_terms != 3) || (x_terms == 2 && W.wk != WK_BF16))
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_f32: float32 activations in two (dense bf16 weights) or three terms");
+  void* hilo = nullptr; void* xs = nullptr; void* scratch = nullptr; void* ws = nullptr; size_t cap = 0;
+  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } g_hilo{hilo}, g_xs{xs}, g_scratch{scratch}, g_ws{ws};
+  if (W.wk == WK_F16 && W.layout == 1) {
+    MI_HIP(hipMalloc(&hilo, 2 * (size_t)W.N * W.K * sizeof(uint16_t)));
+    MI_TRY(launch_f16_to_hilo(W, hilo, nullptr));
+    W.wk = WK_BF16; W.w = hilo; W.K = 2 * KT;
+    c.kx = KT;
+  }
+  if (!gemm_prefill_supported(W, c, (size_t)c.M))
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_f32: call not supported by the tile GEMM");
+  MI_HIP(hipMalloc(&xs, split3_bytes((size_t)c.M, KT)));
+  MI_TRY(launch_split3_rows(c.x, c.ldx, c.pro == PRO_NORM ? c.norm_w : nullptr, c.eps, xs, c.M, KT, nullptr, x_terms));
+  c.x = xs; c.ldx = x_terms * KT; c.pro = PRO_NONE;
+  if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, KT)));
+  if (c.M < 4096) { cap = (size_t)128 << 20; MI_HIP(hipMalloc(&ws, cap)); }
+  int rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
+  if (rc == MI_OK && iters >= 1 && avg_ms) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  const int rc2 = finish();
+  return rc != MI_OK ? rc : rc2;
+}
+
+// launch_split3_rows on its own: rows x K float32 (row stride ldx; RMS-normalised first when norm_w is not null) ->
+// out[rows][terms x K] bf16, [hi | mid | lo] or [hi | mid]
+int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, int rows, int K, int terms, void* out) {
+  if (!x || !out || rows < 1 || K < 1) return fail(MI_ERR_INVALID, "bad argument");
+  MI_TRY(ready());
+  MI_TRY(launch_split3_rows(x, ldx, norm_w, eps, out, rows, K, nullptr, terms));
+  return finish();
 }
 
 int mi_op_gemv_uses_mfma(const mi_op_linear* w, const mi_op_gemv_args* a) {

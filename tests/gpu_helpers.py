@@ -130,3 +130,25 @@ def gemm_prefill(ol: L.OpLinear, x, M, act, *, epi=0, out=None, ldo=0, resid=Non
     ms = C.c_float(0.0)
     L.check(L.lib().mi_op_gemm_prefill(C.byref(ol), C.byref(a), int(iters), C.byref(ms)))
     return ms.value if iters >= 1 else None
+
+
+def gemm_prefill_f32(ol: L.OpLinear, x, M, *, x_terms=3, epi=0, out=None, ldo=0, resid=None, pair_offset=0, norm_w=None, eps=0.0,
+                     iters=0, ldx=None, check=True):
+    """gemm_prefill.hip on float32 activations (the split of x, then the tile GEMM over its image) -> the return code when
+    check is False, else the mean launch ms or None."""
+    a = gemv_args(x, M, "float32", pro=1 if norm_w is not None else 0, norm_w=norm_w, eps=eps, epi=epi, out=out, ldo=ldo,
+                  resid=resid, pair_offset=pair_offset, ldx=ldx)
+    torch.cuda.synchronize()
+    ms = C.c_float(0.0)
+    rc = L.lib().mi_op_gemm_prefill_f32(C.byref(ol), C.byref(a), int(x_terms), int(iters), C.byref(ms))
+    if not check:
+        return rc
+    L.check(rc)
+    return ms.value if iters >= 1 else None
+
+
+def split_rows(x, rows, K, terms, out, *, norm_w=None, eps=0.0, ldx=None):
+    """launch_split3_rows on its own: float32 rows -> out[rows][terms x K] bf16 bit patterns (out: an int16 tensor)."""
+    torch.cuda.synchronize()
+    L.check(L.lib().mi_op_split_rows(ptr(x), int(ldx if ldx is not None else x.shape[-1]), ptr(norm_w), float(eps), int(rows),
+                                     int(K), int(terms), ptr(out)))

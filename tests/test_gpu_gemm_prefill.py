@@ -1,4 +1,5 @@
-"""Kernel-level parity (-m gpu) of gemm_prefill.hip's 256 x 256 tile -- the GEMM of the prefill call (generate_step's
+"""Kernel-level parity (-m gpu) of gemm_prefill.hip on 16-bit activations (float32 activations: test_gpu_gemm_prefill_f32.py),
+mostly its 256 x 256 tile -- the GEMM of the prefill call (generate_step's
 first model call, utils.py:243-262 -> every nn.Linear over B x L rows, llama.py:64-67,93,143,160-165) -- through
 mi_op_gemm_prefill (include/mi355_ops.h): against the oracle's matmul on sampled rows, and the LDS-DMA kernel bit for bit
 against the register-staged kernel it replaced (same MFMA chain per accumulator, so the float32 sums must be identical)."""
@@ -8,12 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import ref_quant
 from oracle.numerics import matmul_nt, round_to
 
 pytestmark = pytest.mark.gpu
 
 from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import dev, gemm_prefill, host, op_linear, to_tiled  # noqa: E402
+from gpu_helpers import dev, dev_u32, gemm_prefill, host, op_linear, to_tiled  # noqa: E402
 from test_gpu_kernels import _assert_close  # noqa: E402
 
 RNG = np.random.default_rng(777)
@@ -143,3 +145,55 @@ def test_k_split_of_the_lds_dma_tile(act, kind, M, N, K):
     h = dev(h0, act)
     _run(ol, xd, M, act, 1, epi=L.EPI_RESID, resid=h, out=h, ldo=N)
     _assert_close(host(h)[rows], round_to(h0[rows] + y, act), act)
+
+
+@pytest.mark.parametrize("act,kind", [("bfloat16", "bf16"), ("float16", "f16")])
+@pytest.mark.parametrize("M,N,K", [
+    (33, 208, 64),           # 128 x 128 tile, 1 x 2 blocks, ragged rows, N ragged against 128 (208 = 128 + 80); one K tile
+    (200, 208, 1024),        # 128 x 128 tile, 2 x 2 blocks, 16 K tiles split into 2 slices of 8 + the reduce
+    (2085, 5648, 64),        # 9 x 23 = 207 blocks of the 256 tile, last column block 16 wide; one K tile is below the LDS-DMA
+                             # tile's two: the register-staged tile whatever MI_GEMM_DMA says
+])
+def test_ragged_n_and_the_128_row_tile(act, kind, M, N, K):
+    ol, w, keep = _weight(kind, N, K)
+    x = round_to(RNG.standard_normal((M, K)).astype(np.float32), act)
+    h0 = round_to(RNG.standard_normal((M, N)).astype(np.float32), act)
+    xd = dev(x, act)
+    rows = _rows(M)
+    y = round_to(matmul_nt(x[rows], w), act)
+    pad = 8
+    out = torch.full((M + 3, N + pad), 7.0, dtype=xd.dtype, device="cuda")
+    _run(ol, xd, M, act, 1, epi=L.EPI_STORE, out=out, ldo=N + pad)
+    o = host(out)
+    assert np.all(o[M:] == 7.0), "rows past M were written"
+    assert np.all(o[:, N:] == 7.0), "columns past N were written"
+    _assert_close(o[:M, :N][rows], y, act)
+    h = torch.full((M + 3, N + pad), 7.0, dtype=xd.dtype, device="cuda")
+    h[:M, :N] = dev(h0, act)
+    _run(ol, xd, M, act, 1, epi=L.EPI_RESID, resid=h, out=h, ldo=N + pad)
+    o = host(h)
+    assert np.all(o[M:] == 7.0) and np.all(o[:, N:] == 7.0)
+    _assert_close(o[:M, :N][rows], round_to(h0[rows] + y, act), act)
+
+
+@pytest.mark.parametrize("kind,act", [("q4_bf16", "bfloat16"), ("q4_f16", "float16"), ("q8_bf16", "bfloat16"), ("q8_f16", "float16")])
+@pytest.mark.parametrize("M,N,K", [
+    (150, 208, 512),         # [hi | lo] copy: 16 K tiles; 128 x 128 tile, 2 x 2 blocks, 2 slices of 8
+    (300, 464, 512),         # LDS-DMA 256 tile, 2 x 2 ragged blocks, 2 slices of 8
+])
+def test_int4_and_int8_weights_through_their_hi_lo_copy(kind, act, M, N, K):
+    """Quantised weights (group 64): the launch dequantises into a [hi | lo] 16-bit copy (scratch made inside the call) and walks
+    x twice.  Against the oracle's product with the float32 dequantisation."""
+    bits = 4 if kind.startswith("q4") else 8
+    packed, scales, biases = ref_quant.quantize(round_to(RNG.standard_normal((N, K)).astype(np.float32) * 0.05, act), 64, bits, act)
+    wdense = ref_quant.dequantize(packed, scales, biases, 64, bits)
+    pd, sd, bd = dev_u32(packed), dev(scales, act), dev(biases, act)
+    ol, keep = op_linear(kind, N, K, pd, sd, bd), [pd, sd, bd]
+    assert to_tiled(ol, keep)
+    x = round_to(RNG.standard_normal((M, K)).astype(np.float32), act)
+    xd = dev(x, act)
+    out = torch.full((M + 3, N), 7.0, dtype=xd.dtype, device="cuda")
+    _run(ol, xd, M, act, 1, epi=L.EPI_STORE, out=out, ldo=N)
+    o = host(out)
+    assert np.all(o[M:] == 7.0), "rows past M were written"
+    _assert_close(o[:M], round_to(matmul_nt(x, wdense), act), act)
