@@ -135,6 +135,16 @@ int mi_op_attention_decode(const mi_op_attn_shape* s, const void* qkv, void* kca
                            const int32_t* offsets, const void* q_norm_w, const void* k_norm_w, float eps,
                            const float* cos_tab, const float* sin_tab, void* out, float scale, int rnd_out,
                            int nsplit, float* partial, int32_t* counters, int variant, int iters, float* avg_ms);
+/* the same launch with the cache row and the KV length of every sequence chosen by the caller.  rows: device [B] or NULL
+ * (identity) -- sequence b lives in cache row rows[b], offsets[] is indexed by cache row (a step over a subset of the cache's
+ * rows).  host_row / host_off: HOST arrays [B] or both NULL; when given (B <= 32) they travel in the kernel arguments as in
+ * the engine's decode step -- host_row[b] = the cache row of b, host_off[b] = offsets[that row] -- and the kernel reads
+ * neither rows nor offsets. */
+int mi_op_attention_decode_host(const mi_op_attn_shape* s, const void* qkv, void* kcache, void* vcache,
+                                const int32_t* offsets, const void* q_norm_w, const void* k_norm_w, float eps,
+                                const float* cos_tab, const float* sin_tab, void* out, float scale, int rnd_out,
+                                int nsplit, float* partial, int32_t* counters, int variant, int iters, float* avg_ms,
+                                const int32_t* rows, const int32_t* host_row, const int32_t* host_off);
 int mi_op_sample(float* logits, int B, int V, float temperature, float top_p, const float* uniforms,
                  int top_logprobs, int32_t* tokens_out, float* logprob_out, float* prob_row0_out,
                  int32_t* topk_ids, float* topk_logprobs, float* row_stats);

@@ -122,6 +122,8 @@ SIGNATURES = {
     "mi_op_attention": (C.c_int, [C.POINTER(OpAttnShape), _P, _P, _P, _P, _P, C.c_float, C.c_int, _P]),
     "mi_op_attention_decode": (C.c_int, [C.POINTER(OpAttnShape), _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_float,
                                          C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_attention_decode_host": (C.c_int, [C.POINTER(OpAttnShape), _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_float,
+                                              C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _I32P, _I32P]),
     "mi_op_sample": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
 }
 

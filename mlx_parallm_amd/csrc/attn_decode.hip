@@ -20,21 +20,27 @@
 namespace mi {
 
 // Debug build (tools/debug/build_trace_lib.sh): wall-clock stamps of the MFMA decode attention, one 16-slot row per workgroup in
-// a buffer of their own (gemm_skinny.hip owns it): 0 entry, 1 every load of the prologue has landed (the first round's K / V
-// were issued in front of them and return in order), 2 prologue barrier, 3 last MFMA, 4 partial stored, 5 end;
-// 6 + r: wave 0 enters round r of a float32 cache (r <= 9).
+// a buffer of their own (gemm_skinny.hip owns it): 0 entry, 1 every load of the prologue has landed (16-bit caches: the first
+// round's K / V were issued in front of them and return in order; float32 caches: the prologue's loads go first and the wait
+// leaves the K / V loads behind them in flight), 2 prologue barrier, 3 last MFMA, 4 partial stored, 5 end;
+// 6 + r: wave 0 enters round r of a float32 cache (r <= 8); 15: the first round's K / V and the prologue's loads have all been
+// issued (the clock is read there and stored with stamp 1: a store in between would count in vmcnt).
 #ifdef MI_SK_TRACE
 unsigned long long* dbg_trace_slot(int N, int K, int grid, int epi, int M, int kind, int pro, int act);   // gemm_skinny.hip
 #define AT_TRACE_PARAM , unsigned long long* trace
 #define AT_TRACE_ARG , trace
-#define AT_STAMP(i) do { if (trace != nullptr && threadIdx.x == 0) trace[(size_t)((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 16 + (i)] = wall_clock64(); } while (0)
-#define AT_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define AT_STAMP_ROUND(r) AT_STAMP(6 + min((int)(r), 9))       // float32 caches: wave 0 enters round r (slots 6..15)
+#define AT_STAMP_AT(i, t) do { if (trace != nullptr && threadIdx.x == 0) trace[(size_t)((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 16 + (i)] = (t); } while (0)
+#define AT_STAMP(i) AT_STAMP_AT(i, wall_clock64())
+#define AT_CLOCK(t) const unsigned long long t = wall_clock64()
+#define AT_LANDED(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")   // n loads issued behind the prologue's stay in flight
+#define AT_STAMP_ROUND(r) AT_STAMP(6 + min((int)(r), 8))       // float32 caches: wave 0 enters round r (slots 6..14)
 #else
 #define AT_TRACE_PARAM
 #define AT_TRACE_ARG
+#define AT_STAMP_AT(i, t) do { } while (0)
 #define AT_STAMP(i) do { } while (0)
-#define AT_LANDED() do { } while (0)
+#define AT_CLOCK(t) do { } while (0)
+#define AT_LANDED(n) do { } while (0)
 #define AT_STAMP_ROUND(r) do { } while (0)
 #endif
 
@@ -111,6 +117,22 @@ __device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int
   return merged_out(O[0], L);
 }
 
+// Cache row and KV length of batch entry b (wave-uniform).  The host knows both (it advances the lengths itself) and passes
+// them in the kernel arguments: n_host_off > 0.  On that path nothing may touch vector memory -- the first K/V load waits for
+// these two values.  Written as `cond ? c.host_row[b] : rows[b]`, hipcc selects between the two ADDRESSES and emits one
+// flat_load_dword per value, one waiting for the other.  So the argument arrays are read unconditionally (index clamped: B
+// may exceed 32 on the other path) and each value goes through readfirstlane before the select: the two sources stay two
+// values, and the kernel-argument one stays a scalar load.  Device path (op-level calls, row-subset steps): rows[b], then offsets[row].
+struct RowLen { int kb, pos; };
+__device__ __forceinline__ RowLen row_and_length(const AttnDecodeCall& c, int b) {
+  const int bi = min(b, 31);
+  const int hrow = __builtin_amdgcn_readfirstlane(c.host_row[bi]);
+  const int hoff = __builtin_amdgcn_readfirstlane(c.host_off[bi]);
+  if (c.n_host_off > 0) return RowLen{hrow, hoff};
+  const int kb = c.s.rows ? c.s.rows[b] : b;
+  return RowLen{kb, c.offsets[kb]};
+}
+
 // D must be a multiple of 32 for 16-bit caches (two elements per dword per lane); float caches any D % 16 == 0
 template <typename T, int D, int G, bool NORM, bool PAGED>
 __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecodeCall c) {
@@ -123,10 +145,8 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecodeCall c) {
   const int b = bh / s.Hkv, kh = bh % s.Hkv;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, gq = lane >> 4;
-  // the host knows every row's length (it advances them itself); taking it from the kernel arguments
-  // removes a dependent global load from the head of the chain
-  const int kb = c.n_host_off > 0 ? c.host_row[b] : (s.rows ? s.rows[b] : b);   // cache row of batch entry b
-  const int pos = c.n_host_off > 0 ? c.host_off[b] : c.offsets[kb];
+  const RowLen rl = row_and_length(c, b);
+  const int kb = rl.kb, pos = rl.pos;            // cache row of batch entry b, tokens already in it
   const int n_keys = pos + 1;
   const int chunk = (n_keys + c.nsplit - 1) / c.nsplit;
   const int s0 = split * chunk, s1 = min(n_keys, s0 + chunk);
@@ -513,10 +533,8 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, gq = lane >> 4;      // VALU prologue view: lane li of a row owns D/16 elements
   const int c16 = li, g4 = gq;                   // MFMA view: column / lane group
-  // the host knows every row's length (it advances them itself); taking it from the kernel arguments
-  // removes a dependent global load from the head of the chain
-  const int kb = c.n_host_off > 0 ? c.host_row[b] : (s.rows ? s.rows[b] : b);   // cache row of batch entry b
-  const int pos = c.n_host_off > 0 ? c.host_off[b] : c.offsets[kb];
+  const RowLen rl = row_and_length(c, b);
+  const int kb = rl.kb, pos = rl.pos;            // cache row of batch entry b, tokens already in it
   // the pos cached keys are cut evenly over the splits (a 1024-key context = 4 x 256 = one round each); the
   // new key is merged by the last split from registers / LDS
   // (float32: in whole 16-key tiles -- a wave's unit of work -- so that at most one split ends in a ragged tile)
@@ -578,8 +596,16 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
       }
     }
   };
-  issue_k(s0);
-  issue_v(s0);
+  // 16-bit caches: the first round's K / V go out before anything else.  float32 caches: behind the prologue's loads -- a
+  // CU returns loads in the order of issue, and a round of float32 K / V is 128 KiB per CU: in front, it held the
+  // prologue (and with it the barrier, the q fragments and the first product) back until the whole round had landed.
+  // (Block-paged float32 caches keep the old order: their K / V addresses wait for a block-table load, which would
+  // queue behind the prologue's loads; not measured.)
+  constexpr bool PRO_FIRST = F32 && !PAGED;
+  if constexpr (!PRO_FIRST) {
+    issue_k(s0);
+    issue_v(s0);
+  }
 
   // ---- prologue, spread over the workgroup: lane group (wave, gq) = vector vi owns ONE of the G query
   // heads (vi < G), the new key (vi == G) or the new value (vi == G + 1): raw load, RMSNorm, RoPE,
@@ -616,11 +642,20 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   }
   uint32_t r0[NW32];
   if constexpr (NORM) load_raw<NW32>((const T*)(is_k ? c.k_norm_w : c.q_norm_w) + li * EPL, r0);
-  // every global load the prologue waits for is in the queue ahead of this.  (Two barriers: where a hook used to sit
-  // between them; with one, hipcc allocates the body's registers differently.)
+  constexpr int KV_BEHIND = PRO_FIRST ? NP + 4 * NH : 0;   // K / V loads per lane of a float32 round, in the queue behind the prologue's
+  if constexpr (PRO_FIRST) {
+    __builtin_amdgcn_sched_barrier(0);
+    issue_k(s0);
+    issue_v(s0);
+  }
+  // every global load the prologue waits for is in the queue ahead of this; what the arithmetic below waits for is
+  // vmcnt(KV_BEHIND), not an empty queue.  (Two barriers: where a hook used to sit between them; with one, hipcc allocates
+  // the body's registers differently.)
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_sched_barrier(0);
-  AT_LANDED();
+  AT_CLOCK(t_issued);
+  AT_LANDED(KV_BEHIND);
+  AT_STAMP_AT(15, t_issued);
   AT_STAMP(1);
   if constexpr (QS) {                            // the q|k|v linear's combine and epilogue: slices in order from zero, then x rs
     float tot = 0.f;

@@ -292,14 +292,8 @@ int mi_op_attention(const mi_op_attn_shape* s, const void* q, const void* kcache
   return finish();
 }
 
-int mi_op_attention_decode(const mi_op_attn_shape* s, const void* qkv, void* kcache, void* vcache,
-                           const int32_t* offsets, const void* q_norm_w, const void* k_norm_w, float eps,
-                           const float* cos_tab, const float* sin_tab, void* out, float scale, int rnd_out,
-                           int nsplit, float* partial, int32_t* counters, int variant, int iters, float* avg_ms) {
-  if (!s) return fail(MI_ERR_INVALID, "null argument");
-  MI_TRY(ready());
-  AttnDecodeCall ac{to_shape(s), qkv, kcache, vcache, offsets, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
-                    out, scale, rnd_out, nsplit, partial, (int*)counters, variant};
+// one launch, or iters back-to-back launches behind a warm-up one, timed into *avg_ms
+static int run_attention_decode(const AttnDecodeCall& ac, int iters, float* avg_ms) {
   if (iters <= 1) {
     MI_TRY(launch_attention_decode(ac, nullptr));
     return finish();
@@ -316,6 +310,36 @@ int mi_op_attention_decode(const mi_op_attn_shape* s, const void* qkv, void* kca
   if (avg_ms) *avg_ms = ms / iters;
   hipEventDestroy(e0); hipEventDestroy(e1);
   return finish();
+}
+
+int mi_op_attention_decode(const mi_op_attn_shape* s, const void* qkv, void* kcache, void* vcache,
+                           const int32_t* offsets, const void* q_norm_w, const void* k_norm_w, float eps,
+                           const float* cos_tab, const float* sin_tab, void* out, float scale, int rnd_out,
+                           int nsplit, float* partial, int32_t* counters, int variant, int iters, float* avg_ms) {
+  if (!s) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  AttnDecodeCall ac{to_shape(s), qkv, kcache, vcache, offsets, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
+                    out, scale, rnd_out, nsplit, partial, (int*)counters, variant};
+  return run_attention_decode(ac, iters, avg_ms);
+}
+
+int mi_op_attention_decode_host(const mi_op_attn_shape* s, const void* qkv, void* kcache, void* vcache,
+                                const int32_t* offsets, const void* q_norm_w, const void* k_norm_w, float eps,
+                                const float* cos_tab, const float* sin_tab, void* out, float scale, int rnd_out,
+                                int nsplit, float* partial, int32_t* counters, int variant, int iters, float* avg_ms,
+                                const int32_t* rows, const int32_t* host_row, const int32_t* host_off) {
+  if (!s) return fail(MI_ERR_INVALID, "null argument");
+  if ((host_row != nullptr) != (host_off != nullptr)) return fail(MI_ERR_INVALID, "attention_decode_host: host_row and host_off come together");
+  if (host_row && (s->B < 1 || s->B > 32)) return fail(MI_ERR_INVALID, "attention_decode_host: host arrays take 1..32 sequences");
+  MI_TRY(ready());
+  AttnDecodeCall ac{to_shape(s), qkv, kcache, vcache, offsets, q_norm_w, k_norm_w, eps, cos_tab, sin_tab,
+                    out, scale, rnd_out, nsplit, partial, (int*)counters, variant};
+  ac.s.rows = rows;
+  if (host_row) {                                  // as the engine's decode step fills them
+    ac.n_host_off = s->B;
+    for (int b = 0; b < s->B; ++b) { ac.host_row[b] = host_row[b]; ac.host_off[b] = host_off[b]; }
+  }
+  return run_attention_decode(ac, iters, avg_ms);
 }
 
 int mi_op_sample(float* logits, int B, int V, float temperature, float top_p, const float* uniforms,

@@ -86,8 +86,9 @@ def report_attention_side(path, steps):
     q|k|v -> decode attention -> o -> down.  One row per distinct launch signature over the last `steps` steps, in the order
     of first appearance.  Linears: stage = entry -> first chunk staged, stream = the K slice, tail = last MFMA -> the
     workgroup's last stamp (publish-only: its stores; otherwise publish / count and, for the last arriver, combine + epilogue).
-    Attention (kind -2; -3 = it adds the q|k|v slices): landed = entry -> every prologue load has arrived (the first round's
-    K / V are in front of them), prologue = -> the barrier behind norm / RoPE / append, rounds = -> last MFMA, store = -> the
+    Attention (kind -2; -3 = it adds the q|k|v slices): landed = entry -> every prologue load has arrived (16-bit caches: the
+    first round's K / V are in front of them; float32: behind them, still in flight), prologue = -> the barrier behind norm /
+    RoPE / append, rounds = -> last MFMA, store = -> the
     partial (or the output) is stored, tail = -> end (ticket, and for the last arriver the combine).  A second table gives each
     attention launch's stamps, one per round of a float32 cache included, for the median workgroup and for the one that
     ends last.  All in us, means over workgroups and launches; total = first entry -> last end of the launch; to_next = -> first entry of the next stamped launch."""
@@ -125,9 +126,11 @@ def report_attention_side(path, steps):
             end = st[:, 5].max()
             # the workgroup's own timeline, from its entry: median workgroup and the one that ends last.  Round stamps
             # (6 + r, float32 caches) are wave 0's; a slot the launch did not write holds an older launch's stamp.
+            # issued (slot 15) = the first round's K / V and the prologue's loads are all in the queue: the cache row and
+            # the KV length are known and every address is computed.
             rel = (st - st[:, :1]) * TICK_US
             lastwg = int(np.argmax(st[:, 5]))
-            pts = [("landed", 1), ("barrier", 2)] + [(f"round{r}", 6 + r) for r in range(10)] + [("last_mfma", 3), ("stored", 4), ("end", 5)]
+            pts = [("issued", 15), ("landed", 1), ("barrier", 2)] + [(f"round{r}", 6 + r) for r in range(9)] + [("last_mfma", 3), ("stored", 4), ("end", 5)]
             for name, col in pts:
                 okm = (st[:, col] >= st[:, 0]) & (st[:, col] <= st[:, 5])
                 if col >= 6 and okm.sum() * 2 < len(okm):                  # a round that fewer than half of the workgroups reach
@@ -172,7 +175,7 @@ def report_attention_side(path, steps):
         if k[0] not in (-2, -3):
             continue
         a = acc[k]
-        names = ["entry", "landed", "barrier"] + [f"round{r}" for r in range(10)] + ["last_mfma", "stored", "end"]
+        names = ["entry", "issued", "landed", "barrier"] + [f"round{r}" for r in range(9)] + ["last_mfma", "stored", "end"]
         names = [n for n in names if a["tl_med_" + n] or a["tl_last_" + n]]
         print(f"attention kind {k[0]}, {k[4]} splits, grid {k[3]}: a workgroup's stamps in us from its own entry (entry: from the launch's first entry)")
         print(f"{'':>10} " + " ".join(f"{n:>9}" for n in names))
