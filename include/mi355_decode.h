@@ -35,7 +35,7 @@ extern "C" {
  * `struct_size`, which the caller sets to sizeof() of ITS definition -- a binding generated from another version of this
  * header (a shorter mi_sample_params would make the library read pointers past its end) is refused with MI_ERR_INVALID
  * by mi_engine_create / mi_decode_sample / mi_step_enqueue(_rows) / mi_score_tokens instead of being read. */
-#define MI_ABI_VERSION 2
+#define MI_ABI_VERSION 3
 
 #define MI_OK 0
 #define MI_ERR_INVALID (-1)
@@ -79,6 +79,13 @@ typedef struct mi_model_desc {
   int32_t quant_bits;        /* 0 = no quantised tensors; else 4 or 8 */
   int32_t quant_group_size;  /* 64 (32 / 128 also accepted) */
   int32_t max_positions;     /* RoPE table length = largest KV capacity a mi_kv may have */
+  /* ABI 3 (llama.py:59-67,155-162,77-82); MI_ARCH_LLAMA */
+  int32_t attention_bias;    /* q/k/v/o_proj carry a `.bias` tensor ([N], model dtype or float32) */
+  int32_t mlp_bias;          /* gate/up/down_proj carry a `.bias` tensor */
+  int32_t rope_traditional;  /* nn.RoPE(traditional=True): pairs (2 i, 2 i + 1) of a head rotate.  mi_engine_finalize regroups
+                              * the q / k rows (and biases; mi_engine_set_lora: the columns of B) into the half-split order
+                              * of the kernels -- q.k is unchanged, V / O / the caches are untouched.  MI_ARCH_QWEN3 with the
+                              * flag: MI_ERR_UNSUPPORTED (q_norm / k_norm would need the same regrouping) */
 } mi_model_desc;
 
 /* arguments of the `sample` closure (utils.py:345-364) + top_p_sampling (sample_utils.py:3-38) */
@@ -110,7 +117,9 @@ void mi_engine_destroy(mi_engine* e);
 
 /* One call per checkpoint tensor, named as in the safetensors file (e.g.
  * "model.layers.3.self_attn.q_proj.weight" / ".scales" / ".biases", "model.norm.weight",
- * "lm_head.weight"); replaces model.load_weights (utils.py:693-702).  `data` is a host
+ * "lm_head.weight"); replaces model.load_weights (utils.py:693-702).  "<proj>.bias" (1-D, N elements, float32 / bf16 / f16;
+ * not the quantisation ".biases") is taken for q/k/v/o_proj when desc.attention_bias is set and for gate/up/down_proj when
+ * desc.mlp_bias is set; with the flag off the name is unknown (MI_ERR_NOTFOUND), as the reference filters it.  `data` is a host
  * pointer (on_device = 0) or a device pointer on the engine's device (on_device = 1, e.g. a
  * torch tensor that was just filled by an RCCL broadcast); the bytes are COPIED.
  * Unknown names -> MI_ERR_NOTFOUND (the reference filters them, utils.py:693-698). */
@@ -119,11 +128,14 @@ int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const
 
 /* LoRALinear for one projection (mlx-lm load_adapters, utils.py:742-744; file layout
  * rl_training/lora_init.py:140-153).  proj: "self_attn.q_proj" etc.  A is (K, r), B is (r, N),
- * row-major, dtype MI_F32/BF16/F16.  y += (scale * ((x A) B)).astype(x.dtype). */
+ * row-major, dtype MI_F32/BF16/F16.  y += (scale * ((x A) B)).astype(x.dtype), on top of the projection's bias when it has
+ * one.  With desc.rope_traditional the columns of B of q_proj / k_proj are regrouped like the rows of the matrix (the
+ * caller passes them in checkpoint order, also on a hot-swap). */
 int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B,
                        int rank, float scale, int dtype, int on_device);
 
-/* checks that every tensor was set, fuses q|k|v and gate|up buffers, builds RoPE tables */
+/* checks that every tensor was set (a missing `.bias` of a set bias flag: MI_ERR_NOTFOUND with its name), fuses q|k|v and
+ * gate|up buffers, regroups q / k for rope_traditional, builds RoPE tables */
 int mi_engine_finalize(mi_engine* e);
 
 /* ---- KV cache: replaces _KVPool.get / PagedKVCache (utils.py:199-223, base.py:93-150) -- */

@@ -57,6 +57,9 @@ typedef struct mi_op_linear {
   const void* biases;
   int32_t layout;        /* 0 = row-major (checkpoint order), 1 = tile-major (mi_op_repack_tiled; then w is
                             the tiled buffer and scales/biases are unused) */
+  const float* bias;     /* [N] float32 bias of nn.Linear / nn.QuantizedLinear (llama.py:59-67,155-162), or NULL.  Dense
+                            weights: y = T(acc + b); quantised: y = T(T(acc) + b).  mi_op_gemv, mi_op_gemm_skinny,
+                            mi_op_gemm_prefill(_f32) apply it; mi_op_gemv_f32 and a forced gemm_q4 plan refuse it */
 } mi_op_linear;
 
 typedef struct mi_op_gemv_args {

@@ -18,7 +18,7 @@ MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
 MI_KV_MODEL = -1
 MI_ARCH_LLAMA, MI_ARCH_QWEN3 = 0, 1
 MI_MAX_TOP_LOGPROBS = 20
-MI_ABI_VERSION = 2
+MI_ABI_VERSION = 3
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
 PRO_NONE, PRO_NORM = 0, 1
@@ -35,6 +35,7 @@ class ModelDesc(C.Structure):
         ("vocab_size", C.c_int32), ("rms_norm_eps", C.c_float), ("rope_theta", C.c_float),
         ("rope_scale", C.c_float), ("tie_word_embeddings", C.c_int32), ("act_dtype", C.c_int32),
         ("quant_bits", C.c_int32), ("quant_group_size", C.c_int32), ("max_positions", C.c_int32),
+        ("attention_bias", C.c_int32), ("mlp_bias", C.c_int32), ("rope_traditional", C.c_int32),
     ]
 
 
@@ -52,7 +53,8 @@ class SampleParams(C.Structure):
 
 class OpLinear(C.Structure):
     _fields_ = [("wk", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("group", C.c_int32),
-                ("w", C.c_void_p), ("scales", C.c_void_p), ("biases", C.c_void_p), ("layout", C.c_int32)]
+                ("w", C.c_void_p), ("scales", C.c_void_p), ("biases", C.c_void_p), ("layout", C.c_int32),
+                ("bias", C.c_void_p)]
 
 
 class OpGemvArgs(C.Structure):

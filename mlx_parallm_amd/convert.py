@@ -153,7 +153,8 @@ def convert(hf_path: str, mlx_path: str = "mlx_model", quantize: bool = False, q
     config = load_config(model_path)
     weights = load_weights_dir(model_path)
     target = torch.float16 if quantize else _DTYPES[dtype]
-    weights = {k: (v.to(target) if v.is_floating_point() and not _is_packed_aux(k, weights) else v) for k, v in weights.items()}
+    weights = {k: (v.to(target) if v.is_floating_point() and not _is_packed_aux(k, weights) and not _is_linear_bias(k, v) else v)
+               for k, v in weights.items()}
     if quantize:
         print("[INFO] Quantizing")
         weights, config = quantize_model(weights, config, q_group_size, q_bits)
@@ -169,6 +170,12 @@ def convert(hf_path: str, mlx_path: str = "mlx_model", quantize: bool = False, q
         for f in glob.glob(str(model_path / pat)):
             shutil.copy(f, out)
     save_config(config, config_path=out / "config.json")
+
+
+def _is_linear_bias(name: str, t: torch.Tensor) -> bool:
+    """the 1-D ``<proj>.bias`` of nn.Linear(bias=True) (attention_bias / mlp_bias): travels untouched -- it is neither
+    quantised (1-D) nor cast, the engine reads it as float32 whatever its dtype -- and is not the quantisation ``.biases``."""
+    return name.endswith(".bias") and t.ndim == 1
 
 
 def _is_packed_aux(name: str, weights: Dict[str, Any]) -> bool:

@@ -63,6 +63,18 @@ __device__ __forceinline__ T store_act(float v, int rnd) {
   else return (T)v;
 }
 
+// The bias of a linear layer.  nn.Linear adds it to the float32 accumulator (mx.addmm): one rounding, T(acc + b).
+// nn.QuantizedLinear adds it to the rounded result of quantized_matmul: two roundings, T(T(acc) + b) (`two`).  T = float
+// without a logical rounding (PagedKVCache mode after layer 0): acc + b either way.  The add is never contracted with a
+// product that made acc (the deferred RMSNorm's rs * acc): y = rs * acc + b has two float32 roundings.
+template <typename T>
+__device__ __forceinline__ float add_bias(float acc, float b, bool two, int rnd) {
+#pragma clang fp contract(off)
+  if (two) acc = to_f32(store_act<T>(acc, rnd));
+  const float s = acc + b;
+  return to_f32(store_act<T>(s, rnd));
+}
+
 // scale * q + bias with two roundings (the oracle's `q * scale + bias`); hipcc would otherwise
 // contract it into one FMA (-ffp-contract=fast is the HIP default, and __fmul_rn is a plain `*`).
 __device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {

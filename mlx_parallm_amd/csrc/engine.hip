@@ -55,6 +55,9 @@ struct FusedLinear {
   float* lora_a[2] = {nullptr, nullptr};
   float* lora_b[2] = {nullptr, nullptr};
   int seen_w[3] = {0, 0, 0}, seen_s[3] = {0, 0, 0}, seen_b[3] = {0, 0, 0};
+  float* bias = nullptr;         // [rows of all parts] float32: the parts' `.bias` tensors (attention_bias / mlp_bias), as loaded
+  int seen_bias[3] = {0, 0, 0};
+  bool qk_regrouped = false;     // rope_traditional: permute_qk_heads has run (a finalize that failed later is not repeated on it)
 };
 
 struct LayerW {
@@ -234,6 +237,61 @@ int set_vector(mi_engine* e, void*& dst, int n, const void* data, const int64_t*
   return copy_in(dst, data, (size_t)n * dtype_size(dtype), on_device, e->stream);
 }
 
+// `<proj>.bias` of part `part` (1-D, the part's rows; float32 or a 16-bit float) -> float32 at the part's rows of f.bias
+int set_bias(mi_engine* e, FusedLinear& f, int part, const void* data, const int64_t* shape, int ndim, int dtype,
+             int on_device, const std::string& name) {
+  const int rows = f.part_rows[part];
+  int total = 0, row0 = 0;
+  for (int i = 0; i < f.n_parts; ++i) { if (i < part) row0 += f.part_rows[i]; total += f.part_rows[i]; }
+  if (ndim != 1 || shape[0] != rows) return fail(MI_ERR_INVALID, name + ": wrong shape");
+  if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, name + ": bad dtype");
+  if (f.bias == nullptr) MI_HIP(hipMalloc(&f.bias, (size_t)total * sizeof(float)));
+  if (dtype == MI_F32) {
+    MI_TRY(copy_in(f.bias + row0, data, (size_t)rows * sizeof(float), on_device, e->stream));
+  } else {
+    void* tmp = nullptr;
+    MI_HIP(hipMalloc(&tmp, (size_t)rows * dtype_size(dtype)));
+    int rc = copy_in(tmp, data, (size_t)rows * dtype_size(dtype), on_device, e->stream);
+    if (rc == MI_OK) rc = launch_convert(tmp, dtype, f.bias + row0, MI_F32, (size_t)rows, e->stream);
+    if (rc == MI_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MI_ERR_RUNTIME, name + ": converting the bias failed");
+    hipFree(tmp);
+    MI_TRY(rc);
+  }
+  f.seen_bias[part] = 1;
+  return MI_OK;
+}
+
+// rope_traditional: the first `nrows` rows (whole heads of D) of a row-major device array regrouped in place (kernels.h)
+int head_perm_inplace(mi_engine* e, void* buf, size_t nrows, int D, size_t row_bytes) {
+  if (buf == nullptr || nrows == 0 || row_bytes == 0) return MI_OK;
+  void* tmp = nullptr;
+  MI_HIP(hipMalloc(&tmp, nrows * row_bytes));
+  int rc = launch_head_perm_rows(buf, tmp, nrows, D, row_bytes, e->stream);
+  if (rc == MI_OK && (hipMemcpyAsync(buf, tmp, nrows * row_bytes, hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
+                      hipStreamSynchronize(e->stream) != hipSuccess))
+    rc = fail(MI_ERR_RUNTIME, "regrouping the q / k rows for rope_traditional failed");
+  hipFree(tmp);
+  return rc;
+}
+
+// the q and k parts of a q|k|v matrix as loaded (row-major, before the tile-major repack): codes, scales, quantisation
+// biases and linear biases.  Quantisation groups run along K, so whole rows move.
+int permute_qk_heads(mi_engine* e, FusedLinear& f) {
+  int total = 0;
+  if (f.qk_regrouped || f.W.layout == 1) return MI_OK;
+  for (int i = 0; i < f.n_parts; ++i) { total += f.part_rows[i]; if (!f.seen_w[i]) return MI_OK; }   // (finalize_linear reports it)
+  const size_t nrows = (size_t)f.part_rows[0] + f.part_rows[1];
+  const int D = e->d.head_dim;
+  MI_TRY(head_perm_inplace(e, f.w, nrows, D, f.w_bytes / total));
+  if (f.quant && f.scales != nullptr && f.biases != nullptr) {
+    MI_TRY(head_perm_inplace(e, f.scales, nrows, D, f.s_bytes / total));
+    MI_TRY(head_perm_inplace(e, f.biases, nrows, D, f.s_bytes / total));
+  }
+  if (f.bias != nullptr && f.seen_bias[0] && f.seen_bias[1]) MI_TRY(head_perm_inplace(e, f.bias, nrows, D, sizeof(float)));
+  f.qk_regrouped = true;
+  return MI_OK;
+}
+
 int finalize_linear(mi_engine* e, FusedLinear& f, int K, const std::string& name) {
   int total = 0;
   for (int i = 0; i < f.n_parts; ++i) {
@@ -246,6 +304,7 @@ int finalize_linear(mi_engine* e, FusedLinear& f, int K, const std::string& name
   f.W.wk = kind_of(f, e->d.quant_bits);
   f.W.w = f.w; f.W.scales = f.scales; f.W.biases = f.biases;
   f.W.N = total; f.W.K = K; f.W.group = e->d.quant_group_size > 0 ? e->d.quant_group_size : 64;
+  f.W.bias = f.bias;
   // "repack weights": tile-major layout for the matrices the streaming kernels read (repack.hip)
   if (e->opt_tile_weights && tiled_supported(f.W.wk, f.W.N, f.W.K, f.W.group)) {
     void* dst = nullptr;
@@ -268,7 +327,7 @@ int make_f32_copy(mi_engine* e, const void* src, int n, void** dst) {
 }
 
 void free_linear(FusedLinear& f) {
-  hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8);
+  hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
   for (int i = 0; i < 2; ++i) { hipFree(f.lora_a[i]); hipFree(f.lora_b[i]); }
 }
 
@@ -345,6 +404,7 @@ bool ensure_hilo(mi_engine* e, FusedLinear& f) {
 }
 bool gu8_wanted(const mi_engine* e, const FusedLinear& f, int pair_offset) {
   const bool has_lora = f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr;
+  if (f.W.bias != nullptr) return false;        // the interleaved copy's epilogues carry no bias: the paired-tile SwiGLU kernels run
   return e->opt_gu8 && !e->opt_force_v1 && !has_lora && f.W.layout == 1 && (f.W.wk == WK_BF16 || f.W.wk == WK_F16) &&
          f.W.N == 2 * pair_offset && pair_offset % 16 == 0;
 }
@@ -528,7 +588,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     // consumer_combine: the offer is taken by the call that the publish-only instantiation covers (gemm_skinny.hip, CC) --
     // <= 8 unrounded float32 rows with the RMSNorm deferred, a dense bf16 matrix as loaded, no LoRA, 2..8 K slices
     if (published != nullptr && f.W.wk == WK_BF16 && c.kx == 0 && f0.W.lora_b[0] == nullptr && f0.W.lora_b[1] == nullptr &&
-        c.rnd == RND_NONE && defer && rows <= 8) {
+        f0.W.bias == nullptr && c.rnd == RND_NONE && defer && rows <= 8) {      // (a bias is added where slices are combined: the last arriver)
       const int ks = gemm_skinny_ksplit(f.W, c, rows);
       if (ks >= 2 && ks <= 8) {
         MI_TRY(ensure_cc_pub(e, f.W.N));
@@ -1065,6 +1125,9 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
   if (d.quant_bits != 0 && d.quant_bits != 4 && d.quant_bits != 8) return fail(MI_ERR_UNSUPPORTED, "quant_bits must be 0, 4 or 8");
   if (d.hidden_size % 8 || d.intermediate_size % 8 || (d.num_heads * d.head_dim) % 8)
     return fail(MI_ERR_UNSUPPORTED, "hidden / intermediate sizes must be multiples of 8");
+  if (d.rope_traditional && d.arch == MI_ARCH_QWEN3)
+    return fail(MI_ERR_UNSUPPORTED, "rope_traditional with arch qwen3 is not supported (q_norm / k_norm would need the same regrouping)");
+  if (d.rope_traditional && d.head_dim % 2 != 0) return fail(MI_ERR_INVALID, "rope_traditional needs an even head_dim");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(MI_ERR_RUNTIME, "no HIP device available (this library has no CPU backend)");
@@ -1126,8 +1189,27 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
     const size_t n = strlen(suf);
     if (name.size() > n && name.compare(name.size() - n, n, suf) == 0) { base = name.substr(0, name.size() - n); kind = k; }
   };
-  strip(".weight", 0); strip(".scales", 1); strip(".biases", 2);
+  strip(".weight", 0); strip(".scales", 1); strip(".biases", 2); strip(".bias", 3);    // (".biases" does not end in ".bias")
   if (kind < 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  if (kind == 3) {       // nn.Linear(bias=True): only where the model has one -- anything else is an unmatched tensor
+    const std::string pre = "model.layers.";
+    const size_t dot = base.compare(0, pre.size(), pre) == 0 ? base.find('.', pre.size()) : std::string::npos;
+    int li = -1;
+    if (dot != std::string::npos) { try { li = std::stoi(base.substr(pre.size(), dot - pre.size())); } catch (...) { li = -1; } }
+    if (li < 0 || li >= d.num_layers) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+    const std::string sub = base.substr(dot + 1);
+    LayerW& l = e->layers[li];
+    FusedLinear* f = nullptr; int part = 0; bool attn = true;
+    if (sub == "self_attn.q_proj") { f = &l.qkv; part = 0; }
+    else if (sub == "self_attn.k_proj") { f = &l.qkv; part = 1; }
+    else if (sub == "self_attn.v_proj") { f = &l.qkv; part = 2; }
+    else if (sub == "self_attn.o_proj") { f = &l.o; }
+    else if (sub == "mlp.gate_proj") { f = &l.gate_up; part = 0; attn = false; }
+    else if (sub == "mlp.up_proj") { f = &l.gate_up; part = 1; attn = false; }
+    else if (sub == "mlp.down_proj") { f = &l.down; attn = false; }
+    if (f == nullptr || !(attn ? d.attention_bias : d.mlp_bias)) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+    return set_bias(e, *f, part, data, shape, ndim, dtype, on_device, name);
+  }
   const int H = d.hidden_size, I = d.intermediate_size, QD = d.num_heads * d.head_dim;
   if (base == "model.embed_tokens") return set_linear(e, e->embed, 0, H, kind, data, shape, ndim, dtype, on_device, name);
   if (base == "lm_head") {
@@ -1191,6 +1273,8 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
   MI_HIP(hipMalloc(&f->lora_b[slot], (size_t)rank * n * sizeof(float)));
   MI_TRY(copy_in(f->lora_a[slot], A, (size_t)K * rank * sizeof(float), on_device, e->stream));
   MI_TRY(copy_in(f->lora_b[slot], B, (size_t)rank * n * sizeof(float), on_device, e->stream));
+  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
+  if (d.rope_traditional && f == &l.qkv && row0 < QD + KD) MI_TRY(head_perm_inplace(e, f->lora_b[slot], (size_t)rank * n, d.head_dim, sizeof(float)));
   f->W.lora_a[slot] = f->lora_a[slot]; f->W.lora_b[slot] = f->lora_b[slot];
   f->W.lora_row0[slot] = row0; f->W.lora_n[slot] = n; f->W.lora_rank[slot] = rank; f->W.lora_scale[slot] = scale;
   return MI_OK;
@@ -1205,6 +1289,16 @@ int mi_engine_finalize(mi_engine* e) {
   for (int i = 0; i < d.num_layers; ++i) {
     LayerW& l = e->layers[i];
     const std::string p = "model.layers." + std::to_string(i);
+    {   // a set bias flag makes the `.bias` of each of its projections a required tensor
+      const struct { const FusedLinear* f; int part; const char* sub; int32_t want; } req[7] = {
+          {&l.qkv, 0, ".self_attn.q_proj.bias", d.attention_bias}, {&l.qkv, 1, ".self_attn.k_proj.bias", d.attention_bias},
+          {&l.qkv, 2, ".self_attn.v_proj.bias", d.attention_bias}, {&l.o, 0, ".self_attn.o_proj.bias", d.attention_bias},
+          {&l.gate_up, 0, ".mlp.gate_proj.bias", d.mlp_bias}, {&l.gate_up, 1, ".mlp.up_proj.bias", d.mlp_bias},
+          {&l.down, 0, ".mlp.down_proj.bias", d.mlp_bias}};
+      for (const auto& r : req)
+        if (r.want && !r.f->seen_bias[r.part]) return fail(MI_ERR_NOTFOUND, p + r.sub + " not set");
+    }
+    if (d.rope_traditional) MI_TRY(permute_qk_heads(e, l.qkv));      // in front of the tile-major repack
     MI_TRY(finalize_linear(e, l.qkv, H, p + ".self_attn.{q,k,v}_proj"));
     MI_TRY(finalize_linear(e, l.o, QD, p + ".self_attn.o_proj"));
     MI_TRY(finalize_linear(e, l.gate_up, H, p + ".mlp.{gate,up}_proj"));

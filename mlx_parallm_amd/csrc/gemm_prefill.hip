@@ -57,15 +57,27 @@ struct GemmParams {
   // few hundred tokens against N = 4096: 32 x 2..8 blocks); slice z leaves its float32 partial tile in ws[z][M][N] and
   // splitk_epilogue_kernel adds the slices in order and applies the epilogue
   int ksplit; float* ws;
+  // LinearW::bias ([N] float32, or null), added where an output element gets its epilogue -- once, after the K slices of a
+  // split launch are summed; bias2 = quantised weights (two roundings).  SwiGLU: gate bias[n], up bias[n + pair_offset].
+  const float* bias; int bias2;
 };
+
+// T(acc) of the 16-bit epilogues, with the bias when the matrix has one
+template <typename AT>
+__device__ __forceinline__ float round_biased(const GemmParams& p, int n, float acc) {
+  if (p.bias != nullptr) return add_bias<AT>(acc, p.bias[n], p.bias2 != 0, RND_NONE);
+  return (float)(AT)acc;
+}
 
 // the epilogues in float32 storage (PagedKVCache mode after layer 0: every op produces a float32 array)
 __device__ __forceinline__ void epi32_swiglu(const GemmParams& p, int m, int n, float gt, float up) {
+  if (p.bias != nullptr) { gt = add_bias<float>(gt, p.bias[n], false, RND_NONE); up = add_bias<float>(up, p.bias[n + p.pair_offset], false, RND_NONE); }
   const float sig = 1.0f / (1.0f + expf(-gt));
   const float sl = gt * sig;
   ((float*)p.out)[(size_t)m * p.ldo + n] = sl * up;
 }
 __device__ __forceinline__ void epi32_plain(const GemmParams& p, int m, int n, float y) {
+  if (p.bias != nullptr) y = add_bias<float>(y, p.bias[n], false, RND_NONE);
   if (p.epi == EPI_STORE) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
   else { float* h = (float*)p.resid; h[(size_t)m * p.ldo + n] = h[(size_t)m * p.ldo + n] + y; }
 }
@@ -203,7 +215,7 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmParams p) {
           const int n = bn * 64 + wn * 32 + j * 16 + c16;
           if (n >= p.pair_offset) continue;
           if (p.out32) { epi32_swiglu(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]); continue; }
-          const float gt = (float)(AT)acc[mt][j][r], up = (float)(AT)acc[mt][j + 2][r];
+          const float gt = round_biased<AT>(p, n, acc[mt][j][r]), up = round_biased<AT>(p, n + p.pair_offset, acc[mt][j + 2][r]);
           const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
           const float sl = (float)(AT)(gt * sig);
           out[(size_t)m * p.ldo + n] = (AT)(sl * up);
@@ -214,7 +226,7 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmParams p) {
           const int n = bn * BN + wn * 64 + nt * 16 + c16;
           if (n >= p.N) continue;
           if (p.out32) { epi32_plain(p, m, n, acc[mt][nt][r]); continue; }
-          const float y = (float)(AT)acc[mt][nt][r];
+          const float y = round_biased<AT>(p, n, acc[mt][nt][r]);
           if (p.epi == EPI_STORE) out[(size_t)m * p.ldo + n] = (AT)y;
           else {
             AT* h = (AT*)p.resid;
@@ -238,7 +250,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (p.out32) { epi32_plain(p, m, n + j, a[j]); continue; }
-    const float y = (float)(AT)a[j];
+    const float y = round_biased<AT>(p, n + j, a[j]);
     if (p.epi == EPI_STORE) ((AT*)p.out)[(size_t)m * p.ldo + n + j] = (AT)y;
     else { AT* h = (AT*)p.resid; h[(size_t)m * p.ldo + n + j] = (AT)((float)h[(size_t)m * p.ldo + n + j] + y); }
   }
@@ -263,7 +275,7 @@ __device__ __forceinline__ void tile256_epilogue(const GemmParams& p, f32x4 (&ac
           const int n = bn * 128 + wn * 32 + j * 16 + c16;
           if (n >= p.pair_offset) continue;
           if (p.out32) { epi32_swiglu(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]); continue; }
-          const float gt = (float)(AT)acc[mt][j][r], up = (float)(AT)acc[mt][j + 2][r];
+          const float gt = round_biased<AT>(p, n, acc[mt][j][r]), up = round_biased<AT>(p, n + p.pair_offset, acc[mt][j + 2][r]);
           const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
           const float sl = (float)(AT)(gt * sig);
           out[(size_t)m * p.ldo + n] = (AT)(sl * up);
@@ -274,7 +286,7 @@ __device__ __forceinline__ void tile256_epilogue(const GemmParams& p, f32x4 (&ac
           const int n = bn * BN2 + wn * 64 + nt * 16 + c16;
           if (n >= p.N) continue;
           if (p.out32) { epi32_plain(p, m, n, acc[mt][nt][r]); continue; }
-          const float y = (float)(AT)acc[mt][nt][r];
+          const float y = round_biased<AT>(p, n, acc[mt][nt][r]);
           if (p.epi == EPI_STORE) out[(size_t)m * p.ldo + n] = (AT)y;
           else {
             AT* h = (AT*)p.resid;
@@ -310,8 +322,10 @@ __device__ __forceinline__ void tile256_epilogue_resid(const GemmParams& p, f32x
         const int m = m0 + wm * 128 + mt * 16 + 4 * g + r;
         const int n = bn * BN2 + wn * 64 + nt * 16 + c16;
         if (m >= p.M || n >= p.N) continue;
-        if constexpr (std::is_same<HT, float>::value) h[(size_t)m * p.ldo + n] = hv[r][nt] + acc[mt][nt][r];
-        else h[(size_t)m * p.ldo + n] = (AT)((float)hv[r][nt] + (float)(AT)acc[mt][nt][r]);
+        if constexpr (std::is_same<HT, float>::value) {
+          const float y = p.bias != nullptr ? add_bias<float>(acc[mt][nt][r], p.bias[n], false, RND_NONE) : acc[mt][nt][r];
+          h[(size_t)m * p.ldo + n] = hv[r][nt] + y;
+        } else h[(size_t)m * p.ldo + n] = (AT)((float)hv[r][nt] + round_biased<AT>(p, n, acc[mt][nt][r]));
       }
   }
 }
@@ -962,6 +976,7 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
     if (hilo) p.kw = 2 * kt;
   }
   p.epi = c.epi; p.out = c.out; p.ldo = c.ldo; p.resid = c.resid; p.pair_offset = c.pair_offset;
+  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
   const bool sw = c.epi == EPI_SWIGLU;
   const int ncols = sw ? c.pair_offset : W.N;
   // The 256 x 256 tile only where its grid fills the chip: at 8 x 1024 rows every linear has >= 512 blocks, but one prompt

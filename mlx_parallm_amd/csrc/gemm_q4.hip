@@ -588,6 +588,7 @@ static Q4Plan q4_plan(const LinearW& W, const GemvCall& c, size_t rows) {
 // int4 (group 64) weights, 16-bit activations, 17..128 rows
 bool gemm_q4_supported(const LinearW& W, const GemvCall& c, size_t rows) {
   if (c.force_v1 || W.layout != 1 || c.rnd != RND_NONE) return false;
+  if (W.bias != nullptr) return false;            // a biased linear stays on skinny_kernel's int4 instantiations
   const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.group == 64 &&
                   W.K % 128 == 0;
   if (!q4 || rows < 17 || rows > 128 || c.ldx % 8 != 0) return false;

@@ -99,6 +99,7 @@ struct SkinnyParams {
   const float* lora_b0; const float* lora_b1;
   int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
   int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
+  const float* bias; int bias2;     // LinearW::bias, added where the K slices are combined (once); bias2 = quantised weights
 #ifdef MI_SK_TRACE
   unsigned long long* trace;       // debug build: [workgroup][8] wall-clock stamps of this launch (tools/debug/skinny_trace.py)
 #endif
@@ -120,14 +121,22 @@ struct SkinnyParams {
 // next launch (the decode attention's prologue) adds the slices.
 // It is selected by a TAG in place of the activation type (bf16_publish, a bf16): the kernel keeps its template signature,
 // and every other instantiation its name, code and registers.
+// BIAS (a linear with LinearW::bias): the same way, tags bf16_bias / f16_bias -- the epilogue adds the bias where the K slices
+// are combined; a model without biases runs the instantiations it always ran (a load under a run-time null check in the
+// epilogue cost the int4 decode step 0.3 %).
 struct bf16_publish {};
-template <typename A> struct sk_act { using type = A; static constexpr int cc = 0; };
-template <> struct sk_act<bf16_publish> { using type = bf16; static constexpr int cc = 1; };
+struct bf16_bias {};
+struct f16_bias {};
+template <typename A> struct sk_act { using type = A; static constexpr int cc = 0; static constexpr bool bias = false; };
+template <> struct sk_act<bf16_publish> { using type = bf16; static constexpr int cc = 1; static constexpr bool bias = false; };
+template <> struct sk_act<bf16_bias> { using type = bf16; static constexpr int cc = 0; static constexpr bool bias = true; };
+template <> struct sk_act<f16_bias> { using type = f16; static constexpr int cc = 0; static constexpr bool bias = true; };
 
 template <typename ATG, int QB, int MT, bool SWIGLU, bool X32 = false>
 __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT >= 5 || (X32 && QB == 8 && MT == 2)) ? 2 : 4) void skinny_kernel(const SkinnyParams p) {
   using AT = typename sk_act<ATG>::type;
   constexpr int CC = sk_act<ATG>::cc;
+  constexpr bool BIAS = sk_act<ATG>::bias;
   static_assert(CC == 0 || (CC == 1 && X32 && QB == 0 && MT == 1 && !SWIGLU), "consumer_combine: 0, or 1 on the float32, 16-row, dense, plain instantiation");
   constexpr bool Q4 = QB == 4, Q8 = QB == 8, QUANT = QB != 0;
   static_assert(!X32 || MT <= 2, "float32 activations: 16- and 32-row instantiations");
@@ -755,12 +764,17 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
         const float rsm = dn ? rs_row[ml] : 1.0f;
         y0 = scale_row(y0, rsm);
         if constexpr (SWIGLU) {
-          const float gt = round_rt(y0, p.rnd), up = round_rt(acc[NA - 1][mt][r] * rsm, p.rnd);
+          float gt = round_rt(y0, p.rnd), up = round_rt(acc[NA - 1][mt][r] * rsm, p.rnd);
+          if constexpr (BIAS) {                  // y = rs * acc + b: the row scale first
+            gt = add_bias<float>(y0, p.bias[n], p.bias2 != 0, p.rnd);
+            up = add_bias<float>(scale_row(acc[NA - 1][mt][r], rsm), p.bias[n + p.pair_offset], p.bias2 != 0, p.rnd);
+          }
           const float sig = round_rt(1.0f / (1.0f + expf(-gt)), p.rnd);
           const float sl = round_rt(gt * sig, p.rnd);
           o32[(size_t)m * p.ldo + n] = round_rt(sl * up, p.rnd);
         } else {
           float y = round_rt(y0, p.rnd);
+          if constexpr (BIAS) y = add_bias<float>(y0, p.bias[n], p.bias2 != 0, p.rnd);
           if (p.lora_t != nullptr) {             // LoRALinear in this mode: y + T(scale (x A) B), the term in float32 (App. A.6)
 #pragma unroll
             for (int sl = 0; sl < 2; ++sl) {
@@ -790,12 +804,17 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
         continue;
       }
       if constexpr (SWIGLU) {
-        const float gt = (float)(AT)y0, up = (float)(AT)acc[NA - 1][mt][r];
+        float gt = (float)(AT)y0, up = (float)(AT)acc[NA - 1][mt][r];
+        if constexpr (BIAS) {
+          gt = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
+          up = add_bias<AT>(acc[NA - 1][mt][r], p.bias[n + p.pair_offset], p.bias2 != 0, RND_NONE);
+        }
         const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
         const float sl = (float)(AT)(gt * sig);
         out[(size_t)m * p.ldo + n] = (AT)(sl * up);
       } else {
         float y = (float)(AT)y0;
+        if constexpr (BIAS) y = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
         if (p.lora_t != nullptr) {
 #pragma unroll
           for (int sl = 0; sl < 2; ++sl) {
@@ -1084,6 +1103,7 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
   p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
   p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
   p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
+  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
   const int qb = (W.wk == WK_Q8_BF16 || W.wk == WK_Q8_F16) ? 8 : wk_is_quant(W.wk) ? 4 : 0;
   const bool sw = c.epi == EPI_SWIGLU;
   const int grid = pl.nslab > 1 ? (pl.ngroups * pl.ksplit + 7) / 8 * 8 * pl.nslab : pl.ngroups * pl.ksplit;
@@ -1099,8 +1119,8 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
   const bool publish = c.cc_pub != nullptr;
   if (publish) {
     const bool lora = c.lora_t != nullptr || W.lora_b[0] != nullptr || W.lora_b[1] != nullptr;
-    if (c.act != MI_F32 || c.rnd != RND_NONE || qb != 0 || sw || pl.mt != 1 || pl.nslab != 1 || rows > 8 || p.kx != W.K || lora)
-      return fail(MI_ERR_INVALID, "gemm_skinny: consumer_combine needs <= 8 rows of float32 on a dense bf16 linear without LoRA");
+    if (c.act != MI_F32 || c.rnd != RND_NONE || qb != 0 || sw || pl.mt != 1 || pl.nslab != 1 || rows > 8 || p.kx != W.K || lora || W.bias != nullptr)
+      return fail(MI_ERR_INVALID, "gemm_skinny: consumer_combine needs <= 8 rows of float32 on a dense bf16 linear without LoRA or bias");
     if (!(defer_norm && pl.ksplit > 1 && pl.ksplit <= 8 && c.epi == EPI_STORE && c.cc_pub_sq != nullptr))
       return fail(MI_ERR_INVALID, "gemm_skinny: publish-only mode needs the deferred RMSNorm, a plain store and 2..8 K slices");
     p.pub = c.cc_pub; p.pub_sq = c.cc_pub_sq;
@@ -1114,15 +1134,22 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
       MI_HIP(hipGetLastError());
       return MI_OK;
     };
-#define GO32(QBV) do { \
-      if (pl.mt == 1) return sw ? launch32(skinny_kernel<bf16, QBV, 1, true, true>) : launch32(skinny_kernel<bf16, QBV, 1, false, true>); \
-      return sw ? launch32(skinny_kernel<bf16, QBV, 2, true, true>) : launch32(skinny_kernel<bf16, QBV, 2, false, true>); } while (0)
+#define GO32(T, QBV) do { \
+      if (pl.mt == 1) return sw ? launch32(skinny_kernel<T, QBV, 1, true, true>) : launch32(skinny_kernel<T, QBV, 1, false, true>); \
+      return sw ? launch32(skinny_kernel<T, QBV, 2, true, true>) : launch32(skinny_kernel<T, QBV, 2, false, true>); } while (0)
     if (publish) return launch32(skinny_kernel<bf16_publish, 0, 1, false, true>);
-    if (qb == 4) GO32(4);
-    if (qb == 8) GO32(8);
-    GO32(0);
+    if (W.bias != nullptr) {
+      if (qb == 4) GO32(bf16_bias, 4);
+      if (qb == 8) GO32(bf16_bias, 8);
+      GO32(bf16_bias, 0);
+    }
+    if (qb == 4) GO32(bf16, 4);
+    if (qb == 8) GO32(bf16, 8);
+    GO32(bf16, 0);
 #undef GO32
   }
+  if (W.bias != nullptr)
+    return c.act == MI_BF16 ? launch_at<bf16_bias>(p, qb, sw, pl.mt, grid, st) : launch_at<f16_bias>(p, qb, sw, pl.mt, grid, st);
   return c.act == MI_BF16 ? launch_at<bf16>(p, qb, sw, pl.mt, grid, st) : launch_at<f16>(p, qb, sw, pl.mt, grid, st);
 }
 

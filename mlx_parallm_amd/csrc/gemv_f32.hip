@@ -315,6 +315,7 @@ bool gemv_f32_supported(const LinearW& W, const GemvCall& c) {
   if (c.act != MI_F32 || c.rnd != RND_NONE || c.kx != 0) return false;
   if (c.M < 1 || c.M > 8) return false;
   if (W.lora_b[0] != nullptr || W.lora_b[1] != nullptr || c.lora_t != nullptr) return false;
+  if (W.bias != nullptr) return false;            // a biased linear runs on the split-K kernel (gemm_skinny.hip)
   if (W.K < 32 || W.K % 32 != 0 || W.N < 16 || W.N % 16 != 0 || c.ldx % 4 != 0) return false;
   if (c.pro != PRO_NONE && (c.pro != PRO_NORM || c.norm_w == nullptr)) return false;
   return c.epi == EPI_STORE || c.epi == EPI_STORE_F32 || c.epi == EPI_RESID || c.epi == EPI_SWIGLU_GU8;

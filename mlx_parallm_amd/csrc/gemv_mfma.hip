@@ -57,6 +57,15 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_gu8_kernel(MfmaParams p) {
   ph.run();
 }
 
+// ... and for a linear with a bias (LinearW::bias): Phase's BIAS instantiation
+template <typename AT, bool Q4, int MB, bool SWIGLU, int NW, int J, bool DB>
+__global__ __launch_bounds__(NW * 64) void gemv_mfma_bias_kernel(MfmaParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Phase<AT, Q4, MB, SWIGLU, NW, J, DB, true> ph(p, smem_raw);
+  if (ph.ntiles <= 0) return;
+  ph.run();
+}
+
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
 
 int cu_count() {
@@ -75,6 +84,7 @@ int launch_j(const MfmaParams& p, hipStream_t st) {
   if constexpr (!Q4 && !SWIGLU) {
     if (p.epi == EPI_SWIGLU_GU8) kern = gemv_mfma_gu8_kernel<AT, MB, NW, J, DB>;
   }
+  if (p.bias != nullptr) kern = gemv_mfma_bias_kernel<AT, Q4, MB, SWIGLU, NW, J, DB>;     // (never with EPI_SWIGLU_GU8: launch_gemv_mfma)
   constexpr int NA = SWIGLU ? 2 : 1;
   const size_t lds = phase_lds_bytes<NW, NA, Q4>(p.kc, MB, DB ? 2 : 1);
   MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -138,6 +148,7 @@ MfmaParams make_params(const LinearW& W, const GemvCall& c) {
   p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
   p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
   p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
+  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
   return p;
 }
 
@@ -165,6 +176,8 @@ bool gemv_mfma_supported(const LinearW& W, const GemvCall& c) {
 }
 
 int launch_gemv_mfma(const LinearW& W, const GemvCall& c, hipStream_t st) {
+  // the row-interleaved gate|up copy has no biased form (engine: gu8_wanted declines, the paired-tile SwiGLU kernel runs)
+  if (c.epi == EPI_SWIGLU_GU8 && W.bias != nullptr) return fail(MI_ERR_UNSUPPORTED, "gemv_mfma: no bias on the row-interleaved gate|up copy");
   const bool q4 = wk_is_quant(W.wk);
   const MfmaParams p = make_params(W, c);
   g_ev_start = (hipEvent_t)c.ev_start; g_ev_stop = (hipEvent_t)c.ev_stop;

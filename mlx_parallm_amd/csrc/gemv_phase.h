@@ -25,6 +25,7 @@ struct MfmaParams {
   const float* lora_b0; const float* lora_b1;
   int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
   int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
+  const float* bias; int bias2;     // LinearW::bias; bias2 = quantised weights (two roundings)
 #ifdef MI_SK_TRACE
   unsigned long long* trace;       // debug build (tools/debug/build_trace_lib.sh): [workgroup][16] wall-clock stamps
 #endif
@@ -152,7 +153,9 @@ __host__ __device__ constexpr int phase_nbuf(int K, int kc, int MB, bool q4) { (
 // activations), so a workgroup has its whole batch -- 128 KiB for a dense bf16 tile at K = 4096 --
 // in flight at once.  The next batch is issued right after the MFMAs of the current one retire its
 // registers, i.e. before the cross-wave reduction and the epilogue, which keeps HBM busy across tiles.
-template <typename AT, bool Q4, int MB, bool SWIGLU, int NW, int J, bool DB = false>
+// BIAS: the epilogue adds MfmaParams::bias (an instantiation of its own -- gemv_mfma_bias_kernel -- so that the kernels of a
+// model without biases keep their code: a load under a run-time null check made every launch ~0.1 % slower)
+template <typename AT, bool Q4, int MB, bool SWIGLU, int NW, int J, bool DB = false, bool BIAS = false>
 struct Phase {
   static constexpr int NT = NW * 64;
   static constexpr int NA = SWIGLU ? 2 : 1;
@@ -387,7 +390,11 @@ struct Phase {
         if (m < p.M) {
           AT* out = (AT*)p.out;
           if constexpr (SWIGLU) {
-            const float gt = (float)(AT)y0, up = (float)(AT)y1;
+            float gt = (float)(AT)y0, up = (float)(AT)y1;
+            if constexpr (BIAS) {                  // gate and up each get their own bias in front of silu(g) * u
+              gt = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
+              up = add_bias<AT>(y1, p.bias[n + p.pair_offset], p.bias2 != 0, RND_NONE);
+            }
             const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
             const float sl = (float)(AT)(gt * sig);
             store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)(sl * up));
@@ -404,6 +411,7 @@ struct Phase {
             }
           } else {
             float y = (float)(AT)y0;
+            if constexpr (BIAS) y = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);       // in front of the LoRA term
             if (p.lora_t != nullptr) {
 #pragma unroll
               for (int sl = 0; sl < 2; ++sl) {

@@ -41,6 +41,7 @@ struct GemvParams {
   int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
   int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
   int lora_rnd;
+  const float* bias; int bias2;     // LinearW::bias; bias2 = quantised weights (two roundings)
 };
 
 // ---- 8 consecutive weights of one row, as fp32 -------------------------------------------
@@ -231,8 +232,12 @@ __global__ __launch_bounds__(NTHR) void gemv_v1_kernel(GemvParams p) {
     AT* out = (AT*)p.out;
     if (p.epi == EPI_SWIGLU) {
       // nn.silu(gate) * up, every op rounded to the activation dtype (llama.py:165)
-      const float g = to_f32(store_act<AT>(mine[0], p.rnd));
-      const float u = to_f32(store_act<AT>(mine[1], p.rnd));
+      float g = to_f32(store_act<AT>(mine[0], p.rnd));
+      float u = to_f32(store_act<AT>(mine[1], p.rnd));
+      if (p.bias != nullptr) {
+        g = add_bias<AT>(mine[0], p.bias[rows[a][0]], p.bias2 != 0, p.rnd);
+        u = add_bias<AT>(mine[1], p.bias[rows[a][1]], p.bias2 != 0, p.rnd);
+      }
       const float sig = to_f32(store_act<AT>(1.0f / (1.0f + expf(-g)), p.rnd));
       const float s = to_f32(store_act<AT>(g * sig, p.rnd));
       out[(size_t)m * p.ldo + rows[a][0]] = store_act<AT>(s * u, p.rnd);
@@ -243,6 +248,7 @@ __global__ __launch_bounds__(NTHR) void gemv_v1_kernel(GemvParams p) {
       const int n = rows[a][r];
       if (r == 1 && 2 * ((blockIdx.x * 4 + wave) * PW + a) + 1 >= p.N) continue;
       float y = to_f32(store_act<AT>(mine[r], p.rnd));
+      if (p.bias != nullptr) y = add_bias<AT>(mine[r], p.bias[n], p.bias2 != 0, p.rnd);
       // LoRALinear: y + (scale * ((x A) B)).astype(x.dtype)
       if (p.lora_t != nullptr) {
 #pragma unroll
@@ -431,6 +437,7 @@ GemvParams make_params(const LinearW& W, const GemvCall& c) {
   p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
   p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
   p.lora_rnd = RND_NONE;
+  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
   return p;
 }
 

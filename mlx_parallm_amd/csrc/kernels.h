@@ -19,6 +19,10 @@ struct LinearW {
   const float* lora_b[2] = {nullptr, nullptr};
   int lora_row0[2] = {0, 0}, lora_n[2] = {0, 0}, lora_rank[2] = {0, 0};
   float lora_scale[2] = {0.f, 0.f};
+  // nn.Linear(bias=True) / nn.QuantizedLinear(bias=True) (llama.py:59-67,155-162): [N] float32, the checkpoint's values,
+  // concatenated across the parts of a fused matrix; null = no bias.  Dense weights: y = T(acc + b) (mx.addmm, one
+  // rounding); quantised weights: y = T(T(acc) + b) (quantized_matmul, then + bias) -- add_bias() in common.h.
+  const float* bias = nullptr;
 };
 
 enum : int { PRO_NONE = 0, PRO_NORM = 1 };
@@ -281,6 +285,11 @@ int launch_sample(const SampleCall& c, hipStream_t st);
 int launch_advance_offsets(int32_t* offsets, const int32_t* rows, int B, int L, hipStream_t st);
 // dst[i][:] = src[idx[i]][:] for n rows of row_bytes (a multiple of 16) each; idx on the device
 int launch_gather_rows(const void* src, size_t row_bytes, const int32_t* idx, int n, void* dst, hipStream_t st);
+// rope_traditional (llama.py:77-82) at load time: dst row (h D + j) = src row (h D + 2 j), dst row (h D + D/2 + j) = src row
+// (h D + 2 j + 1) for j < D/2, over nrows = heads x D rows of row_bytes each (src != dst).  Applied alike to the q and k rows of
+// a q|k|v matrix (codes, scales, quantisation biases), to their linear biases and to the columns of a LoRA B (as rows of
+// 4 bytes, nrows = rank x n), it turns the interleaved rotation into the half-split one of the kernels; q.k is unchanged.
+int launch_head_perm_rows(const void* src, void* dst, size_t nrows, int D, size_t row_bytes, hipStream_t st);
 int launch_rope_tables(float* cos_tab, float* sin_tab, int max_pos, int D, float base, float scale,
                        hipStream_t st);
 int launch_convert(const void* src, int src_dt, void* dst, int dst_dt, size_t n, hipStream_t st);

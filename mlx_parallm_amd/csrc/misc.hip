@@ -573,6 +573,29 @@ int launch_gather_rows(const void* src, size_t row_bytes, const int32_t* idx, in
   return MI_OK;
 }
 
+// rope_traditional: rows of a [nrows][row_u16 x 2 bytes] array regrouped inside every run of D rows (one head), new row j <-
+// old row 2 j, new row D/2 + j <- old row 2 j + 1: the interleaved pairs (2 i, 2 i + 1) become the half-split pairs
+// (i, i + D/2) that the RoPE kernels rotate.  One thread per 16-bit unit of the destination (load time only).
+__global__ __launch_bounds__(256) void head_perm_rows_kernel(const uint16_t* src, uint16_t* dst, size_t nrows, int D, size_t row_u16) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nrows * row_u16) return;
+  const size_t row = i / row_u16, col = i - row * row_u16;
+  const int j = (int)(row % (size_t)D), half = D / 2;
+  const size_t srow = row - j + (j < half ? 2 * j : 2 * (j - half) + 1);
+  dst[i] = src[srow * row_u16 + col];
+}
+
+int launch_head_perm_rows(const void* src, void* dst, size_t nrows, int D, size_t row_bytes, hipStream_t st) {
+  if (D < 2 || D % 2 != 0 || nrows % (size_t)D != 0 || row_bytes % 2 != 0)
+    return fail(MI_ERR_INVALID, "head_perm_rows: whole heads of an even head_dim, rows of whole 16-bit units");
+  const size_t total = nrows * (row_bytes / 2);
+  if (total == 0) return MI_OK;
+  hipLaunchKernelGGL(head_perm_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint16_t*)src,
+                     (uint16_t*)dst, nrows, D, row_bytes / 2);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
 int launch_advance_offsets(int32_t* offsets, const int32_t* rows, int B, int L, hipStream_t st) {
   hipLaunchKernelGGL(advance_offsets_kernel, dim3(1), dim3(64 * ((B + 63) / 64)), 0, st, offsets, rows, B, L);
   MI_HIP(hipGetLastError());

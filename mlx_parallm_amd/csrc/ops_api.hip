@@ -31,6 +31,7 @@ LinearW to_linear(const mi_op_linear* w) {
   W.wk = w->wk; W.w = w->w; W.scales = w->scales; W.biases = w->biases; W.N = w->N; W.K = w->K;
   W.group = w->group > 0 ? w->group : 64;
   W.layout = w->layout;
+  W.bias = w->bias;
   return W;
 }
 

@@ -238,6 +238,9 @@ class Engine:
         d.quant_bits = int(q["bits"]) if q else 0
         d.quant_group_size = int(q["group_size"]) if q else 0
         d.max_positions = int(max_positions or min(int(config.get("max_position_embeddings", 4096)), 32768))
+        d.attention_bias = int(bool(config.get("attention_bias", False)))            # llama.py:59-67
+        d.mlp_bias = int(bool(config.get("mlp_bias", False)))                        # llama.py:155-162
+        d.rope_traditional = int(bool(config.get("rope_traditional", False)))        # llama.py:77-82
         self.desc = d
         self.config = dict(config)
         self.model_type = mt

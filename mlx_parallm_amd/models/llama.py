@@ -47,10 +47,6 @@ class ModelArgs(BaseModelArgs):
             elif "rope_type" in self.rope_scaling:
                 if self.rope_scaling["rope_type"] not in ["llama3", "linear"]:
                     raise ValueError(f"rope_scaling 'rope_type' {self.rope_scaling['rope_type']} not supported")
-        if self.attention_bias or self.mlp_bias:
-            raise NotImplementedError("attention_bias / mlp_bias are not supported by the MI355X engine")
-        if self.rope_traditional:
-            raise NotImplementedError("rope_traditional=True is not supported by the MI355X engine")
 
 
 class _LayerStub:

@@ -36,8 +36,10 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
                  intermediate_size: int, num_attention_heads: int, num_key_value_heads: Optional[int],
                  rope_theta: float, tie_word_embeddings: bool, quantization: Optional[Dict[str, Any]],
                  head_dim: Optional[int] = None, rms_norm_eps: float = 1e-6,
-                 max_position_embeddings: int = 4096) -> Dict[str, Any]:
-    """build_tiny_model.py:70-101 (+ head_dim / max_position_embeddings for qwen3)."""
+                 max_position_embeddings: int = 4096, attention_bias: bool = False, mlp_bias: bool = False,
+                 rope_traditional: bool = False) -> Dict[str, Any]:
+    """build_tiny_model.py:70-101 (+ head_dim / max_position_embeddings for qwen3, and the three ModelArgs switches
+    of llama.py:29-32)."""
     cfg: Dict[str, Any] = {
         "model_type": model_type,
         "hidden_size": int(hidden_size),
@@ -48,10 +50,10 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
         "rms_norm_eps": float(rms_norm_eps),
         "vocab_size": int(vocab_size),
         "rope_theta": float(rope_theta),
-        "rope_traditional": False,
+        "rope_traditional": bool(rope_traditional),
         "rope_scaling": None,
-        "attention_bias": False,
-        "mlp_bias": False,
+        "attention_bias": bool(attention_bias),
+        "mlp_bias": bool(mlp_bias),
         "tie_word_embeddings": bool(tie_word_embeddings),
         "max_position_embeddings": int(max_position_embeddings),
     }
@@ -66,7 +68,9 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
 def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", norm_jitter: float = 0.0,
                  weight_std: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """Random weights keyed like an MLX / HF checkpoint.  ``weight_std``: N(0, std) instead of
-    the MLX initialisers (SURVEY §8d synthetic weights)."""
+    the MLX initialisers (SURVEY §8d synthetic weights).  With ``attention_bias`` / ``mlp_bias`` in ``cfg`` the
+    projections get a 1-D ``.bias`` each, drawn at about the RMS of the layer's outputs for inputs of unit RMS
+    (|W x| ~ sqrt(K) x the RMS of W's entries) -- nn.Linear's own U(-1/sqrt(K), 1/sqrt(K)) would vanish against it."""
     rng = np.random.default_rng(seed)
     H, I, V = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
     nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
@@ -80,6 +84,11 @@ def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", nor
             s = 1.0 / np.sqrt(k)
             a = rng.uniform(-s, s, size=(n, k)).astype(np.float32)
         return torch.from_numpy(a).to(tdt)
+
+    def bias(weight):
+        n, k = weight.shape
+        s = float(weight.to(torch.float32).pow(2).mean().sqrt()) * np.sqrt(k)
+        return torch.from_numpy((rng.standard_normal(n, dtype=np.float32) * np.float32(s))).to(tdt)
 
     def norm(n):
         a = np.ones(n, dtype=np.float32)
@@ -108,6 +117,13 @@ def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", nor
     w["model.norm.weight"] = norm(H)
     if not cfg["tie_word_embeddings"]:
         w["lm_head.weight"] = lin(V, H)
+    # (drawn after every weight, so that the weights of a seed do not depend on the bias flags)
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"model.layers.{i}."
+        projs = (["self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj"] if cfg.get("attention_bias") else []) + \
+                (["mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"] if cfg.get("mlp_bias") else [])
+        for name in projs:
+            w[p + name + ".bias"] = bias(w[p + name + ".weight"])
     return w
 
 
@@ -153,7 +169,8 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
                      q_group_size: int = 64, vocab_size: Optional[int] = None, dtype: str = "float32",
                      head_dim: Optional[int] = None, with_tokenizer: bool = True, norm_jitter: float = 0.0,
                      weight_std: Optional[float] = None, rms_norm_eps: float = 1e-6,
-                     max_position_embeddings: int = 4096) -> Dict[str, Any]:
+                     max_position_embeddings: int = 4096, attention_bias: bool = False, mlp_bias: bool = False,
+                     rope_traditional: bool = False) -> Dict[str, Any]:
     """scripts/build_tiny_model.py:104-160.  Returns the config dict it wrote."""
     from safetensors.torch import save_file
 
@@ -169,7 +186,8 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
                        num_hidden_layers=layers, intermediate_size=intermediate_size,
                        num_attention_heads=heads, num_key_value_heads=kv_heads, rope_theta=rope_theta,
                        tie_word_embeddings=tie_word_embeddings, quantization=quant, head_dim=head_dim,
-                       rms_norm_eps=rms_norm_eps, max_position_embeddings=max_position_embeddings)
+                       rms_norm_eps=rms_norm_eps, max_position_embeddings=max_position_embeddings,
+                       attention_bias=attention_bias, mlp_bias=mlp_bias, rope_traditional=rope_traditional)
     w = init_weights(cfg, seed=seed, dtype=dtype, norm_jitter=norm_jitter, weight_std=weight_std)
     if quantize_model:
         w = quantize_weights(w, q_group_size, q_bits)

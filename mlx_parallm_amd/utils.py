@@ -364,6 +364,8 @@ def _checkpoint_dtype(weights: Dict[str, Any]) -> str:
         if k.endswith(".scales"):
             return {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}[t.dtype]
     for k, t in weights.items():
+        if k.endswith(".bias") and t.ndim == 1:         # a linear bias keeps its own dtype through convert(): not the model's
+            continue
         if t.dtype in (torch.float32, torch.bfloat16, torch.float16):
             return {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}[t.dtype]
     return "float32"
