@@ -100,6 +100,11 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
  * row-interleaved copy the engine keeps is made inside the call).  a->pro may be MI_PRO_NORM: the row scale is applied in
  * the epilogue.  iters >= 1 also times that many back-to-back launches into *avg_ms. */
 int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
+/* the whole-K form of that kernel (the o_proj launch of the float32-KV decode step) on its own: the same operator and, output
+ * for output, the same bits, for a narrow linear -- N / 16 at most the device's compute units (one 16-row tile per workgroup),
+ * K <= 4096, a->pro = MI_PRO_NONE, MI_EPI_STORE / MI_EPI_STORE_F32 / MI_EPI_RESID.  Anything else is MI_ERR_UNSUPPORTED.
+ * iters >= 1 also times that many back-to-back launches into *avg_ms. */
+int mi_op_gemv_f32_whole(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* gemm_prefill.hip on its own: the tile GEMM of the prefill call (generate_step's first model call, utils.py:243-262: every
  * nn.Linear over B x L rows at once).  a->M rows of 16-bit activations, tile-major dense 16-bit weights, a->pro =
  * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms.

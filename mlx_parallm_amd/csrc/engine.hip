@@ -542,7 +542,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
   // float32-KV decode step of <= 8 sequences, the WIDE linears (at least 4 tiles per CU: gate|up on its row-interleaved copy,
   // lm_head): one pass over W with one workgroup per CU and no K split (gemv_f32.hip) instead of the 9..128-row kernel below,
   // whose tile groups x K slices leave CUs idle at this shape and meet through a workspace.  RMSNorm is deferred to the
-  // epilogue there.  Narrow linears (q|k|v, o, down: 1-1.5 tiles per CU) stay below -- measured, DESIGN §8d.
+  // epilogue there.  Narrow linears (q|k|v, down: 1-1.5 tiles per CU) stay below -- measured, DESIGN §8d.
   if (e->opt_skinny_gemm && e->cur_L == 1 && rows <= 8 && c.act == MI_F32 && c.rnd == RND_NONE && c.kx == 0) {
     GemvCall cw = c;
     cw.M = (int)rows;
@@ -556,6 +556,13 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       Prof pr(e, prof);
       if (cw.pro == PRO_NORM && !e->opt_defer_norm) MI_TRY(norm_into_xn(e, cw, rows, KT, cw.rnd));
       return launch_gemv_f32(wv, cw, e->stream);
+    }
+    // ... and the one NARROW linear whose whole tile a workgroup can request at once (K <= 4096, at most one tile per CU,
+    // no prologue: o_proj of Mistral-7B): one tile per workgroup over the whole K, no K split, no partial tiles, no arrival
+    // counter (gemv_f32.hip, the whole-K form).  Below half the CUs the K split is what fills the chip.
+    if (f.W.N / 16 > gemv_cu_count() / 2 && gemv_f32_whole_supported(f.W, cw)) {
+      Prof pr(e, prof);
+      return launch_gemv_f32_whole(f.W, cw, e->stream);
     }
   }
   // decode steps: the streaming kernel up to 96 rows for dense weights -- above that the K-split tile GEMM is ahead

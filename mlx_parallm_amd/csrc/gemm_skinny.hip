@@ -27,9 +27,11 @@
 // would otherwise need a full pass over its rows before the first MFMA.
 //
 // Float32 activations (the float32-KV mode of a bf16 model, X32 instantiations): the decode step's WIDE dense linears at
-// <= 8 rows (gate|up, lm_head: at least 4 tiles per CU) run on gemv_f32.hip -- one pass, no K split.  The float32 calls
-// that still reach this kernel: 9..32 rows, the rounded layer-0 calls, the narrow linears (q|k|v, o, down: the K split over
-// workgroups is what fills the CUs there), quantised and [hi | lo] matrices, LoRA layers.
+// <= 8 rows (gate|up, lm_head: at least 4 tiles per CU) run on gemv_f32.hip -- one pass, no K split -- and so does the one
+// narrow linear whose whole tile a workgroup can request at once (o_proj where N / 16 is between half the CUs and all of
+// them and K <= 4096: gemv_f32_whole_kernel).  The float32 calls that still reach this kernel: 9..32 rows, the rounded
+// layer-0 calls, the other narrow linears (q|k|v, down, a narrower or longer o_proj: the K split over workgroups is what
+// fills the CUs there), biased, quantised and [hi | lo] matrices, LoRA layers.
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -985,7 +987,8 @@ int launch_at(const SkinnyParams& p, int qb, bool swiglu, int mt, int grid, hipS
 // 4181 -> 5973, Qwen3-14B bf16 1401 -> 2386; at 8 rows and below gemv_mfma.hip wins, 3.59 vs 3.95 ms/step).
 // The float32-activation calls have no such hand-over inside this file: gemm_skinny_supported() takes them from 1 row up,
 // and the engine routes the wide <= 8-row ones (>= 4 tiles per CU, dense bf16, no rounding) to gemv_f32.hip in front of it:
-// 3.82 vs 4.07 ms/step; the narrow ones lose there (q|k|v 19.3 vs 15.2 us, o 16.2 vs 10.8, down 40.6 vs 23.1) and stay.
+// 3.82 vs 4.07 ms/step; the narrow ones lose there (q|k|v 19.3 vs 15.2 us, o 16.2 vs 10.8, down 40.6 vs 23.1) and stay,
+// except an o_proj of one tile per CU and K <= 4096, which the router gives to gemv_f32.hip's whole-K form.
 constexpr int SKINNY_MIN_ROWS = 9;
 
 bool gemm_skinny_supported(const LinearW& W, const GemvCall& c, size_t rows) {

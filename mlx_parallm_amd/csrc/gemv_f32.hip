@@ -37,9 +37,14 @@
 // Resources: 512 threads, 254 VGPRs (one workgroup per CU), no scratch.  LDS: 32.5 KiB static -- the cross-wave
 // reduction of a pass ([8 tiles][8 waves][32 lanes] float4 = 32 KiB, written once per pass after the last chunk) and
 // the waves' row sums of squares (8 x 8 floats).
+//
+// A second kernel of this file, gemv_f32_whole_kernel, is the same operator for the one NARROW linear of that step whose
+// whole tile fits a workgroup's load queue (o_proj: one tile per CU, K <= 4096): no ring, no chunks, every load up front,
+// bit-identical outputs.  Its notes are in front of it.  q|k|v and down_proj stay on the split-K kernel (gemm_skinny.hip).
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "gemv_phase.h"
 
@@ -76,6 +81,18 @@ __device__ __forceinline__ gptr uniform_ptr(const void* base, size_t off) {
   const uint64_t a = (uint64_t)base + off;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
   return (gptr)(((uint64_t)hi << 32) | lo);
+}
+
+// Two floats -> hi + mid + lo exactly (three bf16 terms each) -> one dword of a lane's two A-fragment images: `low` lanes
+// (fragment rows 0..7) hold hi and lo, the others mid and zeros.  Every kernel of this file splits x here, which is why
+// their outputs agree bit for bit.
+__device__ __forceinline__ void split3(f32x2 f, bool low, uint32_t& a0, uint32_t& a1) {
+  const uint32_t hi = pack2<bf16>(f);
+  const f32x2 r1 = f - unpack2<bf16>(hi);
+  const uint32_t mid = pack2<bf16>(r1);
+  const uint32_t lo = pack2<bf16>(r1 - unpack2<bf16>(mid));
+  a0 = low ? hi : mid;
+  a1 = low ? lo : 0u;
 }
 
 template <bool GU8>
@@ -146,12 +163,7 @@ struct F32Body {
         sq = fmaf(f.x, f.x, sq); sq = fmaf(f.y, f.y, sq);
         f = f * wf;
       }
-      const uint32_t hi = pack2<bf16>(f);
-      const f32x2 r1 = f - unpack2<bf16>(hi);
-      const uint32_t mid = pack2<bf16>(r1);
-      const uint32_t lo = pack2<bf16>(r1 - unpack2<bf16>(mid));
-      a0[j] = low ? hi : mid;
-      a1[j] = low ? lo : 0u;
+      split3(f, low, a0[j], a1[j]);
     }
     af[u][0] = u32x4{a0[0], a0[1], a0[2], a0[3]};
     af[u][1] = u32x4{a1[0], a1[1], a1[2], a1[3]};
@@ -305,6 +317,124 @@ __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_gu8_kernel(F32Params p) 
   b.run();
 }
 
+// ---- The whole-K form: one 16-row tile per workgroup, K <= 4096, every byte of the launch requested up front --------------
+// A narrow linear (N / 16 <= CUs: o_proj) has one tile per CU, and at K <= 4096 a wave's share of it is at most 16 k-blocks
+// -- the 16 loads a wave of the kernel above keeps in flight.  So there is no ring and no chunk: wave v issues the loads of
+// ALL its blocks v, v + 8, v + 16, ... at once (128 KiB per CU at K = 4096), multiplies them in ascending order as they
+// land, and the workgroup ends in the reduction and epilogue of F32Body::pass<1>.  Same splits (split3), same MFMAs in the
+// same order, same sums: every output is bit-identical to gemv_f32_kernel on the same call.
+//
+// Program order, straight-line (no load under a branch; a slot past the wave's last block re-loads a valid block and is
+// ignored).  A CU returns loads in issue order, so what a block's MFMAs need is asked for in the order they need it:
+//   * EPI_RESID: the two h values of each epilogue thread (only this workgroup writes them in this launch), first -- two
+//     4-byte loads, out of the way before the stream.
+//   * then PER BLOCK, x and right behind it the block's weights: x0 w0 x1 w1 ... x15 w15.
+//     x: M rows x K floats, once per workgroup, 16 bytes per thread and load.  Lane l of wave v takes row l & 7, piece
+//     l >> 3 (4 floats) of the block: a wave-load covers one 128-byte line of each of the 8 rows, and wave v stages
+//     exactly the blocks it multiplies -- x crosses lanes (through LDS), never waves, so there is no workgroup barrier
+//     between x and the MFMAs.  (Fewer than 8 rows: the lanes of the missing rows re-load the last row into an image row
+//     that is never read.)
+//     weights: non-temporal, uniform 64-bit base + 32-bit lane offset (uniform_ptr).
+//     All of x in front of all the weights (the first form built) was measured and is slower in the step: 11.17 against
+//     10.58 us per launch (traces of two boxes), 0.051-0.058 against 0.082 ms per step in the A/B.  The
+//     reasoning behind the interleaved order, an estimate that no stamp backs: 128 x-loads per CU at 16 cycles each on
+//     the CU's address path are ~0.85 us before the first weight request leaves, and HBM idles meanwhile; interleaved,
+//     the first weight request leaves behind ONE x load, x (an L2 hit) is back long before the weights in front of it,
+//     and the in-order return hands every block its x just ahead of its weights.  Back to back, with the matrix
+//     resident in the Infinity Cache, the order is the other way round (9.7 against 10.0 us), and the step is what counts.
+// Then per block, as its loads land (counted vmcnt: 31, 30, ... 0): x -> LDS -> the lane's fragment position -> split ->
+// two MFMAs.  The LDS round trip and the split of block u run while block u's weights are still on their way.
+//
+// LDS image of x, float32, in fragment order: k-block kb is one KiB, [half h of the 8 floats][lane group g][row m] x 16
+// bytes.  A store (8 consecutive lanes = the 8 rows of one piece) fills 128 contiguous bytes; a fragment read
+// (ds_read_b128: 16-lane groups that span two g and all rows; lanes c16 and c16 + 8 share an address) covers 256
+// contiguous bytes: neither has a bank conflict.  The raw x of all 16 blocks is in registers as loaded (64 VGPRs, next to
+// the 64 of the weights: everything is in flight at once); a block's pieces leave for LDS as they land, and only ONE block's
+// fragment position is read back and split at a time: never 16 blocks of split fragments.
+//
+// Resources: 512 threads, 155 VGPRs, one workgroup per CU, no scratch.  LDS (dynamic, above 64 KiB -> function attribute):
+// the 4-KiB reduction + K / 32 KiB of x (at least one block per wave, so that the ignored slots stay inside it): 132 KiB
+// at K = 4096.
+constexpr int F32W_UB = 16;                      // k-blocks per wave: K <= 8 * 16 * 32
+constexpr int F32W_RED = F32_NW * 32 * 16;       // bytes of the cross-wave reduction, in front of the x image
+constexpr size_t f32_whole_lds_bytes(int K) { return F32W_RED + (size_t)(K / 32 > F32_NW ? K / 32 : F32_NW) * 1024; }
+
+__global__ __launch_bounds__(F32_NW * 64) void gemv_f32_whole_kernel(F32Params p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char whole_lds[];
+  float* red = (float*)whole_lds;
+  unsigned char* ximg = whole_lds + F32W_RED;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c16 = lane & 15, g = lane >> 4;
+  const int w = blockIdx.x, nkb = p.K / 32;
+
+  // (b) thread (m, c) of wave 0 finishes columns c and c + 8 of row m (F32Body::pass): its h now, not as a dependent load
+  // at the very end.  Straight-line: the pointer is selected, the load is not under a branch.
+  const int em = (tid >> 3) & 7, ecc = tid & 7;
+  const bool ep = tid < 64 && em < p.M;
+  const bool res = ep && p.epi == EPI_RESID;
+  const size_t eo = (size_t)em * p.ldo + w * 16 + ecc;
+  const float* hp = res ? p.resid + eo : p.x;
+  const float h0 = hp[0], h1 = hp[res ? 8 : 0];
+  __builtin_amdgcn_sched_barrier(0);
+  // (a), (c) per block: its x -- row lane & 7 (clamped), 16-byte piece lane >> 3 of the block's 128 bytes per row -- then its weights
+  u32x4 xs[F32W_UB], ring[F32W_UB];
+  const uint32_t xlane = ((uint32_t)min(lane & 7, p.M - 1) * (uint32_t)p.ldx + 4u * (lane >> 3)) * 4u;   // (<= 8 rows: far below 4 GiB)
+#pragma unroll
+  for (int u = 0; u < F32W_UB; ++u) {
+    const int kb = u * F32_NW + wave, b = kb < nkb ? kb : 0;
+    const gptr xb = uniform_ptr(p.x, (size_t)b * 128);
+    xs[u] = *(gptr16)(xb + xlane);
+    __builtin_amdgcn_sched_barrier(0);
+    const gptr tb = uniform_ptr(p.w, ((size_t)w * nkb + b) * 1024);
+    ring[u] = __builtin_nontemporal_load((gptr16)(tb + (uint32_t)lane * 16u));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // Per block, as its loads land: x -> LDS image (wave-uniform branch, no load inside) -> this lane's fragment position ->
+  // split -> two MFMAs.  The image rows a wave reads are the ones it wrote, and the LDS operations of a wave complete in order.
+  const uint32_t wofs = (uint32_t)(((lane >> 3) & 1) * 512 + ((lane >> 4) * 8 + (lane & 7)) * 16);
+  const uint32_t rofs = (uint32_t)((g * 8 + min(c16 & 7, p.M - 1)) * 16);
+  const bool low = c16 < 8;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < F32W_UB; ++u) {
+    const int kb = u * F32_NW + wave;
+    const bool valid = kb < nkb;                    // (wave-uniform)
+    // a slot past the end reads the wave's own first image block (inside the allocation, written by no other wave)
+    unsigned char* blk = ximg + (valid ? kb : wave) * 1024;
+    if (valid) *(u32x4*)(blk + wofs) = xs[u];
+    __builtin_amdgcn_wave_barrier();
+    const u32x4 r0 = *(const u32x4*)(blk + rofs), r1 = *(const u32x4*)(blk + rofs + 512);
+    const uint32_t xd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+    uint32_t a0[4], a1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) split3(f32x2{__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])}, low, a0[j], a1[j]);
+    if (valid) {
+      acc = mfma16<bf16>(u32x4{a0[0], a0[1], a0[2], a0[3]}, ring[u], acc);
+      acc = mfma16<bf16>(u32x4{a1[0], a1[1], a1[2], a1[3]}, ring[u], acc);
+    }
+  }
+
+  // ---- cross-wave reduction and epilogue: F32Body::pass<1>, tile 0
+  f32x4 v = acc;
+  v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
+  if (lane < 32) *(f32x4*)&red[(wave * 32 + lane) * 4] = v;
+  __syncthreads();
+  if (ep) {
+    const int el = (em >> 2) * 16 + ecc, r = em & 3;
+    float y0 = 0.f, y1 = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < F32_NW; ++ww) {
+      y0 += red[(ww * 32 + el) * 4 + r];
+      y1 += red[(ww * 32 + el + 8) * 4 + r];
+    }
+    if (p.epi == EPI_RESID) {
+      p.resid[eo] = h0 + y0; p.resid[eo + 8] = h1 + y1;
+    } else {                                        // EPI_STORE and EPI_STORE_F32 coincide
+      p.out[eo] = y0; p.out[eo + 8] = y1;
+    }
+  }
+}
+
 }  // namespace
 
 // float32 activations without logical rounding, <= 8 rows, dense bf16 tile-major weights, no LoRA, no [hi | lo] walk;
@@ -332,6 +462,38 @@ int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st) {
   const int nwg = std::min(W.N / 16, gemv_cu_count());     // one workgroup per CU; tiles are dealt in-kernel
   if (c.epi == EPI_SWIGLU_GU8) hipLaunchKernelGGL(gemv_f32_gu8_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
   else hipLaunchKernelGGL(gemv_f32_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// The whole-K form: what gemv_f32_supported takes, without a prologue, K <= 4096 (16 k-blocks per wave) and at most one
+// tile per CU (the tile is the workgroup's only work: more tiles than CUs would queue whole workgroups behind one another)
+bool gemv_f32_whole_supported(const LinearW& W, const GemvCall& c) {
+  if (!gemv_f32_supported(W, c)) return false;
+  if (c.pro != PRO_NONE) return false;
+  if (c.epi != EPI_STORE && c.epi != EPI_STORE_F32 && c.epi != EPI_RESID) return false;
+  if (W.K > F32_NW * F32W_UB * 32) return false;
+  return W.N / 16 <= gemv_cu_count();
+}
+
+int launch_gemv_f32_whole(const LinearW& W, const GemvCall& c, hipStream_t st) {
+  if (!gemv_f32_whole_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "gemv_f32_whole: call not supported by this kernel");
+  F32Params p{};
+  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
+  p.pro = PRO_NONE; p.norm_w = nullptr; p.eps = 0.f;
+  p.w = W.w; p.N = W.N; p.K = W.K;
+  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
+  if (c.epi == EPI_RESID ? p.resid == nullptr : p.out == nullptr) return fail(MI_ERR_INVALID, "gemv_f32_whole: output buffer missing");
+  // the opt-in for LDS above 64 KiB belongs to the kernel object of the CURRENT device: one flag per device, set after the call
+  static std::atomic<bool> attr_done[64];
+  int dev = 0;
+  MI_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
+    MI_HIP(hipFuncSetAttribute((const void*)gemv_f32_whole_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)f32_whole_lds_bytes(F32_NW * F32W_UB * 32)));
+    if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(gemv_f32_whole_kernel, dim3(W.N / 16), dim3(F32_NW * 64), f32_whole_lds_bytes(W.K), st, p);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

@@ -109,6 +109,10 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
 // EPI_STORE_F32 / EPI_RESID in float32, EPI_SWIGLU_GU8 on the row-interleaved gate|up copy (W = the copy).
 bool gemv_f32_supported(const LinearW& W, const GemvCall& c);
 int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st);
+// the same operator, bit for bit, for a NARROW linear of K <= 4096 (o_proj): one 16-row tile per workgroup over the whole K,
+// at most one tile per CU, c.pro = PRO_NONE, EPI_STORE / EPI_STORE_F32 / EPI_RESID; every load of the launch issued up front
+bool gemv_f32_whole_supported(const LinearW& W, const GemvCall& c);
+int launch_gemv_f32_whole(const LinearW& W, const GemvCall& c, hipStream_t st);
 int gemv_cu_count();            // compute units of the current device (gemv_mfma.hip)
 
 // int4 (group 64) weights, 17..128 rows of 16-bit activations (gemm_q4.hip): x prepared once per launch (fragment-major,

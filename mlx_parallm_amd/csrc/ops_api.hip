@@ -116,6 +116,31 @@ int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, f
   return rc != MI_OK ? rc : rc2;
 }
 
+// the whole-K form of gemv_f32.hip on its own (one tile per workgroup: N / 16 <= CUs, K <= 4096, a->pro = MI_PRO_NONE; plain,
+// float32 and residual stores), with the refusals of its launch.  iters >= 1 additionally times `iters` back-to-back launches.
+int mi_op_gemv_f32_whole(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  const LinearW W = to_linear(w);
+  const GemvCall c = to_call(a);
+  if (!gemv_f32_whole_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_whole: call not supported by this kernel");
+  int rc = launch_gemv_f32_whole(W, c, nullptr);
+  if (rc == MI_OK && iters >= 1 && avg_ms) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32_whole(W, c, nullptr);
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  const int rc2 = finish();
+  return rc != MI_OK ? rc : rc2;
+}
+
 // gemm_skinny.hip on its own: a->M in 9..128 (int4 / int8: 1..128), a->pro must be MI_PRO_NONE; ksplit 0 = the cost model's choice
 // (*ksplit_used returns it); iters >= 1 additionally times `iters` back-to-back launches.  int4 weights above 16 rows with
 // ksplit <= 0 run gemm_q4.hip (a->pro may then be MI_PRO_NORM); ksplit < 0 forces its plan: -(mt | TW << 3 | KW << 7 | ksplit << 11 | NS << 15).
