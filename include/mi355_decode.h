@@ -127,10 +127,15 @@ int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const
                          int ndim, int dtype, int on_device);
 
 /* LoRALinear for one projection (mlx-lm load_adapters, utils.py:742-744; file layout
- * rl_training/lora_init.py:140-153).  proj: "self_attn.q_proj" etc.  A is (K, r), B is (r, N),
- * row-major, dtype MI_F32/BF16/F16.  y += (scale * ((x A) B)).astype(x.dtype), on top of the projection's bias when it has
- * one.  With desc.rope_traditional the columns of B of q_proj / k_proj are regrouped like the rows of the matrix (the
- * caller passes them in checkpoint order, also on a hot-swap). */
+ * rl_training/lora_init.py:140-153; whatever lora_parameters.keys names, lora_init.py:72,95-96).  proj: any of the seven
+ * linears of a block -- "self_attn.q_proj" / "k_proj" / "v_proj" / "o_proj", "mlp.gate_proj" / "up_proj" / "down_proj" --
+ * in any combination (q, k and v together; gate and up: their terms are added BEFORE silu(gate) * up); any other name,
+ * lm_head and the embedding included, is MI_ERR_UNSUPPORTED.  A is (K, r), B is (r, N), row-major, float32 (16-bit factors
+ * and ranks outside 1..64: MI_ERR_UNSUPPORTED).  y += (scale * ((x A) B)).astype(x.dtype), on top of the projection's bias
+ * when it has one.  With desc.rope_traditional the columns of B of q_proj / k_proj are regrouped like the rows of the matrix
+ * (the caller passes them in checkpoint order, also on a hot-swap).  May be called on a finalized, live engine: a projection
+ * that is already adapted is hot-swapped, a new one is added; the outputs do not depend on the order in which the
+ * projections arrived.  A refused call changes nothing. */
 int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B,
                        int rank, float scale, int dtype, int on_device);
 

@@ -54,6 +54,11 @@ struct FusedLinear {
   bool hilo_failed = false, gu8_failed = false;
   float* lora_a[2] = {nullptr, nullptr};
   float* lora_b[2] = {nullptr, nullptr};
+  // q|k|v with q, k AND v adapted: the range that does not fit LinearW's two (always k: the fewest columns) lives here,
+  // outside the streaming kernels' parameter blocks.  launch_lora_down3 makes its t with the other two, launch_lora_up_add3
+  // adds its term to the stored output behind the main launch.  Set only while both slots of W are taken, so every
+  // "is this matrix adapted" test of the router keeps reading W.lora_b[0] / [1].
+  LoraRange lora3;
   int seen_w[3] = {0, 0, 0}, seen_s[3] = {0, 0, 0}, seen_b[3] = {0, 0, 0};
   float* bias = nullptr;         // [rows of all parts] float32: the parts' `.bias` tensors (attention_bias / mlp_bias), as loaded
   int seen_bias[3] = {0, 0, 0};
@@ -90,6 +95,8 @@ struct mi_engine {
   size_t ws_rows = 0; size_t ws_logit_rows = 0;
   void* h = nullptr; void* qkv = nullptr; void* q = nullptr; void* attn = nullptr; void* act = nullptr;
   float* logits = nullptr; float* lora_t = nullptr;
+  float* lora_t3 = nullptr;                               // [rows][64]: t of a q|k|v matrix's third range (FusedLinear::lora3)
+  void* gu = nullptr; size_t gu_rows = 0;                 // [rows][2 I]: the stored output of an ADAPTED gate|up (swiglu_rows_kernel reads it)
   int32_t* d_tokens = nullptr; size_t d_tokens_cap = 0;
   const int32_t* tok_src = nullptr;                       // device-fed step: the embedding reads the sampler's output in place
   int32_t* d_forced = nullptr; size_t d_forced_cap = 0;   // mi_score_tokens targets
@@ -329,13 +336,14 @@ int make_f32_copy(mi_engine* e, const void* src, int n, void** dst) {
 void free_linear(FusedLinear& f) {
   hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
   for (int i = 0; i < 2; ++i) { hipFree(f.lora_a[i]); hipFree(f.lora_b[i]); }
+  hipFree(const_cast<float*>(f.lora3.a)); hipFree(const_cast<float*>(f.lora3.b));
 }
 
 int ensure_workspace(mi_engine* e, size_t rows, size_t logit_rows, int B) {
   const mi_model_desc& d = e->d;
   if (rows > e->ws_rows) {
     MI_HIP(hipStreamSynchronize(e->stream));
-    hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->lora_t);
+    hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->lora_t); hipFree(e->lora_t3);
     const size_t es = 4;  // sized for float32 activations (the widest mode)
     const size_t nqkv = (size_t)(d.num_heads + 2 * d.num_kv_heads) * d.head_dim;
     MI_HIP(hipMalloc(&e->h, rows * d.hidden_size * es));
@@ -344,6 +352,7 @@ int ensure_workspace(mi_engine* e, size_t rows, size_t logit_rows, int B) {
     MI_HIP(hipMalloc(&e->attn, rows * (size_t)d.num_heads * d.head_dim * es));
     MI_HIP(hipMalloc(&e->act, rows * (size_t)d.intermediate_size * es));
     MI_HIP(hipMalloc(&e->lora_t, rows * 2 * 64 * sizeof(float)));
+    MI_HIP(hipMalloc(&e->lora_t3, rows * 64 * sizeof(float)));
     hipFree(e->xn);
     MI_HIP(hipMalloc(&e->xn, rows * (size_t)d.hidden_size * es));
     e->ws_rows = rows;
@@ -483,6 +492,30 @@ int check_cc_guards(mi_engine* e, int nqkv) {
 float* cc_pub_tiles(mi_engine* e) { return e->cc_pub + CC_GUARD; }                                     // [8 slices][8 rows][nqkv]
 float* cc_pub_sumsq(mi_engine* e, int nqkv) { return e->cc_pub + 2 * CC_GUARD + (size_t)8 * 8 * nqkv; }   // [8 slices][8 rows]
 
+// the stored output of an adapted gate|up, grown on demand like the other scratch buffers
+int ensure_gu(mi_engine* e, size_t rows) {
+  if (rows <= e->gu_rows) return MI_OK;
+  MI_HIP(hipStreamSynchronize(e->stream));
+  hipFree(e->gu); e->gu = nullptr; e->gu_rows = 0;
+  MI_HIP(hipMalloc(&e->gu, rows * 2 * (size_t)e->d.intermediate_size * 4));     // (sized for float32 activations)
+  e->gu_rows = rows;
+  return MI_OK;
+}
+
+// t = x A for the adapted ranges of f0 on the call's c.M rows, rows [r, r + c.M) of the engine's t buffers: ONE launch,
+// whether the matrix has one, two (lora_down_kernel) or three ranges (lora_down3_kernel)
+int lora_down_rows(mi_engine* e, const FusedLinear& f0, const GemvCall& c, size_t r) {
+  if (f0.lora3.b != nullptr)
+    return launch_lora_down3(f0.W, f0.lora3, c, e->lora_t + r * 128, 128, e->lora_t3 + r * 64, 64, e->stream);
+  return launch_lora_down(f0.W, c, e->lora_t + r * 128, 128, e->stream);
+}
+// the third range's term, added to the `rows` stored rows of c.out behind a launch whose epilogue added the other two
+int lora_third_up_add(mi_engine* e, const FusedLinear& f0, GemvCall c, size_t rows) {
+  if (f0.lora3.b == nullptr) return MI_OK;
+  c.M = (int)rows;
+  return launch_lora_up_add3(nullptr, f0.lora3, c, e->lora_t, 128, e->lora_t3, 64, e->stream);
+}
+
 // y = W x for `rows` rows, split into launches of at most 16 (MFMA) / 8 (generic) rows.
 // consumer_combine: `published` != null is an OFFER of the caller's -- "the next launch can add K slices published in the
 // seam buffer instead of reading c.out".  The router takes it on the one route whose kernel has the publish-only form, and
@@ -584,7 +617,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     c.M = (int)rows;
     if (f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr) {     // (normalises on its own when c.pro says so)
       c.lora_t = e->lora_t; c.lora_t_ld = 128;
-      MI_TRY(launch_lora_down(f0.W, c, e->lora_t, 128, e->stream));
+      MI_TRY(lora_down_rows(e, f0, c, 0));
     }
     // float32 activations without logical rounding (PagedKVCache mode after layer 0): the kernel applies the row scale
     // of the RMSNorm in its epilogue (gemm_skinny.hip "defer_norm") -- no norm launch, nothing waits for row statistics
@@ -615,7 +648,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     MI_TRY(ensure_skinny_ws(e, need, groups));
     MI_TRY(launch_gemm_skinny(f.W, c, rows, e->stream, e->sk_ws, e->sk_ctr));
     if (produce) { e->sq_valid = true; e->sq_src = c.resid; e->sq_parts = tgroups; e->sq_K = f.W.N; e->sq_ld = leave_ld; }
-    return MI_OK;
+    return lora_third_up_add(e, f0, c, rows);
   }
   if (e->opt_prefill_gemm && gemm_prefill_supported(f.W, c, rows)) {
     // prefill: one MFMA tile GEMM over all rows (the RMSNorm runs as its own row-wise kernel)
@@ -657,8 +690,9 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     if (f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr) {   // y = T(y + T(scale (x A) B)) on the adapted columns
       GemvCall cl = c.act == MI_F32 ? c_in : c;
       cl.M = (int)rows;
-      MI_TRY(launch_lora_down(f0.W, cl, e->lora_t, 128, e->stream));
-      MI_TRY(launch_lora_up_add(f0.W, cl, e->lora_t, 128, e->stream));
+      MI_TRY(lora_down_rows(e, f0, cl, 0));
+      if (f0.lora3.b != nullptr) MI_TRY(launch_lora_up_add3(&f0.W, f0.lora3, cl, e->lora_t, 128, e->lora_t3, 64, e->stream));   // (all three in one launch)
+      else MI_TRY(launch_lora_up_add(f0.W, cl, e->lora_t, 128, e->stream));
     }
     return MI_OK;
   }
@@ -668,7 +702,8 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     // over W.  A tile GEMM with the three-way split of x is the next step for this mode.
     Prof pr(e, prof);
     const bool lora32 = f.W.lora_b[0] != nullptr || f.W.lora_b[1] != nullptr;
-    if (lora32) { GemvCall cl = c; cl.M = (int)rows; MI_TRY(launch_lora_down(f0.W, cl, e->lora_t, 128, e->stream)); }
+    if (lora32) { GemvCall cl = c; cl.M = (int)rows; MI_TRY(lora_down_rows(e, f0, cl, 0)); }
+    const GemvCall c_out = c;
     if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
     // workspace for every chunk size that is launched below: full 32-row chunks and the tail, whose plan (tile rows,
     // K split) is made for ITS row count and can need more partial-tile space than the 32-row plan
@@ -687,7 +722,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
       if (lora32) { cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128; }
       MI_TRY(launch_gemm_skinny(f.W, cc, (size_t)cc.M, e->stream, e->sk_ws, e->sk_ctr));
     }
-    return MI_OK;
+    return lora_third_up_add(e, f0, c_out, rows);
   }
   // the generic per-8 / per-16-row kernels read the matrix as loaded (an f16 model falls back to its f16 weights, exact VALU)
   c.kx = 0;
@@ -714,7 +749,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     GemvCall cc = row_slab(c, r, std::min(step, rows - r), es_in, es_out);
     if (has_lora) {
       cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128;
-      MI_TRY(launch_lora_down(f0.W, cc, e->lora_t + r * 128, 128, e->stream));
+      MI_TRY(lora_down_rows(e, f0, cc, r));
     }
     if (gu8) {
       LinearW wv = f0.W;                       // (a view: the copy stays owned by f0)
@@ -725,7 +760,7 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     }
     MI_TRY(launch_gemv(f0.W, cc, e->stream));
   }
-  return MI_OK;
+  return lora_third_up_add(e, f0, c, rows);
 }
 
 // ---- block-paged KV: host-side block management (the device only sees the table) ------------------------------------
@@ -976,7 +1011,17 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
       c.eps = d.rms_norm_eps; c.epi = EPI_SWIGLU; c.out = e->act; c.ldo = I; c.pair_offset = I;
-      MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up")); }
+      if (lw.gate_up.W.lora_b[0] != nullptr || lw.gate_up.W.lora_b[1] != nullptr) {
+        // adapted gate and / or up: no SwiGLU epilogue carries the LoRA term, so the linear stores gate|up (plain store:
+        // every kernel family adds the two ranges there) and a row-wise kernel applies SwiGLU to the stored rows
+        MI_TRY(ensure_gu(e, R));
+        c.epi = EPI_STORE; c.out = e->gu; c.ldo = 2 * I; c.pair_offset = 0;
+        MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up"));
+        Prof pr(e, "swiglu_rows");
+        MI_TRY(launch_swiglu_rows(e->gu, 2 * I, e->act, I, (int)R, I, act, c.rnd, st));
+      } else {
+        MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up"));
+      } }
     { // down_proj + residual (llama.py:165,190)
       GemvCall c; c.x = e->act; c.ldx = I; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
       MI_TRY(gemv_rows(e, lw.down, c, R, es, es, "gemv_down")); }
@@ -1169,7 +1214,7 @@ void mi_engine_destroy(mi_engine* e) {
   hipFree(e->final_norm32); hipFree(e->xn); hipFree(e->xs); hipFree(e->gk_ws);
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
-  hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->d_forced); hipFree(e->d_gather);
+  hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->lora_t3); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
   hipFree(e->d_rowpar); hipFree(e->deq_scratch);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
@@ -1262,28 +1307,52 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
   LayerW& l = e->layers[layer];
   const std::string p(proj);
   FusedLinear* f = nullptr; int row0 = 0, n = 0, K = d.hidden_size;
-  const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
+  const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, I = d.intermediate_size;
   if (p == "self_attn.q_proj") { f = &l.qkv; row0 = 0; n = QD; }
   else if (p == "self_attn.k_proj") { f = &l.qkv; row0 = QD; n = KD; }
   else if (p == "self_attn.v_proj") { f = &l.qkv; row0 = QD + KD; n = KD; }
   else if (p == "self_attn.o_proj") { f = &l.o; row0 = 0; n = d.hidden_size; K = QD; }
-  else if (p == "mlp.down_proj") { f = &l.down; row0 = 0; n = d.hidden_size; K = d.intermediate_size; }
-  else return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (q/k/v/o/down only)");
-  int slot = -1;
+  else if (p == "mlp.gate_proj") { f = &l.gate_up; row0 = 0; n = I; }
+  else if (p == "mlp.up_proj") { f = &l.gate_up; row0 = I; n = I; }
+  else if (p == "mlp.down_proj") { f = &l.down; row0 = 0; n = d.hidden_size; K = I; }
+  else return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the seven linears of a block only)");
+  // where the range goes: its own place when it is already adapted (hot-swap), else a free slot of LinearW, else -- q|k|v
+  // with both slots taken -- the third place beside it.  With all three adapted the third is ALWAYS k (a slot holding k
+  // hands it over), so that an engine computes the same bits whatever order the projections arrived in.
+  int slot = -1; bool third = false, move_k = false;
   for (int i = 0; i < 2; ++i) if (f->lora_b[i] != nullptr && f->W.lora_row0[i] == row0) slot = i;   // hot-swap
-  if (slot < 0) for (int i = 0; i < 2; ++i) if (f->lora_b[i] == nullptr) { slot = i; break; }
-  if (slot < 0) return fail(MI_ERR_UNSUPPORTED, "at most two adapted projections per fused matrix");
+  if (slot < 0 && f->lora3.b != nullptr && f->lora3.row0 == row0) third = true;                      // hot-swap
+  if (slot < 0 && !third) for (int i = 0; i < 2; ++i) if (f->lora_b[i] == nullptr) { slot = i; break; }
+  if (slot < 0 && !third) {
+    if (f != &l.qkv || f->lora3.b != nullptr) return fail(MI_ERR_UNSUPPORTED, "no free place for another adapted range on this matrix");
+    if (row0 == QD) third = true;
+    else { slot = f->W.lora_row0[0] == QD ? 0 : 1; move_k = true; }
+  }
   MI_HIP(hipStreamSynchronize(e->stream));
-  hipFree(f->lora_a[slot]); hipFree(f->lora_b[slot]);
-  f->lora_a[slot] = f->lora_b[slot] = nullptr;
-  MI_HIP(hipMalloc(&f->lora_a[slot], (size_t)K * rank * sizeof(float)));
-  MI_HIP(hipMalloc(&f->lora_b[slot], (size_t)rank * n * sizeof(float)));
-  MI_TRY(copy_in(f->lora_a[slot], A, (size_t)K * rank * sizeof(float), on_device, e->stream));
-  MI_TRY(copy_in(f->lora_b[slot], B, (size_t)rank * n * sizeof(float), on_device, e->stream));
+  float* na = nullptr; float* nb = nullptr;
+  MI_HIP(hipMalloc(&na, (size_t)K * rank * sizeof(float)));
+  if (hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); hipFree(na); return fail(MI_ERR_RUNTIME, "LoRA: out of device memory"); }
+  int rc = copy_in(na, A, (size_t)K * rank * sizeof(float), on_device, e->stream);
+  if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
   // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
-  if (d.rope_traditional && f == &l.qkv && row0 < QD + KD) MI_TRY(head_perm_inplace(e, f->lora_b[slot], (size_t)rank * n, d.head_dim, sizeof(float)));
-  f->W.lora_a[slot] = f->lora_a[slot]; f->W.lora_b[slot] = f->lora_b[slot];
-  f->W.lora_row0[slot] = row0; f->W.lora_n[slot] = n; f->W.lora_rank[slot] = rank; f->W.lora_scale[slot] = scale;
+  if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
+  if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
+  if (move_k) {           // k leaves its slot for the third place; the new range takes the slot
+    f->lora3.a = f->lora_a[slot]; f->lora3.b = f->lora_b[slot];
+    f->lora3.row0 = f->W.lora_row0[slot]; f->lora3.n = f->W.lora_n[slot]; f->lora3.rank = f->W.lora_rank[slot]; f->lora3.scale = f->W.lora_scale[slot];
+    f->lora_a[slot] = f->lora_b[slot] = nullptr;
+  }
+  if (third) {
+    hipFree(const_cast<float*>(f->lora3.a)); hipFree(const_cast<float*>(f->lora3.b));
+    f->lora3.a = na; f->lora3.b = nb; f->lora3.row0 = row0; f->lora3.n = n; f->lora3.rank = rank; f->lora3.scale = scale;
+  } else {
+    hipFree(f->lora_a[slot]); hipFree(f->lora_b[slot]);
+    f->lora_a[slot] = na; f->lora_b[slot] = nb;
+    f->W.lora_a[slot] = na; f->W.lora_b[slot] = nb;
+    f->W.lora_row0[slot] = row0; f->W.lora_n[slot] = n; f->W.lora_rank[slot] = rank; f->W.lora_scale[slot] = scale;
+  }
+  // an adapted gate|up never runs a SwiGLU epilogue again: its row-interleaved copy (ensure_gu8) is dead weight
+  if (f == &l.gate_up && f->w_gu8 != nullptr) { hipFree(f->w_gu8); f->w_gu8 = nullptr; }
   return MI_OK;
 }
 

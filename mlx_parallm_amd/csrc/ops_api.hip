@@ -268,6 +268,13 @@ int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, in
   return finish();
 }
 
+// swiglu_rows_kernel (lora.hip) on its own; the launch validates its arguments
+int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd) {
+  MI_TRY(ready());
+  MI_TRY(launch_swiglu_rows(x, ldx, out, ldo, M, I, act, rnd, nullptr));
+  return finish();
+}
+
 int mi_op_gemv_uses_mfma(const mi_op_linear* w, const mi_op_gemv_args* a) {
   if (!w || !a) return 0;
   return gemv_mfma_supported(to_linear(w), to_call(a)) ? 1 : 0;

@@ -278,6 +278,10 @@ class Engine:
         return skipped
 
     def set_lora(self, layer: int, proj: str, a, b, scale: float) -> None:
+        """``mi_engine_set_lora``: adapt (or hot-swap) one projection of block ``layer`` -- any of the seven linears
+        (``self_attn.q_proj`` / ``k_proj`` / ``v_proj`` / ``o_proj``, ``mlp.gate_proj`` / ``up_proj`` / ``down_proj``), in any
+        combination, also on a finalized engine.  ``a`` (K, r), ``b`` (r, N); converted to float32; r in 1..64.  Any other
+        name raises NotImplementedError and leaves the engine as it was.  Published prefixes are forgotten."""
         import torch
         ta = torch.as_tensor(a).to(torch.float32).contiguous()
         tb = torch.as_tensor(b).to(torch.float32).contiguous()

@@ -426,7 +426,8 @@ def load_adapters(model, adapter_path: str):
     """mlx-lm ``load_adapters`` as the reference uses it (utils.py:742-744): read
     ``adapter_config.json`` (``fine_tune_type``, ``num_layers``, ``lora_parameters``; written by
     rl_training/lora_init.py:140-153), adapt the LAST ``num_layers`` blocks, load
-    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``)."""
+    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``).  ``lora_parameters.keys`` may name any of the
+    seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the config's order."""
     from safetensors.torch import load_file
 
     adapter_path = Path(adapter_path)
