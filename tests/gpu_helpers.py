@@ -95,9 +95,11 @@ def attn_shape(B, L_, Hq, Hkv, D, act, kv, rnd, cap) -> L.OpAttnShape:
 
 
 def close_frac(got: np.ndarray, want: np.ndarray, dtype: str, atol: float = 0.0) -> float:
-    """Fraction of elements further than 2 ulp(dtype) (relative) + atol from the oracle."""
-    tol = ULP[dtype] * np.maximum(np.abs(want), np.abs(got)) + atol
-    return float(np.mean(np.abs(got - want) > tol))
+    """Fraction of elements further than 2 ulp(dtype) (relative) + atol from the oracle.  A non-finite `got` is far."""
+    with np.errstate(invalid="ignore"):
+        tol = ULP[dtype] * np.maximum(np.abs(want), np.abs(got)) + atol
+        far = ~(np.abs(got - want) <= tol)
+    return float(np.mean(far | ~np.isfinite(got)))
 
 
 def q4_force(mt=0, tw=0, kw=0, ksplit=0, ns=0) -> int:
