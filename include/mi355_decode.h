@@ -35,7 +35,7 @@ extern "C" {
  * `struct_size`, which the caller sets to sizeof() of ITS definition -- a binding generated from another version of this
  * header (a shorter mi_sample_params would make the library read pointers past its end) is refused with MI_ERR_INVALID
  * by mi_engine_create / mi_decode_sample / mi_step_enqueue(_rows) / mi_score_tokens instead of being read. */
-#define MI_ABI_VERSION 3
+#define MI_ABI_VERSION 4
 
 #define MI_OK 0
 #define MI_ERR_INVALID (-1)
@@ -107,6 +107,22 @@ typedef struct mi_sample_params {
   int64_t stream_position;         /* Philox counter of this step when uniforms == NULL: >= 0 = the caller's own step index
                                     * (generate_step passes 0, 1, 2, ...: the same seed then reproduces the same tokens,
                                     * like re-seeding mx.random before a call); < 0 = the engine's running step counter */
+  /* ABI 4: per-request sampling controls.  Candidates are ordered by descending logit, ties by ascending id; a row with
+   * temperature > 0 keeps the SHORTEST (by count) of three prefixes of that order and draws from it with u * mass(kept);
+   * greedy rows ignore all of them, and the reported logprobs stay those of the unfiltered distribution. */
+  int32_t top_k;                   /* 0 < top_k < V: keep the first top_k candidates (a cut inside a tie group keeps its lowest
+                                    * ids); the nucleus is then taken over them, against top_p * (their mass).  Else off */
+  float min_p;                     /* 0 < min_p <= 1: keep the candidates with p >= min_p * p_max, tested on the device as
+                                    * (logit - max) * (1 / temperature) >= logf(min_p) in float32.  0 = off */
+  const int32_t* row_top_k;        /* [B] or NULL, each on its own: per-row values instead of the scalar (rows as for */
+  const float* row_min_p;          /* row_temperature; mi_step_enqueue_mixed: one entry per wanted segment) */
+  const uint64_t* row_seed;        /* [B], both or neither.  A row with row_position[b] >= 0 draws from the Philox stream */
+  const int64_t* row_position;     /* (row_seed[b], row_position[b], 0): what the call-wide stream (seed, stream_position)
+                                    * gives row 0, whichever index the row has and whoever shares the step.  < 0: the row
+                                    * keeps the call-wide stream (seed, step, b).  `uniforms` take precedence over both.
+                                    * Violations (top_k < 0, min_p outside [0, 1] or NaN, a per-row value out of range,
+                                    * row_seed without row_position or the reverse) are MI_ERR_INVALID naming the field,
+                                    * before anything is enqueued */
 } mi_sample_params;
 
 #define MI_MAX_TOP_LOGPROBS 20
@@ -196,7 +212,7 @@ int mi_decode_sample(mi_engine* e, mi_kv* kv, const int32_t* tokens_in, int B, i
  * log softmax(logits[b,i] (+ logit_bias) (/ temperature if sp->logprobs_at_temperature))[targets[b,i]]
  * into logprob_out [B*L] (targets < 0: position skipped, 0.0 reported) and, if sp->top_logprobs = k > 0,
  * the k most likely ids / logprobs of that position into topk_ids / topk_logprobs [B*L,k].
- * Nothing is sampled; sp->top_p, uniforms and seed are ignored. */
+ * Nothing is sampled; sp->top_p, uniforms, seed and the ABI 4 controls (top_k, min_p, row streams) are ignored. */
 int mi_score_tokens(mi_engine* e, mi_kv* kv, const int32_t* tokens, const int32_t* targets, int B, int L,
                     const mi_sample_params* sp, float* logprob_out, int32_t* topk_ids, float* topk_logprobs);
 
@@ -220,7 +236,8 @@ int mi_step_enqueue_rows(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, co
  * segments (decode rows) must come first; `tokens` is the concatenation (sum of lens).  want[i] != 0: sample a token
  * from the logits after the segment's last position (every decode row, and the LAST chunk of a prompt); want[i] == 0:
  * an inner chunk, no logits.  mi_step_wait then returns the results of the wanted segments, in segment order (the
- * ticket's batch = their count; row_temperature / row_top_p, if given, have one entry per wanted segment).  Explicit
+ * ticket's batch = their count; row_temperature / row_top_p and the other per-row arrays, if given, have one entry per wanted
+ * segment).  Explicit
  * tokens only: the device-resident token feed of mi_step_enqueue(_rows) restarts after a mixed step. */
 int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const int32_t* lens, const int32_t* want, int n,
                           const int32_t* tokens, const mi_sample_params* sp, int64_t* ticket);

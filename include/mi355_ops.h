@@ -15,6 +15,7 @@
  *                     qwen3.py:65-70; llama.py:107-125; base.py:66-85,119-140
  *   mi_op_attention   mx.fast.scaled_dot_product_attention + causal mask: llama.py:139-141; base.py:17-40
  *   mi_op_sample      sample closure + top_p_sampling: utils.py:345-364; sample_utils.py:3-38
+ *   mi_op_sample_ex   the same kernel with top_k / min_p and per-row random streams (no counterpart in the reference)
  */
 #ifndef MI355_OPS_H
 #define MI355_OPS_H
@@ -163,6 +164,17 @@ int mi_op_attention_decode_host(const mi_op_attn_shape* s, const void* qkv, void
 int mi_op_sample(float* logits, int B, int V, float temperature, float top_p, const float* uniforms,
                  int top_logprobs, int32_t* tokens_out, float* logprob_out, float* prob_row0_out,
                  int32_t* topk_ids, float* topk_logprobs, float* row_stats);
+/* the same kernel with every sampling control of mi_sample_params (mi355_decode.h, where the semantics are written down)
+ * exposed: scalar top_k / min_p; DEVICE arrays [B] or NULL row_temperature + row_top_p (both or neither), row_top_k, row_min_p
+ * (each on its own), row_seed + row_position (both or neither); the call-wide Philox key `seed` and counter `step`; `uniforms`
+ * (device [B] or NULL) take precedence over every stream.  With all of them off / NULL and seed = step = 0 the call is
+ * mi_op_sample, bit for bit.  top_k < 0, min_p outside [0, 1] or NaN, or half a pair: MI_ERR_INVALID, nothing is launched.
+ * Per-row values are not read by the host: a row_top_k <= 0 or >= V and a row_min_p outside (0, 1] leave that control off. */
+int mi_op_sample_ex(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                    const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                    const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                    const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                    float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats);
 
 #ifdef __cplusplus
 }

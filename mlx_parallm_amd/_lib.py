@@ -18,7 +18,7 @@ MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
 MI_KV_MODEL = -1
 MI_ARCH_LLAMA, MI_ARCH_QWEN3 = 0, 1
 MI_MAX_TOP_LOGPROBS = 20
-MI_ABI_VERSION = 3
+MI_ABI_VERSION = 4
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
 PRO_NONE, PRO_NORM = 0, 1
@@ -48,6 +48,9 @@ class SampleParams(C.Structure):
         ("logprobs_at_temperature", C.c_int32),
         ("row_temperature", C.POINTER(C.c_float)), ("row_top_p", C.POINTER(C.c_float)),
         ("stream_position", C.c_int64),
+        ("top_k", C.c_int32), ("min_p", C.c_float),
+        ("row_top_k", C.POINTER(C.c_int32)), ("row_min_p", C.POINTER(C.c_float)),
+        ("row_seed", C.POINTER(C.c_uint64)), ("row_position", C.POINTER(C.c_int64)),
     ]
 
 
@@ -129,6 +132,8 @@ SIGNATURES = {
     "mi_op_attention_decode_host": (C.c_int, [C.POINTER(OpAttnShape), _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_float,
                                               C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _I32P, _I32P]),
     "mi_op_sample": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "mi_op_sample_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
+                                  C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -102,6 +102,7 @@ struct mi_engine {
   int32_t* d_forced = nullptr; size_t d_forced_cap = 0;   // mi_score_tokens targets
   int32_t* d_gather = nullptr;                            // token positions whose hidden state feeds the head (mixed steps)
   float* d_rowpar = nullptr; size_t d_rowpar_cap = 0;     // per-row temperature | top_p of the current step
+  char* d_rowext = nullptr; size_t d_rowext_cap = 0;      // per-row seed | position (8 bytes each) | top_k | min_p
   void* deq_scratch = nullptr; size_t deq_cap = 0;        // [hi | lo] 16-bit copy of one int4 matrix (prefill GEMM)
   void* sk_ws = nullptr; size_t sk_ws_cap = 0;            // split-K partial tiles of gemm_skinny.hip
   unsigned* sk_ctr = nullptr; int sk_ctr_cap = 0;         // its per-tile-group arrival counters (zero between launches)
@@ -1081,6 +1082,22 @@ int check_params(const mi_sample_params* sp) {
   return MI_OK;
 }
 
+// The ABI 4 controls of a sampling call over B rows, checked before anything is enqueued (mi_score_tokens ignores them)
+int check_controls(const mi_sample_params* sp, int B) {
+  if (!sp) return MI_OK;
+  if (sp->top_k < 0) return fail(MI_ERR_INVALID, "mi_sample_params.top_k must be >= 0 (0 = off)");
+  if (!(sp->min_p >= 0.f && sp->min_p <= 1.f)) return fail(MI_ERR_INVALID, "mi_sample_params.min_p must be in [0, 1] (0 = off)");
+  if ((sp->row_seed != nullptr) != (sp->row_position != nullptr))
+    return fail(MI_ERR_INVALID, "mi_sample_params.row_seed and row_position come together");
+  for (int b = 0; b < B; ++b) {
+    if (sp->row_top_k && sp->row_top_k[b] < 0)
+      return fail(MI_ERR_INVALID, "mi_sample_params.row_top_k[" + std::to_string(b) + "] must be >= 0 (0 = off)");
+    if (sp->row_min_p && !(sp->row_min_p[b] >= 0.f && sp->row_min_p[b] <= 1.f))
+      return fail(MI_ERR_INVALID, "mi_sample_params.row_min_p[" + std::to_string(b) + "] must be in [0, 1] (0 = off)");
+  }
+  return MI_OK;
+}
+
 int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* forced = nullptr) {
   mi_sample_params def{}; def.struct_size = sizeof(def); def.temperature = 0.f; def.top_p = 1.f; def.stream_position = -1;
   if (!sp) sp = &def;
@@ -1103,6 +1120,23 @@ int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* f
     MI_HIP(hipMemcpyAsync(e->d_rowpar, sp->row_temperature, B * sizeof(float), hipMemcpyHostToDevice, st));
     MI_HIP(hipMemcpyAsync(e->d_rowpar + B, sp->row_top_p, B * sizeof(float), hipMemcpyHostToDevice, st));
   }
+  const bool ext_rows = !forced && (sp->row_top_k || sp->row_min_p || sp->row_position);
+  if (ext_rows) {                                           // like d_rowpar: [seed B | position B | top_k B | min_p B]
+    if ((size_t)B > e->d_rowext_cap) {
+      MI_HIP(hipStreamSynchronize(st));
+      hipFree(e->d_rowext);
+      e->d_rowext = nullptr; e->d_rowext_cap = 0;
+      MI_HIP(hipMalloc(&e->d_rowext, 24 * (size_t)B));
+      e->d_rowext_cap = B;
+    }
+    char* base = e->d_rowext;
+    if (sp->row_position) {
+      MI_HIP(hipMemcpyAsync(base, sp->row_seed, B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      MI_HIP(hipMemcpyAsync(base + 8 * (size_t)B, sp->row_position, B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    if (sp->row_top_k) MI_HIP(hipMemcpyAsync(base + 16 * (size_t)B, sp->row_top_k, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (sp->row_min_p) MI_HIP(hipMemcpyAsync(base + 20 * (size_t)B, sp->row_min_p, B * sizeof(float), hipMemcpyHostToDevice, st));
+  }
   Prof pr(e, "sample");
   SampleCall sc{};
   sc.logits = e->logits; sc.B = B; sc.V = e->d.vocab_size; sc.rnd = RND_NONE;
@@ -1114,6 +1148,12 @@ int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* f
   sc.lp_temp = sp->logprobs_at_temperature;
   sc.row_temp = per_row ? e->d_rowpar : nullptr;
   sc.row_top_p = per_row ? e->d_rowpar + B : nullptr;
+  if (!forced) {                                            // teacher forcing samples nothing: the controls stay off
+    sc.top_k = sp->top_k; sc.min_p = sp->min_p;
+    if (sp->row_position) { sc.row_seed = (const uint64_t*)e->d_rowext; sc.row_position = (const int64_t*)(e->d_rowext + 8 * (size_t)B); }
+    if (sp->row_top_k) sc.row_top_k = (const int32_t*)(e->d_rowext + 16 * (size_t)B);
+    if (sp->row_min_p) sc.row_min_p = (const float*)(e->d_rowext + 20 * (size_t)B);
+  }
   sc.tokens_out = e->d_next; sc.logprob_out = e->d_logprob; sc.prob_row0_out = forced ? nullptr : e->d_prob0;
   sc.topk_ids = e->d_topk_ids; sc.topk_logprobs = e->d_topk_lp; sc.row_stats = e->d_rowstats;
   return launch_sample(sc, st);
@@ -1215,7 +1255,7 @@ void mi_engine_destroy(mi_engine* e) {
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
   hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->lora_t3); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
-  hipFree(e->d_rowpar); hipFree(e->deq_scratch);
+  hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
   hipFree(e->d_uniforms); hipFree(e->d_topk_ids); hipFree(e->d_topk_lp); hipFree(e->d_bias_ids); hipFree(e->d_bias_vals);
@@ -1668,6 +1708,7 @@ int mi_step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* tokens_in, int B, in
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (!tokens_in && L != 1) return fail(MI_ERR_INVALID, "device-resident token feed needs L == 1");
   if (!tokens_in && e->maxB < B) return fail(MI_ERR_INVALID, "no previous step to take tokens from");
+  MI_TRY(check_controls(sp, B));
   return step_enqueue(e, kv, nullptr, B, tokens_in, L, sp, ticket);
 }
 
@@ -1684,6 +1725,7 @@ int mi_step_enqueue_rows(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, co
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (!tokens_in && L != 1) return fail(MI_ERR_INVALID, "device-resident token feed needs L == 1");
   if (!tokens_in && e->last_n != n) return fail(MI_ERR_INVALID, "device-resident token feed needs the row set of the previous step");
+  MI_TRY(check_controls(sp, n));
   return step_enqueue(e, kv, rows, n, tokens_in, L, sp, ticket);
 }
 
@@ -1706,6 +1748,7 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
   MI_TRY(check_call(e, kv, kv->B, 1));
   if (!ticket) return fail(MI_ERR_INVALID, "null ticket");
   if (sp && (sp->row_temperature != nullptr) != (sp->row_top_p != nullptr)) return fail(MI_ERR_INVALID, "row_temperature and row_top_p come together");
+  MI_TRY(check_controls(sp, n_out));
   MI_TRY(ensure_workspace(e, R, (size_t)std::max(n_out, 1), std::max(n, kv->B)));
   for (size_t i = 0; i < R; ++i)
     if (tokens[i] < 0 || tokens[i] >= e->d.vocab_size) return fail(MI_ERR_INVALID, "token id out of range");

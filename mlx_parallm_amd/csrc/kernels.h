@@ -303,6 +303,13 @@ struct SampleCall {
   int32_t* topk_ids;         // device [B][top_logprobs]
   float* topk_logprobs;
   float* row_stats;          // device [B][2] scratch: (max, logsumexp)
+  // top-k / min-p / per-row streams (sample_kernel<true>).  Behind the older fields, whose offsets the kernel without them keeps
+  int top_k = 0;             // 0 < top_k < V: keep the first top_k candidates of the order (else off)
+  float min_p = 0.f;         // 0 < min_p <= 1: keep p >= min_p * p_max, as (l - max) * (1/T) >= logf(min_p) in float32 (0: off)
+  const int32_t* row_top_k = nullptr;    // device [B] or null: per-row top_k / min_p instead of the scalars (each on its own)
+  const float* row_min_p = nullptr;
+  const uint64_t* row_seed = nullptr;    // device [B], both or neither: row b with row_position[b] >= 0 draws
+  const int64_t* row_position = nullptr; // philox(row_seed[b], row_position[b], 0); < 0: the call-wide (seed, step, b)
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 

@@ -109,6 +109,13 @@ int launch_embed_wk(const LinearW& W, const EmbedCall& c, hipStream_t st) {
 //   temp>0: candidates in descending-probability order (ties: ascending id); nucleus keeps the
 //           prefix whose INCLUSIVE cumulative probability is <= top_p (empty -> top-1, quirk Q5);
 //           the draw is an inverse-CDF pick with one uniform per row.
+//   top_k / min_p: two more prefixes of the same order.  top-k keeps the first k candidates (a cut inside
+//           a tie group keeps its lowest ids); the nucleus is then cut against top_p * Z_k, Z_k = the mass of those k;
+//           min-p keeps the candidates with (l - max) * (1/T) >= logf(min_p) in float32, i.e. p >= min_p * p_max.  The kept
+//           set is the SHORTEST of the three, compared by COUNT (far-tail masses are 0 in fixed point, so a prefix
+//           defined by mass can run past the k-th candidate); the draw is the same pick with u * mass(kept).
+//   streams: a row with row_position[b] >= 0 draws philox(row_seed[b], row_position[b], 0) -- what the call-wide stream
+//           gives row 0 -- whichever index it has in the step; the others keep (seed, step, b).
 // Cumulative masses are integers (probability * 2^40 summed with integer atomics), so the
 // result does not depend on the order in which threads add.
 constexpr int ST = 1024;
@@ -233,6 +240,8 @@ __device__ void build_hist0(const float* lg, int V, float mx, float inv_t, unsig
 // Which bin holds the element at which the descending cumulative mass (starting from `above`) first exceeds
 // `target`?  One wave scans the 256 bins from 255 down (4 bins per lane + a wave scan: two block barriers instead of
 // a block-wide scan); returns through out_sh: mass / count of everything above that bin, and the bin (-1: all fits).
+// BY_COUNT: `target` is a number of candidates instead -- the bin that holds the candidate with that 0-based position.
+template <bool BY_COUNT = false>
 __device__ void select_bin(const unsigned long long* hist_m, const int* hist_c, unsigned long long above, int above_cnt,
                            unsigned long long target, unsigned long long*, int*, int*, Prefix* out_sh) {
   __syncthreads();
@@ -253,7 +262,7 @@ __device__ void select_bin(const unsigned long long* hist_m, const int* hist_c, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (pos == 256) {
-        if (c[j] > 0 && cum + m[j] > target) { pos = 4 * L + j; pm = cum; pc = cnt; }
+        if (c[j] > 0 && (BY_COUNT ? (unsigned long long)(cnt + c[j]) > target : cum + m[j] > target)) { pos = 4 * L + j; pm = cum; pc = cnt; }
         else { cum += m[j]; cnt += c[j]; }
       }
     }
@@ -268,7 +277,13 @@ __device__ void select_bin(const unsigned long long* hist_m, const int* hist_c, 
 
 // Find the descending-order prefix whose cumulative mass is <= target (radix descent over the order key, 8 bits per
 // level; level 0 comes from the cached histogram, the lower levels touch only the elements under the chosen prefix).
-__device__ Prefix find_prefix(const float* lg, int V, float mx, float inv_t, unsigned long long target,
+// BY_COUNT: the prefix of the first `target` candidates instead (target < V) -- kstar = the key of the candidate at that
+// position, ntie = how many candidates of that key lie before it, mass = above + ntie * each like the mass descent.
+// (EXT: one copy per instantiation of the kernel, so that the code of the one without the newer controls does not depend on
+// what the other one calls.  The descent stays a called function, aligned like a kernel: where its loops fall in the
+// instruction cache's lines then does not depend on what the file holds in front of it.)
+template <bool EXT, bool BY_COUNT = false>
+__device__ __attribute__((aligned(256))) Prefix find_prefix(const float* lg, int V, float mx, float inv_t, unsigned long long target,
                               unsigned long long* hist_m, int* hist_c, Prefix* out_sh, const Hist0* h0,
                               unsigned long long* sc_m, int* sc_c, int* sel) {
   uint32_t prefix_bits = 0;   // fixed high bits of kstar so far
@@ -278,7 +293,7 @@ __device__ Prefix find_prefix(const float* lg, int V, float mx, float inv_t, uns
   for (int level = 0; level < 4; ++level) {
     const int shift = 24 - 8 * level;
     if (level == 0) {
-      select_bin(h0->m, h0->c, above, above_cnt, target, sc_m, sc_c, sel, out_sh);
+      select_bin<BY_COUNT>(h0->m, h0->c, above, above_cnt, target, sc_m, sc_c, sel, out_sh);
     } else {
       __syncthreads();
       for (int i = threadIdx.x; i < 256; i += ST) { hist_m[i] = 0; hist_c[i] = 0; }
@@ -292,7 +307,7 @@ __device__ Prefix find_prefix(const float* lg, int V, float mx, float inv_t, uns
         }
       });
       __syncthreads();
-      select_bin(hist_m, hist_c, above, above_cnt, target, sc_m, sc_c, sel, out_sh);
+      select_bin<BY_COUNT>(hist_m, hist_c, above, above_cnt, target, sc_m, sc_c, sel, out_sh);
     }
     above = out_sh->mass;
     above_cnt = out_sh->count;
@@ -311,7 +326,8 @@ __device__ Prefix find_prefix(const float* lg, int V, float mx, float inv_t, uns
     const unsigned long long each = mass_fx(__uint_as_float((prefix_bits & 0x80000000u) ? (prefix_bits & 0x7fffffffu) : ~prefix_bits), mx, inv_t);
     unsigned long long cum = above;
     int n = 0;
-    while (each > 0 && cum + each <= target) { cum += each; ++n; }
+    if constexpr (BY_COUNT) { n = (int)target - above_cnt; cum += (unsigned long long)n * each; }
+    else while (each > 0 && cum + each <= target) { cum += each; ++n; }
     out_sh->mass = cum;
     out_sh->ntie = n;
     out_sh->count = above_cnt + n;
@@ -398,6 +414,29 @@ __device__ int nth_tie(const float* lg, int V, uint32_t kstar, int rank, int* sh
   return last;
 }
 
+// min-p: the candidates with (l - max) * (1/T) >= thr (thr = logf(min_p) <= 0: the arg-max always passes).  The predicate is
+// monotone in l, so they are a prefix of the order, whole tie groups; one walk counts them and sums their masses (into *cnt /
+// *mass, shared).
+__device__ Prefix min_p_prefix(const float* lg, int V, float mx, float inv_t, float thr, unsigned long long* mass, int* cnt) {
+  __syncthreads();
+  if (threadIdx.x == 0) { *mass = 0; *cnt = 0; }
+  __syncthreads();
+  unsigned long long m = 0; int n = 0;
+  for_row(lg, V, [&](float l, int) {
+    if ((l - mx) * inv_t >= thr) { m += mass_fx(l, mx, inv_t); ++n; }
+  });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { m += __shfl_xor(m, o, 64); n += __shfl_xor(n, o, 64); }
+  if ((threadIdx.x & 63) == 0) { atomicAdd(mass, m); atomicAdd(cnt, n); }
+  __syncthreads();
+  Prefix r{0u, 0, *mass, *cnt};
+  __syncthreads();
+  return r;
+}
+
+// EXT = false: temperature / top-p with the call-wide stream, the launch of every call that sets none of the newer controls
+// (its code does not change when they do).  EXT = true: + top-k, min-p and per-row streams.
+template <bool EXT>
 __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
   __shared__ ArgMax sh_am[ST / 64];
   __shared__ float sh_f[ST / 64];
@@ -447,26 +486,52 @@ __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
     const unsigned long long Z = all.mass;
     Prefix kept = all;
     uint32_t keep_key = 0; int keep_tie = 0x7fffffff;
-    if (top_p > 0.f && top_p < 1.f) {
-      const unsigned long long tgt = (unsigned long long)((double)top_p * (double)Z);
-      kept = find_prefix(lg, V, mx, inv_t, tgt, hist_m, hist_c, &sh_p, &h0, sc_m, sc_c, &sel_sh);
-      keep_key = kept.kstar; keep_tie = kept.ntie;
-      if (kept.count == 0) {  // top token alone exceeds top_p (reference: 0/0); keep top-1
-        kept.count = 1; kept.mass = mass_fx(mx, mx, inv_t);
-        keep_key = order_key(mx); keep_tie = 1;
+    bool by_count = false;     // kept was cut by top-k / min-p: its last candidate is known by position, not by (key, tie)
+    if constexpr (EXT) {
+      const int top_k = c.row_top_k ? c.row_top_k[b] : c.top_k;
+      if (top_k > 0 && top_k < all.count) {     // the first top_k candidates: kept.count = top_k, kept.mass = Z_k
+        kept = find_prefix<EXT, true>(lg, V, mx, inv_t, (unsigned long long)top_k, hist_m, hist_c, &sh_p, &h0, sc_m, sc_c, &sel_sh);
+        by_count = true;
       }
     }
-    const float u = c.uniforms ? c.uniforms[b] : philox_uniform(c.seed, c.step, (uint32_t)b);
+    if (top_p > 0.f && top_p < 1.f) {
+      // (EXT: against top_p * Z_k, the nucleus of the top-k survivors; kept.mass == Z without top-k)
+      const unsigned long long tgt = (unsigned long long)((double)top_p * (double)(EXT ? kept.mass : Z));
+      Prefix nuc = find_prefix<EXT>(lg, V, mx, inv_t, tgt, hist_m, hist_c, &sh_p, &h0, sc_m, sc_c, &sel_sh);
+      uint32_t nuc_key = nuc.kstar; int nuc_tie = nuc.ntie;
+      if (nuc.count == 0) {  // top token alone exceeds top_p (reference: 0/0); keep top-1
+        nuc.count = 1; nuc.mass = mass_fx(mx, mx, inv_t);
+        nuc_key = order_key(mx); nuc_tie = 1;
+      }
+      if (!EXT || nuc.count < kept.count) { kept = nuc; keep_key = nuc_key; keep_tie = nuc_tie; by_count = false; }
+    }
+    if constexpr (EXT) {
+      const float min_p = c.row_min_p ? c.row_min_p[b] : c.min_p;
+      if (min_p > 0.f) {
+        const Prefix mp = min_p_prefix(lg, V, mx, inv_t, logf(min_p), &sh_p.mass, &sh_p.count);
+        // (a count of 0 is a threshold above the arg-max, min_p > 1: off)
+        if (mp.count > 0 && mp.count < kept.count) { kept.count = mp.count; kept.mass = mp.mass; by_count = true; }
+      }
+    }
+    float u;
+    if (c.uniforms) u = c.uniforms[b];
+    else if (EXT && c.row_position && c.row_position[b] >= 0) u = philox_uniform(c.row_seed[b], (uint64_t)c.row_position[b], 0u);
+    else u = philox_uniform(c.seed, c.step, (uint32_t)b);
     // first candidate whose inclusive cumulative mass exceeds u * Z_kept
     unsigned long long y = (unsigned long long)((double)u * (double)kept.mass);
     if (y >= kept.mass) y = kept.mass - 1;
-    Prefix pk = find_prefix(lg, V, mx, inv_t, y, hist_m, hist_c, &sh_p, &h0, sc_m, sc_c, &sel_sh);
+    Prefix pk = find_prefix<EXT>(lg, V, mx, inv_t, y, hist_m, hist_c, &sh_p, &h0, sc_m, sc_c, &sel_sh);
     // pk.count candidates lie strictly before the pick; the pick is the next one in order
     int rank_in_key = pk.ntie;
     uint32_t key = pk.kstar;
     if (pk.count >= kept.count) {  // numerical corner: clamp to the last kept candidate
       key = keep_key; rank_in_key = max(keep_tie - 1, 0);
       if (keep_tie == 0x7fffffff) { key = pk.kstar; rank_in_key = max(pk.ntie - 1, 0); }
+      if (EXT && by_count) {       // ... which is the candidate at position kept.count - 1
+        const Prefix last = find_prefix<EXT, true>(lg, V, mx, inv_t, (unsigned long long)(kept.count - 1), hist_m, hist_c, &sh_p,
+                                              &h0, sc_m, sc_c, &sel_sh);
+        key = last.kstar; rank_in_key = last.ntie;
+      }
     }
     token = nth_tie(lg, V, key, rank_in_key, sh_i, tie_tbl, &sel_sh);
     if (token < 0 || token >= V) token = a.i;
@@ -549,7 +614,9 @@ int launch_embed(const LinearW& W, const EmbedCall& c, hipStream_t st) {
 
 int launch_sample(const SampleCall& c, hipStream_t st) {
   if (c.top_logprobs < 0 || c.top_logprobs > MI_MAX_TOP_LOGPROBS) return fail(MI_ERR_INVALID, "sample: top_logprobs out of range");
-  hipLaunchKernelGGL(sample_kernel, dim3(c.B), dim3(ST), 0, st, c);
+  const bool ext = c.top_k > 0 || c.min_p > 0.f || c.row_top_k || c.row_min_p || c.row_position;
+  if (ext) hipLaunchKernelGGL(sample_kernel<true>, dim3(c.B), dim3(ST), 0, st, c);
+  else hipLaunchKernelGGL(sample_kernel<false>, dim3(c.B), dim3(ST), 0, st, c);
   MI_HIP(hipGetLastError());
   if (c.prob_row0_out) {
     hipLaunchKernelGGL(prob_row0_kernel, dim3(1), dim3(64 * ((c.B + 63) / 64)), 0, st, c.logits, c.row_stats,

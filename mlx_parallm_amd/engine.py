@@ -46,11 +46,12 @@ def _i32(a) -> np.ndarray:
 
 
 class SampleArgs:
-    """Arguments of the reference's ``sample`` closure (utils.py:345-364)."""
+    """Arguments of the reference's ``sample`` closure (utils.py:345-364), plus ``top_k`` / ``min_p`` (0 = off; the
+    semantics are in mi355_decode.h and DESIGN.md §2)."""
 
     def __init__(self, temp: float = 0.0, top_p: float = 1.0, logit_bias: Optional[Dict[int, float]] = None,
                  uniforms: Optional[Sequence[float]] = None, seed: int = 0, top_logprobs: int = 0,
-                 logprobs_at_temperature: bool = False, stream_position: int = -1):
+                 logprobs_at_temperature: bool = False, stream_position: int = -1, top_k: int = 0, min_p: float = 0.0):
         self.c = L.SampleParams()
         self.c.struct_size = C.sizeof(L.SampleParams)
         self.c.temperature = float(temp)
@@ -59,6 +60,8 @@ class SampleArgs:
         self.c.top_logprobs = int(top_logprobs)
         self.c.logprobs_at_temperature = 1 if logprobs_at_temperature else 0
         self.c.stream_position = int(stream_position)      # >= 0: Philox counter = the caller's step index (reproducible)
+        self.c.top_k = int(top_k)
+        self.c.min_p = float(min_p)
         self._keep = []
         if logit_bias:
             ids = np.ascontiguousarray(list(logit_bias.keys()), dtype=np.int32)
@@ -78,6 +81,27 @@ class SampleArgs:
         self._row = (t, p)
         self.c.row_temperature = t.ctypes.data_as(C.POINTER(C.c_float))
         self.c.row_top_p = p.ctypes.data_as(C.POINTER(C.c_float))
+
+    def set_row_filters(self, top_ks, min_ps) -> None:
+        """Per-row top_k / min_p (one entry per row of the step) instead of the scalars; either may be None."""
+        k = None if top_ks is None else np.ascontiguousarray(top_ks, dtype=np.int32)
+        m = None if min_ps is None else np.ascontiguousarray(min_ps, dtype=np.float32)
+        if any(a is not None and a.ndim != 1 for a in (k, m)) or (k is not None and m is not None and k.shape != m.shape):
+            raise ValueError("set_row_filters: top_ks and min_ps must be 1-D and of equal length")
+        self._row_filters = (k, m)
+        self.c.row_top_k = None if k is None else k.ctypes.data_as(C.POINTER(C.c_int32))
+        self.c.row_min_p = None if m is None else m.ctypes.data_as(C.POINTER(C.c_float))
+
+    def set_row_streams(self, seeds, positions) -> None:
+        """Per-row Philox streams: row b with positions[b] >= 0 draws from (seeds[b], positions[b]) whichever row of the step
+        it is; positions[b] < 0 keeps the call-wide stream."""
+        s = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        p = np.ascontiguousarray(positions, dtype=np.int64)
+        if s.shape != p.shape or s.ndim != 1:
+            raise ValueError("set_row_streams: seeds and positions must be 1-D and of equal length")
+        self._row_streams = (s, p)
+        self.c.row_seed = s.ctypes.data_as(C.POINTER(C.c_uint64))
+        self.c.row_position = p.ctypes.data_as(C.POINTER(C.c_int64))
 
     def set_uniforms(self, uniforms) -> None:
         if uniforms is None:

@@ -256,6 +256,14 @@ def first_request_params(req: AnyRequest) -> Tuple[int, float, float]:
     return int(mt), float(temp), float(top_p)
 
 
+def request_controls(req: AnyRequest) -> Dict[str, Any]:
+    """``top_k`` / ``min_p`` / ``seed`` of a request as keyword arguments of the generation functions (for a batch: of
+    its first request, like first_request_params); a request without a seed gets a fresh random one."""
+    seed = getattr(req, "seed", None)
+    return dict(top_k=int(getattr(req, "top_k", 0) or 0), min_p=float(getattr(req, "min_p", 0.0) or 0.0),
+                seed=int(seed) if seed is not None else int.from_bytes(os.urandom(4), "little"))
+
+
 @dataclass
 class ExpandedBatch:
     prompts: List[str] = field(default_factory=list)
@@ -451,7 +459,7 @@ def completion_with_logprobs(model, tokenizer, model_id: str, request: Completio
         temp_eff = (temperature if temperature > 0 else 1.0) if nucleus else 0.0      # main.py:578-581
         steps = generate_step(first, model, temp=temp_eff, top_p=top_p if nucleus else 1.0, logit_bias=bias, cache=cache,
                               top_logprobs=topk, return_details=True, logprobs_at_temperature=temperature > 0,
-                              seed=int.from_bytes(os.urandom(4), "little"))
+                              **request_controls(request))
         for _, res in _take(steps, request.max_tokens):
             t = int(res["tokens"][0])
             gen_ids.append(t)
@@ -566,7 +574,7 @@ async def batch_processing_worker(state: ServerState) -> None:
             stats: Dict[str, float] = {}
             kw = dict(model=rec.model_instance, tokenizer=tok, max_tokens=max_tokens, temp=temp, top_p=top_p,
                       max_context_length=cfg.max_context_length, stats=stats,
-                      seed=int.from_bytes(os.urandom(4), "little"))
+                      **request_controls(batch[0].request_data))
             async with state.engine_lock:
                 if cfg.diverse_mode or expanded.any_n_gt1:          # main.py:1074-1086
                     results = await batch_generate_text(prompts=expanded.prompts, disable_prefix_cache=True, **kw)
@@ -663,10 +671,11 @@ async def streaming_batch_worker(state: ServerState) -> None:
             closed = [False] * len(live)
             cancel = threading.Event()
             model = rec.model_instance
+            controls = request_controls(head)
 
             def make_iter():
                 return batch_stream_generate_text(model, tok, prompts, max_tokens, temp=temperature, top_p=top_p,
-                                                  seed=int.from_bytes(os.urandom(4), "little"))
+                                                  **controls)
 
             async with state.engine_lock:
                 async for step in iterate_in_thread(make_iter, cancel):
@@ -925,9 +934,11 @@ def _request_params(req: AnyRequest) -> Tuple[int, float, float]:
     return int(req.max_tokens), float(req.temperature), float(req.top_p)
 
 
-def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyRequest, on_delta: Optional[Callable] = None):
+def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyRequest, on_delta: Optional[Callable] = None,
+            choice: int = 0):
     """Queue one sequence; -> (future resolving to (text, n_prompt, n_completion, finish_reason), n_prompt, sequence).
-    ``sequence.cancel()`` frees its KV slot when the caller gives up (timeout, client disconnect)."""
+    ``sequence.cancel()`` frees its KV slot when the caller gives up (timeout, client disconnect).  A request with a
+    ``seed`` gives choice i the stream of ``seed + i``; without one the sequence draws from the scheduler's stream."""
     loop = asyncio.get_running_loop()
     fut: asyncio.Future = loop.create_future()
     ids = _ids_of(tok, text)[0]
@@ -944,7 +955,10 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
             loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(result))
 
     try:
-        seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink)
+        seed = getattr(req, "seed", None)
+        seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink, top_k=int(getattr(req, "top_k", 0) or 0),
+                                     min_p=float(getattr(req, "min_p", 0.0) or 0.0),
+                                     seed=None if seed is None else int(seed) + choice)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return fut, len(ids), seq
@@ -960,7 +974,7 @@ async def _scheduled_response(state: ServerState, request: AnyRequest, tok: Toke
         text = prompt_text_of(request, tok)
     except Exception as e:
         raise HTTPException(status_code=500, detail=f"Error processing request: {e}")
-    subs = [_submit(state, tok, text, request) for _ in range(n)]
+    subs = [_submit(state, tok, text, request, choice=i) for i in range(n)]
     futs = [sub[0] for sub in subs]
     try:
         results = await asyncio.wait_for(asyncio.gather(*futs), timeout=state.config.request_timeout_seconds)
@@ -1059,8 +1073,7 @@ async def _completion_stream(state: ServerState, request: CompletionRequest,
 
     def make_iter():
         return stream_generate(rec.model_instance, tok, request.prompt, max_tokens=request.max_tokens,
-                               temp=request.temperature, top_p=request.top_p,
-                               seed=int.from_bytes(os.urandom(4), "little"))
+                               temp=request.temperature, top_p=request.top_p, **request_controls(request))
 
     try:
         async with state.stream_slots:

@@ -7,8 +7,10 @@ for -- a request does not wait for the running batch to finish -- and does it on
   * the KV cache has ``max_slots`` rows; a sequence owns one row from admission to its last token;
   * admission = reset the row, prefill the prompt on that row alone (no padding: other rows are not part
     of the call, ``mi_step_enqueue_rows`` with n = 1), emit its first token;
-  * every decode step runs on exactly the rows that are alive, each with its own temperature / top_p
-    (``mi_sample_params.row_temperature / row_top_p``);
+  * every decode step runs on exactly the rows that are alive, each with its own temperature / top_p / top_k / min_p
+    (``mi_sample_params.row_temperature / row_top_p / row_top_k / row_min_p``); a sequence submitted with a ``seed`` draws
+    from its own random stream (``row_seed`` = the seed, ``row_position`` = how many sampling steps the sequence has had), so
+    its draws do not depend on the slot it got or on who else is alive;
   * while the row set is stable the next step is enqueued before the current one is read back, sampled tokens
     stay on the device (the same one-step-ahead pipelining as generate_step, utils.py:420-427); when a sequence
     finishes or a request is waiting, the step already in flight completes, its tokens for finished rows are
@@ -40,11 +42,19 @@ Sink = Callable[["Sequence", Optional[str], Optional[str]], None]
 class Sequence:
     _ids = itertools.count()
 
-    def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok):
+    def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok, *, top_k: int = 0,
+                 min_p: float = 0.0, seed: Optional[int] = None):
+        if int(top_k) < 0:
+            raise ValueError("top_k must be >= 0 (0 = off)")
+        if not 0.0 <= float(min_p) <= 1.0:
+            raise ValueError("min_p must be in [0, 1] (0 = off)")
         self.id = next(Sequence._ids)
         self.prompt = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         self.max_tokens = int(max_tokens)
         self.temp, self.top_p = float(temp), float(top_p)
+        self.top_k, self.min_p = int(top_k), float(min_p)
+        self.seed = None if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.sample_steps = 0              # sampling steps enqueued for this sequence so far: the position in its stream
         self.sink = sink
         self.detok = detok
         self.generated: List[int] = []
@@ -145,8 +155,10 @@ class ContinuousScheduler:
         return need + growth <= st["free_blocks"] + st["evictable_blocks"]
 
     # ------------------------------------------------------------------ client side (any thread)
-    def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink) -> Sequence:
-        seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer))
+    def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, *, top_k: int = 0,
+               min_p: float = 0.0, seed: Optional[int] = None) -> Sequence:
+        seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer),
+                       top_k=top_k, min_p=min_p, seed=seed)
         if len(seq.prompt) == 0:
             raise ValueError("empty prompt")
         if len(seq.prompt) + seq.max_tokens > self.model.engine.max_positions:
@@ -242,6 +254,11 @@ class ContinuousScheduler:
         self._seed = (self._seed + 1) & 0xFFFFFFFF
         sp = SampleArgs(temp=seqs[0].temp, top_p=seqs[0].top_p, seed=self._seed)
         sp.set_row_params([s.temp for s in seqs], [s.top_p for s in seqs])
+        sp.set_row_filters([s.top_k for s in seqs], [s.min_p for s in seqs])
+        # a seeded sequence: its own stream, at the number of sampling steps it has had; the others: the step's stream
+        sp.set_row_streams([s.seed or 0 for s in seqs], [-1 if s.seed is None else s.sample_steps for s in seqs])
+        for s in seqs:
+            s.sample_steps += 1
         return sp
 
     def _admit(self, seq: Sequence, slot: int) -> None:
@@ -474,10 +491,10 @@ class ReplicaPool:
     def _load(self, r: ContinuousScheduler) -> int:
         return len(r.pending) + sum(1 for s in r.slots if s is not None and not s.finished)
 
-    def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink) -> Sequence:
+    def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, **controls) -> Sequence:
         with self._lock:                      # (choice and enqueue together, so concurrent submits spread out)
             r = min(self.replicas, key=self._load)
-            return r.submit(prompt_ids, max_tokens, temp, top_p, sink)
+            return r.submit(prompt_ids, max_tokens, temp, top_p, sink, **controls)
 
     def start(self) -> None:
         for r in self.replicas:

@@ -94,6 +94,9 @@ class CompletionRequest(BaseModel):
     max_tokens: int = Field(100, ge=0)
     temperature: float = Field(0.0, ge=0.0, le=2.0)
     top_p: float = Field(1.0, ge=0.0, le=1.0)
+    top_k: int = Field(0, ge=0)                      # 0 = off (extension: the device sampler's top-k / min-p / seed)
+    min_p: float = Field(0.0, ge=0.0, le=1.0)        # 0 = off
+    seed: Optional[int] = None                       # None = a fresh random stream per request
     stream: Optional[bool] = False
     n: Optional[int] = 1
     logprobs: Optional[int] = None
@@ -113,6 +116,9 @@ class ChatCompletionRequest(BaseModel):
     messages: List[ChatMessage]
     temperature: Optional[float] = 0.7
     top_p: Optional[float] = 1.0
+    top_k: int = Field(0, ge=0)
+    min_p: float = Field(0.0, ge=0.0, le=1.0)
+    seed: Optional[int] = None
     n: Optional[int] = 1
     stream: Optional[bool] = False
     stop: Optional[Union[str, List[str]]] = None

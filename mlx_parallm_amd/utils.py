@@ -194,6 +194,8 @@ def generate_step(
     top_logprobs: int = 0,
     return_details: bool = False,
     logprobs_at_temperature: bool = False,
+    top_k: int = 0,
+    min_p: float = 0.0,
 ) -> Generator[Tuple[np.ndarray, np.ndarray], None, None]:
     """A generator producing token ids from the given prompts (utils.py:315-427).
 
@@ -209,7 +211,9 @@ def generate_step(
     ``uniforms_fn(step) -> (B,)``
     caller-supplied noise, ``top_logprobs``, ``return_details`` (yield the dict ``tokens / logprobs /
     probs_row0 / top_ids / top_logprobs`` instead), ``logprobs_at_temperature`` (report logprobs under
-    ``softmax(logits / temp)``, as the server's logprobs path does, instead of ``softmax(logits)``).
+    ``softmax(logits / temp)``, as the server's logprobs path does, instead of ``softmax(logits)``), ``top_k`` / ``min_p``
+    (0 = off: keep the ``top_k`` most likely tokens, take the nucleus over them, keep ``p >= min_p * p_max``; greedy calls
+    ignore both; ``stream_generate``, ``batch_generate``, ``generate`` and ``batch_stream_generate_text`` pass them through).
     """
     if repetition_penalty:
         raise NotImplementedError("repetition_penalty not supported.")           # utils.py:366-367
@@ -230,7 +234,7 @@ def generate_step(
         u = uniforms_fn(step) if (uniforms_fn is not None and temp != 0) else None
         return SampleArgs(temp=temp, top_p=top_p, logit_bias=logit_bias, uniforms=u, seed=seed,
                           top_logprobs=top_logprobs, logprobs_at_temperature=logprobs_at_temperature,
-                          stream_position=step)
+                          stream_position=step, top_k=top_k, min_p=min_p)
 
     def emit(res):
         if return_details:
@@ -520,7 +524,8 @@ def batch_stream_generate_text(model, tokenizer, prompts_tokens, max_tokens: int
 async def batch_generate_text(model, tokenizer, prompts: List[str], max_tokens: int = 100, temp: float = 0.7,
                               top_p: float = 1.0, disable_prefix_cache: bool = False,
                               max_context_length: Optional[int] = None, *, seed: Optional[int] = None,
-                              stats: Optional[Dict[str, float]] = None) -> List[Tuple[str, int, int]]:
+                              stats: Optional[Dict[str, float]] = None, top_k: int = 0, min_p: float = 0.0
+                              ) -> List[Tuple[str, int, int]]:
     """-> [(text, n_prompt_tokens, n_completion_tokens)] per prompt (utils.py:1087-1346).
 
     Tokenise (left pad, truncate to the effective max length), optional shared-prefix prefill,
@@ -591,7 +596,8 @@ async def batch_generate_text(model, tokenizer, prompts: List[str], max_tokens: 
         t_start = time.perf_counter()
         t_first = None
         for step_num, (ids, _) in _take(
-                generate_step(suffix_batch, model, cache=caches, temp=temp, top_p=top_p, seed=seed), max_tokens):
+                generate_step(suffix_batch, model, cache=caches, temp=temp, top_p=top_p, seed=seed, top_k=top_k,
+                              min_p=min_p), max_tokens):
             if t_first is None:
                 t_first = time.perf_counter()
             any_active = False

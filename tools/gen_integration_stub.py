@@ -16,7 +16,8 @@ BEGIN, END = "# --- BEGIN generated structs (tools/gen_integration_stub.py) ---"
 
 _NAMES = {C.c_int32: "C.c_int32", C.c_uint32: "C.c_uint32", C.c_float: "C.c_float", C.c_uint64: "C.c_uint64",
           C.c_int64: "C.c_int64", C.c_void_p: "C.c_void_p", C.POINTER(C.c_int32): "C.POINTER(C.c_int32)",
-          C.POINTER(C.c_float): "C.POINTER(C.c_float)"}
+          C.POINTER(C.c_float): "C.POINTER(C.c_float)", C.POINTER(C.c_uint64): "C.POINTER(C.c_uint64)",
+          C.POINTER(C.c_int64): "C.POINTER(C.c_int64)"}
 
 
 def struct_src(cls, comment: str) -> str:
