@@ -274,6 +274,11 @@ int mi_profile_read(mi_engine* e, int64_t* n_launches, double* total_ms);
  *                             Any other value: MI_ERR_INVALID, the option keeps its value.
  *   "consumer_combine_guard"  (a check, the value is ignored) MI_OK when the sentinels around the buffer of the q|k|v seam are
  *                             intact, MI_ERR_NOTFOUND when that seam has not run yet, MI_ERR_RUNTIME when one was overwritten
+ *   "resident_x"              0 / 1, for the wide linears (gate|up, lm_head: at least 4 tiles per CU, K <= 4096) of float32-KV
+ *                             decode steps of <= 8 rows on dense bf16 weights (outputs are bit-identical):
+ *                             1: the one-pass GEMV keeps x and the norm weights in LDS for the whole launch (default);
+ *                             0: it fetches them from L2 chunk by chunk (the form every other K runs on).
+ *                             Any other value: MI_ERR_INVALID, the option keeps its value.
  *   "prefill_x_terms"         3: float32-activation (PagedKVCache mode) prefill multiplies an EXACT three-term 16-bit split of x
  *                             by dense bf16 weights (three walks of W); default 2: hi + lo, 16+ mantissa bits of x, two walks
  *                             (the CPU float32-accumulating variants do not move under it: DESIGN 8d); int4 always 3

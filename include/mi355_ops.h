@@ -106,6 +106,11 @@ int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, f
  * K <= 4096, a->pro = MI_PRO_NONE, MI_EPI_STORE / MI_EPI_STORE_F32 / MI_EPI_RESID.  Anything else is MI_ERR_UNSUPPORTED.
  * iters >= 1 also times that many back-to-back launches into *avg_ms. */
 int mi_op_gemv_f32_whole(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
+/* the resident form of that kernel (the gate|up and lm_head launches of the float32-KV decode step) on its own: the calls,
+ * prologue and epilogues of mi_op_gemv_f32 and, output for output, the same bits, with x and the norm weights kept in LDS for
+ * the whole launch -- K <= 4096.  Anything else is MI_ERR_UNSUPPORTED.  mi_op_gemv_f32 itself always runs the chunked kernel.
+ * iters >= 1 also times that many back-to-back launches into *avg_ms. */
+int mi_op_gemv_f32_resident(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* gemm_prefill.hip on its own: the tile GEMM of the prefill call (generate_step's first model call, utils.py:243-262: every
  * nn.Linear over B x L rows at once).  a->M rows of 16-bit activations, tile-major dense 16-bit weights, a->pro =
  * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms.

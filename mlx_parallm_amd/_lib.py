@@ -117,6 +117,7 @@ SIGNATURES = {
                                     C.POINTER(C.c_float)]),
     "mi_op_gemv_f32": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_float)]),
     "mi_op_gemv_f32_whole": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_gemv_f32_resident": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_float)]),
     "mi_op_gemm_prefill": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_float)]),
     "mi_op_gemm_prefill_f32": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mi_op_split_rows": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P]),

@@ -134,6 +134,9 @@ struct mi_engine {
   // the q|k|v linear of a float32-KV decode step publishes its K slices' partial rows and the decode attention's prologue
   // adds them (0: the linear's last arriver combines).  Bit-identical outputs; measurements and history: DESIGN §8e
   int opt_consumer_combine = 1;
+  // the wide linears of a float32-KV decode step (gate|up, lm_head) at K <= 4096 on the resident form of gemv_f32.hip (x kept in
+  // LDS; 0: the chunked kernel).  Bit-identical outputs; measurements: DESIGN §5, §8d
+  int opt_resident_x = 1;
   float* cc_pub = nullptr; size_t cc_pub_floats = 0;   // the q|k|v seam: [guard][8 slices][8 rows][nqkv][guard][8 slices][8 rows][guard]
   float* d_sq = nullptr;        // [4096 tile groups][16 rows]
   bool sq_valid = false; const void* sq_src = nullptr; int sq_parts = 0, sq_K = 0, sq_ld = 0;
@@ -589,6 +592,8 @@ int gemv_rows_on(mi_engine* e, const FusedLinear& f, const FusedLinear& f0, Gemv
     if (take && wv.N / 16 >= 4 * gemv_cu_count() && gemv_f32_supported(wv, cw)) {
       Prof pr(e, prof);
       if (cw.pro == PRO_NORM && !e->opt_defer_norm) MI_TRY(norm_into_xn(e, cw, rows, KT, cw.rnd));
+      // K <= 4096: x and the norm weights stay in LDS, the stream loop waits for weight loads only (same bits)
+      if (e->opt_resident_x && gemv_f32_resident_supported(wv, cw)) return launch_gemv_f32_resident(wv, cw, e->stream);
       return launch_gemv_f32(wv, cw, e->stream);
     }
     // ... and the one NARROW linear whose whole tile a workgroup can request at once (K <= 4096, at most one tile per CU,
@@ -1834,6 +1839,7 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value) {
   if (k == "skinny_gemm") { e->opt_skinny_gemm = value != 0; return MI_OK; }
   if (k == "norm_handover") { e->opt_norm_handover = value != 0; return MI_OK; }
   if (k == "consumer_combine") { if (value != 0 && value != 1) return fail(MI_ERR_INVALID, "consumer_combine: 0 or 1"); e->opt_consumer_combine = (int)value; return MI_OK; }
+  if (k == "resident_x") { if (value != 0 && value != 1) return fail(MI_ERR_INVALID, "resident_x: 0 or 1"); e->opt_resident_x = (int)value; return MI_OK; }
   if (k == "consumer_combine_guard") return check_cc_guards(e, (e->d.num_heads + 2 * e->d.num_kv_heads) * e->d.head_dim);   // (a check, not a setting)
   if (k == "defer_norm") { e->opt_defer_norm = value != 0; return MI_OK; }
   if (k == "prefill_x_terms") { if (value != 2 && value != 3) return fail(MI_ERR_INVALID, "prefill_x_terms: 2 or 3"); e->opt_prefill_x_terms = (int)value; return MI_OK; }

@@ -113,6 +113,11 @@ int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st);
 // at most one tile per CU, c.pro = PRO_NONE, EPI_STORE / EPI_STORE_F32 / EPI_RESID; every load of the launch issued up front
 bool gemv_f32_whole_supported(const LinearW& W, const GemvCall& c);
 int launch_gemv_f32_whole(const LinearW& W, const GemvCall& c, hipStream_t st);
+// the same operator, bit for bit, for the WIDE linears of K <= 4096 (gate|up, lm_head): the stream of launch_gemv_f32 with
+// x and the norm weights staged once per workgroup and kept in LDS (152.25 KiB at K = 4096), so that the stream loop waits
+// for weight loads only; everything gemv_f32_supported takes at such a K
+bool gemv_f32_resident_supported(const LinearW& W, const GemvCall& c);
+int launch_gemv_f32_resident(const LinearW& W, const GemvCall& c, hipStream_t st);
 int gemv_cu_count();            // compute units of the current device (gemv_mfma.hip)
 
 // int4 (group 64) weights, 17..128 rows of 16-bit activations (gemm_q4.hip): x prepared once per launch (fragment-major,

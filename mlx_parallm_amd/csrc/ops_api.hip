@@ -141,6 +141,40 @@ int mi_op_gemv_f32_whole(const mi_op_linear* w, const mi_op_gemv_args* a, int it
   return rc != MI_OK ? rc : rc2;
 }
 
+// the resident form of gemv_f32.hip on its own (x and the norm weights kept in LDS: K <= 4096): mi_op_gemv_f32's calls,
+// epilogues and prologue, with the refusals of its launch.  iters >= 1 additionally times `iters` back-to-back launches.
+int mi_op_gemv_f32_resident(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  LinearW W = to_linear(w);
+  GemvCall c = to_call(a);
+  void* gu8 = nullptr;
+  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } guard{gu8};
+  if (c.epi == EPI_SWIGLU) {
+    GemvCall probe = c; probe.epi = EPI_SWIGLU_GU8;
+    if (!gemv_f32_resident_supported(W, probe)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_resident: call not supported by this kernel");
+    MI_HIP(hipMalloc(&gu8, (size_t)W.N * W.K * sizeof(uint16_t)));
+    MI_TRY(launch_gate_up_interleave(W, c.pair_offset, gu8, nullptr));
+    W.w = gu8; c.epi = EPI_SWIGLU_GU8;
+  }
+  if (!gemv_f32_resident_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_resident: call not supported by this kernel");
+  int rc = launch_gemv_f32_resident(W, c, nullptr);
+  if (rc == MI_OK && iters >= 1 && avg_ms) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32_resident(W, c, nullptr);
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  const int rc2 = finish();
+  return rc != MI_OK ? rc : rc2;
+}
+
 // gemm_skinny.hip on its own: a->M in 9..128 (int4 / int8: 1..128), a->pro must be MI_PRO_NONE; ksplit 0 = the cost model's choice
 // (*ksplit_used returns it); iters >= 1 additionally times `iters` back-to-back launches.  int4 weights above 16 rows with
 // ksplit <= 0 run gemm_q4.hip (a->pro may then be MI_PRO_NORM); ksplit < 0 forces its plan: -(mt | TW << 3 | KW << 7 | ksplit << 11 | NS << 15).
