@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/mi355_decode.h"
@@ -24,6 +27,19 @@ int fail(int code, const std::string& msg);
     int _rc = (expr);         \
     if (_rc != MI_OK) return _rc; \
   } while (0)
+
+// The opt-in of `kernels` for `bytes` of dynamic LDS (more than 64 KiB).  It belongs to the kernel objects of the CURRENT
+// device (one engine per GPU may live in one process: server --devices), and several scheduler threads launch concurrently:
+// one flag per device in `done` (a static array of the caller, one per set of kernels), set after the calls.
+inline int lds_opt_in(std::atomic<bool> (&done)[64], std::initializer_list<const void*> kernels, int bytes) {
+  int dev = 0;
+  MI_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+    for (const void* kern : kernels) MI_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
+  }
+  return MI_OK;
+}
 
 // ---- element types ------------------------------------------------------------------------
 using bf16 = __bf16;

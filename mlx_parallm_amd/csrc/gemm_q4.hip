@@ -614,13 +614,8 @@ namespace {
 template <typename AT, int MT, bool SW>
 int q4_launch_k(const Q4Params& p, int grid, int nthreads, size_t lds, hipStream_t st) {
   auto kern = q4_kernel<AT, MT, SW>;
-  static std::atomic<bool> attr_done[64];
-  int dev = 0;
-  MI_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
-    MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 34 * 1024));
-    if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> opted[64];
+  MI_TRY(lds_opt_in(opted, {(const void*)kern}, 2 * 34 * 1024));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(nthreads), lds, st, p);
   MI_HIP(hipGetLastError());
   return MI_OK;

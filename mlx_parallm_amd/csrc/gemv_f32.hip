@@ -1,10 +1,21 @@
 // gemv_f32.hip -- one-pass weight-streaming GEMV for FLOAT32 activations, <= 8 rows, on dense bf16 weights in the
-// tile-major layout (repack.hip): the wide linears (gate|up, lm_head) of a decode step in the float32-KV
-// ("PagedKVCache") mode of a bf16 model.
+// tile-major layout (repack.hip): gate|up, lm_head and o_proj of a decode step in the float32-KV ("PagedKVCache") mode of
+// a bf16 model.  q|k|v and down_proj stay on the split-K kernel (gemm_skinny.hip).
 //
 // Same operator and the same arithmetic contract as skinny_kernel<.., X32> (gemm_skinny.hip): x = hi + mid + lo exactly
 // (three bf16 terms), every product exact in the float32 accumulator -- a float32 dot product in another summation
-// order; outputs float32, no logical rounding.  What differs is the shape of the launch, which is that of gemv_mfma.hip:
+// order; outputs float32, no logical rounding.  The launch has the shape of gemv_mfma.hip.  Three forms, ONE set of parts:
+//
+//   chunked   gemv_f32{,_gu8}_kernel            any K; a chunk's x comes from L2 through registers (F32Body).  The yardstick.
+//   whole-K   gemv_f32_whole_kernel             K <= 4096, one tile per CU (o_proj): no ring, every load up front
+//   resident  gemv_f32_resident{,_gu8}_kernel   K <= 4096; x and the norm weights stay in LDS (F32Resident): what gate|up
+//                                               and lm_head of Mistral-7B run on
+//
+// All three split x in split8, fetch weights in load_w, sum the waves in publish / sum_waves and address outputs in out_ofs;
+// the chunked and the resident stream share F32Body's position (step), reduction and epilogue (finish, store_out) and pass
+// dispatch (with_pass_size); the two LDS forms share the x image (ximg_*).  So they split, multiply and sum alike by
+// construction, and every output of every form is bit-identical to gemv_f32_kernel on the same call.  What follows is the
+// stream of F32Body; the notes of the other two forms are in front of them.
 //
 //   * One 8-wave workgroup per CU, 16-row tiles of W dealt round-robin (tile = w + i G), NO K split over workgroups:
 //     no workspace, no arrival counter, no partial tiles, nothing that another workgroup of the launch reads.
@@ -27,12 +38,11 @@
 //     ignored).  D = 16 (128 KiB per CU) when a pass has 4 or 8 tiles; otherwise the largest of 14 / 12 / 10 that divides
 //     the 4 NT loads of a chunk, so that the slot of every load is static.
 //     Inside a chunk the waits are the counted vmcnt(D - 1) and the stream does not drain.  AT EVERY CHUNK END IT DOES, in
-//     this kernel: a wave's loads return in issue order, and split_x of the next chunk needs x that was requested two
+//     the chunked form: a wave's loads return in issue order, and split_x of the next chunk needs x that was requested two
 //     positions earlier, behind all but one or two of the wave's weight loads -- the compiler's wait there is vmcnt(8), with
 //     12 x / norm-weight loads younger than the weights it lets through.  The wave stands for about a memory round trip with
 //     its ring nearly empty, and all waves of all workgroups reach their chunk ends together (the wait sequences: DESIGN §8d).
-//     The resident form at the end of this file takes x out of the vector-memory queue of the loop; it is what the wide
-//     linears of K <= 4096 run on.  This kernel stays for every other K and as the bit-for-bit yardstick.
+//     The resident form takes x out of the vector-memory queue of the loop.
 //   * RMSNorm (PRO_NORM) is deferred and local: x is multiplied by the norm weight while it is split, the squares of the
 //     raw x are summed on the way (first pass only: each element once per launch), and rs[m] = rsqrt(mean + eps) scales
 //     the dot product in the epilogue.  Every workgroup sees all of x, so it owns the complete row sums.  In float32
@@ -41,15 +51,9 @@
 // Every load is addressed as a wave-uniform 64-bit base plus a 32-bit lane offset: with one 64-bit address pair per load
 // position the loop spilled, and a spill reload drains the prefetch queue.
 //
-// Resources: 512 threads, 254 VGPRs (one workgroup per CU), no scratch.  LDS: 32.5 KiB static -- the cross-wave
-// reduction of a pass ([8 tiles][8 waves][32 lanes] float4 = 32 KiB, written once per pass after the last chunk) and
-// the waves' row sums of squares (8 x 8 floats).
-//
-// A second kernel of this file, gemv_f32_whole_kernel, is the same operator for the one NARROW linear of that step whose
-// whole tile fits a workgroup's load queue (o_proj: one tile per CU, K <= 4096): no ring, no chunks, every load up front,
-// bit-identical outputs.  Its notes are in front of it.  q|k|v and down_proj stay on the split-K kernel (gemm_skinny.hip).
-// A third, gemv_f32_resident{,_gu8}_kernel, is this kernel's stream with x and the norm weights kept in LDS (K <= 4096): the
-// form gate|up and lm_head of Mistral-7B run on, bit-identical again; its notes are in front of it, too.
+// Resources of the chunked form: 512 threads, 255 VGPRs (one workgroup per CU), no scratch.  LDS: 32.5 KiB static -- the
+// cross-wave reduction of a pass ([8 tiles][8 waves][32 lanes] float4 = 32 KiB, written once per pass after the last chunk)
+// and the waves' row sums of squares (8 x 8 floats).
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -67,6 +71,7 @@ constexpr int F32_NW = 8;                       // waves per workgroup
 constexpr int F32_TP = 8;                       // tiles per pass (one accumulator each)
 constexpr int F32_KB = 32;                      // k-blocks (of 32) per chunk: chunks of 1024
 constexpr int F32_UB = F32_KB / F32_NW;         // blocks per wave, tile and chunk
+constexpr int F32_LB = 16;                      // k-blocks per wave of the forms that hold a wave's x at once: K <= 8 * 16 * 32
 
 struct F32Params {
   const float* x; int ldx; int M;
@@ -92,9 +97,14 @@ __device__ __forceinline__ gptr uniform_ptr(const void* base, size_t off) {
   return (gptr)(((uint64_t)hi << 32) | lo);
 }
 
+// this lane's 16 bytes of the 1-KiB block (tile t, k-block kb) of W, non-temporal (a tile is K * 32 bytes)
+__device__ __forceinline__ u32x4 load_w(const void* w, int t, int kb, int nkb, int lane) {
+  const gptr tb = uniform_ptr(w, ((size_t)t * nkb + kb) * 1024);
+  return __builtin_nontemporal_load((gptr16)(tb + (uint32_t)lane * 16u));
+}
+
 // Two floats -> hi + mid + lo exactly (three bf16 terms each) -> one dword of a lane's two A-fragment images: `low` lanes
-// (fragment rows 0..7) hold hi and lo, the others mid and zeros.  Every kernel of this file splits x here, which is why
-// their outputs agree bit for bit.
+// (fragment rows 0..7) hold hi and lo, the others mid and zeros.
 __device__ __forceinline__ void split3(f32x2 f, bool low, uint32_t& a0, uint32_t& a1) {
   const uint32_t hi = pack2<bf16>(f);
   const f32x2 r1 = f - unpack2<bf16>(hi);
@@ -102,6 +112,93 @@ __device__ __forceinline__ void split3(f32x2 f, bool low, uint32_t& a0, uint32_t
   const uint32_t lo = pack2<bf16>(r1 - unpack2<bf16>(mid));
   a0 = low ? hi : mid;
   a1 = low ? lo : 0u;
+}
+
+// THE split of this file.  The 8 floats of a lane's A-fragment position of one k-block (two registers of raw x and, under
+// `norm`, two of the norm weights of its columns) -> (x * w_norm) -> hi / mid / lo -> the lane's two fragment images `a`.
+// `add`: the fmaf chain of the squares of the raw x goes to ss.  (The sum stays in here: handed back to the caller for the
+// add, the same arithmetic compiled to another schedule of the chunked kernels, with spills.)
+__device__ __forceinline__ void split8(const u32x4 (&x)[2], const u32x4 (&n)[2], bool norm, bool low, u32x4 (&a)[2], bool add, float& ss) {
+  const uint32_t xd[8] = {x[0].x, x[0].y, x[0].z, x[0].w, x[1].x, x[1].y, x[1].z, x[1].w};
+  const uint32_t nd[8] = {n[0].x, n[0].y, n[0].z, n[0].w, n[1].x, n[1].y, n[1].z, n[1].w};
+  uint32_t a0[4], a1[4];
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f32x2 f = {__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])};
+    if (norm) {
+      const f32x2 wf = {__uint_as_float(nd[2 * j]), __uint_as_float(nd[2 * j + 1])};
+      sq = fmaf(f.x, f.x, sq); sq = fmaf(f.y, f.y, sq);
+      f = f * wf;
+    }
+    split3(f, low, a0[j], a1[j]);
+  }
+  a[0] = u32x4{a0[0], a0[1], a0[2], a0[3]};
+  a[1] = u32x4{a1[0], a1[1], a1[2], a1[3]};
+  if (add) ss += sq;
+}
+
+// ---- The LDS image of x, float32, in fragment order (the whole-K and the resident form) ------------------------------------
+// k-block kb is one KiB: [half h of the 8 floats][lane group g][row m] x 16 bytes.  Wave v fetches and stores exactly the
+// blocks it multiplies, so x crosses lanes (through LDS), never waves: no workgroup barrier between x and the MFMAs.
+// Fetch: M rows x K floats once per workgroup, 16 bytes per lane and load; lane l takes row l & 7, piece l >> 3 (4 floats)
+// of the block: a wave-load covers one 128-byte line of each of the 8 rows.  (Fewer than 8 rows: the lanes of the missing
+// rows re-load the last row into an image row that is never read.)  A store (8 consecutive lanes = the 8 rows of one
+// piece) fills 128 contiguous bytes; a fragment read (ds_read_b128: 16-lane groups that span two g and all rows; lanes c16
+// and c16 + 8 share an address) covers 256 contiguous bytes: neither has a bank conflict.
+constexpr int XIMG_BLOCK = 1024, XIMG_HALF = 512;
+__device__ __forceinline__ uint32_t ximg_fetch_ofs(int lane, int M, int ldx) {      // in x, from the block's first column of row 0
+  return ((uint32_t)min(lane & 7, M - 1) * (uint32_t)ldx + 4u * (lane >> 3)) * 4u;   // (<= 8 rows: far below 4 GiB)
+}
+__device__ __forceinline__ uint32_t ximg_store_ofs(int lane) {                      // in an image block: the fetched piece
+  return (uint32_t)(((lane >> 3) & 1) * XIMG_HALF + ((lane >> 4) * 8 + (lane & 7)) * 16);
+}
+__device__ __forceinline__ uint32_t ximg_read_ofs(int lane, int M) {                // in an image block: the fragment position
+  return (uint32_t)(((lane >> 4) * 8 + min(lane & 7, M - 1)) * 16);
+}
+// STRAIGHT-LINE: a block past the end re-loads block 0
+__device__ __forceinline__ u32x4 ximg_fetch(const float* x, uint32_t fetch_ofs, int kb, int nkb) {
+  const gptr xb = uniform_ptr(x, (size_t)(kb < nkb ? kb : 0) * 128);
+  return *(gptr16)(xb + fetch_ofs);
+}
+__device__ __forceinline__ void ximg_read(const unsigned char* blk, uint32_t read_ofs, u32x4 (&x)[2]) {
+  x[0] = *(const u32x4*)(blk + read_ofs);
+  x[1] = *(const u32x4*)(blk + read_ofs + XIMG_HALF);
+}
+
+// ---- The cross-wave reduction ------------------------------------------------------------------------------------------------
+// Lane (c16, g) holds D rows 4 g + r: rows 0..7 (hi and lo products) in g < 2, rows 8..15 (mid products) in g >= 2 -- added
+// here; lanes 0..31 publish y[m = 4 (lane >> 4) + r][n = lane & 15] of their wave into slot `tl` of `red` (4 KiB per slot)
+__device__ __forceinline__ void publish(float* red, int tl, int wave, int lane, f32x4 v) {
+  v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
+  if (lane < 32) *(f32x4*)&red[((tl * F32_NW + wave) * 32 + lane) * 4] = v;
+}
+// columns cc and cc + 8 of row m of slot t: the waves' parts, wave 0 .. 7 in order
+__device__ __forceinline__ void sum_waves(const float* red, int t, int m, int cc, float& y0, float& y1) {
+  const int el = (m >> 2) * 16 + cc, r = m & 3;
+  y0 = 0.f; y1 = 0.f;
+#pragma unroll
+  for (int ww = 0; ww < F32_NW; ++ww) {
+    y0 += red[((t * F32_NW + ww) * 32 + el) * 4 + r];
+    y1 += red[((t * F32_NW + ww) * 32 + el + 8) * 4 + r];
+  }
+}
+// column cc of row m of a 16-column tile in out / resid (its partner of sum_waves: + 8)
+__device__ __forceinline__ size_t out_ofs(int m, int ldo, int tile, int cc) { return (size_t)m * ldo + tile * 16 + cc; }
+
+// f(NT) for a pass of nt tiles (1..8), NT = nt as a std::integral_constant: THE dispatch on the pass size
+template <class F>
+__device__ __forceinline__ void with_pass_size(int nt, F&& f) {
+  switch (nt) {
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 1>{}); break;
+  }
 }
 
 template <bool GU8>
@@ -137,10 +234,11 @@ struct F32Body {
 
   // STRAIGHT-LINE (gemv_phase.h issue_u): an invalid slot re-loads block 0 of this workgroup's first tile
   __device__ __forceinline__ void issue(int slot, int i, int kb, bool valid) {
-    const int t = valid ? tile_of(i) : w, b = valid ? kb : 0;
-    // a uniform 64-bit tile base plus a 32-bit lane offset (a tile is K * 32 bytes): no per-position address registers
-    const gptr tb = uniform_ptr(p.w, ((size_t)t * nkb + b) * 1024);
-    ring[slot] = __builtin_nontemporal_load((gptr16)(tb + (uint32_t)lane * 16u));
+    ring[slot] = load_w(p.w, valid ? tile_of(i) : w, valid ? kb : 0, nkb, lane);
+  }
+  __device__ __forceinline__ void issue_first(int s, int i0) {
+    const int kb = (s % F32_UB) * F32_NW + wave;
+    issue(s, i0 + s / F32_UB, kb, kb < nkb);
   }
 
   // the x (and norm weights) of this wave's block u of chunk c, into registers
@@ -157,26 +255,32 @@ struct F32Body {
 
   // registers -> (x * w_norm) -> hi / mid / lo -> the two A-fragment images of this lane for block u of chunk c.
   // `count`: the squares of the raw x go to the row sums
-  __device__ __forceinline__ void split_x(int c, int u, bool count) {
-    const bool low = c16 < 8;
-    const int kb = c * F32_KB + u * F32_NW + wave;
-    const uint32_t xd[8] = {xr[u][0].x, xr[u][0].y, xr[u][0].z, xr[u][0].w, xr[u][1].x, xr[u][1].y, xr[u][1].z, xr[u][1].w};
-    const uint32_t nd[8] = {nr[u][0].x, nr[u][0].y, nr[u][0].z, nr[u][0].w, nr[u][1].x, nr[u][1].y, nr[u][1].z, nr[u][1].w};
-    uint32_t a0[4], a1[4];
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 f = {__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])};
-      if (norm) {
-        const f32x2 wf = {__uint_as_float(nd[2 * j]), __uint_as_float(nd[2 * j + 1])};
-        sq = fmaf(f.x, f.x, sq); sq = fmaf(f.y, f.y, sq);
-        f = f * wf;
-      }
-      split3(f, low, a0[j], a1[j]);
+  __device__ __forceinline__ void split(int c, int u, bool count, const u32x4 (&x)[2], const u32x4 (&n)[2]) {
+    split8(x, n, norm, c16 < 8, af[u], count && c * F32_KB + u * F32_NW + wave < nkb, ss);
+  }
+  __device__ __forceinline__ void split_x(int c, int u, bool count) { split(c, u, count, xr[u], nr[u]); }
+
+  // One position of the stream: the MFMA pair of block u of tile t on ring[slot], then the same registers are re-loaded with
+  // the load D positions ahead in this workgroup's sequence (`last`: into the next pass, if there is one: `have_next`)
+  template <int NT>
+  __device__ __forceinline__ void step(int i0, int c, int nc, int t, int u, bool last, bool have_next) {
+    constexpr int L = NT * F32_UB, D = f32_depth(NT);
+    const int pos = t * F32_UB + u, slot = pos % D;
+    if (c * F32_KB + u * F32_NW + wave < nkb) {         // (wave-uniform; no load inside)
+      acc[t] = mfma16<bf16>(af[u][0], ring[slot], acc[t]);
+      acc[t] = mfma16<bf16>(af[u][1], ring[slot], acc[t]);
     }
-    af[u][0] = u32x4{a0[0], a0[1], a0[2], a0[3]};
-    af[u][1] = u32x4{a1[0], a1[1], a1[2], a1[3]};
-    if (count && kb < nkb) ss += sq;
+    __builtin_amdgcn_sched_barrier(0);
+    const int q = pos + D;
+    if (q < L) {
+      const int kb = c * F32_KB + (q % F32_UB) * F32_NW + wave;
+      issue(slot, i0 + q / F32_UB, kb, kb < nkb);
+    } else {
+      const int q2 = q - L;
+      const int kb = nc * F32_KB + (q2 % F32_UB) * F32_NW + wave;
+      issue(slot, (last ? i0 + NT : i0) + q2 / F32_UB, kb, have_next && kb < nkb);
+    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 
   // One pass: tiles i0 .. i0 + NT - 1 of this workgroup over all of K.  `preloaded`: the previous pass has issued this
@@ -188,10 +292,7 @@ struct F32Body {
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (!preloaded) {
 #pragma unroll
-      for (int s = 0; s < D; ++s) {
-        const int kb = (s % F32_UB) * F32_NW + wave;
-        issue(s, i0 + s / F32_UB, kb, kb < nkb);
-      }
+      for (int s = 0; s < D; ++s) issue_first(s, i0);
 #pragma unroll
       for (int u = 0; u < F32_UB; ++u) load_x(0, u);
 #pragma unroll
@@ -214,96 +315,86 @@ struct F32Body {
       for (int t = 0; t < NT; ++t) {
 #pragma unroll
         for (int u = 0; u < F32_UB; ++u) {
-          const int pos = t * F32_UB + u, slot = pos % D;
-          if (c * F32_KB + u * F32_NW + wave < nkb) {       // (wave-uniform; no load inside)
-            acc[t] = mfma16<bf16>(af[u][0], ring[slot], acc[t]);
-            acc[t] = mfma16<bf16>(af[u][1], ring[slot], acc[t]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          // the same registers are re-loaded with the load D positions ahead in this workgroup's sequence
-          const int q = pos + D;
-          if (q < L) {
-            const int kb = c * F32_KB + (q % F32_UB) * F32_NW + wave;
-            issue(slot, i0 + q / F32_UB, kb, kb < nkb);
-          } else {
-            const int q2 = q - L;
-            const int kb = nc * F32_KB + (q2 % F32_UB) * F32_NW + wave;
-            issue(slot, (last ? i0 + NT : i0) + q2 / F32_UB, kb, have_next && kb < nkb);
-          }
-          __builtin_amdgcn_sched_barrier(0);
+          const int pos = t * F32_UB + u;
+          step<NT>(i0, c, nc, t, u, last, have_next);
           if (pos >= L - F32_UB) split_x(nc, pos - (L - F32_UB), first && !last);
           if (pos + XD >= L - F32_UB && pos + XD < L) load_x(nc, pos + XD - (L - F32_UB));
         }
       }
     }
 
-    // ---- cross-wave reduction.  Lane (c16, g) holds D rows 4 g + r: rows 0..7 (hi and lo products) in g < 2, rows
-    // 8..15 (mid products) in g >= 2 -- added here, lanes 0..31 publish y[m = 4 (lane >> 4) + r][n = lane & 15]
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      f32x4 v = acc[t];
-      v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
-      if (lane < 32) *(f32x4*)&red[((t * F32_NW + wave) * 32 + lane) * 4] = v;
+    finish<NT, NT, false>(i0, first);
+  }
+
+  // row scale, GU8, residual and store tail of one output pair
+  __device__ __forceinline__ void store_out(int m, int cc, int tile, float y0, float y1) {
+    y0 *= rs; y1 *= rs;
+    if constexpr (GU8) {
+      // row-interleaved gate|up tile: columns 0..7 are gate rows 8 tile .. + 7, columns 8..15 the matching up rows
+      const float sig = 1.0f / (1.0f + expf(-y0));
+      const float sl = y0 * sig;
+      p.out[(size_t)m * p.ldo + tile * 8 + cc] = sl * y1;
+    } else {
+      const size_t o = out_ofs(m, p.ldo, tile, cc);
+      if (p.epi == EPI_RESID) {
+        const float h0 = p.resid[o], h1 = p.resid[o + 8];
+        p.resid[o] = h0 + y0; p.resid[o + 8] = h1 + y1;
+      } else {                                    // EPI_STORE and EPI_STORE_F32 coincide
+        p.out[o] = y0; p.out[o + 8] = y1;
+      }
     }
+  }
+
+  // the cross-wave reduction and epilogue of a pass, TR tiles per round; OVER: behind a barrier, `red` runs on into the images
+  template <int NT, int TR, bool OVER>
+  __device__ __forceinline__ void finish(int i0, bool first) {
     if (first && norm) {
       float v = ss;                               // lanes c16 < 8: row c16, the four k-groups of the wave's blocks
       v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
       if (lane < 8) sq_sh[wave * 8 + lane] = v;
     }
-    __syncthreads();
-    // thread (t, m, c): columns c and c + 8 of row m of tile t
+    // thread (t, m, c): columns c and c + 8 of row m of tile t of the round
     const int t = tid >> 6, m = (tid >> 3) & 7, cc = tid & 7;
-    if (first && norm) {
-      float tot = 0.f;
 #pragma unroll
-      for (int ww = 0; ww < F32_NW; ++ww) tot += sq_sh[ww * 8 + m];
-      rs = 1.0f / sqrtf(tot / (float)p.K + p.eps);
-    }
-    if (t < NT && m < p.M) {
-      const int el = (m >> 2) * 16 + cc, r = m & 3;
-      float y0 = 0.f, y1 = 0.f;
+    for (int r0 = 0; r0 < NT; r0 += TR) {
+      if (OVER || r0 > 0) __syncthreads();        // the last pass: every wave is done with the images; a later round: with `red`
 #pragma unroll
-      for (int ww = 0; ww < F32_NW; ++ww) {
-        y0 += red[((t * F32_NW + ww) * 32 + el) * 4 + r];
-        y1 += red[((t * F32_NW + ww) * 32 + el + 8) * 4 + r];
+      for (int tl = 0; tl < TR; ++tl) publish(red, tl, wave, lane, acc[r0 + tl]);
+      __syncthreads();
+      if (r0 == 0 && first && norm) {
+        float tot = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < F32_NW; ++ww) tot += sq_sh[ww * 8 + m];
+        rs = 1.0f / sqrtf(tot / (float)p.K + p.eps);
       }
-      y0 *= rs; y1 *= rs;
-      const int tile = w + (i0 + t) * G;          // (t < NT: one of this workgroup's tiles)
-      if constexpr (GU8) {
-        // row-interleaved gate|up tile: columns 0..7 are gate rows 8 tile .. + 7, columns 8..15 the matching up rows
-        const float sig = 1.0f / (1.0f + expf(-y0));
-        const float sl = y0 * sig;
-        p.out[(size_t)m * p.ldo + tile * 8 + cc] = sl * y1;
-      } else {
-        const size_t o = (size_t)m * p.ldo + tile * 16 + cc;
-        if (p.epi == EPI_RESID) {
-          const float h0 = p.resid[o], h1 = p.resid[o + 8];
-          p.resid[o] = h0 + y0; p.resid[o + 8] = h1 + y1;
-        } else {                                  // EPI_STORE and EPI_STORE_F32 coincide
-          p.out[o] = y0; p.out[o + 8] = y1;
-        }
+      if (t < TR && m < p.M) {
+        float y0, y1;
+        sum_waves(red, t, m, cc, y0, y1);
+        store_out(m, cc, w + (i0 + r0 + t) * G, y0, y1);    // (t < TR, r0 + t < NT: one of this workgroup's tiles)
       }
     }
+  }
+
+  // the size of the pass that begins at this workgroup's tile `done`; `roll`: it is full and so is the one behind it
+  __device__ __forceinline__ int pass_size(int done, bool& roll) const {
+    const int nt = min(F32_TP, ntiles - done);
+    roll = nt == F32_TP && ntiles - done - nt >= F32_TP;
+    return nt;
   }
 
   __device__ __forceinline__ void run() {
     int done = 0;
     bool pre = false;
     while (done < ntiles) {
-      const int nt = min(F32_TP, ntiles - done);
-      const bool roll = nt == F32_TP && ntiles - done - nt >= F32_TP;
+      bool roll;
+      const int nt = pass_size(done, roll);
       const bool first = done == 0;
       if (done > 0) __syncthreads();              // `red` is reused
-      switch (nt) {
-        case 8: pass<8>(done, pre, roll, first); break;
-        case 7: pass<7>(done, false, false, first); break;
-        case 6: pass<6>(done, false, false, first); break;
-        case 5: pass<5>(done, false, false, first); break;
-        case 4: pass<4>(done, false, false, first); break;
-        case 3: pass<3>(done, false, false, first); break;
-        case 2: pass<2>(done, false, false, first); break;
-        default: pass<1>(done, false, false, first); break;
-      }
+      // (only a full pass is ever preloaded or rolls)
+      with_pass_size(nt, [&](auto n) __attribute__((always_inline)) {
+        constexpr int NT = decltype(n)::value;
+        pass<NT>(done, NT == F32_TP && pre, NT == F32_TP && roll, first);
+      });
       pre = roll;
       done += nt;
     }
@@ -328,22 +419,15 @@ __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_gu8_kernel(F32Params p) 
 
 // ---- The whole-K form: one 16-row tile per workgroup, K <= 4096, every byte of the launch requested up front --------------
 // A narrow linear (N / 16 <= CUs: o_proj) has one tile per CU, and at K <= 4096 a wave's share of it is at most 16 k-blocks
-// -- the 16 loads a wave of the kernel above keeps in flight.  So there is no ring and no chunk: wave v issues the loads of
-// ALL its blocks v, v + 8, v + 16, ... at once (128 KiB per CU at K = 4096), multiplies them in ascending order as they
-// land, and the workgroup ends in the reduction and epilogue of F32Body::pass<1>.  Same splits (split3), same MFMAs in the
-// same order, same sums: every output is bit-identical to gemv_f32_kernel on the same call.
+// -- the 16 loads a wave of the stream keeps in flight.  So there is no ring and no chunk: wave v issues the loads of ALL
+// its blocks v, v + 8, v + 16, ... at once (128 KiB per CU at K = 4096), multiplies them in ascending order as they land,
+// and the workgroup ends in the reduction of a pass of one tile (publish, sum_waves).
 //
 // Program order, straight-line (no load under a branch; a slot past the wave's last block re-loads a valid block and is
 // ignored).  A CU returns loads in issue order, so what a block's MFMAs need is asked for in the order they need it:
 //   * EPI_RESID: the two h values of each epilogue thread (only this workgroup writes them in this launch), first -- two
-//     4-byte loads, out of the way before the stream.
+//     4-byte loads, out of the way before the stream, not dependent loads at the very end.
 //   * then PER BLOCK, x and right behind it the block's weights: x0 w0 x1 w1 ... x15 w15.
-//     x: M rows x K floats, once per workgroup, 16 bytes per thread and load.  Lane l of wave v takes row l & 7, piece
-//     l >> 3 (4 floats) of the block: a wave-load covers one 128-byte line of each of the 8 rows, and wave v stages
-//     exactly the blocks it multiplies -- x crosses lanes (through LDS), never waves, so there is no workgroup barrier
-//     between x and the MFMAs.  (Fewer than 8 rows: the lanes of the missing rows re-load the last row into an image row
-//     that is never read.)
-//     weights: non-temporal, uniform 64-bit base + 32-bit lane offset (uniform_ptr).
 //     All of x in front of all the weights (the first form built) was measured and is slower in the step: 11.17 against
 //     10.58 us per launch (traces of two boxes), 0.051-0.058 against 0.082 ms per step in the A/B.  The
 //     reasoning behind the interleaved order, an estimate that no stamp backs: 128 x-loads per CU at 16 cycles each on
@@ -351,91 +435,72 @@ __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_gu8_kernel(F32Params p) 
 //     the first weight request leaves behind ONE x load, x (an L2 hit) is back long before the weights in front of it,
 //     and the in-order return hands every block its x just ahead of its weights.  Back to back, with the matrix
 //     resident in the Infinity Cache, the order is the other way round (9.7 against 10.0 us), and the step is what counts.
-// Then per block, as its loads land (counted vmcnt: 31, 30, ... 0): x -> LDS -> the lane's fragment position -> split ->
-// two MFMAs.  The LDS round trip and the split of block u run while block u's weights are still on their way.
-//
-// LDS image of x, float32, in fragment order: k-block kb is one KiB, [half h of the 8 floats][lane group g][row m] x 16
-// bytes.  A store (8 consecutive lanes = the 8 rows of one piece) fills 128 contiguous bytes; a fragment read
-// (ds_read_b128: 16-lane groups that span two g and all rows; lanes c16 and c16 + 8 share an address) covers 256
-// contiguous bytes: neither has a bank conflict.  The raw x of all 16 blocks is in registers as loaded (64 VGPRs, next to
-// the 64 of the weights: everything is in flight at once); a block's pieces leave for LDS as they land, and only ONE block's
-// fragment position is read back and split at a time: never 16 blocks of split fragments.
+// Then per block, as its loads land (counted vmcnt: 31, 30, ... 0): x -> the image -> the lane's fragment position -> split
+// -> two MFMAs.  The LDS round trip and the split of block u run while block u's weights are still on their way.  The raw x
+// of all 16 blocks is in registers as loaded (64 VGPRs, next to the 64 of the weights: everything is in flight at once), and
+// only ONE block's fragment position is read back and split at a time: never 16 blocks of split fragments.
 //
 // Resources: 512 threads, 155 VGPRs, one workgroup per CU, no scratch.  LDS (dynamic, above 64 KiB -> function attribute):
 // the 4-KiB reduction + K / 32 KiB of x (at least one block per wave, so that the ignored slots stay inside it): 132 KiB
 // at K = 4096.
-constexpr int F32W_UB = 16;                      // k-blocks per wave: K <= 8 * 16 * 32
 constexpr int F32W_RED = F32_NW * 32 * 16;       // bytes of the cross-wave reduction, in front of the x image
-constexpr size_t f32_whole_lds_bytes(int K) { return F32W_RED + (size_t)(K / 32 > F32_NW ? K / 32 : F32_NW) * 1024; }
+constexpr size_t f32_whole_lds_bytes(int K) { return F32W_RED + (size_t)(K / 32 > F32_NW ? K / 32 : F32_NW) * XIMG_BLOCK; }
 
 __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_whole_kernel(F32Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char whole_lds[];
   float* red = (float*)whole_lds;
   unsigned char* ximg = whole_lds + F32W_RED;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c16 = lane & 15, g = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int w = blockIdx.x, nkb = p.K / 32;
 
-  // (b) thread (m, c) of wave 0 finishes columns c and c + 8 of row m (F32Body::pass): its h now, not as a dependent load
-  // at the very end.  Straight-line: the pointer is selected, the load is not under a branch.
+  // thread (m, c) of wave 0 finishes columns c and c + 8 of row m (as F32Body::finish): its h now.  Straight-line: the
+  // pointer is selected, the load is not under a branch.
   const int em = (tid >> 3) & 7, ecc = tid & 7;
   const bool ep = tid < 64 && em < p.M;
   const bool res = ep && p.epi == EPI_RESID;
-  const size_t eo = (size_t)em * p.ldo + w * 16 + ecc;
+  const size_t eo = out_ofs(em, p.ldo, w, ecc);
   const float* hp = res ? p.resid + eo : p.x;
   const float h0 = hp[0], h1 = hp[res ? 8 : 0];
   __builtin_amdgcn_sched_barrier(0);
-  // (a), (c) per block: its x -- row lane & 7 (clamped), 16-byte piece lane >> 3 of the block's 128 bytes per row -- then its weights
-  u32x4 xs[F32W_UB], ring[F32W_UB];
-  const uint32_t xlane = ((uint32_t)min(lane & 7, p.M - 1) * (uint32_t)p.ldx + 4u * (lane >> 3)) * 4u;   // (<= 8 rows: far below 4 GiB)
+  u32x4 xs[F32_LB], ring[F32_LB];
+  const uint32_t xlane = ximg_fetch_ofs(lane, p.M, p.ldx);
 #pragma unroll
-  for (int u = 0; u < F32W_UB; ++u) {
-    const int kb = u * F32_NW + wave, b = kb < nkb ? kb : 0;
-    const gptr xb = uniform_ptr(p.x, (size_t)b * 128);
-    xs[u] = *(gptr16)(xb + xlane);
+  for (int u = 0; u < F32_LB; ++u) {
+    const int kb = u * F32_NW + wave;
+    xs[u] = ximg_fetch(p.x, xlane, kb, nkb);
     __builtin_amdgcn_sched_barrier(0);
-    const gptr tb = uniform_ptr(p.w, ((size_t)w * nkb + b) * 1024);
-    ring[u] = __builtin_nontemporal_load((gptr16)(tb + (uint32_t)lane * 16u));
+    ring[u] = load_w(p.w, w, kb < nkb ? kb : 0, nkb, lane);
     __builtin_amdgcn_sched_barrier(0);
   }
 
   // Per block, as its loads land: x -> LDS image (wave-uniform branch, no load inside) -> this lane's fragment position ->
   // split -> two MFMAs.  The image rows a wave reads are the ones it wrote, and the LDS operations of a wave complete in order.
-  const uint32_t wofs = (uint32_t)(((lane >> 3) & 1) * 512 + ((lane >> 4) * 8 + (lane & 7)) * 16);
-  const uint32_t rofs = (uint32_t)((g * 8 + min(c16 & 7, p.M - 1)) * 16);
-  const bool low = c16 < 8;
+  const uint32_t wofs = ximg_store_ofs(lane), rofs = ximg_read_ofs(lane, p.M);
+  const bool low = (lane & 15) < 8;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int u = 0; u < F32W_UB; ++u) {
+  for (int u = 0; u < F32_LB; ++u) {
     const int kb = u * F32_NW + wave;
     const bool valid = kb < nkb;                    // (wave-uniform)
     // a slot past the end reads the wave's own first image block (inside the allocation, written by no other wave)
-    unsigned char* blk = ximg + (valid ? kb : wave) * 1024;
+    unsigned char* blk = ximg + (valid ? kb : wave) * XIMG_BLOCK;
     if (valid) *(u32x4*)(blk + wofs) = xs[u];
     __builtin_amdgcn_wave_barrier();
-    const u32x4 r0 = *(const u32x4*)(blk + rofs), r1 = *(const u32x4*)(blk + rofs + 512);
-    const uint32_t xd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-    uint32_t a0[4], a1[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) split3(f32x2{__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])}, low, a0[j], a1[j]);
+    u32x4 xr[2], a[2];
+    ximg_read(blk, rofs, xr);
+    float none = 0.f;
+    split8(xr, xr, false, low, a, false, none);
     if (valid) {
-      acc = mfma16<bf16>(u32x4{a0[0], a0[1], a0[2], a0[3]}, ring[u], acc);
-      acc = mfma16<bf16>(u32x4{a1[0], a1[1], a1[2], a1[3]}, ring[u], acc);
+      acc = mfma16<bf16>(a[0], ring[u], acc);
+      acc = mfma16<bf16>(a[1], ring[u], acc);
     }
   }
 
-  // ---- cross-wave reduction and epilogue: F32Body::pass<1>, tile 0
-  f32x4 v = acc;
-  v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
-  if (lane < 32) *(f32x4*)&red[(wave * 32 + lane) * 4] = v;
+  publish(red, 0, wave, lane, acc);
   __syncthreads();
   if (ep) {
-    const int el = (em >> 2) * 16 + ecc, r = em & 3;
-    float y0 = 0.f, y1 = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < F32_NW; ++ww) {
-      y0 += red[(ww * 32 + el) * 4 + r];
-      y1 += red[(ww * 32 + el + 8) * 4 + r];
-    }
+    float y0, y1;
+    sum_waves(red, 0, em, ecc, y0, y1);
     if (p.epi == EPI_RESID) {
       p.resid[eo] = h0 + y0; p.resid[eo + 8] = h1 + y1;
     } else {                                        // EPI_STORE and EPI_STORE_F32 coincide
@@ -445,46 +510,29 @@ __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_whole_kernel(F32Params p
 }
 
 // ---- The resident form: the stream of F32Body with x and the norm weights kept in LDS for the whole launch -----------------
-// The chunked kernel above fetches a chunk's x from L2 while the weights stream, and a wave's loads return in issue order:
-// the wait for the next chunk's x (vmcnt(8) where the steady state is vmcnt(D - 1)) is also a wait for all but one or two
-// of the wave's weight loads.  All eight waves of all workgroups reach their chunk ends together, so the chip's request
-// queue runs dry once per chunk.  Here the head stages x ONCE -- wave v exactly the k-blocks v, v + 8, ... that it multiplies,
-// through the float32 fragment-order image of gemv_f32_whole_kernel (1 KiB per k-block; x crosses lanes, never waves: no
-// workgroup barrier between x and the MFMAs) -- and, under PRO_NORM, the norm weights of the same blocks (128 bytes per
-// k-block, read back as a broadcast).  From then on the only vector-memory loads of the stream are the non-temporal weight
-// loads, and every wait in it is the counted vmcnt(D - 1) or higher.  A chunk's four fragment pairs are rebuilt from the
-// images (four ds_read_b128 and the split of split_x per block) where split_x stands in the chunked kernel; the reads are
-// issued in front of the position's MFMAs, which cover their latency.
-//
-// Same tile deal, passes, block ownership, split3 on x * w_norm, MFMAs in the same order, the same fmaf chain for the squares
-// added in the same (chunk, block) order, the same cross-wave sums and epilogues: every output is bit-identical to
-// gemv_f32_kernel / gemv_f32_gu8_kernel on the same call.
-//
-// Head (first pass), straight-line, nothing under a branch, neither a load nor a staging store: the norm weights (two
-// 16-byte loads per lane cover the wave's 16 blocks; without PRO_NORM they read x and are ignored), x0 w0 x1 w1 x2 w2 x3 w3,
-// x4 .. x15, then w4 .. w(D-1); slots past the end re-load block 0.  The first D weight loads with ALL the remaining x behind
-// them (the first order built) make the wait for the last x load a wait for every weight load of the head: each wave, and
-// so the chip, started the stream with an empty ring, and that form gained 0.014 / 0.020 ms per step in two A/B jobs where
-// this one gains 0.059.  In this order the staging waits for w0 .. w3 only (vmcnt(D - 4)).  The first pass is
-// an instantiation of its own in front of the loop over the later ones (see pass()).  Later passes never stage again: x
-// survives in LDS.
+// The head stages x ONCE -- wave v exactly the k-blocks v, v + 8, ... that it multiplies, through the x image above -- and,
+// under PRO_NORM, the norm weights of the same blocks into an image of their own (128 bytes per k-block, read back as a
+// broadcast).  From then on the only vector-memory loads of the stream are the weight loads, and every wait in it is the
+// counted vmcnt(D - 1) or higher.  A chunk's four fragment pairs are rebuilt from the images (four ds_read_b128 and the
+// split per block) where split_x stands in the chunked form; the reads are issued in front of the position's MFMAs, which
+// cover their latency.  Later passes never stage again.  Same tile deal, passes, block ownership, step(), split8 in the same
+// (chunk, block) order, finish(): the outputs are those of gemv_f32_kernel / gemv_f32_gu8_kernel.
 //
 // LDS (dynamic, one workgroup per CU): [row sums 256 B][reduction 8 KiB][x image K / 32 KiB][norm image K / 256 KiB], the
 // images at least 8 blocks (one per wave, so that ignored slots stay inside them), and below K = 4096 one KiB per wave that
 // takes the staging stores of blocks past the end: 152.25 KiB at K = 4096.  The 32-KiB reduction buffer of the chunked
-// kernel does not fit next to the images, so a full pass (8 tiles) with another pass behind it reduces 2 tiles per round
+// form does not fit next to the images, so a full pass (8 tiles) with another pass behind it reduces 2 tiles per round
 // through the 8-KiB buffer.  After the workgroup's LAST pass -- every pass of fewer than 8 tiles is one (run(): nt < 8 only
 // when nothing is left), and so is a full pass with nothing behind it -- nobody reads the images: behind a barrier its
-// reduction takes 4 KiB per tile from the start of the buffer on into the x image, in one round as in the chunked kernel
+// reduction takes 4 KiB per tile from the start of the buffer on into the x image, in one round as in the chunked form
 // (the allocation is at least 32 KiB + 256 B).  Either way the sums are taken wave 0 .. 7 in order.
-constexpr int F32R_UB = 16;                      // k-blocks per wave: K <= 8 * 16 * 32
 constexpr int F32R_SQ = F32_NW * 8 * 4;          // bytes of the waves' row sums, at the start
 constexpr int F32R_RED = 2 * F32_NW * 32 * 16;   // bytes of the 2-tile reduction buffer
 constexpr size_t F32R_LDS_MAX = 160 * 1024;      // gfx950: LDS per CU
 constexpr int f32_res_blocks(int K) { return K / 32 > F32_NW ? K / 32 : F32_NW; }
-constexpr size_t f32_res_dump_bytes(int K) { return K / 32 < F32_NW * F32R_UB ? F32_NW * 1024 : 0; }   // (see stage())
+constexpr size_t f32_res_dump_bytes(int K) { return K / 32 < F32_NW * F32_LB ? F32_NW * 1024 : 0; }   // (see stage())
 constexpr size_t f32_res_lds_bytes(int K) {
-  const size_t img = (size_t)F32R_RED + (size_t)f32_res_blocks(K) * (1024 + 128) + f32_res_dump_bytes(K);
+  const size_t img = (size_t)F32R_RED + (size_t)f32_res_blocks(K) * (XIMG_BLOCK + 128) + f32_res_dump_bytes(K);
   return F32R_SQ + (img > 32 * 1024 ? img : 32 * 1024);
 }
 
@@ -500,27 +548,23 @@ struct F32Resident : F32Body<GU8> {
   __device__ __forceinline__ F32Resident(const F32Params& pp, unsigned char* lds)
       : B(pp, (float*)(lds + F32R_SQ), (float*)lds) {
     ximg = lds + F32R_SQ + F32R_RED;
-    nimg = ximg + (size_t)f32_res_blocks(p.K) * 1024;
-    rofs = (uint32_t)((g * 8 + min(c16 & 7, p.M - 1)) * 16);
+    nimg = ximg + (size_t)f32_res_blocks(p.K) * XIMG_BLOCK;
+    rofs = ximg_read_ofs(lane, p.M);
   }
 
   // The head of the first pass: the norm weights, the first four weight loads with the x of their blocks in front of each,
   // the rest of x, the rest of the first D weight loads; then x and the norm weights into their images.  STRAIGHT-LINE.
-  // A wave's loads return in issue order, so the wait for the last x load is a wait for w0 .. w3 only: the other D - 4
-  // weight loads stay in flight across the staging, and the stream does not start with an empty ring.
+  // (Two 16-byte loads per lane cover the norm weights of the wave's 16 blocks; without PRO_NORM they read x and are ignored.)
+  // A wave's loads return in issue order, so the wait for the last x load is a wait for w0 .. w3 only (vmcnt(D - 4)): the
+  // other D - 4 weight loads stay in flight across the staging.  The first D weight loads with ALL the remaining x behind
+  // them (the first order built) made it a wait for every weight load of the head: each wave, and so the chip, started the
+  // stream with an empty ring, and that form gained 0.014 / 0.020 ms per step in two A/B jobs where this one gains 0.059
+  // (DESIGN §5).
   template <int D>
   __device__ __forceinline__ void stage(int i0) {
-    u32x4 xs[F32R_UB], ns[2];
-    const uint32_t xlane = ((uint32_t)min(lane & 7, p.M - 1) * (uint32_t)p.ldx + 4u * (lane >> 3)) * 4u;   // (<= 8 rows: far below 4 GiB)
-    auto load_xs = [&](int u) {
-      const int kb = u * F32_NW + wave, b = kb < nkb ? kb : 0;
-      const gptr xb = uniform_ptr(p.x, (size_t)b * 128);
-      xs[u] = *(gptr16)(xb + xlane);
-    };
-    auto issue_w = [&](int s) {
-      const int kb = (s % F32_UB) * F32_NW + wave;
-      B::issue(s, i0 + s / F32_UB, kb, kb < nkb);
-    };
+    u32x4 xs[F32_LB], ns[2];
+    const uint32_t xlane = ximg_fetch_ofs(lane, p.M, p.ldx);
+    auto load_xs = [&](int u) { xs[u] = ximg_fetch(p.x, xlane, u * F32_NW + wave, nkb); };
     // lane l: 32 bytes (piece l & 3) of the norm weights of the wave's block l >> 2
     const int nkbl = (lane >> 2) * F32_NW + wave;
     const bool nvalid = nkbl < nkb;
@@ -533,25 +577,25 @@ struct F32Resident : F32Body<GU8> {
     for (int s = 0; s < F32_UB; ++s) {            // (D >= 4 for every pass size)
       load_xs(s);
       __builtin_amdgcn_sched_barrier(0);
-      issue_w(s);
+      B::issue_first(s, i0);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int u = F32_UB; u < F32R_UB; ++u) load_xs(u);
+    for (int u = F32_UB; u < F32_LB; ++u) load_xs(u);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int s = F32_UB; s < D; ++s) issue_w(s);
+    for (int s = F32_UB; s < D; ++s) B::issue_first(s, i0);
     __builtin_amdgcn_sched_barrier(0);
     // No store under a branch either: at the join behind a skipped store the compiler's wait for the skipped load's registers
     // came out as vmcnt(1) / vmcnt(0) in front of the first image reads -- the drain this form exists to remove.  A block past
     // the end (and the norm weights of one) goes to a KiB of the wave's own behind the images, which nobody reads; it is there
     // whenever a wave can have such a block (K < 4096).
-    const uint32_t wofs = (uint32_t)(((lane >> 3) & 1) * 512 + ((lane >> 4) * 8 + (lane & 7)) * 16);
+    const uint32_t wofs = ximg_store_ofs(lane);
     unsigned char* dump = nimg + f32_res_blocks(p.K) * 128 + wave * 1024;
 #pragma unroll
-    for (int u = 0; u < F32R_UB; ++u) {
+    for (int u = 0; u < F32_LB; ++u) {
       const int kb = u * F32_NW + wave;
-      *(u32x4*)((kb < nkb ? ximg + kb * 1024 : dump) + wofs) = xs[u];
+      *(u32x4*)((kb < nkb ? ximg + kb * XIMG_BLOCK : dump) + wofs) = xs[u];
     }
     unsigned char* d = nvalid ? nimg + nkbl * 128 + (lane & 3) * 32 : dump + (lane & 31) * 32;
     *(u32x4*)d = ns[0];
@@ -564,33 +608,9 @@ struct F32Resident : F32Body<GU8> {
   __device__ __forceinline__ void read_img(int c, int u, u32x4 (&xr)[2], u32x4 (&nr)[2]) {
     const int kb = c * F32_KB + u * F32_NW + wave;
     const int b = kb < nkb ? kb : wave;
-    const unsigned char* xb = ximg + b * 1024 + rofs;
     const unsigned char* nb = nimg + b * 128 + g * 32;
-    xr[0] = *(const u32x4*)xb; xr[1] = *(const u32x4*)(xb + 512);
+    ximg_read(ximg + b * XIMG_BLOCK, rofs, xr);
     nr[0] = *(const u32x4*)nb; nr[1] = *(const u32x4*)(nb + 16);
-  }
-
-  // F32Body::split_x on registers read from the images
-  __device__ __forceinline__ void split_img(int c, int u, bool count, const u32x4 (&xr)[2], const u32x4 (&nr)[2]) {
-    const bool low = c16 < 8;
-    const int kb = c * F32_KB + u * F32_NW + wave;
-    const uint32_t xd[8] = {xr[0].x, xr[0].y, xr[0].z, xr[0].w, xr[1].x, xr[1].y, xr[1].z, xr[1].w};
-    const uint32_t nd[8] = {nr[0].x, nr[0].y, nr[0].z, nr[0].w, nr[1].x, nr[1].y, nr[1].z, nr[1].w};
-    uint32_t a0[4], a1[4];
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 f = {__uint_as_float(xd[2 * j]), __uint_as_float(xd[2 * j + 1])};
-      if (norm) {
-        const f32x2 wf = {__uint_as_float(nd[2 * j]), __uint_as_float(nd[2 * j + 1])};
-        sq = fmaf(f.x, f.x, sq); sq = fmaf(f.y, f.y, sq);
-        f = f * wf;
-      }
-      split3(f, low, a0[j], a1[j]);
-    }
-    af[u][0] = u32x4{a0[0], a0[1], a0[2], a0[3]};
-    af[u][1] = u32x4{a1[0], a1[1], a1[2], a1[3]};
-    if (count && kb < nkb) ss += sq;
   }
 
   // the fragments of chunk 0
@@ -599,7 +619,7 @@ struct F32Resident : F32Body<GU8> {
     for (int u = 0; u < F32_UB; ++u) {
       u32x4 xr[2], nr[2];
       read_img(0, u, xr, nr);
-      split_img(0, u, count, xr, nr);
+      B::split(0, u, count, xr, nr);
     }
   }
 
@@ -619,10 +639,7 @@ struct F32Resident : F32Body<GU8> {
         rebuild0(true);
       } else {
 #pragma unroll
-        for (int s = 0; s < D; ++s) {
-          const int kb = (s % F32_UB) * F32_NW + wave;
-          B::issue(s, i0 + s / F32_UB, kb, kb < nkb);
-        }
+        for (int s = 0; s < D; ++s) B::issue_first(s, i0);
         rebuild0(false);
       }
     }
@@ -634,118 +651,44 @@ struct F32Resident : F32Body<GU8> {
       for (int t = 0; t < NT; ++t) {
 #pragma unroll
         for (int u = 0; u < F32_UB; ++u) {
-          const int pos = t * F32_UB + u, slot = pos % D;
+          const int pos = t * F32_UB + u;
           // Block u's fragments are last used at position L - 4 + u and replaced right there by the next chunk's, read from
           // the images in front of the MFMAs.  In the last chunk of a pass that does not roll, chunk 0's are rebuilt, unused
           // (straight-line filler as in F32Body::pass; `count` is false).
           u32x4 xr[2], nr[2];
           if (pos >= L - F32_UB) read_img(nc, pos - (L - F32_UB), xr, nr);
-          if (c * F32_KB + u * F32_NW + wave < nkb) {       // (wave-uniform; no load inside)
-            acc[t] = mfma16<bf16>(af[u][0], ring[slot], acc[t]);
-            acc[t] = mfma16<bf16>(af[u][1], ring[slot], acc[t]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          // the same registers are re-loaded with the load D positions ahead in this workgroup's sequence
-          const int q = pos + D;
-          if (q < L) {
-            const int kb = c * F32_KB + (q % F32_UB) * F32_NW + wave;
-            B::issue(slot, i0 + q / F32_UB, kb, kb < nkb);
-          } else {
-            const int q2 = q - L;
-            const int kb = nc * F32_KB + (q2 % F32_UB) * F32_NW + wave;
-            B::issue(slot, (last ? i0 + NT : i0) + q2 / F32_UB, kb, have_next && kb < nkb);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (pos >= L - F32_UB) split_img(nc, pos - (L - F32_UB), first && !last, xr, nr);
+          B::template step<NT>(i0, c, nc, t, u, last, have_next);
+          if (pos >= L - F32_UB) B::split(nc, pos - (L - F32_UB), first && !last, xr, nr);
         }
       }
     }
 
     // ---- cross-wave reduction and epilogue (see the notes above): the workgroup's last pass in one round over the images
     if constexpr (NT < F32_TP) {
-      finish<NT, NT, true>(i0, first);
+      B::template finish<NT, NT, true>(i0, first);
     } else {
-      if (final) finish<NT, NT, true>(i0, first);
-      else finish<NT, 2, false>(i0, first);
-    }
-  }
-
-  // the cross-wave reduction and epilogue of F32Body::pass, TR tiles per round; OVER: `red` runs on into the images
-  template <int NT, int TR, bool OVER>
-  __device__ __forceinline__ void finish(int i0, bool first) {
-    if (first && norm) {
-      float v = ss;                               // lanes c16 < 8: row c16, the four k-groups of the wave's blocks
-      v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-      if (lane < 8) sq_sh[wave * 8 + lane] = v;
-    }
-    // thread (t, m, c): columns c and c + 8 of row m of tile t of the round
-    const int t = tid >> 6, m = (tid >> 3) & 7, cc = tid & 7;
-#pragma unroll
-    for (int r0 = 0; r0 < NT; r0 += TR) {
-      if (OVER || r0 > 0) __syncthreads();        // the last pass: every wave is done with the images; a later round: with `red`
-#pragma unroll
-      for (int tl = 0; tl < TR; ++tl) {
-        f32x4 v = acc[r0 + tl];
-        v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32); v.z += __shfl_xor(v.z, 32); v.w += __shfl_xor(v.w, 32);
-        if (lane < 32) *(f32x4*)&red[((tl * F32_NW + wave) * 32 + lane) * 4] = v;
-      }
-      __syncthreads();
-      if (r0 == 0 && first && norm) {
-        float tot = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < F32_NW; ++ww) tot += sq_sh[ww * 8 + m];
-        rs = 1.0f / sqrtf(tot / (float)p.K + p.eps);
-      }
-      if (t < TR && m < p.M) {
-        const int el = (m >> 2) * 16 + cc, r = m & 3;
-        float y0 = 0.f, y1 = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < F32_NW; ++ww) {
-          y0 += red[((t * F32_NW + ww) * 32 + el) * 4 + r];
-          y1 += red[((t * F32_NW + ww) * 32 + el + 8) * 4 + r];
-        }
-        y0 *= rs; y1 *= rs;
-        const int tile = w + (i0 + r0 + t) * G;     // (t < TR, r0 + t < NT: one of this workgroup's tiles)
-        if constexpr (GU8) {
-          // row-interleaved gate|up tile: columns 0..7 are gate rows 8 tile .. + 7, columns 8..15 the matching up rows
-          const float sig = 1.0f / (1.0f + expf(-y0));
-          const float sl = y0 * sig;
-          p.out[(size_t)m * p.ldo + tile * 8 + cc] = sl * y1;
-        } else {
-          const size_t o = (size_t)m * p.ldo + tile * 16 + cc;
-          if (p.epi == EPI_RESID) {
-            const float h0 = p.resid[o], h1 = p.resid[o + 8];
-            p.resid[o] = h0 + y0; p.resid[o + 8] = h1 + y1;
-          } else {                                  // EPI_STORE and EPI_STORE_F32 coincide
-            p.out[o] = y0; p.out[o + 8] = y1;
-          }
-        }
-      }
+      if (final) B::template finish<NT, NT, true>(i0, first);
+      else B::template finish<NT, 2, false>(i0, first);
     }
   }
 
   template <bool FIRST>
   __device__ __forceinline__ void pass_of(int nt, int i0, bool preloaded, bool roll, bool final) {
-    switch (nt) {
-      case 8: pass<8, FIRST>(i0, preloaded, roll, final); break;
-      case 7: pass<7, FIRST>(i0, false, false, true); break;
-      case 6: pass<6, FIRST>(i0, false, false, true); break;
-      case 5: pass<5, FIRST>(i0, false, false, true); break;
-      case 4: pass<4, FIRST>(i0, false, false, true); break;
-      case 3: pass<3, FIRST>(i0, false, false, true); break;
-      case 2: pass<2, FIRST>(i0, false, false, true); break;
-      default: pass<1, FIRST>(i0, false, false, true); break;
-    }
+    // (only a full pass is ever preloaded or rolls, and a shorter one is the workgroup's last)
+    with_pass_size(nt, [&](auto n) __attribute__((always_inline)) {
+      constexpr int NT = decltype(n)::value;
+      pass<NT, FIRST>(i0, NT == F32_TP && preloaded, NT == F32_TP && roll, NT < F32_TP || final);
+    });
   }
 
   __device__ __forceinline__ void run() {
     if (ntiles <= 0) return;
-    int done = min(F32_TP, ntiles);
-    bool pre = done == F32_TP && ntiles - done >= F32_TP;
+    bool pre;
+    int done = B::pass_size(0, pre);
     pass_of<true>(done, 0, false, pre, done == ntiles);
     while (done < ntiles) {
-      const int nt = min(F32_TP, ntiles - done);
-      const bool roll = nt == F32_TP && ntiles - done - nt >= F32_TP;
+      bool roll;
+      const int nt = B::pass_size(done, roll);
       __syncthreads();                            // `red` is reused
       pass_of<false>(nt, done, pre, roll, done + nt == ntiles);
       pre = roll;
@@ -767,6 +710,32 @@ __global__ __launch_bounds__(F32_NW * 64) void gemv_f32_resident_gu8_kernel(F32P
   b.run();
 }
 
+// ---- host side -------------------------------------------------------------------------------------------------------------
+// what every launcher of this file refuses
+int f32_check(const char* name, bool supported, const GemvCall& c) {
+  if (!supported) return fail(MI_ERR_UNSUPPORTED, std::string(name) + ": call not supported by this kernel");
+  if (c.epi == EPI_RESID ? c.resid == nullptr : c.out == nullptr) return fail(MI_ERR_INVALID, std::string(name) + ": output buffer missing");
+  return MI_OK;
+}
+
+F32Params make_params(const LinearW& W, const GemvCall& c) {
+  F32Params p{};
+  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
+  p.pro = c.pro; p.norm_w = (const float*)c.norm_w; p.eps = c.eps;
+  p.w = W.w; p.N = W.N; p.K = W.K;
+  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
+  return p;
+}
+
+int f32_launch(void (*kern)(F32Params), int nwg, size_t lds, const LinearW& W, const GemvCall& c, hipStream_t st) {
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(F32_NW * 64), lds, st, make_params(W, c));
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// one workgroup per CU; tiles are dealt in-kernel
+int f32_grid(const LinearW& W) { return std::min(W.N / 16, gemv_cu_count()); }
+
 }  // namespace
 
 // float32 activations without logical rounding, <= 8 rows, dense bf16 tile-major weights, no LoRA, no [hi | lo] walk;
@@ -784,18 +753,8 @@ bool gemv_f32_supported(const LinearW& W, const GemvCall& c) {
 }
 
 int launch_gemv_f32(const LinearW& W, const GemvCall& c, hipStream_t st) {
-  if (!gemv_f32_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "gemv_f32: call not supported by this kernel");
-  F32Params p{};
-  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
-  p.pro = c.pro; p.norm_w = (const float*)c.norm_w; p.eps = c.eps;
-  p.w = W.w; p.N = W.N; p.K = W.K;
-  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
-  if (c.epi == EPI_RESID ? p.resid == nullptr : p.out == nullptr) return fail(MI_ERR_INVALID, "gemv_f32: output buffer missing");
-  const int nwg = std::min(W.N / 16, gemv_cu_count());     // one workgroup per CU; tiles are dealt in-kernel
-  if (c.epi == EPI_SWIGLU_GU8) hipLaunchKernelGGL(gemv_f32_gu8_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
-  else hipLaunchKernelGGL(gemv_f32_kernel, dim3(nwg), dim3(F32_NW * 64), 0, st, p);
-  MI_HIP(hipGetLastError());
-  return MI_OK;
+  MI_TRY(f32_check("gemv_f32", gemv_f32_supported(W, c), c));
+  return f32_launch(c.epi == EPI_SWIGLU_GU8 ? gemv_f32_gu8_kernel : gemv_f32_kernel, f32_grid(W), 0, W, c, st);
 }
 
 // The whole-K form: what gemv_f32_supported takes, without a prologue, K <= 4096 (16 k-blocks per wave) and at most one
@@ -804,64 +763,32 @@ bool gemv_f32_whole_supported(const LinearW& W, const GemvCall& c) {
   if (!gemv_f32_supported(W, c)) return false;
   if (c.pro != PRO_NONE) return false;
   if (c.epi != EPI_STORE && c.epi != EPI_STORE_F32 && c.epi != EPI_RESID) return false;
-  if (W.K > F32_NW * F32W_UB * 32) return false;
+  if (W.K > F32_NW * F32_LB * 32) return false;
   return W.N / 16 <= gemv_cu_count();
 }
 
 int launch_gemv_f32_whole(const LinearW& W, const GemvCall& c, hipStream_t st) {
-  if (!gemv_f32_whole_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "gemv_f32_whole: call not supported by this kernel");
-  F32Params p{};
-  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
-  p.pro = PRO_NONE; p.norm_w = nullptr; p.eps = 0.f;
-  p.w = W.w; p.N = W.N; p.K = W.K;
-  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
-  if (c.epi == EPI_RESID ? p.resid == nullptr : p.out == nullptr) return fail(MI_ERR_INVALID, "gemv_f32_whole: output buffer missing");
-  // the opt-in for LDS above 64 KiB belongs to the kernel object of the CURRENT device: one flag per device, set after the call
-  static std::atomic<bool> attr_done[64];
-  int dev = 0;
-  MI_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
-    MI_HIP(hipFuncSetAttribute((const void*)gemv_f32_whole_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)f32_whole_lds_bytes(F32_NW * F32W_UB * 32)));
-    if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(gemv_f32_whole_kernel, dim3(W.N / 16), dim3(F32_NW * 64), f32_whole_lds_bytes(W.K), st, p);
-  MI_HIP(hipGetLastError());
-  return MI_OK;
+  MI_TRY(f32_check("gemv_f32_whole", gemv_f32_whole_supported(W, c), c));
+  static std::atomic<bool> opted[64];
+  MI_TRY(lds_opt_in(opted, {(const void*)gemv_f32_whole_kernel}, (int)f32_whole_lds_bytes(F32_NW * F32_LB * 32)));
+  return f32_launch(gemv_f32_whole_kernel, W.N / 16, f32_whole_lds_bytes(W.K), W, c, st);
 }
 
 // The resident form: what gemv_f32_supported takes, with at most 16 k-blocks per wave (K <= 4096: the head holds a wave's
 // raw x in registers at once) and the images and the reduction buffer inside a CU's LDS
 bool gemv_f32_resident_supported(const LinearW& W, const GemvCall& c) {
   if (!gemv_f32_supported(W, c)) return false;
-  if (W.K > F32_NW * F32R_UB * 32) return false;
+  if (W.K > F32_NW * F32_LB * 32) return false;
   return f32_res_lds_bytes(W.K) <= F32R_LDS_MAX;
 }
 
 int launch_gemv_f32_resident(const LinearW& W, const GemvCall& c, hipStream_t st) {
-  if (!gemv_f32_resident_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "gemv_f32_resident: call not supported by this kernel");
-  F32Params p{};
-  p.x = (const float*)c.x; p.ldx = c.ldx; p.M = c.M;
-  p.pro = c.pro; p.norm_w = (const float*)c.norm_w; p.eps = c.eps;
-  p.w = W.w; p.N = W.N; p.K = W.K;
-  p.epi = c.epi; p.out = (float*)c.out; p.ldo = c.ldo; p.resid = (float*)c.resid;
-  if (c.epi == EPI_RESID ? p.resid == nullptr : p.out == nullptr) return fail(MI_ERR_INVALID, "gemv_f32_resident: output buffer missing");
-  // the opt-in for LDS above 64 KiB belongs to the kernel objects of the CURRENT device: one flag per device, set after the calls
-  static std::atomic<bool> attr_done[64];
-  int dev = 0;
-  MI_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
-    const int most = (int)f32_res_lds_bytes(F32_NW * F32R_UB * 32);
-    MI_HIP(hipFuncSetAttribute((const void*)gemv_f32_resident_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    MI_HIP(hipFuncSetAttribute((const void*)gemv_f32_resident_gu8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
-  }
-  const int nwg = std::min(W.N / 16, gemv_cu_count());     // one workgroup per CU; tiles are dealt in-kernel
-  const size_t lds = f32_res_lds_bytes(W.K);
-  if (c.epi == EPI_SWIGLU_GU8) hipLaunchKernelGGL(gemv_f32_resident_gu8_kernel, dim3(nwg), dim3(F32_NW * 64), lds, st, p);
-  else hipLaunchKernelGGL(gemv_f32_resident_kernel, dim3(nwg), dim3(F32_NW * 64), lds, st, p);
-  MI_HIP(hipGetLastError());
-  return MI_OK;
+  MI_TRY(f32_check("gemv_f32_resident", gemv_f32_resident_supported(W, c), c));
+  static std::atomic<bool> opted[64];
+  MI_TRY(lds_opt_in(opted, {(const void*)gemv_f32_resident_kernel, (const void*)gemv_f32_resident_gu8_kernel},
+                    (int)f32_res_lds_bytes(F32_NW * F32_LB * 32)));
+  return f32_launch(c.epi == EPI_SWIGLU_GU8 ? gemv_f32_resident_gu8_kernel : gemv_f32_resident_kernel, f32_grid(W),
+                    f32_res_lds_bytes(W.K), W, c, st);
 }
 
 }  // namespace mi

@@ -26,6 +26,57 @@ int finish() {
   return MI_OK;
 }
 
+// One launch; with iters >= 1 and avg_ms, `iters` more behind that warm one, timed by events into *avg_ms.  Returns the
+// first failing launch's code, else finish()'s.
+template <class Launch>
+int run_timed(Launch launch, int iters, float* avg_ms) {
+  int rc = launch();
+  if (rc == MI_OK && iters >= 1 && avg_ms) {
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch();
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  const int rc2 = finish();
+  return rc != MI_OK ? rc : rc2;
+}
+
+// The benchmark entry points' form: a warm launch, then `iters` timed ones; any failing call returns at once, its code unchanged.
+template <class Launch>
+int run_timed_strict(Launch launch, int iters, float* avg_ms) {
+  hipEvent_t e0, e1;
+  MI_HIP(hipEventCreate(&e0)); MI_HIP(hipEventCreate(&e1));
+  MI_TRY(launch());
+  MI_HIP(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < iters; ++i) MI_TRY(launch());
+  MI_HIP(hipEventRecord(e1, nullptr));
+  MI_HIP(hipEventSynchronize(e1));
+  float ms = 0.f;
+  MI_HIP(hipEventElapsedTime(&ms, e0, e1));
+  if (avg_ms) *avg_ms = ms / iters;
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  return finish();
+}
+
+struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } };
+
+// MI_EPI_SWIGLU on a gate|up matrix of 2 x pair_offset rows: its row-interleaved copy is made here, as mi_engine_finalize
+// does, into gu8 (the caller frees it), and W and c are turned to it.  `taken`: the kernel takes the call on that copy.
+int gate_up_interleaved(LinearW& W, GemvCall& c, void*& gu8, bool taken, const char* refusal) {
+  if (c.epi != EPI_SWIGLU) return MI_OK;
+  if (!taken) return fail(MI_ERR_UNSUPPORTED, refusal);
+  MI_HIP(hipMalloc(&gu8, (size_t)W.N * W.K * sizeof(uint16_t)));
+  MI_TRY(launch_gate_up_interleave(W, c.pair_offset, gu8, nullptr));
+  W.w = gu8; c.epi = EPI_SWIGLU_GU8;
+  return MI_OK;
+}
+
 LinearW to_linear(const mi_op_linear* w) {
   LinearW W;
   W.wk = w->wk; W.w = w->w; W.scales = w->scales; W.biases = w->biases; W.N = w->N; W.K = w->K;
@@ -67,18 +118,7 @@ int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters,
   MI_TRY(ready());
   const LinearW W = to_linear(w);
   const GemvCall c = to_call(a);
-  hipEvent_t e0, e1;
-  MI_HIP(hipEventCreate(&e0)); MI_HIP(hipEventCreate(&e1));
-  MI_TRY(launch_gemv(W, c, nullptr));                   // warm-up
-  MI_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) MI_TRY(launch_gemv(W, c, nullptr));
-  MI_HIP(hipEventRecord(e1, nullptr));
-  MI_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  MI_HIP(hipEventElapsedTime(&ms, e0, e1));
-  *avg_ms = ms / iters;
-  hipEventDestroy(e0); hipEventDestroy(e1);
-  return finish();
+  return run_timed_strict([&] { return launch_gemv(W, c, nullptr); }, iters, avg_ms);
 }
 
 // gemv_f32.hip on its own: float32 activations (a->rnd = MI_RND_NONE), a->M in 1..8, dense bf16 tile-major weights; plain,
@@ -91,29 +131,10 @@ int mi_op_gemv_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, f
   LinearW W = to_linear(w);
   GemvCall c = to_call(a);
   void* gu8 = nullptr;
-  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } guard{gu8};
-  if (c.epi == EPI_SWIGLU) {
-    if (W.wk != WK_BF16 || W.layout != 1) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32: call not supported by this kernel");
-    MI_HIP(hipMalloc(&gu8, (size_t)W.N * W.K * sizeof(uint16_t)));
-    MI_TRY(launch_gate_up_interleave(W, c.pair_offset, gu8, nullptr));
-    W.w = gu8; c.epi = EPI_SWIGLU_GU8;
-  }
+  FreeGuard guard{gu8};
+  MI_TRY(gate_up_interleaved(W, c, gu8, W.wk == WK_BF16 && W.layout == 1, "mi_op_gemv_f32: call not supported by this kernel"));
   if (!gemv_f32_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32: call not supported by this kernel");
-  int rc = launch_gemv_f32(W, c, nullptr);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32(W, c, nullptr);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
-  return rc != MI_OK ? rc : rc2;
+  return run_timed([&] { return launch_gemv_f32(W, c, nullptr); }, iters, avg_ms);
 }
 
 // the whole-K form of gemv_f32.hip on its own (one tile per workgroup: N / 16 <= CUs, K <= 4096, a->pro = MI_PRO_NONE; plain,
@@ -124,21 +145,7 @@ int mi_op_gemv_f32_whole(const mi_op_linear* w, const mi_op_gemv_args* a, int it
   const LinearW W = to_linear(w);
   const GemvCall c = to_call(a);
   if (!gemv_f32_whole_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_whole: call not supported by this kernel");
-  int rc = launch_gemv_f32_whole(W, c, nullptr);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32_whole(W, c, nullptr);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
-  return rc != MI_OK ? rc : rc2;
+  return run_timed([&] { return launch_gemv_f32_whole(W, c, nullptr); }, iters, avg_ms);
 }
 
 // the resident form of gemv_f32.hip on its own (x and the norm weights kept in LDS: K <= 4096): mi_op_gemv_f32's calls,
@@ -149,30 +156,11 @@ int mi_op_gemv_f32_resident(const mi_op_linear* w, const mi_op_gemv_args* a, int
   LinearW W = to_linear(w);
   GemvCall c = to_call(a);
   void* gu8 = nullptr;
-  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } guard{gu8};
-  if (c.epi == EPI_SWIGLU) {
-    GemvCall probe = c; probe.epi = EPI_SWIGLU_GU8;
-    if (!gemv_f32_resident_supported(W, probe)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_resident: call not supported by this kernel");
-    MI_HIP(hipMalloc(&gu8, (size_t)W.N * W.K * sizeof(uint16_t)));
-    MI_TRY(launch_gate_up_interleave(W, c.pair_offset, gu8, nullptr));
-    W.w = gu8; c.epi = EPI_SWIGLU_GU8;
-  }
+  FreeGuard guard{gu8};
+  GemvCall probe = c; probe.epi = EPI_SWIGLU_GU8;
+  MI_TRY(gate_up_interleaved(W, c, gu8, gemv_f32_resident_supported(W, probe), "mi_op_gemv_f32_resident: call not supported by this kernel"));
   if (!gemv_f32_resident_supported(W, c)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemv_f32_resident: call not supported by this kernel");
-  int rc = launch_gemv_f32_resident(W, c, nullptr);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemv_f32_resident(W, c, nullptr);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
-  return rc != MI_OK ? rc : rc2;
+  return run_timed([&] { return launch_gemv_f32_resident(W, c, nullptr); }, iters, avg_ms);
 }
 
 // gemm_skinny.hip on its own: a->M in 9..128 (int4 / int8: 1..128), a->pro must be MI_PRO_NONE; ksplit 0 = the cost model's choice
@@ -198,22 +186,9 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
   MI_HIP(hipMemset(ctr, 0, (size_t)groups * sizeof(unsigned)));
   if (ksplit_used) *ksplit_used = ksplit > 0 ? ksplit : gemm_skinny_ksplit(W, c, (size_t)c.M);
   if (ksplit < 0) ksplit = 0;
-  int rc = launch_gemm_skinny(W, c, (size_t)c.M, nullptr, ws, ctr, ksplit);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_skinny(W, c, (size_t)c.M, nullptr, ws, ctr, ksplit);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
+  const int rc = run_timed([&] { return launch_gemm_skinny(W, c, (size_t)c.M, nullptr, ws, ctr, ksplit); }, iters, avg_ms);
   hipFree(ws); hipFree(ctr);
-  return rc != MI_OK ? rc : rc2;
+  return rc;
 }
 
 // gemm_prefill.hip on its own, 16-bit activations: dense 16-bit weights, or int4 / int8 (group 64) weights through the [hi | lo]
@@ -228,25 +203,11 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || (wk_is_quant(W.wk) && !gemm_prefill_supported(W, c, (size_t)c.M)))
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int4 or int8 (group 64) weights, 16-bit activations, no prologue");
   void* ws = nullptr; void* scratch = nullptr; size_t cap = 0;
-  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } g_ws{ws}, g_scratch{scratch};
+  FreeGuard g_ws{ws}, g_scratch{scratch};
   if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, W.K)));
   // K-split workspace as the engine holds it (float32 partial tiles; prompts below 4096 rows)
   if (c.M < 4096) { cap = (size_t)128 << 20; MI_HIP(hipMalloc(&ws, cap)); }
-  int rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
-  return rc != MI_OK ? rc : rc2;
+  return run_timed([&] { return launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap); }, iters, avg_ms);
 }
 
 // gemm_prefill.hip on float32 activations, as gemv_rows_on (engine.hip) runs it: (norm +) launch_split3_rows into a buffer of
@@ -262,7 +223,7 @@ int mi_op_gemm_prefill_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int 
   if (c.M < 1 || c.act != MI_F32 || (x_terms != 2 && x_terms != 3) || (x_terms == 2 && W.wk != WK_BF16))
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_f32: float32 activations in two (dense bf16 weights) or three terms");
   void* hilo = nullptr; void* xs = nullptr; void* scratch = nullptr; void* ws = nullptr; size_t cap = 0;
-  struct FreeGuard { void*& p; ~FreeGuard() { if (p) hipFree(p); } } g_hilo{hilo}, g_xs{xs}, g_scratch{scratch}, g_ws{ws};
+  FreeGuard g_hilo{hilo}, g_xs{xs}, g_scratch{scratch}, g_ws{ws};
   if (W.wk == WK_F16 && W.layout == 1) {
     MI_HIP(hipMalloc(&hilo, 2 * (size_t)W.N * W.K * sizeof(uint16_t)));
     MI_TRY(launch_f16_to_hilo(W, hilo, nullptr));
@@ -276,21 +237,7 @@ int mi_op_gemm_prefill_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int 
   c.x = xs; c.ldx = x_terms * KT; c.pro = PRO_NONE;
   if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, KT)));
   if (c.M < 4096) { cap = (size_t)128 << 20; MI_HIP(hipMalloc(&ws, cap)); }
-  int rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
-  if (rc == MI_OK && iters >= 1 && avg_ms) {
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && rc == MI_OK; ++i) rc = launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = ms / iters;
-    hipEventDestroy(e0); hipEventDestroy(e1);
-  }
-  const int rc2 = finish();
-  return rc != MI_OK ? rc : rc2;
+  return run_timed([&] { return launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap); }, iters, avg_ms);
 }
 
 // launch_split3_rows on its own: rows x K float32 (row stride ldx; RMS-normalised first when norm_w is not null) ->
@@ -365,18 +312,7 @@ static int run_attention_decode(const AttnDecodeCall& ac, int iters, float* avg_
     MI_TRY(launch_attention_decode(ac, nullptr));
     return finish();
   }
-  hipEvent_t e0, e1;
-  MI_HIP(hipEventCreate(&e0)); MI_HIP(hipEventCreate(&e1));
-  MI_TRY(launch_attention_decode(ac, nullptr));
-  MI_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) MI_TRY(launch_attention_decode(ac, nullptr));
-  MI_HIP(hipEventRecord(e1, nullptr));
-  MI_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  MI_HIP(hipEventElapsedTime(&ms, e0, e1));
-  if (avg_ms) *avg_ms = ms / iters;
-  hipEventDestroy(e0); hipEventDestroy(e1);
-  return finish();
+  return run_timed_strict([&] { return launch_attention_decode(ac, nullptr); }, iters, avg_ms);
 }
 
 int mi_op_attention_decode(const mi_op_attn_shape* s, const void* qkv, void* kcache, void* vcache,
