@@ -243,6 +243,24 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
                           const int32_t* tokens, const mi_sample_params* sp, int64_t* ticket);
 /* Forget the contents of one row (its length becomes 0); ordered behind the steps already enqueued. */
 int mi_kv_reset_row(mi_kv* kv, int row);
+/* logit_bias of the REQUEST that occupies cache row `row` (the reference's logit_bias dict, utils.py:346-349, is one per call;
+ * under continuous batching requests with different dicts share a step): n entries (ids[i], values[i]) replace the row's
+ * bias, n == 0 clears it (ids / values may then be NULL).  Set once at admission, it travels with the row -- nothing is
+ * uploaded per step: the device table [batch][MI_MAX_ROW_LOGIT_BIAS] belongs to the mi_kv (either form) and is allocated by
+ * the first call that sets a bias, never inside a step.  mi_kv_reset_row clears the row's bias, mi_kv_reset every row's;
+ * mi_kv_reserve and mi_kv_prefix_attach / _publish leave it alone.
+ * Every entry point that samples through the mi_kv applies it: sampled row b of mi_decode_sample / mi_step_enqueue is cache
+ * row b, sampled row i of mi_step_enqueue_rows is rows[i], wanted segment i of mi_step_enqueue_mixed is its segment's row.
+ * The row's logits become float32(l + v) for its entries, in place and AFTER the call-wide list of mi_sample_params has been
+ * added (an id in both lists gets both, in that order); the arg-max, the nucleus, top_k, min_p, the reported logprob, the
+ * top-k logprobs and prob_row0_out all see the biased row.  mi_forward and mi_score_tokens ignore it.  A step on a cache
+ * without a biased row is the step of a cache that never had one (the same kernel, bit-identical outputs).
+ * Ordered on the engine's stream like mi_kv_reset_row: behind every step already enqueued, ahead of every later one.  The
+ * arrays are copied into library-owned pinned staging before the call returns.
+ * MI_ERR_INVALID, naming the argument, with nothing changed and the previous bias still in force: row outside the cache;
+ * n < 0 or n > MI_MAX_ROW_LOGIT_BIAS; an id outside [0, vocab_size); an id that occurs twice; a value that is not finite. */
+#define MI_MAX_ROW_LOGIT_BIAS 1024   /* entries per row (OpenAI allows 300) */
+int mi_kv_set_row_logit_bias(mi_kv* kv, int row, const int32_t* ids, const float* values, int n);
 /* Block until `ticket` has finished; copy out its results (same meaning as mi_decode_sample). */
 int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logprob_out,
                  float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs);

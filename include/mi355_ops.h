@@ -16,6 +16,7 @@
  *   mi_op_attention   mx.fast.scaled_dot_product_attention + causal mask: llama.py:139-141; base.py:17-40
  *   mi_op_sample      sample closure + top_p_sampling: utils.py:345-364; sample_utils.py:3-38
  *   mi_op_sample_ex   the same kernel with top_k / min_p and per-row random streams (no counterpart in the reference)
+ *   mi_op_sample_rowbias  ... and a call-wide logit_bias list (utils.py:346-349) + the per-row table (no counterpart)
  */
 #ifndef MI355_OPS_H
 #define MI355_OPS_H
@@ -180,6 +181,22 @@ int mi_op_sample_ex(float* logits, int B, int V, float temperature, float top_p,
                     const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
                     const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
                     float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats);
+/* mi_op_sample_ex + both logit_bias inputs of the engine's sampler, all DEVICE arrays: the call-wide list (n_bias entries
+ * bias_ids / bias_values, added to every row: mi_sample_params.logit_bias_*) and then the per-row table of
+ * mi_kv_set_row_logit_bias (mi355_decode.h): sampled row b adds the row_bias_counts[t] entries (row_bias_ids[t][i],
+ * row_bias_values[t][i]) of table row t = row_map ? row_map[b] : b; the table has table_rows rows of `cap` entries each.
+ * logits change in place, logits[b][id] = float32(l + v), an id in both lists gets both, the call-wide one first.  Nothing is
+ * validated on the host beyond the shapes: an id outside [0, V), a t outside [0, table_rows) and entries past `cap` are skipped
+ * by the kernel; duplicate ids within ONE list are a data race (the engine refuses them).  row_bias_counts == NULL (then the
+ * other table arguments are ignored) and n_bias = 0: mi_op_sample_ex, bit for bit, on the same instantiation of the kernel. */
+int mi_op_sample_rowbias(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                         const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                         const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                         const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                         float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
+                         int n_bias, const int32_t* bias_ids, const float* bias_values,
+                         const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
+                         int table_rows, int cap, const int32_t* row_map);
 
 #ifdef __cplusplus
 }

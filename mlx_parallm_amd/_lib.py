@@ -18,6 +18,7 @@ MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
 MI_KV_MODEL = -1
 MI_ARCH_LLAMA, MI_ARCH_QWEN3 = 0, 1
 MI_MAX_TOP_LOGPROBS = 20
+MI_MAX_ROW_LOGIT_BIAS = 1024
 MI_ABI_VERSION = 4
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
@@ -101,6 +102,7 @@ SIGNATURES = {
     "mi_step_enqueue_rows": (C.c_int, [_P, _P, _I32P, C.c_int, _I32P, C.c_int, C.POINTER(SampleParams), C.POINTER(C.c_int64)]),
     "mi_step_enqueue_mixed": (C.c_int, [_P, _P, _I32P, _I32P, _I32P, C.c_int, _I32P, C.POINTER(SampleParams), C.POINTER(C.c_int64)]),
     "mi_kv_reset_row": (C.c_int, [_P, C.c_int]),
+    "mi_kv_set_row_logit_bias": (C.c_int, [_P, C.c_int, _I32P, _F32P, C.c_int]),
     "mi_step_wait": (C.c_int, [_P, C.c_int64, _I32P, _F32P, _F32P, _I32P, _F32P]),
     "mi_profile_select": (C.c_int, [_P, C.c_char_p]),
     "mi_profile_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -135,6 +137,9 @@ SIGNATURES = {
     "mi_op_sample": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "mi_op_sample_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
                                   C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "mi_op_sample_rowbias": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
+                                       C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P,
+                                       C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@
 // [layer][B][Hkv][capacity][D], plus per-row lengths that live ON THE DEVICE so that a decode
 // step needs no host data at all.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <list>
 #include <map>
@@ -158,6 +159,19 @@ struct mi_kv {
   int32_t* d_rows = nullptr;     // [B] scratch: cache rows of the current call (continuous batching)
   float* partial = nullptr; int partial_splits = 0;
   int* counters = nullptr;       // [B*Hkv] split-arrival tickets of the fused decode attention
+  // ---- per-row logit_bias (mi_kv_set_row_logit_bias): one block [B counts | B map | B x MI_MAX_ROW_LOGIT_BIAS ids | as many
+  // values], allocated by the first call that sets a bias.  rb_host_cnt mirrors the counts in enqueue order and rb_biased
+  // counts the rows with entries: a step enqueued while it is 0 launches the sampler without the table.  Uploads go through
+  // RB_STAGE pinned slots [ids | values], each reusable once its event (recorded behind its copies) has passed.
+  static constexpr int RB_STAGE = 4;
+  int32_t* rb_block = nullptr;
+  std::vector<int32_t> rb_host_cnt;
+  int rb_biased = 0;
+  char* rb_stage = nullptr; hipEvent_t rb_ev[RB_STAGE] = {}; int rb_next = 0;
+  int32_t* rb_cnt() const { return rb_block; }
+  int32_t* rb_map() const { return rb_block + B; }                 // the sampled row -> cache row map of a mixed step
+  int32_t* rb_ids() const { return rb_block + 2 * (size_t)B; }
+  float* rb_vals() const { return (float*)(rb_block + 2 * (size_t)B + (size_t)B * MI_MAX_ROW_LOGIT_BIAS); }
   // ---- block-paged form (mi_kv_create_paged): k / v are arenas [layer][block][Hkv][1 << bs_shift][D]; a row owns the
   // blocks its table names, in order; block 0 is never handed out (unassigned table entries point at it, so a clamped
   // address is always mapped memory); cap = bt_stride << bs_shift is the longest sequence a row can hold
@@ -1103,7 +1117,10 @@ int check_controls(const mi_sample_params* sp, int B) {
   return MI_OK;
 }
 
-int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* forced = nullptr) {
+// kv: the cache whose per-row logit_bias table the sampled rows obey (null: none, mi_score_tokens); rb_map: device [B], the
+// cache row of every sampled row, or null when sampled row b is cache row b
+int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* forced = nullptr, const mi_kv* kv = nullptr,
+               const int32_t* rb_map = nullptr) {
   mi_sample_params def{}; def.struct_size = sizeof(def); def.temperature = 0.f; def.top_p = 1.f; def.stream_position = -1;
   if (!sp) sp = &def;
   hipStream_t st = e->stream;
@@ -1161,6 +1178,10 @@ int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* f
   }
   sc.tokens_out = e->d_next; sc.logprob_out = e->d_logprob; sc.prob_row0_out = forced ? nullptr : e->d_prob0;
   sc.topk_ids = e->d_topk_ids; sc.topk_logprobs = e->d_topk_lp; sc.row_stats = e->d_rowstats;
+  if (kv && kv->rb_biased > 0 && !forced) {                 // (no biased row: the launch and the arguments of a cache without a table)
+    sc.rb_cnt = kv->rb_cnt(); sc.rb_ids = kv->rb_ids(); sc.rb_vals = kv->rb_vals(); sc.rb_map = rb_map;
+    sc.rb_rows = kv->B; sc.rb_cap = MI_MAX_ROW_LOGIT_BIAS;
+  }
   return launch_sample(sc, st);
 }
 
@@ -1193,7 +1214,7 @@ int step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, const int3
   const int frc = forward(e, kv, rows, {{0, n, L, 0}}, L, Head::LAST);
   e->tok_src = nullptr;
   MI_TRY(frc);
-  MI_TRY(run_sample(e, n, sp));
+  MI_TRY(run_sample(e, n, sp, nullptr, kv, rows ? kv->d_rows : nullptr));   // (forward left the call's rows in d_rows)
   e->last_n = n;
   return finish_step(e, n, sp, ticket);
 }
@@ -1604,6 +1625,9 @@ void mi_kv_destroy(mi_kv* kv) {
   hipStreamSynchronize(kv->e->stream);
   hipFree(kv->k); hipFree(kv->v); hipFree(kv->d_off); hipFree(kv->partial); hipFree(kv->counters); hipFree(kv->d_rows);
   hipFree(kv->d_btab);
+  hipFree(kv->rb_block);
+  if (kv->rb_stage) hipHostFree(kv->rb_stage);
+  for (hipEvent_t ev : kv->rb_ev) if (ev) hipEventDestroy(ev);
   delete kv;
 }
 
@@ -1612,6 +1636,11 @@ int mi_kv_reset(mi_kv* kv, int batch) {
   if (batch != kv->B) return fail(MI_ERR_INVALID, "mi_kv_reset: batch differs from the allocated batch (create a new kv)");
   MI_HIP(hipSetDevice(kv->e->device));
   MI_HIP(hipMemsetAsync(kv->d_off, 0, kv->B * sizeof(int32_t), kv->e->stream));
+  if (kv->rb_biased > 0) {                                  // every row's logit_bias goes with its contents
+    MI_HIP(hipMemsetAsync(kv->rb_cnt(), 0, kv->B * sizeof(int32_t), kv->e->stream));
+    std::fill(kv->rb_host_cnt.begin(), kv->rb_host_cnt.end(), 0);
+    kv->rb_biased = 0;
+  }
   MI_HIP(hipStreamSynchronize(kv->e->stream));
   std::fill(kv->h_off.begin(), kv->h_off.end(), 0);
   for (int r = 0; r < kv->B; ++r) kv_release_row(kv, r);
@@ -1625,6 +1654,81 @@ int mi_kv_reset_row(mi_kv* kv, int row) {
   MI_HIP(hipMemsetAsync(kv->d_off + row, 0, sizeof(int32_t), kv->e->stream));   // ordered behind the steps already enqueued
   kv->h_off[row] = 0;
   kv_release_row(kv, row);      // (paged: the blocks go back to the pool; whoever gets them next writes behind the steps in flight)
+  if (kv->rb_biased > 0 && kv->rb_host_cnt[row] > 0) {      // the next occupant of the row samples unbiased
+    MI_HIP(hipMemsetAsync(kv->rb_cnt() + row, 0, sizeof(int32_t), kv->e->stream));
+    kv->rb_host_cnt[row] = 0;
+    --kv->rb_biased;
+  }
+  return MI_OK;
+}
+
+int mi_kv_set_row_logit_bias(mi_kv* kv, int row, const int32_t* ids, const float* values, int n) {
+  if (!kv) return fail(MI_ERR_INVALID, "null kv");
+  if (row < 0 || row >= kv->B) return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: row out of range");
+  if (n < 0 || n > MI_MAX_ROW_LOGIT_BIAS)
+    return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: n must be in [0, " + std::to_string(MI_MAX_ROW_LOGIT_BIAS) + "]");
+  if (n > 0 && (!ids || !values)) return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: null ids / values");
+  const int V = kv->e->d.vocab_size;
+  if (n > 0) {
+    std::vector<int32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 0; i < n; ++i) {
+      if (ids[i] < 0 || ids[i] >= V)
+        return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) +
+                                        " is outside the vocabulary [0, " + std::to_string(V) + ")");
+      if (!std::isfinite(values[i]))
+        return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: values[" + std::to_string(i) + "] is not finite");
+      if (i > 0 && sorted[i] == sorted[i - 1])
+        return fail(MI_ERR_INVALID, "mi_kv_set_row_logit_bias: ids names token " + std::to_string(sorted[i]) + " twice");
+    }
+  }
+  MI_HIP(hipSetDevice(kv->e->device));
+  hipStream_t st = kv->e->stream;
+  if (n == 0) {                                             // clear; a cache that never had a bias has nothing to clear
+    if (kv->rb_biased > 0 && kv->rb_host_cnt[row] > 0) {
+      MI_HIP(hipMemsetAsync(kv->rb_cnt() + row, 0, sizeof(int32_t), st));
+      kv->rb_host_cnt[row] = 0;
+      --kv->rb_biased;
+    }
+    return MI_OK;
+  }
+  const size_t cap = MI_MAX_ROW_LOGIT_BIAS;
+  if (!kv->rb_block) {                                      // first use: the table, its staging and their events
+    const size_t words = 2 * (size_t)kv->B + 2 * (size_t)kv->B * cap;
+    int32_t* blk = nullptr; char* stage = nullptr;
+    if (hipMalloc(&blk, words * sizeof(int32_t)) != hipSuccess) return fail(MI_ERR_RUNTIME, "out of device memory allocating the logit_bias table");
+    if (hipHostMalloc(&stage, (size_t)mi_kv::RB_STAGE * cap * 8) != hipSuccess) {
+      hipFree(blk);
+      return fail(MI_ERR_RUNTIME, "out of pinned host memory allocating the logit_bias staging");
+    }
+    for (hipEvent_t& ev : kv->rb_ev)
+      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        for (hipEvent_t& x : kv->rb_ev) { if (x) hipEventDestroy(x); x = nullptr; }
+        hipFree(blk); hipHostFree(stage);
+        return fail(MI_ERR_RUNTIME, "hipEventCreate failed (logit_bias staging)");
+      }
+    if (hipMemsetAsync(blk, 0, 2 * (size_t)kv->B * sizeof(int32_t), st) != hipSuccess) {
+      for (hipEvent_t& x : kv->rb_ev) { hipEventDestroy(x); x = nullptr; }
+      hipFree(blk); hipHostFree(stage);
+      return fail(MI_ERR_RUNTIME, "hipMemsetAsync failed (logit_bias table)");
+    }
+    kv->rb_block = blk; kv->rb_stage = stage;
+    kv->rb_host_cnt.assign(kv->B, 0);
+  }
+  // the caller's arrays -> a pinned slot of ours (they are the caller's again when this returns) -> the row's entries and
+  // then its count, on the engine's stream: behind every step already enqueued, ahead of every later one
+  const int slot = kv->rb_next;
+  MI_HIP(hipEventSynchronize(kv->rb_ev[slot]));             // (a never-recorded event is complete)
+  char* stage = kv->rb_stage + (size_t)slot * cap * 8;
+  memcpy(stage, ids, (size_t)n * sizeof(int32_t));
+  memcpy(stage + cap * 4, values, (size_t)n * sizeof(float));
+  MI_HIP(hipMemcpyAsync(kv->rb_ids() + (size_t)row * cap, stage, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  MI_HIP(hipMemcpyAsync(kv->rb_vals() + (size_t)row * cap, stage + cap * 4, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+  MI_HIP(hipMemsetD32Async((hipDeviceptr_t)(kv->rb_cnt() + row), n, 1, st));
+  MI_HIP(hipEventRecord(kv->rb_ev[slot], st));
+  kv->rb_next = (slot + 1) % mi_kv::RB_STAGE;
+  if (kv->rb_host_cnt[row] == 0) ++kv->rb_biased;
+  kv->rb_host_cnt[row] = n;
   return MI_OK;
 }
 
@@ -1775,7 +1879,16 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
   // Only decode rows: the decode step's kernels.  Otherwise the call is routed like a prefill of R rows (gemv_rows: the
   // weight-streaming kernel for short calls, the K-split 128 x 128 tile for a few hundred rows, plain tiles above).
   MI_TRY(forward(e, kv, rows, groups, R == (size_t)nd ? 1 : 2, n_out > 0 ? Head::GATHER : Head::NONE, gather, "mixed step"));
-  if (n_out > 0) MI_TRY(run_sample(e, n_out, sp));
+  if (n_out > 0) {
+    const int32_t* rb_map = nullptr;
+    if (kv->rb_biased > 0) {                     // sampled row i = the i-th wanted segment: its cache row
+      std::vector<int32_t> wanted;
+      for (int i = 0; i < n; ++i) if (want[i]) wanted.push_back(rows[i]);
+      MI_HIP(hipMemcpyAsync(kv->rb_map(), wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+      rb_map = kv->rb_map();
+    }
+    MI_TRY(run_sample(e, n_out, sp, nullptr, kv, rb_map));
+  }
   e->last_n = -1;                                // the device-resident token feed does not survive a mixed step
   return finish_step(e, n_out, sp, ticket);
 }

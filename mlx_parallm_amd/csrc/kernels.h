@@ -315,6 +315,14 @@ struct SampleCall {
   const float* row_min_p = nullptr;
   const uint64_t* row_seed = nullptr;    // device [B], both or neither: row b with row_position[b] >= 0 draws
   const int64_t* row_position = nullptr; // philox(row_seed[b], row_position[b], 0); < 0: the call-wide (seed, step, b)
+  // per-row logit_bias table (sample_kernel<*, true>; rb_cnt == null: the kernels without it).  Sampled row b adds the
+  // rb_cnt[t] entries (rb_ids[t][i], rb_vals[t][i]) of table row t = rb_map ? rb_map[b] : b, after the call-wide list;
+  // a t outside [0, rb_rows) and entries past rb_cap or with an id outside [0, V) are skipped
+  const int32_t* rb_cnt = nullptr;       // device [rb_rows]
+  const int32_t* rb_ids = nullptr;       // device [rb_rows][rb_cap]
+  const float* rb_vals = nullptr;        // device [rb_rows][rb_cap]
+  const int32_t* rb_map = nullptr;       // device [B] or null: the identity
+  int rb_rows = 0, rb_cap = 0;
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 

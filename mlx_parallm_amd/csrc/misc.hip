@@ -435,8 +435,9 @@ __device__ Prefix min_p_prefix(const float* lg, int V, float mx, float inv_t, fl
 }
 
 // EXT = false: temperature / top-p with the call-wide stream, the launch of every call that sets none of the newer controls
-// (its code does not change when they do).  EXT = true: + top-k, min-p and per-row streams.
-template <bool EXT>
+// (its code does not change when they do).  EXT = true: + top-k, min-p and per-row streams.  ROWB = true: + the per-row
+// logit_bias table (SampleCall::rb_*), launched only when the call carries one.
+template <bool EXT, bool ROWB = false>
 __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
   __shared__ ArgMax sh_am[ST / 64];
   __shared__ float sh_f[ST / 64];
@@ -459,7 +460,20 @@ __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
       const int id = c.bias_ids[i];
       if (id >= 0 && id < V) lg[id] = round_rt(lg[id] + c.bias_vals[i], c.rnd);
     }
-    __syncthreads();
+    __syncthreads();       // (also orders the row's own entries behind these: an id in both lists gets both, in this order)
+  }
+  if constexpr (ROWB) {    // the bias of the request that holds this row's cache row; a row without one reads only its count
+    const int t = c.rb_map ? c.rb_map[b] : b;
+    const int n = (t >= 0 && t < c.rb_rows) ? min(c.rb_cnt[t], c.rb_cap) : 0;
+    if (n > 0) {           // (uniform over the block)
+      const int32_t* ids = c.rb_ids + (size_t)t * c.rb_cap;
+      const float* vals = c.rb_vals + (size_t)t * c.rb_cap;
+      for (int i = threadIdx.x; i < n; i += ST) {
+        const int id = ids[i];
+        if (id >= 0 && id < V) lg[id] = round_rt(lg[id] + vals[i], c.rnd);
+      }
+      __syncthreads();
+    }
   }
   // ---- max / argmax, log-sum-exp
   ArgMax a{-INFINITY, 0x7fffffff};
@@ -615,7 +629,11 @@ int launch_embed(const LinearW& W, const EmbedCall& c, hipStream_t st) {
 int launch_sample(const SampleCall& c, hipStream_t st) {
   if (c.top_logprobs < 0 || c.top_logprobs > MI_MAX_TOP_LOGPROBS) return fail(MI_ERR_INVALID, "sample: top_logprobs out of range");
   const bool ext = c.top_k > 0 || c.min_p > 0.f || c.row_top_k || c.row_min_p || c.row_position;
-  if (ext) hipLaunchKernelGGL(sample_kernel<true>, dim3(c.B), dim3(ST), 0, st, c);
+  if (c.rb_cnt != nullptr) {
+    if (!c.rb_ids || !c.rb_vals || c.rb_rows < 1 || c.rb_cap < 1) return fail(MI_ERR_INVALID, "sample: incomplete row bias table");
+    if (ext) hipLaunchKernelGGL((sample_kernel<true, true>), dim3(c.B), dim3(ST), 0, st, c);
+    else hipLaunchKernelGGL((sample_kernel<false, true>), dim3(c.B), dim3(ST), 0, st, c);
+  } else if (ext) hipLaunchKernelGGL(sample_kernel<true>, dim3(c.B), dim3(ST), 0, st, c);
   else hipLaunchKernelGGL(sample_kernel<false>, dim3(c.B), dim3(ST), 0, st, c);
   MI_HIP(hipGetLastError());
   if (c.prob_row0_out) {

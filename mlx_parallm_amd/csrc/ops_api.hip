@@ -359,28 +359,64 @@ int mi_op_sample(float* logits, int B, int V, float temperature, float top_p, co
   return finish();
 }
 
-int mi_op_sample_ex(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
-                    const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
-                    const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
-                    const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
-                    float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats) {
+// mi_op_sample_ex and mi_op_sample_rowbias: one launch of the sampler with every control; `who` prefixes the refusals
+static int sample_op(const std::string& who, float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                     const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                     const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                     const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                     float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
+                     int n_bias, const int32_t* bias_ids, const float* bias_values,
+                     const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
+                     int table_rows, int cap, const int32_t* row_map) {
   if (!logits || !tokens_out || !row_stats) return fail(MI_ERR_INVALID, "null argument");
-  if (B < 1 || V < 1) return fail(MI_ERR_INVALID, "sample_ex: B and V must be positive");
-  if (top_k < 0) return fail(MI_ERR_INVALID, "sample_ex: top_k must be >= 0 (0 = off)");
-  if (!(min_p >= 0.f && min_p <= 1.f)) return fail(MI_ERR_INVALID, "sample_ex: min_p must be in [0, 1] (0 = off)");
-  if ((row_temperature != nullptr) != (row_top_p != nullptr)) return fail(MI_ERR_INVALID, "sample_ex: row_temperature and row_top_p come together");
-  if ((row_seed != nullptr) != (row_position != nullptr)) return fail(MI_ERR_INVALID, "sample_ex: row_seed and row_position come together");
+  if (B < 1 || V < 1) return fail(MI_ERR_INVALID, who + ": B and V must be positive");
+  if (top_k < 0) return fail(MI_ERR_INVALID, who + ": top_k must be >= 0 (0 = off)");
+  if (!(min_p >= 0.f && min_p <= 1.f)) return fail(MI_ERR_INVALID, who + ": min_p must be in [0, 1] (0 = off)");
+  if ((row_temperature != nullptr) != (row_top_p != nullptr)) return fail(MI_ERR_INVALID, who + ": row_temperature and row_top_p come together");
+  if ((row_seed != nullptr) != (row_position != nullptr)) return fail(MI_ERR_INVALID, who + ": row_seed and row_position come together");
+  if (n_bias < 0 || (n_bias > 0 && (!bias_ids || !bias_values))) return fail(MI_ERR_INVALID, who + ": n_bias entries need bias_ids and bias_values");
+  if (row_bias_counts && (!row_bias_ids || !row_bias_values || table_rows < 1 || cap < 1))
+    return fail(MI_ERR_INVALID, who + ": a table needs row_bias_ids, row_bias_values, table_rows >= 1 and cap >= 1");
   MI_TRY(ready());
   SampleCall sc{};
   sc.logits = logits; sc.B = B; sc.V = V; sc.rnd = RND_NONE; sc.temperature = temperature; sc.top_p = top_p;
+  sc.n_bias = n_bias; sc.bias_ids = bias_ids; sc.bias_vals = bias_values;
   sc.uniforms = uniforms; sc.seed = seed; sc.step = step; sc.top_logprobs = top_logprobs; sc.lp_temp = 0;
   sc.row_temp = row_temperature; sc.row_top_p = row_top_p;
   sc.top_k = top_k; sc.min_p = min_p; sc.row_top_k = row_top_k; sc.row_min_p = row_min_p;
   sc.row_seed = row_seed; sc.row_position = row_position;
   sc.tokens_out = tokens_out; sc.logprob_out = logprob_out; sc.prob_row0_out = prob_row0_out;
   sc.topk_ids = topk_ids; sc.topk_logprobs = topk_logprobs; sc.row_stats = row_stats;
+  if (row_bias_counts) {                           // (null: launch_sample picks the instantiations without the table)
+    sc.rb_cnt = row_bias_counts; sc.rb_ids = row_bias_ids; sc.rb_vals = row_bias_values;
+    sc.rb_rows = table_rows; sc.rb_cap = cap; sc.rb_map = row_map;
+  }
   MI_TRY(launch_sample(sc, nullptr));
   return finish();
+}
+
+int mi_op_sample_ex(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                    const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                    const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                    const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                    float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats) {
+  return sample_op("sample_ex", logits, B, V, temperature, top_p, top_k, min_p, row_temperature, row_top_p, row_top_k, row_min_p,
+                   row_seed, row_position, seed, step, uniforms, top_logprobs, tokens_out, logprob_out, prob_row0_out, topk_ids,
+                   topk_logprobs, row_stats, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr);
+}
+
+int mi_op_sample_rowbias(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                         const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                         const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                         const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                         float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
+                         int n_bias, const int32_t* bias_ids, const float* bias_values,
+                         const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
+                         int table_rows, int cap, const int32_t* row_map) {
+  return sample_op("sample_rowbias", logits, B, V, temperature, top_p, top_k, min_p, row_temperature, row_top_p, row_top_k,
+                   row_min_p, row_seed, row_position, seed, step, uniforms, top_logprobs, tokens_out, logprob_out, prob_row0_out,
+                   topk_ids, topk_logprobs, row_stats, n_bias, bias_ids, bias_values, row_bias_counts, row_bias_ids,
+                   row_bias_values, table_rows, cap, row_map);
 }
 
 }  // extern "C"

@@ -153,6 +153,25 @@ class KVCache:
         """Forget one row (continuous batching: the slot of a finished sequence)."""
         L.check(L.lib().mi_kv_reset_row(self._h, int(row)))
 
+    def set_row_logit_bias(self, row: int, bias: Optional[Dict[int, float]]) -> None:
+        """The logit_bias of the request that occupies ``row`` (``mi_kv_set_row_logit_bias``): it replaces the row's bias,
+        ``None`` / ``{}`` clears it; every later step that samples this row adds it after the call's own ``logit_bias``.
+        ``reset_row`` / ``reset`` clear it.  ValueError (nothing changed): a bad row, more than 1024 entries, an id outside
+        the vocabulary, a non-finite value."""
+        if not bias:
+            L.check(L.lib().mi_kv_set_row_logit_bias(self._h, int(row), None, None, 0))
+            return
+        for k in bias:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                raise ValueError(f"set_row_logit_bias: token id {k!r} is not an int")
+            if not -2 ** 31 <= int(k) < 2 ** 31:
+                raise ValueError(f"set_row_logit_bias: token id {k!r} is outside the vocabulary")
+        ids = np.ascontiguousarray([int(k) for k in bias.keys()], dtype=np.int32)
+        with np.errstate(over="ignore"):           # (a value beyond float32 becomes inf, which the library refuses by name)
+            vals = np.ascontiguousarray(np.asarray([float(v) for v in bias.values()], dtype=np.float64).astype(np.float32))
+        L.check(L.lib().mi_kv_set_row_logit_bias(self._h, int(row), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 vals.ctypes.data_as(C.POINTER(C.c_float)), len(ids)))
+
     def ensure(self, needed_tokens: int) -> None:
         """Grow in ``step``-token blocks like base.py:104-117 (contents are kept)."""
         cap = self.capacity

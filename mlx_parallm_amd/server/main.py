@@ -867,6 +867,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
                 raise HTTPException(status_code=400,
                                     detail="Streaming with n > 1 is not currently supported for completions.")
             if state.scheduler is not None:
+                _request_controls(request, tok)          # (400 while the status line can still say so)
                 return StreamingResponse(_scheduled_completion_stream(state, request, tok), media_type="text/event-stream")
             return StreamingResponse(_completion_stream(state, request, rec), media_type="text/event-stream")
         if state.scheduler is not None:
@@ -890,6 +891,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
         if state.scheduler is not None:
             tok = _wrap(rec.tokenizer_instance)
             if request.stream:
+                _request_controls(request, tok)          # (400 while the status line can still say so)
                 return StreamingResponse(_scheduled_chat_stream(state, request, tok), media_type="text/event-stream")
             return await _scheduled_response(state, request, tok, request.model)
         if request.stream:
@@ -934,16 +936,30 @@ def _request_params(req: AnyRequest) -> Tuple[int, float, float]:
     return int(req.max_tokens), float(req.temperature), float(req.top_p)
 
 
+def _request_controls(req: AnyRequest, tok: TokenizerWrapper) -> Tuple[Optional[Dict[int, float]], List[str]]:
+    """The request's ``logit_bias`` as {token id: value} and its ``stop`` as a list of strings, as the scheduler takes them;
+    what it would refuse (more than 1024 bias entries, a non-finite value, more than 4 stop strings, an empty one) is HTTP 400."""
+    from .scheduler import check_logit_bias, check_stop
+
+    try:
+        bias = check_logit_bias(parse_logit_bias(req.logit_bias, tok))
+        return bias or None, check_stop(getattr(req, "stop", None))
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=str(e))
+
+
 def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyRequest, on_delta: Optional[Callable] = None,
             choice: int = 0):
     """Queue one sequence; -> (future resolving to (text, n_prompt, n_completion, finish_reason), n_prompt, sequence).
     ``sequence.cancel()`` frees its KV slot when the caller gives up (timeout, client disconnect).  A request with a
-    ``seed`` gives choice i the stream of ``seed + i``; without one the sequence draws from the scheduler's stream."""
+    ``seed`` gives choice i the stream of ``seed + i``; without one the sequence draws from the scheduler's stream.
+    Every choice carries the request's ``logit_bias`` (set on its KV row) and ``stop`` list."""
     loop = asyncio.get_running_loop()
     fut: asyncio.Future = loop.create_future()
     ids = _ids_of(tok, text)[0]
     max_tokens, temp, top_p = _request_params(req)
     parts: List[str] = []
+    bias, stop = _request_controls(req, tok)
 
     def sink(seq, delta, reason):            # scheduler thread
         if delta:
@@ -958,7 +974,7 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
         seed = getattr(req, "seed", None)
         seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink, top_k=int(getattr(req, "top_k", 0) or 0),
                                      min_p=float(getattr(req, "min_p", 0.0) or 0.0),
-                                     seed=None if seed is None else int(seed) + choice)
+                                     seed=None if seed is None else int(seed) + choice, logit_bias=bias, stop=stop)
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return fut, len(ids), seq

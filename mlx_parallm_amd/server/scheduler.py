@@ -11,6 +11,9 @@ for -- a request does not wait for the running batch to finish -- and does it on
     (``mi_sample_params.row_temperature / row_top_p / row_top_k / row_min_p``); a sequence submitted with a ``seed`` draws
     from its own random stream (``row_seed`` = the seed, ``row_position`` = how many sampling steps the sequence has had), so
     its draws do not depend on the slot it got or on who else is alive;
+  * a request's ``logit_bias`` is set on its row at admission (``KVCache.set_row_logit_bias``, right after the row's reset) and
+    stays on the device until the row is reset for its next occupant; its ``stop`` strings are matched on the detokenised
+    generated text (``StopMatcher``): the sequence finishes with reason "stop" at that step boundary, as for EOS;
   * while the row set is stable the next step is enqueued before the current one is read back, sampled tokens
     stay on the device (the same one-step-ahead pipelining as generate_step, utils.py:420-427); when a sequence
     finishes or a request is waiting, the step already in flight completes, its tokens for finished rows are
@@ -25,10 +28,11 @@ from __future__ import annotations
 import collections
 import itertools
 import logging
+import math
 import os
 import threading
 import time
-from typing import Callable, Deque, List, Optional
+from typing import Callable, Deque, Dict, List, Optional
 
 import numpy as np
 
@@ -39,15 +43,99 @@ log = logging.getLogger("mlx_parallm_amd.scheduler")
 Sink = Callable[["Sequence", Optional[str], Optional[str]], None]
 
 
+MAX_ROW_LOGIT_BIAS = 1024      # MI_MAX_ROW_LOGIT_BIAS (mi355_decode.h): entries of one request's logit_bias
+MAX_STOP_SEQUENCES = 4         # as the OpenAI API
+
+
+class StopMatcher:
+    """Stop sequences over the detokenised text of ONE generation (never its prompt).
+
+    ``feed(delta) -> (text_to_emit, hit)``: the new text of a step goes in, what may be shown comes out.  The first stop string
+    that completes ends the generation -- when several complete in the same delta, the one that STARTS earliest -- and the
+    emitted text ends just before it.  While nothing has completed, the longest suffix of the text that is a proper prefix
+    of any stop string is held back, so a client never sees the beginning of a stop string that then completes; ``flush()``
+    hands the held text out when the generation ends for another reason (EOS, length)."""
+
+    def __init__(self, stops):
+        self.stops = [str(s) for s in stops]
+        if any(not s for s in self.stops):
+            raise ValueError("stop: an empty stop string")
+        self.hit = False
+        self._held = ""
+
+    def feed(self, delta: Optional[str]):
+        if self.hit:
+            return "", True
+        buf = self._held + (delta or "")
+        starts = [i for i in (buf.find(s) for s in self.stops) if i >= 0]
+        if starts:
+            self.hit, self._held = True, ""
+            return buf[:min(starts)], True
+        hold = 0
+        for s in self.stops:
+            for k in range(min(len(s) - 1, len(buf)), hold, -1):
+                if buf.endswith(s[:k]):
+                    hold = k
+                    break
+        self._held = buf[len(buf) - hold:]
+        return buf[:len(buf) - hold], False
+
+    def flush(self) -> str:
+        out, self._held = self._held, ""
+        return out
+
+
+def check_logit_bias(logit_bias) -> Dict[int, float]:
+    """A request's logit_bias as {token id: value}: ids are ints >= 0, values finite, at most MAX_ROW_LOGIT_BIAS entries
+    (ValueError otherwise; ids beyond the vocabulary are the engine's to refuse)."""
+    if not logit_bias:
+        return {}
+    if not isinstance(logit_bias, dict):
+        raise ValueError("logit_bias must be a dict of token id -> bias")
+    if len(logit_bias) > MAX_ROW_LOGIT_BIAS:
+        raise ValueError(f"logit_bias has {len(logit_bias)} entries, at most {MAX_ROW_LOGIT_BIAS} are supported")
+    out: Dict[int, float] = {}
+    for k, v in logit_bias.items():
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0:
+            raise ValueError(f"logit_bias: token id {k!r} is not an int >= 0")
+        try:
+            fv = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"logit_bias[{k}]: {v!r} is not a number") from None
+        if not math.isfinite(fv):
+            raise ValueError(f"logit_bias[{k}] = {v!r} is not finite")
+        out[int(k)] = fv
+    return out
+
+
+def check_stop(stop) -> List[str]:
+    """A request's stop list: at most MAX_STOP_SEQUENCES non-empty strings (ValueError otherwise)."""
+    if stop is None:
+        return []
+    if isinstance(stop, str):
+        stop = [stop]
+    stop = list(stop)
+    if len(stop) > MAX_STOP_SEQUENCES:
+        raise ValueError(f"stop: at most {MAX_STOP_SEQUENCES} stop sequences are supported, got {len(stop)}")
+    for s in stop:
+        if not isinstance(s, str) or not s:
+            raise ValueError("stop: every stop sequence must be a non-empty string")
+    return stop
+
+
 class Sequence:
     _ids = itertools.count()
 
     def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok, *, top_k: int = 0,
-                 min_p: float = 0.0, seed: Optional[int] = None):
+                 min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
+                 stop: Optional[List[str]] = None):
         if int(top_k) < 0:
             raise ValueError("top_k must be >= 0 (0 = off)")
         if not 0.0 <= float(min_p) <= 1.0:
             raise ValueError("min_p must be in [0, 1] (0 = off)")
+        self.logit_bias = check_logit_bias(logit_bias)     # set on the sequence's cache row at admission
+        self.stop = check_stop(stop)
+        self.stopper = StopMatcher(self.stop) if self.stop else None
         self.id = next(Sequence._ids)
         self.prompt = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         self.max_tokens = int(max_tokens)
@@ -156,9 +244,17 @@ class ContinuousScheduler:
 
     # ------------------------------------------------------------------ client side (any thread)
     def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, *, top_k: int = 0,
-               min_p: float = 0.0, seed: Optional[int] = None) -> Sequence:
+               min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
+               stop: Optional[List[str]] = None) -> Sequence:
         seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer),
-                       top_k=top_k, min_p=min_p, seed=seed)
+                       top_k=top_k, min_p=min_p, seed=seed, logit_bias=logit_bias, stop=stop)
+        if seq.logit_bias:
+            if not hasattr(self.kv, "set_row_logit_bias"):
+                raise ValueError("logit_bias: this KV cache has no per-row logit_bias (set_row_logit_bias)")
+            # (refused here, on the client's thread: at admission the engine's refusal would fail the whole step)
+            vocab = getattr(getattr(self.model.engine, "desc", None), "vocab_size", None)
+            if vocab is not None and max(seq.logit_bias) >= int(vocab):
+                raise ValueError(f"logit_bias: token id {max(seq.logit_bias)} is outside the vocabulary [0, {int(vocab)})")
         if len(seq.prompt) == 0:
             raise ValueError("empty prompt")
         if len(seq.prompt) + seq.max_tokens > self.model.engine.max_positions:
@@ -228,6 +324,12 @@ class ContinuousScheduler:
     def _finish(self, seq: Sequence, reason: str) -> None:
         seq.detok.finalize()
         tail = seq.detok.last_segment
+        if seq.stopper is not None:            # the last text may complete a stop string; else what was held back goes out
+            tail, hit = seq.stopper.feed(tail)
+            if hit:
+                reason = "stop"
+            else:
+                tail += seq.stopper.flush()
         seq.finished = reason
         self._emit(seq, tail if tail else None, reason)
 
@@ -240,11 +342,24 @@ class ContinuousScheduler:
         seq.generated.append(tok)
         seq.detok.add_token(tok)
         delta = seq.detok.last_segment
+        if seq.stopper is not None:
+            delta, hit = seq.stopper.feed(delta)
+            if hit:                            # the text ends just before the stop string; its tokens stay counted in `generated`
+                seq.finished = "stop"
+                self._emit(seq, delta or None, "stop")
+                return
         if len(seq.generated) >= seq.max_tokens:
             seq.detok.finalize()
             tail = seq.detok.last_segment
-            seq.finished = "length"
-            self._emit(seq, (delta or "") + (tail or "") or None, "length")
+            reason = "length"
+            if seq.stopper is not None:        # the detokenizer's tail may complete a stop string; else the held text goes out
+                tail, hit = seq.stopper.feed(tail)
+                if hit:
+                    reason = "stop"
+                else:
+                    tail += seq.stopper.flush()
+            seq.finished = reason
+            self._emit(seq, (delta or "") + (tail or "") or None, reason)
         elif delta:
             self._emit(seq, delta, None)
 
@@ -268,7 +383,9 @@ class ContinuousScheduler:
         if seq.max_tokens <= 0:
             self._finish(seq, "length")
             return
-        self.kv.reset_row(slot)
+        self.kv.reset_row(slot)                   # (also clears the bias of the row's previous occupant)
+        if seq.logit_bias:                        # ahead of the row's first sampling step: the prefill below, or the last chunk
+            self.kv.set_row_logit_bias(slot, seq.logit_bias)
         seq.prefill_pos = 0
         if self.prefix_cache:                     # full blocks of an earlier prompt with the same prefix are mapped, not recomputed
             seq.prefill_pos = self.kv.prefix_attach(slot, seq.prompt)

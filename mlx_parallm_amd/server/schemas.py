@@ -102,6 +102,7 @@ class CompletionRequest(BaseModel):
     logprobs: Optional[int] = None
     echo: Optional[bool] = False
     logit_bias: Optional[Dict[str, float]] = None
+    stop: Optional[Union[str, List[str]]] = None     # up to 4 strings; honoured under the continuous scheduler
 
 
 # ---- /v1/chat/completions (schemas.py:121-172) ----
