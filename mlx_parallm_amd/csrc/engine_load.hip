@@ -1,0 +1,337 @@
+// engine_load.hip -- a checkpoint's tensors and LoRA factors into an engine, and mi_engine_finalize: the fused matrices are
+// checked, regrouped (rope_traditional), repacked tile-major and given their persistent second copies.
+#include <cstring>
+
+#include "engine_impl.h"
+
+using namespace mi;
+
+namespace {
+
+int kind_of(const FusedLinear& f, int bits) {
+  if (!f.quant) return f.dense_dtype == MI_F32 ? WK_F32 : (f.dense_dtype == MI_BF16 ? WK_BF16 : WK_F16);
+  const int base = bits == 8 ? WK_Q8_F32 : WK_Q4_F32;
+  return base + (f.scale_dtype == MI_F32 ? 0 : (f.scale_dtype == MI_BF16 ? 1 : 2));
+}
+
+int copy_in(void* dst, const void* src, size_t bytes, int on_device, hipStream_t st) {
+  MI_HIP(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  MI_HIP(hipStreamSynchronize(st));
+  return MI_OK;
+}
+
+// sub-tensor `part` of a fused linear: kind 0 = weight, 1 = scales, 2 = biases
+int set_linear(mi_engine* e, FusedLinear& f, int part, int K, int kind, const void* data, const int64_t* shape,
+               int ndim, int dtype, int on_device, const std::string& name) {
+  const mi_model_desc& d = e->d;
+  if (ndim != 2) return fail(MI_ERR_INVALID, name + ": expected a 2-D tensor");
+  const int rows = f.part_rows[part];
+  int total = 0, row0 = 0;
+  for (int i = 0; i < f.n_parts; ++i) { if (i < part) row0 += f.part_rows[i]; total += f.part_rows[i]; }
+  if (shape[0] != rows) return fail(MI_ERR_INVALID, name + ": wrong number of rows");
+  if (kind == 0) {
+    const bool packed = dtype == MI_U32;
+    if (packed && d.quant_bits == 0) return fail(MI_ERR_INVALID, name + ": packed weights but desc.quant_bits == 0");
+    const int64_t cols = packed ? (int64_t)K * d.quant_bits / 32 : K;
+    if (shape[1] != cols) return fail(MI_ERR_INVALID, name + ": wrong number of columns");
+    if (!packed && dtype != d.act_dtype)
+      return fail(MI_ERR_UNSUPPORTED, name + ": dense weight dtype differs from the model dtype");
+    if (f.w != nullptr && f.quant != packed) return fail(MI_ERR_UNSUPPORTED, name + ": fused parts mix dense and quantised weights");
+    const size_t row_bytes = (size_t)cols * dtype_size(dtype);
+    if (f.w == nullptr) {
+      f.quant = packed; f.dense_dtype = packed ? -1 : dtype; f.w_bytes = row_bytes * total;
+      MI_HIP(hipMalloc(&f.w, f.w_bytes));
+    }
+    MI_TRY(copy_in((char*)f.w + (size_t)row0 * row_bytes, data, row_bytes * rows, on_device, e->stream));
+    f.seen_w[part] = 1;
+  } else {
+    if (d.quant_bits == 0) return fail(MI_ERR_INVALID, name + ": scales/biases but desc.quant_bits == 0");
+    if (K % d.quant_group_size != 0) return fail(MI_ERR_INVALID, name + ": K not divisible by the group size");
+    const int64_t cols = K / d.quant_group_size;
+    if (shape[1] != cols) return fail(MI_ERR_INVALID, name + ": wrong number of groups");
+    if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, name + ": bad dtype");
+    if (f.scale_dtype >= 0 && f.scale_dtype != dtype) return fail(MI_ERR_UNSUPPORTED, name + ": mixed scale dtypes");
+    f.scale_dtype = dtype;
+    const size_t row_bytes = (size_t)cols * dtype_size(dtype);
+    void*& dst = kind == 1 ? f.scales : f.biases;
+    if (dst == nullptr) { f.s_bytes = row_bytes * total; MI_HIP(hipMalloc(&dst, f.s_bytes)); }
+    MI_TRY(copy_in((char*)dst + (size_t)row0 * row_bytes, data, row_bytes * rows, on_device, e->stream));
+    (kind == 1 ? f.seen_s : f.seen_b)[part] = 1;
+  }
+  return MI_OK;
+}
+
+int set_vector(mi_engine* e, void*& dst, int n, const void* data, const int64_t* shape, int ndim, int dtype,
+               int on_device, const std::string& name) {
+  if (ndim != 1 || shape[0] != n) return fail(MI_ERR_INVALID, name + ": wrong shape");
+  if (dtype != e->d.act_dtype) return fail(MI_ERR_UNSUPPORTED, name + ": norm weight dtype differs from the model dtype");
+  if (dst == nullptr) MI_HIP(hipMalloc(&dst, (size_t)n * dtype_size(dtype)));
+  return copy_in(dst, data, (size_t)n * dtype_size(dtype), on_device, e->stream);
+}
+
+// `<proj>.bias` of part `part` (1-D, the part's rows; float32 or a 16-bit float) -> float32 at the part's rows of f.bias
+int set_bias(mi_engine* e, FusedLinear& f, int part, const void* data, const int64_t* shape, int ndim, int dtype,
+             int on_device, const std::string& name) {
+  const int rows = f.part_rows[part];
+  int total = 0, row0 = 0;
+  for (int i = 0; i < f.n_parts; ++i) { if (i < part) row0 += f.part_rows[i]; total += f.part_rows[i]; }
+  if (ndim != 1 || shape[0] != rows) return fail(MI_ERR_INVALID, name + ": wrong shape");
+  if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, name + ": bad dtype");
+  if (f.bias == nullptr) MI_HIP(hipMalloc(&f.bias, (size_t)total * sizeof(float)));
+  if (dtype == MI_F32) {
+    MI_TRY(copy_in(f.bias + row0, data, (size_t)rows * sizeof(float), on_device, e->stream));
+  } else {
+    void* tmp = nullptr;
+    MI_HIP(hipMalloc(&tmp, (size_t)rows * dtype_size(dtype)));
+    int rc = copy_in(tmp, data, (size_t)rows * dtype_size(dtype), on_device, e->stream);
+    if (rc == MI_OK) rc = launch_convert(tmp, dtype, f.bias + row0, MI_F32, (size_t)rows, e->stream);
+    if (rc == MI_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MI_ERR_RUNTIME, name + ": converting the bias failed");
+    hipFree(tmp);
+    MI_TRY(rc);
+  }
+  f.seen_bias[part] = 1;
+  return MI_OK;
+}
+
+// rope_traditional: the first `nrows` rows (whole heads of D) of a row-major device array regrouped in place (kernels.h)
+int head_perm_inplace(mi_engine* e, void* buf, size_t nrows, int D, size_t row_bytes) {
+  if (buf == nullptr || nrows == 0 || row_bytes == 0) return MI_OK;
+  void* tmp = nullptr;
+  MI_HIP(hipMalloc(&tmp, nrows * row_bytes));
+  int rc = launch_head_perm_rows(buf, tmp, nrows, D, row_bytes, e->stream);
+  if (rc == MI_OK && (hipMemcpyAsync(buf, tmp, nrows * row_bytes, hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
+                      hipStreamSynchronize(e->stream) != hipSuccess))
+    rc = fail(MI_ERR_RUNTIME, "regrouping the q / k rows for rope_traditional failed");
+  hipFree(tmp);
+  return rc;
+}
+
+// the q and k parts of a q|k|v matrix as loaded (row-major, before the tile-major repack): codes, scales, quantisation
+// biases and linear biases.  Quantisation groups run along K, so whole rows move.
+int permute_qk_heads(mi_engine* e, FusedLinear& f) {
+  int total = 0;
+  if (f.qk_regrouped || f.W.layout == 1) return MI_OK;
+  for (int i = 0; i < f.n_parts; ++i) { total += f.part_rows[i]; if (!f.seen_w[i]) return MI_OK; }   // (finalize_linear reports it)
+  const size_t nrows = (size_t)f.part_rows[0] + f.part_rows[1];
+  const int D = e->d.head_dim;
+  MI_TRY(head_perm_inplace(e, f.w, nrows, D, f.w_bytes / total));
+  if (f.quant && f.scales != nullptr && f.biases != nullptr) {
+    MI_TRY(head_perm_inplace(e, f.scales, nrows, D, f.s_bytes / total));
+    MI_TRY(head_perm_inplace(e, f.biases, nrows, D, f.s_bytes / total));
+  }
+  if (f.bias != nullptr && f.seen_bias[0] && f.seen_bias[1]) MI_TRY(head_perm_inplace(e, f.bias, nrows, D, sizeof(float)));
+  f.qk_regrouped = true;
+  return MI_OK;
+}
+
+int finalize_linear(mi_engine* e, FusedLinear& f, int K, const std::string& name) {
+  int total = 0;
+  for (int i = 0; i < f.n_parts; ++i) {
+    total += f.part_rows[i];
+    if (!f.seen_w[i]) return fail(MI_ERR_NOTFOUND, name + ": weight not set");
+    if (f.quant && (!f.seen_s[i] || !f.seen_b[i])) return fail(MI_ERR_NOTFOUND, name + ": scales/biases not set");
+  }
+  if (f.quant && f.scale_dtype != e->d.act_dtype)
+    return fail(MI_ERR_UNSUPPORTED, name + ": scale dtype differs from the model dtype");
+  f.W.wk = kind_of(f, e->d.quant_bits);
+  f.W.w = f.w; f.W.scales = f.scales; f.W.biases = f.biases;
+  f.W.N = total; f.W.K = K; f.W.group = e->d.quant_group_size > 0 ? e->d.quant_group_size : 64;
+  f.W.bias = f.bias;
+  // "repack weights": tile-major layout for the matrices the streaming kernels read (repack.hip)
+  if (e->opt_tile_weights && tiled_supported(f.W.wk, f.W.N, f.W.K, f.W.group)) {
+    void* dst = nullptr;
+    if (hipMalloc(&dst, tiled_bytes(f.W.wk, f.W.N, f.W.K)) != hipSuccess)
+      return fail(MI_ERR_RUNTIME, name + ": out of device memory repacking weights");
+    MI_TRY(launch_repack_tiled(f.W, dst, e->stream));
+    MI_HIP(hipStreamSynchronize(e->stream));
+    hipFree(f.w); hipFree(f.scales); hipFree(f.biases);
+    f.w = dst; f.scales = nullptr; f.biases = nullptr;
+    f.W.w = dst; f.W.scales = nullptr; f.W.biases = nullptr; f.W.layout = 1;
+  }
+  return MI_OK;
+}
+
+int make_f32_copy(mi_engine* e, const void* src, int n, void** dst) {
+  if (src == nullptr) { *dst = nullptr; return MI_OK; }
+  if (e->d.act_dtype == MI_F32) { *dst = nullptr; return MI_OK; }
+  MI_HIP(hipMalloc(dst, (size_t)n * sizeof(float)));
+  return launch_convert(src, e->d.act_dtype, *dst, MI_F32, (size_t)n, e->stream);
+}
+
+// one of the seven linears of a block by its checkpoint name: the fused matrix, the part of it, its K, attention or MLP
+struct Proj { FusedLinear* f; int part, K; bool attn; };
+bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* p) {
+  const int H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  if (sub == "self_attn.q_proj") *p = {&l.qkv, 0, H, true};
+  else if (sub == "self_attn.k_proj") *p = {&l.qkv, 1, H, true};
+  else if (sub == "self_attn.v_proj") *p = {&l.qkv, 2, H, true};
+  else if (sub == "self_attn.o_proj") *p = {&l.o, 0, QD, true};
+  else if (sub == "mlp.gate_proj") *p = {&l.gate_up, 0, H, false};
+  else if (sub == "mlp.up_proj") *p = {&l.gate_up, 1, H, false};
+  else if (sub == "mlp.down_proj") *p = {&l.down, 0, d.intermediate_size, false};
+  else return false;
+  return true;
+}
+
+}  // namespace
+
+void mi::free_linear(FusedLinear& f) {
+  hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
+  for (int i = 0; i < 2; ++i) { hipFree(f.lora_a[i]); hipFree(f.lora_b[i]); }
+  hipFree(const_cast<float*>(f.lora3.a)); hipFree(const_cast<float*>(f.lora3.b));
+}
+
+extern "C" {
+
+int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, const int64_t* shape, int ndim,
+                         int dtype, int on_device) {
+  if (!e || !name_c || !data || !shape) return fail(MI_ERR_INVALID, "null argument");
+  if (e->finalized) return fail(MI_ERR_INVALID, "engine already finalized");
+  MI_HIP(hipSetDevice(e->device));
+  const mi_model_desc& d = e->d;
+  std::string name(name_c);
+  int kind = -1;
+  std::string base;
+  auto strip = [&](const char* suf, int k) {
+    const size_t n = strlen(suf);
+    if (name.size() > n && name.compare(name.size() - n, n, suf) == 0) { base = name.substr(0, name.size() - n); kind = k; }
+  };
+  strip(".weight", 0); strip(".scales", 1); strip(".biases", 2); strip(".bias", 3);    // (".biases" does not end in ".bias")
+  if (kind < 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  const int H = d.hidden_size;
+  if (kind != 3) {
+    if (base == "model.embed_tokens") return set_linear(e, e->embed, 0, H, kind, data, shape, ndim, dtype, on_device, name);
+    if (base == "lm_head") {
+      if (d.tie_word_embeddings) return fail(MI_ERR_NOTFOUND, "lm_head given but tie_word_embeddings is set: " + name);
+      return set_linear(e, e->lm_head, 0, H, kind, data, shape, ndim, dtype, on_device, name);
+    }
+    if (base == "model.norm" && kind == 0) return set_vector(e, e->final_norm, H, data, shape, ndim, dtype, on_device, name);
+  }
+  const std::string pre = "model.layers.";          // model.layers.<li>.<sub>
+  const size_t dot = base.compare(0, pre.size(), pre) == 0 ? base.find('.', pre.size()) : std::string::npos;
+  if (dot == std::string::npos) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  int li = -1;
+  try { li = std::stoi(base.substr(pre.size(), dot - pre.size())); } catch (...) { li = -1; }
+  if (li < 0 || li >= d.num_layers) return fail(MI_ERR_NOTFOUND, (kind == 3 ? "unknown tensor: " : "layer index out of range: ") + name);
+  const std::string sub = base.substr(dot + 1);
+  LayerW& l = e->layers[li];
+  Proj p;
+  if (find_proj(d, l, sub, &p)) {
+    if (kind != 3) return set_linear(e, *p.f, p.part, p.K, kind, data, shape, ndim, dtype, on_device, name);
+    // nn.Linear(bias=True): only where the model has one -- anything else is an unmatched tensor
+    if (p.attn ? d.attention_bias : d.mlp_bias) return set_bias(e, *p.f, p.part, data, shape, ndim, dtype, on_device, name);
+  } else if (kind == 0) {
+    if (sub == "input_layernorm") return set_vector(e, l.in_norm, H, data, shape, ndim, dtype, on_device, name);
+    if (sub == "post_attention_layernorm") return set_vector(e, l.post_norm, H, data, shape, ndim, dtype, on_device, name);
+    if (d.arch == MI_ARCH_QWEN3 && sub == "self_attn.q_norm") return set_vector(e, l.q_norm, d.head_dim, data, shape, ndim, dtype, on_device, name);
+    if (d.arch == MI_ARCH_QWEN3 && sub == "self_attn.k_norm") return set_vector(e, l.k_norm, d.head_dim, data, shape, ndim, dtype, on_device, name);
+  }
+  return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+}
+
+int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
+                       int dtype, int on_device) {
+  if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
+  if (layer < 0 || layer >= e->d.num_layers) return fail(MI_ERR_INVALID, "layer out of range");
+  if (rank < 1 || rank > 64) return fail(MI_ERR_UNSUPPORTED, "LoRA rank must be in [1,64]");
+  if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, "bad LoRA dtype");
+  if (dtype != MI_F32 && dtype != e->d.act_dtype) return fail(MI_ERR_UNSUPPORTED, "LoRA dtype must be float32 or the model dtype");
+  if (dtype != MI_F32) return fail(MI_ERR_UNSUPPORTED, "16-bit LoRA factors are not supported yet (float32 only)");
+  MI_HIP(hipSetDevice(e->device));
+  const mi_model_desc& d = e->d;
+  LayerW& l = e->layers[layer];
+  const std::string p(proj);
+  Proj pj;
+  if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the seven linears of a block only)");
+  FusedLinear* f = pj.f;
+  const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
+  int row0 = 0;
+  for (int i = 0; i < pj.part; ++i) row0 += f->part_rows[i];
+  // where the range goes: its own place when it is already adapted (hot-swap), else a free slot of LinearW, else -- q|k|v
+  // with both slots taken -- the third place beside it.  With all three adapted the third is ALWAYS k (a slot holding k
+  // hands it over), so that an engine computes the same bits whatever order the projections arrived in.
+  int slot = -1; bool third = false, move_k = false;
+  for (int i = 0; i < 2; ++i) if (f->lora_b[i] != nullptr && f->W.lora_row0[i] == row0) slot = i;   // hot-swap
+  if (slot < 0 && f->lora3.b != nullptr && f->lora3.row0 == row0) third = true;                      // hot-swap
+  if (slot < 0 && !third) for (int i = 0; i < 2; ++i) if (f->lora_b[i] == nullptr) { slot = i; break; }
+  if (slot < 0 && !third) {
+    if (f != &l.qkv || f->lora3.b != nullptr) return fail(MI_ERR_UNSUPPORTED, "no free place for another adapted range on this matrix");
+    if (row0 == QD) third = true;
+    else { slot = f->W.lora_row0[0] == QD ? 0 : 1; move_k = true; }
+  }
+  MI_HIP(hipStreamSynchronize(e->stream));
+  float* na = nullptr; float* nb = nullptr;
+  MI_HIP(hipMalloc(&na, (size_t)K * rank * sizeof(float)));
+  if (hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); hipFree(na); return fail(MI_ERR_RUNTIME, "LoRA: out of device memory"); }
+  int rc = copy_in(na, A, (size_t)K * rank * sizeof(float), on_device, e->stream);
+  if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
+  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
+  if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
+  if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
+  if (move_k) {           // k leaves its slot for the third place; the new range takes the slot
+    f->lora3.a = f->lora_a[slot]; f->lora3.b = f->lora_b[slot];
+    f->lora3.row0 = f->W.lora_row0[slot]; f->lora3.n = f->W.lora_n[slot]; f->lora3.rank = f->W.lora_rank[slot]; f->lora3.scale = f->W.lora_scale[slot];
+    f->lora_a[slot] = f->lora_b[slot] = nullptr;
+  }
+  if (third) {
+    hipFree(const_cast<float*>(f->lora3.a)); hipFree(const_cast<float*>(f->lora3.b));
+    f->lora3.a = na; f->lora3.b = nb; f->lora3.row0 = row0; f->lora3.n = n; f->lora3.rank = rank; f->lora3.scale = scale;
+  } else {
+    hipFree(f->lora_a[slot]); hipFree(f->lora_b[slot]);
+    f->lora_a[slot] = na; f->lora_b[slot] = nb;
+    f->W.lora_a[slot] = na; f->W.lora_b[slot] = nb;
+    f->W.lora_row0[slot] = row0; f->W.lora_n[slot] = n; f->W.lora_rank[slot] = rank; f->W.lora_scale[slot] = scale;
+  }
+  // an adapted gate|up never runs a SwiGLU epilogue again: its row-interleaved copy (ensure_gu8) is dead weight
+  if (f == &l.gate_up && f->w_gu8 != nullptr) { hipFree(f->w_gu8); f->w_gu8 = nullptr; }
+  return MI_OK;
+}
+
+int mi_engine_finalize(mi_engine* e) {
+  if (!e) return fail(MI_ERR_INVALID, "null engine");
+  if (e->finalized) return MI_OK;
+  MI_HIP(hipSetDevice(e->device));
+  const mi_model_desc& d = e->d;
+  const int H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  for (int i = 0; i < d.num_layers; ++i) {
+    LayerW& l = e->layers[i];
+    const std::string p = "model.layers." + std::to_string(i);
+    {   // a set bias flag makes the `.bias` of each of its projections a required tensor
+      const struct { const FusedLinear* f; int part; const char* sub; int32_t want; } req[7] = {
+          {&l.qkv, 0, ".self_attn.q_proj.bias", d.attention_bias}, {&l.qkv, 1, ".self_attn.k_proj.bias", d.attention_bias},
+          {&l.qkv, 2, ".self_attn.v_proj.bias", d.attention_bias}, {&l.o, 0, ".self_attn.o_proj.bias", d.attention_bias},
+          {&l.gate_up, 0, ".mlp.gate_proj.bias", d.mlp_bias}, {&l.gate_up, 1, ".mlp.up_proj.bias", d.mlp_bias},
+          {&l.down, 0, ".mlp.down_proj.bias", d.mlp_bias}};
+      for (const auto& r : req)
+        if (r.want && !r.f->seen_bias[r.part]) return fail(MI_ERR_NOTFOUND, p + r.sub + " not set");
+    }
+    if (d.rope_traditional) MI_TRY(permute_qk_heads(e, l.qkv));      // in front of the tile-major repack
+    MI_TRY(finalize_linear(e, l.qkv, H, p + ".self_attn.{q,k,v}_proj"));
+    MI_TRY(finalize_linear(e, l.o, QD, p + ".self_attn.o_proj"));
+    MI_TRY(finalize_linear(e, l.gate_up, H, p + ".mlp.{gate,up}_proj"));
+    MI_TRY(finalize_linear(e, l.down, d.intermediate_size, p + ".mlp.down_proj"));
+    if (!l.in_norm || !l.post_norm) return fail(MI_ERR_NOTFOUND, p + ": layernorm weights not set");
+    if (d.arch == MI_ARCH_QWEN3 && (!l.q_norm || !l.k_norm)) return fail(MI_ERR_NOTFOUND, p + ": q_norm/k_norm not set");
+    MI_TRY(make_f32_copy(e, l.in_norm, H, &l.in_norm32));
+    MI_TRY(make_f32_copy(e, l.post_norm, H, &l.post_norm32));
+    MI_TRY(make_f32_copy(e, l.q_norm, d.head_dim, &l.q_norm32));
+    MI_TRY(make_f32_copy(e, l.k_norm, d.head_dim, &l.k_norm32));
+    // persistent second copies, while mem_get_info still tells a scheduler the truth about what is left for its KV arena
+    (void)ensure_gu8(e, l.gate_up, d.intermediate_size);
+    if (d.act_dtype == MI_F16) { (void)ensure_hilo(e, l.qkv); (void)ensure_hilo(e, l.o); (void)ensure_hilo(e, l.gate_up); (void)ensure_hilo(e, l.down); }
+  }
+  MI_TRY(finalize_linear(e, e->embed, H, "model.embed_tokens"));
+  if (!d.tie_word_embeddings) MI_TRY(finalize_linear(e, e->lm_head, H, "lm_head"));
+  if (d.act_dtype == MI_F16) (void)ensure_hilo(e, d.tie_word_embeddings ? e->embed : e->lm_head);
+  if (!e->final_norm) return fail(MI_ERR_NOTFOUND, "model.norm.weight not set");
+  MI_TRY(make_f32_copy(e, e->final_norm, H, &e->final_norm32));
+  const size_t n = (size_t)d.max_positions * (d.head_dim / 2);
+  MI_HIP(hipMalloc(&e->cos_tab, n * sizeof(float)));
+  MI_HIP(hipMalloc(&e->sin_tab, n * sizeof(float)));
+  MI_TRY(launch_rope_tables(e->cos_tab, e->sin_tab, d.max_positions, d.head_dim, d.rope_theta, d.rope_scale, e->stream));
+  MI_HIP(hipStreamSynchronize(e->stream));
+  e->finalized = true;
+  return MI_OK;
+}
+
+}  // extern "C"

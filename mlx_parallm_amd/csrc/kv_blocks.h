@@ -1,0 +1,180 @@
+// kv_blocks.h -- the host side of a block-paged KV cache (mi_kv_create_paged): the block pool, the rows' block tables and the
+// prefix cache.  Standard library only: the device sees nothing but the table that engine_kv.hip uploads, and
+// tests/cpu/kv_blocks_test.cpp compiles this header alone, under the sanitizers.
+//
+// A row owns the blocks its table names, in order; block 0 is never handed out (unassigned table entries point at it, so a
+// clamped address is always mapped memory).  refcnt[b] = rows that map block b + 1 if the prefix cache holds it.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <list>
+#include <unordered_map>
+#include <vector>
+
+namespace mi {
+
+struct KvBlocks {
+  enum class Ensure { OK, TOO_LONG, EXHAUSTED };
+  int bs_shift = 0, nblocks = 0, bt_stride = 0;
+  std::vector<int32_t> h_btab;   // [rows][bt_stride]: what the device's table is a copy of (btab_dirty: since the last upload)
+  std::vector<int> row_blocks;   // blocks in use per row
+  std::vector<int> refcnt;
+  std::vector<int> free_blocks;
+  bool btab_dirty = false;
+  // prefix cache: full blocks of prompts, keyed by the hash of ALL tokens up to and including the block; an entry keeps
+  // the block's own tokens and its parent's key, so a hit is verified token by token (no reliance on the hash alone)
+  struct PrefixEntry { int block; uint64_t parent; std::vector<int32_t> tokens; std::list<uint64_t>::iterator lru_it; };
+  std::unordered_map<uint64_t, PrefixEntry> prefix;
+  std::list<uint64_t> lru;       // front = most recently used
+  int64_t stat_hit_tokens = 0, stat_lookup_tokens = 0, stat_evictions = 0;
+
+  // block_tokens: a power of two; the longest sequence of a row is bt_stride << bs_shift tokens
+  void init(int slots, int block_tokens, int n_blocks, int max_tokens_per_row) {
+    while ((1 << bs_shift) < block_tokens) ++bs_shift;
+    nblocks = n_blocks;
+    bt_stride = (max_tokens_per_row + block_tokens - 1) / block_tokens;
+    h_btab.assign((size_t)slots * bt_stride, 0);
+    row_blocks.assign(slots, 0);
+    refcnt.assign(n_blocks, 0);
+    for (int b = n_blocks - 1; b >= 1; --b) free_blocks.push_back(b);     // block 0 stays out of circulation
+  }
+
+  // the row's table covers `tokens` positions after this; a failure leaves the blocks the row already has
+  Ensure ensure(int row, int tokens) {
+    const int need = (tokens + (1 << bs_shift) - 1) >> bs_shift;
+    if (need > bt_stride) return Ensure::TOO_LONG;
+    while (row_blocks[row] < need) {
+      const int blk = take_block();
+      if (blk < 0) return Ensure::EXHAUSTED;
+      h_btab[(size_t)row * bt_stride + row_blocks[row]++] = blk;
+      btab_dirty = true;
+    }
+    return Ensure::OK;
+  }
+
+  void release_row(int row) {
+    for (int i = 0; i < row_blocks[row]; ++i) {
+      release_block(h_btab[(size_t)row * bt_stride + i]);
+      h_btab[(size_t)row * bt_stride + i] = 0;
+    }
+    if (row_blocks[row] > 0) btab_dirty = true;
+    row_blocks[row] = 0;
+  }
+
+  // An EMPTY row (the caller checks) maps the published blocks that its prompt of n tokens starts with; returns the tokens they
+  // hold.  Full blocks only, and at least one token of the prompt is left to run (its logits are needed).
+  int attach(int row, const int32_t* tokens, int n) {
+    const int bs = 1 << bs_shift;
+    uint64_t parent = 0;
+    int reused = 0;
+    std::vector<uint64_t> chain;
+    while (reused + bs <= n - 1 && row_blocks[row] < bt_stride) {
+      const uint64_t h = prefix_hash(parent, tokens + reused, bs);
+      auto it = prefix.find(h);
+      if (it == prefix.end() || !same_prefix(it->second, parent, tokens + reused)) break;
+      h_btab[(size_t)row * bt_stride + row_blocks[row]++] = it->second.block;
+      ++refcnt[it->second.block];
+      chain.push_back(h);
+      parent = h;
+      reused += bs;
+    }
+    lru_touch_chain(chain);
+    stat_lookup_tokens += n;
+    stat_hit_tokens += reused;
+    if (reused > 0) btab_dirty = true;
+    return reused;
+  }
+
+  // the full blocks of the row's first n tokens (all of them in its cache already: the caller checks) enter the prefix cache
+  void publish(int row, const int32_t* tokens, int n) {
+    const int bs = 1 << bs_shift;
+    uint64_t parent = 0;
+    std::vector<uint64_t> chain;
+    for (int i = 0; (i + 1) * bs <= n; ++i) {
+      const uint64_t h = prefix_hash(parent, tokens + i * bs, bs);
+      auto it = prefix.find(h);
+      if (it == prefix.end()) {
+        PrefixEntry pe;
+        pe.block = h_btab[(size_t)row * bt_stride + i]; pe.parent = parent; pe.tokens.assign(tokens + i * bs, tokens + (i + 1) * bs);
+        lru.push_front(h);
+        pe.lru_it = lru.begin();
+        ++refcnt[pe.block];                     // the cache's own reference: the block outlives the row
+        prefix.emplace(h, std::move(pe));
+      } else if (!same_prefix(it->second, parent, tokens + i * bs)) {
+        break;                                  // a different prefix owns this key: leave it (and everything behind it) alone
+      }
+      chain.push_back(h);
+      parent = h;
+    }
+    lru_touch_chain(chain);
+  }
+
+  void clear_prefix() {
+    for (auto& p : prefix) release_block(p.second.block);
+    prefix.clear();
+    lru.clear();
+  }
+
+  // free blocks | blocks in circulation (-1 each without a pool) | cached blocks | hit tokens | looked-up tokens | evictions |
+  // evictable: published blocks that only the cache holds -- what evict_one can actually give back
+  void stats(int64_t* out, int n) const {
+    int64_t evictable = 0;
+    for (const auto& pe : prefix) evictable += refcnt[pe.second.block] == 1 ? 1 : 0;
+    const int64_t v[7] = {nblocks > 0 ? (int64_t)free_blocks.size() : -1, nblocks > 0 ? (int64_t)nblocks - 1 : -1,
+                          (int64_t)prefix.size(), stat_hit_tokens, stat_lookup_tokens, stat_evictions, evictable};
+    for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
+  }
+
+ private:
+  static uint64_t prefix_hash(uint64_t parent, const int32_t* toks, int n) {
+    uint64_t h = parent ^ 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < n; ++i) { h ^= (uint64_t)(uint32_t)toks[i] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xD6E8FEB86659FD93ull; }
+    return h ? h : 1;
+  }
+  bool same_prefix(const PrefixEntry& pe, uint64_t parent, const int32_t* toks) const {
+    return pe.parent == parent && memcmp(pe.tokens.data(), toks, sizeof(int32_t) << bs_shift) == 0;
+  }
+
+  void release_block(int blk) {
+    if (blk <= 0) return;
+    if (--refcnt[blk] == 0) free_blocks.push_back(blk);
+  }
+
+  // A prefix chain is only reachable from its first block (attach stops at the first miss), so a chain is made "recent"
+  // leaf first: afterwards its root is the most recently used entry and its deepest block the oldest of the chain --
+  // eviction (from the back) takes leaves before their parents and never strands children behind a missing parent.
+  void lru_touch_chain(const std::vector<uint64_t>& chain) {
+    for (auto h = chain.rbegin(); h != chain.rend(); ++h) {
+      auto it = prefix.find(*h);
+      if (it == prefix.end()) continue;
+      lru.erase(it->second.lru_it);
+      lru.push_front(*h);
+      it->second.lru_it = lru.begin();
+    }
+  }
+
+  // a block nobody but the prefix cache holds can be taken back (least recently used first)
+  bool evict_one() {
+    for (auto it = lru.rbegin(); it != lru.rend(); ++it) {
+      auto pe = prefix.find(*it);
+      if (pe == prefix.end() || refcnt[pe->second.block] != 1) continue;
+      const int blk = pe->second.block;
+      lru.erase(pe->second.lru_it);
+      prefix.erase(pe);
+      release_block(blk);
+      ++stat_evictions;
+      return true;
+    }
+    return false;
+  }
+
+  int take_block() {
+    if (free_blocks.empty() && !evict_one()) return -1;
+    const int blk = free_blocks.back();
+    free_blocks.pop_back();
+    refcnt[blk] = 1;
+    return blk;
+  }
+};
+
+}  // namespace mi

@@ -117,7 +117,7 @@ def test_short_prefill_on_the_streaming_kernel(big):
     """A short prompt (dense weights: <= 64 rows, quantised: <= 96 / 128) goes through the decode steps' weight-streaming
     kernel (one read of W, split K) instead of the tile GEMM: same model, another summation order -- the logits agree to
     rounding noise with the tile-GEMM route (option short_prefill_skinny = 0), and it is the faster route at that size
-    (measured crossovers: gemv_rows in engine.hip)."""
+    (measured crossovers: the routes of gemv_rows in engine_linear.hip)."""
     import time
 
     eng, cfg = big
