@@ -307,10 +307,12 @@ int launch_attn_g(const AttnCall& c, hipStream_t st) {
   switch (G) {
     case 1: AK(1); break;
     case 2: AK(2); break;
+    case 3: AK(3); break;
     case 4: AK(4); break;
     case 5: AK(5); break;
+    case 6: AK(6); break;
     case 8: AK(8); break;
-    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8");
+    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
   }
 #undef AK
   MI_HIP(hipGetLastError());

@@ -1084,13 +1084,14 @@ int launch_mfma_gn(const AttnDecodeCall& c, hipStream_t st) {
     switch (c.s.Hq / c.s.Hkv) {
       case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
       case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
-      case 3: if constexpr (sizeof(T) == 4) return launch_mfma_g<T, D, 3, NORM>(c, st); else break;   // (float32 caches only)
+      case 3: return launch_mfma_g<T, D, 3, NORM>(c, st);
       case 4: return launch_mfma_g<T, D, 4, NORM>(c, st);
       case 5: return launch_mfma_g<T, D, 5, NORM>(c, st);
+      case 6: return launch_mfma_g<T, D, 6, NORM>(c, st);
       case 8: return launch_mfma_g<T, D, 8, NORM>(c, st);
     }
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8 (3: float32 caches, head_dim 64 / 128, matrix-core kernel only)");
+  return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
 }
 
 template <typename T, int D, bool NORM>
@@ -1106,10 +1107,12 @@ int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
   switch (s.Hq / s.Hkv) {
     case 1: DK(1); break;
     case 2: DK(2); break;
+    case 3: DK(3); break;
     case 4: DK(4); break;
     case 5: DK(5); break;
+    case 6: DK(6); break;
     case 8: DK(8); break;
-    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 4, 5 or 8 (3: float32 caches, head_dim 64 / 128, matrix-core kernel only)");
+    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
   }
 #undef DK
   MI_HIP(hipGetLastError());
@@ -1139,10 +1142,7 @@ int launch_d(const AttnDecodeCall& c, hipStream_t st) {
 bool attention_decode_supported(const AttnShape& s, int variant) {
   if (s.L != 1 || s.act != s.kv) return false;
   const int G = s.Hkv > 0 ? s.Hq / s.Hkv : 0;
-  // G = 3: the float32 matrix-core kernel (variant 0) alone has it (no VALU, prefill or unfused kernel takes it: the geometry
-  // is reachable through mi_op_attention_decode only, not through a model)
-  if (G == 3) return variant != 1 && s.act == MI_F32 && (s.D == 64 || s.D == 128);
-  if (!(G == 1 || G == 2 || G == 4 || G == 5 || G == 8)) return false;
+  if (!(G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8)) return false;
   if (s.act == MI_F32) return s.D == 16 || s.D == 32 || s.D == 64 || s.D == 128;
   return s.D == 32 || s.D == 64 || s.D == 128;
 }

@@ -477,11 +477,13 @@ int launch_pd(const AttnCall& c, hipStream_t st) {
   switch (c.s.Hq / c.s.Hkv) {
     case 1: return launch_pg<T, D, 1>(c, st);
     case 2: return launch_pg<T, D, 2>(c, st);
+    case 3: return launch_pg<T, D, 3>(c, st);
     case 4: return launch_pg<T, D, 4>(c, st);
     case 5: return launch_pg<T, D, 5>(c, st);
+    case 6: return launch_pg<T, D, 6>(c, st);
     case 8: return launch_pg<T, D, 8>(c, st);
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 4, 5 or 8");
+  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
 }
 
 template <typename T>
@@ -841,11 +843,13 @@ int launch_pd32(const AttnCall& c, hipStream_t st) {
   switch (c.s.Hq / c.s.Hkv) {
     case 1: return launch_pg32<D, 1>(c, st);
     case 2: return launch_pg32<D, 2>(c, st);
+    case 3: return launch_pg32<D, 3>(c, st);
     case 4: return launch_pg32<D, 4>(c, st);
     case 5: return launch_pg32<D, 5>(c, st);
+    case 6: return launch_pg32<D, 6>(c, st);
     case 8: return launch_pg32<D, 8>(c, st);
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 4, 5 or 8");
+  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
 }
 
 }  // namespace
@@ -854,7 +858,7 @@ bool attention_prefill_supported(const AttnShape& s) {
   if (s.L < 2 || s.act != s.kv) return false;
   if (s.Hkv <= 0 || s.Hq % s.Hkv != 0) return false;
   const int G = s.Hq / s.Hkv;
-  if (!(G == 1 || G == 2 || G == 4 || G == 5 || G == 8)) return false;
+  if (!(G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8)) return false;
   if (s.act == MI_F32) return s.D == 64 || s.D == 128;        // (s.rnd = logical rounding of the output, applied at the store)
   if ((s.act != MI_BF16 && s.act != MI_F16) || s.rnd != RND_NONE) return false;
   return s.D == 32 || s.D == 64 || s.D == 128;
