@@ -10,6 +10,7 @@
  * Reference op each one replaces (MLX call sites in the reference):
  *   mi_op_gemv        nn.Linear / nn.QuantizedLinear (+ fused RMSNorm / residual / SwiGLU):
  *                     llama.py:64-67,93,143,160-165,175-177,188-190,250-252; qwen3.py:37-40,63,115
+ *   mi_op_gemv_gu8    nn.silu(gate_proj(x)) * up_proj(x) on the row-interleaved gate|up copy: llama.py:160-165
  *   mi_op_embed       nn.Embedding / QuantizedEmbedding: llama.py:212; qwen3.py:166
  *   mi_op_rope_append q_norm/k_norm + nn.RoPE + cache.update_and_fetch:
  *                     qwen3.py:65-70; llama.py:107-125; base.py:66-85,119-140
@@ -86,6 +87,14 @@ typedef struct mi_op_attn_shape {
 
 int mi_op_gemv(const mi_op_linear* w, const mi_op_gemv_args* a);
 int mi_op_gemv_uses_mfma(const mi_op_linear* w, const mi_op_gemv_args* a);
+/* the SwiGLU launch of the decode GEMV on the row-interleaved gate|up copy (gemv_mfma.hip: gemv_mfma_gu8_kernel, what the
+ * engine runs for a dense 16-bit mlp.gate_proj | mlp.up_proj at 1..16 rows) on its own.  w: a tile-major dense bf16 / f16
+ * gate|up matrix of 2 x a->pair_offset rows, a->epi = MI_EPI_SWIGLU, the other fields of a as for mi_op_gemv; the
+ * row-interleaved copy (tile t = gate rows 8t..8t+7, then up rows 8t..8t+7) is made inside the call, as mi_op_gemv_f32 does.
+ * mi_op_gemv with MI_EPI_SWIGLU runs the paired-tile form instead.  MI_ERR_UNSUPPORTED, nothing launched: a bias, quantised
+ * or row-major weights, activations of another type than the weights, a->rnd != MI_RND_NONE, a->M outside 1..16,
+ * a->pair_offset % 16 != 0, w->N != 2 * a->pair_offset, a->ldx % 8 != 0, w->K % 32 != 0, another epilogue. */
+int mi_op_gemv_gu8(const mi_op_linear* w, const mi_op_gemv_args* a);
 /* launches the same call `iters` times back to back and returns the mean launch time (HIP events) */
 int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* the split-K weight-streaming GEMM the engine uses for decode steps of 9..128 rows (int4 / int8 weights: 1..128), on its own:

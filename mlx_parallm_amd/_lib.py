@@ -114,6 +114,7 @@ SIGNATURES = {
     # mi355_ops.h
     "mi_op_gemv": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs)]),
     "mi_op_gemv_uses_mfma": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs)]),
+    "mi_op_gemv_gu8": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs)]),
     "mi_op_gemv_bench": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_float)]),
     "mi_op_gemm_skinny": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.POINTER(C.c_int), C.c_int,
                                     C.POINTER(C.c_float)]),

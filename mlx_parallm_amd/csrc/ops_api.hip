@@ -7,6 +7,7 @@
 namespace mi {
 int launch_gemv(const LinearW& W, const GemvCall& c, hipStream_t st);
 bool gemv_mfma_supported(const LinearW& W, const GemvCall& c);
+int launch_gemv_mfma(const LinearW& W, const GemvCall& c, hipStream_t st);
 }  // namespace mi
 
 using namespace mi;
@@ -119,6 +120,26 @@ int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters,
   const LinearW W = to_linear(w);
   const GemvCall c = to_call(a);
   return run_timed_strict([&] { return launch_gemv(W, c, nullptr); }, iters, avg_ms);
+}
+
+// gemv_mfma.hip's launch on the row-interleaved gate|up copy (gemv_mfma_gu8_kernel) on its own: a->epi = MI_EPI_SWIGLU, w a
+// tile-major dense 16-bit gate|up matrix of 2 x a->pair_offset rows.  The copy is made here, as mi_engine_finalize does; what
+// the engine's gu8_wanted + gemv_mfma_supported would not take is refused, nothing launched.
+int mi_op_gemv_gu8(const mi_op_linear* w, const mi_op_gemv_args* a) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  LinearW W = to_linear(w);
+  GemvCall c = to_call(a);
+  const char* refusal = "mi_op_gemv_gu8: call not supported by this kernel";
+  GemvCall probe = c; probe.epi = EPI_SWIGLU_GU8;
+  const bool taken = c.epi == EPI_SWIGLU && W.bias == nullptr && W.layout == 1 && (W.wk == WK_BF16 || W.wk == WK_F16) &&
+                     c.pair_offset > 0 && c.pair_offset % 16 == 0 && W.N == 2 * c.pair_offset && gemv_mfma_supported(W, probe);
+  if (!taken) return fail(MI_ERR_UNSUPPORTED, refusal);
+  void* gu8 = nullptr;
+  FreeGuard guard{gu8};
+  MI_TRY(gate_up_interleaved(W, c, gu8, taken, refusal));
+  MI_TRY(launch_gemv_mfma(W, c, nullptr));
+  return finish();
 }
 
 // gemv_f32.hip on its own: float32 activations (a->rnd = MI_RND_NONE), a->M in 1..8, dense bf16 tile-major weights; plain,

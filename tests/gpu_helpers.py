@@ -88,6 +88,16 @@ def gemv_args(x, M, act, *, pro=0, norm_w=None, eps=0.0, epi=0, out=None, ldo=0,
     return a
 
 
+def gemv_gu8(ol: L.OpLinear, a: L.OpGemvArgs, check=True) -> int:
+    """mi_op_gemv_gu8: the SwiGLU launch of gemv_mfma.hip on the row-interleaved gate|up copy (made inside the call)
+    -> the return code when check is False."""
+    torch.cuda.synchronize()
+    rc = L.lib().mi_op_gemv_gu8(C.byref(ol), C.byref(a))
+    if check:
+        L.check(rc)
+    return rc
+
+
 def attn_shape(B, L_, Hq, Hkv, D, act, kv, rnd, cap) -> L.OpAttnShape:
     s = L.OpAttnShape()
     s.B, s.L, s.Hq, s.Hkv, s.D, s.act, s.kv, s.rnd, s.cap = B, L_, Hq, Hkv, D, MIDT[act], MIDT[kv], rnd, cap
