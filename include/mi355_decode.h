@@ -51,6 +51,7 @@ extern "C" {
 
 #define MI_ARCH_LLAMA 0 /* mlx_parallm/models/llama.py (also model_type "mistral": utils.py:33-36) */
 #define MI_ARCH_QWEN3 1 /* mlx_parallm/models/qwen3.py: + per-head q_norm/k_norm (qwen3.py:65-70) */
+#define MI_ARCH_PHI3 2 /* mlx_parallm/models/phi3.py */
 
 /* KV-cache element type selector for mi_kv_create */
 #define MI_KV_MODEL (-1) /* BatchedKVCache semantics: KV in the model dtype (models/base.py:66-85) */
@@ -138,7 +139,12 @@ void mi_engine_destroy(mi_engine* e);
  * desc.mlp_bias is set; with the flag off the name is unknown (MI_ERR_NOTFOUND), as the reference filters it.  `data` is a host
  * pointer (on_device = 0) or a device pointer on the engine's device (on_device = 1, e.g. a
  * torch tensor that was just filled by an RCCL broadcast); the bytes are COPIED.
- * Unknown names -> MI_ERR_NOTFOUND (the reference filters them, utils.py:693-698). */
+ * Unknown names -> MI_ERR_NOTFOUND (the reference filters them, utils.py:693-698).
+ * MI_ARCH_PHI3 (phi3.py:48-49,116): "self_attn.qkv_proj" holds q, then k, then v along the rows and "mlp.gate_up_proj" gate,
+ * then up; each is one tensor per ".weight" / ".scales" / ".biases" with all the rows (any other row count: MI_ERR_INVALID
+ * naming it), and the split names (q_proj, ..., up_proj) are unknown.  phi3.py has no linear biases and no tied head:
+ * desc.attention_bias, mlp_bias or tie_word_embeddings set is MI_ERR_INVALID at mi_engine_create; rope_traditional and
+ * rope_scale are those of MI_ARCH_LLAMA (phi3.py:73-81). */
 int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const int64_t* shape,
                          int ndim, int dtype, int on_device);
 
@@ -151,7 +157,10 @@ int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const
  * when it has one.  With desc.rope_traditional the columns of B of q_proj / k_proj are regrouped like the rows of the matrix
  * (the caller passes them in checkpoint order, also on a hot-swap).  May be called on a finalized, live engine: a projection
  * that is already adapted is hot-swapped, a new one is added; the outputs do not depend on the order in which the
- * projections arrived.  A refused call changes nothing. */
+ * projections arrived.  A refused call changes nothing.
+ * MI_ARCH_PHI3: proj is "self_attn.qkv_proj", "self_attn.o_proj", "mlp.gate_up_proj" or "mlp.down_proj", the names an
+ * adapter file of that family carries.  For the two fused ones A (K, r) is shared and B (r, N) is cut by columns into the
+ * parts: bit for bit what one call per part with its column slice gives on an engine with split projections. */
 int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B,
                        int rank, float scale, int dtype, int on_device);
 

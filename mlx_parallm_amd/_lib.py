@@ -16,7 +16,7 @@ LIB_PATH = Path(os.environ.get("MLX_PARALLM_AMD_LIB") or (CSRC / "libmi355_decod
 # dtype / enum constants (mirror of the headers)
 MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
 MI_KV_MODEL = -1
-MI_ARCH_LLAMA, MI_ARCH_QWEN3 = 0, 1
+MI_ARCH_LLAMA, MI_ARCH_QWEN3, MI_ARCH_PHI3 = 0, 1, 2
 MI_MAX_TOP_LOGPROBS = 20
 MI_MAX_ROW_LOGIT_BIAS = 1024
 MI_ABI_VERSION = 4

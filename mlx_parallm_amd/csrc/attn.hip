@@ -37,6 +37,20 @@ __device__ __forceinline__ void load_row_piece(const T* p, float (&o)[N]) {
     const T* e = (const T*)&v;
 #pragma unroll
     for (int j = 0; j < N; ++j) o[j] = (float)e[j];
+  } else if constexpr (BYTES == 24) {             // head_dim 96, float32: a lane's 6 elements, 8-byte aligned
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const u32x2 v = *((const u32x2*)p + i);
+      const T* e = (const T*)&v;
+#pragma unroll
+      for (int j = 0; j < 8 / (int)sizeof(T); ++j) o[i * (8 / sizeof(T)) + j] = (float)e[j];
+    }
+  } else if constexpr (BYTES == 12) {             // head_dim 96, 16-bit: 6 elements, 4-byte aligned
+    struct W3 { uint32_t a, b, c; };
+    const W3 v = *(const W3*)p;
+    const T* e = (const T*)&v;
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] = (float)e[j];
   } else {
 #pragma unroll
     for (int j = 0; j < N; ++j) o[j] = (float)p[j];
@@ -304,6 +318,14 @@ int launch_attn_g(const AttnCall& c, hipStream_t st) {
   const int G = s.Hq / s.Hkv;
 #define AK(GV) do { if (s.btab) hipLaunchKernelGGL((attn_kernel<AT, KT, D, GV, true>), grid, block, 0, st, c); \
                     else hipLaunchKernelGGL((attn_kernel<AT, KT, D, GV, false>), grid, block, 0, st, c); } while (0)
+  if constexpr (D == 96) {                        // Phi-3's width: the groups the other attention kernels serve at it
+    switch (G) {
+      case 1: AK(1); break;
+      case 2: AK(2); break;
+      case 4: AK(4); break;
+      default: return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
+    }
+  } else {
   switch (G) {
     case 1: AK(1); break;
     case 2: AK(2); break;
@@ -313,6 +335,7 @@ int launch_attn_g(const AttnCall& c, hipStream_t st) {
     case 6: AK(6); break;
     case 8: AK(8); break;
     default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
+  }
   }
 #undef AK
   MI_HIP(hipGetLastError());
@@ -330,9 +353,10 @@ int launch_attn_d(const AttnCall& c, hipStream_t st) {
     case 16: return launch_attn_g<AT, KT, 16>(c, st);
     case 32: return launch_attn_g<AT, KT, 32>(c, st);
     case 64: return launch_attn_g<AT, KT, 64>(c, st);
+    case 96: return launch_attn_g<AT, KT, 96>(c, st);
     case 128: return launch_attn_g<AT, KT, 128>(c, st);
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention: head_dim must be 16, 32, 64 or 128");
+  return fail(MI_ERR_UNSUPPORTED, "attention: head_dim must be 16, 32, 64, 96 or 128");
 }
 
 

@@ -73,6 +73,16 @@ __device__ __forceinline__ void load_raw(const void* p, uint32_t (&o)[NW32]) {
   } else if constexpr (NW32 == 2) {
     const u32x2 v = *(const u32x2*)p;
     o[0] = v.x; o[1] = v.y;
+  } else if constexpr (NW32 == 6) {               // head_dim 96, float32: 24 bytes, 8-byte aligned
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const u32x2 v = *((const u32x2*)p + i);
+      o[2 * i] = v.x; o[2 * i + 1] = v.y;
+    }
+  } else if constexpr (NW32 == 3) {               // head_dim 96, 16-bit: 12 bytes, 4-byte aligned (one global_load_dwordx3)
+    struct W3 { uint32_t a, b, c; };
+    const W3 v = *(const W3*)p;
+    o[0] = v.a; o[1] = v.b; o[2] = v.c;
   } else {
 #pragma unroll
     for (int i = 0; i < NW32; ++i) o[i] = ((const uint32_t*)p)[i];
@@ -423,6 +433,7 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecodeCall c) {
 //   * lane (c16 = head, g) ends up with O[head][16 dt + 4g + r]; the online-softmax rescale is a per-
 //     lane scalar.  Waves, the new key and the splits are merged as in the VALU kernel.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
@@ -520,12 +531,16 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   AT_STAMP(0);
   static_assert(!QS || sizeof(T) == 4, "partial q|k|v rows: float32 activations");
   constexpr bool F32 = sizeof(T) == 4;           // float32 q / caches / outputs, multiplied exactly on v_mfma_f32_16x16x4_f32
-  static_assert(D % 32 == 0 && D <= 128 && G <= 8 && (!F32 || D % 64 == 0), "16-bit caches: head_dim 32/64/96/128; float32: 64/128");
+  constexpr bool BLK = sizeof(T) == 4 && G <= 4; // float32, at most 4 query heads per kv head: the 16-block MFMA loop
+  static_assert(D % 32 == 0 && D <= 128 && G <= 8 && (!F32 || D % 64 == 0 || (D == 96 && BLK && !QS)),
+                "16-bit caches: head_dim 32/64/96/128; float32: 64/128, and 96 in the 16-block form");
   constexpr int EPL = D / 16, NW32 = EPL * (int)sizeof(T) / 4, NTH = NWV * 64;
   constexpr int KK = D / 32, DT = D / 16, NV = (32 * D * 2) / (64 * 16);   // K steps, 16-d tiles, 16-B V loads per lane
   constexpr int KPW = F32 ? 16 : 32;             // keys per wave and round
   constexpr int NP = D / 16, NH = D / 64 > 0 ? D / 64 : 1;   // float32: 16-byte K pieces per lane and tile, 64-d halves of a V row
-  constexpr bool BLK = F32 && G <= 4;            // float32, at most 4 query heads per kv head: the 16-block MFMA loop
+  // float32, head_dim 96: behind the one 64-d half a row has 32 more floats, 8 bytes per lane: lane (c16, g4) loads
+  // V[key 4 g4 + r][64 + 2 c16 .. + 1], two more A tiles (e < 2) whose row c16 is d = 64 + 2 c16 + e -- accO[4], accO[5]
+  constexpr bool VT = F32 && D % 64 == 32;
   constexpr float LOG2E = 1.4426950408889634f;
   const AttnShape& s = c.s;
   const int split = blockIdx.x, bh = blockIdx.y;
@@ -559,6 +574,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   // ---- the K fragments and V rows of the first round go out before anything else
   u32x4 kf[F32 ? 1 : 2][F32 ? 1 : KK], vrow[F32 ? 1 : NV];
   f32x4 kf32[F32 ? NP : 1], vv32[F32 ? 4 : 1][F32 ? NH : 1];
+  f32x2 vt32[VT ? 4 : 1];
   const int klast = max(send - 1, 0);            // every address is clamped to a valid row: no load sits under a branch
   auto issue_k = [&](int base) {                 // keys base + KPW wave + [0, KPW)
     const int k0 = base + KPW * wave;
@@ -586,6 +602,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
         const size_t ro = kv_elem<PAGED>(s, kb, kh, key);
 #pragma unroll
         for (int h = 0; h < NH; ++h) vv32[r][h] = *(const f32x4*)(vc + ro + 64 * h + 4 * c16);
+        if constexpr (VT) vt32[r] = *(const f32x2*)(vc + ro + 64 * NH + 2 * c16);
       }
     } else {                                     // 32 keys x (D/8) 16-byte pieces, lane-linear: piece = i * 64 + lane
 #pragma unroll
@@ -642,7 +659,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
   }
   uint32_t r0[NW32];
   if constexpr (NORM) load_raw<NW32>((const T*)(is_k ? c.k_norm_w : c.q_norm_w) + li * EPL, r0);
-  constexpr int KV_BEHIND = PRO_FIRST ? NP + 4 * NH : 0;   // K / V loads per lane of a float32 round, in the queue behind the prologue's
+  constexpr int KV_BEHIND = PRO_FIRST ? NP + 4 * NH + (VT ? 4 : 0) : 0;   // K / V loads per lane of a float32 round, in the queue behind the prologue's
   if constexpr (PRO_FIRST) {
     __builtin_amdgcn_sched_barrier(0);
     issue_k(s0);
@@ -820,6 +837,12 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
         for (int h = 0; h < NH; ++h)
 #pragma unroll
           for (int e = 0; e < 4; ++e) accO[h * 4 + e] = mfma_blk(pa[r], vv32[r][h][e], accO[h * 4 + e]);
+      if constexpr (VT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) accO[NH * 4 + e] = mfma_blk(pa[r], vt32[r][e], accO[NH * 4 + e]);
+      }
       __builtin_amdgcn_sched_barrier(0);
       if (more) issue_v(base + KPW * NWV);
       __builtin_amdgcn_sched_barrier(0);
@@ -941,11 +964,11 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     // the same reduce-scatter over the lane groups for O: group g4 is left with O[head g4][64 h + 4 c16 + e], 16 bytes per h
     const bool gb0 = (g4 & 1) != 0, gb1 = (g4 & 2) != 0;
     l_run = row16_sum(l_run);
-    f32x4 oh[NH];
+    f32x4 oh[NH + (VT ? 1 : 0)];                  // (head_dim 96: the 8-byte tail in oh[NH][0], oh[NH][1])
 #pragma unroll
-    for (int h = 0; h < NH; ++h)
+    for (int h = 0; h < NH + (VT ? 1 : 0); ++h)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
+      for (int e = 0; e < (h < NH ? 4 : 2); ++e) {
         const f32x4 a = accO[h * 4 + e];
         float k0v = gb1 ? a[2] : a[0], k1v = gb1 ? a[3] : a[1];
         k0v += __shfl_xor(gb1 ? a[0] : a[2], 32, 64);
@@ -956,6 +979,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
       if (c16 == 0) { st_m[wave * G + g4] = m_run; st_l[wave * G + g4] = l_run; }
 #pragma unroll
       for (int h = 0; h < NH; ++h) *(f32x4*)(st_o + (size_t)(wave * G + g4) * D + 64 * h + 4 * c16) = oh[h];
+      if constexpr (VT) *(f32x2*)(st_o + (size_t)(wave * G + g4) * D + 64 * NH + 2 * c16) = f32x2{oh[NH][0], oh[NH][1]};
     }
   } else {
   l_run += __shfl_xor(l_run, 16, 64);
@@ -1045,7 +1069,9 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
                                              c.qkv_pub != nullptr ? -3 : -2, c.counters != nullptr ? 1 : 0, s.act);
 #endif
   if (c.qkv_pub != nullptr) {
-    if constexpr (sizeof(T) == 4) {
+    if constexpr (sizeof(T) == 4 && D % 64 != 0) {     // head_dim 96: the engine makes no such offer (engine.hip, cc_attn)
+      return fail(MI_ERR_UNSUPPORTED, "attention_decode: partial q|k|v rows need head_dim 64 or 128");
+    } else if constexpr (sizeof(T) == 4) {
       if (c.qkv_pub_sq == nullptr || c.qkv_ksplit < 2 || c.qkv_ksplit > 8 || s.B > 8 || c.hidden_k <= 0)
         return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need 2..8 K slices and at most 8 sequences");
       constexpr size_t lds = attn_mfma_lds_total<G, D, 4>();
@@ -1075,12 +1101,24 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
   return MI_OK;
 }
 
+// head_dim 96 (Phi-3): Hq/Hkv 1, 2 and 4 only, in every kernel of this file; the float32 matrix-core kernel has it in its
+// 16-block form (G <= 4), which those three groups all take
 template <typename T, int D>
-constexpr bool attn_mfma_ok() { return (sizeof(T) == 2 && D % 32 == 0) || (sizeof(T) == 4 && D % 64 == 0); }
+constexpr bool attn_mfma_ok() { return (sizeof(T) == 2 && D % 32 == 0) || (sizeof(T) == 4 && (D % 64 == 0 || D == 96)); }
+constexpr bool attn_group_ok(int D, int G) {
+  return D == 96 ? (G == 1 || G == 2 || G == 4) : (G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8);
+}
 
 template <typename T, int D, bool NORM>
 int launch_mfma_gn(const AttnDecodeCall& c, hipStream_t st) {
-  if constexpr (attn_mfma_ok<T, D>()) {
+  if constexpr (D == 96) {
+    switch (c.s.Hq / c.s.Hkv) {
+      case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
+      case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
+      case 4: return launch_mfma_g<T, D, 4, NORM>(c, st);
+    }
+    return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
+  } else if constexpr (attn_mfma_ok<T, D>()) {
     switch (c.s.Hq / c.s.Hkv) {
       case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
       case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
@@ -1104,6 +1142,14 @@ int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
   const dim3 grid(c.nsplit, s.B * s.Hkv), block(512);
 #define DK(GV) do { if (s.btab) hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, true>), grid, block, 0, st, c); \
                     else hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, false>), grid, block, 0, st, c); } while (0)
+  if constexpr (D == 96) {
+    switch (s.Hq / s.Hkv) {
+      case 1: DK(1); break;
+      case 2: DK(2); break;
+      case 4: DK(4); break;
+      default: return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
+    }
+  } else {
   switch (s.Hq / s.Hkv) {
     case 1: DK(1); break;
     case 2: DK(2); break;
@@ -1113,6 +1159,7 @@ int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
     case 6: DK(6); break;
     case 8: DK(8); break;
     default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
+  }
   }
 #undef DK
   MI_HIP(hipGetLastError());
@@ -1132,6 +1179,7 @@ int launch_d(const AttnDecodeCall& c, hipStream_t st) {
     case 16: if constexpr (sizeof(T) == 4) return launch_g<T, 16>(c, st); break;
     case 32: return launch_g<T, 32>(c, st);
     case 64: return launch_g<T, 64>(c, st);
+    case 96: return launch_g<T, 96>(c, st);
     case 128: return launch_g<T, 128>(c, st);
   }
   return fail(MI_ERR_UNSUPPORTED, "attention_decode: head_dim not supported by the fused kernel");
@@ -1142,9 +1190,9 @@ int launch_d(const AttnDecodeCall& c, hipStream_t st) {
 bool attention_decode_supported(const AttnShape& s, int variant) {
   if (s.L != 1 || s.act != s.kv) return false;
   const int G = s.Hkv > 0 ? s.Hq / s.Hkv : 0;
-  if (!(G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8)) return false;
-  if (s.act == MI_F32) return s.D == 16 || s.D == 32 || s.D == 64 || s.D == 128;
-  return s.D == 32 || s.D == 64 || s.D == 128;
+  if (!attn_group_ok(s.D, G)) return false;
+  if (s.act == MI_F32) return s.D == 16 || s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;
+  return s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;
 }
 
 int launch_attention_decode(const AttnDecodeCall& c, hipStream_t st) {

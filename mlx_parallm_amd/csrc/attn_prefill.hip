@@ -474,6 +474,14 @@ int launch_pg(const AttnCall& c, hipStream_t st) {
 
 template <typename T, int D>
 int launch_pd(const AttnCall& c, hipStream_t st) {
+  if constexpr (D == 96) {                            // (attention_prefill_supported admits Hq/Hkv 1, 2 and 4 at this width)
+    switch (c.s.Hq / c.s.Hkv) {
+      case 1: return launch_pg<T, D, 1>(c, st);
+      case 2: return launch_pg<T, D, 2>(c, st);
+      case 4: return launch_pg<T, D, 4>(c, st);
+    }
+    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
+  } else
   switch (c.s.Hq / c.s.Hkv) {
     case 1: return launch_pg<T, D, 1>(c, st);
     case 2: return launch_pg<T, D, 2>(c, st);
@@ -491,9 +499,10 @@ int launch_pt(const AttnCall& c, hipStream_t st) {
   switch (c.s.D) {
     case 32: return launch_pd<T, 32>(c, st);
     case 64: return launch_pd<T, 64>(c, st);
+    case 96: return launch_pd<T, 96>(c, st);
     case 128: return launch_pd<T, 128>(c, st);
   }
-  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim must be 32, 64 or 128");
+  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim must be 32, 64, 96 or 128");
 }
 
 
@@ -832,6 +841,8 @@ int launch_pg32(const AttnCall& c, hipStream_t st) {
   if (env == nullptr || atoi(env) == 0) {
     if (s.btab) hipLaunchKernelGGL((attn_prefill_f32s_kernel<D, G, true>), grid, block, 0, st, c);
     else hipLaunchKernelGGL((attn_prefill_f32s_kernel<D, G, false>), grid, block, 0, st, c);
+  } else if constexpr (D % 64 != 0) {                 // the exact form's V image is made of 64-wide halves of a row
+    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: the exact float32 form needs head_dim 64 or 128");
   } else if (s.btab) hipLaunchKernelGGL((attn_prefill_f32_kernel<D, G, true>), grid, block, 0, st, c);
   else hipLaunchKernelGGL((attn_prefill_f32_kernel<D, G, false>), grid, block, 0, st, c);
   MI_HIP(hipGetLastError());
@@ -840,6 +851,14 @@ int launch_pg32(const AttnCall& c, hipStream_t st) {
 
 template <int D>
 int launch_pd32(const AttnCall& c, hipStream_t st) {
+  if constexpr (D == 96) {
+    switch (c.s.Hq / c.s.Hkv) {
+      case 1: return launch_pg32<D, 1>(c, st);
+      case 2: return launch_pg32<D, 2>(c, st);
+      case 4: return launch_pg32<D, 4>(c, st);
+    }
+    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
+  } else
   switch (c.s.Hq / c.s.Hkv) {
     case 1: return launch_pg32<D, 1>(c, st);
     case 2: return launch_pg32<D, 2>(c, st);
@@ -859,15 +878,16 @@ bool attention_prefill_supported(const AttnShape& s) {
   if (s.Hkv <= 0 || s.Hq % s.Hkv != 0) return false;
   const int G = s.Hq / s.Hkv;
   if (!(G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8)) return false;
-  if (s.act == MI_F32) return s.D == 64 || s.D == 128;        // (s.rnd = logical rounding of the output, applied at the store)
+  if (s.D == 96 && !(G == 1 || G == 2 || G == 4)) return false;
+  if (s.act == MI_F32) return s.D == 64 || s.D == 96 || s.D == 128;   // (s.rnd = logical rounding of the output, applied at the store)
   if ((s.act != MI_BF16 && s.act != MI_F16) || s.rnd != RND_NONE) return false;
-  return s.D == 32 || s.D == 64 || s.D == 128;
+  return s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;
 }
 
 int launch_attention_prefill(const AttnCall& c, hipStream_t st) {
   if (!attention_prefill_supported(c.s)) return fail(MI_ERR_UNSUPPORTED, "attention_prefill: shape / dtype not supported");
   if (c.nsplit != 1) return fail(MI_ERR_INVALID, "attention_prefill: no split-KV");
-  if (c.s.act == MI_F32) return c.s.D == 128 ? launch_pd32<128>(c, st) : launch_pd32<64>(c, st);
+  if (c.s.act == MI_F32) return c.s.D == 128 ? launch_pd32<128>(c, st) : c.s.D == 96 ? launch_pd32<96>(c, st) : launch_pd32<64>(c, st);
   return c.s.act == MI_BF16 ? launch_pt<bf16>(c, st) : launch_pt<f16>(c, st);
 }
 

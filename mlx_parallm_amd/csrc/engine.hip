@@ -414,7 +414,9 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     return fail(MI_ERR_INVALID, "mi_model_desc.struct_size = " + std::to_string(desc->struct_size) + ", this library (ABI " +
                                     std::to_string(MI_ABI_VERSION) + ") expects " + std::to_string(sizeof(mi_model_desc)));
   const mi_model_desc& d = *desc;
-  if (d.arch != MI_ARCH_LLAMA && d.arch != MI_ARCH_QWEN3) return fail(MI_ERR_UNSUPPORTED, "unsupported arch");
+  if (d.arch != MI_ARCH_LLAMA && d.arch != MI_ARCH_QWEN3 && d.arch != MI_ARCH_PHI3) return fail(MI_ERR_UNSUPPORTED, "unsupported arch");
+  if (d.arch == MI_ARCH_PHI3 && (d.attention_bias || d.mlp_bias || d.tie_word_embeddings))
+    return fail(MI_ERR_INVALID, "arch phi3 has neither linear biases nor a tied lm_head (attention_bias, mlp_bias, tie_word_embeddings must be 0)");
   if (d.hidden_size <= 0 || d.num_layers <= 0 || d.num_heads <= 0 || d.num_kv_heads <= 0 || d.head_dim <= 0 ||
       d.intermediate_size <= 0 || d.vocab_size <= 0 || d.max_positions <= 0)
     return fail(MI_ERR_INVALID, "model dimensions must be positive");

@@ -61,6 +61,26 @@ int set_linear(mi_engine* e, FusedLinear& f, int part, int K, int kind, const vo
   return MI_OK;
 }
 
+// MI_ARCH_PHI3: a checkpoint's fused matrix (phi3.py: qkv_proj = q, then k, then v along the rows; gate_up_proj = gate, then
+// up) stored as the parts of f.  Dense rows, or the rows of codes / scales / quantisation biases: groups run along K, so
+// whole rows move.
+int set_linear_fused(mi_engine* e, FusedLinear& f, int K, int kind, const void* data, const int64_t* shape,
+                     int ndim, int dtype, int on_device, const std::string& name) {
+  if (ndim != 2) return fail(MI_ERR_INVALID, name + ": expected a 2-D tensor");
+  int total = 0;
+  for (int i = 0; i < f.n_parts; ++i) total += f.part_rows[i];
+  if (shape[0] != total) return fail(MI_ERR_INVALID, name + ": wrong number of rows (the fused matrix has " + std::to_string(total) + ")");
+  if (shape[1] <= 0 || dtype_size(dtype) == 0) return fail(MI_ERR_INVALID, name + ": bad shape or dtype");
+  const size_t row_bytes = (size_t)shape[1] * dtype_size(dtype);
+  size_t row0 = 0;
+  for (int i = 0; i < f.n_parts; ++i) {
+    const int64_t sub[2] = {f.part_rows[i], shape[1]};
+    MI_TRY(set_linear(e, f, i, K, kind, (const char*)data + row0 * row_bytes, sub, 2, dtype, on_device, name));
+    row0 += f.part_rows[i];
+  }
+  return MI_OK;
+}
+
 int set_vector(mi_engine* e, void*& dst, int n, const void* data, const int64_t* shape, int ndim, int dtype,
                int on_device, const std::string& name) {
   if (ndim != 1 || shape[0] != n) return fail(MI_ERR_INVALID, name + ": wrong shape");
@@ -158,10 +178,19 @@ int make_f32_copy(mi_engine* e, const void* src, int n, void** dst) {
   return launch_convert(src, e->d.act_dtype, *dst, MI_F32, (size_t)n, e->stream);
 }
 
-// one of the seven linears of a block by its checkpoint name: the fused matrix, the part of it, its K, attention or MLP
+// one of the seven linears of a block by its checkpoint name: the fused matrix, the part of it, its K, attention or MLP.
+// MI_ARCH_PHI3 names q|k|v and gate|up as one linear each (part -1: every part of f); the split names are unknown there.
 struct Proj { FusedLinear* f; int part, K; bool attn; };
 bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* p) {
   const int H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  if (d.arch == MI_ARCH_PHI3) {
+    if (sub == "self_attn.qkv_proj") *p = {&l.qkv, -1, H, true};
+    else if (sub == "mlp.gate_up_proj") *p = {&l.gate_up, -1, H, false};
+    else if (sub == "self_attn.o_proj") *p = {&l.o, 0, QD, true};
+    else if (sub == "mlp.down_proj") *p = {&l.down, 0, d.intermediate_size, false};
+    else return false;
+    return true;
+  }
   if (sub == "self_attn.q_proj") *p = {&l.qkv, 0, H, true};
   else if (sub == "self_attn.k_proj") *p = {&l.qkv, 1, H, true};
   else if (sub == "self_attn.v_proj") *p = {&l.qkv, 2, H, true};
@@ -217,6 +246,7 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
   LayerW& l = e->layers[li];
   Proj p;
   if (find_proj(d, l, sub, &p)) {
+    if (kind != 3 && p.part < 0) return set_linear_fused(e, *p.f, p.K, kind, data, shape, ndim, dtype, on_device, name);
     if (kind != 3) return set_linear(e, *p.f, p.part, p.K, kind, data, shape, ndim, dtype, on_device, name);
     // nn.Linear(bias=True): only where the model has one -- anything else is an unmatched tensor
     if (p.attn ? d.attention_bias : d.mlp_bias) return set_bias(e, *p.f, p.part, data, shape, ndim, dtype, on_device, name);
@@ -229,20 +259,9 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
   return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
 }
 
-int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
-                       int dtype, int on_device) {
-  if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
-  if (layer < 0 || layer >= e->d.num_layers) return fail(MI_ERR_INVALID, "layer out of range");
-  if (rank < 1 || rank > 64) return fail(MI_ERR_UNSUPPORTED, "LoRA rank must be in [1,64]");
-  if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, "bad LoRA dtype");
-  if (dtype != MI_F32 && dtype != e->d.act_dtype) return fail(MI_ERR_UNSUPPORTED, "LoRA dtype must be float32 or the model dtype");
-  if (dtype != MI_F32) return fail(MI_ERR_UNSUPPORTED, "16-bit LoRA factors are not supported yet (float32 only)");
-  MI_HIP(hipSetDevice(e->device));
+// one adapted range: part pj.part of pj.f, float32 factors A (K, rank) and B (rank, the part's rows)
+static int set_lora_part(mi_engine* e, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
   const mi_model_desc& d = e->d;
-  LayerW& l = e->layers[layer];
-  const std::string p(proj);
-  Proj pj;
-  if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the seven linears of a block only)");
   FusedLinear* f = pj.f;
   const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
   int row0 = 0;
@@ -287,6 +306,47 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
   return MI_OK;
 }
 
+int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
+                       int dtype, int on_device) {
+  if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
+  if (layer < 0 || layer >= e->d.num_layers) return fail(MI_ERR_INVALID, "layer out of range");
+  if (rank < 1 || rank > 64) return fail(MI_ERR_UNSUPPORTED, "LoRA rank must be in [1,64]");
+  if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, "bad LoRA dtype");
+  if (dtype != MI_F32 && dtype != e->d.act_dtype) return fail(MI_ERR_UNSUPPORTED, "LoRA dtype must be float32 or the model dtype");
+  if (dtype != MI_F32) return fail(MI_ERR_UNSUPPORTED, "16-bit LoRA factors are not supported yet (float32 only)");
+  MI_HIP(hipSetDevice(e->device));
+  const mi_model_desc& d = e->d;
+  LayerW& l = e->layers[layer];
+  const std::string p(proj);
+  Proj pj;
+  if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the linears of a block only)");
+  if (pj.part >= 0) return set_lora_part(e, l, pj, A, B, rank, scale, on_device);
+  // MI_ARCH_PHI3, qkv_proj / gate_up_proj: A is shared, B (rank, N) is cut by columns into the parts -- what one call per
+  // part with the column slice does on an engine with split projections
+  int N = 0;
+  for (int i = 0; i < pj.f->n_parts; ++i) N += pj.f->part_rows[i];
+  std::vector<float> hb((size_t)rank * N), slice;
+  MI_HIP(hipMemcpy(hb.data(), B, hb.size() * sizeof(float), on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+  int col0 = 0;
+  for (int i = 0; i < pj.f->n_parts; ++i) {
+    const int n = pj.f->part_rows[i];
+    slice.resize((size_t)rank * n);
+    for (int r = 0; r < rank; ++r) memcpy(&slice[(size_t)r * n], &hb[(size_t)r * N + col0], (size_t)n * sizeof(float));
+    float* sb = slice.data();
+    void* db = nullptr;
+    if (on_device) {                               // (A stays where it is: the slice goes where A is)
+      MI_HIP(hipMalloc(&db, slice.size() * sizeof(float)));
+      if (hipMemcpy(db, sb, slice.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(db); return fail(MI_ERR_RUNTIME, "LoRA: copying a column slice failed"); }
+    }
+    const Proj part{pj.f, i, pj.K, pj.attn};
+    const int rc = set_lora_part(e, l, part, A, on_device ? db : (const void*)sb, rank, scale, on_device);
+    hipFree(db);
+    MI_TRY(rc);
+    col0 += n;
+  }
+  return MI_OK;
+}
+
 int mi_engine_finalize(mi_engine* e) {
   if (!e) return fail(MI_ERR_INVALID, "null engine");
   if (e->finalized) return MI_OK;
@@ -306,9 +366,9 @@ int mi_engine_finalize(mi_engine* e) {
         if (r.want && !r.f->seen_bias[r.part]) return fail(MI_ERR_NOTFOUND, p + r.sub + " not set");
     }
     if (d.rope_traditional) MI_TRY(permute_qk_heads(e, l.qkv));      // in front of the tile-major repack
-    MI_TRY(finalize_linear(e, l.qkv, H, p + ".self_attn.{q,k,v}_proj"));
+    MI_TRY(finalize_linear(e, l.qkv, H, p + (d.arch == MI_ARCH_PHI3 ? ".self_attn.qkv_proj" : ".self_attn.{q,k,v}_proj")));
     MI_TRY(finalize_linear(e, l.o, QD, p + ".self_attn.o_proj"));
-    MI_TRY(finalize_linear(e, l.gate_up, H, p + ".mlp.{gate,up}_proj"));
+    MI_TRY(finalize_linear(e, l.gate_up, H, p + (d.arch == MI_ARCH_PHI3 ? ".mlp.gate_up_proj" : ".mlp.{gate,up}_proj")));
     MI_TRY(finalize_linear(e, l.down, d.intermediate_size, p + ".mlp.down_proj"));
     if (!l.in_norm || !l.post_norm) return fail(MI_ERR_NOTFOUND, p + ": layernorm weights not set");
     if (d.arch == MI_ARCH_QWEN3 && (!l.q_norm || !l.k_norm)) return fail(MI_ERR_NOTFOUND, p + ": q_norm/k_norm not set");

@@ -248,24 +248,31 @@ class Engine:
     def __init__(self, config: dict, device: int = 0, max_positions: Optional[int] = None,
                  act_dtype: str = "bfloat16"):
         mt = {"mistral": "llama"}.get(config["model_type"], config["model_type"])   # utils.py:33-36
-        if mt not in ("llama", "qwen3"):
+        if mt not in ("llama", "qwen3", "phi3"):
             raise ValueError(f"Model type {config['model_type']} not supported.")    # utils.py:62-65
         nh = int(config["num_attention_heads"])
         d = L.ModelDesc()
         d.struct_size = C.sizeof(L.ModelDesc)
-        d.arch = L.MI_ARCH_QWEN3 if mt == "qwen3" else L.MI_ARCH_LLAMA
+        d.arch = {"qwen3": L.MI_ARCH_QWEN3, "phi3": L.MI_ARCH_PHI3}.get(mt, L.MI_ARCH_LLAMA)
         d.hidden_size = int(config["hidden_size"])
         d.num_layers = int(config["num_hidden_layers"])
         d.num_heads = nh
         d.num_kv_heads = int(config.get("num_key_value_heads") or nh)
-        d.head_dim = int(config.get("head_dim") or d.hidden_size // nh)
+        # phi3.py:53 divides; a head_dim key in a Phi-3 config is ignored, as the reference ignores it
+        d.head_dim = d.hidden_size // nh if mt == "phi3" else int(config.get("head_dim") or d.hidden_size // nh)
         d.intermediate_size = int(config["intermediate_size"])
         d.vocab_size = int(config["vocab_size"])
         d.rms_norm_eps = float(config["rms_norm_eps"])
         d.rope_theta = float(config.get("rope_theta", 10000.0))
         scale = 1.0
         rs = config.get("rope_scaling")
-        if rs:                                                                      # llama.py:36-46,69-76
+        if rs and mt == "phi3":                                                     # phi3.py:31-40,60-81
+            kind = rs.get("type")
+            if kind == "su":
+                raise NotImplementedError("rope_scaling type su is not supported by the MI355X engine")
+            if kind == "linear":
+                scale = 1.0 / float(rs["factor"])
+        elif rs:                                                                    # llama.py:36-46,69-76
             if "factor" not in rs:
                 raise ValueError("rope_scaling must contain 'factor'")
             kind = rs.get("type", rs.get("rope_type"))
@@ -274,7 +281,7 @@ class Engine:
             elif kind not in ("llama3", "default", None):
                 raise ValueError(f"rope_scaling type {kind} not supported")
         d.rope_scale = scale
-        tie_default = mt == "llama"           # llama.py:30 default True; mlx-lm qwen3 default False
+        tie_default = mt == "llama"           # llama.py:30 default True; mlx-lm qwen3 default False; phi3.py:194 has its own lm_head
         d.tie_word_embeddings = int(bool(config.get("tie_word_embeddings", tie_default)))
         d.act_dtype = _DT_NAMES[act_dtype]
         q = config.get("quantization")
@@ -323,7 +330,8 @@ class Engine:
     def set_lora(self, layer: int, proj: str, a, b, scale: float) -> None:
         """``mi_engine_set_lora``: adapt (or hot-swap) one projection of block ``layer`` -- any of the seven linears
         (``self_attn.q_proj`` / ``k_proj`` / ``v_proj`` / ``o_proj``, ``mlp.gate_proj`` / ``up_proj`` / ``down_proj``), in any
-        combination, also on a finalized engine.  ``a`` (K, r), ``b`` (r, N); converted to float32; r in 1..64.  Any other
+        combination, also on a finalized engine; on a phi3 engine ``self_attn.qkv_proj`` / ``o_proj``, ``mlp.gate_up_proj`` /
+        ``down_proj``, the fused ones with ``b`` cut by columns into q, k, v / gate, up.  ``a`` (K, r), ``b`` (r, N); converted to float32; r in 1..64.  Any other
         name raises NotImplementedError and leaves the engine as it was.  Published prefixes are forgotten."""
         import torch
         ta = torch.as_tensor(a).to(torch.float32).contiguous()

@@ -142,6 +142,52 @@ def quantize_weights(w: Dict[str, torch.Tensor], group_size: int, bits: int) -> 
     return out
 
 
+_PHI3_FUSED = (("self_attn.qkv_proj", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")),
+               ("mlp.gate_up_proj", ("mlp.gate_proj", "mlp.up_proj")))
+
+
+def fuse_phi3(w: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A Llama-form checkpoint (dense or quantised) in Phi-3 form: ``qkv_proj`` = q, then k, then v along the rows,
+    ``gate_up_proj`` = gate, then up (phi3.py:56-57,93-95,120,125).  Quantisation groups run along K, so stacking rows
+    of codes, scales and biases is quantising the stacked matrix."""
+    out = dict(w)
+    layers = sorted({int(k.split(".")[2]) for k in w if k.startswith("model.layers.")})
+    for i in layers:
+        p = f"model.layers.{i}."
+        for fused, parts in _PHI3_FUSED:
+            for suf in (".weight", ".scales", ".biases"):
+                if p + parts[0] + suf in w:
+                    out[p + fused + suf] = torch.cat([out.pop(p + name + suf) for name in parts], dim=0)
+    return out
+
+
+def split_phi3(w: Dict[str, torch.Tensor], cfg: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+    """The inverse of ``fuse_phi3`` for the geometry in ``cfg``: the Llama-form twin of a Phi-3 checkpoint."""
+    nh = int(cfg["num_attention_heads"])
+    nkv = int(cfg.get("num_key_value_heads") or nh)
+    D = int(cfg["hidden_size"]) // nh
+    rows = {"self_attn.qkv_proj": [nh * D, nkv * D, nkv * D], "mlp.gate_up_proj": [int(cfg["intermediate_size"])] * 2}
+    out = dict(w)
+    for k in list(w):
+        for fused, parts in _PHI3_FUSED:
+            for suf in (".weight", ".scales", ".biases"):
+                if k.endswith(fused + suf):
+                    for name, t in zip(parts, torch.split(out.pop(k), rows[fused], dim=0)):
+                        out[k[: -len(fused + suf)] + name + suf] = t.contiguous()
+    return out
+
+
+def phi3_config(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The key set of a Phi-3 ``config.json`` (phi3.py:11-25): no ``head_dim``, no ``tie_word_embeddings``, no bias flags."""
+    keys = ("hidden_size", "num_hidden_layers", "intermediate_size", "num_attention_heads", "num_key_value_heads",
+            "rms_norm_eps", "vocab_size", "rope_theta", "rope_traditional", "rope_scaling", "max_position_embeddings",
+            "quantization", "quantization_config")
+    out = {k: cfg[k] for k in keys if k in cfg}
+    out["model_type"] = "phi3"
+    out["original_max_position_embeddings"] = int(cfg["max_position_embeddings"])
+    return out
+
+
 def build_byte_tokenizer(dst: Path) -> int:
     """Writes a byte-level HF fast tokenizer (256 byte tokens + <|endoftext|>, <|im_start|>,
     <|im_end|>) with a ChatML template.  Returns its vocabulary size."""
@@ -176,6 +222,15 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
 
     dst = Path(dst)
     dst.mkdir(parents=True, exist_ok=True)
+    phi3 = model_type == "phi3"
+    if phi3:
+        # models/phi3.py: no linear biases, an lm_head of its own, head_dim = hidden_size // heads.  The tensors are those
+        # that model_type="llama" draws with the same arguments; q|k|v and gate|up are written as one matrix each.
+        if tie_word_embeddings or attention_bias or mlp_bias:
+            raise ValueError("phi3 has neither a tied lm_head nor linear biases: pass tie_word_embeddings=False")
+        if head_dim is not None and head_dim != hidden_size // heads:
+            raise ValueError("phi3: head_dim is hidden_size // heads")
+        model_type, head_dim = "llama", None
     tok_vocab = build_byte_tokenizer(dst) if with_tokenizer else 0
     if vocab_size is None:
         vocab_size = 151936                                  # build_tiny_model.py:125 fallback
@@ -191,6 +246,9 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
     w = init_weights(cfg, seed=seed, dtype=dtype, norm_jitter=norm_jitter, weight_std=weight_std)
     if quantize_model:
         w = quantize_weights(w, q_group_size, q_bits)
+    if phi3:
+        w = fuse_phi3(w)
+        cfg = phi3_config(cfg)
     save_file({k: v.contiguous() for k, v in w.items()}, str(dst / "model.safetensors"), metadata={"format": "mlx"})
     (dst / "config.json").write_text(json.dumps(cfg, indent=4, sort_keys=True))   # utils.save_config sorts keys
     return cfg
