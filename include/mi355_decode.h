@@ -270,6 +270,27 @@ int mi_kv_reset_row(mi_kv* kv, int row);
  * n < 0 or n > MI_MAX_ROW_LOGIT_BIAS; an id outside [0, vocab_size); an id that occurs twice; a value that is not finite. */
 #define MI_MAX_ROW_LOGIT_BIAS 1024   /* entries per row (OpenAI allows 300) */
 int mi_kv_set_row_logit_bias(mi_kv* kv, int row, const int32_t* ids, const float* values, int n);
+/* logprobs of the REQUEST that occupies cache row `row` (the reference reports them for one request at a time,
+ * server/main.py:571-584; under continuous batching requests that want them share a step with requests that do not):
+ * top_logprobs in 0..MI_MAX_TOP_LOGPROBS is the row's own count of top entries, at_temperature != 0 reports the row's
+ * logprob_out and top entries under softmax(logits / T_b), T_b the row's sampling temperature, when T_b > 0 (else the plain
+ * log-softmax).  (0, 0) clears the row: it keeps the call's top_logprobs / logprobs_at_temperature again, as every row without
+ * a setting does.  Like the bias it is set once at admission and travels with the row -- nothing is uploaded per step; the
+ * device table [batch] belongs to the mi_kv (either form) and is allocated by the first call that sets a row, never inside a
+ * step.  mi_kv_reset_row clears the row's setting, mi_kv_reset every row's; mi_kv_reserve and mi_kv_prefix_attach / _publish
+ * leave it alone.  Every entry point that samples through the mi_kv obeys it, with the row mapping of the bias (sampled row b
+ * of mi_decode_sample / mi_step_enqueue is cache row b, of mi_step_enqueue_rows rows[b], of mi_step_enqueue_mixed its wanted
+ * segment's row); mi_score_tokens ignores it.  Ordered on the engine's stream like mi_kv_reset_row.
+ * Layout: a step enqueued while at least one row of its cache has a setting returns topk_ids / topk_logprobs as
+ * [B][MI_MAX_TOP_LOGPROBS] (mi_step_wait / mi_decode_sample copy B x MI_MAX_TOP_LOGPROBS entries: size the buffers for it):
+ * a row's first k_b entries are its top list, the entries behind them hold id -1 and logprob -inf.  A row whose list runs past
+ * its last comparable logit (k_b > the number of logits that are not NaN) gets id 0 and the logprob of -inf there, as the
+ * call-wide count does.  A row with k_b = 0 costs no walk of its logits; from k_b = 4 on the list is selected in at most five
+ * walks, whatever k_b, and is bit for bit the list that k_b rounds of arg-max give.  A step on a cache without a setting is
+ * the step of a cache that never had one (the same kernel and arguments, the [B][top_logprobs] layout).
+ * MI_ERR_INVALID, naming the argument, with nothing changed and the previous setting in force: row outside the cache;
+ * top_logprobs outside [0, MI_MAX_TOP_LOGPROBS]; at_temperature other than 0 or 1. */
+int mi_kv_set_row_logprobs(mi_kv* kv, int row, int top_logprobs, int at_temperature);
 /* Block until `ticket` has finished; copy out its results (same meaning as mi_decode_sample). */
 int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logprob_out,
                  float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs);

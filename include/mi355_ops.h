@@ -18,6 +18,7 @@
  *   mi_op_sample      sample closure + top_p_sampling: utils.py:345-364; sample_utils.py:3-38
  *   mi_op_sample_ex   the same kernel with top_k / min_p and per-row random streams (no counterpart in the reference)
  *   mi_op_sample_rowbias  ... and a call-wide logit_bias list (utils.py:346-349) + the per-row table (no counterpart)
+ *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
  */
 #ifndef MI355_OPS_H
 #define MI355_OPS_H
@@ -206,6 +207,28 @@ int mi_op_sample_rowbias(float* logits, int B, int V, float temperature, float t
                          int n_bias, const int32_t* bias_ids, const float* bias_values,
                          const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
                          int table_rows, int cap, const int32_t* row_map);
+/* mi_op_sample_rowbias + the per-row logprobs settings of mi_kv_set_row_logprobs (mi355_decode.h), DEVICE arrays
+ * [table_rows] indexed like the bias table (t = row_map ? row_map[b] : b; row_bias_counts may be NULL: settings without a
+ * table): row_top_logprobs[t] >= 0 is sampled row b's own count of top entries (capped at MI_MAX_TOP_LOGPROBS) and
+ * row_at_temperature[t] != 0 reports its logprob_out and top entries under softmax(logits / T_b) when T_b > 0;
+ * row_top_logprobs[t] < 0, or a t outside the table: the row keeps the call's top_logprobs and logprobs_at_temperature.
+ * n_row_settings = the number of table rows with a setting, which the host knows (the kernel does not count them):
+ *   > 0: topk_ids / topk_logprobs are [B][MI_MAX_TOP_LOGPROBS]: a row's first k_b entries as mi_op_sample_ex writes them at
+ *        top_logprobs = k_b (bit for bit; past the row's last comparable logit: id 0 and the logprob of -inf), then (-1, -inf);
+ *   0:   the launch, the arguments and the [B][top_logprobs] layout of mi_op_sample_rowbias, whatever the arrays hold.
+ * method: how a row with k_b > 0 finds its entries.  1: k rounds of arg-max, one walk of the row each (the form of every
+ * other entry point); 2: the selection -- a count descent to the k_b-th key, one gather walk, at most five walks whatever
+ * k_b; 0: per row, the selection from the measured crossover k_b >= 4 on (what the engine launches).  All three write the
+ * same bits.  logprobs_at_temperature is the call-wide flag of mi_sample_params, which mi_op_sample_ex leaves off. */
+int mi_op_sample_rowlp(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                       const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                       const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                       const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                       float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
+                       int n_bias, const int32_t* bias_ids, const float* bias_values,
+                       const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
+                       int table_rows, int cap, const int32_t* row_map, const int32_t* row_top_logprobs,
+                       const int32_t* row_at_temperature, int n_row_settings, int logprobs_at_temperature, int method);
 
 #ifdef __cplusplus
 }

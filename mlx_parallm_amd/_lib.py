@@ -103,6 +103,7 @@ SIGNATURES = {
     "mi_step_enqueue_mixed": (C.c_int, [_P, _P, _I32P, _I32P, _I32P, C.c_int, _I32P, C.POINTER(SampleParams), C.POINTER(C.c_int64)]),
     "mi_kv_reset_row": (C.c_int, [_P, C.c_int]),
     "mi_kv_set_row_logit_bias": (C.c_int, [_P, C.c_int, _I32P, _F32P, C.c_int]),
+    "mi_kv_set_row_logprobs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mi_step_wait": (C.c_int, [_P, C.c_int64, _I32P, _F32P, _F32P, _I32P, _F32P]),
     "mi_profile_select": (C.c_int, [_P, C.c_char_p]),
     "mi_profile_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -141,6 +142,9 @@ SIGNATURES = {
     "mi_op_sample_rowbias": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
                                        C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P,
                                        C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "mi_op_sample_rowlp": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
+                                     C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P,
+                                     C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -362,16 +362,21 @@ int run_sample(mi_engine* e, int B, const mi_sample_params* sp, const int32_t* f
     sc.rb_cnt = kv->rb_cnt(); sc.rb_ids = kv->rb_ids(); sc.rb_vals = kv->rb_vals(); sc.rb_map = rb_map;
     sc.rb_rows = kv->B; sc.rb_cap = MI_MAX_ROW_LOGIT_BIAS;
   }
+  if (kv && kv->lp_set > 0 && !forced) {                    // (no row setting: the launch, the arguments and the layout of before)
+    sc.lp_k = kv->lp_k(); sc.lp_flag = kv->lp_flag(); sc.topk_stride = MI_MAX_TOP_LOGPROBS;
+    sc.rb_map = rb_map; sc.rb_rows = kv->B;
+  }
   return launch_sample(sc, st);
 }
 
 // The step's results -> a pinned slot (tokens | logprobs | row-0 probabilities: one copy, d_next and the slot's block
 // share the layout), then the event mi_step_wait waits for.
-int finish_step(mi_engine* e, int B, const mi_sample_params* sp, int64_t* ticket) {
+// kv with a row logprobs setting: the top-k arrays have the fixed stride MI_MAX_TOP_LOGPROBS (mi_kv_set_row_logprobs)
+int finish_step(mi_engine* e, int B, const mi_sample_params* sp, int64_t* ticket, const mi_kv* kv) {
   hipStream_t st = e->stream;
   const int64_t t = e->next_ticket++;
   Slot& s = e->slots[t % NSLOT];
-  s.B = B; s.topk = sp ? sp->top_logprobs : 0; s.ticket = t;
+  s.B = B; s.topk = (kv && kv->lp_set > 0) ? MI_MAX_TOP_LOGPROBS : sp ? sp->top_logprobs : 0; s.ticket = t;
   if (B > 0) {
     MI_HIP(hipMemcpyAsync(s.tokens, e->d_next, ((size_t)2 * e->maxB + B) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (s.topk > 0) {
@@ -396,7 +401,7 @@ int step_enqueue(mi_engine* e, mi_kv* kv, const int32_t* rows, int n, const int3
   MI_TRY(frc);
   MI_TRY(run_sample(e, n, sp, nullptr, kv, rows ? kv->d_rows : nullptr));   // (forward left the call's rows in d_rows)
   e->last_n = n;
-  return finish_step(e, n, sp, ticket);
+  return finish_step(e, n, sp, ticket, kv);
 }
 
 }  // namespace
@@ -587,16 +592,16 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
   MI_TRY(forward(e, kv, rows, groups, R == (size_t)nd ? 1 : 2, n_out > 0 ? Head::GATHER : Head::NONE, gather, "mixed step"));
   if (n_out > 0) {
     const int32_t* rb_map = nullptr;
-    if (kv->rb_biased > 0) {                     // sampled row i = the i-th wanted segment: its cache row
+    if (kv->rb_biased > 0 || kv->lp_set > 0) {   // sampled row i = the i-th wanted segment: its cache row
       std::vector<int32_t> wanted;
       for (int i = 0; i < n; ++i) if (want[i]) wanted.push_back(rows[i]);
-      MI_HIP(hipMemcpyAsync(kv->rb_map(), wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-      rb_map = kv->rb_map();
+      rb_map = kv->rb_biased > 0 ? kv->rb_map() : kv->lp_map();
+      MI_HIP(hipMemcpyAsync((void*)rb_map, wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     }
     MI_TRY(run_sample(e, n_out, sp, nullptr, kv, rb_map));
   }
   e->last_n = -1;                                // the device-resident token feed does not survive a mixed step
-  return finish_step(e, n_out, sp, ticket);
+  return finish_step(e, n_out, sp, ticket, n_out > 0 ? kv : nullptr);
 }
 
 int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logprob_out, float* prob_row0_out,

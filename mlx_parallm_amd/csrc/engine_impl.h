@@ -179,6 +179,15 @@ struct mi_kv {
   int32_t* rb_map() const { return rb_block + B; }                 // the sampled row -> cache row map of a mixed step
   int32_t* rb_ids() const { return rb_block + 2 * (size_t)B; }
   float* rb_vals() const { return (float*)(rb_block + 2 * (size_t)B + (size_t)B * MI_MAX_ROW_LOGIT_BIAS); }
+  // ---- per-row logprobs settings (mi_kv_set_row_logprobs): one block [B counts (-1: no setting) | B flags | B map], allocated
+  // by the first call that sets a row.  lp_host_k mirrors the counts in enqueue order and lp_set counts the rows with a
+  // setting: a step enqueued while it is 0 launches the sampler without the settings and returns the [B][top_logprobs] layout.
+  int32_t* lp_block = nullptr;
+  std::vector<int32_t> lp_host_k;
+  int lp_set = 0;
+  int32_t* lp_k() const { return lp_block; }
+  int32_t* lp_flag() const { return lp_block + B; }
+  int32_t* lp_map() const { return lp_block + 2 * (size_t)B; }     // (mixed steps of a cache without a bias table)
   // ---- block-paged form (mi_kv_create_paged): k / v are arenas [layer][block][Hkv][1 << bs_shift][D], blocks.h_btab names
   // every row's blocks and d_btab is its copy on the device; cap = bt_stride << bs_shift is the longest sequence a row can hold
   bool paged = false;

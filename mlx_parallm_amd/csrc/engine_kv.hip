@@ -84,6 +84,16 @@ int rb_clear_row(mi_kv* kv, int row) {
   return MI_OK;
 }
 
+// the row's logprobs setting -> none, behind the steps already enqueued
+int lp_clear_row(mi_kv* kv, int row) {
+  if (kv->lp_set > 0 && kv->lp_host_k[row] >= 0) {
+    MI_HIP(hipMemsetD32Async((hipDeviceptr_t)(kv->lp_k() + row), -1, 1, kv->e->stream));
+    kv->lp_host_k[row] = -1;
+    --kv->lp_set;
+  }
+  return MI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -170,7 +180,7 @@ void mi_kv_destroy(mi_kv* kv) {
   hipStreamSynchronize(kv->e->stream);
   hipFree(kv->k); hipFree(kv->v); hipFree(kv->d_off); hipFree(kv->partial); hipFree(kv->counters); hipFree(kv->d_rows);
   hipFree(kv->d_btab);
-  hipFree(kv->rb_block);
+  hipFree(kv->rb_block); hipFree(kv->lp_block);
   if (kv->rb_stage) hipHostFree(kv->rb_stage);
   for (hipEvent_t ev : kv->rb_ev) if (ev) hipEventDestroy(ev);
   delete kv;
@@ -182,6 +192,7 @@ int mi_kv_reset(mi_kv* kv, int batch) {
   MI_HIP(hipSetDevice(kv->e->device));
   MI_HIP(hipMemsetAsync(kv->d_off, 0, kv->B * sizeof(int32_t), kv->e->stream));
   for (int r = 0; r < kv->B; ++r) MI_TRY(rb_clear_row(kv, r));     // every row's logit_bias goes with its contents
+  for (int r = 0; r < kv->B; ++r) MI_TRY(lp_clear_row(kv, r));     // and its logprobs setting
   MI_HIP(hipStreamSynchronize(kv->e->stream));
   std::fill(kv->h_off.begin(), kv->h_off.end(), 0);
   for (int r = 0; r < kv->B; ++r) kv_release_row(kv, r);
@@ -195,7 +206,35 @@ int mi_kv_reset_row(mi_kv* kv, int row) {
   MI_HIP(hipMemsetAsync(kv->d_off + row, 0, sizeof(int32_t), kv->e->stream));   // ordered behind the steps already enqueued
   kv->h_off[row] = 0;
   kv_release_row(kv, row);      // (paged: the blocks go back to the pool; whoever gets them next writes behind the steps in flight)
-  return rb_clear_row(kv, row);                             // the next occupant of the row samples unbiased
+  MI_TRY(rb_clear_row(kv, row));                            // the next occupant of the row samples unbiased
+  return lp_clear_row(kv, row);                             // and reports what its own request asks for
+}
+
+int mi_kv_set_row_logprobs(mi_kv* kv, int row, int top_logprobs, int at_temperature) {
+  if (!kv) return fail(MI_ERR_INVALID, "null kv");
+  if (row < 0 || row >= kv->B) return fail(MI_ERR_INVALID, "mi_kv_set_row_logprobs: row out of range");
+  if (top_logprobs < 0 || top_logprobs > MI_MAX_TOP_LOGPROBS)
+    return fail(MI_ERR_INVALID, "mi_kv_set_row_logprobs: top_logprobs must be in [0, " + std::to_string(MI_MAX_TOP_LOGPROBS) + "]");
+  if (at_temperature != 0 && at_temperature != 1) return fail(MI_ERR_INVALID, "mi_kv_set_row_logprobs: at_temperature must be 0 or 1");
+  MI_HIP(hipSetDevice(kv->e->device));
+  hipStream_t st = kv->e->stream;
+  if (top_logprobs == 0 && at_temperature == 0) return lp_clear_row(kv, row);   // (a cache that never had a setting: nothing to clear)
+  if (!kv->lp_block) {                                      // first use: the table, every row without a setting
+    int32_t* blk = nullptr;
+    if (hipMalloc(&blk, 3 * (size_t)kv->B * sizeof(int32_t)) != hipSuccess) return fail(MI_ERR_RUNTIME, "out of device memory allocating the logprobs settings");
+    if (hipMemsetAsync(blk, 0xff, 3 * (size_t)kv->B * sizeof(int32_t), st) != hipSuccess) {
+      hipFree(blk);
+      return fail(MI_ERR_RUNTIME, "hipMemsetAsync failed (logprobs settings)");
+    }
+    kv->lp_block = blk;
+    kv->lp_host_k.assign(kv->B, -1);
+  }
+  // the flag, then the count that makes it a setting: behind every step already enqueued, ahead of every later one
+  MI_HIP(hipMemsetD32Async((hipDeviceptr_t)(kv->lp_flag() + row), at_temperature, 1, st));
+  MI_HIP(hipMemsetD32Async((hipDeviceptr_t)(kv->lp_k() + row), top_logprobs, 1, st));
+  if (kv->lp_host_k[row] < 0) ++kv->lp_set;
+  kv->lp_host_k[row] = top_logprobs;
+  return MI_OK;
 }
 
 int mi_kv_set_row_logit_bias(mi_kv* kv, int row, const int32_t* ids, const float* values, int n) {

@@ -323,6 +323,15 @@ struct SampleCall {
   const float* rb_vals = nullptr;        // device [rb_rows][rb_cap]
   const int32_t* rb_map = nullptr;       // device [B] or null: the identity
   int rb_rows = 0, rb_cap = 0;
+  // per-row logprobs settings (sample_kernel<*, true, true>; lp_k == null: the kernels without them).  Sampled row b on table
+  // row t = rb_map ? rb_map[b] : b (t in [0, rb_rows)) with lp_k[t] >= 0 reports lp_k[t] top entries and, with lp_flag[t] != 0
+  // and a row temperature > 0, logprobs under softmax(logits / T_b); lp_k[t] < 0 (or t outside the table): the call's
+  // top_logprobs / lp_temp.  topk_ids / topk_logprobs are then [B][topk_stride]; entries past a row's count hold (-1, -inf).
+  // rb_cnt may be null with lp_k set (settings without a bias table)
+  const int32_t* lp_k = nullptr;         // device [rb_rows]
+  const int32_t* lp_flag = nullptr;      // device [rb_rows]
+  int topk_stride = 0;                   // >= every count (MI_MAX_TOP_LOGPROBS)
+  int lp_method = 0;                     // 0: per row by LP_SELECT_MIN_K; 1: the k-round form on every row; 2: the selection
 };
 int launch_sample(const SampleCall& c, hipStream_t st);
 

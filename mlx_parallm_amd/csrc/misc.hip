@@ -434,10 +434,179 @@ __device__ Prefix min_p_prefix(const float* lg, int V, float mx, float inv_t, fl
   return r;
 }
 
+// ---- top-k logprobs in a bounded number of walks (sample_kernel<*, *, true>) ----------------------------------------------
+// The k-round form below the kernel's sampling part walks the row once per entry.  This one finds the key of the k-th
+// candidate by a radix descent over counts (8 bits per level, one walk each, at most four), stops descending as soon as
+// everything from the chosen bin upwards fits LP_CAND slots, gathers in one more walk, and orders the few gathered
+// candidates by (logit descending, id ascending): at most five walks, whatever k.  The order is that of the k-round form's
+// float comparisons, which differs from order_key in two places: a NaN is never a candidate (key 0, never counted, never
+// gathered) and -0.0 ties +0.0 by id (both get the key of +0.0; the gathered VALUE is kept, its sign reaches the logprob).
+constexpr int LP_CAND = 64;
+// Smallest per-row count that takes the selection instead of k rounds: the smallest k at which it measured faster in every
+// cell of the launch-time table of DESIGN.md §5 (profiles/sampler_rowlp_launch_times.txt; B = 8, µs, rounds / selection --
+// V = 32000: k = 3 22.2 / 23.1, k = 4 27.2 / 23.2, k = 20 106.1 / 24.9; V = 151936: k = 3 72.1 / 70.5, k = 4 90.1 / 70.7,
+// k = 20 378.3 / 72.6.  A round costs one walk, the selection three on ordinary rows).
+constexpr int LP_SELECT_MIN_K = 4;
+
+__device__ __forceinline__ uint32_t lp_key(float f) {
+  if (f != f) return 0u;
+  return f == 0.f ? 0x80000000u : order_key(f);
+}
+
+__device__ __forceinline__ float lp_value(float v, float mx, float lp_scale, float lp_lse) { return (v - mx) * lp_scale - lp_lse; }
+
+// Writes out_ids / out_lp [0, k) of one row; false (nothing written): the row's shape does not fit the tie table and the
+// caller runs the k-round form (V not a multiple of 4 above 65536 ids, or above 262144).
+__device__ bool lp_select_topk(const float* lg, int V, int k, float mx, float lp_scale, float lp_lse, int32_t* out_ids,
+                               float* out_lp, unsigned long long* hist_m, int* hist_c, int (*pc)[8], Prefix* out_sh,
+                               unsigned long long* sc_m, int* sc_c, int* sel, int* tbl) {
+  __shared__ float cand_v[LP_CAND];
+  __shared__ int cand_i[LP_CAND], cand_n;
+  __shared__ int te_at[MI_MAX_TOP_LOGPROBS], te_first[MI_MAX_TOP_LOGPROBS], te_take[MI_MAX_TOP_LOGPROBS], te_n;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool vec = (V & 3) == 0 && (((uintptr_t)lg) & 15) == 0;
+  const int per = vec ? 4 : 1;
+  const int nch = (V + per * ST - 1) / (per * ST);
+  if (nch * (ST / 64) > TIE_TBL) return false;               // (uniform)
+  __syncthreads();
+  for (int i = tid; i < 8 * 256; i += ST) pc[i >> 3][i & 7] = 0;
+  for (int i = tid; i < 256; i += ST) hist_m[i] = 0;          // select_bin sums masses too: zeros, unused
+  if (tid == 0) { cand_n = 0; te_n = 0; }
+  __syncthreads();
+  const int cp = tid & 7;
+  for_row(lg, V, [&](float l, int) {                          // walk 1: count-only level-0 histogram, private copies as build_hist0
+    const uint32_t key = lp_key(l);
+    if (key) atomicAdd(&pc[key >> 24][cp], 1);
+  });
+  __syncthreads();
+  if (tid < 256) {
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) n += pc[tid][q];
+    hist_c[tid] = n;
+  }
+  select_bin<true>(hist_m, hist_c, 0ull, 0, ~0ull, sc_m, sc_c, sel, out_sh);   // target past the end: the number of candidates
+  const int ke = min(k, out_sh->count);                      // entries past the last comparable logit are filler
+  uint32_t bits = 0, mask = 0;
+  int above = 0, binc = 0;
+  bool exact = true;
+  if (ke > 0) {
+    for (int level = 0; level < 4; ++level) {
+      const int shift = 24 - 8 * level;
+      if (level > 0) {
+        __syncthreads();
+        for (int i = tid; i < 256; i += ST) hist_c[i] = 0;
+        __syncthreads();
+        for_row(lg, V, [&](float l, int) {
+          const uint32_t key = lp_key(l);
+          if (key && (key & mask) == bits) atomicAdd(&hist_c[(key >> shift) & 255], 1);
+        });
+      }
+      select_bin<true>(hist_m, hist_c, 0ull, above, (unsigned long long)(ke - 1), sc_m, sc_c, sel, out_sh);
+      above = out_sh->count;
+      const int bin = max(out_sh->ntie, 0);                  // (ke - 1 < the count: a bin is always found)
+      binc = hist_c[bin];
+      bits |= (uint32_t)bin << shift;
+      mask |= 255u << shift;
+      if (above + binc <= LP_CAND) { exact = false; break; } // everything from this bin upwards fits the list
+    }
+    if (!exact) {                                             // gather walk: every candidate with key >= the bin's first key
+      const uint32_t ge = max(bits, 1u);
+      for_row(lg, V, [&](float l, int i) {
+        if (lp_key(l) >= ge) {
+          const int s = atomicAdd(&cand_n, 1);
+          if (s < LP_CAND) { cand_v[s] = l; cand_i[s] = i; }
+        }
+      });
+    } else {
+      // gather walk in index order (chunks of per * ST ids, as nth_tie): the candidates above kstar = bits go to the list
+      // (above < ke of them), the ties of kstar are counted per (chunk, wave); the first ke - above of them by id follow
+      const uint32_t kstar = bits;
+      auto load = [&](int j, float (&v)[4], bool (&ok)[4]) {
+        const int base = per * (ST * j + tid);
+        if (vec) {
+          float4 x = {0.f, 0.f, 0.f, 0.f};
+          const bool in = base < V;
+          if (in) x = *(const float4*)(lg + base);
+          v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+          ok[0] = ok[1] = ok[2] = ok[3] = in;
+        } else {
+          ok[0] = base < V; ok[1] = ok[2] = ok[3] = false;
+          v[0] = ok[0] ? lg[base] : 0.f; v[1] = v[2] = v[3] = 0.f;
+        }
+      };
+      for (int j = 0; j < nch; ++j) {
+        float v[4]; bool ok[4];
+        load(j, v, ok);
+        int n = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t key = ok[e] ? lp_key(v[e]) : 0u;
+          if (key > kstar) {
+            const int s = atomicAdd(&cand_n, 1);
+            if (s < LP_CAND) { cand_v[s] = v[e]; cand_i[s] = per * (ST * j + tid) + e; }
+          }
+          n += __popcll(__ballot(key == kstar));
+        }
+        if (lane == 0) tbl[j * (ST / 64) + wave] = n;
+      }
+      __syncthreads();
+      if (tid == 0) {                                         // the (chunk, wave) entries that hold the first ke - above ties
+        int left = ke - above, m = 0;
+        for (int i = 0; i < nch * (ST / 64) && left > 0 && m < MI_MAX_TOP_LOGPROBS; ++i) {
+          const int n = tbl[i];
+          if (n > 0) { const int take = min(n, left); te_at[m] = i; te_first[m] = ke - above - left; te_take[m] = take; ++m; left -= take; }
+        }
+        te_n = m;
+      }
+      __syncthreads();
+      const int m = te_n;
+      for (int x = 0; x < m; ++x) {
+        const int at = te_at[x];
+        if (wave != at % (ST / 64)) continue;                 // (uniform over the wave)
+        float v[4]; bool ok[4];
+        load(at / (ST / 64), v, ok);
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        bool is[4];
+        int before = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { is[e] = ok[e] && lp_key(v[e]) == kstar; before += __popcll(__ballot(is[e]) & lt); }
+        int r = before;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (is[e]) {
+            if (r < te_take[x]) {
+              const int pos = above + te_first[x] + r;        // < ke
+              out_ids[pos] = per * (ST * (at / (ST / 64)) + tid) + e;
+              out_lp[pos] = lp_value(v[e], mx, lp_scale, lp_lse);
+            }
+            ++r;
+          }
+      }
+    }
+    __syncthreads();
+    const int n = min(cand_n, LP_CAND);
+    if (tid < n) {                                            // rank among the gathered: (logit descending, id ascending)
+      const float v = cand_v[tid]; const int id = cand_i[tid];
+      int r = 0;
+      for (int u = 0; u < n; ++u) r += (cand_v[u] > v || (cand_v[u] == v && cand_i[u] < id)) ? 1 : 0;
+      if (r < ke) { out_ids[r] = id; out_lp[r] = lp_value(v, mx, lp_scale, lp_lse); }
+    }
+  }
+  if (tid >= ke && tid < k) {                                 // what a k-round arg-max without candidates reports
+    out_ids[tid] = 0;
+    out_lp[tid] = lp_value(-INFINITY, mx, lp_scale, lp_lse);
+  }
+  __syncthreads();
+  return true;
+}
+
 // EXT = false: temperature / top-p with the call-wide stream, the launch of every call that sets none of the newer controls
 // (its code does not change when they do).  EXT = true: + top-k, min-p and per-row streams.  ROWB = true: + the per-row
-// logit_bias table (SampleCall::rb_*), launched only when the call carries one.
-template <bool EXT, bool ROWB = false>
+// logit_bias table (SampleCall::rb_*), launched only when the call carries one.  ROWLP = true (with ROWB; the bias table may
+// then be absent): + the per-row logprobs settings (SampleCall::lp_*): a row's own count of top entries and its own
+// at-temperature flag, the top-k arrays at the fixed stride c.topk_stride, and lp_select_topk for the rows it pays for.
+template <bool EXT, bool ROWB = false, bool ROWLP = false>
 __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
   __shared__ ArgMax sh_am[ST / 64];
   __shared__ float sh_f[ST / 64];
@@ -464,7 +633,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
   }
   if constexpr (ROWB) {    // the bias of the request that holds this row's cache row; a row without one reads only its count
     const int t = c.rb_map ? c.rb_map[b] : b;
-    const int n = (t >= 0 && t < c.rb_rows) ? min(c.rb_cnt[t], c.rb_cap) : 0;
+    const int n = (t >= 0 && t < c.rb_rows && (!ROWLP || c.rb_cnt)) ? min(c.rb_cnt[t], c.rb_cap) : 0;
     if (n > 0) {           // (uniform over the block)
       const int32_t* ids = c.rb_ids + (size_t)t * c.rb_cap;
       const float* vals = c.rb_vals + (size_t)t * c.rb_cap;
@@ -552,7 +721,12 @@ __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
   }
   // logprobs are reported as (lg - mx) * lp_scale - lp_lse: the plain log-softmax, or the one of logits / T
   float lp_scale = 1.0f, lp_lse = lse - mx;
-  if (c.lp_temp && temperature > 0.f) {
+  int top_n = c.top_logprobs, lp_temp = c.lp_temp;   // this row's count of top entries and its at-temperature flag
+  if constexpr (ROWLP) {
+    const int t = c.rb_map ? c.rb_map[b] : b;
+    if (t >= 0 && t < c.rb_rows && c.lp_k[t] >= 0) { top_n = min(c.lp_k[t], c.topk_stride); lp_temp = c.lp_flag[t]; }
+  }
+  if (lp_temp && temperature > 0.f) {
     lp_scale = 1.0f / temperature;
     float st = se;                               // T = 1: the sum of the pass above, term for term (no second walk of the row)
     if (lp_scale != 1.0f) {                      // (uniform)
@@ -569,18 +743,29 @@ __global__ __launch_bounds__(ST) void sample_kernel(SampleCall c) {
     c.tokens_out[b] = token;
     if (c.logprob_out) c.logprob_out[b] = (c.forced && forced < 0) ? 0.f : (lg[token] - mx) * lp_scale - lp_lse;
   }
+  const int tk_stride = ROWLP ? c.topk_stride : c.top_logprobs;
+  if constexpr (ROWLP) {   // entries past the row's count: (-1, -inf); the row's own entries by the selection where it pays
+    for (int r = top_n + (int)threadIdx.x; r < tk_stride; r += ST) {
+      c.topk_ids[(size_t)b * tk_stride + r] = -1;
+      c.topk_logprobs[(size_t)b * tk_stride + r] = -INFINITY;
+    }
+    if (top_n > 0 && (c.lp_method == 2 || (c.lp_method == 0 && top_n >= LP_SELECT_MIN_K)) &&
+        lp_select_topk(lg, V, top_n, mx, lp_scale, lp_lse, c.topk_ids + (size_t)b * tk_stride, c.topk_logprobs + (size_t)b * tk_stride,
+                       hist_m, hist_c, priv_c, &sh_p, sc_m, sc_c, &sel_sh, tie_tbl))
+      top_n = 0;
+  }
   // ---- top-k logprobs: k rounds of arg-max with exclusion of already emitted ids
-  if (c.top_logprobs > 0) {
+  if (top_n > 0) {
     float prev_v = INFINITY; int prev_i = -1;
-    for (int r = 0; r < c.top_logprobs; ++r) {
+    for (int r = 0; r < top_n; ++r) {
       ArgMax t{-INFINITY, 0x7fffffff};
       for_row(lg, V, [&](float v, int i) {
         if (v < prev_v || (v == prev_v && i > prev_i)) t = am_better(t, ArgMax{v, i});
       });
       t = block_argmax(t, sh_am);
       if (threadIdx.x == 0) {
-        c.topk_ids[(size_t)b * c.top_logprobs + r] = t.i < V ? t.i : 0;
-        c.topk_logprobs[(size_t)b * c.top_logprobs + r] = (t.v - mx) * lp_scale - lp_lse;
+        c.topk_ids[(size_t)b * tk_stride + r] = t.i < V ? t.i : 0;
+        c.topk_logprobs[(size_t)b * tk_stride + r] = (t.v - mx) * lp_scale - lp_lse;
       }
       prev_v = t.v; prev_i = t.i;
     }
@@ -629,7 +814,14 @@ int launch_embed(const LinearW& W, const EmbedCall& c, hipStream_t st) {
 int launch_sample(const SampleCall& c, hipStream_t st) {
   if (c.top_logprobs < 0 || c.top_logprobs > MI_MAX_TOP_LOGPROBS) return fail(MI_ERR_INVALID, "sample: top_logprobs out of range");
   const bool ext = c.top_k > 0 || c.min_p > 0.f || c.row_top_k || c.row_min_p || c.row_position;
-  if (c.rb_cnt != nullptr) {
+  if (c.lp_k != nullptr) {
+    if (!c.lp_flag || c.rb_rows < 1 || c.topk_stride < 1 || c.topk_stride > MI_MAX_TOP_LOGPROBS || c.top_logprobs > c.topk_stride ||
+        !c.topk_ids || !c.topk_logprobs || c.lp_method < 0 || c.lp_method > 2)
+      return fail(MI_ERR_INVALID, "sample: incomplete row logprobs settings");
+    if (c.rb_cnt && (!c.rb_ids || !c.rb_vals || c.rb_cap < 1)) return fail(MI_ERR_INVALID, "sample: incomplete row bias table");
+    if (ext) hipLaunchKernelGGL((sample_kernel<true, true, true>), dim3(c.B), dim3(ST), 0, st, c);
+    else hipLaunchKernelGGL((sample_kernel<false, true, true>), dim3(c.B), dim3(ST), 0, st, c);
+  } else if (c.rb_cnt != nullptr) {
     if (!c.rb_ids || !c.rb_vals || c.rb_rows < 1 || c.rb_cap < 1) return fail(MI_ERR_INVALID, "sample: incomplete row bias table");
     if (ext) hipLaunchKernelGGL((sample_kernel<true, true>), dim3(c.B), dim3(ST), 0, st, c);
     else hipLaunchKernelGGL((sample_kernel<false, true>), dim3(c.B), dim3(ST), 0, st, c);

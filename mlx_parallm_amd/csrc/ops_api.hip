@@ -388,8 +388,12 @@ static int sample_op(const std::string& who, float* logits, int B, int V, float 
                      float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
                      int n_bias, const int32_t* bias_ids, const float* bias_values,
                      const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
-                     int table_rows, int cap, const int32_t* row_map) {
+                     int table_rows, int cap, const int32_t* row_map, const int32_t* row_lp_k = nullptr,
+                     const int32_t* row_lp_flag = nullptr, int n_row_settings = 0, int lp_at_temperature = 0, int method = 0) {
   if (!logits || !tokens_out || !row_stats) return fail(MI_ERR_INVALID, "null argument");
+  if (n_row_settings < 0 || (n_row_settings > 0 && (!row_lp_k || !row_lp_flag || table_rows < 1 || !topk_ids || !topk_logprobs)))
+    return fail(MI_ERR_INVALID, who + ": row settings need row_lp_k, row_lp_flag, table_rows >= 1 and the top-k outputs");
+  if (method < 0 || method > 2) return fail(MI_ERR_INVALID, who + ": method must be 0, 1 or 2");
   if (B < 1 || V < 1) return fail(MI_ERR_INVALID, who + ": B and V must be positive");
   if (top_k < 0) return fail(MI_ERR_INVALID, who + ": top_k must be >= 0 (0 = off)");
   if (!(min_p >= 0.f && min_p <= 1.f)) return fail(MI_ERR_INVALID, who + ": min_p must be in [0, 1] (0 = off)");
@@ -402,7 +406,7 @@ static int sample_op(const std::string& who, float* logits, int B, int V, float 
   SampleCall sc{};
   sc.logits = logits; sc.B = B; sc.V = V; sc.rnd = RND_NONE; sc.temperature = temperature; sc.top_p = top_p;
   sc.n_bias = n_bias; sc.bias_ids = bias_ids; sc.bias_vals = bias_values;
-  sc.uniforms = uniforms; sc.seed = seed; sc.step = step; sc.top_logprobs = top_logprobs; sc.lp_temp = 0;
+  sc.uniforms = uniforms; sc.seed = seed; sc.step = step; sc.top_logprobs = top_logprobs; sc.lp_temp = lp_at_temperature ? 1 : 0;
   sc.row_temp = row_temperature; sc.row_top_p = row_top_p;
   sc.top_k = top_k; sc.min_p = min_p; sc.row_top_k = row_top_k; sc.row_min_p = row_min_p;
   sc.row_seed = row_seed; sc.row_position = row_position;
@@ -411,6 +415,10 @@ static int sample_op(const std::string& who, float* logits, int B, int V, float 
   if (row_bias_counts) {                           // (null: launch_sample picks the instantiations without the table)
     sc.rb_cnt = row_bias_counts; sc.rb_ids = row_bias_ids; sc.rb_vals = row_bias_values;
     sc.rb_rows = table_rows; sc.rb_cap = cap; sc.rb_map = row_map;
+  }
+  if (n_row_settings > 0) {                        // (0: the launch of a call without the arrays, whatever they hold)
+    sc.lp_k = row_lp_k; sc.lp_flag = row_lp_flag; sc.topk_stride = MI_MAX_TOP_LOGPROBS; sc.lp_method = method;
+    sc.rb_rows = table_rows; sc.rb_map = row_map;
   }
   MI_TRY(launch_sample(sc, nullptr));
   return finish();
@@ -438,6 +446,22 @@ int mi_op_sample_rowbias(float* logits, int B, int V, float temperature, float t
                    row_min_p, row_seed, row_position, seed, step, uniforms, top_logprobs, tokens_out, logprob_out, prob_row0_out,
                    topk_ids, topk_logprobs, row_stats, n_bias, bias_ids, bias_values, row_bias_counts, row_bias_ids,
                    row_bias_values, table_rows, cap, row_map);
+}
+
+int mi_op_sample_rowlp(float* logits, int B, int V, float temperature, float top_p, int top_k, float min_p,
+                       const float* row_temperature, const float* row_top_p, const int32_t* row_top_k, const float* row_min_p,
+                       const uint64_t* row_seed, const int64_t* row_position, uint64_t seed, uint64_t step,
+                       const float* uniforms, int top_logprobs, int32_t* tokens_out, float* logprob_out,
+                       float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs, float* row_stats,
+                       int n_bias, const int32_t* bias_ids, const float* bias_values,
+                       const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
+                       int table_rows, int cap, const int32_t* row_map, const int32_t* row_top_logprobs,
+                       const int32_t* row_at_temperature, int n_row_settings, int logprobs_at_temperature, int method) {
+  return sample_op("sample_rowlp", logits, B, V, temperature, top_p, top_k, min_p, row_temperature, row_top_p, row_top_k,
+                   row_min_p, row_seed, row_position, seed, step, uniforms, top_logprobs, tokens_out, logprob_out, prob_row0_out,
+                   topk_ids, topk_logprobs, row_stats, n_bias, bias_ids, bias_values, row_bias_counts, row_bias_ids,
+                   row_bias_values, table_rows, cap, row_map, row_top_logprobs, row_at_temperature, n_row_settings,
+                   logprobs_at_temperature, method);
 }
 
 }  // extern "C"

@@ -148,10 +148,33 @@ class KVCache:
         if batch_size is not None and batch_size != self.batch_size:
             raise ValueError("KVCache.reset with a different batch size: create a new cache")
         L.check(L.lib().mi_kv_reset(self._h, self.batch_size))
+        self._row_logprobs().clear()
 
     def reset_row(self, row: int) -> None:
         """Forget one row (continuous batching: the slot of a finished sequence)."""
         L.check(L.lib().mi_kv_reset_row(self._h, int(row)))
+        self._row_logprobs().pop(int(row), None)
+
+    def _row_logprobs(self) -> Dict[int, int]:
+        """Host mirror of the rows with a logprobs setting (row -> count): tells ``Engine.step_wait`` which layout a step
+        enqueued on this cache returns."""
+        return self.__dict__.setdefault("_row_lp", {})
+
+    def set_row_logprobs(self, row: int, top_logprobs: int, at_temperature: bool = False) -> None:
+        """The logprobs of the request that occupies ``row`` (``mi_kv_set_row_logprobs``): every later step that samples the
+        row reports ``top_logprobs`` (0..20) top entries for it and, with ``at_temperature``, its logprobs under
+        ``softmax(logits / T)`` of the row's own temperature.  ``(0, False)`` clears the row, as ``reset_row`` / ``reset`` do.
+        While any row of the cache has a setting, ``Engine.step_wait`` returns ``top_ids`` / ``top_logprobs`` as
+        ``(B, 20)`` plus ``top_counts``.  ValueError (nothing changed): a bad row or count."""
+        if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)):
+            raise ValueError(f"set_row_logprobs: top_logprobs {top_logprobs!r} is not an int")
+        if not -2 ** 31 <= int(top_logprobs) < 2 ** 31 or not -2 ** 31 <= int(row) < 2 ** 31:
+            raise ValueError("set_row_logprobs: argument out of range")
+        L.check(L.lib().mi_kv_set_row_logprobs(self._h, int(row), int(top_logprobs), int(bool(at_temperature))))
+        if int(top_logprobs) == 0 and not at_temperature:
+            self._row_logprobs().pop(int(row), None)
+        else:
+            self._row_logprobs()[int(row)] = int(top_logprobs)
 
     def set_row_logit_bias(self, row: int, bias: Optional[Dict[int, float]]) -> None:
         """The logit_bias of the request that occupies ``row`` (``mi_kv_set_row_logit_bias``): it replaces the row's bias,
@@ -396,7 +419,19 @@ class Engine:
                                             C.byref(sp.c), C.byref(ticket)))
         self._last_B = kv.batch_size
         self._last_topk = sp.c.top_logprobs
+        self._note_row_logprobs(kv, int(ticket.value), range(kv.batch_size), sp)
         return int(ticket.value)
+
+    def _note_row_logprobs(self, kv: KVCache, ticket: int, rows, sp: SampleArgs) -> None:
+        """A step enqueued on a cache with row logprobs settings comes back at the fixed stride: remember, per sampled
+        row, how many of its entries count (its own setting, else the call's)."""
+        mirror = kv._row_logprobs()
+        if not mirror:
+            return
+        notes = self.__dict__.setdefault("_lp_tickets", {})
+        notes[ticket] = np.asarray([mirror.get(int(r), int(sp.c.top_logprobs)) for r in rows], dtype=np.int32)
+        for old in [t for t in notes if t < ticket - 16]:
+            del notes[old]
 
     def step_enqueue_rows(self, kv: KVCache, rows, tokens=None, sample: Optional[SampleArgs] = None) -> int:
         """``mi_step_enqueue_rows``: one step on the cache rows ``rows`` only (continuous batching).  ``tokens``
@@ -417,6 +452,7 @@ class Engine:
         kv.ensure(max(offs[int(i)] for i in r) + Lq)
         L.check(L.lib().mi_step_enqueue_rows(self._h, kv._h, r.ctypes.data_as(C.POINTER(C.c_int32)), len(r), tok_ptr, Lq,
                                              C.byref(sp.c), C.byref(ticket)))
+        self._note_row_logprobs(kv, int(ticket.value), r, sp)
         return int(ticket.value)
 
     def step_enqueue_mixed(self, kv: KVCache, rows, token_lists, want=None, sample: Optional[SampleArgs] = None) -> int:
@@ -438,14 +474,21 @@ class Engine:
         L.check(L.lib().mi_step_enqueue_mixed(self._h, kv._h, r.ctypes.data_as(I32), lens.ctypes.data_as(I32),
                                               w.ctypes.data_as(I32), len(r), toks.ctypes.data_as(I32), C.byref(sp.c),
                                               C.byref(ticket)))
+        self._note_row_logprobs(kv, int(ticket.value), [ri for ri, wi in zip(r, w) if wi], sp)
         return int(ticket.value)
 
     def step_wait(self, ticket: int, batch_size: int, top_logprobs: int = 0):
+        """Results of an enqueued step.  A step whose cache had a row logprobs setting (``KVCache.set_row_logprobs``)
+        returns ``top_ids`` / ``top_logprobs`` as ``(B, 20)`` and ``top_counts`` (B,): row b's first ``top_counts[b]``
+        entries are its list, the rest is filler (-1, -inf)."""
         B = int(batch_size)
         toks = np.empty(B, dtype=np.int32)
         lp = np.empty(B, dtype=np.float32)
         p0 = np.empty(B, dtype=np.float32)
         k = int(top_logprobs)
+        counts = self.__dict__.get("_lp_tickets", {}).pop(int(ticket), None)
+        if counts is not None:
+            k = L.MI_MAX_TOP_LOGPROBS
         tk_i = np.empty((B, max(k, 1)), dtype=np.int32)
         tk_l = np.empty((B, max(k, 1)), dtype=np.float32)
         L.check(L.lib().mi_step_wait(self._h, int(ticket), toks.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -454,6 +497,8 @@ class Engine:
         res = {"tokens": toks, "logprobs": lp, "probs_row0": p0}
         if k > 0:
             res["top_ids"], res["top_logprobs"] = tk_i[:, :k], tk_l[:, :k]
+        if counts is not None:
+            res["top_counts"] = counts
         return res
 
     def score_tokens(self, kv: KVCache, tokens, targets, sample: Optional[SampleArgs] = None):

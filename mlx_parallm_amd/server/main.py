@@ -24,6 +24,9 @@ reference blocks its loop while it streams).
 Deliberate differences, each a defect of the reference's path:
   * logprobs / echo / perplexity use the KV cache and the device-side scorer (``mi_score_tokens``);
     the reference re-runs the whole sequence per generated token (main.py:564-594).
+  * under the continuous scheduler a ``logprobs`` completion without ``echo`` / ``stream`` is n rows of the shared
+    steps (``_scheduled_response``): ``n``, ``stop`` and ``seed`` work, ``finish_reason`` is the real one and ``text``
+    carries no EOS text; the reference runs it alone, one choice, ``finish_reason`` "stop".
   * temperature is applied once under top-p (the reference divides by T twice, main.py:576-579).
   * ``prompt_tps_*`` / ``decode_tps_*`` metrics are filled in (the reference never updates them).
 """
@@ -414,6 +417,23 @@ def _score_prefix(model, handle, ids: np.ndarray, sample) -> Dict[str, np.ndarra
     return {k: np.concatenate([p[k] for p in parts], axis=1) for k in parts[0]} if parts else {}
 
 
+def logprobs_sampling(temperature: float, top_p: float) -> Tuple[float, float, bool]:
+    """How a ``logprobs`` completion samples (main.py:578-581), on the exclusive path and under the scheduler alike:
+    -> (temperature, top_p, logprobs at temperature).  Greedy unless 0 < top_p < 1; the nucleus at T = 1 when the request's
+    temperature is 0; logprobs under softmax(logits / T) when the request's temperature is > 0."""
+    nucleus = 0.0 < top_p < 1.0
+    temp_eff = (temperature if temperature > 0 else 1.0) if nucleus else 0.0
+    return temp_eff, (top_p if nucleus else 1.0), temperature > 0
+
+
+def logprobs_object(hf, token_ids, token_logprobs, top) -> Dict[str, Any]:
+    """The ``logprobs`` object of one completion choice: ``top`` = one (ids, logprobs) pair per token."""
+    tokens = list(hf.convert_ids_to_tokens([int(t) for t in token_ids]))
+    return {"tokens": tokens, "token_logprobs": [float(x) for x in token_logprobs],
+            "top_logprobs": [{hf.convert_ids_to_tokens([int(j)])[0]: float(lp) for j, lp in zip(ti, tl)} for ti, tl in top],
+            "text_offset": [0] * len(tokens)}
+
+
 def completion_with_logprobs(model, tokenizer, model_id: str, request: CompletionRequest) -> CompletionResponse:
     """``logprobs`` / ``echo`` completions (main.py:457-625), single sequence.
 
@@ -455,10 +475,9 @@ def completion_with_logprobs(model, tokenizer, model_id: str, request: Completio
     gen_lps: List[float] = []
     gen_top: List[Dict[str, float]] = []
     if request.max_tokens > 0:
-        nucleus = 0.0 < top_p < 1.0
-        temp_eff = (temperature if temperature > 0 else 1.0) if nucleus else 0.0      # main.py:578-581
-        steps = generate_step(first, model, temp=temp_eff, top_p=top_p if nucleus else 1.0, logit_bias=bias, cache=cache,
-                              top_logprobs=topk, return_details=True, logprobs_at_temperature=temperature > 0,
+        temp_eff, top_p_eff, at_temperature = logprobs_sampling(temperature, top_p)
+        steps = generate_step(first, model, temp=temp_eff, top_p=top_p_eff, logit_bias=bias, cache=cache,
+                              top_logprobs=topk, return_details=True, logprobs_at_temperature=at_temperature,
                               **request_controls(request))
         for _, res in _take(steps, request.max_tokens):
             t = int(res["tokens"][0])
@@ -856,6 +875,9 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
         if (request.logprobs is not None and request.logprobs > 0) or request.echo is True:
             if request.logprobs is not None and request.logprobs > 20:
                 raise HTTPException(status_code=400, detail="logprobs must be <= 20")
+            if state.scheduler is not None and request.logprobs and request.echo is not True and not request.stream:
+                # n choices with the sampled tokens' logprobs: rows of the shared steps, nobody waits for them
+                return await _scheduled_response(state, request, tok, request.model)
             async with state.engine_lock:
                 try:
                     return await loop.run_in_executor(None, _exclusive(state, completion_with_logprobs), rec.model_instance,
@@ -953,11 +975,15 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
     """Queue one sequence; -> (future resolving to (text, n_prompt, n_completion, finish_reason), n_prompt, sequence).
     ``sequence.cancel()`` frees its KV slot when the caller gives up (timeout, client disconnect).  A request with a
     ``seed`` gives choice i the stream of ``seed + i``; without one the sequence draws from the scheduler's stream.
-    Every choice carries the request's ``logit_bias`` (set on its KV row) and ``stop`` list."""
+    Every choice carries the request's ``logit_bias`` (set on its KV row) and ``stop`` list.  A completion that asks for
+    ``logprobs`` samples as ``logprobs_sampling`` says and its sequence collects the per-token lists."""
     loop = asyncio.get_running_loop()
     fut: asyncio.Future = loop.create_future()
     ids = _ids_of(tok, text)[0]
     max_tokens, temp, top_p = _request_params(req)
+    lp_k, lp_at_t = int(getattr(req, "logprobs", None) or 0) if isinstance(req, CompletionRequest) else 0, False
+    if lp_k > 0:
+        temp, top_p, lp_at_t = logprobs_sampling(temp, top_p)
     parts: List[str] = []
     bias, stop = _request_controls(req, tok)
 
@@ -974,7 +1000,8 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
         seed = getattr(req, "seed", None)
         seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink, top_k=int(getattr(req, "top_k", 0) or 0),
                                      min_p=float(getattr(req, "min_p", 0.0) or 0.0),
-                                     seed=None if seed is None else int(seed) + choice, logit_bias=bias, stop=stop)
+                                     seed=None if seed is None else int(seed) + choice, logit_bias=bias, stop=stop,
+                                     **({"logprobs": lp_k, "logprobs_at_temperature": lp_at_t} if lp_k > 0 else {}))
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return fut, len(ids), seq
@@ -1007,8 +1034,11 @@ async def _scheduled_response(state: ServerState, request: AnyRequest, tok: Toke
     usage = CompletionUsage(prompt_tokens=results[0][1], completion_tokens=sum(r[2] for r in results),
                             total_tokens=results[0][1] + sum(r[2] for r in results))
     if isinstance(request, CompletionRequest):
+        lp_objs: List[Optional[Dict[str, Any]]] = [None] * len(results)
+        if request.logprobs:                 # (the sequences are finished: their lists no longer change)
+            lp_objs = [logprobs_object(tok._tokenizer, sub[2].token_ids, sub[2].token_logprobs, sub[2].top) for sub in subs]
         return CompletionResponse(model=model_name, usage=usage, choices=[
-            CompletionChoice(text=r[0], index=i, finish_reason=r[3]) for i, r in enumerate(results)])
+            CompletionChoice(text=r[0], index=i, logprobs=lp_objs[i], finish_reason=r[3]) for i, r in enumerate(results)])
     return ChatCompletionResponse(model=model_name, usage=usage, choices=[
         ChatCompletionChoice(index=i, message=ChatMessage(role="assistant", content=r[0].strip()), finish_reason=r[3])
         for i, r in enumerate(results)])

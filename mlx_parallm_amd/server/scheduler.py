@@ -14,6 +14,10 @@ for -- a request does not wait for the running batch to finish -- and does it on
   * a request's ``logit_bias`` is set on its row at admission (``KVCache.set_row_logit_bias``, right after the row's reset) and
     stays on the device until the row is reset for its next occupant; its ``stop`` strings are matched on the detokenised
     generated text (``StopMatcher``): the sequence finishes with reason "stop" at that step boundary, as for EOS;
+  * a request's ``logprobs`` (0..20 top entries per sampled token, optionally under ``softmax(logits / T)``) are set on its row
+    at admission next to the bias (``KVCache.set_row_logprobs``) and cleared with the row; the sequence collects, per sampled
+    token, the id, its logprob and its top list from the results of the shared steps, so such a request never takes the
+    engine away from the others;
   * while the row set is stable the next step is enqueued before the current one is read back, sampled tokens
     stay on the device (the same one-step-ahead pipelining as generate_step, utils.py:420-427); when a sequence
     finishes or a request is waiting, the step already in flight completes, its tokens for finished rows are
@@ -45,6 +49,7 @@ Sink = Callable[["Sequence", Optional[str], Optional[str]], None]
 
 MAX_ROW_LOGIT_BIAS = 1024      # MI_MAX_ROW_LOGIT_BIAS (mi355_decode.h): entries of one request's logit_bias
 MAX_STOP_SEQUENCES = 4         # as the OpenAI API
+MAX_TOP_LOGPROBS = 20          # MI_MAX_TOP_LOGPROBS (mi355_decode.h)
 
 
 class StopMatcher:
@@ -128,9 +133,17 @@ class Sequence:
 
     def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok, *, top_k: int = 0,
                  min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
-                 stop: Optional[List[str]] = None):
+                 stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False):
         if int(top_k) < 0:
             raise ValueError("top_k must be >= 0 (0 = off)")
+        if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"logprobs must be an int in [0, {MAX_TOP_LOGPROBS}]")
+        # per sampled token, in sampling order (an EOS that ends the sequence included, tokens behind a stop hit included):
+        # its id, its logprob and -- logprobs > 0 -- its top list as (ids, logprobs) arrays of that length
+        self.logprobs, self.logprobs_at_temperature = int(logprobs), bool(logprobs_at_temperature)
+        self.token_ids: List[int] = []
+        self.token_logprobs: List[float] = []
+        self.top: List[tuple] = []
         if not 0.0 <= float(min_p) <= 1.0:
             raise ValueError("min_p must be in [0, 1] (0 = off)")
         self.logit_bias = check_logit_bias(logit_bias)     # set on the sequence's cache row at admission
@@ -196,6 +209,7 @@ class ContinuousScheduler:
         self.steps = 0                     # decode steps executed
         self.prefills = 0
         self.max_rows_seen = 0
+        self.borrows = 0                   # times somebody took the engine away from the steps (borrow_engine)
         # chunked prefill: an arriving prompt enters the cache in chunks of at most `chunk_tokens` tokens, each chunk in
         # the SAME pass over the weights as the live rows' decode step (engine.step_enqueue_mixed).  0 = the older
         # behaviour: the whole prompt is prefilled alone while the live rows wait.
@@ -245,9 +259,12 @@ class ContinuousScheduler:
     # ------------------------------------------------------------------ client side (any thread)
     def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, *, top_k: int = 0,
                min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
-               stop: Optional[List[str]] = None) -> Sequence:
+               stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False) -> Sequence:
         seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer),
-                       top_k=top_k, min_p=min_p, seed=seed, logit_bias=logit_bias, stop=stop)
+                       top_k=top_k, min_p=min_p, seed=seed, logit_bias=logit_bias, stop=stop, logprobs=logprobs,
+                       logprobs_at_temperature=logprobs_at_temperature)
+        if (seq.logprobs or seq.logprobs_at_temperature) and not hasattr(self.kv, "set_row_logprobs"):
+            raise ValueError("logprobs: this KV cache has no per-row logprobs setting (set_row_logprobs)")
         if seq.logit_bias:
             if not hasattr(self.kv, "set_row_logit_bias"):
                 raise ValueError("logit_bias: this KV cache has no per-row logit_bias (set_row_logit_bias)")
@@ -293,6 +310,7 @@ class ContinuousScheduler:
             s = self.s
             with s.cv:
                 s._waiters += 1
+                s.borrows += 1
                 s.cv.notify_all()
             while True:
                 with s.cv:
@@ -333,9 +351,15 @@ class ContinuousScheduler:
         seq.finished = reason
         self._emit(seq, tail if tail else None, reason)
 
-    def _on_token(self, seq: Sequence, tok: int) -> None:
+    def _on_token(self, seq: Sequence, tok: int, res=None, i: int = 0) -> None:
+        """Sampled row ``i`` of the step results ``res`` gave ``seq`` the token ``tok``."""
         eos = self.tok.eos_token_id
         seq.last_token = tok
+        if res is not None and (seq.logprobs or seq.logprobs_at_temperature):
+            seq.token_ids.append(tok)
+            seq.token_logprobs.append(float(res["logprobs"][i]))
+            if seq.logprobs:               # (the row's own count of entries, at the front of its fixed-stride list)
+                seq.top.append((np.array(res["top_ids"][i, :seq.logprobs]), np.array(res["top_logprobs"][i, :seq.logprobs])))
         if tok == eos:
             self._finish(seq, "stop")
             return
@@ -386,6 +410,8 @@ class ContinuousScheduler:
         self.kv.reset_row(slot)                   # (also clears the bias of the row's previous occupant)
         if seq.logit_bias:                        # ahead of the row's first sampling step: the prefill below, or the last chunk
             self.kv.set_row_logit_bias(slot, seq.logit_bias)
+        if seq.logprobs or seq.logprobs_at_temperature:
+            self.kv.set_row_logprobs(slot, seq.logprobs, seq.logprobs_at_temperature)
         seq.prefill_pos = 0
         if self.prefix_cache:                     # full blocks of an earlier prompt with the same prefix are mapped, not recomputed
             seq.prefill_pos = self.kv.prefix_attach(slot, seq.prompt)
@@ -400,7 +426,7 @@ class ContinuousScheduler:
             self.kv.prefix_publish(slot, seq.prompt)
         if self.metrics is not None:
             self.metrics.record_throughput({"prompt_tokens": float(len(seq.prompt)), "prompt_time": time.perf_counter() - t0})
-        self._on_token(seq, int(res["tokens"][0]))
+        self._on_token(seq, int(res["tokens"][0]), res, 0)
 
     def _mixed_step(self, decoding: List[Sequence], prefilling: List[Sequence]) -> None:
         """One pass over the weights: every live row decodes one token AND up to `chunk_tokens` prompt tokens of the
@@ -439,12 +465,12 @@ class ContinuousScheduler:
                 self.chunks += 1
                 if self.prefix_cache and s.prefill_pos == len(s.prompt):
                     self.kv.prefix_publish(s.slot, s.prompt)      # (enqueued above: later readers are ordered behind it)
-        for s, t in zip(wanted, res["tokens"] if wanted else []):
+        for i, (s, t) in enumerate(zip(wanted, res["tokens"] if wanted else [])):
             if s in prefilling:
                 s.prefilled = True
                 self.prefills += 1
             if not s.finished:
-                self._on_token(s, int(t))
+                self._on_token(s, int(t), res, i)
         if self.metrics is not None:
             self.metrics.record_throughput({"decode_tokens": float(len(decoding)), "decode_time": dt,
                                             "prompt_tokens": float(n_chunk_tokens), "prompt_time": dt})
@@ -457,7 +483,9 @@ class ContinuousScheduler:
             if s is not None and s.finished:
                 self.slots[i] = None
                 if self.paged:                 # the row's blocks go back to the arena now (waiting requests count on them)
-                    self.kv.reset_row(i)
+                    self.kv.reset_row(i)       # (its logprobs setting goes with them)
+                elif s.logprobs or s.logprobs_at_temperature:
+                    self.kv.set_row_logprobs(i, 0, False)     # a contiguous row is reset at its next admission: clear now
 
     def _drop_cancelled_pending(self) -> None:
         with self.cv:
@@ -478,9 +506,9 @@ class ContinuousScheduler:
             if inflight is not None:
                 ticket, seqs = inflight
                 res = eng.step_wait(ticket, len(seqs))
-                for s, t in zip(seqs, res["tokens"]):
+                for i, (s, t) in enumerate(zip(seqs, res["tokens"])):
                     if not s.finished:
-                        self._on_token(s, int(t))
+                        self._on_token(s, int(t), res, i)
                 inflight = None
                 sp_keep.clear()
             with self.cv:
@@ -554,9 +582,9 @@ class ContinuousScheduler:
                     ticket, seqs = inflight
                     res = eng.step_wait(ticket, len(seqs))
                     self.steps += 1
-                    for s, t in zip(seqs, res["tokens"]):
+                    for i, (s, t) in enumerate(zip(seqs, res["tokens"])):
                         if not s.finished:
-                            self._on_token(s, int(t))
+                            self._on_token(s, int(t), res, i)
                     inflight = nxt
                     if len(sp_keep) > 2:
                         del sp_keep[0]
@@ -628,3 +656,7 @@ class ReplicaPool:
     @property
     def max_rows_seen(self) -> int:
         return max(r.max_rows_seen for r in self.replicas)
+
+    @property
+    def borrows(self) -> int:
+        return sum(r.borrows for r in self.replicas)
