@@ -512,6 +512,12 @@ __device__ __forceinline__ float row16_max(float v) {
   return v;
 }
 
+// A piece of a cached K / V row in the matrix-core kernel: one CU reads it once per step, and gigabytes of weights and other
+// rows pass before the next step reads it again, so it goes past the caches like the weight streams (gemv_f32.hip: load_w).
+// The KV append and the prologue's loads keep the default policy.
+template <typename V>
+__device__ __forceinline__ V load_kv(const void* p) { return __builtin_nontemporal_load((const V*)p); }
+
 // (a call, not an assignment: the address is computed before the value, which the epilogue's schedule depends on)
 template <typename T>
 __device__ __forceinline__ void store_out(T* p, T v) { *p = v; }
@@ -525,11 +531,26 @@ __device__ __forceinline__ void store_out(T* p, T v) { *p = v; }
 // QS (consumer_combine, float32 only): the q / k_new / v_new vectors are not read from c.qkv -- the q|k|v linear ran
 // publish-only (gemm_skinny.hip, skinny_kernel<bf16_publish, ..>) and each lane group adds the K slices' partial rows of ITS vector here,
 // at the place of its one load, with the arithmetic of that linear's last arriver (common.h: add_slice, rs_from_sumsq,
-// scale_row).  Up to 8 slices, all fetched in one round trip behind the first round's K/V loads.
-template <typename T, int D, int G, bool NORM, bool PAGED, bool QS = false>
+// scale_row).  QSN = 2, 4 or 8 slices (the class of the launch's count: 2, 3..4, 5..8; inside a class a slice past the last
+// re-loads the last), all fetched in one round trip in front of the first round's K/V loads.
+// Owners only: the prologue -- its global loads and its arithmetic -- runs in the lane groups that own a vector and nowhere
+// else.  A split that does not own the new position has the G query heads only (the new key and value are neither loaded,
+// summed, rotated nor scored there; its ninth merge slot is written neutral by wave NWV - 1); the new value loads neither
+// cos / sin nor norm weights; a wave without an owner (wave * 4 >= vectors) goes from row and length straight to
+// issue_k / issue_v.  The vectors stay PACKED from wave 0 up (4 per wave): a wave's instruction issue costs the same with
+// 16 or with 64 live lanes, so one vector per wave would put the prologue's ~300 instructions and its wait in front of round
+// 0 in G + 2 waves instead of (G + 5) / 4, for the same bytes on the CU's address path; at G = 4 six waves of eight (seven
+// in the splits without the new position) now issue round 0 at entry.  In the disassembly of
+// attn_decode_mfma_qs_kernel<128,4,false,false,4> an owner wave issues 12 prologue loads (8 slice, 4 cos / sin; the slices'
+// row sums are scalar loads), then the 16 K / V loads, and its arithmetic waits vmcnt(23) .. vmcnt(16); the parent issued
+// 28 + 16 in every wave.  Measured ("owners only"): 17.58 -> 16.6-16.9 us per launch under the profiler, barrier
+// at 5.5 us of the workgroup instead of 7.0.
+template <typename T, int D, int G, bool NORM, bool PAGED, int QSN = 0>
 __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, unsigned char* smem AT_TRACE_PARAM) {
   AT_STAMP(0);
+  constexpr bool QS = QSN > 0;
   static_assert(!QS || sizeof(T) == 4, "partial q|k|v rows: float32 activations");
+  static_assert(QSN == 0 || QSN == 2 || QSN == 4 || QSN == 8, "K slices fetched: the classes 2, 3..4, 5..8");
   constexpr bool F32 = sizeof(T) == 4;           // float32 q / caches / outputs, multiplied exactly on v_mfma_f32_16x16x4_f32
   constexpr bool BLK = sizeof(T) == 4 && G <= 4; // float32, at most 4 query heads per kv head: the 16-block MFMA loop
   static_assert(D % 32 == 0 && D <= 128 && G <= 8 && (!F32 || D % 64 == 0 || (D == 96 && BLK && !QS)),
@@ -582,14 +603,14 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
       const int key = min(k0 + c16, klast);
       const size_t ro = kv_elem<PAGED>(s, kb, kh, key);
 #pragma unroll
-      for (int i = 0; i < NP; ++i) kf32[i] = *(const f32x4*)(kc + ro + 16 * i + 4 * g4);
+      for (int i = 0; i < NP; ++i) kf32[i] = load_kv<f32x4>(kc + ro + 16 * i + 4 * g4);
     } else {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int key = min(k0 + 16 * t + c16, klast);
         const size_t ro = kv_elem<PAGED>(s, kb, kh, key);
 #pragma unroll
-        for (int kk = 0; kk < KK; ++kk) kf[t][kk] = *(const u32x4*)(kc + ro + 32 * kk + 8 * g4);
+        for (int kk = 0; kk < KK; ++kk) kf[t][kk] = load_kv<u32x4>(kc + ro + 32 * kk + 8 * g4);
       }
     }
   };
@@ -601,15 +622,15 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
         const int key = min(k0 + 4 * g4 + r, klast);
         const size_t ro = kv_elem<PAGED>(s, kb, kh, key);
 #pragma unroll
-        for (int h = 0; h < NH; ++h) vv32[r][h] = *(const f32x4*)(vc + ro + 64 * h + 4 * c16);
-        if constexpr (VT) vt32[r] = *(const f32x2*)(vc + ro + 64 * NH + 2 * c16);
+        for (int h = 0; h < NH; ++h) vv32[r][h] = load_kv<f32x4>(vc + ro + 64 * h + 4 * c16);
+        if constexpr (VT) vt32[r] = load_kv<f32x2>(vc + ro + 64 * NH + 2 * c16);
       }
     } else {                                     // 32 keys x (D/8) 16-byte pieces, lane-linear: piece = i * 64 + lane
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int piece = i * 64 + lane, kl = piece / (D / 8), dc = piece % (D / 8);
         const int key = min(k0 + kl, klast);
-        vrow[i] = *(const u32x4*)(vc + kv_elem<PAGED>(s, kb, kh, key) + 8 * dc);
+        vrow[i] = load_kv<u32x4>(vc + kv_elem<PAGED>(s, kb, kh, key) + 8 * dc);
       }
     }
   };
@@ -624,118 +645,161 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     issue_v(s0);
   }
 
-  // ---- prologue, spread over the workgroup: lane group (wave, gq) = vector vi owns ONE of the G query
-  // heads (vi < G), the new key (vi == G) or the new value (vi == G + 1): raw load, RMSNorm, RoPE,
-  // result to LDS.  One code path for every group (pointers are selected, nothing branches), so a wave
-  // spends the time of one vector, not of G + 1.
+  // ---- prologue, spread over the workgroup: lane group (wave, gq) = vector vi owns ONE of the G query heads (vi < G), the
+  // new key (vi == G) or the new value (vi == G + 1): raw load, RMSNorm, RoPE, result to LDS.  Owners only (see the header):
+  //   * a split that does not own the new position has G vectors, not G + 2 -- the new key and the new value are neither
+  //     loaded, summed, rotated nor scored there;
+  //   * a lane group without a vector is masked out of every load and every instruction of the prologue;
+  //   * a wave without any owner (wv * 4 >= nvec: waves 2..7 at G = 4 in the owning split, 1..7 in the others) branches
+  //     round it -- a scalar branch: from row and length straight to issue_k / issue_v.
+  // Inside an owner wave the lane groups run one path side by side, so the wave spends the time of one vector.
   const int vi = wave * 4 + gq;
-  const bool is_q = vi < G, is_k = vi == G, is_v = vi == G + 1;
+  const int nvec = owner ? G + 2 : G;
+  const bool is_q = vi < G, is_k = owner && vi == G, is_v = owner && vi == G + 1;
+  const bool has_vec = vi < nvec, rot = is_q || is_k;          // rot: the vectors that are normed and rotated
+  const bool wave_owns = __builtin_amdgcn_readfirstlane(wave) * 4 < nvec;
   const bool hi = li >= 8;
   const T* src = row + (is_q ? (size_t)(kh * G + vi) * D : is_k ? (size_t)nq + (size_t)kh * D
                                                                : (size_t)nq + (size_t)(s.Hkv + kh) * D) + li * EPL;
   uint32_t raw[NW32];
-  constexpr int QSN = QS ? 8 : 1;                // K slices fetched per lane group (host: qkv_ksplit <= 8)
-  f32x4 qs_p[QSN][QS ? EPL / 4 : 1];
-  float qs_sq[QSN];
-  if constexpr (QS) {                            // straight-line: a slice past the last re-loads the last
-    const size_t ld = (size_t)nq + 2 * (size_t)s.Hkv * D, col = (size_t)(src - row);
-#pragma unroll
-    for (int j = 0; j < QSN; ++j) {
-      const int sl = min(j, c.qkv_ksplit - 1);
-      const float* pp = c.qkv_pub + ((size_t)sl * 8 + b) * ld + col;
-#pragma unroll
-      for (int i = 0; i < EPL / 4; ++i) qs_p[j][i] = *(const f32x4*)(pp + 4 * i);
-      qs_sq[j] = c.qkv_pub_sq[sl * 8 + b];
-    }
-  } else {
-    load_raw<NW32>(src, raw);
-  }
+  // K slices fetched per lane group: the launch picks the class of c.qkv_ksplit (2, 3..4, 5..8 -> QSN 2, 4, 8)
+  f32x4 qs_p[QS ? QSN : 1][QS ? EPL / 4 : 1];
+  float qs_sq[QS ? QSN : 1];
   float cs[EPL], sn[EPL];
-  {
-    const float* cp = c.cos_tab + (size_t)pos * (D / 2) + (li & 7) * EPL;
-    const float* sp = c.sin_tab + (size_t)pos * (D / 2) + (li & 7) * EPL;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) { cs[e] = cp[e]; sn[e] = sp[e]; }
-  }
   uint32_t r0[NW32];
-  if constexpr (NORM) load_raw<NW32>((const T*)(is_k ? c.k_norm_w : c.q_norm_w) + li * EPL, r0);
   constexpr int KV_BEHIND = PRO_FIRST ? NP + 4 * NH + (VT ? 4 : 0) : 0;   // K / V loads per lane of a float32 round, in the queue behind the prologue's
+  auto pro_loads = [&]() {                       // (runs under both tests below, in the lane groups that own a vector)
+    {
+      if constexpr (QS) {                        // straight-line: inside a class, a slice past the last re-loads the last
+        const size_t ld = (size_t)nq + 2 * (size_t)s.Hkv * D, col = (size_t)(src - row);
+#pragma unroll
+        for (int j = 0; j < QSN; ++j) {
+          const int sl = min(j, c.qkv_ksplit - 1);
+          const float* pp = c.qkv_pub + ((size_t)sl * 8 + b) * ld + col;
+#pragma unroll
+          for (int i = 0; i < EPL / 4; ++i) qs_p[j][i] = *(const f32x4*)(pp + 4 * i);
+          qs_sq[j] = c.qkv_pub_sq[sl * 8 + b];
+        }
+      } else {
+        load_raw<NW32>(src, raw);
+      }
+      if (rot) {                                 // the new value is neither normed nor rotated: no tables, no weights
+        const float* cp = c.cos_tab + (size_t)pos * (D / 2) + (li & 7) * EPL;
+        const float* sp = c.sin_tab + (size_t)pos * (D / 2) + (li & 7) * EPL;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) { cs[e] = cp[e]; sn[e] = sp[e]; }
+        if constexpr (NORM) load_raw<NW32>((const T*)(is_k ? c.k_norm_w : c.q_norm_w) + li * EPL, r0);
+      }
+    }
+  };
+  auto pro_math = [&]() {
+    // (thread 0, which writes the stamps, always owns query head 0)
+    AT_CLOCK(t_issued);
+    AT_LANDED(KV_BEHIND);
+    AT_STAMP_AT(15, t_issued);
+    AT_STAMP(1);
+    {
+      if constexpr (QS) {                        // the q|k|v linear's combine and epilogue: slices in order from zero, then x rs
+        float tot = 0.f;
+#pragma unroll
+        for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) tot = add_slice(tot, qs_sq[j]);
+        const float rs = rs_from_sumsq(tot, c.hidden_k, c.qkv_eps);
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          float a = 0.f;
+#pragma unroll
+          for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) a = add_slice(a, qs_p[j][e >> 2][e & 3]);
+          raw[e] = __float_as_uint(scale_row(a, rs));
+        }
+      }
+      uint32_t pk[NW32];
+      if (rot) {
+        float x[EPL];
+        raw_to_f32<T, EPL, NW32>(raw, x);
+        if constexpr (NORM) {
+          float nw[EPL];
+          raw_to_f32<T, EPL, NW32>(r0, nw);
+          float ss = 0.f;
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) ss = fmaf(x[e], x[e], ss);
+          ss = row16_sum(ss);
+          const float rs = 1.0f / sqrtf(ss / (float)D + c.eps);
+#pragma unroll
+          for (int e = 0; e < EPL; ++e)
+            x[e] = to_f32(store_act<T>(to_f32(store_act<T>(x[e] * rs, s.rnd)) * nw[e], s.rnd));
+        }
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const float p = row16_ror8(x[e]);
+          const float o = hi ? (p * sn[e] + x[e] * cs[e]) : (x[e] * cs[e] - p * sn[e]);
+          x[e] = to_f32(store_act<T>(o, s.rnd));
+        }
+        if constexpr (F32) {
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) pk[e] = __float_as_uint(x[e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < EPL / 2; ++e) pk[e] = pack2<T>(x[2 * e], x[2 * e + 1]);
+        }
+        // q heads at rows 0..G-1 of q_sh, the new key at row G (a split without the new position leaves row G
+        // unwritten, and does not read it: the new key's scores are not computed there)
+#pragma unroll
+        for (int i = 0; i < NW32; ++i) ((uint32_t*)(q_sh + (size_t)vi * D + li * EPL))[i] = pk[i];
+      } else {                                   // v: untouched bits
+#pragma unroll
+        for (int i = 0; i < NW32; ++i) pk[i] = raw[i];
+      }
+      if (!is_q && pos < s.cap) {                // KV append (base.py:66-85); is_k / is_v: only in the split that owns pos
+        T* dst = (is_k ? kc : vc) + kv_elem<PAGED>(s, kb, kh, pos) + li * EPL;
+#pragma unroll
+        for (int i = 0; i < NW32; ++i) ((uint32_t*)dst)[i] = pk[i];
+      }
+      if (is_v) {                                // merge slot 8 = the new key: O = v_new (for every head)
+        float vf[EPL];
+        raw_to_f32<T, EPL, NW32>(raw, vf);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) st_o[(NWV * G + g) * D + li * EPL + e] = vf[e];
+      }
+    }
+  };
   if constexpr (PRO_FIRST) {
+    // float32, contiguous: the owners' loads, then ONE copy of round 0's issue for every wave, then the owners' arithmetic.
+    // It waits for vmcnt(KV_BEHIND), not for an empty queue: at the join behind the first branch the owners' loads are
+    // pending on one path and unknown on the other, which keeps their distance to the end of the queue exact.  (With a
+    // copy of the issue in each arm of `if (wave_owns) .. else ..` hipcc lets the arm without the prologue fall into the
+    // other under an empty exec mask, counts that arm's K / V loads as pending on the owners' path and puts vmcnt(7) ..
+    // vmcnt(1) in front of the owners' K / V issue: a round trip of the prologue's loads before round 0 leaves.)
+    if (wave_owns) if (has_vec) pro_loads();
     __builtin_amdgcn_sched_barrier(0);
     issue_k(s0);
     issue_v(s0);
-  }
-  // every global load the prologue waits for is in the queue ahead of this; what the arithmetic below waits for is
-  // vmcnt(KV_BEHIND), not an empty queue.  (Two barriers: where a hook used to sit between them; with one, hipcc allocates
-  // the body's registers differently.)
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_sched_barrier(0);
-  AT_CLOCK(t_issued);
-  AT_LANDED(KV_BEHIND);
-  AT_STAMP_AT(15, t_issued);
-  AT_STAMP(1);
-  if constexpr (QS) {                            // the q|k|v linear's combine and epilogue: slices in order from zero, then x rs
-    float tot = 0.f;
-#pragma unroll
-    for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) tot = add_slice(tot, qs_sq[j]);
-    const float rs = rs_from_sumsq(tot, c.hidden_k, c.qkv_eps);
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      float a = 0.f;
-#pragma unroll
-      for (int j = 0; j < QSN; ++j) if (j < c.qkv_ksplit) a = add_slice(a, qs_p[j][e >> 2][e & 3]);
-      raw[e] = __float_as_uint(scale_row(a, rs));
-    }
-  }
-  float x[EPL];
-  raw_to_f32<T, EPL, NW32>(raw, x);
-  if constexpr (NORM) {
-    float nw[EPL];
-    raw_to_f32<T, EPL, NW32>(r0, nw);
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) ss = fmaf(x[e], x[e], ss);
-    ss = row16_sum(ss);
-    const float rs = 1.0f / sqrtf(ss / (float)D + c.eps);
-#pragma unroll
-    for (int e = 0; e < EPL; ++e)
-      x[e] = to_f32(store_act<T>(to_f32(store_act<T>(x[e] * rs, s.rnd)) * nw[e], s.rnd));
-  }
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) {
-    const float p = row16_ror8(x[e]);
-    const float o = hi ? (p * sn[e] + x[e] * cs[e]) : (x[e] * cs[e] - p * sn[e]);
-    x[e] = to_f32(store_act<T>(o, s.rnd));
-  }
-  uint32_t pk[NW32];
-  if constexpr (F32) {
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) pk[e] = is_v ? raw[e] : __float_as_uint(x[e]);
+    // (Two barriers: where a hook used to sit between them; with one, hipcc allocates the body's registers differently.)
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave_owns) if (has_vec) pro_math();
   } else {
-#pragma unroll
-    for (int e = 0; e < EPL / 2; ++e) pk[e] = is_v ? raw[e] : pack2<T>(x[2 * e], x[2 * e + 1]);   // v: untouched bits
-  }
-  if (is_q || is_k) {                            // q heads at rows 0..G-1 of q_sh, the new key at row G
-#pragma unroll
-    for (int i = 0; i < NW32; ++i) ((uint32_t*)(q_sh + (size_t)vi * D + li * EPL))[i] = pk[i];
-  }
-  if (owner && (is_k || is_v) && pos < s.cap) {  // KV append (base.py:66-85)
-    T* dst = (is_k ? kc : vc) + kv_elem<PAGED>(s, kb, kh, pos) + li * EPL;
-#pragma unroll
-    for (int i = 0; i < NW32; ++i) ((uint32_t*)dst)[i] = pk[i];
-  }
-  if (is_v) {                                    // merge slot 8 = the new key: O = v_new (for every head)
-    float vf[EPL];
-    raw_to_f32<T, EPL, NW32>(raw, vf);
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) st_o[(NWV * G + g) * D + li * EPL + e] = owner ? vf[e] : 0.f;
+    // round 0 is out already: loads and arithmetic under ONE branch.  (Under two, hipcc counts the loads as pending on the
+    // path that skips the arithmetic, and every wave meets vmcnt(0) -- the whole of round 0 -- behind the barrier.)
+    if (wave_owns) if (has_vec) {
+      pro_loads();
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
+      pro_math();
+    }
   }
   const float sc2 = c.scale * LOG2E;
   __syncthreads();
   AT_STAMP(2);
-  if (wave == NWV - 1) {                         // scores of the new key: q_sh rows 0..G-1 against row G
+  if (wave == NWV - 1 && !owner) {
+    // A split without the new position: merge slot 8 is neutral -- zeros under the maximum -1e30 and the sum 0, the words
+    // the parent wrote there from a loaded and rotated new key -- and nothing of the new key or value is read for it.  Such
+    // a split leaves q_sh row G unwritten (nothing reads it); every word the merge below reads is written.
+    for (int i = lane; i < G * D / 4; i += 64) *(f32x4*)(st_o + NWV * G * D + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (lane < G) { st_m[NWV * G + lane] = -1e30f; st_l[NWV * G + lane] = 0.f; }
+  }
+  if (wave == NWV - 1 && owner) {                // scores of the new key: q_sh rows 0..G-1 against row G
     uint32_t kn[NW32];
 #pragma unroll
     for (int i = 0; i < NW32; ++i) kn[i] = ((const uint32_t*)(q_sh + (size_t)G * D + li * EPL))[i];
@@ -752,7 +816,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
         for (int i = 0; i < NW32; ++i) d = dot2<T>(kn[i], ((const uint32_t*)(q_sh + (size_t)g * D + li * EPL))[i], d);
       }
       d = row16_sum(d) * sc2;
-      if (li == 0 && gq + 4 * j < G) { st_m[NWV * G + g] = owner ? d : -1e30f; st_l[NWV * G + g] = owner ? 1.f : 0.f; }
+      if (li == 0 && gq + 4 * j < G) { st_m[NWV * G + g] = d; st_l[NWV * G + g] = 1.f; }
     }
   }
   u32x4 qf[F32 ? 1 : KK];
@@ -1052,11 +1116,28 @@ __global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_kernel(AttnDecodeCa
 }
 
 // consumer_combine: the same launch with the q|k|v partial rows added in the prologue (a kernel of its own: the
-// ordinary instantiations keep their code and registers)
-template <int D, int G, bool NORM, bool PAGED>
+// ordinary instantiations keep their code and registers).  QSN: the K slices each owner fetches -- 2, 4 or 8 for the
+// q|k|v launch's 2, 3..4 or 5..8 (launch_mfma_qs_n), so the launch of the headline shape (4 slices) fetches 4, not 8
+template <int D, int G, bool NORM, bool PAGED, int QSN>
 __global__ __launch_bounds__(NWV * 64) void attn_decode_mfma_qs_kernel(AttnDecodeCall c AT_TRACE_PARAM) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  attn_decode_mfma_body<float, D, G, NORM, PAGED, true>(c, smem AT_TRACE_ARG);
+  attn_decode_mfma_body<float, D, G, NORM, PAGED, QSN>(c, smem AT_TRACE_ARG);
+}
+
+template <int D, int G, bool NORM, bool PAGED, int QSN>
+int launch_mfma_qs(const AttnDecodeCall& c, const dim3 grid, hipStream_t st AT_TRACE_PARAM) {
+  constexpr size_t lds = attn_mfma_lds_total<G, D, 4>();
+  auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, PAGED, QSN>;
+  MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+template <int D, int G, bool NORM, bool PAGED>
+int launch_mfma_qs_n(const AttnDecodeCall& c, const dim3 grid, hipStream_t st AT_TRACE_PARAM) {
+  if (c.qkv_ksplit <= 2) return launch_mfma_qs<D, G, NORM, PAGED, 2>(c, grid, st AT_TRACE_ARG);
+  if (c.qkv_ksplit <= 4) return launch_mfma_qs<D, G, NORM, PAGED, 4>(c, grid, st AT_TRACE_ARG);
+  return launch_mfma_qs<D, G, NORM, PAGED, 8>(c, grid, st AT_TRACE_ARG);
 }
 
 template <typename T, int D, int G, bool NORM>
@@ -1074,18 +1155,7 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
     } else if constexpr (sizeof(T) == 4) {
       if (c.qkv_pub_sq == nullptr || c.qkv_ksplit < 2 || c.qkv_ksplit > 8 || s.B > 8 || c.hidden_k <= 0)
         return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need 2..8 K slices and at most 8 sequences");
-      constexpr size_t lds = attn_mfma_lds_total<G, D, 4>();
-      if (s.btab) {
-        auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, true>;
-        MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
-      } else {
-        auto kern = attn_decode_mfma_qs_kernel<D, G, NORM, false>;
-        MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
-      }
-      MI_HIP(hipGetLastError());
-      return MI_OK;
+      return s.btab ? launch_mfma_qs_n<D, G, NORM, true>(c, grid, st AT_TRACE_ARG) : launch_mfma_qs_n<D, G, NORM, false>(c, grid, st AT_TRACE_ARG);
     } else {
       return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need float32 activations");
     }
