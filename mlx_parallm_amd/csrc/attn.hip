@@ -12,7 +12,7 @@
 // (sequence, kv-head) are one contiguous stream; a wave reads four rows per instruction
 // (16 lanes x 16 B per 128-element bf16 row).  K/V go straight to VGPRs (read once, no reuse
 // across waves); the GQA group (Hq/Hkv query heads) shares every K/V row read.
-#include "kernels.h"
+#include "attn_dispatch.h"
 
 namespace mi {
 
@@ -315,30 +315,11 @@ template <typename AT, typename KT, int D>
 int launch_attn_g(const AttnCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   const dim3 grid(c.nsplit, s.B * s.Hkv, s.L), block(256);
-  const int G = s.Hq / s.Hkv;
-#define AK(GV) do { if (s.btab) hipLaunchKernelGGL((attn_kernel<AT, KT, D, GV, true>), grid, block, 0, st, c); \
-                    else hipLaunchKernelGGL((attn_kernel<AT, KT, D, GV, false>), grid, block, 0, st, c); } while (0)
-  if constexpr (D == 96) {                        // Phi-3's width: the groups the other attention kernels serve at it
-    switch (G) {
-      case 1: AK(1); break;
-      case 2: AK(2); break;
-      case 4: AK(4); break;
-      default: return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
-    }
-  } else {
-  switch (G) {
-    case 1: AK(1); break;
-    case 2: AK(2); break;
-    case 3: AK(3); break;
-    case 4: AK(4); break;
-    case 5: AK(5); break;
-    case 6: AK(6); break;
-    case 8: AK(8); break;
-    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
-  }
-  }
-#undef AK
-  MI_HIP(hipGetLastError());
+  MI_TRY(attn_dispatch<D>("attention", s, [&](auto g, auto paged) {
+    hipLaunchKernelGGL((attn_kernel<AT, KT, D, g(), paged()>), grid, block, 0, st, c);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }));
   if (c.nsplit > 1) {
     hipLaunchKernelGGL((attn_combine_kernel<AT>), dim3(s.B * s.L * s.Hq), dim3(D), 0, st, c.partial,
                        (AT*)c.out, c.nsplit, D, s.rnd);
@@ -359,34 +340,34 @@ int launch_attn_d(const AttnCall& c, hipStream_t st) {
   return fail(MI_ERR_UNSUPPORTED, "attention: head_dim must be 16, 32, 64, 96 or 128");
 }
 
-
 }  // namespace
 
 int launch_rope_append(const RopeAppendCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   if (s.D % 2 != 0) return fail(MI_ERR_UNSUPPORTED, "rope: head_dim must be even");
   if (s.D == 128 && s.rnd == RND_NONE && s.L > 1 && s.kv == s.act && (s.act == MI_BF16 || s.act == MI_F16)) {
-    const dim3 grid_r(s.B * s.L), block_r(256);
-    if (s.act == MI_BF16) {
-      if (s.btab) hipLaunchKernelGGL((rope_append_rows_kernel<bf16, true>), grid_r, block_r, 0, st, c);
-      else hipLaunchKernelGGL((rope_append_rows_kernel<bf16, false>), grid_r, block_r, 0, st, c);
-    } else {
-      if (s.btab) hipLaunchKernelGGL((rope_append_rows_kernel<f16, true>), grid_r, block_r, 0, st, c);
-      else hipLaunchKernelGGL((rope_append_rows_kernel<f16, false>), grid_r, block_r, 0, st, c);
-    }
-    MI_HIP(hipGetLastError());
-    return MI_OK;
+    const dim3 grid(s.B * s.L), block(256);
+    auto rows = [&](auto at) {
+      return attn_dispatch_paged(s, [&](auto paged) {
+        hipLaunchKernelGGL((rope_append_rows_kernel<decltype(at), paged()>), grid, block, 0, st, c);
+        MI_HIP(hipGetLastError());
+        return MI_OK;
+      });
+    };
+    return s.act == MI_BF16 ? rows(bf16{}) : rows(f16{});
   }
   const dim3 grid(s.Hq + 2 * s.Hkv, s.B * s.L), block(64);
-#define RA(AT, KT) do { if (s.btab) hipLaunchKernelGGL((rope_append_kernel<AT, KT, true>), grid, block, 0, st, c); \
-                        else hipLaunchKernelGGL((rope_append_kernel<AT, KT, false>), grid, block, 0, st, c); } while (0)
-  if (s.act == MI_F32 && s.kv == MI_F32) RA(float, float);
-  else if (s.act == MI_BF16 && s.kv == MI_BF16) RA(bf16, bf16);
-  else if (s.act == MI_F16 && s.kv == MI_F16) RA(f16, f16);
-  else return fail(MI_ERR_UNSUPPORTED, "rope_append: activation / KV dtype combination not supported");
-#undef RA
-  MI_HIP(hipGetLastError());
-  return MI_OK;
+  auto heads = [&](auto at) {                         // activations and cache of one type
+    return attn_dispatch_paged(s, [&](auto paged) {
+      hipLaunchKernelGGL((rope_append_kernel<decltype(at), decltype(at), paged()>), grid, block, 0, st, c);
+      MI_HIP(hipGetLastError());
+      return MI_OK;
+    });
+  };
+  if (s.act == MI_F32 && s.kv == MI_F32) return heads(float{});
+  if (s.act == MI_BF16 && s.kv == MI_BF16) return heads(bf16{});
+  if (s.act == MI_F16 && s.kv == MI_F16) return heads(f16{});
+  return fail(MI_ERR_UNSUPPORTED, "rope_append: activation / KV dtype combination not supported");
 }
 
 int launch_attention(const AttnCall& c, hipStream_t st) {

@@ -15,6 +15,8 @@
 //     (sequence, kv-head) combines them (agent-scope release -> ticket -> acquire; nobody waits).
 #include <type_traits>
 
+#include "attn_dispatch.h"
+#include "attn_mfma.h"
 #include "gemv_phase.h"
 
 namespace mi {
@@ -46,8 +48,6 @@ unsigned long long* dbg_trace_slot(int N, int K, int grid, int epi, int M, int k
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -432,39 +432,7 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecodeCall c) {
 //     i of the group receives column i) -- conflict-free, and exactly the key order of P above;
 //   * lane (c16 = head, g) ends up with O[head][16 dt + 4g + r]; the online-softmax rescale is a per-
 //     lane scalar.  Waves, the new key and the splits are merged as in the VALU kernel.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma_kq(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<T, bf16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, a), __builtin_bit_cast(bf16x8v, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8v, a), __builtin_bit_cast(f16x8v, b), c, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  T v[2] = {(T)a, (T)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-// P as TWO 16-bit operands (round 4): hi = T(p), lo = T(p - hi).  The reference's attention keeps the softmax numerators in
-// float32 (App. A.4); feeding them to the matrix core as ONE 16-bit value was a rounding the oracle does not have -- the
-// CPU variant with that rounding (oracle/numerics.py SDPA_P16) reproduces the 1.05 - 1.33 x excess of the device's mean
-// |logprob - exact| over the float32-accumulating variants.  hi + lo carries 16+ mantissa bits; the second
-// MFMA per V tile costs ~0.2 us per launch.
-template <typename T>
-__device__ __forceinline__ void pack2_split(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const T ha = (T)a, hb = (T)b;
-  T h[2] = {ha, hb};
-  T l[2] = {(T)(a - (float)ha), (T)(b - (float)hb)};
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
 
 constexpr int NWV = 8;                           // waves per workgroup of the MFMA kernel
 
@@ -963,7 +931,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
     for (int t = 0; t < 2; ++t) {
       sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < KK; ++kk) sc[t] = mfma_kq<T>(kf[t][kk], qf[kk], sc[t]);
+      for (int kk = 0; kk < KK; ++kk) sc[t] = mfma16<T>(kf[t][kk], qf[kk], sc[t]);
     }
     __builtin_amdgcn_sched_barrier(0);
     issue_k(base + 32 * NWV);                    // rolling prefetch: the next round's K into the registers just consumed
@@ -1017,8 +985,8 @@ __device__ __forceinline__ void attn_decode_mfma_body(const AttnDecodeCall& c, u
       const uint32_t* w0 = (const uint32_t*)&v0;
       const uint32_t* w1 = (const uint32_t*)&v1;
       const u32x4 vf = {w0[0], w0[1], w1[0], w1[1]};
-      accO[dt] = mfma_kq<T>(vf, pf, accO[dt]);
-      accO[dt] = mfma_kq<T>(vf, pl, accO[dt]);
+      accO[dt] = mfma16<T>(vf, pf, accO[dt]);
+      accO[dt] = mfma16<T>(vf, pl, accO[dt]);
     }
   }
   }
@@ -1140,7 +1108,7 @@ int launch_mfma_qs_n(const AttnDecodeCall& c, const dim3 grid, hipStream_t st AT
   return launch_mfma_qs<D, G, NORM, PAGED, 8>(c, grid, st AT_TRACE_ARG);
 }
 
-template <typename T, int D, int G, bool NORM>
+template <typename T, int D, int G, bool NORM, bool PAGED>
 int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   const dim3 grid(c.nsplit, s.B * s.Hkv);
@@ -1155,85 +1123,38 @@ int launch_mfma_g(const AttnDecodeCall& c, hipStream_t st) {
     } else if constexpr (sizeof(T) == 4) {
       if (c.qkv_pub_sq == nullptr || c.qkv_ksplit < 2 || c.qkv_ksplit > 8 || s.B > 8 || c.hidden_k <= 0)
         return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need 2..8 K slices and at most 8 sequences");
-      return s.btab ? launch_mfma_qs_n<D, G, NORM, true>(c, grid, st AT_TRACE_ARG) : launch_mfma_qs_n<D, G, NORM, false>(c, grid, st AT_TRACE_ARG);
+      return launch_mfma_qs_n<D, G, NORM, PAGED>(c, grid, st AT_TRACE_ARG);
     } else {
       return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows need float32 activations");
     }
   }
-#define LAUNCH_MFMA(PG) do { \
-    auto kern = attn_decode_mfma_kernel<T, D, G, NORM, PG>; \
-    constexpr size_t lds = attn_mfma_lds_total<G, D, (int)sizeof(T)>(); \
-    MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG); } while (0)
-  if (s.btab) LAUNCH_MFMA(true); else LAUNCH_MFMA(false);
-#undef LAUNCH_MFMA
+  auto kern = attn_decode_mfma_kernel<T, D, G, NORM, PAGED>;
+  constexpr size_t lds = attn_mfma_lds_total<G, D, (int)sizeof(T)>();
+  MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, c AT_TRACE_ARG);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
 
-// head_dim 96 (Phi-3): Hq/Hkv 1, 2 and 4 only, in every kernel of this file; the float32 matrix-core kernel has it in its
-// 16-block form (G <= 4), which those three groups all take
+// the widths of the matrix-core kernel; the float32 one has head_dim 96 in its 16-block form (G <= 4), which the three groups
+// served at that width (attn_dispatch.h) all take
 template <typename T, int D>
 constexpr bool attn_mfma_ok() { return (sizeof(T) == 2 && D % 32 == 0) || (sizeof(T) == 4 && (D % 64 == 0 || D == 96)); }
-constexpr bool attn_group_ok(int D, int G) {
-  return D == 96 ? (G == 1 || G == 2 || G == 4) : (G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8);
-}
-
-template <typename T, int D, bool NORM>
-int launch_mfma_gn(const AttnDecodeCall& c, hipStream_t st) {
-  if constexpr (D == 96) {
-    switch (c.s.Hq / c.s.Hkv) {
-      case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
-      case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
-      case 4: return launch_mfma_g<T, D, 4, NORM>(c, st);
-    }
-    return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
-  } else if constexpr (attn_mfma_ok<T, D>()) {
-    switch (c.s.Hq / c.s.Hkv) {
-      case 1: return launch_mfma_g<T, D, 1, NORM>(c, st);
-      case 2: return launch_mfma_g<T, D, 2, NORM>(c, st);
-      case 3: return launch_mfma_g<T, D, 3, NORM>(c, st);
-      case 4: return launch_mfma_g<T, D, 4, NORM>(c, st);
-      case 5: return launch_mfma_g<T, D, 5, NORM>(c, st);
-      case 6: return launch_mfma_g<T, D, 6, NORM>(c, st);
-      case 8: return launch_mfma_g<T, D, 8, NORM>(c, st);
-    }
-  }
-  return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
-}
 
 template <typename T, int D, bool NORM>
 int launch_gn(const AttnDecodeCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   if constexpr (attn_mfma_ok<T, D>()) {
-    if (c.variant != 1) return launch_mfma_gn<T, D, NORM>(c, st);
+    if (c.variant != 1)
+      return attn_dispatch<D>("attention", s, [&](auto g, auto paged) { return launch_mfma_g<T, D, g(), NORM, paged()>(c, st); });
   }
   if (c.qkv_pub != nullptr) return fail(MI_ERR_INVALID, "attention_decode: partial q|k|v rows are read by the float32 MFMA kernel only");
   const dim3 grid(c.nsplit, s.B * s.Hkv), block(512);
-#define DK(GV) do { if (s.btab) hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, true>), grid, block, 0, st, c); \
-                    else hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, NORM, false>), grid, block, 0, st, c); } while (0)
-  if constexpr (D == 96) {
-    switch (s.Hq / s.Hkv) {
-      case 1: DK(1); break;
-      case 2: DK(2); break;
-      case 4: DK(4); break;
-      default: return fail(MI_ERR_UNSUPPORTED, "attention: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
-    }
-  } else {
-  switch (s.Hq / s.Hkv) {
-    case 1: DK(1); break;
-    case 2: DK(2); break;
-    case 3: DK(3); break;
-    case 4: DK(4); break;
-    case 5: DK(5); break;
-    case 6: DK(6); break;
-    case 8: DK(8); break;
-    default: return fail(MI_ERR_UNSUPPORTED, "attention: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
-  }
-  }
-#undef DK
-  MI_HIP(hipGetLastError());
-  return MI_OK;
+  return attn_dispatch<D>("attention", s, [&](auto g, auto paged) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, D, g(), NORM, paged()>), grid, block, 0, st, c);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  });
 }
 
 template <typename T, int D>
@@ -1257,17 +1178,16 @@ int launch_d(const AttnDecodeCall& c, hipStream_t st) {
 
 }  // namespace
 
-bool attention_decode_supported(const AttnShape& s, int variant) {
+bool attention_decode_supported(const AttnShape& s) {
   if (s.L != 1 || s.act != s.kv) return false;
-  const int G = s.Hkv > 0 ? s.Hq / s.Hkv : 0;
-  if (!attn_group_ok(s.D, G)) return false;
-  if (s.act == MI_F32) return s.D == 16 || s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;
+  if (!attn_group_ok(s.D, s.Hkv > 0 ? s.Hq / s.Hkv : 0)) return false;
+  if (s.D == 16) return s.act == MI_F32;
   return s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;
 }
 
 int launch_attention_decode(const AttnDecodeCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
-  if (!attention_decode_supported(s, c.variant)) return fail(MI_ERR_UNSUPPORTED, "attention_decode: shape / dtype not supported by this variant");
+  if (!attention_decode_supported(s)) return fail(MI_ERR_UNSUPPORTED, "attention_decode: shape / dtype not supported");
   if (c.nsplit < 1 || (c.nsplit > 1 && c.partial == nullptr))
     return fail(MI_ERR_INVALID, "attention_decode: bad split configuration");
   if (s.act == MI_F32) return launch_d<float>(c, st);

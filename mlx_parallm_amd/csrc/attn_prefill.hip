@@ -17,47 +17,20 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "attn_dispatch.h"
+#include "attn_mfma.h"
 
 namespace mi {
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<T, bf16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ void pack2_split(float a, float b, uint32_t& hi, uint32_t& lo) {   // as in attn_decode.hip
-  const T ha = (T)a, hb = (T)b;
-  T h[2] = {ha, hb};
-  T l[2] = {(T)(a - (float)ha), (T)(b - (float)hb)};
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  T v[2] = {(T)a, (T)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
 constexpr int QT = 16;      // queries per query group (one MFMA column set)
 constexpr int KB = 32;      // keys per block
 
-// QG: query groups of 16 per wave (the launcher uses 1: see launch_pg).  With QG = 2 a workgroup covers 32 queries and every
-// K / V fragment a wave reads from LDS feeds two MFMAs.
+// QG: query groups of 16 per wave (the launcher uses 1: see launch_pd).  With QG = 2 a workgroup covers 32 queries and every
+// K / V fragment a wave reads from LDS feeds two MFMAs.  (The `u` loops of one trip are not free to go: without them hipcc hoists
+// the head offset of q / out and the softmax's shuffle lanes in another order, and every instantiation of both kernels gets
+// another register allocation, 1 .. 4 VGPRs either way -- compared on the compiler's output, gfx950, ROCm 7.)
 // (launch bounds: two waves per SIMD, i.e. up to 256 registers.  Left to itself hipcc aims at three, keeps the output
 // accumulators in AGPRs and moves them to VGPRs and back around every rescale: 88 v_accvgpr moves per block of 16 MFMAs.)
 template <typename T, int D, int G, bool PAGED, int QG>
@@ -164,7 +137,7 @@ __global__ __launch_bounds__(G * 64, 2) void attn_prefill_kernel(AttnCall c) {
         for (int u = 0; u < QG; ++u) sc[u][t] = mfma16<T>(kf, qf[u][kk], sc[u][t]);
       }
     }
-    u32x4 pf[QG], pl[QG];                             // P = hi + lo, two 16-bit operands (attn_decode.hip pack2_split)
+    u32x4 pf[QG], pl[QG];                             // P = hi + lo, two 16-bit operands (attn_mfma.h pack2_split)
 #pragma unroll
     for (int u = 0; u < QG; ++u) {
       // The vector ALU, not the matrix core, bounds this loop (~110 vector instructions + 9 transcendentals per 16 MFMAs
@@ -365,7 +338,7 @@ __global__ __launch_bounds__(G * 64, G >= 2 ? 2 : 1) void attn_prefill_dma_kerne
         for (int u = 0; u < QG; ++u) sc[u][t] = mfma16<T>(kf, qf[u][kk], sc[u][t]);
       }
     }
-    u32x4 pf[QG], pl[QG];                             // P = hi + lo, two 16-bit operands (attn_decode.hip pack2_split)
+    u32x4 pf[QG], pl[QG];                             // P = hi + lo, two 16-bit operands (attn_mfma.h pack2_split)
 #pragma unroll
     for (int u = 0; u < QG; ++u) {
       // The vector ALU, not the matrix core, bounds this loop (~110 vector instructions + 9 transcendentals per 16 MFMAs
@@ -453,45 +426,21 @@ __global__ __launch_bounds__(G * 64, G >= 2 ? 2 : 1) void attn_prefill_dma_kerne
   }
 }
 
-template <typename T, int D, int G>
-int launch_pg(const AttnCall& c, hipStream_t st) {
+template <typename T, int D>
+int launch_pd(const AttnCall& c, hipStream_t st) {
   const AttnShape& s = c.s;
   // one query group per wave.  Two (32 queries per workgroup, every K / V fragment feeding two MFMAs) was built and
   // measured: prefill 83.3 .. 83.8 k tok/s against 84.0 .. 84.1 k (same box, alternating runs) -- the vector ALU bounds the
   // loop, not the LDS traffic -- and 79 k once the leaner softmax below pushed it past 256 registers.
-  const dim3 grid((s.L + QT - 1) / QT, s.B * s.Hkv), block(G * 64);
   const char* env = getenv("MI_ATTN_PREFILL_DMA");     // A/B and the bit-equality test: 0 = the register-staged kernel (read per call)
-  if (env == nullptr || atoi(env) != 0) {
-    if (s.btab) hipLaunchKernelGGL((attn_prefill_dma_kernel<T, D, G, true, 1>), grid, block, 0, st, c);
-    else hipLaunchKernelGGL((attn_prefill_dma_kernel<T, D, G, false, 1>), grid, block, 0, st, c);
-  } else {
-    if (s.btab) hipLaunchKernelGGL((attn_prefill_kernel<T, D, G, true, 1>), grid, block, 0, st, c);
-    else hipLaunchKernelGGL((attn_prefill_kernel<T, D, G, false, 1>), grid, block, 0, st, c);
-  }
-  MI_HIP(hipGetLastError());
-  return MI_OK;
-}
-
-template <typename T, int D>
-int launch_pd(const AttnCall& c, hipStream_t st) {
-  if constexpr (D == 96) {                            // (attention_prefill_supported admits Hq/Hkv 1, 2 and 4 at this width)
-    switch (c.s.Hq / c.s.Hkv) {
-      case 1: return launch_pg<T, D, 1>(c, st);
-      case 2: return launch_pg<T, D, 2>(c, st);
-      case 4: return launch_pg<T, D, 4>(c, st);
-    }
-    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
-  } else
-  switch (c.s.Hq / c.s.Hkv) {
-    case 1: return launch_pg<T, D, 1>(c, st);
-    case 2: return launch_pg<T, D, 2>(c, st);
-    case 3: return launch_pg<T, D, 3>(c, st);
-    case 4: return launch_pg<T, D, 4>(c, st);
-    case 5: return launch_pg<T, D, 5>(c, st);
-    case 6: return launch_pg<T, D, 6>(c, st);
-    case 8: return launch_pg<T, D, 8>(c, st);
-  }
-  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
+  const bool dma = env == nullptr || atoi(env) != 0;
+  return attn_dispatch<D>("attention_prefill", s, [&](auto g, auto paged) {
+    const dim3 grid((s.L + QT - 1) / QT, s.B * s.Hkv), block(g() * 64);
+    if (dma) hipLaunchKernelGGL((attn_prefill_dma_kernel<T, D, g(), paged(), 1>), grid, block, 0, st, c);
+    else hipLaunchKernelGGL((attn_prefill_kernel<T, D, g(), paged(), 1>), grid, block, 0, st, c);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  });
 }
 
 template <typename T>
@@ -504,7 +453,6 @@ int launch_pt(const AttnCall& c, hipStream_t st) {
   }
   return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim must be 32, 64, 96 or 128");
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // float32 activations and caches (the PagedKVCache mode: base.py:104-140 keeps float32 K / V, and SDPA then runs in
@@ -833,52 +781,30 @@ __global__ __launch_bounds__(G * 64, 2) void attn_prefill_f32s_kernel(AttnCall c
   }
 }
 
-template <int D, int G>
-int launch_pg32(const AttnCall& c, hipStream_t st) {
-  const AttnShape& s = c.s;
-  const dim3 grid((s.L + QT - 1) / QT, s.B * s.Hkv), block(G * 64);
-  const char* env = getenv("MI_ATTN_PREFILL_F32_EXACT");   // A/B and the comparison test (read per call): 1 = exact float32 products
-  if (env == nullptr || atoi(env) == 0) {
-    if (s.btab) hipLaunchKernelGGL((attn_prefill_f32s_kernel<D, G, true>), grid, block, 0, st, c);
-    else hipLaunchKernelGGL((attn_prefill_f32s_kernel<D, G, false>), grid, block, 0, st, c);
-  } else if constexpr (D % 64 != 0) {                 // the exact form's V image is made of 64-wide halves of a row
-    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: the exact float32 form needs head_dim 64 or 128");
-  } else if (s.btab) hipLaunchKernelGGL((attn_prefill_f32_kernel<D, G, true>), grid, block, 0, st, c);
-  else hipLaunchKernelGGL((attn_prefill_f32_kernel<D, G, false>), grid, block, 0, st, c);
-  MI_HIP(hipGetLastError());
-  return MI_OK;
-}
-
 template <int D>
 int launch_pd32(const AttnCall& c, hipStream_t st) {
-  if constexpr (D == 96) {
-    switch (c.s.Hq / c.s.Hkv) {
-      case 1: return launch_pg32<D, 1>(c, st);
-      case 2: return launch_pg32<D, 2>(c, st);
-      case 4: return launch_pg32<D, 4>(c, st);
+  const AttnShape& s = c.s;
+  const char* env = getenv("MI_ATTN_PREFILL_F32_EXACT");   // A/B and the comparison test (read per call): 1 = exact float32 products
+  const bool exact = env != nullptr && atoi(env) != 0;
+  return attn_dispatch<D>("attention_prefill", s, [&](auto g, auto paged) {
+    const dim3 grid((s.L + QT - 1) / QT, s.B * s.Hkv), block(g() * 64);
+    if (!exact) {
+      hipLaunchKernelGGL((attn_prefill_f32s_kernel<D, g(), paged()>), grid, block, 0, st, c);
+    } else if constexpr (D % 64 != 0) {               // the exact form's V image is made of 64-wide halves of a row
+      return fail(MI_ERR_UNSUPPORTED, "attention_prefill: the exact float32 form needs head_dim 64 or 128");
+    } else {
+      hipLaunchKernelGGL((attn_prefill_f32_kernel<D, g(), paged()>), grid, block, 0, st, c);
     }
-    return fail(MI_ERR_UNSUPPORTED, "attention_prefill: head_dim 96 needs Hq/Hkv of 1, 2 or 4");
-  } else
-  switch (c.s.Hq / c.s.Hkv) {
-    case 1: return launch_pg32<D, 1>(c, st);
-    case 2: return launch_pg32<D, 2>(c, st);
-    case 3: return launch_pg32<D, 3>(c, st);
-    case 4: return launch_pg32<D, 4>(c, st);
-    case 5: return launch_pg32<D, 5>(c, st);
-    case 6: return launch_pg32<D, 6>(c, st);
-    case 8: return launch_pg32<D, 8>(c, st);
-  }
-  return fail(MI_ERR_UNSUPPORTED, "attention_prefill: Hq/Hkv must be 1, 2, 3, 4, 5, 6 or 8");
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  });
 }
 
 }  // namespace
 
 bool attention_prefill_supported(const AttnShape& s) {
   if (s.L < 2 || s.act != s.kv) return false;
-  if (s.Hkv <= 0 || s.Hq % s.Hkv != 0) return false;
-  const int G = s.Hq / s.Hkv;
-  if (!(G == 1 || G == 2 || G == 3 || G == 4 || G == 5 || G == 6 || G == 8)) return false;
-  if (s.D == 96 && !(G == 1 || G == 2 || G == 4)) return false;
+  if (s.Hkv <= 0 || s.Hq % s.Hkv != 0 || !attn_group_ok(s.D, s.Hq / s.Hkv)) return false;
   if (s.act == MI_F32) return s.D == 64 || s.D == 96 || s.D == 128;   // (s.rnd = logical rounding of the output, applied at the store)
   if ((s.act != MI_BF16 && s.act != MI_F16) || s.rnd != RND_NONE) return false;
   return s.D == 32 || s.D == 64 || s.D == 96 || s.D == 128;

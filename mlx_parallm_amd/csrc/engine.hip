@@ -188,7 +188,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
       const void* qkv_g = (const char*)e->qkv + g.tok0 * (size_t)nqkv * es;
       void* q_g = (char*)e->q + g.tok0 * (size_t)Hq * D * es;
       void* o_g = (char*)e->attn + g.tok0 * (size_t)Hq * D * es;
-      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s, e->opt_attn_mfma ? 0 : 1)) {
+      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
         // decode: norm + RoPE + append + attention + split combine in one launch
         AttnDecodeCall ac{s, qkv_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
                           o_g, 1.0f / sqrtf((float)D), RND_NONE, nsplit[gi], kv->partial, kv->counters,

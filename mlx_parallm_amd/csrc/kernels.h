@@ -284,7 +284,7 @@ struct AttnDecodeCall {
   float qkv_eps = 0.f;
 };
 int launch_attention_decode(const AttnDecodeCall& c, hipStream_t st);
-bool attention_decode_supported(const AttnShape& s, int variant = 0);   // variant: AttnDecodeCall::variant (1 = the VALU kernel)
+bool attention_decode_supported(const AttnShape& s);
 bool gemv_mfma_supported(const LinearW& W, const GemvCall& c);
 
 struct SampleCall {

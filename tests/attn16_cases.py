@@ -295,3 +295,14 @@ LOOKUP_LENS = [0, 2, 31, 32, 33, 255, 256, 300]         # cached keys of batch e
 LOOKUP_ROWS = [7, 2, 11, 0, 5, 9, 3, 6]                 # ... which lives in this row of a 12-row cache
 LOOKUP_NROWS = 12
 LOOKUP_CAP = 308
+
+
+def check_new_rows(gk, gv, kc_ref, vc_ref, rows, lens, act):
+    """The V cache and every K row but the new ones: exactly the oracle's; the new K row (norm + RoPE in float32 against the
+    oracle's float64): within 2 units of max(|want|, 2), the worst-element bound test_gpu_kernels.py holds for it."""
+    assert np.array_equal(gv, vc_ref)
+    for r, n in zip(rows, lens):
+        err = np.abs(gk[r, :, n] - kc_ref[r, :, n])
+        assert np.all(err <= 2 * UNIT[act] * np.maximum(np.abs(kc_ref[r, :, n]), 2.0)), (r, n, float(err.max()))
+        gk[r, :, n] = kc_ref[r, :, n]
+    assert np.array_equal(gk, kc_ref)

@@ -11,7 +11,7 @@ DS = [32, 64, 96, 128]                      # head_dim of the matrix-core kernel
 
 
 def served(D, G):
-    """attn_group_ok(): head_dim 96 has the groups 1, 2 and 4 only."""
+    """AttnGroups (attn_dispatch.h): head_dim 96 has the groups 1, 2 and 4 only."""
     return G in ((1, 2, 4) if D == 96 else GS)
 
 

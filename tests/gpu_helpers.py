@@ -3,6 +3,8 @@ kernel-level C ABI (include/mi355_ops.h) through ctypes."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import os
 
 import numpy as np
 import torch
@@ -102,6 +104,78 @@ def attn_shape(B, L_, Hq, Hkv, D, act, kv, rnd, cap) -> L.OpAttnShape:
     s = L.OpAttnShape()
     s.B, s.L, s.Hq, s.Hkv, s.D, s.act, s.kv, s.rnd, s.cap = B, L_, Hq, Hkv, D, MIDT[act], MIDT[kv], rnd, cap
     return s
+
+
+def identity_rope(max_pos, D):
+    cos = torch.ones((max_pos, D // 2), dtype=torch.float32, device="cuda")
+    return cos, torch.zeros_like(cos)
+
+
+@functools.lru_cache(maxsize=None)
+def rope_tables(D, max_pos, base):
+    """mi_op_rope_tables, computed once per (D, max_pos, base) and shared (read-only)."""
+    cos = torch.zeros((max_pos, D // 2), dtype=torch.float32, device="cuda")
+    sin = torch.zeros_like(cos)
+    torch.cuda.synchronize()
+    L.check(L.lib().mi_op_rope_tables(ptr(cos), ptr(sin), max_pos, D, base, 1.0))
+    return cos, sin
+
+
+def _raw(t) -> C.c_void_p:
+    return t if isinstance(t, C.c_void_p) else ptr(t)
+
+
+def attention(s, q_d, kc_d, vc_d, off_d, nsplit=1, *, dma=None, exact=None, out=None, check=True):
+    """mi_op_attention -> the output tensor (the return code when check is False).  dma "1" / "0": the LDS-DMA / the
+    register-staged 16-bit prefill kernel; exact "1" / "0": exact float32 products / two-term operands in the float32 prefill
+    (both are read by the library per call: set for this call only)."""
+    if out is None:
+        out = torch.zeros((s.B * s.L, s.Hq * s.D), dtype=q_d.dtype, device="cuda")
+    part = torch.zeros((s.B * s.L * s.Hq * nsplit * (s.D + 2),), dtype=torch.float32, device="cuda")
+    env = {k: v for k, v in (("MI_ATTN_PREFILL_DMA", dma), ("MI_ATTN_PREFILL_F32_EXACT", exact)) if v is not None}
+    os.environ.update(env)
+    try:
+        torch.cuda.synchronize()
+        rc = L.lib().mi_op_attention(C.byref(s), ptr(q_d), ptr(kc_d), ptr(vc_d), ptr(off_d), ptr(out), float(s.D ** -0.5),
+                                     nsplit, ptr(part))
+        torch.cuda.synchronize()
+    finally:
+        for k in env:
+            del os.environ[k]
+    if not check:
+        return rc
+    L.check(rc)
+    return out
+
+
+def attention_decode(s, qkv_d, kc, vc, off_d, cos, sin, nsplit, variant=0, *, qn_d=None, kn_d=None, rows_d=None, hrow=None,
+                     hoff=None, repeat=1, out=None, read=None, check=True):
+    """mi_op_attention_decode, or mi_op_attention_decode_host when device rows (rows_d) or the host lookup (hrow, hoff: ctypes
+    int32 arrays) are given; `repeat` launches on the same buffers -> the output of each as float32 NumPy (a list when
+    repeat > 1).  The arrival tickets must be back at zero after every launch.  kc, vc and out are tensors or raw pointers
+    (buffers the caller fences); `read` replaces the read-back of out after a launch.  check False: one launch -> its
+    return code."""
+    part = torch.zeros((s.B * s.Hq * nsplit * (s.D + 2),), dtype=torch.float32, device="cuda")
+    ctr = torch.zeros((s.B * s.Hkv,), dtype=torch.int32, device="cuda")
+    if out is None:
+        out = torch.zeros((s.B, s.Hq * s.D), dtype=qkv_d.dtype, device="cuda")
+    args = (C.byref(s), ptr(qkv_d), _raw(kc), _raw(vc), ptr(off_d), ptr(qn_d), ptr(kn_d), 1e-6, ptr(cos), ptr(sin), _raw(out),
+            float(s.D ** -0.5), 0, nsplit, ptr(part), ptr(ctr), variant, 1, None)
+    outs = []
+    for _ in range(repeat):
+        torch.cuda.synchronize()
+        if rows_d is None and hrow is None:
+            rc = L.lib().mi_op_attention_decode(*args)
+        else:
+            rc = L.lib().mi_op_attention_decode_host(*args, ptr(rows_d), hrow, hoff)
+        if check:
+            L.check(rc)
+        torch.cuda.synchronize()
+        assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
+        if not check:
+            return rc
+        outs.append(read() if read is not None else host(out))
+    return outs if repeat > 1 else outs[0]
 
 
 def close_frac(got: np.ndarray, want: np.ndarray, dtype: str, atol: float = 0.0) -> float:

@@ -1,5 +1,5 @@
 """The owner map of the decode attention's prologue (tests/attn_owner_cases.py), checked without a device, and held against
-the lines of attn_decode.hip it restates."""
+the lines of attn_decode.hip and the group table of attn_dispatch.h it restates."""
 import os
 import re
 
@@ -7,7 +7,8 @@ import pytest
 
 import attn_owner_cases as own
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mlx_parallm_amd", "csrc", "attn_decode.hip")
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mlx_parallm_amd", "csrc")
+SRC = os.path.join(CSRC, "attn_decode.hip")
 
 
 @pytest.mark.parametrize("owner_split", [True, False])
@@ -59,10 +60,12 @@ def test_the_source_says_the_same():
         assert line in body, line
     # every prologue load and every instruction behind it stands under the two tests
     assert body.count("if (wave_owns) if (has_vec)") == 3
-    m = re.search(r"constexpr bool attn_group_ok\(int D, int G\) \{\s*return D == 96 \? \(([^)]*)\) : \(([^)]*)\);", src)
-    d96 = [int(x) for x in re.findall(r"G == (\d+)", m.group(1))]
-    rest = [int(x) for x in re.findall(r"G == (\d+)", m.group(2))]
+    table = open(os.path.join(CSRC, "attn_dispatch.h")).read()
+    rest = re.search(r"template <int D>\s*struct AttnGroups : std::integer_sequence<int, ([\d, ]+)>", table).group(1)
+    d96 = re.search(r"struct AttnGroups<96> : std::integer_sequence<int, ([\d, ]+)>", table).group(1)
+    rest, d96 = [int(x) for x in rest.split(",")], [int(x) for x in d96.split(",")]
     assert rest == own.GS and d96 == [g for g in own.GS if own.served(96, g)]
+    assert table.count("struct AttnGroups") == 2                             # 96 is the only width with a table of its own
     # the slice classes of the consumer_combine prologue
     for ks, cls in ((2, 2), (3, 4), (4, 4), (5, 8), (8, 8)):
         assert own.slice_class(ks) == cls

@@ -28,7 +28,6 @@ value: 5.4 - 9.3 % beyond half a unit.
 """
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -38,65 +37,11 @@ pytestmark = pytest.mark.gpu
 
 import attn16_cases as cases  # noqa: E402
 from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import attn_shape, dev, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import attention, attention_decode, attn_shape, dev, dev_i32, host, identity_rope, ptr, rope_tables  # noqa: E402
 
 ACTS = ["bfloat16", "float16"]
 DS = [32, 64, 128]
 GS = [1, 2, 4, 5, 8]
-
-
-def _identity_rope(max_pos, D):
-    cos = torch.ones((max_pos, D // 2), dtype=torch.float32, device="cuda")
-    return cos, torch.zeros_like(cos)
-
-
-@functools.lru_cache(maxsize=None)
-def _rope_tables(D, max_pos, base):
-    cos = torch.zeros((max_pos, D // 2), dtype=torch.float32, device="cuda")
-    sin = torch.zeros_like(cos)
-    torch.cuda.synchronize()
-    L.check(L.lib().mi_op_rope_tables(ptr(cos), ptr(sin), max_pos, D, base, 1.0))
-    return cos, sin
-
-
-def _attention(s, q_d, kc_d, vc_d, off_d, D, nsplit=1, dma=None):
-    """mi_op_attention; dma "1" / "0": the LDS-DMA / the register-staged prefill kernel (read by the library per call)."""
-    Hq = s.Hq
-    out = torch.zeros((s.B * s.L, Hq * D), dtype=q_d.dtype, device="cuda")
-    part = torch.zeros((s.B * s.L * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    if dma is not None:
-        os.environ["MI_ATTN_PREFILL_DMA"] = dma
-    try:
-        torch.cuda.synchronize()
-        L.check(L.lib().mi_op_attention(C.byref(s), ptr(q_d), ptr(kc_d), ptr(vc_d), ptr(off_d), ptr(out), float(D ** -0.5),
-                                        nsplit, ptr(part)))
-        torch.cuda.synchronize()
-    finally:
-        if dma is not None:
-            del os.environ["MI_ATTN_PREFILL_DMA"]
-    return out
-
-
-def _decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, D, nsplit, variant, qn_d=None, kn_d=None, rows_d=None, hrow=None, hoff=None,
-            repeat=1):
-    """mi_op_attention_decode(_host), `repeat` launches on the same buffers -> the outputs of each; tickets checked."""
-    B, Hq, Hkv = s.B, s.Hq, s.Hkv
-    out = torch.zeros((B, Hq * D), dtype=qkv_d.dtype, device="cuda")
-    part = torch.zeros((B * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    ctr = torch.zeros((B * Hkv,), dtype=torch.int32, device="cuda")
-    outs = []
-    for _ in range(repeat):
-        torch.cuda.synchronize()
-        args = (C.byref(s), ptr(qkv_d), ptr(kc_d), ptr(vc_d), ptr(off_d), ptr(qn_d), ptr(kn_d), cases.EPS, ptr(cos), ptr(sin),
-                ptr(out), float(D ** -0.5), 0, nsplit, ptr(part), ptr(ctr), variant, 1, None)
-        if rows_d is None and hrow is None:
-            L.check(L.lib().mi_op_attention_decode(*args))
-        else:
-            L.check(L.lib().mi_op_attention_decode_host(*args, ptr(rows_d), hrow, hoff))
-        torch.cuda.synchronize()
-        assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
-        outs.append(host(out))
-    return outs if repeat > 1 else outs[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -115,7 +60,7 @@ def test_prefill_one_hot_selects_one_v_row_bit_for_bit(act, D, G):
     s = attn_shape(B, L_, Hq, Hkv, D, act, act, 0, cases.PREFILL_CAP)
     q_d, kc_d, vc_d = dev(c["q"].reshape(B * L_, Hq * D), act), dev(c["k"], act), dev(c["v"], act)
     off_d = dev_i32(cases.PREFILL_OFFS)
-    outs = {dma: _attention(s, q_d, kc_d, vc_d, off_d, D, dma=dma) for dma in ("1", "0")}
+    outs = {dma: attention(s, q_d, kc_d, vc_d, off_d, dma=dma) for dma in ("1", "0")}
     for dma, out in outs.items():
         got = host(out).reshape(B, L_, Hq, D)
         bad = [(b, t, h, int(c["winner"][b, t, h])) for b in range(B) for t in range(L_) for h in range(Hq)
@@ -137,7 +82,7 @@ def test_decode_one_hot_selects_one_v_row_bit_for_bit(act, D, G, nsplit):
     cand, launches = cases.decode_launches(Hq, Hkv, D, nsplit)
     cases.assert_decode_coverage(cand, launches, D)
     vc, vnew = cases.decode_values(Hkv, D, act)
-    cos, sin = _identity_rope(cases.DECODE_CAP + 1, D)
+    cos, sin = identity_rope(cases.DECODE_CAP + 1, D)
     s = attn_shape(B, 1, Hq, Hkv, D, act, act, 0, cases.DECODE_CAP)
     off_d, vc0_d = dev_i32(cases.DECODE_POS), dev(vc, act)
     rows_i, pos_i = torch.arange(B, device="cuda"), torch.tensor(cases.DECODE_POS, device="cuda")
@@ -150,7 +95,7 @@ def test_decode_one_hot_selects_one_v_row_bit_for_bit(act, D, G, nsplit):
         kca_d[rows_i, :, pos_i] = qkv_d[:, Hq * D:(Hq + Hkv) * D].reshape(B, Hkv, D)
         for variant in (0, 1):
             kc_d, vc_d = kc0_d.clone(), vc0_d.clone()
-            got = _decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, D, nsplit, variant).reshape(B, Hq, D)
+            got = attention_decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, nsplit, variant).reshape(B, Hq, D)
             bad = [(b, h, int(key[b, h])) for b in range(B) for h in range(Hq) if not np.array_equal(got[b, h], want[b, h])]
             assert not bad, (variant, p, bad[:8], len(bad))
             # the new K / V row at pos, nothing else
@@ -172,7 +117,7 @@ def test_unfused_decode_one_hot_selects_one_v_row_bit_for_bit(act, Hq, Hkv, D, n
     for p, (key, d) in enumerate(launches):
         qkv, _, want, kc_after, vc_after = cases.decode_one_hot(Hq, Hkv, D, key, d, vc, vnew)
         q_d = dev(qkv[:, :Hq * D], act)
-        got = host(_attention(s, q_d, dev(kc_after, act), dev(vc_after, act), off_d, D, nsplit=nsplit)).reshape(B, Hq, D)
+        got = host(attention(s, q_d, dev(kc_after, act), dev(vc_after, act), off_d, nsplit)).reshape(B, Hq, D)
         bad = [(b, h, int(key[b, h])) for b in range(B) for h in range(Hq) if not np.array_equal(got[b, h], want[b, h])]
         assert not bad, (p, bad[:8], len(bad))
 
@@ -191,17 +136,6 @@ def _random_decode_case(Hq, Hkv, D, norm, act):
     return inp, want[:, 0], kc_ref, vc_ref
 
 
-def _check_new_rows(gk, gv, kc_ref, vc_ref, rows, lens, act):
-    """The V cache and every K row but the new ones: exactly the oracle's; the new K row (norm + RoPE in float32 against the
-    oracle's float64): within 2 units of max(|want|, 2), the worst-element bound test_gpu_kernels.py holds for it."""
-    assert np.array_equal(gv, vc_ref)
-    for r, n in zip(rows, lens):
-        err = np.abs(gk[r, :, n] - kc_ref[r, :, n])
-        assert np.all(err <= 2 * cases.UNIT[act] * np.maximum(np.abs(kc_ref[r, :, n]), 2.0)), (r, n, float(err.max()))
-        gk[r, :, n] = kc_ref[r, :, n]
-    assert np.array_equal(gk, kc_ref)
-
-
 @pytest.mark.parametrize("nsplit", [1, 3, 8])
 @pytest.mark.parametrize("variant", [0, 1])
 @pytest.mark.parametrize("act", ACTS)
@@ -210,12 +144,13 @@ def test_decode_random_rows_under_the_rule(Hq, Hkv, D, norm, act, variant, nspli
     inp, want, kc_ref, vc_ref = _random_decode_case(Hq, Hkv, D, norm, act)
     lens = cases.RANDOM_DECODE_LENS
     B, cap = len(lens), max(lens) + 8
-    cos, sin = _rope_tables(D, cap + 8, cases.rope_base(norm))
+    cos, sin = rope_tables(D, cap + 8, cases.rope_base(norm))
     s = attn_shape(B, 1, Hq, Hkv, D, act, act, 0, cap)
     kc_d, vc_d = dev(inp["kc"], act), dev(inp["vc"], act)
     qn_d, kn_d = (dev(inp["qn"], act), dev(inp["kn"], act)) if norm else (None, None)
-    got = _decode(s, dev(inp["qkv"][:, 0], act), kc_d, vc_d, dev_i32(lens), cos, sin, D, nsplit, variant, qn_d, kn_d)
-    _check_new_rows(host(kc_d), host(vc_d), kc_ref, vc_ref, range(B), lens, act)
+    got = attention_decode(s, dev(inp["qkv"][:, 0], act), kc_d, vc_d, dev_i32(lens), cos, sin, nsplit, variant,
+                           qn_d=qn_d, kn_d=kn_d)
+    cases.check_new_rows(host(kc_d), host(vc_d), kc_ref, vc_ref, range(B), lens, act)
     cases.assert_rule(got, want, act, f"decode variant {variant} ({Hq},{Hkv},{D}) {act} nsplit {nsplit}")
 
 
@@ -238,7 +173,7 @@ def test_prefill_random_rows_under_the_rule(Hq, Hkv, D, norm, act, L_):
     offs = cases.RANDOM_PREFILL_OFFS
     B, cap, max_pos = len(offs), cases.RANDOM_PREFILL_CAP, cases.RANDOM_PREFILL_CAP + 8
     nqkv = (Hq + 2 * Hkv) * D
-    cos, sin = _rope_tables(D, max_pos, cases.rope_base(norm))
+    cos, sin = rope_tables(D, max_pos, cases.rope_base(norm))
     s = attn_shape(B, L_, Hq, Hkv, D, act, act, 0, cap)
     qkv_d, kc_d, vc_d = dev(inp["qkv"].reshape(B * L_, nqkv), act), dev(inp["kc"], act), dev(inp["vc"], act)
     q_d = torch.zeros((B * L_, Hq * D), dtype=qkv_d.dtype, device="cuda")
@@ -249,7 +184,7 @@ def test_prefill_random_rows_under_the_rule(Hq, Hkv, D, norm, act, L_):
                                       cases.EPS, ptr(cos), ptr(sin), max_pos))
     torch.cuda.synchronize()
     assert np.array_equal(host(vc_d), vc_ref)
-    outs = {dma: _attention(s, q_d, kc_d, vc_d, off_d, D, dma=dma) for dma in ("1", "0")}
+    outs = {dma: attention(s, q_d, kc_d, vc_d, off_d, dma=dma) for dma in ("1", "0")}
     assert torch.equal(outs["1"], outs["0"])
     cases.assert_rule(host(outs["1"]).reshape(B, L_, Hq * D), want, act, f"prefill ({Hq},{Hkv},{D}) {act} L {L_}")
 
@@ -290,20 +225,20 @@ def _lookup_args(lookup, row_lens):
 def test_host_and_device_lookup_agree_bit_for_bit(Hq, Hkv, D, act, variant, nsplit):
     inp, want, kc_ref, vc_ref, row_lens = _lookup_case(Hq, Hkv, D, act)
     B = len(cases.LOOKUP_LENS)
-    cos, sin = _rope_tables(D, cases.LOOKUP_CAP + 8, cases.rope_base(False))
+    cos, sin = rope_tables(D, cases.LOOKUP_CAP + 8, cases.rope_base(False))
     s = attn_shape(B, 1, Hq, Hkv, D, act, act, 0, cases.LOOKUP_CAP)
     qkv_d = dev(inp["qkv"][:, 0], act)
     res = {}
     for lookup in ("device", "host"):
         kc_d, vc_d = dev(inp["kc"], act), dev(inp["vc"], act)
         off_d, rows_d, hrow, hoff = _lookup_args(lookup, row_lens)
-        first, second = _decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, D, nsplit, variant, rows_d=rows_d, hrow=hrow, hoff=hoff,
-                                repeat=2)
+        first, second = attention_decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, nsplit, variant, rows_d=rows_d, hrow=hrow,
+                                         hoff=hoff, repeat=2)
         assert np.array_equal(first, second), lookup       # the same call twice on the same buffers
         res[lookup] = (second, host(kc_d), host(vc_d))
     (od, kd, vd), (oh, kh, vh) = res["device"], res["host"]
     assert np.array_equal(oh, od)
     assert np.array_equal(kh, kd) and np.array_equal(vh, vd)
-    _check_new_rows(kh, vh, kc_ref, vc_ref, cases.LOOKUP_ROWS, cases.LOOKUP_LENS, act)
+    cases.check_new_rows(kh, vh, kc_ref, vc_ref, cases.LOOKUP_ROWS, cases.LOOKUP_LENS, act)
     for name, o in (("device", od), ("host", oh)):
         cases.assert_rule(o, want, act, f"decode variant {variant} ({Hq},{Hkv},{D}) {act} nsplit {nsplit} {name} lookup")

@@ -28,10 +28,10 @@ pytestmark = pytest.mark.gpu
 import attn16_cases as cases  # noqa: E402
 import attn_d96_cases as d96  # noqa: E402
 import test_gpu_attn_16bit as base16  # noqa: E402
-import test_gpu_attn_f32_blocks as base32  # noqa: E402
+import attn_f32_cases as f32  # noqa: E402
 import test_gpu_attn_gqa as gqa_tests  # noqa: E402
 from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import attn_shape, dev, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import attention, attn_shape, dev, dev_i32, host, identity_rope, ptr  # noqa: E402
 
 ACTS = ["bfloat16", "float16"]
 MI_ERR_UNSUPPORTED = -3
@@ -96,15 +96,15 @@ def test_f32_prefill_two_term_against_the_oracle_and_exact_form_refused(Hq, Hkv,
     """attn_prefill_f32s_kernel (two-term bf16 operands, the default) within rtol 1e-4 / atol 2e-5 of the float64 oracle on
     every query.  attn_prefill_f32_kernel (MI_ATTN_PREFILL_F32_EXACT=1) builds its V image from 64-wide halves of a row: it
     refuses D = 96 with MI_ERR_UNSUPPORTED (NotImplementedError through the binding) before it launches."""
-    kc, vc, q, want = gqa_tests._f32_prefill_case(Hq, Hkv, D, L_)
+    kc, vc, q, want = f32.prefill_case(Hq, Hkv, D, L_)
     offs, B = d96.F32_PREFILL_OFFS, len(d96.F32_PREFILL_OFFS)
     s = attn_shape(B, L_, Hq, Hkv, D, "float32", "float32", 0, d96.F32_PREFILL_CAP)
     q_d, kc_d, vc_d, off_d = dev(q.reshape(B * L_, Hq * D)), dev(kc), dev(vc), dev_i32(offs)
-    two = gqa_tests._attention32(s, q_d, kc_d, vc_d, off_d, Hq, D, exact="0").reshape(B, L_, Hq, D)
+    two = host(attention(s, q_d, kc_d, vc_d, off_d, exact="0")).reshape(B, L_, Hq, D)
     print(f"F32 prefill ({Hq},{Hkv},{D}) L {L_}: max |err| two-term {np.abs(two - want).max():.3e}")
     assert np.allclose(two, want, rtol=1e-4, atol=2e-5), np.abs(two - want).max()
     with pytest.raises(NotImplementedError, match="exact float32 form"):
-        gqa_tests._attention32(s, q_d, kc_d, vc_d, off_d, Hq, D, exact="1")
+        attention(s, q_d, kc_d, vc_d, off_d, exact="1")
 
 
 @pytest.mark.parametrize("nsplit", [1, 3])
@@ -112,14 +112,14 @@ def test_f32_unfused_decode_against_the_oracle(nsplit):
     """mi_op_attention with L = 1 on float32 caches (attn_kernel + attn_combine_kernel) over the caches the fused kernel leaves
     behind, at the bound tests/test_gpu_kernels.py holds for this kernel (rtol 1e-4, atol 2e-5)."""
     Hq, Hkv, D = d96.F32_UNFUSED_GEOM
-    c = base32._random_case(Hq, Hkv, D, "ragged")
+    c = f32.random_case(Hq, Hkv, D, "ragged")
     B = len(c["offs"])
     s = attn_shape(B, 1, Hq, Hkv, D, "float32", "float32", 0, c["cap"])
     # (the unfused kernel takes q after RoPE: rotated here with the oracle's tables)
     c_ref, s_ref = ref_model.rope_tables(D, 1e4, 1.0, max(c["offs"]) + 16)
     q = c["qkv"][:, :Hq * D].reshape(B, 1, Hq, D).transpose(0, 2, 1, 3)
     q = ref_model.rope(q, "float32", np.array([[o] for o in c["offs"]]), c_ref, s_ref).transpose(0, 2, 1, 3).reshape(B, Hq * D)
-    got = gqa_tests._attention32(s, dev(q), dev(c["kc_ref"]), dev(c["vc_ref"]), dev_i32(c["offs"]), Hq, D, nsplit=nsplit)
+    got = host(attention(s, dev(q), dev(c["kc_ref"]), dev(c["vc_ref"]), dev_i32(c["offs"]), nsplit))
     print(f"F32 unfused ({Hq},{Hkv},{D}) nsplit {nsplit}: max |err| {np.abs(got - c['want']).max():.3e}")
     assert np.allclose(got, c["want"], rtol=1e-4, atol=2e-5), np.abs(got - c["want"]).max()
 
@@ -139,7 +139,7 @@ def test_other_groups_at_96_and_other_widths_are_refused(Hq, Hkv, D, act):
     kc_d, vc_d = dev(rng.standard_normal((B, Hkv, cap, D)), act), dev(rng.standard_normal((B, Hkv, cap, D)), act)
     kc0, vc0 = kc_d.clone(), vc_d.clone()
     off_d = dev_i32([5, 9])
-    cos, sin = base16._identity_rope(cap + 1, D)
+    cos, sin = identity_rope(cap + 1, D)
     lib = L.lib()
     for L_ in (1, 18):
         s = attn_shape(B, L_, Hq, Hkv, D, act, act, 0, cap)

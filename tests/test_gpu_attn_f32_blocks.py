@@ -7,37 +7,19 @@ per-wave trip count and the cut of the cached keys over the splits in whole 16-k
 * Engine-level decode runs whose KV length crosses a 16-key and a 128 x nsplit boundary: 32 rows at one split, and 8 rows at
   2 splits and across a change of the split count (3 -> 4).
 """
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
-import torch
 
-from oracle import ref_generate, ref_model, ref_sample
+from oracle import ref_generate, ref_sample
 
 pytestmark = pytest.mark.gpu
 
-from mlx_parallm_amd import _lib as L  # noqa: E402
+import attn_f32_cases as f32  # noqa: E402
 from mlx_parallm_amd import utils  # noqa: E402
 from mlx_parallm_amd.engine import SampleArgs  # noqa: E402
-from gpu_helpers import attn_shape, dev, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import attention_decode, attn_shape, dev, dev_i32, host, identity_rope, rope_tables  # noqa: E402
 
 ACT = "float32"
-
-
-def _decode(s, qkv_d, kc_d, vc_d, off_d, cos, sin, Hq, Hkv, D, nsplit):
-    B = qkv_d.shape[0]
-    out = torch.zeros((B, Hq * D), dtype=torch.float32, device="cuda")
-    part = torch.zeros((B * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    ctr = torch.zeros((B * Hkv,), dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    L.check(L.lib().mi_op_attention_decode(C.byref(s), ptr(qkv_d), ptr(kc_d), ptr(vc_d), ptr(off_d), None, None, 1e-6,
-                                           ptr(cos), ptr(sin), ptr(out), float(D ** -0.5), 0, nsplit, ptr(part),
-                                           ptr(ctr), 0, 1, None))
-    torch.cuda.synchronize()
-    assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
-    return host(out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -73,8 +55,7 @@ def test_one_hot_scores_select_one_v_row_bit_for_bit(Hq, Hkv, D, nsplit):
     vc = rng.standard_normal((B, Hkv, cap, D)).astype(np.float32)
     vnew = rng.standard_normal((B, Hkv * D)).astype(np.float32)
     cand = [_lane_keys(pos, nsplit) for pos in LANE_POS]
-    cos = torch.ones((cap + 1, D // 2), dtype=torch.float32, device="cuda")
-    sin = torch.zeros_like(cos)
+    cos, sin = identity_rope(cap + 1, D)
     s = attn_shape(B, 1, Hq, Hkv, D, ACT, ACT, 0, cap)
     vc_d, off_d = dev(vc), dev_i32(LANE_POS)
     seen_keys, seen_d = set(), set()
@@ -97,7 +78,7 @@ def test_one_hot_scores_select_one_v_row_bit_for_bit(Hq, Hkv, D, nsplit):
                     want[b, h] = vc[b, kh, key]
                 seen_keys.add((b, key))
                 seen_d.add(((d % 16) // 4, d // 64))
-        got = _decode(s, dev(qkv), dev(kc), vc_d, off_d, cos, sin, Hq, Hkv, D, nsplit).reshape(B, Hq, D)
+        got = attention_decode(s, dev(qkv), dev(kc), vc_d, off_d, cos, sin, nsplit).reshape(B, Hq, D)
         bad = [(b, h) for b in range(B) for h in range(Hq) if not np.array_equal(got[b, h], want[b, h])]
         assert not bad, (p, bad[:8], len(bad))
     # the sweep reached every candidate key of every row, every lane-group quarter of d and every 64-half
@@ -109,41 +90,6 @@ def test_one_hot_scores_select_one_v_row_bit_for_bit(Hq, Hkv, D, nsplit):
 # random data against the float64 oracle
 
 GEOMS = [(8, 2, 128), (6, 2, 128), (5, 1, 128), (2, 2, 64)]
-BATCHES = {"ragged": [0, 1, 15, 16, 17, 127, 128, 129], "long": [1100, 2047]}
-
-
-@functools.lru_cache(maxsize=None)
-def _random_case(Hq, Hkv, D, batch):
-    """Inputs and the oracle's output / cache rows, computed once and shared by every split count (never modified)."""
-    offs = BATCHES[batch]
-    B, cap, max_pos = len(offs), max(offs) + 8, max(offs) + 16
-    rng = np.random.default_rng(4321 + Hq + D + len(offs))
-    cos = torch.zeros((max_pos, D // 2), dtype=torch.float32, device="cuda")
-    sin = torch.zeros_like(cos)
-    torch.cuda.synchronize()
-    L.check(L.lib().mi_op_rope_tables(ptr(cos), ptr(sin), max_pos, D, 1e4, 1.0))
-    c_ref, s_ref = ref_model.rope_tables(D, 1e4, 1.0, max_pos)
-    nqkv = (Hq + 2 * Hkv) * D
-    kc = rng.standard_normal((B, Hkv, cap, D)).astype(np.float32)
-    vc = rng.standard_normal((B, Hkv, cap, D)).astype(np.float32)
-    qkv = rng.standard_normal((B, 1, nqkv)).astype(np.float32)
-    q = qkv[..., :Hq * D].reshape(B, 1, Hq, D)
-    k = qkv[..., Hq * D:(Hq + Hkv) * D].reshape(B, 1, Hkv, D)
-    v = qkv[..., (Hq + Hkv) * D:].reshape(B, 1, Hkv, D).transpose(0, 2, 1, 3)
-    pos = np.array([[o] for o in offs])
-    q = ref_model.rope(q.transpose(0, 2, 1, 3), ACT, pos, c_ref, s_ref)
-    k = ref_model.rope(k.transpose(0, 2, 1, 3), ACT, pos, c_ref, s_ref)
-    kc_ref, vc_ref = kc.copy(), vc.copy()
-    want = np.zeros((B, Hq * D), np.float32)
-    for b in range(B):
-        kc_ref[b, :, offs[b]:offs[b] + 1] = k[b]
-        vc_ref[b, :, offs[b]:offs[b] + 1] = v[b]
-        n = offs[b] + 1
-        o, _ = ref_model.sdpa(q[b:b + 1], kc_ref[b:b + 1, :, :n], vc_ref[b:b + 1, :, :n], D ** -0.5, None, ACT, ACT)
-        want[b] = o[0].transpose(1, 0, 2).reshape(Hq * D)
-    for a in (kc, vc, qkv, kc_ref, vc_ref, want):
-        a.setflags(write=False)
-    return dict(offs=offs, cap=cap, cos=cos, sin=sin, kc=kc, vc=vc, qkv=qkv.reshape(B, nqkv), kc_ref=kc_ref, vc_ref=vc_ref, want=want)
 
 
 @pytest.mark.parametrize("nsplit", [1, 3, 4, 8, 16])
@@ -153,11 +99,12 @@ def test_random_rows_against_the_oracle(Hq, Hkv, D, batch, nsplit):
     """Ragged rows around the 16-key tile and the 128-key round (waves and whole splits without keys, one ragged tile), 1100
     keys (a third round on two waves only at 4 splits) and 2047 (sixteen rounds at one split); the cache receives exactly the
     new K / V row."""
-    c = _random_case(Hq, Hkv, D, batch)
+    c = f32.random_case(Hq, Hkv, D, batch)
+    cos, sin = rope_tables(D, f32.max_pos(batch), f32.ROPE_BASE)
     B = len(c["offs"])
     s = attn_shape(B, 1, Hq, Hkv, D, ACT, ACT, 0, c["cap"])
     kc_d, vc_d = dev(c["kc"]), dev(c["vc"])
-    got = _decode(s, dev(c["qkv"]), kc_d, vc_d, dev_i32(c["offs"]), c["cos"], c["sin"], Hq, Hkv, D, nsplit)
+    got = attention_decode(s, dev(c["qkv"]), kc_d, vc_d, dev_i32(c["offs"]), cos, sin, nsplit)
     gk, gv = host(kc_d), host(vc_d)
     for b, o in enumerate(c["offs"]):
         assert np.allclose(gk[b, :, o], c["kc_ref"][b, :, o], rtol=2e-5, atol=4e-5)      # (RoPE in float32 against float64 tables)

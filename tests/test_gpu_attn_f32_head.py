@@ -14,14 +14,12 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
 from oracle import ref_model
 
 pytestmark = pytest.mark.gpu
 
-from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import attn_shape, dev, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import attention_decode, attn_shape, dev, dev_i32, host, rope_tables  # noqa: E402
 
 ACT = "float32"
 LENS = [0, 1, 15, 16, 17, 127, 128, 129]               # cached keys of batch entry b
@@ -34,30 +32,17 @@ def _i32(a):
     return (C.c_int32 * len(a))(*a)
 
 
-def _decode(c, nsplit, lookup, kc_d, vc_d):
-    """One launch; lookup "device": rows[b] and offsets[row] are loaded by the kernel, "host": both come with the arguments."""
+def _decode(c, nsplit, lookup, kc_d, vc_d, repeat=1):
+    """lookup "device": rows[b] and offsets[row] are loaded by the kernel, "host": both come with the arguments."""
     Hq, Hkv, D = c["geom"]
-    B = len(LENS)
-    s = attn_shape(B, 1, Hq, Hkv, D, ACT, ACT, 0, c["cap"])
-    out = torch.zeros((B, Hq * D), dtype=torch.float32, device="cuda")
-    part = torch.zeros((B * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    ctr = torch.zeros((B * Hkv,), dtype=torch.int32, device="cuda")
+    s = attn_shape(len(LENS), 1, Hq, Hkv, D, ACT, ACT, 0, c["cap"])
     if lookup == "host":
         off_d, rows_d, hrow, hoff = dev_i32(np.zeros(NROWS)), None, _i32(ROWS), _i32(LENS)
     else:
         off_d, rows_d, hrow, hoff = dev_i32(c["row_lens"]), dev_i32(ROWS), None, None
-    qkv_d = dev(c["qkv"])
-
-    def launch():
-        torch.cuda.synchronize()
-        L.check(L.lib().mi_op_attention_decode_host(C.byref(s), ptr(qkv_d), ptr(kc_d), ptr(vc_d), ptr(off_d), None, None, 1e-6,
-                                                    ptr(c["cos"]), ptr(c["sin"]), ptr(out), float(D ** -0.5), 0, nsplit,
-                                                    ptr(part), ptr(ctr), 0, 1, None, ptr(rows_d), hrow, hoff))
-        torch.cuda.synchronize()
-        assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
-        return host(out)
-
-    return launch
+    cos, sin = rope_tables(D, max(LENS) + 16, 1e4)
+    return attention_decode(s, dev(c["qkv"]), kc_d, vc_d, off_d, cos, sin, nsplit, rows_d=rows_d, hrow=hrow, hoff=hoff,
+                            repeat=repeat)
 
 
 @functools.lru_cache(maxsize=None)
@@ -65,10 +50,6 @@ def _case(Hq, Hkv, D):
     """Inputs and the oracle's output / cache rows, computed once and shared by every test (never modified)."""
     B, cap, max_pos = len(LENS), max(LENS) + 8, max(LENS) + 16
     rng = np.random.default_rng(977 + Hq + D)
-    cos = torch.zeros((max_pos, D // 2), dtype=torch.float32, device="cuda")
-    sin = torch.zeros_like(cos)
-    torch.cuda.synchronize()
-    L.check(L.lib().mi_op_rope_tables(ptr(cos), ptr(sin), max_pos, D, 1e4, 1.0))
     c_ref, s_ref = ref_model.rope_tables(D, 1e4, 1.0, max_pos)
     nqkv = (Hq + 2 * Hkv) * D
     kc = rng.standard_normal((NROWS, Hkv, cap, D)).astype(np.float32)
@@ -91,7 +72,7 @@ def _case(Hq, Hkv, D):
         want[b] = o[0].transpose(1, 0, 2).reshape(Hq * D)
     for a in (kc, vc, qkv, kc_ref, vc_ref, want, row_lens):
         a.setflags(write=False)
-    return dict(geom=(Hq, Hkv, D), cap=cap, cos=cos, sin=sin, kc=kc, vc=vc, qkv=qkv.reshape(B, nqkv), kc_ref=kc_ref, vc_ref=vc_ref,
+    return dict(geom=(Hq, Hkv, D), cap=cap, kc=kc, vc=vc, qkv=qkv.reshape(B, nqkv), kc_ref=kc_ref, vc_ref=vc_ref,
                 want=want, row_lens=row_lens)
 
 
@@ -102,7 +83,7 @@ def test_host_and_device_lookup_agree_bit_for_bit(Hq, Hkv, D, nsplit):
     res = {}
     for lookup in ("device", "host"):
         kc_d, vc_d = dev(c["kc"]), dev(c["vc"])
-        res[lookup] = (_decode(c, nsplit, lookup, kc_d, vc_d)(), host(kc_d), host(vc_d))
+        res[lookup] = (_decode(c, nsplit, lookup, kc_d, vc_d), host(kc_d), host(vc_d))
     (od, kd, vd), (oh, kh, vh) = res["device"], res["host"]
     assert np.array_equal(oh, od), np.abs(oh - od).max()
     assert np.array_equal(kh, kd) and np.array_equal(vh, vd)
@@ -121,8 +102,6 @@ def test_same_call_twice_on_the_same_buffers(Hq, Hkv, D):
     """Nothing of the first launch's prologue (q in LDS, partials, tickets) may reach the second: equal outputs, tickets at
     zero after each (checked inside), the oracle's bound on both."""
     c = _case(Hq, Hkv, D)
-    launch = _decode(c, 4, "host", dev(c["kc"]), dev(c["vc"]))
-    first = launch().copy()
-    second = launch()
+    first, second = _decode(c, 4, "host", dev(c["kc"]), dev(c["vc"]), repeat=2)
     assert np.array_equal(first, second), np.abs(first - second).max()
     assert np.allclose(second, c["want"], rtol=1e-5, atol=2e-6), np.abs(second - c["want"]).max()

@@ -13,8 +13,6 @@ variant 0, VALU variant 1; 16-bit and float32 caches) and the unfused attn_kerne
 tests/test_gpu_gqa_models.py, bit for bit against the contiguous ones.)
 """
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 import pytest
@@ -27,9 +25,9 @@ pytestmark = pytest.mark.gpu
 import attn16_cases as cases  # noqa: E402
 import attn_gqa_cases as gqa  # noqa: E402
 import test_gpu_attn_16bit as base16  # noqa: E402
-import test_gpu_attn_f32_blocks as base32  # noqa: E402
+import attn_f32_cases as f32  # noqa: E402
 from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import attn_shape, dev, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import attention, attention_decode, attn_shape, dev, dev_i32, host, identity_rope, ptr, rope_tables  # noqa: E402
 
 ACTS = ["bfloat16", "float16"]
 MI_ERR_UNSUPPORTED = -3
@@ -78,31 +76,18 @@ def test_prefill_random_rows_under_the_rule(Hq, Hkv, D, norm, act, L_):
 # ---------------------------------------------------------------------------------------------------------------------------
 # float32 caches
 
-def _decode32(s, qkv_d, kc_d, vc_d, off_d, cos, sin, Hq, Hkv, D, nsplit, variant):
-    B = qkv_d.shape[0]
-    out = torch.zeros((B, Hq * D), dtype=torch.float32, device="cuda")
-    part = torch.zeros((B * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    ctr = torch.zeros((B * Hkv,), dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    L.check(L.lib().mi_op_attention_decode(C.byref(s), ptr(qkv_d), ptr(kc_d), ptr(vc_d), ptr(off_d), None, None, 1e-6,
-                                           ptr(cos), ptr(sin), ptr(out), float(D ** -0.5), 0, nsplit, ptr(part),
-                                           ptr(ctr), variant, 1, None))
-    torch.cuda.synchronize()
-    assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
-    return host(out)
-
-
 @pytest.mark.parametrize("nsplit", [1, 3, 4, 8])
 @pytest.mark.parametrize("batch", ["ragged", "long"])
 @pytest.mark.parametrize("variant,Hq,Hkv,D", [(v, *g) for v, gs in gqa.F32_DECODE_GEOMS.items() for g in gs])
 def test_f32_decode_random_rows_against_the_oracle(variant, Hq, Hkv, D, batch, nsplit):
     """tests/test_gpu_attn_f32_blocks.py::test_random_rows_against_the_oracle (its batches, its oracle, its bound) with the
     variant as a parameter: 0 = the 16x16x4 matrix-core loop at G = 6, 1 = the vector-ALU kernel at G = 3 and 6."""
-    c = base32._random_case(Hq, Hkv, D, batch)
+    c = f32.random_case(Hq, Hkv, D, batch)
+    cos, sin = rope_tables(D, f32.max_pos(batch), f32.ROPE_BASE)
     B = len(c["offs"])
     s = attn_shape(B, 1, Hq, Hkv, D, "float32", "float32", 0, c["cap"])
     kc_d, vc_d = dev(c["kc"]), dev(c["vc"])
-    got = _decode32(s, dev(c["qkv"]), kc_d, vc_d, dev_i32(c["offs"]), c["cos"], c["sin"], Hq, Hkv, D, nsplit, variant)
+    got = attention_decode(s, dev(c["qkv"]), kc_d, vc_d, dev_i32(c["offs"]), cos, sin, nsplit, variant)
     gk, gv = host(kc_d), host(vc_d)
     for b, o in enumerate(c["offs"]):
         assert np.allclose(gk[b, :, o], c["kc_ref"][b, :, o], rtol=2e-5, atol=4e-5)      # (RoPE in float32 against float64 tables)
@@ -114,49 +99,18 @@ def test_f32_decode_random_rows_against_the_oracle(variant, Hq, Hkv, D, batch, n
     assert np.allclose(got, c["want"], rtol=1e-5, atol=2e-6), err.max()
 
 
-@functools.lru_cache(maxsize=None)
-def _f32_prefill_case(Hq, Hkv, D, L_):
-    """A cache that already holds the call's keys, the queries and the float64 oracle's outputs (read-only, shared)."""
-    offs, cap = gqa.F32_PREFILL_OFFS, gqa.F32_PREFILL_CAP
-    rng = np.random.default_rng(977 + 10 * Hq + D + L_)
-    B = len(offs)
-    kc = rng.standard_normal((B, Hkv, cap, D)).astype(np.float32)
-    vc = rng.standard_normal((B, Hkv, cap, D)).astype(np.float32)
-    q = rng.standard_normal((B, L_, Hq, D)).astype(np.float32)
-    want = cases.prefill_oracle(q, kc, vc, offs, L_, D, "float32")
-    for a in (kc, vc, q, want):
-        a.setflags(write=False)
-    return kc, vc, q, want
-
-
-def _attention32(s, q_d, kc_d, vc_d, off_d, Hq, D, nsplit=1, exact=None):
-    out = torch.zeros((s.B * s.L, Hq * D), dtype=torch.float32, device="cuda")
-    part = torch.zeros((s.B * s.L * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    if exact is not None:
-        os.environ["MI_ATTN_PREFILL_F32_EXACT"] = exact
-    try:
-        torch.cuda.synchronize()
-        L.check(L.lib().mi_op_attention(C.byref(s), ptr(q_d), ptr(kc_d), ptr(vc_d), ptr(off_d), ptr(out), float(D ** -0.5),
-                                        nsplit, ptr(part)))
-        torch.cuda.synchronize()
-    finally:
-        if exact is not None:
-            del os.environ["MI_ATTN_PREFILL_F32_EXACT"]
-    return host(out)
-
-
 @pytest.mark.parametrize("L_", gqa.F32_PREFILL_L)
 @pytest.mark.parametrize("Hq,Hkv,D", gqa.F32_PREFILL_GEOMS)
 def test_f32_prefill_both_forms_against_the_oracle(Hq, Hkv, D, L_):
     """attn_prefill_f32s_kernel (two-term bf16 operands, the default) within rtol 1e-4 / atol 2e-5 of the float64 oracle and
     attn_prefill_f32_kernel (MI_ATTN_PREFILL_F32_EXACT=1, exact products) within rtol 1e-5 / atol 2e-6: the bounds of
     tests/test_gpu_kernels.py::test_prefill_attention_many_blocks, here on every query."""
-    kc, vc, q, want = _f32_prefill_case(Hq, Hkv, D, L_)
+    kc, vc, q, want = f32.prefill_case(Hq, Hkv, D, L_)
     offs, B = gqa.F32_PREFILL_OFFS, len(gqa.F32_PREFILL_OFFS)
     s = attn_shape(B, L_, Hq, Hkv, D, "float32", "float32", 0, gqa.F32_PREFILL_CAP)
     q_d, kc_d, vc_d, off_d = dev(q.reshape(B * L_, Hq * D)), dev(kc), dev(vc), dev_i32(offs)
-    two = _attention32(s, q_d, kc_d, vc_d, off_d, Hq, D, exact="0").reshape(B, L_, Hq, D)
-    exact = _attention32(s, q_d, kc_d, vc_d, off_d, Hq, D, exact="1").reshape(B, L_, Hq, D)
+    two = host(attention(s, q_d, kc_d, vc_d, off_d, exact="0")).reshape(B, L_, Hq, D)
+    exact = host(attention(s, q_d, kc_d, vc_d, off_d, exact="1")).reshape(B, L_, Hq, D)
     print(f"F32 prefill ({Hq},{Hkv},{D}) L {L_}: max |err| two-term {np.abs(two - want).max():.3e}, exact {np.abs(exact - want).max():.3e}")
     assert np.allclose(two, want, rtol=1e-4, atol=2e-5), np.abs(two - want).max()
     assert np.allclose(exact, want, rtol=1e-5, atol=2e-6), np.abs(exact - want).max()
@@ -167,14 +121,14 @@ def test_f32_unfused_decode_against_the_oracle(nsplit):
     """mi_op_attention with L = 1 on float32 caches (attn_kernel + attn_combine_kernel) over the caches the fused kernel leaves
     behind, at the bound tests/test_gpu_kernels.py holds for this kernel (rtol 1e-4, atol 2e-5)."""
     Hq, Hkv, D = gqa.F32_UNFUSED_GEOM
-    c = base32._random_case(Hq, Hkv, D, "ragged")
+    c = f32.random_case(Hq, Hkv, D, "ragged")
     B = len(c["offs"])
     s = attn_shape(B, 1, Hq, Hkv, D, "float32", "float32", 0, c["cap"])
     # (the unfused kernel takes q after RoPE: rotated here with the oracle's tables)
     c_ref, s_ref = ref_model.rope_tables(D, 1e4, 1.0, max(c["offs"]) + 16)
     q = c["qkv"][:, :Hq * D].reshape(B, 1, Hq, D).transpose(0, 2, 1, 3)
     q = ref_model.rope(q, "float32", np.array([[o] for o in c["offs"]]), c_ref, s_ref).transpose(0, 2, 1, 3).reshape(B, Hq * D)
-    got = _attention32(s, dev(q), dev(c["kc_ref"]), dev(c["vc_ref"]), dev_i32(c["offs"]), Hq, D, nsplit=nsplit)
+    got = host(attention(s, dev(q), dev(c["kc_ref"]), dev(c["vc_ref"]), dev_i32(c["offs"]), nsplit))
     print(f"F32 unfused ({Hq},{Hkv},{D}) nsplit {nsplit}: max |err| {np.abs(got - c['want']).max():.3e}")
     assert np.allclose(got, c["want"], rtol=1e-4, atol=2e-5), np.abs(got - c["want"]).max()
 
@@ -191,7 +145,7 @@ def test_seven_query_heads_per_kv_head_are_still_refused(act):
     rng = np.random.default_rng(5)
     kc_d, vc_d = dev(rng.standard_normal((B, Hkv, cap, D)), act), dev(rng.standard_normal((B, Hkv, cap, D)), act)
     off_d = dev_i32([5, 9])
-    cos, sin = base16._identity_rope(cap + 1, D)
+    cos, sin = identity_rope(cap + 1, D)
     lib = L.lib()
     for L_ in (1, 18):
         s = attn_shape(B, L_, Hq, Hkv, D, act, act, 0, cap)

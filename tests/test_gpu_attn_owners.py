@@ -13,7 +13,7 @@ through mi_op_attention_decode (rows and lengths from device memory) and mi_op_a
 Reference and bounds are those of the existing kernel-level tests of the same call: the float64 oracle of
 tests/attn16_cases.py; float32 within rtol 1e-5 / atol 2e-6 and the new K row within rtol 2e-5 / atol 4e-5
 (tests/test_gpu_attn_f32_blocks.py, tests/test_gpu_attn_gqa.py), 16-bit caches under cases.assert_rule and
-test_gpu_attn_16bit._check_new_rows.  At every split count the same bounds hold, and in addition
+attn16_cases.check_new_rows.  At every split count the same bounds hold, and in addition
   * the two entry points agree bit for bit, and so does the same call made twice;
   * the cache rows at pos are bit for bit what the call with one split appends;
   * every other cache row, and the sentinel margins around the output and both caches, are untouched.
@@ -29,9 +29,7 @@ pytestmark = pytest.mark.gpu
 
 import attn16_cases as cases  # noqa: E402
 import attn_owner_cases as own  # noqa: E402
-import test_gpu_attn_16bit as base16  # noqa: E402
-from mlx_parallm_amd import _lib as L  # noqa: E402
-from gpu_helpers import TDT, attn_shape, dev_i32, host, ptr  # noqa: E402
+from gpu_helpers import TDT, attention_decode, attn_shape, dev_i32, host, rope_tables  # noqa: E402
 
 B, HKV = 3, 2
 POS = [0, 1, 15, 16, 17, 256, 273]
@@ -76,28 +74,23 @@ def _case(G, D, act, lens):
 def _launch(G, D, act, lens, inp, nsplit, entry, repeat=1):
     """`repeat` launches on the same buffers -> ([outputs], K cache, V cache); margins and tickets checked after each."""
     Hq = G * HKV
-    cos, sin = base16._rope_tables(D, CAP + 8, cases.rope_base(False))
+    cos, sin = rope_tables(D, CAP + 8, cases.rope_base(False))
     s = attn_shape(B, 1, Hq, HKV, D, act, act, 0, CAP)
     kc, vc = _Fenced(inp["kc"], act), _Fenced(inp["vc"], act)
     out = _Fenced(np.zeros((B, Hq * D), np.float32), act)
     qkv_d = torch.from_numpy(inp["qkv"][:, 0]).to(TDT[act]).cuda().contiguous()
-    part = torch.zeros((B * Hq * nsplit * (D + 2),), dtype=torch.float32, device="cuda")
-    ctr = torch.zeros((B * HKV,), dtype=torch.int32, device="cuda")
     if entry == "host":                                    # no device rows, zeroed device lengths: only the arguments can serve
-        off_d, tail = dev_i32(np.zeros(B)), (None, (C.c_int32 * B)(*range(B)), (C.c_int32 * B)(*lens))
+        off_d, hrow, hoff = dev_i32(np.zeros(B)), (C.c_int32 * B)(*range(B)), (C.c_int32 * B)(*lens)
     else:
-        off_d, tail = dev_i32(lens), None
-    outs = []
-    for _ in range(repeat):
-        args = (C.byref(s), ptr(qkv_d), kc.ptr(), vc.ptr(), ptr(off_d), None, None, cases.EPS, ptr(cos), ptr(sin), out.ptr(),
-                float(D ** -0.5), 0, nsplit, ptr(part), ptr(ctr), 0, 1, None)
-        torch.cuda.synchronize()
-        L.check(L.lib().mi_op_attention_decode(*args) if tail is None else L.lib().mi_op_attention_decode_host(*args, *tail))
-        torch.cuda.synchronize()
-        assert not ctr.cpu().numpy().any()                 # tickets are handed back for the next launch
+        off_d, hrow, hoff = dev_i32(lens), None, None
+
+    def read():
         assert out.margins_intact() and kc.margins_intact() and vc.margins_intact(), (entry, nsplit, lens)
-        outs.append(out.get())
-    return outs, kc.get(), vc.get()
+        return out.get()
+
+    outs = attention_decode(s, qkv_d, kc.ptr(), vc.ptr(), off_d, cos, sin, nsplit, hrow=hrow, hoff=hoff, repeat=repeat,
+                            out=out.ptr(), read=read)
+    return (outs if repeat > 1 else [outs]), kc.get(), vc.get()
 
 
 def _check_batch(G, D, act, lens):
@@ -126,7 +119,7 @@ def _check_batch(G, D, act, lens):
                   f"{float((err / (1e-5 * np.abs(want) + 2e-6)).max()):.3f}")
             assert np.allclose(dev_out, want, rtol=1e-5, atol=2e-6), (what, nsplit, err.max())
         else:
-            base16._check_new_rows(gk, gv, kc_ref, vc_ref, range(B), lens, act)
+            cases.check_new_rows(gk, gv, kc_ref, vc_ref, range(B), lens, act)
             cases.assert_rule(dev_out, want, act, f"{what} nsplit {nsplit}")
 
 
