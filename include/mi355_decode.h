@@ -252,6 +252,19 @@ int mi_step_enqueue_mixed(mi_engine* e, mi_kv* kv, const int32_t* rows, const in
                           const int32_t* tokens, const mi_sample_params* sp, int64_t* ticket);
 /* Forget the contents of one row (its length becomes 0); ordered behind the steps already enqueued. */
 int mi_kv_reset_row(mi_kv* kv, int row);
+/* Row `dst` (empty: mi_kv_reset_row first) becomes a copy of the first n_tokens tokens of row `src`, 1 <= n_tokens <= length
+ * of src: the n choices of one request share one prompt prefill.  Paged cache: the full blocks are shared read-only (a block
+ * that is not full is never shared) and the partly filled tail is copied into a block of dst's own, which costs one block --
+ * none when n_tokens is a multiple of block_tokens.  Contiguous cache: all n_tokens are copied.  One launch either way, for
+ * every layer, KV head, K and V.  dst's length becomes n_tokens; its logit_bias and logprobs setting are NOT forked: it starts
+ * as an empty row does.  src keeps running untouched, and either row may be reset first.
+ * Ordered on the engine's stream like mi_kv_reset_row: behind every step already enqueued (the pending appends of src are
+ * in), ahead of every later one.
+ * MI_ERR_INVALID, naming the argument, with nothing changed: a null kv; src or dst outside the cache; src == dst; a dst that is
+ * not empty; n_tokens outside [1, length of src].  MI_ERR_RUNTIME when the arena has no block for the tail: nothing changed.
+ * MI_ERR_RUNTIME when the launch or the length update fails: dst is empty again and its blocks are back in the arena, but a
+ * prefix-cache block that was evicted to make room for the tail stays evicted. */
+int mi_kv_fork_row(mi_kv* kv, int src, int dst, int n_tokens);
 /* logit_bias of the REQUEST that occupies cache row `row` (the reference's logit_bias dict, utils.py:346-349, is one per call;
  * under continuous batching requests with different dicts share a step): n entries (ids[i], values[i]) replace the row's
  * bias, n == 0 clears it (ids / values may then be NULL).  Set once at admission, it travels with the row -- nothing is

@@ -18,6 +18,7 @@
  *   mi_op_sample      sample closure + top_p_sampling: utils.py:345-364; sample_utils.py:3-38
  *   mi_op_sample_ex   the same kernel with top_k / min_p and per-row random streams (no counterpart in the reference)
  *   mi_op_sample_rowbias  ... and a call-wide logit_bias list (utils.py:346-349) + the per-row table (no counterpart)
+ *   mi_op_kv_copy_tokens  the tail copy of mi_kv_fork_row (no counterpart in the reference)
  *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
  */
 #ifndef MI355_OPS_H
@@ -148,6 +149,16 @@ int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, in
  * storage.  M >= 1, I a positive multiple of 8 (else MI_ERR_UNSUPPORTED), ldx >= 2 I, ldo >= I, buffers aligned to their
  * element (else MI_ERR_INVALID); nothing is launched on a refused call. */
 int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd);
+/* the copy of mi_kv_fork_row (mi355_decode.h) on its own, one launch: in each of `layers` layers (layer_elems elements apart),
+ * for each of Hkv heads (head_stride elements apart) and in kcache and vcache alike, the n_tokens x D elements at element
+ * offset src_off (of head 0, inside the layer) are copied to dst_off, in 16-byte pieces.  kv_dtype = MI_F32 / MI_BF16 /
+ * MI_F16 elements.  Paged arena [block][Hkv][block_tokens][D]: head_stride = block_tokens x D, the offsets those of the
+ * first tail token in the two blocks; contiguous cache [row][Hkv][cap][D]: head_stride = cap x D, the offsets those of the
+ * two rows.  MI_ERR_UNSUPPORTED: a span, stride, offset or pointer that is no multiple of 16 bytes (head widths 32, 64, 96
+ * and 128 always are); MI_ERR_INVALID: spans that leave the layer or where a destination touches a source.  Nothing is
+ * launched on a refused call. */
+int mi_op_kv_copy_tokens(void* kcache, void* vcache, int kv_dtype, int layers, int64_t layer_elems, int Hkv, int D,
+                         int64_t head_stride, int64_t src_off, int64_t dst_off, int n_tokens);
 /* tile-major weight layout of the streaming kernels (what mi_engine_finalize applies to eligible
  * matrices): returns the size of the tiled buffer (0 if the matrix is not eligible) / fills `dst`. */
 uint64_t mi_op_tiled_bytes(const mi_op_linear* row_major);

@@ -102,6 +102,7 @@ SIGNATURES = {
     "mi_step_enqueue_rows": (C.c_int, [_P, _P, _I32P, C.c_int, _I32P, C.c_int, C.POINTER(SampleParams), C.POINTER(C.c_int64)]),
     "mi_step_enqueue_mixed": (C.c_int, [_P, _P, _I32P, _I32P, _I32P, C.c_int, _I32P, C.POINTER(SampleParams), C.POINTER(C.c_int64)]),
     "mi_kv_reset_row": (C.c_int, [_P, C.c_int]),
+    "mi_kv_fork_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mi_kv_set_row_logit_bias": (C.c_int, [_P, C.c_int, _I32P, _F32P, C.c_int]),
     "mi_kv_set_row_logprobs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mi_step_wait": (C.c_int, [_P, C.c_int64, _I32P, _F32P, _F32P, _I32P, _F32P]),
@@ -126,6 +127,7 @@ SIGNATURES = {
     "mi_op_gemm_prefill_f32": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mi_op_split_rows": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P]),
     "mi_op_swiglu_rows": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_op_kv_copy_tokens": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "mi_op_tiled_bytes": (C.c_uint64, [C.POINTER(OpLinear)]),
     "mi_op_repack_tiled": (C.c_int, [C.POINTER(OpLinear), _P]),
     "mi_op_embed": (C.c_int, [C.POINTER(OpLinear), _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -52,6 +52,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv-blocks", type=int, default=None, help="continuous scheduler: 64-token blocks of the paged KV arena "
                    "(default: every slot at full length, capped at 80 %% of the free device memory).")
     p.add_argument("--no-prefix-cache", action="store_true", help="continuous scheduler: do not reuse the KV blocks of a common prompt prefix.")
+    p.add_argument("--fork-choices", action="store_true", help="continuous scheduler: the n choices of a request share one "
+                   "prompt prefill (the KV row is forked; the last prompt token of a forked choice runs as a decode step).")
     p.add_argument("--version", action="version", version="0.2.0")
     return p
 
@@ -64,7 +66,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> ServerConfig:
                         max_concurrent_streams=ns.max_concurrent_streams, scheduler=ns.scheduler,
                         diverse_mode=bool(ns.diverse_mode), max_context_length=ns.max_context_length, device=ns.device,
                         devices=[int(x) for x in ns.devices.split(",")] if ns.devices else None,
-                        chunk_tokens=ns.chunk_tokens, kv_blocks=ns.kv_blocks, prefix_cache=not ns.no_prefix_cache)
+                        chunk_tokens=ns.chunk_tokens, kv_blocks=ns.kv_blocks, prefix_cache=not ns.no_prefix_cache,
+                        fork_choices=bool(ns.fork_choices))
 
 
 def cli_runner(argv: Optional[Sequence[str]] = None) -> None:

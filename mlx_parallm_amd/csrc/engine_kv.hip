@@ -1,4 +1,4 @@
-// engine_kv.hip -- the mi_kv_* entry points: contiguous and block-paged caches, prefix reuse, per-row logit_bias.  The paged
+// engine_kv.hip -- the mi_kv_* entry points: contiguous and block-paged caches, prefix reuse, forked rows, per-row logit_bias.  The paged
 // cache's host state (block pool, tables, prefix cache) is mi::KvBlocks (kv_blocks.h); here are the argument checks and
 // whatever a call enqueues on the engine's stream.
 #include <cmath>
@@ -208,6 +208,45 @@ int mi_kv_reset_row(mi_kv* kv, int row) {
   kv_release_row(kv, row);      // (paged: the blocks go back to the pool; whoever gets them next writes behind the steps in flight)
   MI_TRY(rb_clear_row(kv, row));                            // the next occupant of the row samples unbiased
   return lp_clear_row(kv, row);                             // and reports what its own request asks for
+}
+
+int mi_kv_fork_row(mi_kv* kv, int src, int dst, int n_tokens) {
+  if (!kv) return fail(MI_ERR_INVALID, "null kv");
+  if (src < 0 || src >= kv->B) return fail(MI_ERR_INVALID, "mi_kv_fork_row: src out of range");
+  if (dst < 0 || dst >= kv->B) return fail(MI_ERR_INVALID, "mi_kv_fork_row: dst out of range");
+  if (src == dst) return fail(MI_ERR_INVALID, "mi_kv_fork_row: src and dst are the same row");
+  if (kv->h_off[dst] != 0 || (kv->paged && kv->blocks.row_blocks[dst] != 0))
+    return fail(MI_ERR_INVALID, "mi_kv_fork_row: dst must be empty (mi_kv_reset_row first)");
+  if (n_tokens < 1 || n_tokens > kv->h_off[src])
+    return fail(MI_ERR_INVALID, "mi_kv_fork_row: n_tokens must be in [1, " + std::to_string(kv->h_off[src]) + "], the length of src");
+  MI_HIP(hipSetDevice(kv->e->device));
+  const mi_model_desc& d = kv->e->d;
+  hipStream_t st = kv->e->stream;
+  // on the engine's stream: behind every step already enqueued (the appends of src are in), ahead of every later one
+  int rc = MI_OK;
+  if (kv->paged) {
+    int src_blk = 0, dst_blk = 0;
+    switch (kv->blocks.fork(src, dst, n_tokens, &src_blk, &dst_blk)) {
+      case KvBlocks::Ensure::TOO_LONG: return fail(MI_ERR_INVALID, "mi_kv_fork_row: n_tokens is longer than the row's block table");
+      case KvBlocks::Ensure::EXHAUSTED: return fail(MI_ERR_RUNTIME, "mi_kv_fork_row: the block arena has no block for the tail (every block is held by a live sequence)");
+      case KvBlocks::Ensure::OK: break;
+    }
+    const int bs = 1 << kv->blocks.bs_shift, tail = n_tokens & (bs - 1);
+    if (tail > 0) {       // the full blocks are shared; the tail starts at the same token of both blocks
+      const size_t head = (size_t)bs * d.head_dim, blk = (size_t)d.num_kv_heads * head;
+      rc = launch_kv_copy_tokens(kv->k, kv->v, kv->dtype, d.num_layers, kv_layer_elems(kv, d), d.num_kv_heads, d.head_dim, head,
+                                 (size_t)src_blk * blk, (size_t)dst_blk * blk, tail, st);
+    }
+  } else {
+    const size_t head = (size_t)kv->cap * d.head_dim, row = (size_t)d.num_kv_heads * head;
+    rc = launch_kv_copy_tokens(kv->k, kv->v, kv->dtype, d.num_layers, kv_layer_elems(kv, d), d.num_kv_heads, d.head_dim, head,
+                               (size_t)src * row, (size_t)dst * row, n_tokens, st);
+  }
+  if (rc == MI_OK && hipMemsetD32Async((hipDeviceptr_t)(kv->d_off + dst), n_tokens, 1, st) != hipSuccess)
+    rc = fail(MI_ERR_RUNTIME, "mi_kv_fork_row: hipMemsetD32Async failed");
+  if (rc != MI_OK) { kv_release_row(kv, dst); return rc; }     // dst stays empty
+  kv->h_off[dst] = n_tokens;
+  return MI_OK;
 }
 
 int mi_kv_set_row_logprobs(mi_kv* kv, int row, int top_logprobs, int at_temperature) {

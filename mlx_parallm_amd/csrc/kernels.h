@@ -338,6 +338,11 @@ int launch_sample(const SampleCall& c, hipStream_t st);
 int launch_advance_offsets(int32_t* offsets, const int32_t* rows, int B, int L, hipStream_t st);
 // dst[i][:] = src[idx[i]][:] for n rows of row_bytes (a multiple of 16) each; idx on the device
 int launch_gather_rows(const void* src, size_t row_bytes, const int32_t* idx, int n, void* dst, hipStream_t st);
+// the first tokens of a cache row given to another row (mi_kv_fork_row): for every layer, kv head and for K and V alike, the
+// n_tokens x D elements at src_off go to dst_off -- element offsets of head 0 inside a layer of layer_elems elements, head h
+// at + h x head_stride.  One launch, 16-byte pieces; everything must be a multiple of 16 bytes and the spans apart.
+int launch_kv_copy_tokens(void* kcache, void* vcache, int kv_dtype, int layers, size_t layer_elems, int Hkv, int D,
+                          size_t head_stride, size_t src_off, size_t dst_off, int n_tokens, hipStream_t st);
 // rope_traditional (llama.py:77-82) at load time: dst row (h D + j) = src row (h D + 2 j), dst row (h D + D/2 + j) = src row
 // (h D + 2 j + 1) for j < D/2, over nrows = heads x D rows of row_bytes each (src != dst).  Applied alike to the q and k rows of
 // a q|k|v matrix (codes, scales, quantisation biases), to their linear biases and to the columns of a LoRA B (as rows of

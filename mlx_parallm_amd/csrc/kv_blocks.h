@@ -4,6 +4,10 @@
 //
 // A row owns the blocks its table names, in order; block 0 is never handed out (unassigned table entries point at it, so a
 // clamped address is always mapped memory).  refcnt[b] = rows that map block b + 1 if the prefix cache holds it.
+//
+// Sharing (attach, fork) is read-only and covers FULL blocks alone.  The invariant: a block that is not full is mapped by
+// exactly one row and is never in the prefix cache.  No shared block is ever written, because the kernels append at a row's
+// own length only -- behind its last full block, in a block of its own (ensure) or in the private copy that fork made.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -107,6 +111,27 @@ struct KvBlocks {
       parent = h;
     }
     lru_touch_chain(chain);
+  }
+
+  // An EMPTY row `dst` (the caller checks) becomes a copy of the first n_tokens tokens of `src` (1 <= n_tokens <= the length
+  // of src: the caller checks).  The n_tokens >> bs_shift full blocks are mapped, not copied (one more reference each); a
+  // partly filled tail gets ONE block of dst's own (take_block: a cache-only prefix block may be evicted for it, as in
+  // ensure), and the two tail block ids are reported for the caller's copy -- both 0 when n_tokens is a multiple of the
+  // block size, which needs neither a block nor a copy.  A failure leaves both rows, refcnt and the free list as they were.
+  Ensure fork(int src, int dst, int n_tokens, int* src_tail_blk, int* dst_tail_blk) {
+    const int full = n_tokens >> bs_shift;
+    const bool tail = (n_tokens & ((1 << bs_shift) - 1)) != 0;
+    *src_tail_blk = *dst_tail_blk = 0;
+    if (full + (tail ? 1 : 0) > bt_stride) return Ensure::TOO_LONG;
+    int own = 0;
+    if (tail && (own = take_block()) < 0) return Ensure::EXHAUSTED;      // first: nothing else has changed yet
+    const int32_t* s = &h_btab[(size_t)src * bt_stride];
+    int32_t* d = &h_btab[(size_t)dst * bt_stride];
+    for (int i = 0; i < full; ++i) { d[i] = s[i]; ++refcnt[s[i]]; }
+    if (tail) { d[full] = own; *src_tail_blk = s[full]; *dst_tail_blk = own; }
+    row_blocks[dst] = full + (tail ? 1 : 0);
+    btab_dirty = true;
+    return Ensure::OK;
   }
 
   void clear_prefix() {

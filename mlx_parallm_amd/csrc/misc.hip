@@ -850,6 +850,42 @@ int launch_gather_rows(const void* src, size_t row_bytes, const int32_t* idx, in
   return MI_OK;
 }
 
+// mi_kv_fork_row's copy: for every (layer, kv head, K | V) -- blockIdx.y -- the span of span_vecs 16-byte pieces at src_vec
+// goes to dst_vec, both counted from the head's start in the K or V array (layer stride layer_vecs, head stride head_vecs).
+// blockIdx.x strides over the pieces, one piece per lane and round.  The spans of one launch never overlap (two blocks of an
+// arena, two rows of a cache).
+__global__ __launch_bounds__(256) void kv_copy_tokens_kernel(u128* kc, u128* vc, size_t layer_vecs, int Hkv, size_t head_vecs,
+                                                             size_t src_vec, size_t dst_vec, unsigned span_vecs) {
+  const unsigned unit = blockIdx.y, lh = unit >> 1, layer = lh / (unsigned)Hkv, head = lh - layer * (unsigned)Hkv;
+  u128* base = ((unit & 1) ? vc : kc) + (size_t)layer * layer_vecs + (size_t)head * head_vecs;
+  const u128* s = base + src_vec;
+  u128* d = base + dst_vec;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < span_vecs; i += gridDim.x * 256) d[i] = s[i];
+}
+
+int launch_kv_copy_tokens(void* kcache, void* vcache, int kv_dtype, int layers, size_t layer_elems, int Hkv, int D,
+                          size_t head_stride, size_t src_off, size_t dst_off, int n_tokens, hipStream_t st) {
+  if (kv_dtype != MI_F32 && kv_dtype != MI_BF16 && kv_dtype != MI_F16) return fail(MI_ERR_INVALID, "kv_copy_tokens: bad element type");
+  if (!kcache || !vcache || layers < 1 || Hkv < 1 || D < 1 || n_tokens < 1) return fail(MI_ERR_INVALID, "kv_copy_tokens: bad argument");
+  const size_t es = dtype_size(kv_dtype), span = (size_t)n_tokens * D;
+  if (((uintptr_t)kcache | (uintptr_t)vcache) % 16 != 0 || (layer_elems * es) % 16 != 0 || (head_stride * es) % 16 != 0 ||
+      (src_off * es) % 16 != 0 || (dst_off * es) % 16 != 0 || (span * es) % 16 != 0)
+    return fail(MI_ERR_UNSUPPORTED, "kv_copy_tokens: every span, stride and offset must be a multiple of 16 bytes");
+  // the spans lie inside their heads and the heads inside a layer; no head's destination touches any head's source: the two
+  // sets of heads lie apart (two blocks, two rows), or they interleave with room for a span on either side
+  const size_t delta = src_off < dst_off ? dst_off - src_off : src_off - dst_off, r = head_stride ? delta % head_stride : 0;
+  if (span > head_stride || std::max(src_off, dst_off) + (size_t)(Hkv - 1) * head_stride + span > layer_elems ||
+      !(delta >= (size_t)Hkv * head_stride || (r >= span && head_stride - r >= span)))
+    return fail(MI_ERR_INVALID, "kv_copy_tokens: the spans overlap or leave the layer");
+  const size_t units = (size_t)layers * Hkv * 2, span_vecs = span * es / 16;
+  if (units > 65535 || span_vecs > 0xffffffffu - 32 * 256) return fail(MI_ERR_UNSUPPORTED, "kv_copy_tokens: too many layers x heads, or a span too long");
+  const unsigned gx = (unsigned)std::min<size_t>((span_vecs + 255) / 256, 32);
+  hipLaunchKernelGGL(kv_copy_tokens_kernel, dim3(gx, (unsigned)units), dim3(256), 0, st, (u128*)kcache, (u128*)vcache,
+                     layer_elems * es / 16, Hkv, head_stride * es / 16, src_off * es / 16, dst_off * es / 16, (unsigned)span_vecs);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
 // rope_traditional: rows of a [nrows][row_u16 x 2 bytes] array regrouped inside every run of D rows (one head), new row j <-
 // old row 2 j, new row D/2 + j <- old row 2 j + 1: the interleaved pairs (2 i, 2 i + 1) become the half-split pairs
 // (i, i + D/2) that the RoPE kernels rotate.  One thread per 16-bit unit of the destination (load time only).

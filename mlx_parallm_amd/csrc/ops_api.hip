@@ -277,6 +277,16 @@ int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, 
   return finish();
 }
 
+// kv_copy_tokens_kernel (misc.hip) on its own; the launch validates its arguments
+int mi_op_kv_copy_tokens(void* kcache, void* vcache, int kv_dtype, int layers, int64_t layer_elems, int Hkv, int D,
+                         int64_t head_stride, int64_t src_off, int64_t dst_off, int n_tokens) {
+  if (layer_elems < 1 || head_stride < 1 || src_off < 0 || dst_off < 0) return fail(MI_ERR_INVALID, "kv_copy_tokens: bad argument");
+  MI_TRY(ready());
+  MI_TRY(launch_kv_copy_tokens(kcache, vcache, kv_dtype, layers, (size_t)layer_elems, Hkv, D, (size_t)head_stride, (size_t)src_off,
+                               (size_t)dst_off, n_tokens, nullptr));
+  return finish();
+}
+
 int mi_op_gemv_uses_mfma(const mi_op_linear* w, const mi_op_gemv_args* a) {
   if (!w || !a) return 0;
   return gemv_mfma_supported(to_linear(w), to_call(a)) ? 1 : 0;

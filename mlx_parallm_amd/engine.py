@@ -155,6 +155,17 @@ class KVCache:
         L.check(L.lib().mi_kv_reset_row(self._h, int(row)))
         self._row_logprobs().pop(int(row), None)
 
+    def fork_row(self, src: int, dst: int, n_tokens: int) -> None:
+        """Row ``dst`` (empty: ``reset_row`` first) becomes a copy of the first ``n_tokens`` tokens of row ``src``
+        (``mi_kv_fork_row``): a paged cache shares the full blocks and copies the partly filled tail into a block of
+        ``dst``'s own, a contiguous one copies all of them.  ``offsets[dst]`` is ``n_tokens`` afterwards; the row's logit_bias
+        and logprobs setting are not forked.  ValueError (nothing changed): a bad row, ``src == dst``, a ``dst`` that is not
+        empty, ``n_tokens`` outside ``[1, offsets[src]]``; RuntimeError (nothing changed): no block for the tail."""
+        for name, v in (("src", src), ("dst", dst), ("n_tokens", n_tokens)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"fork_row: {name} {v!r} is not an int32")
+        L.check(L.lib().mi_kv_fork_row(self._h, int(src), int(dst), int(n_tokens)))
+
     def _row_logprobs(self) -> Dict[int, int]:
         """Host mirror of the rows with a logprobs setting (row -> count): tells ``Engine.step_wait`` which layout a step
         enqueued on this cache returns."""

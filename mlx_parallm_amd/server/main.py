@@ -97,6 +97,7 @@ class ServerConfig:
     chunk_tokens: int = 256
     kv_blocks: Optional[int] = None
     prefix_cache: bool = True
+    fork_choices: bool = False                    # the n choices of a request share one prompt prefill (KV rows are forked)
 
     @classmethod
     def from_env(cls, base: Optional["ServerConfig"] = None) -> "ServerConfig":
@@ -807,7 +808,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             state.scheduler = ReplicaPool([rec.model_instance] + state.extra_replicas, rec.tokenizer_instance,
                                           max_slots=config.max_batch_size, metrics=state.metrics,
                                           chunk_tokens=config.chunk_tokens, kv_blocks=config.kv_blocks,
-                                          prefix_cache=config.prefix_cache)
+                                          prefix_cache=config.prefix_cache, fork_choices=config.fork_choices)
             state.scheduler.start()
             state.tasks = []
         else:
@@ -971,12 +972,13 @@ def _request_controls(req: AnyRequest, tok: TokenizerWrapper) -> Tuple[Optional[
 
 
 def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyRequest, on_delta: Optional[Callable] = None,
-            choice: int = 0):
+            choice: int = 0, group=None):
     """Queue one sequence; -> (future resolving to (text, n_prompt, n_completion, finish_reason), n_prompt, sequence).
     ``sequence.cancel()`` frees its KV slot when the caller gives up (timeout, client disconnect).  A request with a
     ``seed`` gives choice i the stream of ``seed + i``; without one the sequence draws from the scheduler's stream.
     Every choice carries the request's ``logit_bias`` (set on its KV row) and ``stop`` list.  A completion that asks for
-    ``logprobs`` samples as ``logprobs_sampling`` says and its sequence collects the per-token lists."""
+    ``logprobs`` samples as ``logprobs_sampling`` says and its sequence collects the per-token lists.  ``group``: what the
+    choices of one request share (``scheduler.new_group()``), so that a scheduler with ``fork_choices`` prefills once."""
     loop = asyncio.get_running_loop()
     fut: asyncio.Future = loop.create_future()
     ids = _ids_of(tok, text)[0]
@@ -1001,7 +1003,8 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
         seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink, top_k=int(getattr(req, "top_k", 0) or 0),
                                      min_p=float(getattr(req, "min_p", 0.0) or 0.0),
                                      seed=None if seed is None else int(seed) + choice, logit_bias=bias, stop=stop,
-                                     **({"logprobs": lp_k, "logprobs_at_temperature": lp_at_t} if lp_k > 0 else {}))
+                                     **({"logprobs": lp_k, "logprobs_at_temperature": lp_at_t} if lp_k > 0 else {}),
+                                     **({"group": group} if group is not None else {}))
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return fut, len(ids), seq
@@ -1017,7 +1020,8 @@ async def _scheduled_response(state: ServerState, request: AnyRequest, tok: Toke
         text = prompt_text_of(request, tok)
     except Exception as e:
         raise HTTPException(status_code=500, detail=f"Error processing request: {e}")
-    subs = [_submit(state, tok, text, request, choice=i) for i in range(n)]
+    group = state.scheduler.new_group() if n > 1 else None     # one per request: its choices share the prompt
+    subs = [_submit(state, tok, text, request, choice=i, group=group) for i in range(n)]
     futs = [sub[0] for sub in subs]
     try:
         results = await asyncio.wait_for(asyncio.gather(*futs), timeout=state.config.request_timeout_seconds)

@@ -18,6 +18,10 @@ for -- a request does not wait for the running batch to finish -- and does it on
     at admission next to the bias (``KVCache.set_row_logprobs``) and cleared with the row; the sequence collects, per sampled
     token, the id, its logprob and its top list from the results of the shared steps, so such a request never takes the
     engine away from the others;
+  * with ``fork_choices`` the ``n`` choices of one request (``submit(..., group=new_group())``) share one prompt prefill: the
+    first member prefills, the others wait for it at the head of the queue and then get its row's first ``P - 1`` tokens
+    (``KVCache.fork_row``: full blocks shared, the tail copied) and run the last prompt token themselves -- ``P + (n - 1)``
+    prompt tokens instead of ``n * P``;
   * while the row set is stable the next step is enqueued before the current one is read back, sampled tokens
     stay on the device (the same one-step-ahead pipelining as generate_step, utils.py:420-427); when a sequence
     finishes or a request is waiting, the step already in flight completes, its tokens for finished rows are
@@ -128,12 +132,27 @@ def check_stop(stop) -> List[str]:
     return stop
 
 
+class Group:
+    """What the sequences of one request's ``n`` choices share (``new_group()``, ``submit(..., group=g)``): a scheduler with
+    ``fork_choices`` prefills their common prompt once and forks the KV row for the others."""
+    __slots__ = ("replica",)
+
+    def __init__(self):
+        self.replica = None            # ReplicaPool with fork_choices: the replica of the first member (a row is forked inside one cache)
+
+
+def new_group() -> Group:
+    return Group()
+
+
 class Sequence:
     _ids = itertools.count()
 
     def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok, *, top_k: int = 0,
                  min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
-                 stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False):
+                 stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False,
+                 group: Optional[Group] = None):
+        self.group = group
         if int(top_k) < 0:
             raise ValueError("top_k must be >= 0 (0 = off)")
         if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
@@ -176,7 +195,8 @@ class Sequence:
 class ContinuousScheduler:
     def __init__(self, model, tokenizer, max_slots: int = 8, kv_dtype: Optional[str] = None, capacity: int = 1024,
                  metrics=None, chunk_tokens: int = 256, paged: bool = True, block_tokens: int = 64,
-                 kv_blocks: Optional[int] = None, prefix_cache: bool = True, step_rows: int = 256):
+                 kv_blocks: Optional[int] = None, prefix_cache: bool = True, step_rows: int = 256,
+                 fork_choices: bool = False):
         from ..engine import SampleArgs      # noqa: F401  (fail early if the library is missing)
         from ..utils import DEFAULT_KV_DTYPE
 
@@ -196,6 +216,13 @@ class ContinuousScheduler:
             self.kv = eng.new_kv(self.max_slots, capacity=capacity, kv_dtype=kv_dtype or DEFAULT_KV_DTYPE)
         self.prefix_cache = bool(prefix_cache) and self.paged
         self.prefix_hit_tokens = 0
+        # the choices of one request (submit(..., group=)) share one prompt prefill: a member admitted while another one
+        # holds the prompt in its row gets that row's first P - 1 tokens (KVCache.fork_row) and runs the last prompt token
+        # itself, so every choice samples its first token from its own stream.  Off by default: the forked member's last
+        # prompt token goes through the decode-shaped path, not through a prefill of its own.
+        self.fork_choices = bool(fork_choices) and hasattr(self.kv, "fork_row")
+        self.forks = 0                     # rows forked from a group member instead of prefilled
+        self.fork_tokens = 0               # prompt tokens they did not have to run
         self.slots: List[Optional[Sequence]] = [None] * self.max_slots
         self.pending: Deque[Sequence] = collections.deque()
         self.cv = threading.Condition()
@@ -259,10 +286,11 @@ class ContinuousScheduler:
     # ------------------------------------------------------------------ client side (any thread)
     def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, *, top_k: int = 0,
                min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
-               stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False) -> Sequence:
+               stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False,
+               group: Optional[Group] = None) -> Sequence:
         seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer),
                        top_k=top_k, min_p=min_p, seed=seed, logit_bias=logit_bias, stop=stop, logprobs=logprobs,
-                       logprobs_at_temperature=logprobs_at_temperature)
+                       logprobs_at_temperature=logprobs_at_temperature, group=group)
         if (seq.logprobs or seq.logprobs_at_temperature) and not hasattr(self.kv, "set_row_logprobs"):
             raise ValueError("logprobs: this KV cache has no per-row logprobs setting (set_row_logprobs)")
         if seq.logit_bias:
@@ -400,6 +428,27 @@ class ContinuousScheduler:
             s.sample_steps += 1
         return sp
 
+    def new_group(self) -> Group:
+        return new_group()
+
+    def _group_live(self, seq: Sequence) -> List[Sequence]:
+        """The members of ``seq``'s group that hold a row and are still running, with the same prompt."""
+        if not self.fork_choices or seq.group is None or len(seq.prompt) < 2:
+            return []
+        return [s for s in self.slots if s is not None and s is not seq and s.group is seq.group and not s.finished
+                and not s.cancelled and np.array_equal(s.prompt, seq.prompt)]
+
+    def _fork_donor(self, seq: Sequence) -> Optional[Sequence]:
+        """A live member whose row already holds the first P - 1 prompt tokens (it may be decoding by now)."""
+        need = len(seq.prompt) - 1
+        return next((s for s in self._group_live(seq) if s.prefill_pos >= need), None)
+
+    def _waits_for_donor(self, seq: Sequence) -> bool:
+        """A member is still prefilling the prompt: ``seq`` stays at the head of ``pending`` until it is through (a donor that
+        is cancelled or finishes meanwhile is no longer live, and ``seq`` is admitted the normal way)."""
+        live = self._group_live(seq)
+        return bool(live) and self._fork_donor(seq) is None
+
     def _admit(self, seq: Sequence, slot: int) -> None:
         eng = self.model.engine
         seq.slot = slot
@@ -413,7 +462,19 @@ class ContinuousScheduler:
         if seq.logprobs or seq.logprobs_at_temperature:
             self.kv.set_row_logprobs(slot, seq.logprobs, seq.logprobs_at_temperature)
         seq.prefill_pos = 0
-        if self.prefix_cache:                     # full blocks of an earlier prompt with the same prefix are mapped, not recomputed
+        donor = self._fork_donor(seq)
+        if donor is not None:                     # a sibling's row holds the prompt: its first P - 1 tokens, the last one runs here
+            try:
+                self.kv.fork_row(donor.slot, slot, len(seq.prompt) - 1)
+                seq.prefill_pos = len(seq.prompt) - 1
+                self.forks += 1
+                self.fork_tokens += seq.prefill_pos
+            except RuntimeError as e:             # no block for the tail, nothing has changed: the prompt runs as any other
+                if "no block for the tail" not in str(e):
+                    raise                         # (a failed launch is the step's failure, not an arena shortage)
+                log.warning("sequence %d: fork_row found no block, prefilling the prompt", seq.id)
+                donor = None
+        if donor is None and self.prefix_cache:   # full blocks of an earlier prompt with the same prefix are mapped, not recomputed
             seq.prefill_pos = self.kv.prefix_attach(slot, seq.prompt)
             self.prefix_hit_tokens += seq.prefill_pos
         if self.chunk_tokens > 0:                 # the prompt enters the cache chunk by chunk, inside the decode steps
@@ -536,7 +597,9 @@ class ContinuousScheduler:
                         with self.cv:
                             free = [i for i, s in enumerate(self.slots) if s is None]
                             seq = self.pending[0] if (free and self.pending) else None
-                            if seq is not None and not self._fits(seq):
+                            if seq is not None and self._waits_for_donor(seq):
+                                seq = None                   # wait for the sibling's prefill: its row is forked then
+                            elif seq is not None and not self._fits(seq):
                                 if any(s is not None and not s.finished for s in self.slots):
                                     seq = None               # wait for blocks: a live sequence will give some back
                                 else:
@@ -638,8 +701,25 @@ class ReplicaPool:
 
     def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, **controls) -> Sequence:
         with self._lock:                      # (choice and enqueue together, so concurrent submits spread out)
-            r = min(self.replicas, key=self._load)
+            group = controls.get("group")
+            if group is not None and group.replica is not None:
+                r = group.replica             # the members of a group share one cache: where the first one went
+            else:
+                r = min(self.replicas, key=self._load)
+                if group is not None and r.fork_choices:      # (a replica that does not fork: its members spread as ever)
+                    group.replica = r
             return r.submit(prompt_ids, max_tokens, temp, top_p, sink, **controls)
+
+    def new_group(self) -> Group:
+        return new_group()
+
+    @property
+    def forks(self) -> int:
+        return sum(r.forks for r in self.replicas)
+
+    @property
+    def fork_tokens(self) -> int:
+        return sum(r.fork_tokens for r in self.replicas)
 
     def start(self) -> None:
         for r in self.replicas:
