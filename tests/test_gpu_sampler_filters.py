@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import sampler_filters_ref as sfr
+from sampler_filters_ref import _nucleus_cut_slack, _sampler_edge_bound
 from oracle import ref_sample
 from oracle.numerics import round_to
 
@@ -18,6 +19,9 @@ from gpu_helpers import dev, dev_i32, ptr  # noqa: E402
 B = 8
 U_LAST = 1.0 - 2.0 ** -24                  # the largest float32 below 1: the draw that must land on the last kept candidate
 VS = [37, 5000, 32000, 151936]             # 37: the scalar path (V % 4 != 0); 32000: bf16-rounded, big tie groups; 151936: largest
+# either side of the tie table's capacity (64 chunks of 1024 lanes): 65535 (scalar walk) and 262144 (vector walk) fill it exactly,
+# 65537 and 262148 need a 65th chunk and take the rank loop
+EDGE_VS = [65535, 65537, 262144, 262148]
 
 
 def _dev_i64(a, dtype):
@@ -62,43 +66,6 @@ def masked(row, top_k):
     if 0 < top_k < len(out):
         out[sfr.oracle_order(out)[top_k:]] = -np.inf
     return out
-
-
-# ---- the two derived bounds of tests/test_gpu_kernels.py, copied: test modules do not import each other
-def _nucleus_cut_slack(lg_row, temp, top_p, n):
-    """The nucleus itself is cut at top_p * Z: if the full distribution's cumulative at the cut lies within the same
-    arithmetic's worst-case error (+ the float32 top_p) of top_p, the device may keep one candidate more or fewer, which
-    renormalises every edge by that candidate's share.  -> that share (0.0 when the cut is not that close)."""
-    if top_p >= 1.0:
-        return 0.0
-    with np.errstate(divide="ignore", invalid="ignore"):
-        xs = lg_row.astype(np.float64) / float(temp)
-        pf = np.exp(xs - xs.max())
-    order = np.lexsort((np.arange(len(pf)), -pf))
-    pf = pf[order] / pf.sum()
-    cf = np.cumsum(pf)
-    ef = (5.5 * np.abs(np.log(np.maximum(pf / pf[0], 1e-300))) + 2.0) * 2.0 ** -24
-    slack = float(np.sum(pf * ef)) + abs(float(np.float32(top_p)) - top_p) + (len(pf) + 1) * 2.0 ** -40
-    near = [k for k in (n - 2, n - 1) if 0 <= k < len(cf) and abs(cf[k] - top_p) <= slack]
-    if not near:
-        return 0.0
-    return float(pf[min(n, len(pf) - 1)] / cf[n - 1]) + float(pf[n - 1] / cf[n - 1])
-
-
-def _sampler_edge_bound(lg_row, temp, top_p, ids, pr, j, u):
-    """How far the device's boundary between candidates j and j + 1 may lie from the oracle's cumulative c_j: relative mass
-    error eps_i = (5.5 |a_i| + 2) 2^-24 of candidate i (a_i = (l_i - max) / T in nats), the worst case of those errors on
-    either side of the edge, one 2^-40 unit per candidate and for u * Z, half an ulp of the float32 u, and the share of a
-    nucleus cut that is itself ambiguous."""
-    x = lg_row.astype(np.float64)
-    a = np.abs((x[ids] - x.max()) / float(temp))
-    p = np.asarray(pr, np.float64) / np.sum(pr)
-    eps = (5.5 * a + 2.0) * 2.0 ** -24
-    c = float(np.cumsum(p)[j])
-    below, above = float(np.sum((p * eps)[: j + 1])), float(np.sum((p * eps)[j + 1:]))
-    mass = ((1.0 - c) * below + c * above) / (1.0 - below - above)
-    bound = mass + (len(ids) + 1) * 2.0 ** -40 + 0.5 * float(np.spacing(np.float32(u)))
-    return bound + _nucleus_cut_slack(lg_row, temp, top_p, len(ids))
 
 
 def _min_p_ambiguous(row, temp, min_p):
@@ -189,7 +156,7 @@ def test_top_k_matches_the_reference(V):
 
 
 # ---- 3. top-k, then the nucleus over the survivors (cut against top_p * Z_k)
-@pytest.mark.parametrize("V", VS)
+@pytest.mark.parametrize("V", VS + EDGE_VS)
 @pytest.mark.parametrize("k,top_p,temp", [(50, 0.9, 0.7), (5, 0.3, 1.0)])
 def test_top_k_then_top_p(V, k, top_p, temp):
     rng = np.random.default_rng(300 + V + k)
@@ -282,7 +249,7 @@ def test_one_seed_gives_a_uniform_stream_over_positions():
 
 
 # ---- 7. defaults: everything off is mi_op_sample, bit for bit
-@pytest.mark.parametrize("V", VS)
+@pytest.mark.parametrize("V", VS + EDGE_VS)
 def test_everything_off_is_bit_identical_to_mi_op_sample(V):
     rng = np.random.default_rng(700 + V)
     lg = make_rows(V, rng)

@@ -18,6 +18,13 @@ FLAGS = [1, 0, 1, 0, 0]                               # rows 0 and 2 report unde
 ROW_MAP = [4, 0, 6, 3, 2]                             # sampled row -> table row: neither the identity nor monotone
 VS = [5, 33, 1000, 32000, 151936]                     # k > V; V % 4 != 0 (the scalar walks); V below one pass of 1024 threads
 KINDS = ["gaussian", "ints", "equal", "special", "bf16"]
+# The widths on either side of the tie table's capacity (TIE_TBL = 1024 entries of one (chunk of 1024 lanes, wave) each, i.e. 64
+# chunks): 65535 ids in the scalar walk and 262144 in the vector walk fill it exactly; 65537 and 262148 need a 65th chunk, so the
+# selection declines and the rounds answer.  gaussian and bf16 only: ints / equal make tie groups of tens of thousands of ids
+# there, which the sampler's rank loop beyond the table walks once per tie rank.
+EDGE_VS = [65535, 65537, 262144, 262148]
+EDGE_KINDS = ["gaussian", "bf16"]
+CASES = [(V, kind) for V in VS for kind in KINDS] + [(V, kind) for V in EDGE_VS for kind in EDGE_KINDS]
 TEMPS = [0.0, 0.7, 1.0]
 
 
@@ -91,7 +98,7 @@ def table(ks=KS, flags=FLAGS):
     return k, f, n
 
 
-@pytest.fixture(scope="module", params=[(V, kind) for V in VS for kind in KINDS], ids=lambda p: f"V{p[0]}-{p[1]}")
+@pytest.fixture(scope="module", params=CASES, ids=lambda p: f"V{p[0]}-{p[1]}")
 def case(request):
     """The rows of one (V, kind) and, per temperature, the yardstick outputs for every (k, flag) the settings use."""
     V, kind = request.param
