@@ -17,9 +17,7 @@
 //     silu(gate) * up happens in registers.
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
-
-#include "kernels.h"
+#include "linear_epilogue.h"
 
 namespace mi {
 
@@ -27,21 +25,8 @@ int gemv_cu_count();      // gemv_mfma.hip
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int LDA = 72;   // LDS row stride in elements (144 B)
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<T, bf16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 struct GemmParams {
   const void* x; int ldx; int M;
@@ -62,22 +47,21 @@ struct GemmParams {
   const float* bias; int bias2;
 };
 
-// T(acc) of the 16-bit epilogues, with the bias when the matrix has one
-template <typename AT>
+// T(acc) of column n, with the bias when the matrix has one (T = float: the float32-storage epilogues, no rounding)
+template <typename T>
 __device__ __forceinline__ float round_biased(const GemmParams& p, int n, float acc) {
-  if (p.bias != nullptr) return add_bias<AT>(acc, p.bias[n], p.bias2 != 0, RND_NONE);
-  return (float)(AT)acc;
+  return linear_value<T>(acc, p.bias != nullptr, p.bias, n, p.bias2, RND_NONE);
+}
+// out[m][n] = the SwiGLU of the gate / up accumulators of column n, in storage type T
+template <typename T>
+__device__ __forceinline__ void epi_swiglu(const GemmParams& p, int m, int n, float gacc, float uacc) {
+  const float gt = round_biased<T>(p, n, gacc), up = round_biased<T>(p, n + p.pair_offset, uacc);
+  ((T*)p.out)[(size_t)m * p.ldo + n] = (T)swiglu_value<T>(gt, up, RND_NONE);
 }
 
-// the epilogues in float32 storage (PagedKVCache mode after layer 0: every op produces a float32 array)
-__device__ __forceinline__ void epi32_swiglu(const GemmParams& p, int m, int n, float gt, float up) {
-  if (p.bias != nullptr) { gt = add_bias<float>(gt, p.bias[n], false, RND_NONE); up = add_bias<float>(up, p.bias[n + p.pair_offset], false, RND_NONE); }
-  const float sig = 1.0f / (1.0f + expf(-gt));
-  const float sl = gt * sig;
-  ((float*)p.out)[(size_t)m * p.ldo + n] = sl * up;
-}
+// the plain epilogue in float32 storage (PagedKVCache mode after layer 0: every op produces a float32 array)
 __device__ __forceinline__ void epi32_plain(const GemmParams& p, int m, int n, float y) {
-  if (p.bias != nullptr) y = add_bias<float>(y, p.bias[n], false, RND_NONE);
+  y = round_biased<float>(p, n, y);
   if (p.epi == EPI_STORE) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
   else { float* h = (float*)p.resid; h[(size_t)m * p.ldo + n] = h[(size_t)m * p.ldo + n] + y; }
 }
@@ -214,11 +198,8 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmParams p) {
         for (int j = 0; j < 2; ++j) {
           const int n = bn * 64 + wn * 32 + j * 16 + c16;
           if (n >= p.pair_offset) continue;
-          if (p.out32) { epi32_swiglu(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]); continue; }
-          const float gt = round_biased<AT>(p, n, acc[mt][j][r]), up = round_biased<AT>(p, n + p.pair_offset, acc[mt][j + 2][r]);
-          const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-          const float sl = (float)(AT)(gt * sig);
-          out[(size_t)m * p.ldo + n] = (AT)(sl * up);
+          if (p.out32) epi_swiglu<float>(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]);
+          else epi_swiglu<AT>(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]);
         }
       } else {
 #pragma unroll
@@ -274,11 +255,8 @@ __device__ __forceinline__ void tile256_epilogue(const GemmParams& p, f32x4 (&ac
         for (int j = 0; j < 2; ++j) {
           const int n = bn * 128 + wn * 32 + j * 16 + c16;
           if (n >= p.pair_offset) continue;
-          if (p.out32) { epi32_swiglu(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]); continue; }
-          const float gt = round_biased<AT>(p, n, acc[mt][j][r]), up = round_biased<AT>(p, n + p.pair_offset, acc[mt][j + 2][r]);
-          const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-          const float sl = (float)(AT)(gt * sig);
-          out[(size_t)m * p.ldo + n] = (AT)(sl * up);
+          if (p.out32) epi_swiglu<float>(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]);
+          else epi_swiglu<AT>(p, m, n, acc[mt][j][r], acc[mt][j + 2][r]);
         }
       } else {
 #pragma unroll
@@ -323,7 +301,7 @@ __device__ __forceinline__ void tile256_epilogue_resid(const GemmParams& p, f32x
         const int n = bn * BN2 + wn * 64 + nt * 16 + c16;
         if (m >= p.M || n >= p.N) continue;
         if constexpr (std::is_same<HT, float>::value) {
-          const float y = p.bias != nullptr ? add_bias<float>(acc[mt][nt][r], p.bias[n], false, RND_NONE) : acc[mt][nt][r];
+          const float y = round_biased<float>(p, n, acc[mt][nt][r]);
           h[(size_t)m * p.ldo + n] = hv[r][nt] + y;
         } else h[(size_t)m * p.ldo + n] = (AT)((float)hv[r][nt] + round_biased<AT>(p, n, acc[mt][nt][r]));
       }

@@ -49,10 +49,7 @@ struct Q4Params {
   int ksplit;         // K slices over workgroups
   int nslab, nunits;  // row slabs of 16 MT rows; units = tile groups x ksplit
   float* ws; unsigned* ctr;
-  const float* lora_t; int lora_t_ld;
-  const float* lora_b0; const float* lora_b1;
-  int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
-  int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
+  EpiTerms e;         // the LoRA ranges (linear_epilogue.h); the bias members stay null: gemm_q4_supported refuses a biased linear
 };
 
 // ---- x -> fragment-major nibble order + group sums (+ RMSNorm).  One 256-thread workgroup per row (rows padded to 16 Mt:
@@ -449,10 +446,8 @@ __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) 
       for (int r = 0; r < 4; ++r) {
         const int m = row0 + mt * 16 + g * 4 + r;
         if (m >= p.M) continue;
-        const float gt = (float)(AT)acc[0][mt][r], up = (float)(AT)acc[1][mt][r];
-        const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-        const float sl = (float)(AT)(gt * sig);
-        out[(size_t)m * p.ldo + n] = (AT)(sl * up);
+        const float gt = rounded<AT>(acc[0][mt][r], RND_NONE), up = rounded<AT>(acc[1][mt][r], RND_NONE);
+        out[(size_t)m * p.ldo + n] = (AT)swiglu_value<AT>(gt, up, RND_NONE);
       }
     return;
   }
@@ -476,22 +471,7 @@ __global__ __launch_bounds__(Q4_NWMAX * 64, 3) void q4_kernel(const Q4Params p) 
       for (int r = 0; r < 4; ++r) {
         const int m = row0 + mt * 16 + g * 4 + r;
         if (m >= p.M) continue;
-        float y = (float)(AT)acc[a][mt][r];
-        if (p.lora_t != nullptr) {
-#pragma unroll
-          for (int sl = 0; sl < 2; ++sl) {
-            const int r0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-            const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-            const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-            const float* lb = sl ? p.lora_b1 : p.lora_b0;
-            if (lb != nullptr && n >= r0 && n < r0 + ln) {
-              const float* tt = p.lora_t + (size_t)m * p.lora_t_ld + sl * (p.lora_t_ld / 2);
-              float z = lora_dot(tt, lb + (n - r0), ln, rk);
-              z = (sl ? p.lora_scale_1 : p.lora_scale_0) * z;
-              y = (float)(AT)(y + (float)(AT)z);
-            }
-          }
-        }
+        const float y = lora_term<AT>(rounded<AT>(acc[a][mt][r], RND_NONE), p.e, m, n, RND_NONE, RND_NONE);
         if (p.epi == EPI_STORE) out[(size_t)m * p.ldo + n] = (AT)y;
         else if (p.epi == EPI_STORE_F32) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
         else ((AT*)p.resid)[(size_t)m * p.ldo + n] = (AT)(hres[mt * 4 + r] + y);
@@ -662,10 +642,7 @@ int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t
   p.ntu = pl.ntu; p.ntiles = pl.ntiles; p.TW = pl.TW; p.KW = pl.KW; p.NS = pl.NS; p.nblk = pl.nblk; p.ksplit = pl.ksplit;
   p.nslab = pl.nslab; p.nunits = pl.ngroups * pl.ksplit;
   p.ws = (float*)((char*)ws + pl.prep_bytes); p.ctr = ctr;
-  p.lora_t = c.lora_t; p.lora_t_ld = c.lora_t_ld;
-  p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
-  p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
-  p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
+  p.e = epi_terms(W, c);
   const size_t lds = 2 * (size_t)(pl.KW * 4 * pl.mt + 2) * 1024;
   const int nthreads = (pl.TW * pl.KW + pl.NS) * 64;
   const int grid = pl.nslab > 1 ? (p.nunits + 7) / 8 * 8 * pl.nslab : p.nunits;

@@ -97,11 +97,7 @@ struct SkinnyParams {
   unsigned* ctr;     // [tile groups] arrival counters, zero between launches
   // consumer_combine (the CC instantiation below only):
   float* pub; float* pub_sq;       // publish-only producer: partial tiles row-major [ksplit][8][N], the slices' row sums of squares [ksplit][8]
-  const float* lora_t; int lora_t_ld;
-  const float* lora_b0; const float* lora_b1;
-  int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
-  int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
-  const float* bias; int bias2;     // LinearW::bias, added where the K slices are combined (once); bias2 = quantised weights
+  EpiTerms e;                      // LoRA ranges and bias (linear_epilogue.h), applied where the K slices are combined (once)
 #ifdef MI_SK_TRACE
   unsigned long long* trace;       // debug build: [workgroup][8] wall-clock stamps of this launch (tools/debug/skinny_trace.py)
 #endif
@@ -390,13 +386,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
           }
         }
 #pragma unroll
-        for (int a = 0; a < NA; ++a) {
-          const f32x4 d = dq[a];
-          acc[a][mt].x = fmaf(sc[a], d.x, fmaf(bb[a], sxv.x, acc[a][mt].x));
-          acc[a][mt].y = fmaf(sc[a], d.y, fmaf(bb[a], sxv.y, acc[a][mt].y));
-          acc[a][mt].z = fmaf(sc[a], d.z, fmaf(bb[a], sxv.z, acc[a][mt].z));
-          acc[a][mt].w = fmaf(sc[a], d.w, fmaf(bb[a], sxv.w, acc[a][mt].w));
-        }
+        for (int a = 0; a < NA; ++a) quant_accumulate(acc[a][mt], sc[a], bb[a], dq[a], sxv);
       }
     } else if constexpr (!Q4) {
 #pragma unroll
@@ -456,10 +446,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
             f32x4 d = {0.f, 0.f, 0.f, 0.f};
             d = mfma16<AT>(c0, wq[a][0], d);
             d = mfma16<AT>(c1, wq[a][1], d);
-            acc[a][mt].x = fmaf(sc[a], d.x, fmaf(bb[a], csx.x, acc[a][mt].x));
-            acc[a][mt].y = fmaf(sc[a], d.y, fmaf(bb[a], csx.y, acc[a][mt].y));
-            acc[a][mt].z = fmaf(sc[a], d.z, fmaf(bb[a], csx.z, acc[a][mt].z));
-            acc[a][mt].w = fmaf(sc[a], d.w, fmaf(bb[a], csx.w, acc[a][mt].w));
+            quant_accumulate(acc[a][mt], sc[a], bb[a], d, csx);
           }
           c0 = n0; c1 = n1; csx = nsx;
           __builtin_amdgcn_sched_barrier(0);
@@ -494,13 +481,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
             }
           }
 #pragma unroll
-          for (int a = 0; a < NA; ++a) {
-            const f32x4 d = dq[a];
-            acc[a][mt].x = fmaf(sc[a], d.x, fmaf(bb[a], sxv.x, acc[a][mt].x));
-            acc[a][mt].y = fmaf(sc[a], d.y, fmaf(bb[a], sxv.y, acc[a][mt].y));
-            acc[a][mt].z = fmaf(sc[a], d.z, fmaf(bb[a], sxv.z, acc[a][mt].z));
-            acc[a][mt].w = fmaf(sc[a], d.w, fmaf(bb[a], sxv.w, acc[a][mt].w));
-          }
+          for (int a = 0; a < NA; ++a) quant_accumulate(acc[a][mt], sc[a], bb[a], dq[a], sxv);
         }
       }
       }
@@ -734,7 +715,7 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
 
   // ================= epilogue: lane (c16, g) holds y[16 mt + 4 g + r][16 tile + c16]
   const int n = tile * 16 + c16;
-  AT* out = (AT*)p.out;
+  XT* out = (XT*)p.out;
   float hsq[NH ? MT * 4 : 1];
 #pragma unroll
   for (int i = 0; i < (NH ? MT * 4 : 1); ++i) hsq[i] = 0.f;
@@ -760,88 +741,33 @@ __global__ __launch_bounds__(SK_NW * 64, (QB == 4 || (QB == 8 && MT >= 3) || MT 
       const int ml = mt * 16 + g * 4 + r;
       if (ml >= Mloc || !valid) continue;
       const int m = row0 + ml;                   // the row in the caller's arrays
-      float y0 = acc[0][mt][r];
-      if constexpr (X32) {                        // float32 storage, run-time logical rounding (gemv_v1.hip's epilogue)
-        float* o32 = (float*)p.out;
+      // XT is the storage type: AT, or float32 with the run-time logical rounding p.rnd (X32), whose deferred RMSNorm puts
+      // the row scale in front of everything else (y = rs * acc + b: the row scale first)
+      float y0 = acc[0][mt][r], y1 = acc[NA - 1][mt][r];
+      if constexpr (X32) {
         const float rsm = dn ? rs_row[ml] : 1.0f;
-        y0 = scale_row(y0, rsm);
-        if constexpr (SWIGLU) {
-          float gt = round_rt(y0, p.rnd), up = round_rt(acc[NA - 1][mt][r] * rsm, p.rnd);
-          if constexpr (BIAS) {                  // y = rs * acc + b: the row scale first
-            gt = add_bias<float>(y0, p.bias[n], p.bias2 != 0, p.rnd);
-            up = add_bias<float>(scale_row(acc[NA - 1][mt][r], rsm), p.bias[n + p.pair_offset], p.bias2 != 0, p.rnd);
-          }
-          const float sig = round_rt(1.0f / (1.0f + expf(-gt)), p.rnd);
-          const float sl = round_rt(gt * sig, p.rnd);
-          o32[(size_t)m * p.ldo + n] = round_rt(sl * up, p.rnd);
-        } else {
-          float y = round_rt(y0, p.rnd);
-          if constexpr (BIAS) y = add_bias<float>(y0, p.bias[n], p.bias2 != 0, p.rnd);
-          if (p.lora_t != nullptr) {             // LoRALinear in this mode: y + T(scale (x A) B), the term in float32 (App. A.6)
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-              const int r0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-              const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-              const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-              const float* lb = sl ? p.lora_b1 : p.lora_b0;
-              if (lb != nullptr && n >= r0 && n < r0 + ln) {
-                const float* tt = p.lora_t + (size_t)m * p.lora_t_ld + sl * (p.lora_t_ld / 2);
-                float z = lora_dot(tt, lb + (n - r0), ln, rk);
-                z = round_rt((sl ? p.lora_scale_1 : p.lora_scale_0) * z, p.rnd);
-                y = round_rt(y + z, p.rnd);
-              }
-            }
-          }
-          if (p.epi == EPI_RESID) {
-            float* h = (float*)p.resid;
-            float hv;
-            if constexpr (HPRE) hv = hpre[mt * 4 + r];
-            else if constexpr (HLATE) hv = hlate[mt * 4 + r];
-            else hv = h[(size_t)m * p.ldo + n];
-            h[(size_t)m * p.ldo + n] = round_rt(hv + y, p.rnd);
-          } else {
-            o32[(size_t)m * p.ldo + n] = y;     // EPI_STORE and EPI_STORE_F32 coincide
-          }
-        }
-        continue;
+        y0 = scale_row(y0, rsm); y1 = scale_row(y1, rsm);
       }
+      const size_t o = (size_t)m * p.ldo + n;
       if constexpr (SWIGLU) {
-        float gt = (float)(AT)y0, up = (float)(AT)acc[NA - 1][mt][r];
-        if constexpr (BIAS) {
-          gt = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
-          up = add_bias<AT>(acc[NA - 1][mt][r], p.bias[n + p.pair_offset], p.bias2 != 0, RND_NONE);
-        }
-        const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-        const float sl = (float)(AT)(gt * sig);
-        out[(size_t)m * p.ldo + n] = (AT)(sl * up);
+        const float gt = linear_value<XT>(y0, BIAS, p.e.bias, n, p.e.bias2, p.rnd);
+        const float up = linear_value<XT>(y1, BIAS, p.e.bias, n + p.pair_offset, p.e.bias2, p.rnd);
+        out[o] = from_f32<XT>(swiglu_value<XT>(gt, up, p.rnd));
       } else {
-        float y = (float)(AT)y0;
-        if constexpr (BIAS) y = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
-        if (p.lora_t != nullptr) {
-#pragma unroll
-          for (int sl = 0; sl < 2; ++sl) {
-            const int r0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-            const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-            const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-            const float* lb = sl ? p.lora_b1 : p.lora_b0;
-            if (lb != nullptr && n >= r0 && n < r0 + ln) {
-              const float* tt = p.lora_t + (size_t)m * p.lora_t_ld + sl * (p.lora_t_ld / 2);
-              float z = lora_dot(tt, lb + (n - r0), ln, rk);
-              z = (sl ? p.lora_scale_1 : p.lora_scale_0) * z;
-              y = (float)(AT)(y + (float)(AT)z);
-            }
-          }
-        }
-        if (p.epi == EPI_STORE) out[(size_t)m * p.ldo + n] = (AT)y;
-        else if (p.epi == EPI_STORE_F32) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
-        else {
-          AT* h = (AT*)p.resid;
+        float y = linear_value<XT>(y0, BIAS, p.e.bias, n, p.e.bias2, p.rnd);
+        y = lora_term<XT>(y, p.e, m, n, p.rnd, RND_NONE);
+        if (p.epi == EPI_STORE || (X32 && p.epi == EPI_STORE_F32)) {      // (float32 storage: the two coincide)
+          out[o] = from_f32<XT>(y);
+        } else if (p.epi == EPI_STORE_F32) {
+          ((float*)p.out)[o] = y;
+        } else {  // EPI_RESID
+          XT* h = (XT*)p.resid;
           float h0;
           if constexpr (HPRE) h0 = hpre[mt * 4 + r];
           else if constexpr (HLATE) h0 = hlate[mt * 4 + r];
-          else h0 = (float)h[(size_t)m * p.ldo + n];
-          const AT hv = (AT)(h0 + y);
-          h[(size_t)m * p.ldo + n] = hv;
+          else h0 = to_f32(h[o]);
+          const XT hv = store_act<XT>(h0 + y, p.rnd);
+          h[o] = hv;
           if constexpr (NH) hsq[mt * 4 + r] = (float)hv * (float)hv;
         }
       }
@@ -1095,11 +1021,7 @@ int launch_gemm_skinny(const LinearW& W, const GemvCall& c, size_t rows, hipStre
   p.ws = (float*)ws; p.ctr = ctr;
   p.defer_norm = defer_norm ? 1 : 0;
   p.sqws = (defer_norm && pl.ksplit > 1) ? (float*)((char*)ws + (size_t)pl.ksplit * pl.ntiles * pl.na * pl.mt * 1024) : nullptr;
-  p.lora_t = c.lora_t; p.lora_t_ld = c.lora_t_ld;
-  p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
-  p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
-  p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
-  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
+  p.e = epi_terms(W, c);
   const int qb = (W.wk == WK_Q8_BF16 || W.wk == WK_Q8_F16) ? 8 : wk_is_quant(W.wk) ? 4 : 0;
   const bool sw = c.epi == EPI_SWIGLU;
   const int grid = pl.nslab > 1 ? (pl.ngroups * pl.ksplit + 7) / 8 * 8 * pl.nslab : pl.ngroups * pl.ksplit;

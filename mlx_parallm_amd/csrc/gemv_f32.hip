@@ -331,9 +331,7 @@ struct F32Body {
     y0 *= rs; y1 *= rs;
     if constexpr (GU8) {
       // row-interleaved gate|up tile: columns 0..7 are gate rows 8 tile .. + 7, columns 8..15 the matching up rows
-      const float sig = 1.0f / (1.0f + expf(-y0));
-      const float sl = y0 * sig;
-      p.out[(size_t)m * p.ldo + tile * 8 + cc] = sl * y1;
+      p.out[(size_t)m * p.ldo + tile * 8 + cc] = swiglu_value<float>(y0, y1, RND_NONE);
     } else {
       const size_t o = out_ofs(m, p.ldo, tile, cc);
       if (p.epi == EPI_RESID) {

@@ -84,7 +84,7 @@ int launch_j(const MfmaParams& p, hipStream_t st) {
   if constexpr (!Q4 && !SWIGLU) {
     if (p.epi == EPI_SWIGLU_GU8) kern = gemv_mfma_gu8_kernel<AT, MB, NW, J, DB>;
   }
-  if (p.bias != nullptr) kern = gemv_mfma_bias_kernel<AT, Q4, MB, SWIGLU, NW, J, DB>;     // (never with EPI_SWIGLU_GU8: launch_gemv_mfma)
+  if (p.e.bias != nullptr) kern = gemv_mfma_bias_kernel<AT, Q4, MB, SWIGLU, NW, J, DB>;     // (never with EPI_SWIGLU_GU8: launch_gemv_mfma)
   constexpr int NA = SWIGLU ? 2 : 1;
   const size_t lds = phase_lds_bytes<NW, NA, Q4>(p.kc, MB, DB ? 2 : 1);
   MI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -144,11 +144,7 @@ MfmaParams make_params(const LinearW& W, const GemvCall& c) {
   const int kc_max = c.M <= 8 ? 6144 : 4096;
   p.kc = (W.K <= kc_max) ? W.K : 4096;
   p.layout = W.layout;
-  p.lora_t = c.lora_t; p.lora_t_ld = c.lora_t_ld;
-  p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
-  p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
-  p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
-  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
+  p.e = epi_terms(W, c);
   return p;
 }
 

@@ -3,15 +3,10 @@
 #pragma once
 #include <type_traits>
 
-#include "kernels.h"
+#include "linear_epilogue.h"
 
 namespace mi {
 namespace gemv {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct MfmaParams {
   const void* x; int ldx; int M;
@@ -21,11 +16,7 @@ struct MfmaParams {
   int epi; void* out; int ldo; void* resid; int pair_offset;
   int layout;       // always 1 here: tile-major (16 rows x 32 k blocks of 1 KiB, repack.hip)
   int kc;       // K elements staged in LDS per chunk
-  const float* lora_t; int lora_t_ld;
-  const float* lora_b0; const float* lora_b1;
-  int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
-  int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
-  const float* bias; int bias2;     // LinearW::bias; bias2 = quantised weights (two roundings)
+  EpiTerms e;   // LoRA ranges and bias (linear_epilogue.h)
 #ifdef MI_SK_TRACE
   unsigned long long* trace;       // debug build (tools/debug/build_trace_lib.sh): [workgroup][16] wall-clock stamps
 #endif
@@ -38,15 +29,6 @@ struct MfmaParams {
 #define PH_STAMP(i) do { } while (0)
 #define PH_STAMP_WAVE(i) do { } while (0)
 #endif
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<T, bf16>::value) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-}
 
 // int4 code pairs -> 16-bit floats.
 //   bf16: (16 + q) = 2^4 * (1 + q/16): exponent 0x4180, q in mantissa bits 3..6 -- two VALU ops per
@@ -359,10 +341,7 @@ struct Phase {
             d = mfma16<AT>(af[s][1], unpack_q4<AT>(dw[s * 2 + 1]), d);
             // y += scale * sum((OFFS+q) x) + (bias - OFFS*scale) * sum(x)   per output row m
             const float sc = (float)sp[s], bb = (float)bp[s] - Magic<AT>::offs * sc;
-            acc[a][t].x = fmaf(sc, d.x, fmaf(bb, sxv[s].x, acc[a][t].x));
-            acc[a][t].y = fmaf(sc, d.y, fmaf(bb, sxv[s].y, acc[a][t].y));
-            acc[a][t].z = fmaf(sc, d.z, fmaf(bb, sxv[s].z, acc[a][t].z));
-            acc[a][t].w = fmaf(sc, d.w, fmaf(bb, sxv[s].w, acc[a][t].w));
+            quant_accumulate(acc[a][t], sc, bb, d, sxv[s]);
           }
         }
     }
@@ -389,44 +368,22 @@ struct Phase {
         }
         if (m < p.M) {
           AT* out = (AT*)p.out;
-          if constexpr (SWIGLU) {
-            float gt = (float)(AT)y0, up = (float)(AT)y1;
-            if constexpr (BIAS) {                  // gate and up each get their own bias in front of silu(g) * u
-              gt = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);
-              up = add_bias<AT>(y1, p.bias[n + p.pair_offset], p.bias2 != 0, RND_NONE);
-            }
-            const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-            const float sl = (float)(AT)(gt * sig);
-            store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)(sl * up));
+          if constexpr (SWIGLU) {                  // gate and up each get their own bias in front of silu(g) * u
+            const float gt = linear_value<AT>(y0, BIAS, p.e.bias, n, p.e.bias2, RND_NONE);
+            const float up = linear_value<AT>(y1, BIAS, p.e.bias, n + p.pair_offset, p.e.bias2, RND_NONE);
+            store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)swiglu_value<AT>(gt, up, RND_NONE));
           } else if (p.epi == EPI_SWIGLU_GU8) {
             // row-interleaved gate|up tile: columns 0..7 are gate, 8..15 the matching up rows (same reduction order as above)
             if ((el & 15) < 8) {
               float yu = 0.f;
 #pragma unroll
               for (int ww = 0; ww < NW; ++ww) yu += red[((ww * NA + 0) * 64 + el + 8) * 4 + r];
-              const float gt = (float)(AT)y0, up = (float)(AT)yu;
-              const float sig = (float)(AT)(1.0f / (1.0f + expf(-gt)));
-              const float sl = (float)(AT)(gt * sig);
-              store_elem<AT>(&out[(size_t)m * p.ldo + (n >> 4) * 8 + (el & 15)], (AT)(sl * up));
+              const float gt = rounded<AT>(y0, RND_NONE), up = rounded<AT>(yu, RND_NONE);
+              store_elem<AT>(&out[(size_t)m * p.ldo + (n >> 4) * 8 + (el & 15)], (AT)swiglu_value<AT>(gt, up, RND_NONE));
             }
           } else {
-            float y = (float)(AT)y0;
-            if constexpr (BIAS) y = add_bias<AT>(y0, p.bias[n], p.bias2 != 0, RND_NONE);       // in front of the LoRA term
-            if (p.lora_t != nullptr) {
-#pragma unroll
-              for (int sl = 0; sl < 2; ++sl) {
-                const int r0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-                const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-                const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-                const float* lb = sl ? p.lora_b1 : p.lora_b0;
-                if (lb != nullptr && n >= r0 && n < r0 + ln) {
-                  const float* tt = p.lora_t + (size_t)m * p.lora_t_ld + sl * (p.lora_t_ld / 2);
-                  float z = lora_dot(tt, lb + (n - r0), ln, rk);
-                  z = (sl ? p.lora_scale_1 : p.lora_scale_0) * z;
-                  y = (float)(AT)(y + (float)(AT)z);
-                }
-              }
-            }
+            float y = linear_value<AT>(y0, BIAS, p.e.bias, n, p.e.bias2, RND_NONE);     // the bias in front of the LoRA term
+            y = lora_term<AT>(y, p.e, m, n, RND_NONE, RND_NONE);
             if (p.epi == EPI_STORE) store_elem<AT>(&out[(size_t)m * p.ldo + n], (AT)y);
             else if (p.epi == EPI_STORE_F32) ((float*)p.out)[(size_t)m * p.ldo + n] = y;
             else {

@@ -14,7 +14,7 @@
 // wave-instruction, weights go HBM -> VGPR directly, never through LDS); the activations are
 // staged once per workgroup into LDS as fp32 in K-chunks of KC; fp32 accumulate; one
 // butterfly reduction per row at the end.
-#include "kernels.h"
+#include "linear_epilogue.h"
 
 namespace mi {
 
@@ -24,10 +24,6 @@ constexpr int KC = 2048;  // K elements of x held in LDS at a time
 constexpr int PW = 2;     // row pairs per wave
 constexpr int NTHR = 256;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct GemvParams {
   const void* x; int ldx; int M;
   int rnd; int pro; const void* norm_w; float eps;
@@ -35,13 +31,8 @@ struct GemvParams {
   int N, K, group, layout;
   int epi; void* out; int ldo; void* resid; int pair_offset;
   int npairs;
-  // LoRA
-  const float* lora_t; int lora_t_ld;
-  const float* lora_b0; const float* lora_b1;
-  int lora_row0_0, lora_n_0, lora_rank_0; float lora_scale_0;
-  int lora_row0_1, lora_n_1, lora_rank_1; float lora_scale_1;
-  int lora_rnd;
-  const float* bias; int bias2;     // LinearW::bias; bias2 = quantised weights (two roundings)
+  EpiTerms e;       // LoRA ranges and bias (linear_epilogue.h)
+  int lora_rnd;     // extra rounding of t and of the LoRA term (lora_add)
 };
 
 // ---- 8 consecutive weights of one row, as fp32 -------------------------------------------
@@ -231,43 +222,17 @@ __global__ __launch_bounds__(NTHR) void gemv_v1_kernel(GemvParams p) {
     const int m = lane;
     AT* out = (AT*)p.out;
     if (p.epi == EPI_SWIGLU) {
-      // nn.silu(gate) * up, every op rounded to the activation dtype (llama.py:165)
-      float g = to_f32(store_act<AT>(mine[0], p.rnd));
-      float u = to_f32(store_act<AT>(mine[1], p.rnd));
-      if (p.bias != nullptr) {
-        g = add_bias<AT>(mine[0], p.bias[rows[a][0]], p.bias2 != 0, p.rnd);
-        u = add_bias<AT>(mine[1], p.bias[rows[a][1]], p.bias2 != 0, p.rnd);
-      }
-      const float sig = to_f32(store_act<AT>(1.0f / (1.0f + expf(-g)), p.rnd));
-      const float s = to_f32(store_act<AT>(g * sig, p.rnd));
-      out[(size_t)m * p.ldo + rows[a][0]] = store_act<AT>(s * u, p.rnd);
+      const float g = linear_value<AT>(mine[0], p.e.bias != nullptr, p.e.bias, rows[a][0], p.e.bias2, p.rnd);
+      const float u = linear_value<AT>(mine[1], p.e.bias != nullptr, p.e.bias, rows[a][1], p.e.bias2, p.rnd);
+      out[(size_t)m * p.ldo + rows[a][0]] = from_f32<AT>(swiglu_value<AT>(g, u, p.rnd));
       continue;
     }
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int n = rows[a][r];
       if (r == 1 && 2 * ((blockIdx.x * 4 + wave) * PW + a) + 1 >= p.N) continue;
-      float y = to_f32(store_act<AT>(mine[r], p.rnd));
-      if (p.bias != nullptr) y = add_bias<AT>(mine[r], p.bias[n], p.bias2 != 0, p.rnd);
-      // LoRALinear: y + (scale * ((x A) B)).astype(x.dtype)
-      if (p.lora_t != nullptr) {
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-          const int row0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-          const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-          const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-          const float* lb = sl ? p.lora_b1 : p.lora_b0;
-          if (lb != nullptr && n >= row0 && n < row0 + ln) {
-            const float* t = p.lora_t + (size_t)m * p.lora_t_ld + sl * (p.lora_t_ld / 2);
-            float z = 0.f;
-            for (int j = 0; j < rk; ++j) z = fmaf(t[j], lb[(size_t)j * ln + (n - row0)], z);
-            z = round_rt(z, p.lora_rnd);
-            z = round_rt((sl ? p.lora_scale_1 : p.lora_scale_0) * z, p.lora_rnd);
-            z = to_f32(store_act<AT>(z, p.rnd));
-            y = to_f32(store_act<AT>(y + z, p.rnd));
-          }
-        }
-      }
+      float y = linear_value<AT>(mine[r], p.e.bias != nullptr, p.e.bias, n, p.e.bias2, p.rnd);
+      y = lora_term<AT>(y, p.e, m, n, p.rnd, p.lora_rnd);
       if (p.epi == EPI_STORE) {
         out[(size_t)m * p.ldo + n] = from_f32<AT>(y);
       } else if (p.epi == EPI_STORE_F32) {
@@ -289,7 +254,7 @@ __global__ __launch_bounds__(NTHR) void lora_down_kernel(GemvParams p, const flo
   __shared__ float red[4];
   const int m = blockIdx.x, slot = blockIdx.y;
   const float* A = slot ? a1 : a0;
-  const int rk = slot ? p.lora_rank_1 : p.lora_rank_0;
+  const int rk = slot ? p.e.r[1].rank : p.e.r[0].rank;
   if (A == nullptr) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const AT* x = (const AT*)p.x + (size_t)m * p.ldx;
@@ -375,19 +340,14 @@ __global__ __launch_bounds__(256) void lora_up_add_kernel(GemvParams p, const fl
   const int m = blockIdx.x;
 #pragma unroll
   for (int sl = 0; sl < 2; ++sl) {
-    const float* lb = sl ? p.lora_b1 : p.lora_b0;
+    const float* lb = p.e.lora_b[sl];
     if (lb == nullptr) continue;
-    const int r0 = sl ? p.lora_row0_1 : p.lora_row0_0;
-    const int ln = sl ? p.lora_n_1 : p.lora_n_0;
-    const int rk = sl ? p.lora_rank_1 : p.lora_rank_0;
-    const float sc = sl ? p.lora_scale_1 : p.lora_scale_0;
+    const int ln = p.e.r[sl].n, rk = p.e.r[sl].rank;
     const float* tt = t + (size_t)m * t_ld + sl * (t_ld / 2);
     for (int n = threadIdx.x; n < ln; n += 256) {
-      float z = lora_dot(tt, lb + n, ln, rk);
-      z = sc * z;
-      AT* o = y + (size_t)m * ldy + r0 + n;
-      if constexpr (sizeof(AT) == 4) *o = round_rt((float)*o + round_rt(z, p.rnd), p.rnd);   // float32 storage, logical rounding (layer 0 of the PagedKVCache mode)
-      else *o = (AT)((float)*o + (float)(AT)z);
+      const float z = lora_dot(tt, lb + n, ln, rk);
+      AT* o = y + (size_t)m * ldy + p.e.r[sl].row0 + n;
+      *o = from_f32<AT>(lora_add<AT>(to_f32(*o), p.e.r[sl].scale, z, p.rnd, RND_NONE));
     }
   }
 }
@@ -432,12 +392,8 @@ GemvParams make_params(const LinearW& W, const GemvCall& c) {
   p.w = W.w; p.scales = W.scales; p.biases = W.biases; p.N = W.N; p.K = W.K; p.group = W.group; p.layout = W.layout;
   p.epi = c.epi; p.out = c.out; p.ldo = c.ldo; p.resid = c.resid; p.pair_offset = c.pair_offset;
   p.npairs = (c.epi == EPI_SWIGLU) ? c.pair_offset : (W.N + 1) / 2;
-  p.lora_t = c.lora_t; p.lora_t_ld = c.lora_t_ld;
-  p.lora_b0 = W.lora_b[0]; p.lora_b1 = W.lora_b[1];
-  p.lora_row0_0 = W.lora_row0[0]; p.lora_n_0 = W.lora_n[0]; p.lora_rank_0 = W.lora_rank[0]; p.lora_scale_0 = W.lora_scale[0];
-  p.lora_row0_1 = W.lora_row0[1]; p.lora_n_1 = W.lora_n[1]; p.lora_rank_1 = W.lora_rank[1]; p.lora_scale_1 = W.lora_scale[1];
+  p.e = epi_terms(W, c);
   p.lora_rnd = RND_NONE;
-  p.bias = W.bias; p.bias2 = wk_is_quant(W.wk) ? 1 : 0;
   return p;
 }
 

@@ -12,7 +12,7 @@
 //                        launch, all three behind the prefill tile GEMM
 #include <algorithm>
 
-#include "kernels.h"
+#include "linear_epilogue.h"
 
 namespace mi {
 
@@ -27,23 +27,6 @@ struct Vec16 {
   static constexpr int N = 16 / (int)sizeof(AT);
   typedef AT type __attribute__((ext_vector_type(16 / sizeof(AT)), aligned(sizeof(AT))));
 };
-
-// sig = T(sigmoid(g)) with the exp taken in float64 and ONE rounding, float64 -> T.  Through float32 (the fused epilogues'
-// expf) the value is rounded twice, and for the few g whose sigmoid lies within a float32 ulp of a midpoint of T's grid
-// (g = 11 x 2^-10: 0.5 + 5.5 ulps of f16 less 2.6e-8) the float32 lands ON the midpoint and the tie goes the wrong way: sig one ulp
-// off, which g * sig can carry to two ulps of the product -- measured: nine elements of 129 x 14336 in f16.  This kernel is
-// bound by its memory traffic; the float64 exp is free here.
-template <typename AT>
-__device__ __forceinline__ float sigmoid_rounded(float g, int rnd) {
-  const double sg = 1.0 / (1.0 + exp(-(double)g));
-  if constexpr (sizeof(AT) == 4) {
-    if (rnd == RND_BF16) return (float)(bf16)sg;
-    if (rnd == RND_F16) return (float)(f16)sg;
-    return (float)sg;
-  } else {
-    return (float)(AT)sg;
-  }
-}
 
 // out[m][n] = T(T(g * T(sigmoid(g))) * u), g = x[m][n], u = x[m][I + n]  (llama.py:165; g and u are already T-rounded)
 template <typename AT>
@@ -60,10 +43,7 @@ __global__ __launch_bounds__(NTHR) void swiglu_rows_kernel(const AT* x, int ldx,
     vec ov;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      const float g = to_f32<AT>(gv[j]), u = to_f32<AT>(uv[j]);
-      const float sig = sigmoid_rounded<AT>(g, rnd);
-      const float s = to_f32(store_act<AT>(g * sig, rnd));
-      ov[j] = store_act<AT>(s * u, rnd);
+      ov[j] = from_f32<AT>(swiglu_value<AT, true>(to_f32<AT>(gv[j]), to_f32<AT>(uv[j]), rnd));      // (the float64 sigmoid)
     }
     *(vec*)(out + m * (size_t)ldo + n) = ov;
   }
@@ -165,11 +145,9 @@ __global__ __launch_bounds__(NTHR) void lora_up_add3_kernel(Up3Params p, AT* y, 
   const float sc = p.scale[r];
   const float* tt = p.t[r] + (size_t)m * p.t_ld[r];
   for (int n = threadIdx.x; n < ln; n += NTHR) {
-    float z = lora_dot(tt, lb + n, ln, rk);
-    z = sc * z;
+    const float z = lora_dot(tt, lb + n, ln, rk);
     AT* o = y + (size_t)m * ldy + p.row0[r] + n;
-    if constexpr (sizeof(AT) == 4) *o = round_rt((float)*o + round_rt(z, p.rnd), p.rnd);
-    else *o = (AT)((float)*o + (float)(AT)z);
+    *o = from_f32<AT>(lora_add<AT>(to_f32(*o), sc, z, p.rnd, RND_NONE));
   }
 }
 
