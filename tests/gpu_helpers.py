@@ -193,9 +193,10 @@ def q4_force(mt=0, tw=0, kw=0, ksplit=0, ns=0) -> int:
 
 
 def gemm_skinny(ol: L.OpLinear, x, M, act, *, epi=0, out=None, ldo=0, resid=None, pair_offset=0, ksplit=0, iters=0, ldx=None,
-                rnd=0, norm_w=None, eps=0.0):
-    """gemm_skinny.hip / gemm_q4.hip on its own (17..128 rows) -> (ksplit used, mean launch ms or None).  norm_w: RMSNorm in
-    front (int4 weights above 16 rows only: gemm_q4.hip's preparation pass applies it)."""
+                rnd=0, norm_w=None, eps=0.0, check=True):
+    """gemm_skinny.hip / gemm_q4.hip on its own (17..128 rows) -> (ksplit used, mean launch ms or None); the return code when
+    check is False.  norm_w: RMSNorm in front (int4 weights above 16 rows: gemm_q4.hip's preparation pass applies it; float32
+    activations without rounding: the deferred norm, norm_w float32).  A linear bias rides on ol.bias (float32 [N])."""
     a = L.OpGemvArgs()
     a.x = x.data_ptr(); a.ldx = ldx if ldx is not None else x.shape[-1]; a.M = M
     a.act = MIDT[act]; a.rnd = rnd; a.pro = 1 if norm_w is not None else 0; a.epi = epi
@@ -205,7 +206,10 @@ def gemm_skinny(ol: L.OpLinear, x, M, act, *, epi=0, out=None, ldo=0, resid=None
     a.pair_offset = pair_offset; a.force_generic = 0
     torch.cuda.synchronize()
     used, ms = C.c_int(0), C.c_float(0.0)
-    L.check(L.lib().mi_op_gemm_skinny(C.byref(ol), C.byref(a), int(ksplit), C.byref(used), int(iters), C.byref(ms)))
+    rc = L.lib().mi_op_gemm_skinny(C.byref(ol), C.byref(a), int(ksplit), C.byref(used), int(iters), C.byref(ms))
+    if not check:
+        return rc
+    L.check(rc)
     return used.value, (ms.value if iters >= 1 else None)
 
 
