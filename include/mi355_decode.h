@@ -164,6 +164,27 @@ int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const
 int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B,
                        int rank, float scale, int dtype, int on_device);
 
+/* Per-request adapters: up to MI_MAX_ADAPTERS LoRA adapters are resident on one engine, every KV row names one of them or
+ * none (mi_kv_set_row_adapter), and every step -- decode, prefill, mixed, mi_score_tokens -- applies to each token row the
+ * adapter of its sequence.  Several fine-tunes of one base model then share its weights and its batch.
+ * mi_engine_set_adapter_lora: one projection of adapter slot `adapter` in [0, MI_MAX_ADAPTERS); projections, layouts, dtypes,
+ * the rank range [1,64], the column cut of a MI_ARCH_PHI3 fused projection and the rope_traditional regrouping of B are those
+ * of mi_engine_set_lora.  Adapters may cover different (layer, projection) subsets and have different ranks.  Works on a
+ * finalized, live engine: an entry that exists is hot-swapped (the stream is drained first).  A refused call changes nothing.
+ * mi_engine_clear_adapter: frees every entry of the slot; the slot is empty again.
+ * Arithmetic of an adapted row: y = T(T(acc [+ b]) + T(scale (x A) B)), then the residual h + y where the projection has one --
+ * the value mi_engine_set_lora gives.  The term runs as two small launches around the base linear ("Per-request
+ * adapters"); a step in which no row names an adapter runs exactly the launches of an engine without adapters.
+ * The table and the engine-wide adapter of mi_engine_set_lora exclude each other: whichever comes second is
+ * MI_ERR_UNSUPPORTED.  A step one of whose rows names an empty slot is MI_ERR_INVALID before anything is launched.
+ * Prefix reuse: the hash chain of a row starts from its adapter slot and the slot's generation (every set / clear bumps it),
+ * so blocks published under one adapter are never attached under another or after the adapter changed; rows without an
+ * adapter keep the keys they always had. */
+#define MI_MAX_ADAPTERS 16
+int mi_engine_set_adapter_lora(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B,
+                               int rank, float scale, int dtype, int on_device);
+int mi_engine_clear_adapter(mi_engine* e, int adapter);
+
 /* checks that every tensor was set (a missing `.bias` of a set bias flag: MI_ERR_NOTFOUND with its name), fuses q|k|v and
  * gate|up buffers, regroups q / k for rope_traditional, builds RoPE tables */
 int mi_engine_finalize(mi_engine* e);
@@ -304,6 +325,13 @@ int mi_kv_set_row_logit_bias(mi_kv* kv, int row, const int32_t* ids, const float
  * MI_ERR_INVALID, naming the argument, with nothing changed and the previous setting in force: row outside the cache;
  * top_logprobs outside [0, MI_MAX_TOP_LOGPROBS]; at_temperature other than 0 or 1. */
 int mi_kv_set_row_logprobs(mi_kv* kv, int row, int top_logprobs, int at_temperature);
+/* The adapter of the REQUEST that occupies cache row `row`: a slot of mi_engine_set_adapter_lora, or -1 = none (the default).
+ * The row must be empty (length 0): its K / V depend on the adapter.  Like the other row settings it is set once at admission
+ * and travels with the row; mi_kv_reset_row sets it back to -1, mi_kv_reset every row's.  mi_kv_fork_row wants dst to name
+ * src's adapter already (MI_ERR_INVALID naming dst otherwise, nothing changed).  The slot may be filled later, but a step on
+ * the row while the slot is empty is refused.  MI_ERR_INVALID, nothing changed: row outside the cache; adapter outside
+ * [-1, MI_MAX_ADAPTERS); a row that is not empty. */
+int mi_kv_set_row_adapter(mi_kv* kv, int row, int adapter);
 /* Block until `ticket` has finished; copy out its results (same meaning as mi_decode_sample). */
 int mi_step_wait(mi_engine* e, int64_t ticket, int32_t* tokens_out, float* logprob_out,
                  float* prob_row0_out, int32_t* topk_ids, float* topk_logprobs);

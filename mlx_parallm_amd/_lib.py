@@ -19,6 +19,7 @@ MI_KV_MODEL = -1
 MI_ARCH_LLAMA, MI_ARCH_QWEN3, MI_ARCH_PHI3 = 0, 1, 2
 MI_MAX_TOP_LOGPROBS = 20
 MI_MAX_ROW_LOGIT_BIAS = 1024
+MI_MAX_ADAPTERS = 16
 MI_ABI_VERSION = 4
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
@@ -83,6 +84,8 @@ SIGNATURES = {
     "mi_engine_destroy": (None, [_P]),
     "mi_engine_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int]),
     "mi_engine_set_lora": (C.c_int, [_P, C.c_int, C.c_char_p, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
+    "mi_engine_set_adapter_lora": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
+    "mi_engine_clear_adapter": (C.c_int, [_P, C.c_int]),
     "mi_engine_finalize": (C.c_int, [_P]),
     "mi_kv_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "mi_kv_create_paged": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -105,6 +108,7 @@ SIGNATURES = {
     "mi_kv_fork_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mi_kv_set_row_logit_bias": (C.c_int, [_P, C.c_int, _I32P, _F32P, C.c_int]),
     "mi_kv_set_row_logprobs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "mi_kv_set_row_adapter": (C.c_int, [_P, C.c_int, C.c_int]),
     "mi_step_wait": (C.c_int, [_P, C.c_int64, _I32P, _F32P, _F32P, _I32P, _F32P]),
     "mi_profile_select": (C.c_int, [_P, C.c_char_p]),
     "mi_profile_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -36,6 +36,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--host", default=d.host)
     p.add_argument("--port", type=int, default=d.port)
     p.add_argument("--lora-path", default=None, help="Optional LoRA adapter directory to apply at start-up.")
+    p.add_argument("--lora-modules", nargs="+", default=None, metavar="NAME=PATH",
+                   help="continuous scheduler: LoRA adapters that share the base model's weights and batch; a request whose "
+                   "`model` is NAME runs on that adapter (not together with --lora-path).")
     p.add_argument("--max-batch-size", type=int, default=d.max_batch_size)
     p.add_argument("--batch-timeout", type=float, default=d.batch_timeout, help="Batching window in seconds.")
     p.add_argument("--request-timeout-seconds", type=float, default=d.request_timeout_seconds)
@@ -58,8 +61,23 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def _lora_modules(parser: argparse.ArgumentParser, items: Optional[Sequence[str]]):
+    if not items:
+        return None
+    out = {}
+    for item in items:
+        name, sep, path = item.partition("=")
+        if not sep or not name or not path or name in out:
+            parser.error(f"--lora-modules: expected distinct NAME=PATH entries, got {item!r}")
+        out[name] = path
+    return out
+
+
 def parse_args(argv: Optional[Sequence[str]] = None) -> ServerConfig:
-    ns = build_parser().parse_args(argv)
+    parser = build_parser()
+    ns = parser.parse_args(argv)
+    if ns.lora_path and ns.lora_modules:
+        parser.error("--lora-path (one adapter for every request) and --lora-modules (an adapter per request) cannot be combined")
     return ServerConfig(model_path=ns.model_path, host=ns.host, port=ns.port, lora_path=ns.lora_path,
                         max_batch_size=ns.max_batch_size, batch_timeout=ns.batch_timeout,
                         request_timeout_seconds=ns.request_timeout_seconds,
@@ -67,7 +85,7 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> ServerConfig:
                         diverse_mode=bool(ns.diverse_mode), max_context_length=ns.max_context_length, device=ns.device,
                         devices=[int(x) for x in ns.devices.split(",")] if ns.devices else None,
                         chunk_tokens=ns.chunk_tokens, kv_blocks=ns.kv_blocks, prefix_cache=not ns.no_prefix_cache,
-                        fork_choices=bool(ns.fork_choices))
+                        fork_choices=bool(ns.fork_choices), lora_modules=_lora_modules(parser, ns.lora_modules))
 
 
 def cli_runner(argv: Optional[Sequence[str]] = None) -> None:

@@ -133,8 +133,50 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
         return fail(MI_ERR_INVALID, std::string(what) + ": KV capacity / max_positions exceeded (call mi_kv_reserve)");
     n += g.B; R += (size_t)g.B * g.L;
   }
+  // per-request adapters: the slot of every token row, from the cache rows and the groups' lengths.  A step none of whose
+  // rows names an adapter (by_row stays false) runs the launches of an engine without adapters, whatever is resident.
+  bool by_row = false;
+  std::vector<int32_t> tok_adapter;
+  for (const AttnGroup& g : groups)
+    for (int b = 0; b < g.B; ++b) {
+      const int a = kv->row_adapter[row_of(g, b)];
+      if (a < 0) continue;
+      if (e->adapter_parts[a] == 0)
+        return fail(MI_ERR_INVALID, std::string(what) + ": cache row " + std::to_string(row_of(g, b)) + " names adapter " + std::to_string(a) +
+                                        ", an empty slot (mi_engine_set_adapter_lora)");
+      if (!by_row) { tok_adapter.assign(R, -1); by_row = true; }
+      std::fill_n(tok_adapter.begin() + g.tok0 + (size_t)b * g.L, g.L, a);
+    }
   e->cur_L = cur_L;
   e->handover.valid = false;
+  if (by_row) {
+    MI_TRY(grow(st, &e->d_row_adapter, &e->d_row_adapter_cap, R * sizeof(int32_t)));
+    MI_TRY(grow(st, &e->lora_rt, &e->lora_rt_cap, R * LORA_ROWS_T_LD * sizeof(float)));
+    MI_TRY(grow(st, &e->ys, &e->ys_cap, R * (size_t)H * 4));                // (sized for float32 activations)
+    MI_TRY(grow(st, &e->gu, &e->gu_cap, R * 2 * (size_t)I * 4));
+    MI_HIP(hipMemcpyAsync(e->d_row_adapter, tok_adapter.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  // the by-row form of linear f in this step: some row runs an adapter and some resident adapter covers f
+  auto rows_adapted = [&](const FusedLinear& f) { return by_row && f.adapters != nullptr && f.adapters->set > 0; };
+  auto rows_call = [&](const FusedLinear& f, int K, int rnd_) {
+    LoraRowsCall rc;
+    rc.table = f.adapters->d; rc.row_adapter = e->d_row_adapter; rc.n_parts = f.n_parts;
+    for (int i = 0, r0 = 0; i < f.n_parts; ++i) { rc.row0[i] = r0; rc.n[i] = f.part_rows[i]; r0 += f.part_rows[i]; }
+    rc.M = (int)R; rc.K = K; rc.act = act; rc.rnd = rnd_; rc.t = e->lora_rt;
+    return rc;
+  };
+  // o_proj / down_proj (c: the EPI_RESID call): with per-request adapters the linear stores y = T(acc [+ b]) to a scratch buffer
+  // and ONE launch adds the rows' terms and then the residual -- y' = T(y + T(scale z)) first, h = T(h + y') second (the
+  // reference's order; adding the term onto an already summed residual would round differently)
+  auto resid_linear = [&](const FusedLinear& f, GemvCall c, int K, const char* prof) -> int {
+    if (!rows_adapted(f)) return gemv_rows(e, f, c, R, es, es, prof);
+    const LoraRowsCall rc = rows_call(f, K, c.rnd);
+    { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, PRO_NONE, nullptr, 0.f, st)); }
+    c.epi = EPI_STORE; c.out = e->ys; c.resid = nullptr;
+    MI_TRY(gemv_rows(e, f, c, R, es, es, prof));
+    Prof pr(e, "lora_rows");
+    return launch_lora_up_add_by_row(rc, e->ys, c.ldo, e->h, c.ldo, st);
+  };
   if (rows) {
     if (!kv->d_rows) MI_HIP(hipMalloc(&kv->d_rows, kv->B * sizeof(int32_t)));
     MI_HIP(hipMemcpyAsync(kv->d_rows, rows, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -177,8 +219,17 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     { // input_layernorm + q|k|v projections (llama.py:187,93)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = rnd; c.pro = PRO_NORM;
       c.norm_w = w32 ? lw.in_norm32 : lw.in_norm; c.eps = d.rms_norm_eps; c.epi = EPI_STORE; c.out = e->qkv; c.ldo = nqkv;
-      // (the offer: gemv_rows takes it -- qkv_ks K slices published -- or runs the ordinary launch)
-      MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv", cc_attn ? &qkv_ks : nullptr)); }
+      if (rows_adapted(lw.qkv)) {
+        // per-request adapters: t = x A by row, the base linear stores q|k|v, the rows' terms are added to the stored output
+        const LoraRowsCall rc = rows_call(lw.qkv, H, rnd);
+        { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, c.pro, c.norm_w, c.eps, st)); }
+        MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv"));
+        Prof pr(e, "lora_rows");
+        MI_TRY(launch_lora_up_add_by_row(rc, e->qkv, nqkv, nullptr, 0, st));
+      } else {
+        // (the offer: gemv_rows takes it -- qkv_ks K slices published -- or runs the ordinary launch)
+        MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv", cc_attn ? &qkv_ks : nullptr));
+      } }
     void* kc = (char*)kv->k + (size_t)li * layer_elems * kes;
     void* vc = (char*)kv->v + (size_t)li * layer_elems * kes;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
@@ -218,11 +269,20 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     }
     { // o_proj + residual (llama.py:143,188)
       GemvCall c; c.x = e->attn; c.ldx = Hq * D; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
-      MI_TRY(gemv_rows(e, lw.o, c, R, es, es, "gemv_o")); }
+      MI_TRY(resid_linear(lw.o, c, Hq * D, "gemv_o")); }
     { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
       c.eps = d.rms_norm_eps; c.epi = EPI_SWIGLU; c.out = e->act; c.ldo = I; c.pair_offset = I;
-      if (adapted(lw.gate_up.W)) {
+      if (rows_adapted(lw.gate_up)) {
+        // per-request adapters: as below, with the rows' own terms added to the stored gate|up ahead of the SwiGLU
+        const LoraRowsCall rc = rows_call(lw.gate_up, H, c.rnd);
+        { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, c.pro, c.norm_w, c.eps, st)); }
+        c.epi = EPI_STORE; c.out = e->gu; c.ldo = 2 * I; c.pair_offset = 0;
+        MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up"));
+        { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_up_add_by_row(rc, e->gu, 2 * I, nullptr, 0, st)); }
+        Prof pr(e, "swiglu_rows");
+        MI_TRY(launch_swiglu_rows(e->gu, 2 * I, e->act, I, (int)R, I, act, c.rnd, st));
+      } else if (adapted(lw.gate_up.W)) {
         // adapted gate and / or up: no SwiGLU epilogue carries the LoRA term, so the linear stores gate|up (plain store:
         // every kernel family adds the two ranges there) and a row-wise kernel applies SwiGLU to the stored rows
         MI_TRY(grow(st, &e->gu, &e->gu_cap, R * 2 * (size_t)I * 4));      // (sized for float32 activations)
@@ -235,7 +295,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
       } }
     { // down_proj + residual (llama.py:165,190)
       GemvCall c; c.x = e->act; c.ldx = I; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
-      MI_TRY(gemv_rows(e, lw.down, c, R, es, es, "gemv_down")); }
+      MI_TRY(resid_linear(lw.down, c, I, "gemv_down")); }
   }
   if (head != Head::NONE) {  // final norm + lm_head / tied embedding (llama.py:231,249-252)
     const FusedLinear& hw = d.tie_word_embeddings ? e->embed : e->lm_head;
@@ -469,6 +529,7 @@ void mi_engine_destroy(mi_engine* e) {
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
   hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->lora_t3); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
   hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch);
+  hipFree(e->d_row_adapter); hipFree(e->lora_rt); hipFree(e->ys);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
   hipFree(e->d_uniforms); hipFree(e->d_topk_ids); hipFree(e->d_topk_lp); hipFree(e->d_bias_ids); hipFree(e->d_bias_vals);

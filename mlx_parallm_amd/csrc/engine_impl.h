@@ -18,10 +18,20 @@
 
 #include "kernels.h"
 #include "kv_blocks.h"
+#include "lora_rows.h"
 
 namespace mi {
 
 inline bool adapted(const LinearW& W) { return W.lora_b[0] != nullptr || W.lora_b[1] != nullptr; }   // LoRA on a row range
+
+// The per-request adapters of one fused matrix (mi_engine_set_adapter_lora): the device table [part][MI_MAX_ADAPTERS] that
+// lora_rows.hip reads, its host mirror (which owns the factors) and the number of entries that hold factors.  Allocated by
+// the first adapter that covers the matrix; a matrix without one keeps its fused launches in every step.
+struct AdapterTable {
+  AdapterPart h[3][MI_MAX_ADAPTERS];
+  AdapterPart* d = nullptr;
+  int set = 0;
+};
 
 struct FusedLinear {
   LinearW W;
@@ -45,6 +55,7 @@ struct FusedLinear {
   // adds its term to the stored output behind the main launch.  Set only while both slots of W are taken, so adapted(W)
   // stays the router's one "is this matrix adapted" test.
   LoraRange lora3;
+  AdapterTable* adapters = nullptr;      // (a pointer: the [hi | lo] view of gemv_rows copies this struct)
   int seen_w[3] = {0, 0, 0}, seen_s[3] = {0, 0, 0}, seen_b[3] = {0, 0, 0};
   float* bias = nullptr;         // [rows of all parts] float32: the parts' `.bias` tensors (attention_bias / mlp_bias), as loaded
   int seen_bias[3] = {0, 0, 0};
@@ -107,6 +118,15 @@ struct mi_engine {
   float* lora_t = nullptr;
   float* lora_t3 = nullptr;                               // [rows][64]: t of a q|k|v matrix's third range (FusedLinear::lora3)
   void* gu = nullptr; size_t gu_cap = 0;                  // [rows][2 I]: the stored output of an ADAPTED gate|up (swiglu_rows_kernel reads it)
+  // ---- per-request adapters: slot s is resident while adapter_parts[s] > 0 ((layer, projection part) entries that hold
+  // factors); adapter_gen[s] counts the changes of the slot (the prefix cache's hash seed: K/V depend on the adapter).
+  // engine_lora: mi_engine_set_lora has adapted this engine -- the two forms exclude each other.
+  int adapter_parts[MI_MAX_ADAPTERS] = {};
+  uint32_t adapter_gen[MI_MAX_ADAPTERS] = {};
+  bool engine_lora = false;
+  int32_t* d_row_adapter = nullptr; size_t d_row_adapter_cap = 0;   // [token rows] of the current step
+  float* lora_rt = nullptr; size_t lora_rt_cap = 0;                 // [token rows][LORA_ROWS_T_LD]: t of the by-row kernels
+  void* ys = nullptr; size_t ys_cap = 0;                            // [token rows][H]: stored o_proj / down_proj output ahead of the by-row up-add
   int32_t* d_tokens = nullptr; size_t d_tokens_cap = 0;
   const int32_t* tok_src = nullptr;                       // device-fed step: the embedding reads the sampler's output in place
   int32_t* d_forced = nullptr; size_t d_forced_cap = 0;   // mi_score_tokens targets
@@ -164,6 +184,7 @@ struct mi_kv {
   int32_t* d_off = nullptr;
   std::vector<int32_t> h_off;
   int32_t* d_rows = nullptr;     // [B] scratch: cache rows of the current call (continuous batching)
+  std::vector<int32_t> row_adapter;      // [B]: adapter slot of the request that occupies the row, -1 = none (mi_kv_set_row_adapter)
   float* partial = nullptr; size_t partial_cap = 0;      // split-KV partials, sized for 16 splits (mi::grow: bytes)
   int* counters = nullptr;       // [B*Hkv] split-arrival tickets of the fused decode attention
   // ---- per-row logit_bias (mi_kv_set_row_logit_bias): one block [B counts | B map | B x MI_MAX_ROW_LOGIT_BIAS ids | as many
@@ -207,6 +228,7 @@ struct Prof {
 
 // engine_load.hip
 void free_linear(FusedLinear& f);
+inline int adapters_resident(const mi_engine* e) { int n = 0; for (int s : e->adapter_parts) n += s > 0; return n; }
 // engine_linear.hip.  gemv_rows: y = W x for `rows` rows on the kernel family its route picks.  consumer_combine: `published` !=
 // null is an OFFER of the caller's -- "the next launch can add K slices published in the seam buffer instead of reading
 // c.out".  The router takes it on the one route whose kernel has the publish-only form, and *published = the number of K

@@ -94,6 +94,12 @@ int lp_clear_row(mi_kv* kv, int row) {
   return MI_OK;
 }
 
+// where the row's prefix hash chains start: K / V depend on the adapter (0 for a row without one: the keys of always)
+uint64_t prefix_seed(const mi_kv* kv, int row) {
+  const int a = kv->row_adapter[row];
+  return a < 0 ? 0 : KvBlocks::adapter_seed(a, kv->e->adapter_gen[a]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,6 +118,7 @@ int mi_kv_create(mi_engine* e, int batch, int capacity_tokens, int kv_dtype, mi_
                                   {(void**)&kv->d_off, batch * sizeof(int32_t)}}, "out of device memory allocating the KV cache");
   if (rc != MI_OK) { delete kv; return rc; }
   kv->h_off.assign(batch, 0);
+  kv->row_adapter.assign(batch, -1);
   *out = kv;
   return MI_OK;
 }
@@ -134,6 +141,7 @@ int mi_kv_create_paged(mi_engine* e, int slots, int block_tokens, int n_blocks, 
                       "out of device memory allocating the paged KV arena");
   if (rc != MI_OK) { delete kv; return rc; }
   kv->h_off.assign(slots, 0);
+  kv->row_adapter.assign(slots, -1);
   *out = kv;
   return MI_OK;
 }
@@ -143,7 +151,7 @@ int mi_kv_prefix_attach(mi_kv* kv, int row, const int32_t* tokens, int n, int* n
   if (!kv->paged) return fail(MI_ERR_INVALID, "prefix reuse needs a paged KV (mi_kv_create_paged)");
   if (row < 0 || row >= kv->B) return fail(MI_ERR_INVALID, "row out of range");
   if (kv->h_off[row] != 0 || kv->blocks.row_blocks[row] != 0) return fail(MI_ERR_INVALID, "prefix attach: the row must be empty (mi_kv_reset_row first)");
-  const int reused = kv->blocks.attach(row, tokens, n);
+  const int reused = kv->blocks.attach(row, tokens, n, prefix_seed(kv, row));
   if (reused > 0) {
     kv->h_off[row] = reused;
     MI_HIP(hipSetDevice(kv->e->device));
@@ -158,7 +166,7 @@ int mi_kv_prefix_publish(mi_kv* kv, int row, const int32_t* tokens, int n) {
   if (!kv->paged) return fail(MI_ERR_INVALID, "prefix reuse needs a paged KV (mi_kv_create_paged)");
   if (row < 0 || row >= kv->B) return fail(MI_ERR_INVALID, "row out of range");
   if (n > kv->h_off[row]) return fail(MI_ERR_INVALID, "prefix publish: those tokens are not in the row's cache yet");
-  kv->blocks.publish(row, tokens, n);
+  kv->blocks.publish(row, tokens, n, prefix_seed(kv, row));
   return MI_OK;
 }
 
@@ -195,6 +203,7 @@ int mi_kv_reset(mi_kv* kv, int batch) {
   for (int r = 0; r < kv->B; ++r) MI_TRY(lp_clear_row(kv, r));     // and its logprobs setting
   MI_HIP(hipStreamSynchronize(kv->e->stream));
   std::fill(kv->h_off.begin(), kv->h_off.end(), 0);
+  std::fill(kv->row_adapter.begin(), kv->row_adapter.end(), -1);
   for (int r = 0; r < kv->B; ++r) kv_release_row(kv, r);
   return MI_OK;
 }
@@ -205,6 +214,7 @@ int mi_kv_reset_row(mi_kv* kv, int row) {
   MI_HIP(hipSetDevice(kv->e->device));
   MI_HIP(hipMemsetAsync(kv->d_off + row, 0, sizeof(int32_t), kv->e->stream));   // ordered behind the steps already enqueued
   kv->h_off[row] = 0;
+  kv->row_adapter[row] = -1;                                // the next occupant of the row names its own adapter
   kv_release_row(kv, row);      // (paged: the blocks go back to the pool; whoever gets them next writes behind the steps in flight)
   MI_TRY(rb_clear_row(kv, row));                            // the next occupant of the row samples unbiased
   return lp_clear_row(kv, row);                             // and reports what its own request asks for
@@ -219,6 +229,9 @@ int mi_kv_fork_row(mi_kv* kv, int src, int dst, int n_tokens) {
     return fail(MI_ERR_INVALID, "mi_kv_fork_row: dst must be empty (mi_kv_reset_row first)");
   if (n_tokens < 1 || n_tokens > kv->h_off[src])
     return fail(MI_ERR_INVALID, "mi_kv_fork_row: n_tokens must be in [1, " + std::to_string(kv->h_off[src]) + "], the length of src");
+  if (kv->row_adapter[dst] != kv->row_adapter[src])
+    return fail(MI_ERR_INVALID, "mi_kv_fork_row: dst names adapter " + std::to_string(kv->row_adapter[dst]) + ", src adapter " +
+                                    std::to_string(kv->row_adapter[src]) + " (mi_kv_set_row_adapter on dst first: K / V depend on the adapter)");
   MI_HIP(hipSetDevice(kv->e->device));
   const mi_model_desc& d = kv->e->d;
   hipStream_t st = kv->e->stream;
@@ -246,6 +259,17 @@ int mi_kv_fork_row(mi_kv* kv, int src, int dst, int n_tokens) {
     rc = fail(MI_ERR_RUNTIME, "mi_kv_fork_row: hipMemsetD32Async failed");
   if (rc != MI_OK) { kv_release_row(kv, dst); return rc; }     // dst stays empty
   kv->h_off[dst] = n_tokens;
+  return MI_OK;
+}
+
+int mi_kv_set_row_adapter(mi_kv* kv, int row, int adapter) {
+  if (!kv) return fail(MI_ERR_INVALID, "null kv");
+  if (row < 0 || row >= kv->B) return fail(MI_ERR_INVALID, "mi_kv_set_row_adapter: row out of range");
+  if (adapter < -1 || adapter >= MI_MAX_ADAPTERS)
+    return fail(MI_ERR_INVALID, "mi_kv_set_row_adapter: adapter " + std::to_string(adapter) + " is outside [-1, " + std::to_string(MI_MAX_ADAPTERS) + ")");
+  if (kv->h_off[row] != 0 || (kv->paged && kv->blocks.row_blocks[row] != 0))
+    return fail(MI_ERR_INVALID, "mi_kv_set_row_adapter: the row must be empty (mi_kv_reset_row first): its K / V depend on the adapter");
+  kv->row_adapter[row] = adapter;
   return MI_OK;
 }
 

@@ -208,6 +208,13 @@ void mi::free_linear(FusedLinear& f) {
   hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
   for (int i = 0; i < 2; ++i) { hipFree(f.lora_a[i]); hipFree(f.lora_b[i]); }
   hipFree(const_cast<float*>(f.lora3.a)); hipFree(const_cast<float*>(f.lora3.b));
+  if (f.adapters != nullptr) {
+    for (auto& part : f.adapters->h)
+      for (AdapterPart& ap : part) { hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b)); }
+    hipFree(f.adapters->d);
+    delete f.adapters;
+    f.adapters = nullptr;
+  }
 }
 
 extern "C" {
@@ -306,9 +313,50 @@ static int set_lora_part(mi_engine* e, LayerW& l, const Proj& pj, const void* A,
   return MI_OK;
 }
 
-int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
-                       int dtype, int on_device) {
+// one adapted range of adapter slot `adapter`: entry [pj.part][adapter] of the matrix's table (lora_rows.h), hot-swapped when
+// it exists.  The stream is drained first and the table entry is written with a blocking copy: no step is in flight.
+static int set_adapter_part(mi_engine* e, int adapter, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
+  const mi_model_desc& d = e->d;
+  FusedLinear* f = pj.f;
+  const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
+  int row0 = 0;
+  for (int i = 0; i < pj.part; ++i) row0 += f->part_rows[i];
+  MI_HIP(hipStreamSynchronize(e->stream));
+  if (f->adapters == nullptr) {
+    AdapterPart* dt = nullptr;
+    MI_HIP(hipMalloc(&dt, sizeof(AdapterTable::h)));
+    if (hipMemset(dt, 0, sizeof(AdapterTable::h)) != hipSuccess) { hipFree(dt); return fail(MI_ERR_RUNTIME, "adapter table: hipMemset failed"); }
+    f->adapters = new AdapterTable();
+    f->adapters->d = dt;
+  }
+  float* na = nullptr; float* nb = nullptr;
+  MI_HIP(hipMalloc(&na, (size_t)K * rank * sizeof(float)));
+  if (hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); hipFree(na); return fail(MI_ERR_RUNTIME, "LoRA: out of device memory"); }
+  int rc = copy_in(na, A, (size_t)K * rank * sizeof(float), on_device, e->stream);
+  if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
+  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
+  if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
+  AdapterPart& slot = f->adapters->h[pj.part][adapter];
+  const AdapterPart fresh{na, nb, rank, scale};
+  if (rc == MI_OK && hipMemcpy(f->adapters->d + pj.part * MI_MAX_ADAPTERS + adapter, &fresh, sizeof(fresh), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(MI_ERR_RUNTIME, "adapter table: hipMemcpy failed");
+  if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
+  if (slot.a == nullptr) { ++f->adapters->set; ++e->adapter_parts[adapter]; }
+  hipFree(const_cast<float*>(slot.a)); hipFree(const_cast<float*>(slot.b));
+  slot = fresh;
+  ++e->adapter_gen[adapter];            // K / V made with the slot's earlier contents are unreachable from now on (kv_blocks.h)
+  return MI_OK;
+}
+
+// mi_engine_set_lora (adapter < 0: the engine-wide adapter) and mi_engine_set_adapter_lora (a slot of the table)
+static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
+                        int dtype, int on_device) {
   if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
+  if (adapter >= MI_MAX_ADAPTERS) return fail(MI_ERR_INVALID, "adapter slot must be in [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
+  if (adapter >= 0 && e->engine_lora)
+    return fail(MI_ERR_UNSUPPORTED, "mi_engine_set_adapter_lora: this engine carries the engine-wide adapter of mi_engine_set_lora; the two exclude each other");
+  if (adapter < 0 && adapters_resident(e) > 0)
+    return fail(MI_ERR_UNSUPPORTED, "mi_engine_set_lora: this engine carries per-request adapters (mi_engine_set_adapter_lora); the two exclude each other");
   if (layer < 0 || layer >= e->d.num_layers) return fail(MI_ERR_INVALID, "layer out of range");
   if (rank < 1 || rank > 64) return fail(MI_ERR_UNSUPPORTED, "LoRA rank must be in [1,64]");
   if (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, "bad LoRA dtype");
@@ -320,7 +368,13 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
   const std::string p(proj);
   Proj pj;
   if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the linears of a block only)");
-  if (pj.part >= 0) return set_lora_part(e, l, pj, A, B, rank, scale, on_device);
+  auto put = [&](const Proj& part, const void* a, const void* b) {
+    if (adapter >= 0) return set_adapter_part(e, adapter, l, part, a, b, rank, scale, on_device);
+    const int rc = set_lora_part(e, l, part, a, b, rank, scale, on_device);
+    if (rc == MI_OK) e->engine_lora = true;
+    return rc;
+  };
+  if (pj.part >= 0) return put(pj, A, B);
   // MI_ARCH_PHI3, qkv_proj / gate_up_proj: A is shared, B (rank, N) is cut by columns into the parts -- what one call per
   // part with the column slice does on an engine with split projections
   int N = 0;
@@ -339,11 +393,48 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
       if (hipMemcpy(db, sb, slice.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(db); return fail(MI_ERR_RUNTIME, "LoRA: copying a column slice failed"); }
     }
     const Proj part{pj.f, i, pj.K, pj.attn};
-    const int rc = set_lora_part(e, l, part, A, on_device ? db : (const void*)sb, rank, scale, on_device);
+    const int rc = put(part, A, on_device ? db : (const void*)sb);
     hipFree(db);
     MI_TRY(rc);
     col0 += n;
   }
+  return MI_OK;
+}
+
+int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
+                       int dtype, int on_device) {
+  return set_lora_any(e, -1, layer, proj, A, B, rank, scale, dtype, on_device);
+}
+
+int mi_engine_set_adapter_lora(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, int rank,
+                               float scale, int dtype, int on_device) {
+  if (adapter < 0 || adapter >= MI_MAX_ADAPTERS)
+    return fail(MI_ERR_INVALID, "mi_engine_set_adapter_lora: adapter " + std::to_string(adapter) + " is outside [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
+  return set_lora_any(e, adapter, layer, proj, A, B, rank, scale, dtype, on_device);
+}
+
+int mi_engine_clear_adapter(mi_engine* e, int adapter) {
+  if (!e) return fail(MI_ERR_INVALID, "null engine");
+  if (adapter < 0 || adapter >= MI_MAX_ADAPTERS)
+    return fail(MI_ERR_INVALID, "mi_engine_clear_adapter: adapter " + std::to_string(adapter) + " is outside [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
+  MI_HIP(hipSetDevice(e->device));
+  MI_HIP(hipStreamSynchronize(e->stream));          // no step reads the factors any more
+  for (LayerW& l : e->layers)
+    for (FusedLinear* f : {&l.qkv, &l.o, &l.gate_up, &l.down}) {
+      if (f->adapters == nullptr) continue;
+      bool changed = false;
+      for (auto& part : f->adapters->h) {
+        AdapterPart& ap = part[adapter];
+        if (ap.a == nullptr) continue;
+        hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b));
+        ap = AdapterPart{};
+        --f->adapters->set;
+        changed = true;
+      }
+      if (changed) MI_HIP(hipMemcpy(f->adapters->d, f->adapters->h, sizeof(AdapterTable::h), hipMemcpyHostToDevice));
+    }
+  e->adapter_parts[adapter] = 0;
+  ++e->adapter_gen[adapter];
   return MI_OK;
 }
 

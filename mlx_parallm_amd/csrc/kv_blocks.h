@@ -65,11 +65,24 @@ struct KvBlocks {
     row_blocks[row] = 0;
   }
 
+  // Where the hash chains of a row that runs adapter `slot` start: K / V depend on the adapter, so chains published under
+  // one (slot, generation) are found under no other -- the seed is the first block's parent, which same_prefix compares,
+  // so this does not rest on the hash alone.  `generation` counts the changes of the slot: the chains of a replaced adapter
+  // become unreachable and leave through the LRU.  Never 0, the seed of a row without an adapter (the keys of always).
+  static uint64_t adapter_seed(int slot, uint32_t generation) {
+    uint64_t z = (((uint64_t)(uint32_t)(slot + 1)) << 32 | generation) + 0x9E3779B97F4A7C15ull;     // splitmix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z ? z : 1;
+  }
+
   // An EMPTY row (the caller checks) maps the published blocks that its prompt of n tokens starts with; returns the tokens they
-  // hold.  Full blocks only, and at least one token of the prompt is left to run (its logits are needed).
-  int attach(int row, const int32_t* tokens, int n) {
+  // hold.  Full blocks only, and at least one token of the prompt is left to run (its logits are needed).  seed: adapter_seed
+  // of the row's adapter, 0 without one.
+  int attach(int row, const int32_t* tokens, int n, uint64_t seed = 0) {
     const int bs = 1 << bs_shift;
-    uint64_t parent = 0;
+    uint64_t parent = seed;
     int reused = 0;
     std::vector<uint64_t> chain;
     while (reused + bs <= n - 1 && row_blocks[row] < bt_stride) {
@@ -90,9 +103,9 @@ struct KvBlocks {
   }
 
   // the full blocks of the row's first n tokens (all of them in its cache already: the caller checks) enter the prefix cache
-  void publish(int row, const int32_t* tokens, int n) {
+  void publish(int row, const int32_t* tokens, int n, uint64_t seed = 0) {
     const int bs = 1 << bs_shift;
-    uint64_t parent = 0;
+    uint64_t parent = seed;
     std::vector<uint64_t> chain;
     for (int i = 0; (i + 1) * bs <= n; ++i) {
       const uint64_t h = prefix_hash(parent, tokens + i * bs, bs);

@@ -1,0 +1,41 @@
+// lora_rows.h -- per-request LoRA adapters (mi_engine_set_adapter_lora / mi_kv_set_row_adapter): the rows of one step run
+// different adapters.  Launch interface of lora_rows.hip; beside kernels.h, so that no linear kernel's header changes.
+//
+// Every fused matrix of a block that some resident adapter covers owns a device table [part][MI_MAX_ADAPTERS] of AdapterPart;
+// a step uploads row_adapter[token row] (-1: none) and each adapted linear runs
+//   launch_lora_down_by_row    t[m][part][0..rank) = x_m A of the row's adapter (x and its RMSNorm staged once per row)
+//   the base linear            plain store, no LoRA term
+//   launch_lora_up_add_by_row  y[m][row0 + n] = R(y + R(scale . z)) per row, optionally followed by h[m][n] = R(h + y')
+// The arithmetic of an element is the single-adapter path's: lora_down3_kernel's summation order, lora_dot, lora_add.
+#pragma once
+#include "kernels.h"
+
+namespace mi {
+
+struct AdapterPart {
+  const float* a = nullptr;    // [K][rank]; null: the adapter does not cover this part
+  const float* b = nullptr;    // [rank][n of the part]
+  int rank = 0;
+  float scale = 0.f;
+};
+
+constexpr int LORA_ROWS_T_LD = 3 * 64;     // floats of t per token row: [part][64]
+
+struct LoraRowsCall {
+  const AdapterPart* table = nullptr;      // device [n_parts][MI_MAX_ADAPTERS]
+  const int32_t* row_adapter = nullptr;    // device [M]: slot of every token row, -1 = none
+  int n_parts = 0;
+  int row0[3] = {0, 0, 0}, n[3] = {0, 0, 0};   // output columns [row0, row0 + n) of every part
+  int M = 0, K = 0;
+  int act = MI_F32, rnd = RND_NONE;
+  float* t = nullptr;                      // device [M][LORA_ROWS_T_LD]
+};
+
+// x [M][ldx] in the activation dtype; pro / norm_w / eps: the linear's prologue.  K <= 36864.
+int launch_lora_down_by_row(const LoraRowsCall& c, const void* x, int ldx, int pro, const void* norm_w, float eps,
+                            hipStream_t st);
+// y [M][ldy]: the stored output of the base linear.  resid != null ([M][ldr], one part whose row0 is 0): every row, adapted
+// or not, ends with resid = R(resid + y'); y itself is then left as the linear stored it.
+int launch_lora_up_add_by_row(const LoraRowsCall& c, void* y, int ldy, void* resid, int ldr, hipStream_t st);
+
+}  // namespace mi

@@ -1,0 +1,197 @@
+// lora_rows.hip -- the LoRA term of a step whose rows run DIFFERENT adapters (lora_rows.h).  Unfused on purpose: the term
+// lives outside the linear kernels' parameter blocks (a per-lane B pointer inside their epilogues would cost registers in
+// kernels that sit at an occupancy edge), behind a plain-store launch of the base linear.
+//   lora_down_by_row_kernel    t = x A of each row's own adapter, for every part of the fused matrix the adapter covers
+//   lora_up_add_by_row_kernel  y += T(scale (t B)) with the row's own B, rank and scale; with a residual operand also h += y'
+#include <algorithm>
+#include <atomic>
+
+#include "linear_epilogue.h"
+#include "lora_rows.h"
+
+namespace mi {
+
+namespace {
+
+constexpr int NTHR = 256;
+constexpr int UP_COLS = 4 * NTHR;      // output columns of one workgroup of the up-add
+
+struct DownRowsParams {
+  const void* x; int ldx; int K;
+  int pro; const void* norm_w; float eps; int rnd;
+  const AdapterPart* table; const int32_t* row_adapter; int n_parts;
+  float* t;
+};
+
+// t[m][part][j] = sum_k xin[m][k] * A[k][j], A = the part's factor of row m's adapter; xin = the (normalised) row, staged once
+// in LDS.  The sum of a column is lora_down3_kernel's (lora.hip): thread tid adds k = tid, tid + 256, ... in ascending order,
+// then the wave sum, then the four waves in order -- t is the bits the single-adapter path makes.  A row without an adapter
+// leaves at once; a part its adapter does not cover is skipped (both are uniform over the workgroup).
+template <typename AT>
+__global__ __launch_bounds__(NTHR) void lora_down_by_row_kernel(DownRowsParams p) {
+  extern __shared__ float xs[];      // [K]
+  __shared__ float rs_sh;
+  __shared__ float red[4];
+  __shared__ float red16[4][16];
+  const int m = blockIdx.x;
+  const int ad = p.row_adapter[m];
+  if (ad < 0 || ad >= MI_MAX_ADAPTERS) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const AT* x = (const AT*)p.x + (size_t)m * p.ldx;
+  for (int k = tid; k < p.K; k += NTHR) xs[k] = to_f32(x[k]);          // (each thread reads back only what it wrote)
+  if (p.pro == PRO_NORM) {
+    float ss = 0.f;
+    for (int k = tid; k < p.K; k += NTHR) { const float v = xs[k]; ss += v * v; }
+    ss = wave_sum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    if (tid == 0) rs_sh = 1.0f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)p.K + p.eps);
+    __syncthreads();
+    const float rs = rs_sh;
+    for (int k = tid; k < p.K; k += NTHR) {
+      const AT xn = store_act<AT>(xs[k] * rs, p.rnd);
+      xs[k] = to_f32(store_act<AT>(to_f32(xn) * to_f32(((const AT*)p.norm_w)[k]), p.rnd));
+    }
+  }
+#pragma unroll 1
+  for (int r = 0; r < p.n_parts; ++r) {
+    const AdapterPart ap = p.table[r * MI_MAX_ADAPTERS + ad];
+    const float* A = ap.a;
+    const int rk = min(ap.rank, 64);
+    if (A == nullptr) continue;
+    float* tr = p.t + (size_t)m * LORA_ROWS_T_LD + r * 64;
+    for (int j0 = 0; j0 < rk; j0 += 16) {
+      float s[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s[j] = 0.f;
+      const bool vec = (rk % 4 == 0) && (j0 + 16 <= rk);
+      if (vec) {
+#pragma unroll 4
+        for (int k = tid; k < p.K; k += NTHR) {
+          const float vv = xs[k];
+          const float4* ar = (const float4*)(A + (size_t)k * rk + j0);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 a4 = ar[q];
+            s[4 * q + 0] = fmaf(vv, a4.x, s[4 * q + 0]);
+            s[4 * q + 1] = fmaf(vv, a4.y, s[4 * q + 1]);
+            s[4 * q + 2] = fmaf(vv, a4.z, s[4 * q + 2]);
+            s[4 * q + 3] = fmaf(vv, a4.w, s[4 * q + 3]);
+          }
+        }
+      } else {
+        for (int k = tid; k < p.K; k += NTHR) {
+          const float vv = xs[k];
+          const float* ar = A + (size_t)k * rk + j0;
+#pragma unroll
+          for (int j = 0; j < 16; ++j)
+            if (j0 + j < rk) s[j] = fmaf(vv, ar[j], s[j]);
+        }
+      }
+      __syncthreads();                 // (red16 of the previous group has been read)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float w = wave_sum(s[j]);
+        if (lane == 0) red16[wave][j] = w;
+      }
+      __syncthreads();
+      if (tid < 16 && j0 + tid < rk) tr[j0 + tid] = red16[0][tid] + red16[1][tid] + red16[2][tid] + red16[3][tid];
+    }
+  }
+}
+
+struct UpRowsParams {
+  const AdapterPart* table; const int32_t* row_adapter; const float* t;
+  int row0[3], n[3];
+  int rnd;
+};
+
+// Part blockIdx.y, columns [blockIdx.z * UP_COLS, + UP_COLS) of token row blockIdx.x, consecutive lanes on consecutive columns:
+//   y[m][row0 + n] = T(y + T(scale * sum_j t[m][part][j] B[j][n]))      lora_dot and lora_add, as lora_up_add3_kernel (lora.hip)
+// with B, rank and scale of the row's own adapter.  resid != null: h[m][n] = T(h[m][n] + y') instead of the store to y (the
+// residual add of EPI_RESID, kernels.h), for EVERY row -- a row whose adapter does not cover the part adds the stored y.
+template <typename AT>
+__global__ __launch_bounds__(NTHR) void lora_up_add_by_row_kernel(UpRowsParams p, AT* y, int ldy, AT* resid, int ldr) {
+  const int m = blockIdx.x, r = blockIdx.y;
+  const int ln = p.n[r];
+  const int n0 = blockIdx.z * UP_COLS;
+  if (n0 >= ln) return;
+  const int ad = p.row_adapter[m];
+  AdapterPart ap{};
+  if (ad >= 0 && ad < MI_MAX_ADAPTERS) ap = p.table[r * MI_MAX_ADAPTERS + ad];
+  const float* lb = ap.b;
+  if (lb == nullptr && resid == nullptr) return;
+  const int rk = min(ap.rank, 64);
+  const float sc = ap.scale;
+  const float* tt = p.t + (size_t)m * LORA_ROWS_T_LD + r * 64;
+  const int n1 = min(ln, n0 + UP_COLS);
+  for (int n = n0 + threadIdx.x; n < n1; n += NTHR) {
+    AT* o = y + (size_t)m * ldy + p.row0[r] + n;
+    float v = to_f32(*o);
+    if (lb != nullptr) v = lora_add<AT>(v, sc, lora_dot(tt, lb + n, ln, rk), p.rnd, RND_NONE);
+    if (resid != nullptr) {
+      AT* h = resid + (size_t)m * ldr + p.row0[r] + n;
+      *h = store_act<AT>(to_f32(*h) + v, p.rnd);
+    } else {
+      *o = from_f32<AT>(v);
+    }
+  }
+}
+
+int check_call(const LoraRowsCall& c, const char* who) {
+  if (c.table == nullptr || c.row_adapter == nullptr || c.t == nullptr) return fail(MI_ERR_INVALID, std::string(who) + ": null argument");
+  if (c.M < 1) return fail(MI_ERR_INVALID, std::string(who) + ": no rows");
+  if (c.n_parts < 1 || c.n_parts > 3) return fail(MI_ERR_INVALID, std::string(who) + ": 1 to 3 parts");
+  if (c.act != MI_F32 && c.act != MI_BF16 && c.act != MI_F16) return fail(MI_ERR_INVALID, std::string(who) + ": bad activation dtype");
+  return MI_OK;
+}
+
+}  // namespace
+
+int launch_lora_down_by_row(const LoraRowsCall& c, const void* x, int ldx, int pro, const void* norm_w, float eps,
+                            hipStream_t st) {
+  MI_TRY(check_call(c, "lora_down_by_row"));
+  if (x == nullptr || c.K < 1 || ldx < c.K || (pro == PRO_NORM && norm_w == nullptr)) return fail(MI_ERR_INVALID, "lora_down_by_row: bad argument");
+  const size_t lds = (size_t)c.K * sizeof(float);
+  if (lds > 144 * 1024) return fail(MI_ERR_UNSUPPORTED, "lora_down_by_row: K above 36864");
+  if (lds > 48 * 1024) {               // (the statics ride beside the row: opt in well below the 64 KiB line)
+    static std::atomic<bool> opted[64];
+    MI_TRY(lds_opt_in(opted, {(const void*)lora_down_by_row_kernel<float>, (const void*)lora_down_by_row_kernel<bf16>,
+                              (const void*)lora_down_by_row_kernel<f16>}, 144 * 1024));
+  }
+  DownRowsParams p{};
+  p.x = x; p.ldx = ldx; p.K = c.K; p.pro = pro; p.norm_w = norm_w; p.eps = eps; p.rnd = c.rnd;
+  p.table = c.table; p.row_adapter = c.row_adapter; p.n_parts = c.n_parts; p.t = c.t;
+  const dim3 grid(c.M), block(NTHR);
+  switch (c.act) {
+    case MI_F32: hipLaunchKernelGGL(lora_down_by_row_kernel<float>, grid, block, lds, st, p); break;
+    case MI_BF16: hipLaunchKernelGGL(lora_down_by_row_kernel<bf16>, grid, block, lds, st, p); break;
+    case MI_F16: hipLaunchKernelGGL(lora_down_by_row_kernel<f16>, grid, block, lds, st, p); break;
+  }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int launch_lora_up_add_by_row(const LoraRowsCall& c, void* y, int ldy, void* resid, int ldr, hipStream_t st) {
+  MI_TRY(check_call(c, "lora_up_add_by_row"));
+  if (y == nullptr) return fail(MI_ERR_INVALID, "lora_up_add_by_row: null output");
+  if (resid != nullptr && (c.n_parts != 1 || c.row0[0] != 0 || ldr < c.n[0])) return fail(MI_ERR_INVALID, "lora_up_add_by_row: a residual goes with one part at column 0");
+  int widest = 0;
+  for (int i = 0; i < c.n_parts; ++i) {
+    if (c.n[i] < 1 || c.row0[i] < 0 || (long long)c.row0[i] + c.n[i] > ldy) return fail(MI_ERR_INVALID, "lora_up_add_by_row: a part lies outside the row");
+    widest = std::max(widest, c.n[i]);
+  }
+  UpRowsParams p{};
+  p.table = c.table; p.row_adapter = c.row_adapter; p.t = c.t; p.rnd = c.rnd;
+  for (int i = 0; i < c.n_parts; ++i) { p.row0[i] = c.row0[i]; p.n[i] = c.n[i]; }
+  const dim3 grid(c.M, c.n_parts, (widest + UP_COLS - 1) / UP_COLS), block(NTHR);
+  switch (c.act) {
+    case MI_BF16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<bf16>, grid, block, 0, st, p, (bf16*)y, ldy, (bf16*)resid, ldr); break;
+    case MI_F16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<f16>, grid, block, 0, st, p, (f16*)y, ldy, (f16*)resid, ldr); break;
+    case MI_F32: hipLaunchKernelGGL(lora_up_add_by_row_kernel<float>, grid, block, 0, st, p, (float*)y, ldy, (float*)resid, ldr); break;
+  }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+}  // namespace mi

@@ -187,6 +187,15 @@ class KVCache:
         else:
             self._row_logprobs()[int(row)] = int(top_logprobs)
 
+    def set_row_adapter(self, row: int, slot: int) -> None:
+        """The adapter of the request that occupies ``row`` (``mi_kv_set_row_adapter``): a slot of
+        ``Engine.set_adapter_lora`` or -1 = none (the default).  The row must be empty; ``reset_row`` / ``reset`` set it back
+        to -1.  ValueError (nothing changed): a bad row or slot, a row that holds tokens."""
+        for name, v in (("row", row), ("slot", slot)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"set_row_adapter: {name} {v!r} is not an int32")
+        L.check(L.lib().mi_kv_set_row_adapter(self._h, int(row), int(slot)))
+
     def set_row_logit_bias(self, row: int, bias: Optional[Dict[int, float]]) -> None:
         """The logit_bias of the request that occupies ``row`` (``mi_kv_set_row_logit_bias``): it replaces the row's bias,
         ``None`` / ``{}`` clears it; every later step that samples this row adds it after the call's own ``logit_bias``.
@@ -378,6 +387,27 @@ class Engine:
         L.check(L.lib().mi_engine_set_lora(self._h, int(layer), proj.encode(), C.c_void_p(ta.data_ptr()),
                                            C.c_void_p(tb.data_ptr()), rank, float(scale), L.MI_F32, int(ta.is_cuda)))
         self.invalidate_prefix_caches()
+
+    def set_adapter_lora(self, slot: int, layer: int, proj: str, a, b, scale: float) -> None:
+        """``mi_engine_set_adapter_lora``: one projection of the per-request adapter in ``slot`` (0..15); arguments as
+        ``set_lora``.  Rows that name the slot (``KVCache.set_row_adapter``) run it, the others do not; also on a finalized,
+        live engine (hot-swap).  Published prefixes are kept: those made under the slot's earlier contents become
+        unreachable.  ValueError: a slot outside the table; NotImplementedError: a bad rank or projection, or an engine that
+        carries the engine-wide adapter of ``set_lora`` -- nothing changed."""
+        import torch
+        ta = torch.as_tensor(a).to(torch.float32).contiguous()
+        tb = torch.as_tensor(b).to(torch.float32).contiguous()
+        if ta.is_cuda != tb.is_cuda:
+            raise ValueError("LoRA factors must live on the same device")
+        if ta.is_cuda:
+            torch.cuda.synchronize()
+        L.check(L.lib().mi_engine_set_adapter_lora(self._h, int(slot), int(layer), proj.encode(), C.c_void_p(ta.data_ptr()),
+                                                   C.c_void_p(tb.data_ptr()), int(ta.shape[1]), float(scale), L.MI_F32,
+                                                   int(ta.is_cuda)))
+
+    def clear_adapter(self, slot: int) -> None:
+        """``mi_engine_clear_adapter``: free the adapter in ``slot``; a step on a row that still names it is refused."""
+        L.check(L.lib().mi_engine_clear_adapter(self._h, int(slot)))
 
     def invalidate_prefix_caches(self) -> None:
         """K / V computed with other weights must not be reused: forget the published prefixes of every paged cache

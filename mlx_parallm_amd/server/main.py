@@ -98,6 +98,9 @@ class ServerConfig:
     kv_blocks: Optional[int] = None
     prefix_cache: bool = True
     fork_choices: bool = False                    # the n choices of a request share one prompt prefill (KV rows are forked)
+    # continuous scheduler: name -> adapter directory.  Every adapter is resident in a slot of the engine's per-request table;
+    # a request whose `model` is such a name runs on it, in the same steps as everybody else.  Not together with lora_path.
+    lora_modules: Optional[Dict[str, str]] = None
 
     @classmethod
     def from_env(cls, base: Optional["ServerConfig"] = None) -> "ServerConfig":
@@ -193,6 +196,7 @@ class StreamQueuedChat:
 
 
 _DONE = "__DONE__"
+MAX_LORA_MODULES = 16              # MI_MAX_ADAPTERS (mi355_decode.h)
 
 
 class ServerState:
@@ -207,6 +211,7 @@ class ServerState:
         self.model_id: Optional[str] = None
         self.scheduler = None              # ReplicaPool of ContinuousSchedulers when config.scheduler == "continuous"
         self.extra_replicas: List[Any] = []   # models on the 2nd .. nth device (config.devices)
+        self.adapters: Dict[str, int] = {}    # config.lora_modules: name -> slot of the engines' adapter tables
 
 
 # ------------------------------------------------------------------------------------------
@@ -753,6 +758,29 @@ def _load_initial_model(state: ServerState) -> None:
         log.error("failed to load %s: %s", rec.id, e, exc_info=True)
 
 
+def load_lora_modules(state: ServerState, models: List[Any]) -> None:
+    """``config.lora_modules``: every adapter into a slot of every replica's table, and a registry record per name beside the
+    base model's (``/v1/models`` lists it; the record shares the base model's instances)."""
+    from ..utils import load_adapter_into
+
+    cfg = state.config
+    base = _loaded(state.model_id)
+    if not cfg.lora_modules or base is None:
+        return
+    if len(cfg.lora_modules) > MAX_LORA_MODULES:
+        raise ValueError(f"lora_modules: at most {MAX_LORA_MODULES} adapters are resident on one engine, got {len(cfg.lora_modules)}")
+    for slot, (name, path) in enumerate(cfg.lora_modules.items()):
+        if name in model_registry:
+            raise ValueError(f"lora_modules: the name {name!r} is taken by a model")
+        for m in models:
+            load_adapter_into(m, slot, path)
+        state.adapters[name] = slot
+        model_registry[name] = InternalModelRecord(id=name, path_or_hf_id=base.path_or_hf_id, status=ModelStatus.LOADED,
+                                                   model_type="causal_lm", adapter_path=path,
+                                                   model_instance=base.model_instance, tokenizer_instance=base.tokenizer_instance)
+        log.info("adapter %s (%s) in slot %d", name, path, slot)
+
+
 def register_model(state: ServerState, model_id: str, model, tokenizer, adapter_path: Optional[str] = None) -> None:
     """Put an already-built model into the registry (tests, embedding the server in another process)."""
     model_registry[model_id] = InternalModelRecord(id=model_id, path_or_hf_id=model_id, status=ModelStatus.LOADED,
@@ -774,6 +802,8 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
         except Exception:          # pragma: no cover
             cli_args = None
         config = ServerConfig.from_env(cli_args)
+    if config.lora_path and config.lora_modules:
+        raise ValueError("lora_path (one adapter for every request) and lora_modules (an adapter per request) cannot be combined")
     state = ServerState(config)
 
     @asynccontextmanager
@@ -800,6 +830,8 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             if config.scheduler != "continuous":
                 log.info("%d devices: using the continuous scheduler", len(config.devices))
                 config.scheduler = "continuous"
+        if rec is not None and config.lora_modules:
+            await asyncio.get_running_loop().run_in_executor(None, load_lora_modules, state, [rec.model_instance] + state.extra_replicas)
         if config.scheduler == "continuous" and rec is not None:
             # admit-on-step over the engine's row-subset steps (server/scheduler.py); every generation route
             # goes through it, the windowed workers are not started
@@ -825,6 +857,9 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             if state.scheduler is not None:
                 await asyncio.get_running_loop().run_in_executor(None, state.scheduler.stop)
                 state.scheduler = None
+            for name in state.adapters:
+                model_registry.pop(name, None)
+            state.adapters = {}
 
     app = FastAPI(title="mlx_parallm_amd Server", version="0.1.0", lifespan=lifespan,
                   description="Batched generation server for the MI355X decode engine (mlx_parallm-compatible API).")
@@ -838,6 +873,13 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             raise HTTPException(status_code=not_ready_status,
                                 detail=f"Model '{model_name}' is not currently loaded or ready. Status: {rec.status.value}")
         return rec
+
+    def no_adapter(model_name: str, what: str) -> None:
+        """A LoRA module is applied per row inside the continuous scheduler's steps; every other path runs the base model."""
+        if model_name in state.adapters:
+            raise HTTPException(status_code=400, detail=(
+                f"Model '{model_name}' is a LoRA module: it is served by the continuous scheduler only "
+                f"(--scheduler continuous), not by {what}."))
 
     async def wait_for(qr: QueuedRequest, what: str):
         try:
@@ -879,6 +921,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             if state.scheduler is not None and request.logprobs and request.echo is not True and not request.stream:
                 # n choices with the sampled tokens' logprobs: rows of the shared steps, nobody waits for them
                 return await _scheduled_response(state, request, tok, request.model)
+            no_adapter(request.model, "the exclusive logprobs / echo path")
             async with state.engine_lock:
                 try:
                     return await loop.run_in_executor(None, _exclusive(state, completion_with_logprobs), rec.model_instance,
@@ -892,9 +935,11 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             if state.scheduler is not None:
                 _request_controls(request, tok)          # (400 while the status line can still say so)
                 return StreamingResponse(_scheduled_completion_stream(state, request, tok), media_type="text/event-stream")
+            no_adapter(request.model, "the exclusive streaming path")
             return StreamingResponse(_completion_stream(state, request, rec), media_type="text/event-stream")
         if state.scheduler is not None:
             return await _scheduled_response(state, request, tok, request.model)
+        no_adapter(request.model, "the windowed batch worker")
         qr = QueuedRequest(request)
         await state.request_queue.put(qr)
         return await wait_for(qr, "request")
@@ -902,6 +947,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
     @app.post("/v1/perplexity", response_model=PerplexityResponse, tags=["Analysis"])
     async def compute_perplexity(request: PerplexityRequest):
         rec = ready_record(request.model, 409)
+        no_adapter(request.model, "the exclusive perplexity path")
         async with state.engine_lock:
             return await asyncio.get_running_loop().run_in_executor(
                 None, _exclusive(state, perplexity_of), rec.model_instance, rec.tokenizer_instance, request.model, request.text)
@@ -917,6 +963,7 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
                 _request_controls(request, tok)          # (400 while the status line can still say so)
                 return StreamingResponse(_scheduled_chat_stream(state, request, tok), media_type="text/event-stream")
             return await _scheduled_response(state, request, tok, request.model)
+        no_adapter(request.model, "the windowed workers")
         if request.stream:
             queued = StreamQueuedChat(request)
             await state.stream_queue.put(queued)
@@ -998,13 +1045,15 @@ def _submit(state: ServerState, tok: TokenizerWrapper, text: str, req: AnyReques
             result = ("".join(parts), len(ids), len(seq.generated), reason)
             loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(result))
 
+    adapters = getattr(state, "adapters", None) or {}      # a LoRA module's name -> its slot; any other model id: the base model
     try:
         seed = getattr(req, "seed", None)
         seq = state.scheduler.submit(ids, max_tokens, temp, top_p, sink, top_k=int(getattr(req, "top_k", 0) or 0),
                                      min_p=float(getattr(req, "min_p", 0.0) or 0.0),
                                      seed=None if seed is None else int(seed) + choice, logit_bias=bias, stop=stop,
                                      **({"logprobs": lp_k, "logprobs_at_temperature": lp_at_t} if lp_k > 0 else {}),
-                                     **({"group": group} if group is not None else {}))
+                                     **({"group": group} if group is not None else {}),
+                                     **({"adapter": adapters[req.model]} if getattr(req, "model", None) in adapters else {}))
     except ValueError as e:
         raise HTTPException(status_code=400, detail=str(e))
     return fut, len(ids), seq

@@ -18,6 +18,9 @@ for -- a request does not wait for the running batch to finish -- and does it on
     at admission next to the bias (``KVCache.set_row_logprobs``) and cleared with the row; the sequence collects, per sampled
     token, the id, its logprob and its top list from the results of the shared steps, so such a request never takes the
     engine away from the others;
+  * a request's LoRA adapter (``submit(..., adapter=slot)``, a slot of ``Engine.set_adapter_lora``; -1 = the base model) is set
+    on its row at admission (``KVCache.set_row_adapter``), right after the reset and ahead of the fork and the prefix lookup --
+    K / V depend on it -- and goes with the row's reset; requests on different adapters share the steps;
   * with ``fork_choices`` the ``n`` choices of one request (``submit(..., group=new_group())``) share one prompt prefill: the
     first member prefills, the others wait for it at the head of the queue and then get its row's first ``P - 1`` tokens
     (``KVCache.fork_row``: full blocks shared, the tail copied) and run the last prompt token themselves -- ``P + (n - 1)``
@@ -54,6 +57,7 @@ Sink = Callable[["Sequence", Optional[str], Optional[str]], None]
 MAX_ROW_LOGIT_BIAS = 1024      # MI_MAX_ROW_LOGIT_BIAS (mi355_decode.h): entries of one request's logit_bias
 MAX_STOP_SEQUENCES = 4         # as the OpenAI API
 MAX_TOP_LOGPROBS = 20          # MI_MAX_TOP_LOGPROBS (mi355_decode.h)
+MAX_ADAPTERS = 16              # MI_MAX_ADAPTERS
 
 
 class StopMatcher:
@@ -151,8 +155,11 @@ class Sequence:
     def __init__(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, detok, *, top_k: int = 0,
                  min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
                  stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False,
-                 group: Optional[Group] = None):
+                 group: Optional[Group] = None, adapter: int = -1):
         self.group = group
+        if isinstance(adapter, bool) or not isinstance(adapter, (int, np.integer)) or not -1 <= int(adapter) < MAX_ADAPTERS:
+            raise ValueError(f"adapter must be a slot in [0, {MAX_ADAPTERS}) or -1 (none)")
+        self.adapter = int(adapter)        # slot of the engine's per-request adapter table, set on the sequence's cache row at admission
         if int(top_k) < 0:
             raise ValueError("top_k must be >= 0 (0 = off)")
         if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
@@ -287,10 +294,12 @@ class ContinuousScheduler:
     def submit(self, prompt_ids, max_tokens: int, temp: float, top_p: float, sink: Sink, *, top_k: int = 0,
                min_p: float = 0.0, seed: Optional[int] = None, logit_bias: Optional[Dict[int, float]] = None,
                stop: Optional[List[str]] = None, logprobs: int = 0, logprobs_at_temperature: bool = False,
-               group: Optional[Group] = None) -> Sequence:
+               group: Optional[Group] = None, adapter: int = -1) -> Sequence:
         seq = Sequence(prompt_ids, max_tokens, temp, top_p, sink, NaiveStreamingDetokenizer(self.tok._tokenizer),
                        top_k=top_k, min_p=min_p, seed=seed, logit_bias=logit_bias, stop=stop, logprobs=logprobs,
-                       logprobs_at_temperature=logprobs_at_temperature, group=group)
+                       logprobs_at_temperature=logprobs_at_temperature, group=group, adapter=adapter)
+        if seq.adapter >= 0 and not hasattr(self.kv, "set_row_adapter"):
+            raise ValueError("adapter: this KV cache has no per-row adapter (set_row_adapter)")
         if (seq.logprobs or seq.logprobs_at_temperature) and not hasattr(self.kv, "set_row_logprobs"):
             raise ValueError("logprobs: this KV cache has no per-row logprobs setting (set_row_logprobs)")
         if seq.logit_bias:
@@ -436,7 +445,7 @@ class ContinuousScheduler:
         if not self.fork_choices or seq.group is None or len(seq.prompt) < 2:
             return []
         return [s for s in self.slots if s is not None and s is not seq and s.group is seq.group and not s.finished
-                and not s.cancelled and np.array_equal(s.prompt, seq.prompt)]
+                and not s.cancelled and s.adapter == seq.adapter and np.array_equal(s.prompt, seq.prompt)]
 
     def _fork_donor(self, seq: Sequence) -> Optional[Sequence]:
         """A live member whose row already holds the first P - 1 prompt tokens (it may be decoding by now)."""
@@ -456,7 +465,9 @@ class ContinuousScheduler:
         if seq.max_tokens <= 0:
             self._finish(seq, "length")
             return
-        self.kv.reset_row(slot)                   # (also clears the bias of the row's previous occupant)
+        self.kv.reset_row(slot)                   # (also clears the bias and the adapter of the row's previous occupant)
+        if seq.adapter >= 0:                      # while the row is empty, ahead of the fork and of prefix_attach: K / V depend on it
+            self.kv.set_row_adapter(slot, seq.adapter)
         if seq.logit_bias:                        # ahead of the row's first sampling step: the prefill below, or the last chunk
             self.kv.set_row_logit_bias(slot, seq.logit_bias)
         if seq.logprobs or seq.logprobs_at_temperature:
@@ -547,6 +558,8 @@ class ContinuousScheduler:
                     self.kv.reset_row(i)       # (its logprobs setting goes with them)
                 elif s.logprobs or s.logprobs_at_temperature:
                     self.kv.set_row_logprobs(i, 0, False)     # a contiguous row is reset at its next admission: clear now
+                if not self.paged and s.adapter >= 0:
+                    self.kv.reset_row(i)       # (an adapter can only leave an empty row: the reset clears it)
 
     def _drop_cancelled_pending(self) -> None:
         with self.cv:

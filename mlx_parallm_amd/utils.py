@@ -426,12 +426,8 @@ def load_model(model_path: Path, lazy: bool = False, model_config: dict = {}, *,
     return model
 
 
-def load_adapters(model, adapter_path: str):
-    """mlx-lm ``load_adapters`` as the reference uses it (utils.py:742-744): read
-    ``adapter_config.json`` (``fine_tune_type``, ``num_layers``, ``lora_parameters``; written by
-    rl_training/lora_init.py:140-153), adapt the LAST ``num_layers`` blocks, load
-    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``).  ``lora_parameters.keys`` may name any of the
-    seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the config's order."""
+def _read_adapter(n_layers: int, adapter_path: str):
+    """The (layer, key, lora_a, lora_b, scale) entries of an adapter directory, in the order ``load_adapters`` applies them."""
     from safetensors.torch import load_file
 
     adapter_path = Path(adapter_path)
@@ -444,14 +440,34 @@ def load_adapters(model, adapter_path: str):
     lp = cfg["lora_parameters"]
     keys = lp.get("keys") or ["self_attn.q_proj", "self_attn.v_proj"]
     weights = load_file(str(adapter_path / "adapters.safetensors"))
-    n_layers = len(model.layers)
     for i in range(n_layers - int(cfg["num_layers"]), n_layers):
         for key in keys:
             base = f"model.layers.{i}.{key}"
             a, b = weights.get(base + ".lora_a"), weights.get(base + ".lora_b")
             if a is None or b is None:
                 continue
-            model.engine.set_lora(i, key, a, b, float(lp["scale"]))
+            yield i, key, a, b, float(lp["scale"])
+
+
+def load_adapters(model, adapter_path: str):
+    """mlx-lm ``load_adapters`` as the reference uses it (utils.py:742-744): read
+    ``adapter_config.json`` (``fine_tune_type``, ``num_layers``, ``lora_parameters``; written by
+    rl_training/lora_init.py:140-153), adapt the LAST ``num_layers`` blocks, load
+    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``).  ``lora_parameters.keys`` may name any of the
+    seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the config's order."""
+    for i, key, a, b, scale in _read_adapter(len(model.layers), adapter_path):
+        model.engine.set_lora(i, key, a, b, scale)
+    return model
+
+
+def load_adapter_into(model, slot: int, adapter_path: str):
+    """The same adapter directory into slot ``slot`` of the engine's per-request adapter table
+    (``Engine.set_adapter_lora``): rows that name the slot (``KVCache.set_row_adapter``) run it, the others do not.  Whatever
+    the slot held before is cleared first, so the slot ends up holding exactly this adapter."""
+    entries = list(_read_adapter(len(model.layers), adapter_path))       # (a bad directory raises before the slot is touched)
+    model.engine.clear_adapter(slot)
+    for i, key, a, b, scale in entries:
+        model.engine.set_adapter_lora(slot, i, key, a, b, scale)
     return model
 
 
