@@ -158,6 +158,10 @@ int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const
  * (the caller passes them in checkpoint order, also on a hot-swap).  May be called on a finalized, live engine: a projection
  * that is already adapted is hot-swapped, a new one is added; the outputs do not depend on the order in which the
  * projections arrived.  A refused call changes nothing.
+ * The engine-wide adapter is a private entry of the per-request adapters' table (below) that every token row of every step
+ * runs, whatever mi_kv_set_row_adapter says: the same launches, the same bits as a batch whose rows all name one slot that
+ * holds these factors.  No slot number reaches it (mi_engine_clear_adapter, mi_kv_set_row_adapter), and the cache rows stay
+ * on "no adapter": prefix keys and forks are those of an engine without adapters.
  * MI_ARCH_PHI3: proj is "self_attn.qkv_proj", "self_attn.o_proj", "mlp.gate_up_proj" or "mlp.down_proj", the names an
  * adapter file of that family carries.  For the two fused ones A (K, r) is shared and B (r, N) is cut by columns into the
  * parts: bit for bit what one call per part with its column slice gives on an engine with split projections. */
@@ -173,7 +177,7 @@ int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A,
  * finalized, live engine: an entry that exists is hot-swapped (the stream is drained first).  A refused call changes nothing.
  * mi_engine_clear_adapter: frees every entry of the slot; the slot is empty again.
  * Arithmetic of an adapted row: y = T(T(acc [+ b]) + T(scale (x A) B)), then the residual h + y where the projection has one --
- * the value mi_engine_set_lora gives.  The term runs as two small launches around the base linear ("Per-request
+ * the value, and the code, of mi_engine_set_lora.  The term runs as two small launches around the base linear ("Per-request
  * adapters"); a step in which no row names an adapter runs exactly the launches of an engine without adapters.
  * The table and the engine-wide adapter of mi_engine_set_lora exclude each other: whichever comes second is
  * MI_ERR_UNSUPPORTED.  A step one of whose rows names an empty slot is MI_ERR_INVALID before anything is launched.

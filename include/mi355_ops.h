@@ -142,7 +142,7 @@ int mi_op_gemm_prefill_f32(const mi_op_linear* w, const mi_op_gemv_args* a, int 
  * norm_w (float32 [K], nn.RMSNorm: llama.py:187,189) is not NULL -> out[rows][terms x K] bf16 = [hi | mid | lo] (terms 3) or
  * [hi | mid] (terms 2) with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): hi + mid + lo == x exactly. */
 int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, int rows, int K, int terms, void* out);
-/* SwiGLU over stored rows (lora.hip): x[M][ldx] holds gate at column n and up at column I + n (the plain-store output of a
+/* SwiGLU over stored rows (lora_rows.hip): x[M][ldx] holds gate at column n and up at column I + n (the plain-store output of a
  * gate|up linear -- what the engine runs when mlp.gate_proj / mlp.up_proj carry a LoRA adapter, whose term must be added before
  * the activation); out[m][n] = T(T(g * T(sigmoid(g))) * u), the rounding points of nn.silu(gate) * up in the activation dtype
  * (llama.py:165), as MI_EPI_SWIGLU (the exp of the sigmoid is taken in float64).  act = MI_F32 / MI_BF16 / MI_F16 storage of x and out, rnd = MI_RND_* on top of float32

@@ -26,10 +26,9 @@ int ensure_workspace(mi_engine* e, size_t rows, size_t logit_rows, int B) {
     MI_HIP(hipStreamSynchronize(e->stream));
     const size_t es = 4;  // sized for float32 activations (the widest mode)
     const size_t nqkv = (size_t)(d.num_heads + 2 * d.num_kv_heads) * d.head_dim, qd = (size_t)d.num_heads * d.head_dim;
-    const struct { void** p; size_t bytes; } bufs[7] = {
+    const struct { void** p; size_t bytes; } bufs[5] = {
         {&e->h, rows * d.hidden_size * es}, {&e->qkv, rows * nqkv * es}, {&e->q, rows * qd * es}, {&e->attn, rows * qd * es},
-        {&e->act, rows * (size_t)d.intermediate_size * es}, {(void**)&e->lora_t, rows * 2 * 64 * sizeof(float)},
-        {(void**)&e->lora_t3, rows * 64 * sizeof(float)}};
+        {&e->act, rows * (size_t)d.intermediate_size * es}};
     e->ws_rows = 0;
     for (const auto& b : bufs) { hipFree(*b.p); *b.p = nullptr; }
     for (const auto& b : bufs) MI_HIP(hipMalloc(b.p, b.bytes));
@@ -133,10 +132,13 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
         return fail(MI_ERR_INVALID, std::string(what) + ": KV capacity / max_positions exceeded (call mi_kv_reserve)");
     n += g.B; R += (size_t)g.B * g.L;
   }
-  // per-request adapters: the slot of every token row, from the cache rows and the groups' lengths.  A step none of whose
-  // rows names an adapter (by_row stays false) runs the launches of an engine without adapters, whatever is resident.
-  bool by_row = false;
+  // adapters: the table column of every token row.  The engine-wide adapter: its private column for every row (the cache rows
+  // name nothing and keep -1, so prefix chains and forks are those of an engine without adapters).  Per-request adapters:
+  // the slot of the row's cache row.  A step none of whose rows names an adapter (by_row stays false) runs the launches of
+  // an engine without adapters, whatever is resident.
+  bool by_row = e->engine_lora;
   std::vector<int32_t> tok_adapter;
+  if (by_row) tok_adapter.assign(R, LORA_ENGINE_COL);
   for (const AttnGroup& g : groups)
     for (int b = 0; b < g.B; ++b) {
       const int a = kv->row_adapter[row_of(g, b)];
@@ -152,12 +154,10 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
   if (by_row) {
     MI_TRY(grow(st, &e->d_row_adapter, &e->d_row_adapter_cap, R * sizeof(int32_t)));
     MI_TRY(grow(st, &e->lora_rt, &e->lora_rt_cap, R * LORA_ROWS_T_LD * sizeof(float)));
-    MI_TRY(grow(st, &e->ys, &e->ys_cap, R * (size_t)H * 4));                // (sized for float32 activations)
-    MI_TRY(grow(st, &e->gu, &e->gu_cap, R * 2 * (size_t)I * 4));
     MI_HIP(hipMemcpyAsync(e->d_row_adapter, tok_adapter.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
-  // the by-row form of linear f in this step: some row runs an adapter and some resident adapter covers f
-  auto rows_adapted = [&](const FusedLinear& f) { return by_row && f.adapters != nullptr && f.adapters->set > 0; };
+  // the adapted form of linear f in this step: some row runs an adapter and some resident adapter covers f
+  auto rows_adapt = [&](const FusedLinear& f) { return by_row && f.adapters != nullptr && f.adapters->set > 0; };
   auto rows_call = [&](const FusedLinear& f, int K, int rnd_) {
     LoraRowsCall rc;
     rc.table = f.adapters->d; rc.row_adapter = e->d_row_adapter; rc.n_parts = f.n_parts;
@@ -165,12 +165,13 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     rc.M = (int)R; rc.K = K; rc.act = act; rc.rnd = rnd_; rc.t = e->lora_rt;
     return rc;
   };
-  // o_proj / down_proj (c: the EPI_RESID call): with per-request adapters the linear stores y = T(acc [+ b]) to a scratch buffer
-  // and ONE launch adds the rows' terms and then the residual -- y' = T(y + T(scale z)) first, h = T(h + y') second (the
+  // o_proj / down_proj (c: the EPI_RESID call): an adapted one stores y = T(acc [+ b]) to a scratch buffer and ONE launch
+  // adds the rows' terms and then the residual -- y' = T(y + T(scale z)) first, h = T(h + y') second (the
   // reference's order; adding the term onto an already summed residual would round differently)
   auto resid_linear = [&](const FusedLinear& f, GemvCall c, int K, const char* prof) -> int {
-    if (!rows_adapted(f)) return gemv_rows(e, f, c, R, es, es, prof);
+    if (!rows_adapt(f)) return gemv_rows(e, f, c, R, es, es, prof);
     const LoraRowsCall rc = rows_call(f, K, c.rnd);
+    MI_TRY(grow(st, &e->ys, &e->ys_cap, R * (size_t)H * 4));                // (sized for float32 activations)
     { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, PRO_NONE, nullptr, 0.f, st)); }
     c.epi = EPI_STORE; c.out = e->ys; c.resid = nullptr;
     MI_TRY(gemv_rows(e, f, c, R, es, es, prof));
@@ -219,8 +220,8 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     { // input_layernorm + q|k|v projections (llama.py:187,93)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = rnd; c.pro = PRO_NORM;
       c.norm_w = w32 ? lw.in_norm32 : lw.in_norm; c.eps = d.rms_norm_eps; c.epi = EPI_STORE; c.out = e->qkv; c.ldo = nqkv;
-      if (rows_adapted(lw.qkv)) {
-        // per-request adapters: t = x A by row, the base linear stores q|k|v, the rows' terms are added to the stored output
+      if (rows_adapt(lw.qkv)) {
+        // adapted: t = x A by row, the base linear stores q|k|v, the rows' terms are added to the stored output
         const LoraRowsCall rc = rows_call(lw.qkv, H, rnd);
         { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, c.pro, c.norm_w, c.eps, st)); }
         MI_TRY(gemv_rows(e, lw.qkv, c, R, es, es, "gemv_qkv"));
@@ -273,21 +274,15 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
       c.eps = d.rms_norm_eps; c.epi = EPI_SWIGLU; c.out = e->act; c.ldo = I; c.pair_offset = I;
-      if (rows_adapted(lw.gate_up)) {
-        // per-request adapters: as below, with the rows' own terms added to the stored gate|up ahead of the SwiGLU
+      if (rows_adapt(lw.gate_up)) {
+        // adapted gate and / or up: no SwiGLU epilogue carries the LoRA term, so the linear stores gate|up, the rows' terms
+        // are added to the stored rows and a row-wise kernel applies SwiGLU to them
         const LoraRowsCall rc = rows_call(lw.gate_up, H, c.rnd);
+        MI_TRY(grow(st, &e->gu, &e->gu_cap, R * 2 * (size_t)I * 4));      // (sized for float32 activations)
         { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_down_by_row(rc, c.x, c.ldx, c.pro, c.norm_w, c.eps, st)); }
         c.epi = EPI_STORE; c.out = e->gu; c.ldo = 2 * I; c.pair_offset = 0;
         MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up"));
         { Prof pr(e, "lora_rows"); MI_TRY(launch_lora_up_add_by_row(rc, e->gu, 2 * I, nullptr, 0, st)); }
-        Prof pr(e, "swiglu_rows");
-        MI_TRY(launch_swiglu_rows(e->gu, 2 * I, e->act, I, (int)R, I, act, c.rnd, st));
-      } else if (adapted(lw.gate_up.W)) {
-        // adapted gate and / or up: no SwiGLU epilogue carries the LoRA term, so the linear stores gate|up (plain store:
-        // every kernel family adds the two ranges there) and a row-wise kernel applies SwiGLU to the stored rows
-        MI_TRY(grow(st, &e->gu, &e->gu_cap, R * 2 * (size_t)I * 4));      // (sized for float32 activations)
-        c.epi = EPI_STORE; c.out = e->gu; c.ldo = 2 * I; c.pair_offset = 0;
-        MI_TRY(gemv_rows(e, lw.gate_up, c, R, es, es, "gemv_gate_up"));
         Prof pr(e, "swiglu_rows");
         MI_TRY(launch_swiglu_rows(e->gu, 2 * I, e->act, I, (int)R, I, act, c.rnd, st));
       } else {
@@ -527,7 +522,7 @@ void mi_engine_destroy(mi_engine* e) {
   hipFree(e->final_norm32); hipFree(e->xn); hipFree(e->xs); hipFree(e->gk_ws);
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
-  hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->lora_t); hipFree(e->lora_t3); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
+  hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
   hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch);
   hipFree(e->d_row_adapter); hipFree(e->lora_rt); hipFree(e->ys);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);

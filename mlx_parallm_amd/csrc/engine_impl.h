@@ -22,15 +22,16 @@
 
 namespace mi {
 
-inline bool adapted(const LinearW& W) { return W.lora_b[0] != nullptr || W.lora_b[1] != nullptr; }   // LoRA on a row range
-
-// The per-request adapters of one fused matrix (mi_engine_set_adapter_lora): the device table [part][MI_MAX_ADAPTERS] that
-// lora_rows.hip reads, its host mirror (which owns the factors) and the number of entries that hold factors.  Allocated by
-// the first adapter that covers the matrix; a matrix without one keeps its fused launches in every step.
+// The adapters of one fused matrix: the device table [part][LORA_TABLE_COLS] that lora_rows.hip reads, its host mirror (which
+// owns the factors) and the number of entries that hold factors.  Columns 0 .. MI_MAX_ADAPTERS - 1 are the per-request slots
+// (mi_engine_set_adapter_lora); column LORA_ENGINE_COL is the engine-wide adapter (mi_engine_set_lora), which no public slot
+// number reaches.  Allocated by the first adapter that covers the matrix; a matrix without one keeps its fused launches in
+// every step.
 struct AdapterTable {
-  AdapterPart h[3][MI_MAX_ADAPTERS];
+  AdapterPart h[3][LORA_TABLE_COLS];
   AdapterPart* d = nullptr;
   int set = 0;
+  bool engine_wide() const { return h[0][LORA_ENGINE_COL].a || h[1][LORA_ENGINE_COL].a || h[2][LORA_ENGINE_COL].a; }
 };
 
 struct FusedLinear {
@@ -48,13 +49,6 @@ struct FusedLinear {
   void* w_hilo = nullptr;        // f16 dense weights in the float32-activation (PagedKVCache) mode: [hi | lo] bf16 copy
   void* w_gu8 = nullptr;         // dense 16-bit gate|up: row-interleaved copy for the decode GEMV (EPI_SWIGLU_GU8)
   bool hilo_failed = false, gu8_failed = false;
-  float* lora_a[2] = {nullptr, nullptr};
-  float* lora_b[2] = {nullptr, nullptr};
-  // q|k|v with q, k AND v adapted: the range that does not fit LinearW's two (always k: the fewest columns) lives here,
-  // outside the streaming kernels' parameter blocks.  launch_lora_down3 makes its t with the other two, launch_lora_up_add3
-  // adds its term to the stored output behind the main launch.  Set only while both slots of W are taken, so adapted(W)
-  // stays the router's one "is this matrix adapted" test.
-  LoraRange lora3;
   AdapterTable* adapters = nullptr;      // (a pointer: the [hi | lo] view of gemv_rows copies this struct)
   int seen_w[3] = {0, 0, 0}, seen_s[3] = {0, 0, 0}, seen_b[3] = {0, 0, 0};
   float* bias = nullptr;         // [rows of all parts] float32: the parts' `.bias` tensors (attention_bias / mlp_bias), as loaded
@@ -115,12 +109,11 @@ struct mi_engine {
   size_t ws_rows = 0;
   void* h = nullptr; void* qkv = nullptr; void* q = nullptr; void* attn = nullptr; void* act = nullptr;
   float* logits = nullptr; size_t logits_cap = 0;
-  float* lora_t = nullptr;
-  float* lora_t3 = nullptr;                               // [rows][64]: t of a q|k|v matrix's third range (FusedLinear::lora3)
   void* gu = nullptr; size_t gu_cap = 0;                  // [rows][2 I]: the stored output of an ADAPTED gate|up (swiglu_rows_kernel reads it)
-  // ---- per-request adapters: slot s is resident while adapter_parts[s] > 0 ((layer, projection part) entries that hold
+  // ---- adapters: per-request slot s is resident while adapter_parts[s] > 0 ((layer, projection part) entries that hold
   // factors); adapter_gen[s] counts the changes of the slot (the prefix cache's hash seed: K/V depend on the adapter).
-  // engine_lora: mi_engine_set_lora has adapted this engine -- the two forms exclude each other.
+  // engine_lora: mi_engine_set_lora has adapted this engine -- every token row of every step runs column LORA_ENGINE_COL of
+  // the tables, whatever kv->row_adapter says; the two forms exclude each other.
   int adapter_parts[MI_MAX_ADAPTERS] = {};
   uint32_t adapter_gen[MI_MAX_ADAPTERS] = {};
   bool engine_lora = false;
@@ -141,7 +134,6 @@ struct mi_engine {
   int32_t* d_topk_ids = nullptr; float* d_topk_lp = nullptr;
   int32_t* d_bias_ids = nullptr; float* d_bias_vals = nullptr;
   int maxB = 0;
-  int max_lora_rank = 0;
   mi::Slot slots[mi::NSLOT];
   int64_t next_ticket = 0;
   uint64_t step_counter = 0;

@@ -30,7 +30,8 @@ bool ensure_hilo(mi_engine* e, FusedLinear& f) {
 }
 static bool gu8_wanted(const mi_engine* e, const FusedLinear& f, int pair_offset) {
   if (f.W.bias != nullptr) return false;        // the interleaved copy's epilogues carry no bias: the paired-tile SwiGLU kernels run
-  return e->opt_gu8 && !e->opt_force_v1 && !adapted(f.W) && f.W.layout == 1 && (f.W.wk == WK_BF16 || f.W.wk == WK_F16) &&
+  if (f.adapters != nullptr && f.adapters->engine_wide()) return false;     // every step stores gate|up for the LoRA term: the copy would never be read
+  return e->opt_gu8 && !e->opt_force_v1 && f.W.layout == 1 && (f.W.wk == WK_BF16 || f.W.wk == WK_F16) &&
          f.W.N == 2 * pair_offset && pair_offset % 16 == 0;
 }
 bool ensure_gu8(mi_engine* e, FusedLinear& f, int pair_offset) {
@@ -111,22 +112,8 @@ int norm_into_xn(mi_engine* e, GemvCall& c, size_t rows, int K, int rnd) {
   return MI_OK;
 }
 
-// t = x A for the adapted ranges of f0 on the call's c.M rows, rows [r, r + c.M) of the engine's t buffers: ONE launch,
-// whether the matrix has one, two (lora_down_kernel) or three ranges (lora_down3_kernel)
-int lora_down_rows(mi_engine* e, const FusedLinear& f0, const GemvCall& c, size_t r) {
-  if (f0.lora3.b != nullptr)
-    return launch_lora_down3(f0.W, f0.lora3, c, e->lora_t + r * 128, 128, e->lora_t3 + r * 64, 64, e->stream);
-  return launch_lora_down(f0.W, c, e->lora_t + r * 128, 128, e->stream);
-}
-// the third range's term, added to the `rows` stored rows of c.out behind a launch whose epilogue added the other two
-int lora_third_up_add(mi_engine* e, const FusedLinear& f0, GemvCall c, size_t rows) {
-  if (f0.lora3.b == nullptr) return MI_OK;
-  c.M = (int)rows;
-  return launch_lora_up_add3(nullptr, f0.lora3, c, e->lora_t, 128, e->lora_t3, 64, e->stream);
-}
-
 // One call of gemv_rows as its routes see it.  f: the matrix the matmul kernels stream (f0 itself, or its [hi | lo] view);
-// f0: the linear as loaded (true K, LoRA); c: a route works on a copy; left: the hand-over the launch before this one left
+// f0: the linear as loaded (true K); c: a route works on a copy; left: the hand-over the launch before this one left
 struct Lin {
   mi_engine* e; const FusedLinear& f; const FusedLinear& f0; const GemvCall& c; size_t rows, es_in, es_out;
   const char* prof; const NormHandover& left; int* published;
@@ -149,7 +136,7 @@ int route_two_slabs(const Lin& a) {
         !gemm_skinny_supported(f.W, a.c, rows))) return NOT_TAKEN;
   const size_t half = (rows + 1) / 2;
   GemvCall probe = a.c; probe.pro = PRO_NONE;
-  if (!(gemm_skinny_supported(f.W, probe, half) && !adapted(f.W))) return NOT_TAKEN;
+  if (!gemm_skinny_supported(f.W, probe, half)) return NOT_TAKEN;
   Prof pr(e, a.prof);
   GemvCall c = a.c;
   if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, rows, a.KT(), c.rnd));
@@ -218,10 +205,6 @@ int route_skinny(const Lin& a) {
   // (float32 activations: the split-K kernel neither leaves nor takes the row statistics -- always the norm launch)
   const int take_ld = (c.act != MI_F32 && c.pro == PRO_NORM) ? gemm_skinny_handover_ld(f.W, c, rows) : 0;
   const bool handed = e->opt_norm_handover && take_ld > 0 && c.ldx == KT && a.left.matches(c.x, KT, take_ld);
-  if (adapted(f.W)) {                          // (normalises on its own when c.pro says so)
-    c.lora_t = e->lora_t; c.lora_t_ld = 128;
-    MI_TRY(lora_down_rows(e, f0, c, 0));
-  }
   // float32 activations without logical rounding (PagedKVCache mode after layer 0): the kernel applies the row scale
   // of the RMSNorm in its epilogue (gemm_skinny.hip "defer_norm") -- no norm launch, nothing waits for row statistics
   const bool defer = e->opt_defer_norm && c.pro == PRO_NORM && c.act == MI_F32 && c.rnd == RND_NONE && !handed;
@@ -229,9 +212,8 @@ int route_skinny(const Lin& a) {
   if (handed) { c.sq_in = e->d_sq; c.sq_parts = a.left.parts; }
   else if (c.pro == PRO_NORM && !defer && !q4_prep) MI_TRY(norm_into_xn(e, c, rows, KT, c.rnd));
   // consumer_combine: the offer is taken by the call that the publish-only instantiation covers (gemm_skinny.hip, CC) --
-  // <= 8 unrounded float32 rows with the RMSNorm deferred, a dense bf16 matrix as loaded, no LoRA, 2..8 K slices
-  if (a.published != nullptr && f.W.wk == WK_BF16 && c.kx == 0 && !adapted(f0.W) &&
-      f0.W.bias == nullptr && c.rnd == RND_NONE && defer && rows <= 8) {      // (a bias is added where slices are combined: the last arriver)
+  // <= 8 unrounded float32 rows with the RMSNorm deferred, a dense bf16 matrix as loaded, 2..8 K slices
+  if (a.published != nullptr && f.W.wk == WK_BF16 && c.kx == 0 && f0.W.bias == nullptr && c.rnd == RND_NONE && defer && rows <= 8) {      // (a bias is added where slices are combined: the last arriver)
     const int ks = gemm_skinny_ksplit(f.W, c, rows);
     if (ks >= 2 && ks <= 8) {
       MI_TRY(ensure_cc_pub(e, f.W.N));
@@ -248,15 +230,15 @@ int route_skinny(const Lin& a) {
   }
   MI_TRY(run_skinny(e, f.W, c, rows));
   if (produce) e->handover.record(c.resid, tgroups, f.W.N, leave_ld);
-  return lora_third_up_add(e, f0, c, rows);
+  return MI_OK;
 }
 
 // 5. prefill: one MFMA tile GEMM over all rows (the RMSNorm runs as its own row-wise kernel)
 int route_prefill_gemm(const Lin& a) {
-  mi_engine* e = a.e; const FusedLinear& f = a.f; const FusedLinear& f0 = a.f0; const size_t rows = a.rows; const int KT = a.KT();
+  mi_engine* e = a.e; const FusedLinear& f = a.f; const size_t rows = a.rows; const int KT = a.KT();
   if (!(e->opt_prefill_gemm && gemm_prefill_supported(f.W, a.c, rows))) return NOT_TAKEN;
   Prof pr(e, a.prof);
-  GemvCall c = a.c;                            // (the LoRA down-projection reads the caller's x and normalises on its own)
+  GemvCall c = a.c;
   if (c.act == MI_F32) {      // PagedKVCache mode: (norm +) exact three-way split of x, then the same tile GEMM over 3 K
     MI_TRY(grow(e->stream, &e->xs, &e->xs_cap, split3_bytes(rows, KT)));
     // dense bf16 weights: two terms (16+ mantissa bits of x, two walks of W; option "prefill_x_terms"); int4 / [hi | lo]
@@ -276,15 +258,7 @@ int route_prefill_gemm(const Lin& a) {
     e->gk_cap = (size_t)128 << 20;
     if (hipMalloc(&e->gk_ws, e->gk_cap) != hipSuccess) { e->gk_ws = nullptr; e->gk_cap = 0; }
   }
-  MI_TRY(launch_gemm_prefill(f.W, c, rows, e->stream, scratch, rows < 4096 ? e->gk_ws : nullptr, e->gk_cap));
-  if (adapted(f.W)) {                          // y = T(y + T(scale (x A) B)) on the adapted columns
-    GemvCall cl = c.act == MI_F32 ? a.c : c;
-    cl.M = (int)rows;
-    MI_TRY(lora_down_rows(e, f0, cl, 0));
-    if (f0.lora3.b != nullptr) MI_TRY(launch_lora_up_add3(&f0.W, f0.lora3, cl, e->lora_t, 128, e->lora_t3, 64, e->stream));   // (all three in one launch)
-    else MI_TRY(launch_lora_up_add(f0.W, cl, e->lora_t, 128, e->stream));
-  }
-  return MI_OK;
+  return launch_gemm_prefill(f.W, c, rows, e->stream, scratch, rows < 4096 ? e->gk_ws : nullptr, e->gk_cap);
 }
 
 // 6. PagedKVCache mode, more than 32 rows (its prefill): 32 rows per launch of the float32-activation streaming kernel
@@ -295,8 +269,6 @@ int route_f32_chunks(const Lin& a) {
   if (!(e->opt_skinny_gemm && a.c.act == MI_F32 && rows > 32 && gemm_skinny_supported(f.W, a.c, 32))) return NOT_TAKEN;
   Prof pr(e, a.prof);
   GemvCall c = a.c;
-  const bool lora32 = adapted(f.W);
-  if (lora32) { GemvCall cl = c; cl.M = (int)rows; MI_TRY(lora_down_rows(e, a.f0, cl, 0)); }
   if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, rows, a.KT(), c.rnd));
   // workspace for every chunk size that is launched below, before the first launch: full 32-row chunks and the tail, whose
   // plan (tile rows, K split) is made for ITS row count and can need more partial-tile space than the 32-row plan
@@ -305,10 +277,9 @@ int route_f32_chunks(const Lin& a) {
   if (const size_t tail = rows % 32) { GemvCall ct = c; ct.M = (int)tail; MI_TRY(skinny_ws_for(e, f.W, ct, tail)); }
   for (size_t r = 0; r < rows; r += 32) {
     GemvCall cc = row_slab(c, r, std::min<size_t>(32, rows - r), a.es_in, a.es_out);
-    if (lora32) { cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128; }
     MI_TRY(launch_gemm_skinny(f.W, cc, (size_t)cc.M, e->stream, e->sk_ws, e->sk_ctr));
   }
-  return lora_third_up_add(e, a.f0, a.c, rows);
+  return MI_OK;
 }
 
 // 7. the generic per-8 / per-16-row kernels read the matrix as loaded (an f16 model falls back to its f16 weights, exact VALU)
@@ -336,10 +307,6 @@ int route_generic(const Lin& a) {
                    ensure_gu8(e, const_cast<FusedLinear&>(f0), c.pair_offset);
   for (size_t r = 0; r < rows; r += step) {
     GemvCall cc = row_slab(c, r, std::min(step, rows - r), a.es_in, a.es_out);
-    if (adapted(f0.W)) {
-      cc.lora_t = e->lora_t + r * 128; cc.lora_t_ld = 128;
-      MI_TRY(lora_down_rows(e, f0, cc, r));
-    }
     if (gu8) {
       LinearW wv = f0.W;                       // (a view: the copy stays owned by f0)
       wv.w = f0.w_gu8;
@@ -349,7 +316,7 @@ int route_generic(const Lin& a) {
     }
     MI_TRY(launch_gemv(f0.W, cc, e->stream));
   }
-  return lora_third_up_add(e, f0, c, rows);
+  return MI_OK;
 }
 
 // the routes in the order they are asked; the first that does not decline runs the call
@@ -377,7 +344,7 @@ int gemv_rows(mi_engine* e, const FusedLinear& f0, GemvCall c, size_t rows, size
   // three-way bf16 split of x by bf16 weights, so an f16 matrix is used through its exact [hi | lo] bf16 copy (2 K
   // columns, x walked twice: GemvCall::kx) -- made by mi_engine_finalize (here only if the option was switched on later),
   // twice the matrix's bytes; without it (allocation failed) the exact VALU kernel reads the f16 matrix.  Everything that is
-  // about x (norms, LoRA down-projection, the split) keeps the true K of f0.
+  // about x (norms, the split) keeps the true K of f0.
   if (c.act == MI_F32 && hilo_wanted(e, f0) && ensure_hilo(e, const_cast<FusedLinear&>(f0))) {
     FusedLinear fh = f0;                       // (a view: the pointers stay owned by f0)
     fh.W.wk = WK_BF16; fh.W.w = f0.w_hilo; fh.W.K = 2 * f0.W.K;

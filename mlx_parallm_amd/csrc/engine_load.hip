@@ -206,8 +206,6 @@ bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* 
 
 void mi::free_linear(FusedLinear& f) {
   hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
-  for (int i = 0; i < 2; ++i) { hipFree(f.lora_a[i]); hipFree(f.lora_b[i]); }
-  hipFree(const_cast<float*>(f.lora3.a)); hipFree(const_cast<float*>(f.lora3.b));
   if (f.adapters != nullptr) {
     for (auto& part : f.adapters->h)
       for (AdapterPart& ap : part) { hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b)); }
@@ -266,56 +264,10 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
   return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
 }
 
-// one adapted range: part pj.part of pj.f, float32 factors A (K, rank) and B (rank, the part's rows)
-static int set_lora_part(mi_engine* e, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
-  const mi_model_desc& d = e->d;
-  FusedLinear* f = pj.f;
-  const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
-  int row0 = 0;
-  for (int i = 0; i < pj.part; ++i) row0 += f->part_rows[i];
-  // where the range goes: its own place when it is already adapted (hot-swap), else a free slot of LinearW, else -- q|k|v
-  // with both slots taken -- the third place beside it.  With all three adapted the third is ALWAYS k (a slot holding k
-  // hands it over), so that an engine computes the same bits whatever order the projections arrived in.
-  int slot = -1; bool third = false, move_k = false;
-  for (int i = 0; i < 2; ++i) if (f->lora_b[i] != nullptr && f->W.lora_row0[i] == row0) slot = i;   // hot-swap
-  if (slot < 0 && f->lora3.b != nullptr && f->lora3.row0 == row0) third = true;                      // hot-swap
-  if (slot < 0 && !third) for (int i = 0; i < 2; ++i) if (f->lora_b[i] == nullptr) { slot = i; break; }
-  if (slot < 0 && !third) {
-    if (f != &l.qkv || f->lora3.b != nullptr) return fail(MI_ERR_UNSUPPORTED, "no free place for another adapted range on this matrix");
-    if (row0 == QD) third = true;
-    else { slot = f->W.lora_row0[0] == QD ? 0 : 1; move_k = true; }
-  }
-  MI_HIP(hipStreamSynchronize(e->stream));
-  float* na = nullptr; float* nb = nullptr;
-  MI_HIP(hipMalloc(&na, (size_t)K * rank * sizeof(float)));
-  if (hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); hipFree(na); return fail(MI_ERR_RUNTIME, "LoRA: out of device memory"); }
-  int rc = copy_in(na, A, (size_t)K * rank * sizeof(float), on_device, e->stream);
-  if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
-  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
-  if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
-  if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
-  if (move_k) {           // k leaves its slot for the third place; the new range takes the slot
-    f->lora3.a = f->lora_a[slot]; f->lora3.b = f->lora_b[slot];
-    f->lora3.row0 = f->W.lora_row0[slot]; f->lora3.n = f->W.lora_n[slot]; f->lora3.rank = f->W.lora_rank[slot]; f->lora3.scale = f->W.lora_scale[slot];
-    f->lora_a[slot] = f->lora_b[slot] = nullptr;
-  }
-  if (third) {
-    hipFree(const_cast<float*>(f->lora3.a)); hipFree(const_cast<float*>(f->lora3.b));
-    f->lora3.a = na; f->lora3.b = nb; f->lora3.row0 = row0; f->lora3.n = n; f->lora3.rank = rank; f->lora3.scale = scale;
-  } else {
-    hipFree(f->lora_a[slot]); hipFree(f->lora_b[slot]);
-    f->lora_a[slot] = na; f->lora_b[slot] = nb;
-    f->W.lora_a[slot] = na; f->W.lora_b[slot] = nb;
-    f->W.lora_row0[slot] = row0; f->W.lora_n[slot] = n; f->W.lora_rank[slot] = rank; f->W.lora_scale[slot] = scale;
-  }
-  // an adapted gate|up never runs a SwiGLU epilogue again: its row-interleaved copy (ensure_gu8) is dead weight
-  if (f == &l.gate_up && f->w_gu8 != nullptr) { hipFree(f->w_gu8); f->w_gu8 = nullptr; }
-  return MI_OK;
-}
-
-// one adapted range of adapter slot `adapter`: entry [pj.part][adapter] of the matrix's table (lora_rows.h), hot-swapped when
-// it exists.  The stream is drained first and the table entry is written with a blocking copy: no step is in flight.
-static int set_adapter_part(mi_engine* e, int adapter, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
+// one adapted range of table column `col` (a per-request slot, or LORA_ENGINE_COL: the engine-wide adapter): entry
+// [pj.part][col] of the matrix's table (lora_rows.h), hot-swapped when it exists.  The stream is drained first and the table
+// entry is written with a blocking copy: no step is in flight.
+static int set_adapter_part(mi_engine* e, int col, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
   const mi_model_desc& d = e->d;
   FusedLinear* f = pj.f;
   const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
@@ -336,19 +288,27 @@ static int set_adapter_part(mi_engine* e, int adapter, LayerW& l, const Proj& pj
   if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
   // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
   if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
-  AdapterPart& slot = f->adapters->h[pj.part][adapter];
+  AdapterPart& slot = f->adapters->h[pj.part][col];
   const AdapterPart fresh{na, nb, rank, scale};
-  if (rc == MI_OK && hipMemcpy(f->adapters->d + pj.part * MI_MAX_ADAPTERS + adapter, &fresh, sizeof(fresh), hipMemcpyHostToDevice) != hipSuccess)
+  if (rc == MI_OK && hipMemcpy(f->adapters->d + pj.part * LORA_TABLE_COLS + col, &fresh, sizeof(fresh), hipMemcpyHostToDevice) != hipSuccess)
     rc = fail(MI_ERR_RUNTIME, "adapter table: hipMemcpy failed");
   if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
-  if (slot.a == nullptr) { ++f->adapters->set; ++e->adapter_parts[adapter]; }
+  const bool was_empty = slot.a == nullptr;
   hipFree(const_cast<float*>(slot.a)); hipFree(const_cast<float*>(slot.b));
   slot = fresh;
-  ++e->adapter_gen[adapter];            // K / V made with the slot's earlier contents are unreachable from now on (kv_blocks.h)
+  f->adapters->set += was_empty;
+  if (col == LORA_ENGINE_COL) {
+    e->engine_lora = true;
+    // an adapted gate|up never runs a SwiGLU epilogue again: its row-interleaved copy (ensure_gu8) is dead weight
+    if (f == &l.gate_up && f->w_gu8 != nullptr) { hipFree(f->w_gu8); f->w_gu8 = nullptr; }
+  } else {
+    e->adapter_parts[col] += was_empty;
+    ++e->adapter_gen[col];              // K / V made with the slot's earlier contents are unreachable from now on (kv_blocks.h)
+  }
   return MI_OK;
 }
 
-// mi_engine_set_lora (adapter < 0: the engine-wide adapter) and mi_engine_set_adapter_lora (a slot of the table)
+// mi_engine_set_lora (adapter < 0: the engine-wide adapter, the table's private column) and mi_engine_set_adapter_lora (a slot)
 static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
                         int dtype, int on_device) {
   if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
@@ -369,10 +329,7 @@ static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, 
   Proj pj;
   if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the linears of a block only)");
   auto put = [&](const Proj& part, const void* a, const void* b) {
-    if (adapter >= 0) return set_adapter_part(e, adapter, l, part, a, b, rank, scale, on_device);
-    const int rc = set_lora_part(e, l, part, a, b, rank, scale, on_device);
-    if (rc == MI_OK) e->engine_lora = true;
-    return rc;
+    return set_adapter_part(e, adapter >= 0 ? adapter : LORA_ENGINE_COL, l, part, a, b, rank, scale, on_device);
   };
   if (pj.part >= 0) return put(pj, A, B);
   // MI_ARCH_PHI3, qkv_proj / gate_up_proj: A is shared, B (rank, N) is cut by columns into the parts -- what one call per

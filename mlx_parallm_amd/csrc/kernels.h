@@ -14,7 +14,9 @@ struct LinearW {
   int layout = 0;              // 0 = row-major (checkpoint order); 1 = tile-major (repack.hip); then
                                // `w` is the single tiled buffer (int4: scales/biases live inside it)
   // LoRA (mlx-lm LoRALinear): rows [lora_row0, lora_row0+lora_n) of this (fused) matrix get
-  // + scale * ((x A) B); A [K][r], B [r][lora_n] stored as float32.
+  // + scale * ((x A) B); A [K][r], B [r][lora_n] stored as float32.  DEAD since the engine-wide adapter runs through
+  // lora_rows.hip: nothing sets these members or GemvCall::lora_t, the epilogues' lora_term always returns at once (DESIGN §5,
+  // "One LoRA path": why they are still here).
   const float* lora_a[2] = {nullptr, nullptr};
   const float* lora_b[2] = {nullptr, nullptr};
   int lora_row0[2] = {0, 0}, lora_n[2] = {0, 0}, lora_rank[2] = {0, 0};
@@ -163,30 +165,11 @@ __host__ __device__ inline int tiled_q8_code_off(size_t row, int k) {   // withi
   return (((k >> 4) & 3) * 16 + (int)(row & 15)) * 16 + (k & 15);
 }
 __host__ __device__ inline int tiled_q8_scale_off(size_t row) { return 1024 + (int)(row & 15) * 2; }   // + 32 for the bias
-// t[m][slot][j] = round(sum_k x[m][k] A[k][j]) for the adapted ranges of W (same prologue as the gemv)
-int launch_lora_down(const LinearW& W, const GemvCall& c, float* t, int t_ld, hipStream_t st);
-// the LoRA term of the GEMV epilogues applied to an already stored c.out (EPI_STORE, c.M rows): after a tile GEMM
-int launch_lora_up_add(const LinearW& W, const GemvCall& c, const float* t, int t_ld, hipStream_t st);
 
-// ---- lora.hip: what carries LoRA beyond the two ranges of LinearW
-// a third adapted row range of a fused matrix (q|k|v with q, k and v all adapted); kept beside the LinearW, never inside it
-struct LoraRange {
-  const float* a = nullptr;    // [K][rank]
-  const float* b = nullptr;    // [rank][n]
-  int row0 = 0, n = 0, rank = 0;
-  float scale = 0.f;
-};
+// ---- lora_rows.hip (the LoRA launches themselves: lora_rows.h)
 // out[m][n] = T(T(g * T(sigmoid(g))) * u) with g = x[m][n], u = x[m][I + n]: the SwiGLU of a gate|up output stored by an
 // EPI_STORE launch (an adapted gate|up), rounding points of EPI_SWIGLU.  I % 8 == 0, ldx >= 2 I, ldo >= I, any M, one launch.
 int launch_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd, hipStream_t st);
-// launch_lora_down for a matrix with three ranges: t (slots 0 / 1 of W, as launch_lora_down lays them out) and t3 [M][t3_ld]
-// (r3) in one launch, x and the RMSNorm prologue read once per row; the same bits per column as launch_lora_down
-int launch_lora_down3(const LinearW& W, const LoraRange& r3, const GemvCall& c, float* t, int t_ld, float* t3, int t3_ld,
-                      hipStream_t st);
-// launch_lora_up_add on r3 alone (W == null: behind a launch whose epilogue added W's two ranges) or on W's ranges and r3
-// (behind the tile GEMM), one launch either way
-int launch_lora_up_add3(const LinearW* W, const LoraRange& r3, const GemvCall& c, const float* t, int t_ld, const float* t3,
-                        int t3_ld, hipStream_t st);
 
 struct EmbedCall {
   const int32_t* tokens;  // device [rows]

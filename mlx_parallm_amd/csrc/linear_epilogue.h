@@ -7,7 +7,8 @@
 //
 //   linear_value   R(acc), or with a bias R(acc + b) (dense) / R(R(acc) + b) (quantised)
 //   swiglu_value   R(R(g . R(sigmoid(g))) . u) from already rounded g and u
-//   lora_add       R(y + R(scale . z)), one adapted range; lora_term: both ranges of EpiTerms on one output element
+//   lora_add       R(y + R(scale . z)), one adapted range (lora_rows.hip); lora_term: both ranges of EpiTerms on one output
+//                  element -- dead, EpiTerms::lora_t is always null (kernels.h, LinearW)
 //   quant_accumulate  acc += scale . d + bias . sum(x) on the four rows a lane holds (the quantised kernels' inner step)
 //
 // Not here: the residual add h <- R(h0 + y).  It is one expression and is tied to each kernel's own prefetch of h.
@@ -20,7 +21,7 @@
 //                  select of R sat between the product and the add -- so the pragma changes no instruction.
 //   quant_accumulate  explicit fmaf, inner term first
 // Two sites that look alike and are NOT: the sigmoid.  The fused epilogues take expf in float32 and round the float32
-// (sigmoid_rounded); swiglu_rows_kernel (lora.hip) takes exp in float64 and rounds once (sigmoid_rounded_f64, the reason is
+// (sigmoid_rounded); swiglu_rows_kernel (lora_rows.hip) takes exp in float64 and rounds once (sigmoid_rounded_f64, the reason is
 // written there).  They differ on the few g whose float32 sigmoid lands on a midpoint of T's grid; both are kept, by name.
 #pragma once
 

@@ -1,12 +1,13 @@
-// lora_rows.h -- per-request LoRA adapters (mi_engine_set_adapter_lora / mi_kv_set_row_adapter): the rows of one step run
-// different adapters.  Launch interface of lora_rows.hip; beside kernels.h, so that no linear kernel's header changes.
+// lora_rows.h -- LoRA, the one path: every token row of a step names the adapter it runs.  Per-request adapters
+// (mi_engine_set_adapter_lora / mi_kv_set_row_adapter) give the rows of one step different adapters; the engine-wide adapter
+// (mi_engine_set_lora) is a private column of the same table that every row names.  Launch interface of lora_rows.hip; beside
+// kernels.h, so that no linear kernel's header changes.
 //
-// Every fused matrix of a block that some resident adapter covers owns a device table [part][MI_MAX_ADAPTERS] of AdapterPart;
+// Every fused matrix of a block that some resident adapter covers owns a device table [part][LORA_TABLE_COLS] of AdapterPart;
 // a step uploads row_adapter[token row] (-1: none) and each adapted linear runs
 //   launch_lora_down_by_row    t[m][part][0..rank) = x_m A of the row's adapter (x and its RMSNorm staged once per row)
 //   the base linear            plain store, no LoRA term
 //   launch_lora_up_add_by_row  y[m][row0 + n] = R(y + R(scale . z)) per row, optionally followed by h[m][n] = R(h + y')
-// The arithmetic of an element is the single-adapter path's: lora_down3_kernel's summation order, lora_dot, lora_add.
 #pragma once
 #include "kernels.h"
 
@@ -20,10 +21,12 @@ struct AdapterPart {
 };
 
 constexpr int LORA_ROWS_T_LD = 3 * 64;     // floats of t per token row: [part][64]
+constexpr int LORA_ENGINE_COL = MI_MAX_ADAPTERS;       // the engine-wide adapter's column, behind the public slots
+constexpr int LORA_TABLE_COLS = MI_MAX_ADAPTERS + 1;   // columns (adapters) of a table row
 
 struct LoraRowsCall {
-  const AdapterPart* table = nullptr;      // device [n_parts][MI_MAX_ADAPTERS]
-  const int32_t* row_adapter = nullptr;    // device [M]: slot of every token row, -1 = none
+  const AdapterPart* table = nullptr;      // device [n_parts][LORA_TABLE_COLS]
+  const int32_t* row_adapter = nullptr;    // device [M]: table column of every token row, -1 = none
   int n_parts = 0;
   int row0[3] = {0, 0, 0}, n[3] = {0, 0, 0};   // output columns [row0, row0 + n) of every part
   int M = 0, K = 0;

@@ -1,8 +1,12 @@
-// lora_rows.hip -- the LoRA term of a step whose rows run DIFFERENT adapters (lora_rows.h).  Unfused on purpose: the term
+// lora_rows.hip -- the LoRA term of a step, each row with the adapter it names (lora_rows.h).  Unfused on purpose: the term
 // lives outside the linear kernels' parameter blocks (a per-lane B pointer inside their epilogues would cost registers in
 // kernels that sit at an occupancy edge), behind a plain-store launch of the base linear.
 //   lora_down_by_row_kernel    t = x A of each row's own adapter, for every part of the fused matrix the adapter covers
 //   lora_up_add_by_row_kernel  y += T(scale (t B)) with the row's own B, rank and scale; with a residual operand also h += y'
+//   swiglu_rows_kernel         gate|up with an adapted range: the linear stores T(acc) to a [rows][2 I] buffer (EPI_STORE), the
+//                              up-add puts the terms on it and this kernel writes act = silu(gate) * up with the rounding
+//                              points of the fused epilogues (gemv_v1.hip EPI_SWIGLU: sig, g * sig, s * u, each rounded to
+//                              the activation dtype)
 #include <algorithm>
 #include <atomic>
 
@@ -24,9 +28,9 @@ struct DownRowsParams {
 };
 
 // t[m][part][j] = sum_k xin[m][k] * A[k][j], A = the part's factor of row m's adapter; xin = the (normalised) row, staged once
-// in LDS.  The sum of a column is lora_down3_kernel's (lora.hip): thread tid adds k = tid, tid + 256, ... in ascending order,
-// then the wave sum, then the four waves in order -- t is the bits the single-adapter path makes.  A row without an adapter
-// leaves at once; a part its adapter does not cover is skipped (both are uniform over the workgroup).
+// in LDS.  The sum of a column: thread tid adds k = tid, tid + 256, ... in ascending order, then the wave sum, then the four
+// waves in order.  A row without an adapter leaves at once; a part its adapter does not cover is skipped (both are uniform
+// over the workgroup).
 template <typename AT>
 __global__ __launch_bounds__(NTHR) void lora_down_by_row_kernel(DownRowsParams p) {
   extern __shared__ float xs[];      // [K]
@@ -35,7 +39,7 @@ __global__ __launch_bounds__(NTHR) void lora_down_by_row_kernel(DownRowsParams p
   __shared__ float red16[4][16];
   const int m = blockIdx.x;
   const int ad = p.row_adapter[m];
-  if (ad < 0 || ad >= MI_MAX_ADAPTERS) return;
+  if (ad < 0 || ad >= LORA_TABLE_COLS) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const AT* x = (const AT*)p.x + (size_t)m * p.ldx;
   for (int k = tid; k < p.K; k += NTHR) xs[k] = to_f32(x[k]);          // (each thread reads back only what it wrote)
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(NTHR) void lora_down_by_row_kernel(DownRowsParams p
   }
 #pragma unroll 1
   for (int r = 0; r < p.n_parts; ++r) {
-    const AdapterPart ap = p.table[r * MI_MAX_ADAPTERS + ad];
+    const AdapterPart ap = p.table[r * LORA_TABLE_COLS + ad];
     const float* A = ap.a;
     const int rk = min(ap.rank, 64);
     if (A == nullptr) continue;
@@ -107,7 +111,7 @@ struct UpRowsParams {
 };
 
 // Part blockIdx.y, columns [blockIdx.z * UP_COLS, + UP_COLS) of token row blockIdx.x, consecutive lanes on consecutive columns:
-//   y[m][row0 + n] = T(y + T(scale * sum_j t[m][part][j] B[j][n]))      lora_dot and lora_add, as lora_up_add3_kernel (lora.hip)
+//   y[m][row0 + n] = T(y + T(scale * sum_j t[m][part][j] B[j][n]))      lora_dot and lora_add (linear_epilogue.h)
 // with B, rank and scale of the row's own adapter.  resid != null: h[m][n] = T(h[m][n] + y') instead of the store to y (the
 // residual add of EPI_RESID, kernels.h), for EVERY row -- a row whose adapter does not cover the part adds the stored y.
 template <typename AT>
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(NTHR) void lora_up_add_by_row_kernel(UpRowsParams p
   if (n0 >= ln) return;
   const int ad = p.row_adapter[m];
   AdapterPart ap{};
-  if (ad >= 0 && ad < MI_MAX_ADAPTERS) ap = p.table[r * MI_MAX_ADAPTERS + ad];
+  if (ad >= 0 && ad < LORA_TABLE_COLS) ap = p.table[r * LORA_TABLE_COLS + ad];
   const float* lb = ap.b;
   if (lb == nullptr && resid == nullptr) return;
   const int rk = min(ap.rank, 64);
@@ -135,6 +139,35 @@ __global__ __launch_bounds__(NTHR) void lora_up_add_by_row_kernel(UpRowsParams p
     } else {
       *o = from_f32<AT>(v);
     }
+  }
+}
+
+// 16 bytes of activations; the alignment is the element's own, so any row stride is a legal address (global loads and
+// stores of gfx950 take unaligned dwordx4)
+template <typename AT>
+struct Vec16 {
+  static constexpr int N = 16 / (int)sizeof(AT);
+  typedef AT type __attribute__((ext_vector_type(16 / sizeof(AT)), aligned(sizeof(AT))));
+};
+
+// out[m][n] = T(T(g * T(sigmoid(g))) * u), g = x[m][n], u = x[m][I + n]  (llama.py:165; g and u are already T-rounded)
+template <typename AT>
+__global__ __launch_bounds__(NTHR) void swiglu_rows_kernel(const AT* x, int ldx, AT* out, int ldo, int M, int I, int rnd) {
+  constexpr int V = Vec16<AT>::N;
+  typedef typename Vec16<AT>::type vec;
+  const size_t per_row = (size_t)(I / V), total = (size_t)M * per_row;
+  for (size_t i = (size_t)blockIdx.x * NTHR + threadIdx.x; i < total; i += (size_t)gridDim.x * NTHR) {
+    const size_t m = i / per_row;
+    const int n = (int)(i - m * per_row) * V;
+    const AT* row = x + m * (size_t)ldx + n;
+    const vec gv = *(const vec*)row;
+    const vec uv = *(const vec*)(row + I);
+    vec ov;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      ov[j] = from_f32<AT>(swiglu_value<AT, true>(to_f32<AT>(gv[j]), to_f32<AT>(uv[j]), rnd));      // (the float64 sigmoid)
+    }
+    *(vec*)(out + m * (size_t)ldo + n) = ov;
   }
 }
 
@@ -189,6 +222,25 @@ int launch_lora_up_add_by_row(const LoraRowsCall& c, void* y, int ldy, void* res
     case MI_BF16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<bf16>, grid, block, 0, st, p, (bf16*)y, ldy, (bf16*)resid, ldr); break;
     case MI_F16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<f16>, grid, block, 0, st, p, (f16*)y, ldy, (f16*)resid, ldr); break;
     case MI_F32: hipLaunchKernelGGL(lora_up_add_by_row_kernel<float>, grid, block, 0, st, p, (float*)y, ldy, (float*)resid, ldr); break;
+  }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int launch_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd, hipStream_t st) {
+  if (x == nullptr || out == nullptr || M < 1 || I < 1 || (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16))
+    return fail(MI_ERR_INVALID, "swiglu_rows: bad argument");
+  if (act != MI_F32 && act != MI_BF16 && act != MI_F16) return fail(MI_ERR_INVALID, "swiglu_rows: bad activation dtype");
+  if (I % 8 != 0) return fail(MI_ERR_UNSUPPORTED, "swiglu_rows: the intermediate size must be a multiple of 8");
+  if ((long long)ldx < 2LL * I || ldo < I) return fail(MI_ERR_INVALID, "swiglu_rows: a row stride is shorter than its row");
+  const size_t es = dtype_size(act);
+  if ((uintptr_t)x % es != 0 || (uintptr_t)out % es != 0) return fail(MI_ERR_INVALID, "swiglu_rows: misaligned buffer");
+  const size_t pieces = (size_t)M * (size_t)(I / (int)(16 / es));
+  const unsigned grid = (unsigned)std::min<size_t>((pieces + NTHR - 1) / NTHR, (size_t)1 << 16);
+  switch (act) {
+    case MI_F32: hipLaunchKernelGGL(swiglu_rows_kernel<float>, dim3(grid), dim3(NTHR), 0, st, (const float*)x, ldx, (float*)out, ldo, M, I, rnd); break;
+    case MI_BF16: hipLaunchKernelGGL(swiglu_rows_kernel<bf16>, dim3(grid), dim3(NTHR), 0, st, (const bf16*)x, ldx, (bf16*)out, ldo, M, I, rnd); break;
+    case MI_F16: hipLaunchKernelGGL(swiglu_rows_kernel<f16>, dim3(grid), dim3(NTHR), 0, st, (const f16*)x, ldx, (f16*)out, ldo, M, I, rnd); break;
   }
   MI_HIP(hipGetLastError());
   return MI_OK;

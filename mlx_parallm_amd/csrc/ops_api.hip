@@ -270,7 +270,7 @@ int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, in
   return finish();
 }
 
-// swiglu_rows_kernel (lora.hip) on its own; the launch validates its arguments
+// swiglu_rows_kernel (lora_rows.hip) on its own; the launch validates its arguments
 int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd) {
   MI_TRY(ready());
   MI_TRY(launch_swiglu_rows(x, ldx, out, ldo, M, I, act, rnd, nullptr));

@@ -375,7 +375,9 @@ class Engine:
         (``self_attn.q_proj`` / ``k_proj`` / ``v_proj`` / ``o_proj``, ``mlp.gate_proj`` / ``up_proj`` / ``down_proj``), in any
         combination, also on a finalized engine; on a phi3 engine ``self_attn.qkv_proj`` / ``o_proj``, ``mlp.gate_up_proj`` /
         ``down_proj``, the fused ones with ``b`` cut by columns into q, k, v / gate, up.  ``a`` (K, r), ``b`` (r, N); converted to float32; r in 1..64.  Any other
-        name raises NotImplementedError and leaves the engine as it was.  Published prefixes are forgotten."""
+        name raises NotImplementedError and leaves the engine as it was.  Published prefixes are forgotten.  One mechanism
+        serves this and ``set_adapter_lora``: the engine-wide adapter is a private entry of the adapter table that every row
+        of every step runs (bit-equal to a batch whose rows all name a slot with these factors)."""
         import torch
         ta = torch.as_tensor(a).to(torch.float32).contiguous()
         tb = torch.as_tensor(b).to(torch.float32).contiguous()

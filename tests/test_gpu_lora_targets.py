@@ -269,6 +269,38 @@ def test_subsets(bank, name, keys, mode):
     model.engine.close()
 
 
+# ------------------------------------------------------------------------------------ a rank of its own per projection
+MIXED_RANKS = {"self_attn.q_proj": 1, "self_attn.k_proj": 5, "self_attn.v_proj": 64, "self_attn.o_proj": 16}
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_q_k_v_at_three_ranks_plus_o(tiny_dirs, tmp_path, mode):
+    """One engine-wide adapter whose q, k and v have ranks 1, 5 and 64 (the scalar and the vector walk of the down kernel in
+    one launch over the three parts of q|k|v) and whose o has rank 16: every part of the table carries its own rank."""
+    name = "qwen3_bf16"
+    path, cfg = tiny_dirs[name]
+    fac, dims, nl = {}, _dims(cfg), cfg["num_hidden_layers"]
+    for i in range(nl - NLAYERS, nl):
+        for ki, (key, rank) in enumerate(MIXED_RANKS.items()):
+            K, n = dims[key]
+            rng = np.random.default_rng([21, i, ki, rank])
+            fac[f"model.layers.{i}.{key}.lora_a"] = (rng.uniform(-1, 1, (K, rank)) / np.sqrt(K)).astype(np.float32)
+            fac[f"model.layers.{i}.{key}.lora_b"] = (rng.standard_normal((rank, n)) * 0.05).astype(np.float32)
+    full = ref_generate.load(path, adapter_path=_write(tmp_path / "full", fac, list(MIXED_RANKS)), max_pos=MAX_POS)
+    no_k = [k for k in MIXED_RANKS if k != "self_attn.k_proj"]
+    less = ref_generate.load(path, adapter_path=_write(tmp_path / "no_k", fac, no_k), max_pos=MAX_POS)
+    toks = _prompts(cfg, 3, 9, seed=15)
+    _, paged, tol = MODES[mode]
+    want = full(toks, cache=full.make_cache(3, paged=paged))[:, -1]
+    effect = float(np.abs(want - less(toks, cache=less.make_cache(3, paged=paged))[:, -1]).max())
+    print(f"{name} {mode}: effect of the rank-5 k_proj on the oracle's logits = {effect:.3f}")
+    assert effect >= 5 * tol, effect
+    model = utils.load_model(path, max_positions=MAX_POS)
+    utils.load_adapters(model, str(tmp_path / "full"))
+    _check(model, full, toks, mode, steps=3, what=f"{name} q r1 + k r5 + v r64 + o r16")
+    model.engine.close()
+
+
 # ------------------------------------------------------------------------------------ live changes
 def _bits(model, cfg, seed=8):
     """logits of a prefill, a decode step at B = 2 and one at B = 12, both KV modes -- for bit-for-bit comparisons"""

@@ -330,8 +330,8 @@ def test_bits_row_does_not_depend_on_its_neighbours_adapters(bank, name, mode):
 @pytest.mark.parametrize("name", NAMES)
 def test_bits_slot_number_and_hot_swap(bank, name):
     """(c) P in slot 0 gives the bits of P in slot 5.  (d) Q replaced by P in place, projection by projection on the live engine:
-    the row gives the bits of a fresh engine with P.  Printed, not asserted: how far a homogeneous table batch is from the
-    engine-wide adapter of mi_engine_set_lora (the base linear may take another route there)."""
+    the row gives the bits of a fresh engine with P.  And the engine-wide adapter of mi_engine_set_lora is a private column of
+    the same table that every row runs: P there gives the bits of a batch whose rows all name P in a slot."""
     cfg = bank.cfg(name)
     m0, m5 = bank.model(name, {0: "P"}), bank.model(name, {5: "P"})
     p0 = _bits(m0, cfg, lambda B: [0] * B)
@@ -348,8 +348,10 @@ def test_bits_slot_number_and_hot_swap(bank, name):
     live.engine.close(); m0.engine.close()
     wide = utils.load_model(bank.tiny[name][0], max_positions=MAX_POS)
     utils.load_adapters(wide, bank.adapter(name, "P"))
-    delta = max(float(np.abs(x - y).max()) for x, y in zip(p0, _bits(wide, cfg, lambda B: [None] * B)))
+    pw = _bits(wide, cfg, lambda B: [None] * B)
+    delta = max(float(np.abs(x - y).max()) for x, y in zip(p0, pw))
     print(f"{name}: max |logit(table, every row on P) - logit(mi_engine_set_lora P)| = {delta:.3e}")
+    _assert_same_bits(p0, pw, "every row on P / mi_engine_set_lora P")
     wide.engine.close()
 
 

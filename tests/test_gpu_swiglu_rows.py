@@ -1,4 +1,4 @@
-"""swiglu_rows_kernel (csrc/lora.hip) through mi_op_swiglu_rows (-m gpu): the SwiGLU of an ADAPTED gate|up linear, whose
+"""swiglu_rows_kernel (csrc/lora_rows.hip) through mi_op_swiglu_rows (-m gpu): the SwiGLU of an ADAPTED gate|up linear, whose
 LoRA term has to be added before the activation -- the linear stores gate|up, this kernel writes silu(gate) * up.
 
 Yardstick: a NumPy restatement of the three rounding points of nn.silu(gate) * up in the activation dtype T (llama.py:165;

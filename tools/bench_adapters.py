@@ -2,19 +2,20 @@
 """What per-request LoRA adapters cost per decode step: bench.py's synthetic weights, device-synchronised step times.
 
 Three engines of one model live side by side -- one that never saw an adapter, one with the engine-wide adapter of
-mi_engine_set_lora, one with four adapters in the per-request table (mi_engine_set_adapter_lora) -- every adapter rank 16 on
+mi_engine_set_lora (the table's private column, which every row runs), one with four adapters in the per-request slots of the
+table (mi_engine_set_adapter_lora) -- every adapter rank 16 on
 all seven linears of every block (scale 10, A ~ U(+-1/sqrt(K)), B ~ N(0, 0.01^2): bench.py's apply_lora recipe).  Five
 configurations, ALTERNATED inside every repetition so that drift hits them alike:
 
     a  no adapter                          the plain engine
-    b  engine-wide adapter                 the fused path: LoRA terms in the linears' epilogues
+    b  engine-wide adapter                 the launches of d (per adapted block 4 down + 4 up-add launches and the SwiGLU: 9)
     c  table resident, every row on -1     must equal a: such a step runs the launches of an engine without adapters
-    d  table, every row on adapter 0       the by-row path: per adapted block 4 down + 4 up-add launches and the SwiGLU (9),
-    e  table, rows spread over 4 adapters  against b's 4 down + the third q|k|v up-add + the SwiGLU (6)
+    d  table, every row on adapter 0       must equal b
+    e  table, rows spread over 4 adapters
 
 Per configuration: a prefill of --context tokens, --warmup steps, then --reps x (--steps decode steps between two device
-syncs); reported: median, min and max ms per step, the run-to-run spread (max - min of a), c - a, and (d - b) and (e - b) per
-block and per added launch (3 per block).
+syncs); reported: median, min and max ms per step, the run-to-run spread (max - min of a), c - a, d - b, e - b, and (d - a)
+per LoRA launch.
 
     python tools/bench_adapters.py [--out profiles/adapters_step_times.json]
     python tools/bench_adapters.py --only mistral-7b-bf16:8:model --reps 1          (one case: for a profiler)
@@ -39,7 +40,7 @@ KEYS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o
         "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
 DEFAULT_CASES = ["mistral-7b-bf16:8:model", "mistral-7b-bf16:8:float32", "qwen3-14b-int4:64:model"]
 RANK, N_TABLE = 16, 4
-LAUNCHES = {"engine_wide": 6, "table": 9}          # LoRA launches per adapted block beside the four linears
+LORA_LAUNCHES = 9                                   # per adapted block beside the four linears: 4 down, 4 up-add, the SwiGLU
 
 
 def adapt(eng, cfg, gen, slot=None):
@@ -130,16 +131,13 @@ def main():
                 leg[k].kv.close()
             med = {k: statistics.median(t) for k, t in times.items()}
             nl = cfg["num_hidden_layers"]
-            added = LAUNCHES["table"] - LAUNCHES["engine_wide"]
             row = dict(workload=wl, batch=B, kv_dtype=kvd, rank=RANK, adapted_layers=nl, context=args.context, steps=args.steps,
                        reps=args.reps, ms_per_step={k: dict(median=round(med[k], 4), min=round(min(t), 4), max=round(max(t), 4))
                                                     for k, t in times.items()},
                        spread_a_ms=round(max(times["a"]) - min(times["a"]), 4), c_minus_a_ms=round(med["c"] - med["a"], 4),
-                       lora_launches_per_block=LAUNCHES,
+                       lora_launches_per_block=LORA_LAUNCHES,
                        d_minus_b_ms=round(med["d"] - med["b"], 4), e_minus_b_ms=round(med["e"] - med["b"], 4),
-                       d_minus_b_us_per_added_launch=round((med["d"] - med["b"]) * 1e3 / (nl * added), 3),
-                       e_minus_b_us_per_added_launch=round((med["e"] - med["b"]) * 1e3 / (nl * added), 3),
-                       d_minus_a_us_per_lora_launch=round((med["d"] - med["a"]) * 1e3 / (nl * LAUNCHES["table"]), 3))
+                       d_minus_a_us_per_lora_launch=round((med["d"] - med["a"]) * 1e3 / (nl * LORA_LAUNCHES), 3))
             if args.twin:
                 row["a2_minus_a_ms"] = round(med["a2"] - med["a"], 4)
             rows.append(row)

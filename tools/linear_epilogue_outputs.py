@@ -4,8 +4,8 @@
     python tools/linear_epilogue_outputs.py --save FILE.npz                  # one build (MLX_PARALLM_AMD_LIB selects another)
     python tools/linear_epilogue_outputs.py --compare A.npz B.npz            # cell count, array count, differing arrays
 
-One fresh process per library.  A cell is one call of an mi_op_* entry point (or one forward pass of an adapted tiny model,
-for the LoRA term that no mi_op_* reaches); what it wrote is kept as raw bits (16-bit outputs as uint16).  A call that the
+One fresh process per library.  A cell is one call of an mi_op_* entry point (or one forward pass of an adapted tiny model:
+the LoRA term of lora_rows.hip behind every route's plain store, which no mi_op_* reaches); what it wrote is kept as raw bits (16-bit outputs as uint16).  A call that the
 library refuses is kept as its error text, so a refusal that changes shows up as a differing array too.
 
 Shapes are the smallest that reach every path: N = 144 output columns (nine tiles: a second tile group with spare waves),
@@ -167,8 +167,9 @@ def kernel_cells(big):
             OUT[f"swiglu_rows|{act}|rnd{rnd}"] = bits(out)
 
 
-# ---- the LoRA term, through the engine: the adapted tiny models of tests/test_gpu_lora_targets.py (rank 16, scale 10, all
-# seven projections of the last two blocks)
+# ---- the LoRA term (lora_rows.hip: down by row, the route's plain store, up-add by row), through the engine: the tiny models
+# of tests/test_gpu_lora_targets.py under the engine-wide adapter (rank 16, scale 10, all seven projections of the last two
+# blocks)
 KEYS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
         "mlp.down_proj")
 TINY = {
