@@ -18,6 +18,8 @@
  *   mi_op_sample      sample closure + top_p_sampling: utils.py:345-364; sample_utils.py:3-38
  *   mi_op_sample_ex   the same kernel with top_k / min_p and per-row random streams (no counterpart in the reference)
  *   mi_op_sample_rowbias  ... and a call-wide logit_bias list (utils.py:346-349) + the per-row table (no counterpart)
+ *   mi_op_lora_rows   LoRALinear's term y + (scale * ((x A) B)).astype(x.dtype), each row with its own adapter (the per-request
+ *                     table has no counterpart in the reference)
  *   mi_op_kv_copy_tokens  the tail copy of mi_kv_fork_row (no counterpart in the reference)
  *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
  */
@@ -149,6 +151,30 @@ int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, in
  * storage.  M >= 1, I a positive multiple of 8 (else MI_ERR_UNSUPPORTED), ldx >= 2 I, ldo >= I, buffers aligned to their
  * element (else MI_ERR_INVALID); nothing is launched on a refused call. */
 int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd);
+/* the LoRA term of a step, each row with the adapter it names (lora_rows.hip), on its own: the two launches that stand around
+ * every adapted linear of the engine, on caller-owned DEVICE buffers.
+ *   MI_LORA_STAGE_DOWN  t[m][part][0..rank) = xs_m A, A [K][rank] float32 = the part's factor of row m's adapter, xs_m = row m
+ *                       of x [M][ldx] (act storage, rnd on top of float32), with pro = MI_PRO_NORM after the RMSNorm of the
+ *                       linear's prologue: xs = T(T(x rs) norm_w), norm_w [K] in act.  K <= 36864 (else MI_ERR_UNSUPPORTED).
+ *   MI_LORA_STAGE_UP    y[m][row0[p] + c] = T(y + T(scale (t[m][p] B)[c])), c in [0, n[p]), B [rank][n[p]] float32, reading the
+ *                       caller's t; with resid != NULL ([M][ldr], one part at column 0) EVERY row, adapted or not, ends with
+ *                       resid[m][c] = T(resid + y') and y stays as it was.
+ *   both (1 | 2)        the down launch, then the up-add, as the engine runs them.
+ * t [M][3 * 64] float32 is the caller's.  row_adapter: device int32 [M], the table column of every row; a value outside
+ * [0, MI_MAX_ADAPTERS] (mi355_decode.h) means "no adapter" and is not refused.  The adapter table is four HOST arrays
+ * [n_parts][MI_MAX_ADAPTERS + 1] (tab_a / tab_b: device pointers; tab_rank; tab_scale), column MI_MAX_ADAPTERS being the
+ * engine-wide adapter's; A = B = NULL: the adapter does not cover the part.  The call uploads it to a device table of its own
+ * and frees that before it returns.  n_parts in 1..3 with HOST arrays row0[] / n[] (read by the up stage only).
+ * MI_ERR_INVALID, nothing launched and no output touched: a null x, y, t, row_adapter or table array that a stage needs; M < 1;
+ * n_parts outside 1..3; stages outside 1..3; a bad act, rnd or pro; a norm without norm_w; ldx < K; a part outside [0, ldy); a
+ * residual with more than one part, a row0 other than 0 or ldr < n[0]; an entry with only one of A / B; a covered entry whose rank
+ * is outside 1..64; A or B not 16-byte aligned; x, norm_w, y or resid not aligned to their element. */
+#define MI_LORA_STAGE_DOWN 1
+#define MI_LORA_STAGE_UP 2
+int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                    float* t, void* y, int ldy, void* resid, int ldr, int stages);
 /* the copy of mi_kv_fork_row (mi355_decode.h) on its own, one launch: in each of `layers` layers (layer_elems elements apart),
  * for each of Hkv heads (head_stride elements apart) and in kcache and vcache alike, the n_tokens x D elements at element
  * offset src_off (of head 0, inside the layer) are copied to dst_off, in 16-byte pieces.  kv_dtype = MI_F32 / MI_BF16 /

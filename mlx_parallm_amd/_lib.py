@@ -25,6 +25,7 @@ WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
 PRO_NONE, PRO_NORM = 0, 1
 EPI_STORE, EPI_STORE_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3
+LORA_STAGE_DOWN, LORA_STAGE_UP = 1, 2
 
 _ERRORS = {-1: ValueError, -2: FileNotFoundError, -3: NotImplementedError, -4: RuntimeError}
 
@@ -131,6 +132,8 @@ SIGNATURES = {
     "mi_op_gemm_prefill_f32": (C.c_int, [C.POINTER(OpLinear), C.POINTER(OpGemvArgs), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mi_op_split_rows": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P]),
     "mi_op_swiglu_rows": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_op_lora_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _I32P, _I32P,
+                                  C.POINTER(_P), C.POINTER(_P), _I32P, _F32P, _P, _P, C.c_int, _P, C.c_int, C.c_int]),
     "mi_op_kv_copy_tokens": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "mi_op_tiled_bytes": (C.c_uint64, [C.POINTER(OpLinear)]),
     "mi_op_repack_tiled": (C.c_int, [C.POINTER(OpLinear), _P]),

@@ -1,8 +1,10 @@
 // ops_api.hip -- kernel-level C entry points (include/mi355_ops.h) on caller-owned device buffers.
 #include <algorithm>
+#include <vector>
 
 #include "../../include/mi355_ops.h"
 #include "kernels.h"
+#include "lora_rows.h"
 
 namespace mi {
 int launch_gemv(const LinearW& W, const GemvCall& c, hipStream_t st);
@@ -274,6 +276,59 @@ int mi_op_split_rows(const float* x, int ldx, const float* norm_w, float eps, in
 int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd) {
   MI_TRY(ready());
   MI_TRY(launch_swiglu_rows(x, ldx, out, ldo, M, I, act, rnd, nullptr));
+  return finish();
+}
+
+// lora_down_by_row_kernel and lora_up_add_by_row_kernel (lora_rows.hip) on their own: the two launches of lora_rows.h on the
+// caller's buffers, the adapter table uploaded from the host arrays for the length of the call.  Everything is validated
+// before the first launch -- the launchers' own refusals included, so that a call of both stages never runs half.
+int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                    float* t, void* y, int ldy, void* resid, int ldr, int stages) {
+  MI_TRY(ready());
+  const bool down = (stages & MI_LORA_STAGE_DOWN) != 0, up = (stages & MI_LORA_STAGE_UP) != 0;
+  if (stages < 1 || stages > (MI_LORA_STAGE_DOWN | MI_LORA_STAGE_UP)) return fail(MI_ERR_INVALID, "mi_op_lora_rows: stages is MI_LORA_STAGE_DOWN, _UP or both");
+  if (!row_adapter || !t || !tab_a || !tab_b || !tab_rank || !tab_scale) return fail(MI_ERR_INVALID, "mi_op_lora_rows: null argument");
+  if (M < 1) return fail(MI_ERR_INVALID, "mi_op_lora_rows: no rows");
+  if (n_parts < 1 || n_parts > 3) return fail(MI_ERR_INVALID, "mi_op_lora_rows: 1 to 3 parts");
+  if (act != MI_F32 && act != MI_BF16 && act != MI_F16) return fail(MI_ERR_INVALID, "mi_op_lora_rows: bad activation dtype");
+  if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, "mi_op_lora_rows: bad rounding mode");
+  if (pro != PRO_NONE && pro != PRO_NORM) return fail(MI_ERR_INVALID, "mi_op_lora_rows: bad prologue");
+  const size_t es = dtype_size(act);
+  if ((uintptr_t)t % sizeof(float) != 0 || (uintptr_t)row_adapter % sizeof(int32_t) != 0) return fail(MI_ERR_INVALID, "mi_op_lora_rows: misaligned buffer");
+  if (down) {
+    if (!x) return fail(MI_ERR_INVALID, "mi_op_lora_rows: null x");
+    if (K < 1 || ldx < K) return fail(MI_ERR_INVALID, "mi_op_lora_rows: a row of x is shorter than K");
+    if (pro == PRO_NORM && !norm_w) return fail(MI_ERR_INVALID, "mi_op_lora_rows: a norm without its weights");
+    if (K > 36864) return fail(MI_ERR_UNSUPPORTED, "mi_op_lora_rows: K above 36864");
+    if ((uintptr_t)x % es != 0 || (uintptr_t)norm_w % es != 0) return fail(MI_ERR_INVALID, "mi_op_lora_rows: misaligned buffer");
+  }
+  if (up) {
+    if (!y || !row0 || !n) return fail(MI_ERR_INVALID, "mi_op_lora_rows: null output");
+    for (int r = 0; r < n_parts; ++r)
+      if (n[r] < 1 || row0[r] < 0 || (long long)row0[r] + n[r] > ldy) return fail(MI_ERR_INVALID, "mi_op_lora_rows: a part lies outside the row");
+    if (resid && (n_parts != 1 || row0[0] != 0 || ldr < n[0])) return fail(MI_ERR_INVALID, "mi_op_lora_rows: a residual goes with one part at column 0");
+    if ((uintptr_t)y % es != 0 || (uintptr_t)resid % es != 0) return fail(MI_ERR_INVALID, "mi_op_lora_rows: misaligned buffer");
+  }
+  std::vector<AdapterPart> table((size_t)n_parts * LORA_TABLE_COLS);
+  for (size_t i = 0; i < table.size(); ++i) {
+    if ((tab_a[i] == nullptr) != (tab_b[i] == nullptr)) return fail(MI_ERR_INVALID, "mi_op_lora_rows: a table entry with only one of A and B");
+    if (tab_a[i] == nullptr) continue;
+    if (tab_rank[i] < 1 || tab_rank[i] > 64) return fail(MI_ERR_INVALID, "mi_op_lora_rows: rank outside 1..64");
+    if ((uintptr_t)tab_a[i] % 16 != 0 || (uintptr_t)tab_b[i] % 16 != 0) return fail(MI_ERR_INVALID, "mi_op_lora_rows: A and B must be 16-byte aligned");
+    table[i].a = tab_a[i]; table[i].b = tab_b[i]; table[i].rank = tab_rank[i]; table[i].scale = tab_scale[i];
+  }
+  void* dtab = nullptr;
+  FreeGuard guard{dtab};
+  MI_HIP(hipMalloc(&dtab, table.size() * sizeof(AdapterPart)));
+  MI_HIP(hipMemcpy(dtab, table.data(), table.size() * sizeof(AdapterPart), hipMemcpyHostToDevice));
+  LoraRowsCall c;
+  c.table = (const AdapterPart*)dtab; c.row_adapter = row_adapter; c.n_parts = n_parts; c.M = M; c.K = K; c.act = act; c.rnd = rnd;
+  c.t = t;
+  if (up) for (int r = 0; r < n_parts; ++r) { c.row0[r] = row0[r]; c.n[r] = n[r]; }
+  if (down) MI_TRY(launch_lora_down_by_row(c, x, ldx, pro, norm_w, eps, nullptr));
+  if (up) MI_TRY(launch_lora_up_add_by_row(c, y, ldy, resid, ldr, nullptr));
   return finish();
 }
 

@@ -39,6 +39,21 @@ def round_to(x: np.ndarray, dtype: str) -> np.ndarray:
     raise ValueError(f"unknown dtype {dtype}")
 
 
+def round_f64(v: np.ndarray, dtype: str) -> np.ndarray:
+    """float64 -> `dtype` with ONE rounding (values as float32).  round_to goes through float32, which rounds twice; a float32
+    rounded to ODD (truncate toward zero, set the last bit when inexact) keeps what the second rounding needs, a 16-bit type
+    having far fewer bits than float32."""
+    v = np.asarray(v, dtype=np.float64)
+    if dtype == "float32":
+        return v.astype(np.float32)
+    f = v.astype(np.float32)
+    away = np.abs(f.astype(np.float64)) > np.abs(v)
+    f = np.where(away, np.nextafter(f, np.float32(0.0)), f).astype(np.float32)
+    inexact = f.astype(np.float64) != v
+    f = (f.view(np.uint32) | inexact.astype(np.uint32)).view(np.float32)
+    return round_to(f, dtype)
+
+
 def bf16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
     return (bits.astype(np.uint32) << 16).view(np.float32)
 

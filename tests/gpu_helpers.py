@@ -178,6 +178,34 @@ def attention_decode(s, qkv_d, kc, vc, off_d, cos, sin, nsplit, variant=0, *, qn
     return outs if repeat > 1 else outs[0]
 
 
+def _addr(v) -> int:
+    return 0 if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+
+
+def lora_rows(*, stages, M, act, rnd, row_adapter, parts, table, t, x=None, ldx=0, K=0, pro=0, norm_w=None, eps=0.0, y=None, ldy=0,
+              resid=None, ldr=0, n_parts=None, check=True):
+    """mi_op_lora_rows: lora_down_by_row_kernel (stages & 1) and lora_up_add_by_row_kernel (stages & 2) of csrc/lora_rows.hip on
+    the caller's buffers -> the return code.  parts: [(row0, n), ...]; table: {(part, column): (A, B, rank, scale)} with A / B
+    tensors, raw addresses or None -- every other entry is null; buffers: tensors, raw addresses or None."""
+    cols = L.MI_MAX_ADAPTERS + 1
+    n_parts = len(parts) if n_parts is None else n_parts
+    slots = max(len(parts), 3) * cols
+    ta, tb = (C.c_void_p * slots)(), (C.c_void_p * slots)()
+    tr, ts = (C.c_int32 * slots)(), (C.c_float * slots)()
+    for (r, col), (a, b, rank, scale) in table.items():
+        ta[r * cols + col], tb[r * cols + col], tr[r * cols + col], ts[r * cols + col] = _addr(a) or None, _addr(b) or None, rank, scale
+    row0 = (C.c_int32 * 3)(*([p[0] for p in parts] + [0] * (3 - len(parts))))
+    n = (C.c_int32 * 3)(*([p[1] for p in parts] + [0] * (3 - len(parts))))
+    torch.cuda.synchronize()
+    rc = L.lib().mi_op_lora_rows(_addr(x) or None, int(ldx), int(M), int(K), int(act), int(rnd), int(pro), _addr(norm_w) or None,
+                                 float(eps), _addr(row_adapter) or None, int(n_parts), row0, n, ta, tb, tr, ts, _addr(t) or None,
+                                 _addr(y) or None, int(ldy), _addr(resid) or None, int(ldr), int(stages))
+    torch.cuda.synchronize()
+    if check:
+        L.check(rc)
+    return rc
+
+
 def close_frac(got: np.ndarray, want: np.ndarray, dtype: str, atol: float = 0.0) -> float:
     """Fraction of elements further than 2 ulp(dtype) (relative) + atol from the oracle.  A non-finite `got` is far."""
     with np.errstate(invalid="ignore"):

@@ -14,7 +14,8 @@ table: tests/skinny_cases.py (what they rest on: tests/test_skinny_cases.py).
 * a biased int4 call above 16 rows stays on skinny_kernel: a forced gemm_q4.hip plan refuses it and leaves the output alone.
 
 Out of scope (no way to them through mi_op_gemm_skinny; their engine-level tests keep them): the RMSNorm hand-over between
-launches (sq_in / sq_out), the publish-only form, [hi | lo] matrices (kx) and the LoRA terms.
+launches (sq_in / sq_out), the publish-only form and [hi | lo] matrices (kx).  The LoRA terms no longer ride in these
+kernels: lora_rows.hip adds them around a plain-store launch, and tests/test_gpu_lora_rows.py checks it at its own level.
 """
 import numpy as np
 import pytest

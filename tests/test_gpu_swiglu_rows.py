@@ -26,7 +26,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.numerics import round_to
+from oracle.numerics import round_f64, round_to
 
 pytestmark = pytest.mark.gpu
 
@@ -50,21 +50,9 @@ def _inputs(M, I, ldx, logical):
     return _INPUTS[key]
 
 
-def _round_f64(v, logical):
-    """float64 -> T with ONE rounding.  round_to goes through float32, which rounds twice; a float32 rounded to ODD (truncate
-    toward zero, set the last bit when inexact) keeps what the second rounding needs, T having far fewer bits than float32."""
-    v = np.asarray(v, dtype=np.float64)
-    f = v.astype(np.float32)
-    away = np.abs(f.astype(np.float64)) > np.abs(v)
-    f = np.where(away, np.nextafter(f, np.float32(0.0)), f).astype(np.float32)
-    inexact = f.astype(np.float64) != v
-    f = (f.view(np.uint32) | inexact.astype(np.uint32)).view(np.float32)
-    return round_to(f, logical)
-
-
 def _yardstick(x, I, logical):
     g, u = x[:, :I].astype(np.float64), x[:, I:2 * I].astype(np.float64)
-    sig = _round_f64(1.0 / (1.0 + np.exp(-g)), logical).astype(np.float64)
+    sig = round_f64(1.0 / (1.0 + np.exp(-g)), logical).astype(np.float64)
     s = round_to(g * sig, logical).astype(np.float64)
     return round_to(s * u, logical)
 
