@@ -52,6 +52,7 @@ extern "C" {
 #define MI_ARCH_LLAMA 0 /* mlx_parallm/models/llama.py (also model_type "mistral": utils.py:33-36) */
 #define MI_ARCH_QWEN3 1 /* mlx_parallm/models/qwen3.py: + per-head q_norm/k_norm (qwen3.py:65-70) */
 #define MI_ARCH_PHI3 2 /* mlx_parallm/models/phi3.py */
+#define MI_ARCH_MIXTRAL 3 /* mlx_parallm/models/mixtral.py: Mistral's attention, a sparse mixture-of-experts MLP (see below) */
 
 /* KV-cache element type selector for mi_kv_create */
 #define MI_KV_MODEL (-1) /* BatchedKVCache semantics: KV in the model dtype (models/base.py:66-85) */
@@ -87,6 +88,10 @@ typedef struct mi_model_desc {
                               * the q / k rows (and biases; mi_engine_set_lora: the columns of B) into the half-split order
                               * of the kernels -- q.k is unchanged, V / O / the caches are untouched.  MI_ARCH_QWEN3 with the
                               * flag: MI_ERR_UNSUPPORTED (q_norm / k_norm would need the same regrouping) */
+  /* MI_ARCH_MIXTRAL (mixtral.py:20,22); ignored by every other arch.  The struct grew without a new MI_ABI_VERSION: struct_size
+   * refuses a binding built against the shorter layout. */
+  int32_t num_local_experts;   /* E in 1..16 */
+  int32_t num_experts_per_tok; /* k in {1, 2}, k <= E */
 } mi_model_desc;
 
 /* arguments of the `sample` closure (utils.py:345-364) + top_p_sampling (sample_utils.py:3-38) */
@@ -144,7 +149,18 @@ void mi_engine_destroy(mi_engine* e);
  * then up; each is one tensor per ".weight" / ".scales" / ".biases" with all the rows (any other row count: MI_ERR_INVALID
  * naming it), and the split names (q_proj, ..., up_proj) are unknown.  phi3.py has no linear biases and no tied head:
  * desc.attention_bias, mlp_bias or tie_word_embeddings set is MI_ERR_INVALID at mi_engine_create; rope_traditional and
- * rope_scale are those of MI_ARCH_LLAMA (phi3.py:73-81). */
+ * rope_scale are those of MI_ARCH_LLAMA (phi3.py:73-81).
+ * MI_ARCH_MIXTRAL (mixtral.py:95-119,198-215): dense 16-bit checkpoints only -- act_dtype MI_F32 or quant_bits != 0 is
+ * MI_ERR_UNSUPPORTED at mi_engine_create naming the field, as are num_local_experts outside 1..16, num_experts_per_tok outside
+ * {1, 2} (or above the expert count) and a hidden_size or intermediate_size that is no multiple of 64; tie_word_embeddings,
+ * attention_bias or mlp_bias set is MI_ERR_INVALID.  The MLP of a block is "block_sparse_moe.gate.weight" [E][H] and either the
+ * stacked tensors "block_sparse_moe.switch_mlp.{gate_proj,up_proj,down_proj}.weight" ([E][I][H], [E][I][H], [E][H][I]) or, per
+ * expert e, "block_sparse_moe.experts.<e>.{w1,w3,w2}.weight" (gate [I][H], up [I][H], down [H][I]; copied into slot e), in any
+ * mix; a wrong shape is MI_ERR_INVALID naming the tensor, ".scales" / ".biases" of these names MI_ERR_UNSUPPORTED, and the
+ * dense "mlp.*" names are unknown.  mi_engine_finalize names the first expert slot that was not set.  The block computes, in
+ * the activations' dtype T: g = T(xn Wg^T); the k largest g, a tie going to the lower expert index; s = T(softmax_float32 over
+ * the selected); y_e = down_e(T(T(silu(gate_e xn)) up_e xn)); h = T(h + T(T(y_a s_a) + T(y_b s_b))).  LoRA: q/k/v/o_proj as
+ * on MI_ARCH_LLAMA, any "block_sparse_moe.*" name MI_ERR_UNSUPPORTED. */
 int mi_engine_set_tensor(mi_engine* e, const char* name, const void* data, const int64_t* shape,
                          int ndim, int dtype, int on_device);
 

@@ -22,6 +22,8 @@
  *                     table has no counterpart in the reference)
  *   mi_op_kv_copy_tokens  the tail copy of mi_kv_fork_row (no counterpart in the reference)
  *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
+ *   mi_op_moe_route / mi_op_moe_linear / mi_op_moe_mlp   MixtralSparseMoeBlock: mixtral.py:108-119 (gate, argpartition, softmax,
+ *                     SwitchGLU, weighted sum)
  */
 #ifndef MI355_OPS_H
 #define MI355_OPS_H
@@ -266,6 +268,30 @@ int mi_op_sample_rowlp(float* logits, int B, int V, float temperature, float top
                        const int32_t* row_bias_counts, const int32_t* row_bias_ids, const float* row_bias_values,
                        int table_rows, int cap, const int32_t* row_map, const int32_t* row_top_logprobs,
                        const int32_t* row_at_temperature, int n_row_settings, int logprobs_at_temperature, int method);
+
+/* ---- the sparse mixture-of-experts MLP of MI_ARCH_MIXTRAL (moe.hip), stage by stage.  T = `act` (MI_F32 / MI_BF16 / MI_F16
+ * storage, `rnd` on top of float32); router and expert weights are dense, row-major, `wdt` = MI_BF16 / MI_F16 and equal to act
+ * unless act is MI_F32 (then widened exactly).  E in 1..16, k in {1, 2}, k <= E; a pair is p = row * k + j.  iters >= 1 also
+ * times that many back-to-back launches into *avg_ms.
+ * mi_op_moe_route: xn [R][ldx] (H % 64 == 0, ldx % 8 == 0), wg [E][H] -> sel [R][k] int32 = the k largest g = T(xn wg^T) in
+ * descending order, a tie going to the lower expert index; score [R][k] in T = T(softmax_float32(g[sel])); meta [2 E] int32 =
+ * the pairs per expert, then where each expert's run starts in list; list [R k] int32 = the pairs grouped by expert, ascending
+ * inside a run (built by a scan: the same in every run). */
+int mi_op_moe_route(const void* xn, int ldx, int R, int H, int act, int rnd, const void* wg, int wdt, int E, int k,
+                    int32_t* sel, void* score, int32_t* meta, int32_t* list, int iters, float* avg_ms);
+/* the grouped linear with a plain store: out[p][n] = T(x[p >> x_shift] . w[e][n]) for every pair p on expert e's list; w
+ * [E][N][K], N % 64 == 0, K % 64 == 0, x [x_rows][ldx], out [pairs][ldo]; pairs on no list are not written.  meta / list as
+ * mi_op_moe_route writes them (DEVICE); the call reads them back first and refuses (MI_ERR_INVALID, nothing launched) runs that
+ * leave list [pairs], an entry outside [0, pairs) or one whose row p >> x_shift is outside x. */
+int mi_op_moe_linear(const void* x, int ldx, int x_rows, int x_shift, int act, int rnd, const void* w, int wdt, int E, int N,
+                     int K, const int32_t* meta, const int32_t* list, int pairs, void* out, int ldo, int iters, float* avg_ms);
+/* the route's outputs through the rest of the block: act[p] = T(T(silu(gate_e xn)) up_e xn), y[p] = down_e act[p] (workspace
+ * of the call's own), out[row] = T(resid[row] + r) or, resid == NULL, r = T(T(y_a s_a) + T(y_b s_b)).  w_gate, w_up [E][I][H],
+ * w_down [E][H][I]; H % 64 == 0, I % 64 == 0; the lists are checked as in mi_op_moe_linear.  stage_ms: NULL or float[3] =
+ * the mean launch time of gate|up, down and combine over iters launches each. */
+int mi_op_moe_mlp(const void* xn, int ldx, int R, int H, int I, int act, int rnd, int wdt, int E, int k, const void* w_gate,
+                  const void* w_up, const void* w_down, const int32_t* meta, const int32_t* list, const void* score,
+                  const void* resid, int ldr, void* out, int ldo, int iters, float* stage_ms);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ LIB_PATH = Path(os.environ.get("MLX_PARALLM_AMD_LIB") or (CSRC / "libmi355_decod
 # dtype / enum constants (mirror of the headers)
 MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
 MI_KV_MODEL = -1
-MI_ARCH_LLAMA, MI_ARCH_QWEN3, MI_ARCH_PHI3 = 0, 1, 2
+MI_ARCH_LLAMA, MI_ARCH_QWEN3, MI_ARCH_PHI3, MI_ARCH_MIXTRAL = 0, 1, 2, 3
 MI_MAX_TOP_LOGPROBS = 20
 MI_MAX_ROW_LOGIT_BIAS = 1024
 MI_MAX_ADAPTERS = 16
@@ -39,6 +39,7 @@ class ModelDesc(C.Structure):
         ("rope_scale", C.c_float), ("tie_word_embeddings", C.c_int32), ("act_dtype", C.c_int32),
         ("quant_bits", C.c_int32), ("quant_group_size", C.c_int32), ("max_positions", C.c_int32),
         ("attention_bias", C.c_int32), ("mlp_bias", C.c_int32), ("rope_traditional", C.c_int32),
+        ("num_local_experts", C.c_int32), ("num_experts_per_tok", C.c_int32),
     ]
 
 
@@ -154,6 +155,12 @@ SIGNATURES = {
     "mi_op_sample_rowlp": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P,
                                      C.c_uint64, C.c_uint64, _P, C.c_int, _P, _P, _P, _P, _P, _P,
                                      C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "mi_op_moe_route": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                  C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_moe_linear": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                   C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_moe_mlp": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

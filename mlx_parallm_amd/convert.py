@@ -155,6 +155,8 @@ def convert(hf_path: str, mlx_path: str = "mlx_model", quantize: bool = False, q
     target = torch.float16 if quantize else _DTYPES[dtype]
     weights = {k: (v.to(target) if v.is_floating_point() and not _is_packed_aux(k, weights) and not _is_linear_bias(k, v) else v)
                for k, v in weights.items()}
+    if quantize and config.get("model_type") == "mixtral":
+        raise NotImplementedError("convert(quantize=True): quantised Mixtral checkpoints are not supported by the MI355X engine")
     if quantize:
         print("[INFO] Quantizing")
         weights, config = quantize_model(weights, config, q_group_size, q_bits)

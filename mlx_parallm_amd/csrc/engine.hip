@@ -101,6 +101,38 @@ int choose_nsplit(const mi_kv* kv, int B, int Hkv, int L, const int32_t* rows = 
   return std::max(1, std::min(ns, 16));
 }
 
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// MI_ARCH_MIXTRAL, the MLP half of a block (mixtral.py:108-119,143-144): xn = post_attention_layernorm(h) once, then route,
+// grouped gate|up + SwiGLU, grouped down, combine + residual -- six kernels on the stream, nothing read back.  T is `act`
+// without a logical rounding (the activations behind the first attention: float32 in the float32-KV mode).
+int moe_block(mi_engine* e, LayerW& lw, size_t R, int act, bool w32) {
+  const mi_model_desc& d = e->d;
+  const int H = d.hidden_size, I = d.intermediate_size, E = d.num_local_experts, k = d.num_experts_per_tok;
+  const size_t es = dtype_size(act), P = R * k;
+  hipStream_t st = e->stream;
+  e->handover.valid = false;      // (o_proj's row sums describe h before this block adds to it: nothing here takes them)
+  const size_t o_sel = 0, o_score = o_sel + align256(P * 4), o_meta = o_score + align256(P * es),
+               o_list = o_meta + align256(2 * (size_t)E * 4), o_act = o_list + align256(P * 4), o_y = o_act + align256(P * I * es),
+               total = o_y + align256(P * H * es);
+  MI_TRY(grow(st, &e->moe_ws, &e->moe_ws_cap, total));
+  char* ws = e->moe_ws;
+  int32_t* sel = (int32_t*)(ws + o_sel); void* score = ws + o_score; int32_t* meta = (int32_t*)(ws + o_meta); int32_t* list = (int32_t*)(ws + o_list);
+  void* acts = ws + o_act; void* y = ws + o_y;
+  { Prof pr(e, "moe_route");
+    MI_TRY(launch_rmsnorm_rows(e->h, H, w32 ? lw.post_norm32 : lw.post_norm, e->xn, H, (int)R, H, d.rms_norm_eps, act, st, true, RND_NONE));
+    MoeRouteCall rc{e->xn, H, (int)R, H, act, RND_NONE, lw.moe_router, d.act_dtype, E, k, sel, score, meta, list};
+    MI_TRY(launch_moe_route(rc, st)); }
+  { Prof pr(e, "moe_gate_up");
+    MoeLinearCall c{e->xn, H, k == 2 ? 1 : 0, act, RND_NONE, lw.moe_w[0], lw.moe_w[1], d.act_dtype, E, I, H, 1, meta, list, acts, I};
+    MI_TRY(launch_moe_linear(c, st)); }
+  { Prof pr(e, "moe_down");
+    MoeLinearCall c{acts, I, 0, act, RND_NONE, lw.moe_w[2], nullptr, d.act_dtype, E, H, I, 0, meta, list, y, H};
+    MI_TRY(launch_moe_linear(c, st)); }
+  Prof pr(e, "moe_combine");
+  return launch_moe_combine(y, score, k, e->h, H, e->h, H, (int)R, H, act, RND_NONE, st);
+}
+
 // A group of cache rows that advance by the same number of tokens in one forward pass: entries [r0, r0 + B) of the
 // call's row list, L tokens each, the group's first token at position tok0 of the token buffer.
 struct AttnGroup { int r0, B, L; size_t tok0; };
@@ -271,6 +303,10 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     { // o_proj + residual (llama.py:143,188)
       GemvCall c; c.x = e->attn; c.ldx = Hq * D; c.act = act; c.rnd = RND_NONE; c.epi = EPI_RESID; c.resid = e->h; c.ldo = H;
       MI_TRY(resid_linear(lw.o, c, Hq * D, "gemv_o")); }
+    if (d.arch == MI_ARCH_MIXTRAL) {
+      MI_TRY(moe_block(e, lw, R, act, w32));
+      continue;
+    }
     { // post_attention_layernorm + gate|up + SwiGLU (llama.py:189,165)
       GemvCall c; c.x = e->h; c.ldx = H; c.act = act; c.rnd = RND_NONE; c.pro = PRO_NORM; c.norm_w = w32 ? lw.post_norm32 : lw.post_norm;
       c.eps = d.rms_norm_eps; c.epi = EPI_SWIGLU; c.out = e->act; c.ldo = I; c.pair_offset = I;
@@ -474,7 +510,8 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     return fail(MI_ERR_INVALID, "mi_model_desc.struct_size = " + std::to_string(desc->struct_size) + ", this library (ABI " +
                                     std::to_string(MI_ABI_VERSION) + ") expects " + std::to_string(sizeof(mi_model_desc)));
   const mi_model_desc& d = *desc;
-  if (d.arch != MI_ARCH_LLAMA && d.arch != MI_ARCH_QWEN3 && d.arch != MI_ARCH_PHI3) return fail(MI_ERR_UNSUPPORTED, "unsupported arch");
+  if (d.arch != MI_ARCH_LLAMA && d.arch != MI_ARCH_QWEN3 && d.arch != MI_ARCH_PHI3 && d.arch != MI_ARCH_MIXTRAL)
+    return fail(MI_ERR_UNSUPPORTED, "unsupported arch");
   if (d.arch == MI_ARCH_PHI3 && (d.attention_bias || d.mlp_bias || d.tie_word_embeddings))
     return fail(MI_ERR_INVALID, "arch phi3 has neither linear biases nor a tied lm_head (attention_bias, mlp_bias, tie_word_embeddings must be 0)");
   if (d.hidden_size <= 0 || d.num_layers <= 0 || d.num_heads <= 0 || d.num_kv_heads <= 0 || d.head_dim <= 0 ||
@@ -488,6 +525,18 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
   if (d.rope_traditional && d.arch == MI_ARCH_QWEN3)
     return fail(MI_ERR_UNSUPPORTED, "rope_traditional with arch qwen3 is not supported (q_norm / k_norm would need the same regrouping)");
   if (d.rope_traditional && d.head_dim % 2 != 0) return fail(MI_ERR_INVALID, "rope_traditional needs an even head_dim");
+  if (d.arch == MI_ARCH_MIXTRAL) {      // mixtral.py: dense 16-bit checkpoints, E <= 16 experts, the best 1 or 2 per token
+    if (d.attention_bias || d.mlp_bias || d.tie_word_embeddings)
+      return fail(MI_ERR_INVALID, "arch mixtral has neither linear biases nor a tied lm_head (attention_bias, mlp_bias, tie_word_embeddings must be 0)");
+    if (d.act_dtype == MI_F32) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: act_dtype must be MI_BF16 or MI_F16 (float32 weights are not supported)");
+    if (d.quant_bits != 0) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits must be 0 (quantised experts are not supported yet)");
+    if (d.num_local_experts < 1 || d.num_local_experts > MOE_MAX_EXPERTS)
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: num_local_experts must be in [1, " + std::to_string(MOE_MAX_EXPERTS) + "]");
+    if (d.num_experts_per_tok < 1 || d.num_experts_per_tok > 2 || d.num_experts_per_tok > d.num_local_experts)
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: num_experts_per_tok must be 1 or 2 and at most num_local_experts");
+    if (d.hidden_size % 64 || d.intermediate_size % 64)
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: hidden_size and intermediate_size must be multiples of 64");
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(MI_ERR_RUNTIME, "no HIP device available (this library has no CPU backend)");
@@ -503,6 +552,7 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     l.o.n_parts = 1; l.o.part_rows[0] = d.hidden_size;
     l.gate_up.n_parts = 2; l.gate_up.part_rows[0] = d.intermediate_size; l.gate_up.part_rows[1] = d.intermediate_size;
     l.down.n_parts = 1; l.down.part_rows[0] = d.hidden_size;
+    if (d.arch == MI_ARCH_MIXTRAL) for (auto& seen : l.moe_seen) seen.assign(d.num_local_experts, 0);
   }
   e->embed.n_parts = 1; e->embed.part_rows[0] = d.vocab_size;
   e->lm_head.n_parts = 1; e->lm_head.part_rows[0] = d.vocab_size;
@@ -518,13 +568,14 @@ void mi_engine_destroy(mi_engine* e) {
     free_linear(l.qkv); free_linear(l.o); free_linear(l.gate_up); free_linear(l.down);
     hipFree(l.in_norm); hipFree(l.post_norm); hipFree(l.q_norm); hipFree(l.k_norm);
     hipFree(l.in_norm32); hipFree(l.post_norm32); hipFree(l.q_norm32); hipFree(l.k_norm32);
+    hipFree(l.moe_router); for (void* w : l.moe_w) hipFree(w);
   }
   hipFree(e->final_norm32); hipFree(e->xn); hipFree(e->xs); hipFree(e->gk_ws);
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
   hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
   hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch);
-  hipFree(e->d_row_adapter); hipFree(e->lora_rt); hipFree(e->ys);
+  hipFree(e->d_row_adapter); hipFree(e->lora_rt); hipFree(e->ys); hipFree(e->moe_ws);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
   hipFree(e->d_uniforms); hipFree(e->d_topk_ids); hipFree(e->d_topk_lp); hipFree(e->d_bias_ids); hipFree(e->d_bias_vals);

@@ -61,6 +61,11 @@ struct LayerW {
   void* in_norm = nullptr; void* post_norm = nullptr; void* q_norm = nullptr; void* k_norm = nullptr;
   // float32 copies for the float32-activation ("PagedKVCache quirk") mode
   void* in_norm32 = nullptr; void* post_norm32 = nullptr; void* q_norm32 = nullptr; void* k_norm32 = nullptr;
+  // MI_ARCH_MIXTRAL (gate_up and down stay empty): the router [E][H] and the experts' matrices stacked by expert, dense in the
+  // model dtype, row-major as loaded -- gate [E][I][H], up [E][I][H], down [E][H][I].  moe_seen[t][e]: slot e of tensor t
+  // (0 gate, 1 up, 2 down) was set, by the stacked tensor or by the expert's own
+  void* moe_router = nullptr; void* moe_w[3] = {nullptr, nullptr, nullptr};
+  std::vector<char> moe_seen[3];
 };
 
 constexpr int NSLOT = 4;
@@ -120,6 +125,8 @@ struct mi_engine {
   int32_t* d_row_adapter = nullptr; size_t d_row_adapter_cap = 0;   // [token rows] of the current step
   float* lora_rt = nullptr; size_t lora_rt_cap = 0;                 // [token rows][LORA_ROWS_T_LD]: t of the by-row kernels
   void* ys = nullptr; size_t ys_cap = 0;                            // [token rows][H]: stored o_proj / down_proj output ahead of the by-row up-add
+  // MI_ARCH_MIXTRAL: sel | score | meta | list | act [R k][I] | y [R k][H] of the current layer, one block (moe_workspace)
+  char* moe_ws = nullptr; size_t moe_ws_cap = 0;
   int32_t* d_tokens = nullptr; size_t d_tokens_cap = 0;
   const int32_t* tok_src = nullptr;                       // device-fed step: the embedding reads the sampler's output in place
   int32_t* d_forced = nullptr; size_t d_forced_cap = 0;   // mi_score_tokens targets

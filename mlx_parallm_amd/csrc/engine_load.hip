@@ -1,5 +1,6 @@
 // engine_load.hip -- a checkpoint's tensors and LoRA factors into an engine, and mi_engine_finalize: the fused matrices are
 // checked, regrouped (rope_traditional), repacked tile-major and given their persistent second copies.
+#include <algorithm>
 #include <cstring>
 
 #include "engine_impl.h"
@@ -191,6 +192,7 @@ bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* 
     else return false;
     return true;
   }
+  if (d.arch == MI_ARCH_MIXTRAL && sub.compare(0, 4, "mlp.") == 0) return false;        // (its MLP is block_sparse_moe: set_moe_tensor)
   if (sub == "self_attn.q_proj") *p = {&l.qkv, 0, H, true};
   else if (sub == "self_attn.k_proj") *p = {&l.qkv, 1, H, true};
   else if (sub == "self_attn.v_proj") *p = {&l.qkv, 2, H, true};
@@ -200,6 +202,54 @@ bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* 
   else if (sub == "mlp.down_proj") *p = {&l.down, 0, d.intermediate_size, false};
   else return false;
   return true;
+}
+
+// MI_ARCH_MIXTRAL: `sub` = "block_sparse_moe.<rest>" of block l.  gate: the router [E][H]; switch_mlp.{gate,up,down}_proj: all
+// experts stacked, 3-D; experts.<e>.{w1,w3,w2}: one expert, 2-D, into slot e (w1 = gate, w3 = up, w2 = down: mixtral.py:203).
+int set_moe_tensor(mi_engine* e, LayerW& l, const std::string& rest, int kind, const void* data, const int64_t* shape, int ndim,
+                   int dtype, int on_device, const std::string& name) {
+  const mi_model_desc& d = e->d;
+  const int64_t E = d.num_local_experts, H = d.hidden_size, I = d.intermediate_size;
+  if (kind == 1 || kind == 2) return fail(MI_ERR_UNSUPPORTED, name + ": quantised experts are not supported");
+  if (kind != 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  if (dtype != d.act_dtype) return fail(MI_ERR_UNSUPPORTED, name + ": dense weight dtype differs from the model dtype");
+  const size_t es = dtype_size(dtype);
+  if (rest == "gate") {
+    if (ndim != 2 || shape[0] != E || shape[1] != H) return fail(MI_ERR_INVALID, name + ": expected shape [num_local_experts][hidden_size]");
+    if (l.moe_router == nullptr) MI_HIP(hipMalloc(&l.moe_router, (size_t)(E * H) * es));
+    return copy_in(l.moe_router, data, (size_t)(E * H) * es, on_device, e->stream);
+  }
+  int t = -1; int64_t slot = -1;                  // tensor (0 gate, 1 up, 2 down); expert slot, -1 = the stacked form
+  if (rest == "switch_mlp.gate_proj") t = 0;
+  else if (rest == "switch_mlp.up_proj") t = 1;
+  else if (rest == "switch_mlp.down_proj") t = 2;
+  else if (rest.compare(0, 8, "experts.") == 0) {
+    const size_t dot = rest.find('.', 8);
+    if (dot == std::string::npos) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+    const std::string idx = rest.substr(8, dot - 8), w = rest.substr(dot + 1);
+    if (idx.empty() || idx.size() > 4 || idx.find_first_not_of("0123456789") != std::string::npos) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+    slot = std::stoi(idx);
+    t = w == "w1" ? 0 : w == "w3" ? 1 : w == "w2" ? 2 : -1;
+    if (t >= 0 && slot >= E) return fail(MI_ERR_NOTFOUND, "expert index out of range: " + name);
+  }
+  if (t < 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  const int64_t rows = t == 2 ? H : I, cols = t == 2 ? I : H;
+  const size_t one = (size_t)(rows * cols) * es;
+  if (slot < 0) {
+    if (ndim != 3 || shape[0] != E || shape[1] != rows || shape[2] != cols)
+      return fail(MI_ERR_INVALID, name + ": expected shape [" + std::to_string(E) + "][" + std::to_string(rows) + "][" + std::to_string(cols) + "]");
+  } else if (ndim != 2 || shape[0] != rows || shape[1] != cols) {
+    return fail(MI_ERR_INVALID, name + ": expected shape [" + std::to_string(rows) + "][" + std::to_string(cols) + "]");
+  }
+  if (l.moe_w[t] == nullptr) MI_HIP(hipMalloc(&l.moe_w[t], one * (size_t)E));
+  if (slot < 0) {
+    MI_TRY(copy_in(l.moe_w[t], data, one * (size_t)E, on_device, e->stream));
+    std::fill(l.moe_seen[t].begin(), l.moe_seen[t].end(), 1);
+  } else {
+    MI_TRY(copy_in((char*)l.moe_w[t] + one * (size_t)slot, data, one, on_device, e->stream));
+    l.moe_seen[t][slot] = 1;
+  }
+  return MI_OK;
 }
 
 }  // namespace
@@ -250,6 +300,8 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
   const std::string sub = base.substr(dot + 1);
   LayerW& l = e->layers[li];
   Proj p;
+  if (d.arch == MI_ARCH_MIXTRAL && sub.compare(0, 17, "block_sparse_moe.") == 0)
+    return set_moe_tensor(e, l, sub.substr(17), kind, data, shape, ndim, dtype, on_device, name);
   if (find_proj(d, l, sub, &p)) {
     if (kind != 3 && p.part < 0) return set_linear_fused(e, *p.f, p.K, kind, data, shape, ndim, dtype, on_device, name);
     if (kind != 3) return set_linear(e, *p.f, p.part, p.K, kind, data, shape, ndim, dtype, on_device, name);
@@ -327,6 +379,8 @@ static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, 
   LayerW& l = e->layers[layer];
   const std::string p(proj);
   Proj pj;
+  if (d.arch == MI_ARCH_MIXTRAL && p.compare(0, 17, "block_sparse_moe.") == 0)
+    return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (arch mixtral: the attention projections only)");
   if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the linears of a block only)");
   auto put = [&](const Proj& part, const void* a, const void* b) {
     return set_adapter_part(e, adapter >= 0 ? adapter : LORA_ENGINE_COL, l, part, a, b, rank, scale, on_device);
@@ -401,6 +455,20 @@ int mi_engine_finalize(mi_engine* e) {
   MI_HIP(hipSetDevice(e->device));
   const mi_model_desc& d = e->d;
   const int H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  // MI_ARCH_MIXTRAL: the router and every expert slot of every block, before anything is repacked (a call that stops here
+  // can be repeated once the missing tensor is set)
+  for (int i = 0; d.arch == MI_ARCH_MIXTRAL && i < d.num_layers; ++i) {
+    const LayerW& l = e->layers[i];
+    const std::string p = "model.layers." + std::to_string(i);
+    if (l.moe_router == nullptr) return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe.gate.weight not set");
+    static const char* const stacked[3] = {"gate_proj", "up_proj", "down_proj"};
+    static const char* const single[3] = {"w1", "w3", "w2"};
+    for (int t = 0; t < 3; ++t)
+      for (int x = 0; x < d.num_local_experts; ++x)
+        if (!l.moe_seen[t][x])
+          return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe: expert " + std::to_string(x) + " of switch_mlp." + stacked[t] + ".weight (experts." +
+                                           std::to_string(x) + "." + single[t] + ".weight) not set");
+  }
   for (int i = 0; i < d.num_layers; ++i) {
     LayerW& l = e->layers[i];
     const std::string p = "model.layers." + std::to_string(i);
@@ -416,8 +484,10 @@ int mi_engine_finalize(mi_engine* e) {
     if (d.rope_traditional) MI_TRY(permute_qk_heads(e, l.qkv));      // in front of the tile-major repack
     MI_TRY(finalize_linear(e, l.qkv, H, p + (d.arch == MI_ARCH_PHI3 ? ".self_attn.qkv_proj" : ".self_attn.{q,k,v}_proj")));
     MI_TRY(finalize_linear(e, l.o, QD, p + ".self_attn.o_proj"));
-    MI_TRY(finalize_linear(e, l.gate_up, H, p + (d.arch == MI_ARCH_PHI3 ? ".mlp.gate_up_proj" : ".mlp.{gate,up}_proj")));
-    MI_TRY(finalize_linear(e, l.down, d.intermediate_size, p + ".mlp.down_proj"));
+    if (d.arch != MI_ARCH_MIXTRAL) {
+      MI_TRY(finalize_linear(e, l.gate_up, H, p + (d.arch == MI_ARCH_PHI3 ? ".mlp.gate_up_proj" : ".mlp.{gate,up}_proj")));
+      MI_TRY(finalize_linear(e, l.down, d.intermediate_size, p + ".mlp.down_proj"));
+    }
     if (!l.in_norm || !l.post_norm) return fail(MI_ERR_NOTFOUND, p + ": layernorm weights not set");
     if (d.arch == MI_ARCH_QWEN3 && (!l.q_norm || !l.k_norm)) return fail(MI_ERR_NOTFOUND, p + ": q_norm/k_norm not set");
     MI_TRY(make_f32_copy(e, l.in_norm, H, &l.in_norm32));
@@ -425,8 +495,11 @@ int mi_engine_finalize(mi_engine* e) {
     MI_TRY(make_f32_copy(e, l.q_norm, d.head_dim, &l.q_norm32));
     MI_TRY(make_f32_copy(e, l.k_norm, d.head_dim, &l.k_norm32));
     // persistent second copies, while mem_get_info still tells a scheduler the truth about what is left for its KV arena
-    (void)ensure_gu8(e, l.gate_up, d.intermediate_size);
-    if (d.act_dtype == MI_F16) { (void)ensure_hilo(e, l.qkv); (void)ensure_hilo(e, l.o); (void)ensure_hilo(e, l.gate_up); (void)ensure_hilo(e, l.down); }
+    if (d.arch != MI_ARCH_MIXTRAL) (void)ensure_gu8(e, l.gate_up, d.intermediate_size);
+    if (d.act_dtype == MI_F16) {
+      (void)ensure_hilo(e, l.qkv); (void)ensure_hilo(e, l.o);
+      if (d.arch != MI_ARCH_MIXTRAL) { (void)ensure_hilo(e, l.gate_up); (void)ensure_hilo(e, l.down); }
+    }
   }
   MI_TRY(finalize_linear(e, e->embed, H, "model.embed_tokens"));
   if (!d.tie_word_embeddings) MI_TRY(finalize_linear(e, e->lm_head, H, "lm_head"));

@@ -171,6 +171,34 @@ __host__ __device__ inline int tiled_q8_scale_off(size_t row) { return 1024 + (i
 // EPI_STORE launch (an adapted gate|up), rounding points of EPI_SWIGLU.  I % 8 == 0, ldx >= 2 I, ldo >= I, any M, one launch.
 int launch_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, int act, int rnd, hipStream_t st);
 
+// ---- moe.hip: the sparse mixture-of-experts MLP (mixtral.py:95-119).  T = the storage type `act` of the activations (with
+// the logical rounding `rnd` on top of float32); expert weights are dense 16-bit (`wdt` = MI_BF16 / MI_F16, = act unless act
+// is MI_F32, where they are widened exactly), row-major as in the checkpoint.  A pair is p = row * k + j.
+constexpr int MOE_MAX_EXPERTS = 16;
+// g = T(xn Wg^T) in float32 accumulation; sel[row][j] = the k largest in descending order, a tie to the lower expert index;
+// score = T(softmax_float32(g[sel])); then the work lists by a scan (reproducible, ascending pairs): meta[e] = the number of
+// pairs of expert e, meta[E + e] = where its run starts in list[R k].  Two kernels, no host round trip.  H % 64 == 0.
+struct MoeRouteCall {
+  const void* xn; int ldx, R, H, act, rnd;
+  const void* wg; int wdt, E, k;         // Wg [E][H]
+  int32_t* sel; void* score;             // [R][k] each (score in T)
+  int32_t* meta; int32_t* list;          // [2 E], [R k]
+};
+int launch_moe_route(const MoeRouteCall& c, hipStream_t st);
+// out[p][n] = T(x[p >> x_shift] . w_e[n]) for every pair p on the list of expert e (plain store), or with swiglu
+// T(T(silu(g)) u) of g = T(x . w_e[n]), u = T(x . w2_e[n]) (linear_epilogue.h).  w, w2: [E][N][K].  N % 64 == 0, K % 64 == 0.
+// Pairs on no list are not written; an expert without pairs costs a workgroup's launch and nothing else.
+struct MoeLinearCall {
+  const void* x; int ldx, x_shift, act, rnd;
+  const void* w; const void* w2; int wdt, E, N, K, swiglu;
+  const int32_t* meta; const int32_t* list;
+  void* out; int ldo;
+};
+int launch_moe_linear(const MoeLinearCall& c, hipStream_t st);
+// r = T(T(y[row k] s[row k]) + T(y[row k + 1] s[row k + 1])) (k = 1: the first term), out[row] = resid ? T(resid[row] + r) : r
+int launch_moe_combine(const void* y, const void* score, int k, const void* resid, int ldr, void* out, int ldo, int R, int H,
+                       int act, int rnd, hipStream_t st);
+
 struct EmbedCall {
   const int32_t* tokens;  // device [rows]
   int rows;

@@ -530,3 +530,68 @@ int mi_op_sample_rowlp(float* logits, int B, int V, float temperature, float top
 }
 
 }  // extern "C"
+
+// ---- moe.hip on its own ---------------------------------------------------------------------------------------------------
+namespace {
+// the lists of a route, read back: every run inside list[pairs], every entry a pair whose row of x exists
+int check_moe_lists(const int32_t* meta, const int32_t* list, int E, int pairs, int x_rows, int x_shift, const char* who) {
+  if (!meta || !list || E < 1 || E > MOE_MAX_EXPERTS || pairs < 1) return fail(MI_ERR_INVALID, std::string(who) + ": bad lists");
+  std::vector<int32_t> hm(2 * (size_t)E), hl((size_t)pairs);
+  MI_HIP(hipMemcpy(hm.data(), meta, hm.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  MI_HIP(hipMemcpy(hl.data(), list, hl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int e = 0; e < E; ++e) {
+    const long long cnt = hm[e], off = hm[E + e];
+    if (cnt < 0 || off < 0 || off + cnt > pairs) return fail(MI_ERR_INVALID, std::string(who) + ": the list of expert " + std::to_string(e) + " leaves the list array");
+    for (long long i = off; i < off + cnt; ++i)
+      if (hl[i] < 0 || hl[i] >= pairs || (hl[i] >> x_shift) >= x_rows)
+        return fail(MI_ERR_INVALID, std::string(who) + ": list entry " + std::to_string(i) + " is no pair of this call");
+  }
+  return MI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_op_moe_route(const void* xn, int ldx, int R, int H, int act, int rnd, const void* wg, int wdt, int E, int k,
+                    int32_t* sel, void* score, int32_t* meta, int32_t* list, int iters, float* avg_ms) {
+  MI_TRY(ready());
+  if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, "mi_op_moe_route: bad rounding mode");
+  const MoeRouteCall c{xn, ldx, R, H, act, rnd, wg, wdt, E, k, sel, score, meta, list};
+  return run_timed([&] { return launch_moe_route(c, nullptr); }, iters, avg_ms);
+}
+
+int mi_op_moe_linear(const void* x, int ldx, int x_rows, int x_shift, int act, int rnd, const void* w, int wdt, int E, int N,
+                     int K, const int32_t* meta, const int32_t* list, int pairs, void* out, int ldo, int iters, float* avg_ms) {
+  MI_TRY(ready());
+  if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, "mi_op_moe_linear: bad rounding mode");
+  if (x_shift < 0 || x_shift > 1 || x_rows < 1) return fail(MI_ERR_INVALID, "mi_op_moe_linear: bad x_rows / x_shift");
+  MI_TRY(check_moe_lists(meta, list, E, pairs, x_rows, x_shift, "mi_op_moe_linear"));
+  const MoeLinearCall c{x, ldx, x_shift, act, rnd, w, nullptr, wdt, E, N, K, 0, meta, list, out, ldo};
+  return run_timed([&] { return launch_moe_linear(c, nullptr); }, iters, avg_ms);
+}
+
+int mi_op_moe_mlp(const void* xn, int ldx, int R, int H, int I, int act, int rnd, int wdt, int E, int k, const void* w_gate,
+                  const void* w_up, const void* w_down, const int32_t* meta, const int32_t* list, const void* score,
+                  const void* resid, int ldr, void* out, int ldo, int iters, float* stage_ms) {
+  MI_TRY(ready());
+  if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, "mi_op_moe_mlp: bad rounding mode");
+  if (R < 1 || k < 1 || k > 2 || H < 64 || I < 64 || (long long)R * k > (1LL << 30)) return fail(MI_ERR_INVALID, "mi_op_moe_mlp: bad shape");
+  if (act != MI_F32 && act != MI_BF16 && act != MI_F16) return fail(MI_ERR_INVALID, "mi_op_moe_mlp: bad activation dtype");
+  const int P = R * k;
+  MI_TRY(check_moe_lists(meta, list, E, P, R, k - 1, "mi_op_moe_mlp"));
+  const size_t es = dtype_size(act);
+  void* acts = nullptr; void* y = nullptr;
+  FreeGuard g1{acts}, g2{y};
+  MI_HIP(hipMalloc(&acts, (size_t)P * I * es));
+  MI_HIP(hipMalloc(&y, (size_t)P * H * es));
+  const MoeLinearCall gu{xn, ldx, k - 1, act, rnd, w_gate, w_up, wdt, E, I, H, 1, meta, list, acts, I};
+  const MoeLinearCall dn{acts, I, 0, act, rnd, w_down, nullptr, wdt, E, H, I, 0, meta, list, y, H};
+  int rc = run_timed([&] { return launch_moe_linear(gu, nullptr); }, iters, stage_ms);
+  if (rc == MI_OK) rc = run_timed([&] { return launch_moe_linear(dn, nullptr); }, iters, stage_ms ? stage_ms + 1 : nullptr);
+  if (rc == MI_OK && resid == out && resid != nullptr && iters >= 1 && stage_ms) rc = fail(MI_ERR_INVALID, "mi_op_moe_mlp: a timed call cannot add into its own residual");
+  if (rc == MI_OK)
+    rc = run_timed([&] { return launch_moe_combine(y, score, k, resid, ldr, out, ldo, R, H, act, rnd, nullptr); }, iters, stage_ms ? stage_ms + 2 : nullptr);
+  return rc;
+}
+
+}  // extern "C"

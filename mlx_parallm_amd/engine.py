@@ -291,24 +291,26 @@ class Engine:
     def __init__(self, config: dict, device: int = 0, max_positions: Optional[int] = None,
                  act_dtype: str = "bfloat16"):
         mt = {"mistral": "llama"}.get(config["model_type"], config["model_type"])   # utils.py:33-36
-        if mt not in ("llama", "qwen3", "phi3"):
+        if mt not in ("llama", "qwen3", "phi3", "mixtral"):
             raise ValueError(f"Model type {config['model_type']} not supported.")    # utils.py:62-65
         nh = int(config["num_attention_heads"])
         d = L.ModelDesc()
         d.struct_size = C.sizeof(L.ModelDesc)
-        d.arch = {"qwen3": L.MI_ARCH_QWEN3, "phi3": L.MI_ARCH_PHI3}.get(mt, L.MI_ARCH_LLAMA)
+        d.arch = {"qwen3": L.MI_ARCH_QWEN3, "phi3": L.MI_ARCH_PHI3, "mixtral": L.MI_ARCH_MIXTRAL}.get(mt, L.MI_ARCH_LLAMA)
         d.hidden_size = int(config["hidden_size"])
         d.num_layers = int(config["num_hidden_layers"])
         d.num_heads = nh
         d.num_kv_heads = int(config.get("num_key_value_heads") or nh)
         # phi3.py:53 divides; a head_dim key in a Phi-3 config is ignored, as the reference ignores it
-        d.head_dim = d.hidden_size // nh if mt == "phi3" else int(config.get("head_dim") or d.hidden_size // nh)
+        d.head_dim = d.hidden_size // nh if mt in ("phi3", "mixtral") else int(config.get("head_dim") or d.hidden_size // nh)   # (mixtral.py:38)
         d.intermediate_size = int(config["intermediate_size"])
         d.vocab_size = int(config["vocab_size"])
         d.rms_norm_eps = float(config["rms_norm_eps"])
         d.rope_theta = float(config.get("rope_theta", 10000.0))
         scale = 1.0
         rs = config.get("rope_scaling")
+        if mt == "mixtral":                                                         # mixtral.py:57-61 builds nn.RoPE without it
+            rs = None
         if rs and mt == "phi3":                                                     # phi3.py:31-40,60-81
             kind = rs.get("type")
             if kind == "su":
@@ -328,6 +330,12 @@ class Engine:
         d.tie_word_embeddings = int(bool(config.get("tie_word_embeddings", tie_default)))
         d.act_dtype = _DT_NAMES[act_dtype]
         q = config.get("quantization")
+        if q and mt == "mixtral":
+            raise NotImplementedError("quantization: quantised Mixtral checkpoints are not supported by the MI355X engine "
+                                      "(dense bfloat16 / float16 experts only)")
+        if mt == "mixtral":                                                         # mixtral.py:20,22
+            d.num_local_experts = int(config.get("num_local_experts", 8))
+            d.num_experts_per_tok = int(config.get("num_experts_per_tok", 2))
         d.quant_bits = int(q["bits"]) if q else 0
         d.quant_group_size = int(q["group_size"]) if q else 0
         d.max_positions = int(max_positions or min(int(config.get("max_position_embeddings", 4096)), 32768))

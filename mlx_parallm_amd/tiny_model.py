@@ -37,9 +37,10 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
                  rope_theta: float, tie_word_embeddings: bool, quantization: Optional[Dict[str, Any]],
                  head_dim: Optional[int] = None, rms_norm_eps: float = 1e-6,
                  max_position_embeddings: int = 4096, attention_bias: bool = False, mlp_bias: bool = False,
-                 rope_traditional: bool = False) -> Dict[str, Any]:
-    """build_tiny_model.py:70-101 (+ head_dim / max_position_embeddings for qwen3, and the three ModelArgs switches
-    of llama.py:29-32)."""
+                 rope_traditional: bool = False, num_local_experts: Optional[int] = None,
+                 num_experts_per_tok: Optional[int] = None) -> Dict[str, Any]:
+    """build_tiny_model.py:70-101 (+ head_dim / max_position_embeddings for qwen3, the three ModelArgs switches
+    of llama.py:29-32, and the two expert counts of mixtral.py:20,22 for model_type "mixtral")."""
     cfg: Dict[str, Any] = {
         "model_type": model_type,
         "hidden_size": int(hidden_size),
@@ -59,6 +60,9 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
     }
     if model_type == "qwen3" or head_dim is not None:
         cfg["head_dim"] = int(head_dim or hidden_size // num_attention_heads)
+    if model_type == "mixtral":
+        cfg["num_local_experts"] = int(num_local_experts)
+        cfg["num_experts_per_tok"] = int(num_experts_per_tok)
     if quantization is not None:
         cfg["quantization"] = dict(quantization)
         cfg["quantization_config"] = dict(quantization)
@@ -66,7 +70,7 @@ def build_config(*, model_type: str, vocab_size: int, hidden_size: int, num_hidd
 
 
 def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", norm_jitter: float = 0.0,
-                 weight_std: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                 weight_std: Optional[float] = None, router_gain: float = 1.0) -> Dict[str, torch.Tensor]:
     """Random weights keyed like an MLX / HF checkpoint.  ``weight_std``: N(0, std) instead of
     the MLX initialisers (SURVEY §8d synthetic weights).  With ``attention_bias`` / ``mlp_bias`` in ``cfg`` the
     projections get a 1-D ``.bias`` each, drawn at about the RMS of the layer's outputs for inputs of unit RMS
@@ -109,9 +113,19 @@ def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", nor
         if cfg["model_type"] == "qwen3":
             w[p + "self_attn.q_norm.weight"] = norm(D)
             w[p + "self_attn.k_norm.weight"] = norm(D)
-        w[p + "mlp.gate_proj.weight"] = lin(I, H)
-        w[p + "mlp.down_proj.weight"] = lin(H, I)
-        w[p + "mlp.up_proj.weight"] = lin(I, H)
+        if cfg["model_type"] == "mixtral":
+            # the stacked form of mixtral.py:198-215: the router (scaled by router_gain, which spreads the gate logits) and
+            # SwitchGLU's three tensors, every expert drawn like the dense MLP's matrices
+            E = cfg["num_local_experts"]
+            m = p + "block_sparse_moe."
+            w[m + "gate.weight"] = (lin(E, H).to(torch.float32) * float(router_gain)).to(tdt)
+            w[m + "switch_mlp.gate_proj.weight"] = torch.stack([lin(I, H) for _ in range(E)])
+            w[m + "switch_mlp.down_proj.weight"] = torch.stack([lin(H, I) for _ in range(E)])
+            w[m + "switch_mlp.up_proj.weight"] = torch.stack([lin(I, H) for _ in range(E)])
+        else:
+            w[p + "mlp.gate_proj.weight"] = lin(I, H)
+            w[p + "mlp.down_proj.weight"] = lin(H, I)
+            w[p + "mlp.up_proj.weight"] = lin(I, H)
         w[p + "input_layernorm.weight"] = norm(H)
         w[p + "post_attention_layernorm.weight"] = norm(H)
     w["model.norm.weight"] = norm(H)
@@ -188,6 +202,40 @@ def phi3_config(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
+_MIXTRAL_EXPERT_NAMES = (("gate_proj", "w1"), ("down_proj", "w2"), ("up_proj", "w3"))      # mixtral.py:203
+
+
+def unstack_experts(w: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A Mixtral checkpoint in the stacked form (``block_sparse_moe.switch_mlp.*``, 3-D) in the per-expert form of the
+    original checkpoints (``block_sparse_moe.experts.<e>.{w1,w2,w3}``, 2-D): the inverse of mixtral.py:198-215."""
+    out: Dict[str, torch.Tensor] = {}
+    for k, t in w.items():
+        for stacked, single in _MIXTRAL_EXPERT_NAMES:
+            tag = f".block_sparse_moe.switch_mlp.{stacked}.weight"
+            if k.endswith(tag):
+                for e in range(t.shape[0]):
+                    out[f"{k[: -len(tag)]}.block_sparse_moe.experts.{e}.{single}.weight"] = t[e].contiguous()
+                break
+        else:
+            out[k] = t
+    return out
+
+
+def stack_experts(w: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of ``unstack_experts`` (what the reference's ``sanitize`` does)."""
+    out = {k: t for k, t in w.items() if ".block_sparse_moe.experts." not in k}
+    groups: Dict[str, Dict[int, torch.Tensor]] = {}
+    for k, t in w.items():
+        if ".block_sparse_moe.experts." in k:
+            head, rest = k.split(".block_sparse_moe.experts.")
+            e, single, _ = rest.split(".")
+            stacked = {s: n for n, s in _MIXTRAL_EXPERT_NAMES}[single]
+            groups.setdefault(f"{head}.block_sparse_moe.switch_mlp.{stacked}.weight", {})[int(e)] = t
+    for k, parts in groups.items():
+        out[k] = torch.stack([parts[e] for e in range(len(parts))])
+    return out
+
+
 def build_byte_tokenizer(dst: Path) -> int:
     """Writes a byte-level HF fast tokenizer (256 byte tokens + <|endoftext|>, <|im_start|>,
     <|im_end|>) with a ChatML template.  Returns its vocabulary size."""
@@ -216,8 +264,13 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
                      head_dim: Optional[int] = None, with_tokenizer: bool = True, norm_jitter: float = 0.0,
                      weight_std: Optional[float] = None, rms_norm_eps: float = 1e-6,
                      max_position_embeddings: int = 4096, attention_bias: bool = False, mlp_bias: bool = False,
-                     rope_traditional: bool = False) -> Dict[str, Any]:
-    """scripts/build_tiny_model.py:104-160.  Returns the config dict it wrote."""
+                     rope_traditional: bool = False, num_local_experts: int = 4, num_experts_per_tok: int = 2,
+                     expert_names: str = "stacked", router_gain: float = 1.0) -> Dict[str, Any]:
+    """scripts/build_tiny_model.py:104-160.  Returns the config dict it wrote.
+
+    ``model_type="mixtral"``: ``num_local_experts`` experts of ``intermediate_size`` each, ``num_experts_per_tok`` of them per
+    token; ``expert_names`` = "stacked" (``switch_mlp.*``, 3-D) or "per_expert" (``experts.<e>.{w1,w2,w3}``, the same numbers);
+    ``router_gain`` scales the router's weights.  Dense 16-bit only: pass ``quantize_model=False`` and a 16-bit ``dtype``."""
     from safetensors.torch import save_file
 
     dst = Path(dst)
@@ -231,6 +284,17 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
         if head_dim is not None and head_dim != hidden_size // heads:
             raise ValueError("phi3: head_dim is hidden_size // heads")
         model_type, head_dim = "llama", None
+    mixtral = model_type == "mixtral"
+    if mixtral:
+        if quantize_model or dtype == "float32":
+            raise ValueError("mixtral: dense bfloat16 / float16 checkpoints only (quantize_model=False, a 16-bit dtype)")
+        if tie_word_embeddings or attention_bias or mlp_bias:
+            raise ValueError("mixtral has neither a tied lm_head nor linear biases: pass tie_word_embeddings=False")
+        if expert_names not in ("stacked", "per_expert"):
+            raise ValueError("expert_names is 'stacked' or 'per_expert'")
+        if head_dim is not None and head_dim != hidden_size // heads:
+            raise ValueError("mixtral: head_dim is hidden_size // heads")
+        head_dim = None
     tok_vocab = build_byte_tokenizer(dst) if with_tokenizer else 0
     if vocab_size is None:
         vocab_size = 151936                                  # build_tiny_model.py:125 fallback
@@ -242,8 +306,11 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
                        num_attention_heads=heads, num_key_value_heads=kv_heads, rope_theta=rope_theta,
                        tie_word_embeddings=tie_word_embeddings, quantization=quant, head_dim=head_dim,
                        rms_norm_eps=rms_norm_eps, max_position_embeddings=max_position_embeddings,
-                       attention_bias=attention_bias, mlp_bias=mlp_bias, rope_traditional=rope_traditional)
-    w = init_weights(cfg, seed=seed, dtype=dtype, norm_jitter=norm_jitter, weight_std=weight_std)
+                       attention_bias=attention_bias, mlp_bias=mlp_bias, rope_traditional=rope_traditional,
+                       num_local_experts=num_local_experts, num_experts_per_tok=num_experts_per_tok)
+    w = init_weights(cfg, seed=seed, dtype=dtype, norm_jitter=norm_jitter, weight_std=weight_std, router_gain=router_gain)
+    if mixtral and expert_names == "per_expert":
+        w = unstack_experts(w)
     if quantize_model:
         w = quantize_weights(w, q_group_size, q_bits)
     if phi3:
