@@ -205,6 +205,32 @@ int mi_engine_set_adapter_lora(mi_engine* e, int adapter, int layer, const char*
                                int rank, float scale, int dtype, int on_device);
 int mi_engine_clear_adapter(mi_engine* e, int adapter);
 
+/* DoRA (mlx-lm DoRALinear; adapter_config.json "fine_tune_type": "dora"): a LoRA entry with one more factor, the magnitude
+ * m (N,) float32, N = the rows of the named projection.  mi_engine_set_dora is mi_engine_set_lora and
+ * mi_engine_set_adapter_dora is mi_engine_set_adapter_lora with that argument: the same projection names, ranks 1..64, float32
+ * factors, MI_ARCH_PHI3 fused projections (m is cut by parts, as B is cut by columns), rope_traditional regrouping (the m of
+ * q_proj / k_proj follows the columns of B), exclusion of the engine-wide adapter and the slots, slot generation bump and
+ * "a refused call changes nothing".  Arithmetic of an adapted row, T = the dtype of x in that call, W (N, K) the base matrix:
+ *   y   = T(x W^T);  out = T(y + T(scale (x A) B))                      -- the LoRA entry, bit for bit
+ *   g[n] = float32(m[n] / || float32(W)[n, :] + (scale B^T A^T)[n, :] ||_2)
+ *   out = T(T(g[n]) * out), then the residual add / silu(gate) * up as always.
+ * g is computed ONCE per call of these functions, by a kernel of fixed summation order (the same inputs give the same bits),
+ * and kept as unrounded float32; the up-add launch rounds it to the T of each call.  It needs the final weights: before
+ * mi_engine_finalize the call is MI_ERR_INVALID.  LoRA and DoRA entries may sit in different slots and in different projections
+ * of one slot; setting LoRA over a DoRA entry drops its gain and the reverse adds one; mi_engine_clear_adapter frees it.  While
+ * no resident entry of a matrix carries a gain its steps launch exactly the kernels of a LoRA-only engine; where one does,
+ * rows whose adapter has no gain (and rows without an adapter) take no multiplication and keep their bits.
+ * Refused, nothing changed: a projection whose base weights are quantised (mlx-lm multiplies x by the dtype-rounded
+ * dequantised matrix there -- another product than QuantizedLinear's, which no kernel here computes) and a projection that
+ * carries a linear bias (the reference adds the bias after the gain, the base kernels add it before): MI_ERR_UNSUPPORTED; a float32 model
+ * (desc.act_dtype MI_F32: the gain kernel reads bf16 / f16 matrices): MI_ERR_UNSUPPORTED; an
+ * m[n] that is not finite, or a row of W + scale (A B)^T whose norm is 0: MI_ERR_INVALID naming the projection.
+ * The arithmetic restates mlx-lm's DoRALinear from its published formula; it could not be run against mlx-lm. */
+int mi_engine_set_dora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, const void* m, int rank,
+                       float scale, int dtype, int on_device);
+int mi_engine_set_adapter_dora(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B,
+                               const void* m, int rank, float scale, int dtype, int on_device);
+
 /* checks that every tensor was set (a missing `.bias` of a set bias flag: MI_ERR_NOTFOUND with its name), fuses q|k|v and
  * gate|up buffers, regroups q / k for rope_traditional, builds RoPE tables */
 int mi_engine_finalize(mi_engine* e);

@@ -20,6 +20,8 @@
  *   mi_op_sample_rowbias  ... and a call-wide logit_bias list (utils.py:346-349) + the per-row table (no counterpart)
  *   mi_op_lora_rows   LoRALinear's term y + (scale * ((x A) B)).astype(x.dtype), each row with its own adapter (the per-request
  *                     table has no counterpart in the reference)
+ *   mi_op_dora_gain / mi_op_dora_rows   mlx-lm DoRALinear's m / ||W + scale (A B)^T|| per output column, and the LoRA term followed
+ *                     by that factor (restated from the published formula; mlx-lm is not among the reference's sources)
  *   mi_op_kv_copy_tokens  the tail copy of mi_kv_fork_row (no counterpart in the reference)
  *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
  *   mi_op_moe_route / mi_op_moe_linear / mi_op_moe_mlp   MixtralSparseMoeBlock: mixtral.py:108-119 (gate, argpartition, softmax,
@@ -177,6 +179,25 @@ int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int 
                     const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
                     const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
                     float* t, void* y, int ldy, void* resid, int ldr, int stages);
+/* DoRA's gain kernel (lora_rows.hip) on its own, what mi_engine_set_dora runs once per adapted part:
+ *   gain[i] = m[i] / || W[row0 + i, :] + scale sum_j B[j][i] A[:, j] ||_2,  i in [0, n)
+ * w: a dense MI_WK_BF16 / MI_WK_F16 matrix, row-major or tile-major (mi_op_repack_tiled); rows [row0, row0 + n) are one part of
+ * it.  A [K][rank], B [rank][n], m [n] and gain [n]: DEVICE float32.  float32 accumulation in a fixed order, no atomics: run to
+ * run, and row-major against tile-major, the bits are the same.  A row whose norm is 0 gets NaN (the engine refuses such an
+ * adapter).  MI_ERR_INVALID, nothing launched: a null pointer, rank outside 1..64, rows outside the matrix, a misaligned
+ * buffer, a tile-major matrix with N % 16 != 0 or K % 32 != 0; MI_ERR_UNSUPPORTED: any other weight kind. */
+int mi_op_dora_gain(const mi_op_linear* w, const float* A, const float* B, const float* m, int rank, float scale, int row0, int n,
+                    float* gain);
+/* mi_op_lora_rows with one more HOST table, tab_gain [n_parts][MI_MAX_ADAPTERS + 1] of DEVICE pointers (float32 [n[p]], as
+ * mi_op_dora_gain writes them; NULL: a plain LoRA entry): the up stage ends a row whose entry has a gain with
+ * y' = T(T(gain[c]) * y') ahead of the residual add.  The gain-aware instantiation of the up-add kernel runs exactly when some
+ * entry has a gain; rows whose entry has none, and rows without an adapter, then take no multiplication -- their outputs are
+ * mi_op_lora_rows', bit for bit.  Refusals as mi_op_lora_rows, and MI_ERR_INVALID, nothing launched: a null tab_gain, a gain on
+ * an entry without A / B, a gain that is not 4-byte aligned. */
+int mi_op_dora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                    const float* const* tab_gain, float* t, void* y, int ldy, void* resid, int ldr, int stages);
 /* the copy of mi_kv_fork_row (mi355_decode.h) on its own, one launch: in each of `layers` layers (layer_elems elements apart),
  * for each of Hkv heads (head_stride elements apart) and in kcache and vcache alike, the n_tokens x D elements at element
  * offset src_off (of head 0, inside the layer) are copied to dst_off, in 16-byte pieces.  kv_dtype = MI_F32 / MI_BF16 /

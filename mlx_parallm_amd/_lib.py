@@ -88,6 +88,8 @@ SIGNATURES = {
     "mi_engine_set_lora": (C.c_int, [_P, C.c_int, C.c_char_p, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
     "mi_engine_set_adapter_lora": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
     "mi_engine_clear_adapter": (C.c_int, [_P, C.c_int]),
+    "mi_engine_set_dora": (C.c_int, [_P, C.c_int, C.c_char_p, _P, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
+    "mi_engine_set_adapter_dora": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, _P, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int]),
     "mi_engine_finalize": (C.c_int, [_P]),
     "mi_kv_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "mi_kv_create_paged": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -135,6 +137,9 @@ SIGNATURES = {
     "mi_op_swiglu_rows": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_op_lora_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _I32P, _I32P,
                                   C.POINTER(_P), C.POINTER(_P), _I32P, _F32P, _P, _P, C.c_int, _P, C.c_int, C.c_int]),
+    "mi_op_dora_gain": (C.c_int, [C.POINTER(OpLinear), _P, _P, _P, C.c_int, C.c_float, C.c_int, C.c_int, _P]),
+    "mi_op_dora_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _I32P, _I32P,
+                                  C.POINTER(_P), C.POINTER(_P), _I32P, _F32P, C.POINTER(_P), _P, _P, C.c_int, _P, C.c_int, C.c_int]),
     "mi_op_kv_copy_tokens": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "mi_op_tiled_bytes": (C.c_uint64, [C.POINTER(OpLinear)]),
     "mi_op_repack_tiled": (C.c_int, [C.POINTER(OpLinear), _P]),

@@ -195,6 +195,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     rc.table = f.adapters->d; rc.row_adapter = e->d_row_adapter; rc.n_parts = f.n_parts;
     for (int i = 0, r0 = 0; i < f.n_parts; ++i) { rc.row0[i] = r0; rc.n[i] = f.part_rows[i]; r0 += f.part_rows[i]; }
     rc.M = (int)R; rc.K = K; rc.act = act; rc.rnd = rnd_; rc.t = e->lora_rt;
+    rc.gain = f.adapters->gains > 0;
     return rc;
   };
   // o_proj / down_proj (c: the EPI_RESID call): an adapted one stores y = T(acc [+ b]) to a scratch buffer and ONE launch

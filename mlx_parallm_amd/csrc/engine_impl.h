@@ -31,6 +31,7 @@ struct AdapterTable {
   AdapterPart h[3][LORA_TABLE_COLS];
   AdapterPart* d = nullptr;
   int set = 0;
+  int gains = 0;                 // entries that carry a DoRA gain (> 0: the up-add's gain-aware instantiation, lora_rows.h)
   bool engine_wide() const { return h[0][LORA_ENGINE_COL].a || h[1][LORA_ENGINE_COL].a || h[2][LORA_ENGINE_COL].a; }
 };
 

@@ -1,6 +1,7 @@
 // engine_load.hip -- a checkpoint's tensors and LoRA factors into an engine, and mi_engine_finalize: the fused matrices are
 // checked, regrouped (rope_traditional), repacked tile-major and given their persistent second copies.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "engine_impl.h"
@@ -258,7 +259,7 @@ void mi::free_linear(FusedLinear& f) {
   hipFree(f.w); hipFree(f.scales); hipFree(f.biases); hipFree(f.w_hilo); hipFree(f.w_gu8); hipFree(f.bias);
   if (f.adapters != nullptr) {
     for (auto& part : f.adapters->h)
-      for (AdapterPart& ap : part) { hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b)); }
+      for (AdapterPart& ap : part) { hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b)); hipFree(const_cast<float*>(ap.gain)); }
     hipFree(f.adapters->d);
     delete f.adapters;
     f.adapters = nullptr;
@@ -319,12 +320,25 @@ int mi_engine_set_tensor(mi_engine* e, const char* name_c, const void* data, con
 // one adapted range of table column `col` (a per-request slot, or LORA_ENGINE_COL: the engine-wide adapter): entry
 // [pj.part][col] of the matrix's table (lora_rows.h), hot-swapped when it exists.  The stream is drained first and the table
 // entry is written with a blocking copy: no step is in flight.
-static int set_adapter_part(mi_engine* e, int col, LayerW& l, const Proj& pj, const void* A, const void* B, int rank, float scale, int on_device) {
+//
+// Two steps, so that a call that covers several parts (a MI_ARCH_PHI3 fused projection) changes nothing when one of them is
+// refused: make_adapter_part builds the device buffers of an entry -- with m (HOST, the part's n values; null: plain LoRA) also
+// the DoRA gain, one launch of launch_dora_gain on the finalized matrix, read back and checked -- and set_adapter_part
+// publishes it.
+static void free_adapter_part(AdapterPart& ap) {
+  hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b)); hipFree(const_cast<float*>(ap.gain));
+  ap = AdapterPart{};
+}
+
+static int make_adapter_part(mi_engine* e, LayerW& l, const Proj& pj, const void* A, const void* B, const float* m, int rank, float scale,
+                             int on_device, const std::string& name, AdapterPart* out) {
   const mi_model_desc& d = e->d;
   FusedLinear* f = pj.f;
   const int QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, K = pj.K, n = f->part_rows[pj.part];
   int row0 = 0;
   for (int i = 0; i < pj.part; ++i) row0 += f->part_rows[i];
+  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
+  const bool regroup = d.rope_traditional && f == &l.qkv && row0 < QD + KD;
   MI_HIP(hipStreamSynchronize(e->stream));
   if (f->adapters == nullptr) {
     AdapterPart* dt = nullptr;
@@ -333,20 +347,45 @@ static int set_adapter_part(mi_engine* e, int col, LayerW& l, const Proj& pj, co
     f->adapters = new AdapterTable();
     f->adapters->d = dt;
   }
-  float* na = nullptr; float* nb = nullptr;
-  MI_HIP(hipMalloc(&na, (size_t)K * rank * sizeof(float)));
-  if (hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); hipFree(na); return fail(MI_ERR_RUNTIME, "LoRA: out of device memory"); }
+  float* na = nullptr; float* nb = nullptr; float* dm = nullptr; float* ng = nullptr;
+  auto drop = [&](int rc) { hipFree(na); hipFree(nb); hipFree(dm); hipFree(ng); return rc; };
+  if (hipMalloc(&na, (size_t)K * rank * sizeof(float)) != hipSuccess || hipMalloc(&nb, (size_t)rank * n * sizeof(float)) != hipSuccess ||
+      (m != nullptr && (hipMalloc(&dm, (size_t)n * sizeof(float)) != hipSuccess || hipMalloc(&ng, (size_t)n * sizeof(float)) != hipSuccess))) {
+    (void)hipGetLastError();
+    return drop(fail(MI_ERR_RUNTIME, name + (m != nullptr ? ": DoRA: out of device memory" : ": LoRA: out of device memory")));
+  }
   int rc = copy_in(na, A, (size_t)K * rank * sizeof(float), on_device, e->stream);
   if (rc == MI_OK) rc = copy_in(nb, B, (size_t)rank * n * sizeof(float), on_device, e->stream);
-  // rope_traditional: the output columns of an adapted q / k projection follow the regrouped rows of the matrix
-  if (rc == MI_OK && d.rope_traditional && f == &l.qkv && row0 < QD + KD) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
+  if (rc == MI_OK && regroup) rc = head_perm_inplace(e, nb, (size_t)rank * n, d.head_dim, sizeof(float));
+  if (rc == MI_OK && m != nullptr) {
+    // DoRA: m follows the rows like B's columns; the gain of the part from the matrix as the linears read it
+    std::vector<float> hg((size_t)n);
+    rc = copy_in(dm, m, (size_t)n * sizeof(float), 0, e->stream);
+    if (rc == MI_OK && regroup) rc = head_perm_inplace(e, dm, (size_t)n, d.head_dim, sizeof(float));
+    if (rc == MI_OK) rc = launch_dora_gain(f->W, row0, n, na, nb, dm, rank, scale, ng, e->stream);
+    if (rc == MI_OK && (hipMemcpyAsync(hg.data(), ng, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+                        hipStreamSynchronize(e->stream) != hipSuccess))
+      rc = fail(MI_ERR_RUNTIME, name + ": computing the DoRA gain failed");
+    for (int i = 0; rc == MI_OK && i < n; ++i)
+      if (!std::isfinite(hg[i]))
+        rc = fail(MI_ERR_INVALID, name + ": DoRA: a row of W + scale (A B)^T has norm 0 (or m / norm is not finite); nothing was changed");
+  }
+  if (rc != MI_OK) return drop(rc);
+  hipFree(dm);
+  *out = AdapterPart{na, nb, rank, scale, ng};
+  return MI_OK;
+}
+
+static int set_adapter_part(mi_engine* e, int col, LayerW& l, const Proj& pj, AdapterPart& fresh) {
+  FusedLinear* f = pj.f;
   AdapterPart& slot = f->adapters->h[pj.part][col];
-  const AdapterPart fresh{na, nb, rank, scale};
-  if (rc == MI_OK && hipMemcpy(f->adapters->d + pj.part * LORA_TABLE_COLS + col, &fresh, sizeof(fresh), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(MI_ERR_RUNTIME, "adapter table: hipMemcpy failed");
-  if (rc != MI_OK) { hipFree(na); hipFree(nb); return rc; }
+  if (hipMemcpy(f->adapters->d + pj.part * LORA_TABLE_COLS + col, &fresh, sizeof(fresh), hipMemcpyHostToDevice) != hipSuccess) {
+    free_adapter_part(fresh);
+    return fail(MI_ERR_RUNTIME, "adapter table: hipMemcpy failed");
+  }
   const bool was_empty = slot.a == nullptr;
-  hipFree(const_cast<float*>(slot.a)); hipFree(const_cast<float*>(slot.b));
+  f->adapters->gains += (fresh.gain != nullptr) - (slot.gain != nullptr);
+  free_adapter_part(slot);
   slot = fresh;
   f->adapters->set += was_empty;
   if (col == LORA_ENGINE_COL) {
@@ -361,9 +400,10 @@ static int set_adapter_part(mi_engine* e, int col, LayerW& l, const Proj& pj, co
 }
 
 // mi_engine_set_lora (adapter < 0: the engine-wide adapter, the table's private column) and mi_engine_set_adapter_lora (a slot)
-static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
-                        int dtype, int on_device) {
-  if (!e || !proj || !A || !B) return fail(MI_ERR_INVALID, "null argument");
+// dora: mi_engine_set_dora / mi_engine_set_adapter_dora -- m (N,) float32 rides with the factors and every part gets a gain
+static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, const void* m, bool dora,
+                        int rank, float scale, int dtype, int on_device) {
+  if (!e || !proj || !A || !B || (dora && !m)) return fail(MI_ERR_INVALID, "null argument");
   if (adapter >= MI_MAX_ADAPTERS) return fail(MI_ERR_INVALID, "adapter slot must be in [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
   if (adapter >= 0 && e->engine_lora)
     return fail(MI_ERR_UNSUPPORTED, "mi_engine_set_adapter_lora: this engine carries the engine-wide adapter of mi_engine_set_lora; the two exclude each other");
@@ -382,16 +422,37 @@ static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, 
   if (d.arch == MI_ARCH_MIXTRAL && p.compare(0, 17, "block_sparse_moe.") == 0)
     return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (arch mixtral: the attention projections only)");
   if (!find_proj(d, l, p, &pj)) return fail(MI_ERR_UNSUPPORTED, "LoRA on " + p + " is not supported (the linears of a block only)");
-  auto put = [&](const Proj& part, const void* a, const void* b) {
-    return set_adapter_part(e, adapter >= 0 ? adapter : LORA_ENGINE_COL, l, part, a, b, rank, scale, on_device);
-  };
-  if (pj.part >= 0) return put(pj, A, B);
-  // MI_ARCH_PHI3, qkv_proj / gate_up_proj: A is shared, B (rank, N) is cut by columns into the parts -- what one call per
-  // part with the column slice does on an engine with split projections
-  int N = 0;
-  for (int i = 0; i < pj.f->n_parts; ++i) N += pj.f->part_rows[i];
+  const std::string name = "model.layers." + std::to_string(layer) + "." + p;
+  int N = 0;                                       // rows of the named projection
+  if (pj.part >= 0) N = pj.f->part_rows[pj.part];
+  else for (int i = 0; i < pj.f->n_parts; ++i) N += pj.f->part_rows[i];
+  std::vector<float> hm;                           // DoRA: m on the host, checked before anything is made
+  if (dora) {
+    if (!e->finalized)
+      return fail(MI_ERR_INVALID, name + ": DoRA needs the final weights (the gain is computed from them): call mi_engine_finalize first");
+    if (pj.f->quant)
+      return fail(MI_ERR_UNSUPPORTED, name + ": DoRA on a projection whose base weights are quantised is not supported");
+    if (pj.f->bias != nullptr)
+      return fail(MI_ERR_UNSUPPORTED, name + ": DoRA on a projection that carries a linear bias is not supported");
+    if (pj.f->W.wk != WK_BF16 && pj.f->W.wk != WK_F16)
+      return fail(MI_ERR_UNSUPPORTED, name + ": DoRA needs dense bf16 / f16 base weights");
+    hm.resize((size_t)N);
+    MI_HIP(hipMemcpy(hm.data(), m, hm.size() * sizeof(float), on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    for (int i = 0; i < N; ++i)
+      if (!std::isfinite(hm[i])) return fail(MI_ERR_INVALID, name + ": DoRA: m[" + std::to_string(i) + "] is not finite; nothing was changed");
+  }
+  const int col = adapter >= 0 ? adapter : LORA_ENGINE_COL;
+  if (pj.part >= 0) {
+    AdapterPart fresh;
+    MI_TRY(make_adapter_part(e, l, pj, A, B, dora ? hm.data() : nullptr, rank, scale, on_device, name, &fresh));
+    return set_adapter_part(e, col, l, pj, fresh);
+  }
+  // MI_ARCH_PHI3, qkv_proj / gate_up_proj: A is shared, B (rank, N) is cut by columns into the parts (and m by parts) -- what
+  // one call per part with the column slice does on an engine with split projections.  Every part is made before the first is
+  // published.
   std::vector<float> hb((size_t)rank * N), slice;
   MI_HIP(hipMemcpy(hb.data(), B, hb.size() * sizeof(float), on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+  AdapterPart made[3];
   int col0 = 0;
   for (int i = 0; i < pj.f->n_parts; ++i) {
     const int n = pj.f->part_rows[i];
@@ -399,29 +460,55 @@ static int set_lora_any(mi_engine* e, int adapter, int layer, const char* proj, 
     for (int r = 0; r < rank; ++r) memcpy(&slice[(size_t)r * n], &hb[(size_t)r * N + col0], (size_t)n * sizeof(float));
     float* sb = slice.data();
     void* db = nullptr;
+    int rc = MI_OK;
     if (on_device) {                               // (A stays where it is: the slice goes where A is)
-      MI_HIP(hipMalloc(&db, slice.size() * sizeof(float)));
-      if (hipMemcpy(db, sb, slice.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { hipFree(db); return fail(MI_ERR_RUNTIME, "LoRA: copying a column slice failed"); }
+      if (hipMalloc(&db, slice.size() * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); db = nullptr; rc = fail(MI_ERR_RUNTIME, name + ": out of device memory for a column slice"); }
+      else if (hipMemcpy(db, sb, slice.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI_ERR_RUNTIME, name + ": copying a column slice failed");
     }
     const Proj part{pj.f, i, pj.K, pj.attn};
-    const int rc = put(part, A, on_device ? db : (const void*)sb);
+    if (rc == MI_OK)
+      rc = make_adapter_part(e, l, part, A, on_device ? db : (const void*)sb, dora ? hm.data() + col0 : nullptr, rank, scale,
+                             on_device, name, &made[i]);
     hipFree(db);
-    MI_TRY(rc);
+    if (rc != MI_OK) {
+      for (int j = 0; j < i; ++j) free_adapter_part(made[j]);
+      return rc;
+    }
     col0 += n;
+  }
+  for (int i = 0; i < pj.f->n_parts; ++i) {
+    const Proj part{pj.f, i, pj.K, pj.attn};
+    const int rc = set_adapter_part(e, col, l, part, made[i]);
+    if (rc != MI_OK) {
+      for (int j = i + 1; j < pj.f->n_parts; ++j) free_adapter_part(made[j]);
+      return rc;
+    }
   }
   return MI_OK;
 }
 
 int mi_engine_set_lora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, int rank, float scale,
                        int dtype, int on_device) {
-  return set_lora_any(e, -1, layer, proj, A, B, rank, scale, dtype, on_device);
+  return set_lora_any(e, -1, layer, proj, A, B, nullptr, false, rank, scale, dtype, on_device);
 }
 
 int mi_engine_set_adapter_lora(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, int rank,
                                float scale, int dtype, int on_device) {
   if (adapter < 0 || adapter >= MI_MAX_ADAPTERS)
     return fail(MI_ERR_INVALID, "mi_engine_set_adapter_lora: adapter " + std::to_string(adapter) + " is outside [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
-  return set_lora_any(e, adapter, layer, proj, A, B, rank, scale, dtype, on_device);
+  return set_lora_any(e, adapter, layer, proj, A, B, nullptr, false, rank, scale, dtype, on_device);
+}
+
+int mi_engine_set_dora(mi_engine* e, int layer, const char* proj, const void* A, const void* B, const void* m, int rank, float scale,
+                       int dtype, int on_device) {
+  return set_lora_any(e, -1, layer, proj, A, B, m, true, rank, scale, dtype, on_device);
+}
+
+int mi_engine_set_adapter_dora(mi_engine* e, int adapter, int layer, const char* proj, const void* A, const void* B, const void* m,
+                               int rank, float scale, int dtype, int on_device) {
+  if (adapter < 0 || adapter >= MI_MAX_ADAPTERS)
+    return fail(MI_ERR_INVALID, "mi_engine_set_adapter_dora: adapter " + std::to_string(adapter) + " is outside [0, " + std::to_string(MI_MAX_ADAPTERS) + ")");
+  return set_lora_any(e, adapter, layer, proj, A, B, m, true, rank, scale, dtype, on_device);
 }
 
 int mi_engine_clear_adapter(mi_engine* e, int adapter) {
@@ -437,8 +524,8 @@ int mi_engine_clear_adapter(mi_engine* e, int adapter) {
       for (auto& part : f->adapters->h) {
         AdapterPart& ap = part[adapter];
         if (ap.a == nullptr) continue;
-        hipFree(const_cast<float*>(ap.a)); hipFree(const_cast<float*>(ap.b));
-        ap = AdapterPart{};
+        f->adapters->gains -= ap.gain != nullptr;
+        free_adapter_part(ap);
         --f->adapters->set;
         changed = true;
       }

@@ -3,6 +3,9 @@
 // kernels that sit at an occupancy edge), behind a plain-store launch of the base linear.
 //   lora_down_by_row_kernel    t = x A of each row's own adapter, for every part of the fused matrix the adapter covers
 //   lora_up_add_by_row_kernel  y += T(scale (t B)) with the row's own B, rank and scale; with a residual operand also h += y'
+//                              <T, true> (launched only for a table that holds a DoRA entry): an entry with a gain then ends its
+//                              row with y' = T(T(g[n]) y')
+//   dora_gain_kernel           g[n] = m[n] / ||W[n] + scale (A B)^T[n]|| of one part, once when a DoRA entry is set
 //   swiglu_rows_kernel         gate|up with an adapted range: the linear stores T(acc) to a [rows][2 I] buffer (EPI_STORE), the
 //                              up-add puts the terms on it and this kernel writes act = silu(gate) * up with the rounding
 //                              points of the fused epilogues (gemv_v1.hip EPI_SWIGLU: sig, g * sig, s * u, each rounded to
@@ -114,7 +117,20 @@ struct UpRowsParams {
 //   y[m][row0 + n] = T(y + T(scale * sum_j t[m][part][j] B[j][n]))      lora_dot and lora_add (linear_epilogue.h)
 // with B, rank and scale of the row's own adapter.  resid != null: h[m][n] = T(h[m][n] + y') instead of the store to y (the
 // residual add of EPI_RESID, kernels.h), for EVERY row -- a row whose adapter does not cover the part adds the stored y.
+//
+// GAIN (DoRA): an entry with a gain ends its row with y' = T(T(g[n]) * y') ahead of the residual add -- g rounded to the call's
+// T here, because one entry serves calls of different T (layer 0's q|k|v of the float32-KV mode rounds to 16 bits, every later
+// linear does not).  The product and the residual add stay two roundings (gain_mul: contract off).  Rows whose entry has no
+// gain, and rows without an entry, take no multiplication: their bits are those of the plain instantiation.
 template <typename AT>
+__device__ __forceinline__ float gain_mul(float g, float v, int rnd) {
+#pragma clang fp contract(off)
+  const float gt = rounded<AT>(g, rnd);
+  const float pr = gt * v;
+  return rounded<AT>(pr, rnd);
+}
+
+template <typename AT, bool GAIN>
 __global__ __launch_bounds__(NTHR) void lora_up_add_by_row_kernel(UpRowsParams p, AT* y, int ldy, AT* resid, int ldr) {
   const int m = blockIdx.x, r = blockIdx.y;
   const int ln = p.n[r];
@@ -133,6 +149,9 @@ __global__ __launch_bounds__(NTHR) void lora_up_add_by_row_kernel(UpRowsParams p
     AT* o = y + (size_t)m * ldy + p.row0[r] + n;
     float v = to_f32(*o);
     if (lb != nullptr) v = lora_add<AT>(v, sc, lora_dot(tt, lb + n, ln, rk), p.rnd, RND_NONE);
+    if constexpr (GAIN) {
+      if (lb != nullptr && ap.gain != nullptr) v = gain_mul<AT>(ap.gain[n], v, p.rnd);
+    }
     if (resid != nullptr) {
       AT* h = resid + (size_t)m * ldr + p.row0[r] + n;
       *h = store_act<AT>(to_f32(*h) + v, p.rnd);
@@ -168,6 +187,71 @@ __global__ __launch_bounds__(NTHR) void swiglu_rows_kernel(const AT* x, int ldx,
       ov[j] = from_f32<AT>(swiglu_value<AT, true>(to_f32<AT>(gv[j]), to_f32<AT>(uv[j]), rnd));      // (the float64 sigmoid)
     }
     *(vec*)(out + m * (size_t)ldo + n) = ov;
+  }
+}
+
+struct GainParams {
+  const void* w; int layout, K, row0, n;
+  const float* a; const float* b; const float* m; int rank; float scale;
+  float* gain;
+};
+
+// W[row][k] of a dense 16-bit matrix, row-major or tile-major (repack.hip)
+template <typename WT>
+__device__ __forceinline__ float dense16_at(const void* w, int layout, size_t row, int k, int K) {
+  if (layout == 1) return to_f32(*(const WT*)((const char*)w + tiled_piece_dense16(row, k & ~7, K) + (size_t)(k & 7) * sizeof(WT)));
+  return to_f32(((const WT*)w)[row * (size_t)K + k]);
+}
+
+// DoRA's gain of the 16 rows [16 blockIdx.x, + 16) of a part: gain[i] = m[i] / sqrt(sum_k d[i][k]^2),
+//   d[i][k] = W[row0 + i][k] + sum_j A[k][j] . (scale . B[j][i]).
+// scale . B of the tile waits in LDS (one rounding each).  Thread tid owns k = tid, tid + 256, ...: per k, d starts from W and
+// takes the rank terms as fmaf in ascending j; d^2 joins the thread's running sum by fmaf, in ascending k.  Then the wave sum
+// (wave_sum: four row rotations, (a + b) + (c + d)), then the four waves in order.  No atomics, nothing depends on the layout
+// of W or on the grid: the same inputs give the same bits.  The longest chain of additions behind one norm is
+// ceil(K / 256) + 9; the error bound that follows from it stands in DESIGN.md §5 ("DoRA").
+// A norm of 0 (or one that is not finite) leaves NaN: the host refuses the adapter.
+template <typename WT>
+__global__ __launch_bounds__(NTHR) void dora_gain_kernel(GainParams p) {
+  __shared__ float sb[64][16];
+  __shared__ float red[4][16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * 16;
+  const int rows = min(16, p.n - n0);
+  const int rk = min(p.rank, 64);
+  for (int e = tid; e < rk * 16; e += NTHR) {
+    const int j = e >> 4, i = e & 15;
+    sb[j][i] = i < rows ? p.scale * p.b[(size_t)j * p.n + n0 + i] : 0.f;
+  }
+  __syncthreads();
+  float acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  const size_t r0 = (size_t)p.row0 + n0;
+  for (int k = tid; k < p.K; k += NTHR) {
+    float d[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) d[i] = dense16_at<WT>(p.w, p.layout, r0 + min(i, rows - 1), k, p.K);   // (a ragged tile repeats its last row)
+    const float* ar = p.a + (size_t)k * rk;
+#pragma unroll 4
+    for (int j = 0; j < rk; ++j) {
+      const float av = ar[j];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) d[i] = fmaf(av, sb[j][i], d[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = fmaf(d[i], d[i], acc[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float w = wave_sum(acc[i]);
+    if (lane == 0) red[wave][i] = w;
+  }
+  __syncthreads();
+  if (tid < rows) {
+    const float tot = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    const float denom = sqrtf(tot);
+    p.gain[n0 + tid] = (denom > 0.f && denom <= 3.0e38f) ? p.m[n0 + tid] / denom : __builtin_nanf("");
   }
 }
 
@@ -218,11 +302,37 @@ int launch_lora_up_add_by_row(const LoraRowsCall& c, void* y, int ldy, void* res
   p.table = c.table; p.row_adapter = c.row_adapter; p.t = c.t; p.rnd = c.rnd;
   for (int i = 0; i < c.n_parts; ++i) { p.row0[i] = c.row0[i]; p.n[i] = c.n[i]; }
   const dim3 grid(c.M, c.n_parts, (widest + UP_COLS - 1) / UP_COLS), block(NTHR);
-  switch (c.act) {
-    case MI_BF16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<bf16>, grid, block, 0, st, p, (bf16*)y, ldy, (bf16*)resid, ldr); break;
-    case MI_F16: hipLaunchKernelGGL(lora_up_add_by_row_kernel<f16>, grid, block, 0, st, p, (f16*)y, ldy, (f16*)resid, ldr); break;
-    case MI_F32: hipLaunchKernelGGL(lora_up_add_by_row_kernel<float>, grid, block, 0, st, p, (float*)y, ldy, (float*)resid, ldr); break;
+  if (c.gain) {                        // a table that holds a DoRA entry; every other call launches the plain instantiation
+    switch (c.act) {
+      case MI_BF16: hipLaunchKernelGGL((lora_up_add_by_row_kernel<bf16, true>), grid, block, 0, st, p, (bf16*)y, ldy, (bf16*)resid, ldr); break;
+      case MI_F16: hipLaunchKernelGGL((lora_up_add_by_row_kernel<f16, true>), grid, block, 0, st, p, (f16*)y, ldy, (f16*)resid, ldr); break;
+      case MI_F32: hipLaunchKernelGGL((lora_up_add_by_row_kernel<float, true>), grid, block, 0, st, p, (float*)y, ldy, (float*)resid, ldr); break;
+    }
+  } else {
+    switch (c.act) {
+      case MI_BF16: hipLaunchKernelGGL((lora_up_add_by_row_kernel<bf16, false>), grid, block, 0, st, p, (bf16*)y, ldy, (bf16*)resid, ldr); break;
+      case MI_F16: hipLaunchKernelGGL((lora_up_add_by_row_kernel<f16, false>), grid, block, 0, st, p, (f16*)y, ldy, (f16*)resid, ldr); break;
+      case MI_F32: hipLaunchKernelGGL((lora_up_add_by_row_kernel<float, false>), grid, block, 0, st, p, (float*)y, ldy, (float*)resid, ldr); break;
+    }
   }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int launch_dora_gain(const LinearW& W, int row0, int n, const float* A, const float* B, const float* m, int rank, float scale,
+                     float* gain, hipStream_t st) {
+  if (W.w == nullptr || A == nullptr || B == nullptr || m == nullptr || gain == nullptr) return fail(MI_ERR_INVALID, "dora_gain: null argument");
+  if (W.wk != WK_BF16 && W.wk != WK_F16) return fail(MI_ERR_UNSUPPORTED, "dora_gain: dense bf16 / f16 weights only");
+  if (rank < 1 || rank > 64) return fail(MI_ERR_INVALID, "dora_gain: rank outside 1..64");
+  if (W.K < 1 || W.N < 1 || n < 1 || row0 < 0 || (long long)row0 + n > W.N) return fail(MI_ERR_INVALID, "dora_gain: the rows lie outside the matrix");
+  if (W.layout != 0 && W.layout != 1) return fail(MI_ERR_INVALID, "dora_gain: bad layout");
+  if (W.layout == 1 && (W.K % 32 != 0 || W.N % 16 != 0)) return fail(MI_ERR_INVALID, "dora_gain: a tile-major matrix has N % 16 == 0 and K % 32 == 0");
+  if ((uintptr_t)W.w % 16 != 0 || (uintptr_t)A % 4 != 0 || (uintptr_t)B % 4 != 0 || (uintptr_t)m % 4 != 0 || (uintptr_t)gain % 4 != 0)
+    return fail(MI_ERR_INVALID, "dora_gain: misaligned buffer");
+  GainParams p{W.w, W.layout, W.K, row0, n, A, B, m, rank, scale, gain};
+  const dim3 grid((n + 15) / 16), block(NTHR);
+  if (W.wk == WK_BF16) hipLaunchKernelGGL(dora_gain_kernel<bf16>, grid, block, 0, st, p);
+  else hipLaunchKernelGGL(dora_gain_kernel<f16>, grid, block, 0, st, p);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

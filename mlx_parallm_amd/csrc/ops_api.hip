@@ -282,10 +282,11 @@ int mi_op_swiglu_rows(const void* x, int ldx, void* out, int ldo, int M, int I, 
 // lora_down_by_row_kernel and lora_up_add_by_row_kernel (lora_rows.hip) on their own: the two launches of lora_rows.h on the
 // caller's buffers, the adapter table uploaded from the host arrays for the length of the call.  Everything is validated
 // before the first launch -- the launchers' own refusals included, so that a call of both stages never runs half.
-int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
-                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
-                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
-                    float* t, void* y, int ldy, void* resid, int ldr, int stages) {
+// tab_gain: null for mi_op_lora_rows (no entry has a gain), the table of mi_op_dora_rows otherwise
+static int lora_rows_op(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                        const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                        const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                        const float* const* tab_gain, float* t, void* y, int ldy, void* resid, int ldr, int stages) {
   MI_TRY(ready());
   const bool down = (stages & MI_LORA_STAGE_DOWN) != 0, up = (stages & MI_LORA_STAGE_UP) != 0;
   if (stages < 1 || stages > (MI_LORA_STAGE_DOWN | MI_LORA_STAGE_UP)) return fail(MI_ERR_INVALID, "mi_op_lora_rows: stages is MI_LORA_STAGE_DOWN, _UP or both");
@@ -319,16 +320,51 @@ int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int 
     if ((uintptr_t)tab_a[i] % 16 != 0 || (uintptr_t)tab_b[i] % 16 != 0) return fail(MI_ERR_INVALID, "mi_op_lora_rows: A and B must be 16-byte aligned");
     table[i].a = tab_a[i]; table[i].b = tab_b[i]; table[i].rank = tab_rank[i]; table[i].scale = tab_scale[i];
   }
+  bool any_gain = false;
+  for (size_t i = 0; tab_gain != nullptr && i < table.size(); ++i) {
+    if (tab_gain[i] == nullptr) continue;
+    if (tab_a[i] == nullptr) return fail(MI_ERR_INVALID, "mi_op_dora_rows: a gain on an entry without A and B");
+    if ((uintptr_t)tab_gain[i] % sizeof(float) != 0) return fail(MI_ERR_INVALID, "mi_op_dora_rows: a gain must be 4-byte aligned");
+    table[i].gain = tab_gain[i];
+    any_gain = true;
+  }
   void* dtab = nullptr;
   FreeGuard guard{dtab};
   MI_HIP(hipMalloc(&dtab, table.size() * sizeof(AdapterPart)));
   MI_HIP(hipMemcpy(dtab, table.data(), table.size() * sizeof(AdapterPart), hipMemcpyHostToDevice));
   LoraRowsCall c;
   c.table = (const AdapterPart*)dtab; c.row_adapter = row_adapter; c.n_parts = n_parts; c.M = M; c.K = K; c.act = act; c.rnd = rnd;
-  c.t = t;
+  c.t = t; c.gain = any_gain;
   if (up) for (int r = 0; r < n_parts; ++r) { c.row0[r] = row0[r]; c.n[r] = n[r]; }
   if (down) MI_TRY(launch_lora_down_by_row(c, x, ldx, pro, norm_w, eps, nullptr));
   if (up) MI_TRY(launch_lora_up_add_by_row(c, y, ldy, resid, ldr, nullptr));
+  return finish();
+}
+
+int mi_op_lora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                    float* t, void* y, int ldy, void* resid, int ldr, int stages) {
+  return lora_rows_op(x, ldx, M, K, act, rnd, pro, norm_w, eps, row_adapter, n_parts, row0, n, tab_a, tab_b, tab_rank, tab_scale,
+                      nullptr, t, y, ldy, resid, ldr, stages);
+}
+
+// ... with the gains of DoRA entries in the table (the gain-aware instantiation of the up-add when one is set)
+int mi_op_dora_rows(const void* x, int ldx, int M, int K, int act, int rnd, int pro, const void* norm_w, float eps,
+                    const int32_t* row_adapter, int n_parts, const int32_t* row0, const int32_t* n,
+                    const float* const* tab_a, const float* const* tab_b, const int32_t* tab_rank, const float* tab_scale,
+                    const float* const* tab_gain, float* t, void* y, int ldy, void* resid, int ldr, int stages) {
+  if (!tab_gain) return fail(MI_ERR_INVALID, "mi_op_dora_rows: null argument");
+  return lora_rows_op(x, ldx, M, K, act, rnd, pro, norm_w, eps, row_adapter, n_parts, row0, n, tab_a, tab_b, tab_rank, tab_scale,
+                      tab_gain, t, y, ldy, resid, ldr, stages);
+}
+
+// dora_gain_kernel (lora_rows.hip) on its own; the launch validates its arguments
+int mi_op_dora_gain(const mi_op_linear* w, const float* A, const float* B, const float* m, int rank, float scale, int row0, int n,
+                    float* gain) {
+  if (!w) return fail(MI_ERR_INVALID, "mi_op_dora_gain: null argument");
+  MI_TRY(ready());
+  MI_TRY(launch_dora_gain(to_linear(w), row0, n, A, B, m, rank, scale, gain, nullptr));
   return finish();
 }
 

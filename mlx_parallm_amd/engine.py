@@ -415,6 +415,38 @@ class Engine:
                                                    C.c_void_p(tb.data_ptr()), int(ta.shape[1]), float(scale), L.MI_F32,
                                                    int(ta.is_cuda)))
 
+    @staticmethod
+    def _dora_factors(a, b, m):
+        import torch
+        ta = torch.as_tensor(a).to(torch.float32).contiguous()
+        tb = torch.as_tensor(b).to(torch.float32).contiguous()
+        tm = torch.as_tensor(m).to(torch.float32).contiguous()
+        if not (ta.is_cuda == tb.is_cuda == tm.is_cuda):
+            raise ValueError("DoRA factors must live on the same device")
+        if tm.dim() != 1 or tb.dim() != 2 or ta.dim() != 2 or tm.shape[0] != tb.shape[1] or ta.shape[1] != tb.shape[0]:
+            raise ValueError(f"DoRA factors: a (K, r), b (r, N), m (N,) expected, got {tuple(ta.shape)}, {tuple(tb.shape)}, {tuple(tm.shape)}")
+        if ta.is_cuda:
+            torch.cuda.synchronize()
+        return ta, tb, tm
+
+    def set_dora(self, layer: int, proj: str, a, b, m, scale: float) -> None:
+        """``mi_engine_set_dora``: ``set_lora`` with DoRA's magnitude ``m`` (N,) -- the adapted rows end with
+        ``T(T(g) * y)``, ``g = m / ||W + scale (a b)^T||`` per output column, computed once here from the final weights (the
+        engine must be finalized: ValueError before).  NotImplementedError, nothing changed: a projection whose base weights
+        are quantised or that carries a linear bias; ValueError: an ``m`` that is not finite, an adapted row of norm 0."""
+        ta, tb, tm = self._dora_factors(a, b, m)
+        L.check(L.lib().mi_engine_set_dora(self._h, int(layer), proj.encode(), C.c_void_p(ta.data_ptr()), C.c_void_p(tb.data_ptr()),
+                                           C.c_void_p(tm.data_ptr()), int(ta.shape[1]), float(scale), L.MI_F32, int(ta.is_cuda)))
+        self.invalidate_prefix_caches()
+
+    def set_adapter_dora(self, slot: int, layer: int, proj: str, a, b, m, scale: float) -> None:
+        """``mi_engine_set_adapter_dora``: one DoRA projection of the per-request adapter in ``slot``; ``set_adapter_lora``
+        with ``m`` as in ``set_dora``.  LoRA and DoRA entries may share a slot; setting one over the other replaces it."""
+        ta, tb, tm = self._dora_factors(a, b, m)
+        L.check(L.lib().mi_engine_set_adapter_dora(self._h, int(slot), int(layer), proj.encode(), C.c_void_p(ta.data_ptr()),
+                                                   C.c_void_p(tb.data_ptr()), C.c_void_p(tm.data_ptr()), int(ta.shape[1]),
+                                                   float(scale), L.MI_F32, int(ta.is_cuda)))
+
     def clear_adapter(self, slot: int) -> None:
         """``mi_engine_clear_adapter``: free the adapter in ``slot``; a step on a row that still names it is refused."""
         L.check(L.lib().mi_engine_clear_adapter(self._h, int(slot)))

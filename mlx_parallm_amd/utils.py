@@ -427,7 +427,8 @@ def load_model(model_path: Path, lazy: bool = False, model_config: dict = {}, *,
 
 
 def _read_adapter(n_layers: int, adapter_path: str):
-    """The (layer, key, lora_a, lora_b, scale) entries of an adapter directory, in the order ``load_adapters`` applies them."""
+    """The (layer, key, lora_a, lora_b, m, scale) entries of an adapter directory, in the order ``load_adapters`` applies
+    them; ``m`` is DoRA's magnitude (``fine_tune_type`` "dora", or the older ``"use_dora": true``) and None for LoRA."""
     from safetensors.torch import load_file
 
     adapter_path = Path(adapter_path)
@@ -435,8 +436,9 @@ def _read_adapter(n_layers: int, adapter_path: str):
     if not cfg_file.exists():
         raise FileNotFoundError(f"The adapter path does not exist: {adapter_path}")
     cfg = json.loads(cfg_file.read_text())
-    if cfg.get("fine_tune_type", "lora") != "lora":
-        raise NotImplementedError(f"fine_tune_type {cfg.get('fine_tune_type')} not supported (lora only)")
+    kind = cfg.get("fine_tune_type") or ("dora" if cfg.get("use_dora") else "lora")
+    if kind not in ("lora", "dora"):
+        raise NotImplementedError(f"fine_tune_type {kind} not supported (lora and dora only)")
     lp = cfg["lora_parameters"]
     keys = lp.get("keys") or ["self_attn.q_proj", "self_attn.v_proj"]
     weights = load_file(str(adapter_path / "adapters.safetensors"))
@@ -446,28 +448,40 @@ def _read_adapter(n_layers: int, adapter_path: str):
             a, b = weights.get(base + ".lora_a"), weights.get(base + ".lora_b")
             if a is None or b is None:
                 continue
-            yield i, key, a, b, float(lp["scale"])
+            m = None
+            if kind == "dora":
+                m = weights.get(base + ".m")
+                if m is None:
+                    raise ValueError(f"DoRA adapter {adapter_path}: {base}.m is missing")
+            yield i, key, a, b, m, float(lp["scale"])
 
 
 def load_adapters(model, adapter_path: str):
     """mlx-lm ``load_adapters`` as the reference uses it (utils.py:742-744): read
     ``adapter_config.json`` (``fine_tune_type``, ``num_layers``, ``lora_parameters``; written by
     rl_training/lora_init.py:140-153), adapt the LAST ``num_layers`` blocks, load
-    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``).  ``lora_parameters.keys`` may name any of the
-    seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the config's order."""
-    for i, key, a, b, scale in _read_adapter(len(model.layers), adapter_path):
-        model.engine.set_lora(i, key, a, b, scale)
+    ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``, for DoRA also ``.m``).  ``lora_parameters.keys``
+    may name any of the seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the
+    config's order -- a DoRA entry through ``Engine.set_dora``, a LoRA entry through ``Engine.set_lora``."""
+    for i, key, a, b, m, scale in list(_read_adapter(len(model.layers), adapter_path)):   # (a bad directory raises first)
+        if m is None:
+            model.engine.set_lora(i, key, a, b, scale)
+        else:
+            model.engine.set_dora(i, key, a, b, m, scale)
     return model
 
 
 def load_adapter_into(model, slot: int, adapter_path: str):
     """The same adapter directory into slot ``slot`` of the engine's per-request adapter table
-    (``Engine.set_adapter_lora``): rows that name the slot (``KVCache.set_row_adapter``) run it, the others do not.  Whatever
-    the slot held before is cleared first, so the slot ends up holding exactly this adapter."""
+    (``Engine.set_adapter_lora`` / ``set_adapter_dora``): rows that name the slot (``KVCache.set_row_adapter``) run it, the
+    others do not.  Whatever the slot held before is cleared first, so the slot ends up holding exactly this adapter."""
     entries = list(_read_adapter(len(model.layers), adapter_path))       # (a bad directory raises before the slot is touched)
     model.engine.clear_adapter(slot)
-    for i, key, a, b, scale in entries:
-        model.engine.set_adapter_lora(slot, i, key, a, b, scale)
+    for i, key, a, b, m, scale in entries:
+        if m is None:
+            model.engine.set_adapter_lora(slot, i, key, a, b, scale)
+        else:
+            model.engine.set_adapter_dora(slot, i, key, a, b, m, scale)
     return model
 
 

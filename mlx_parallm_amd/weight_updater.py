@@ -1,12 +1,13 @@
-"""LoRA hot-swap on a live engine (mirror of ``mlx_parallm/rl_training/weight_updater.py:17-90``).
+"""LoRA / DoRA hot-swap on a live engine (mirror of ``mlx_parallm/rl_training/weight_updater.py:17-90``).
 
 ``apply_lora_update(model, adapter_path, lock=...)`` re-reads an adapter directory and replaces the LoRA
 factors of the running model in place -- < 10 MB over PCIe, no weight reload; in a multi-GPU deployment each
 rank calls it for its own replica.  Accepted layouts, in the reference's order of preference:
 ``adapter_config.json`` + ``adapters.safetensors`` (mlx-lm ``load_adapters``), else ``adapter.npz``, else
 ``adapters.safetensors`` / ``model*.safetensors`` without a config; keys
-``model.layers.<i>.<proj>.lora_a`` (K, r) / ``.lora_b`` (r, N).  Without a config the scale of the currently
-loaded adapter is kept (``default_scale`` if there is none).
+``model.layers.<i>.<proj>.lora_a`` (K, r) / ``.lora_b`` (r, N), and for a DoRA adapter ``.m`` (N,).  Without a config the
+scale of the currently loaded adapter is kept (``default_scale`` if there is none) and a key with a sibling ``.m`` is a DoRA
+entry.
 """
 from __future__ import annotations
 
@@ -63,7 +64,11 @@ def apply_lora_update(model, adapter_path: str, *, lock: Optional[RLock] = None,
             b = arrays.get(k[: -len("lora_a")] + "lora_b")
             if b is None:
                 continue
-            model.engine.set_lora(int(m.group(1)), m.group(2), np.asarray(a), np.asarray(b), scale)
+            mag = arrays.get(k[: -len("lora_a")] + "m")          # a sibling `.m`: a DoRA entry
+            if mag is None:
+                model.engine.set_lora(int(m.group(1)), m.group(2), np.asarray(a), np.asarray(b), scale)
+            else:
+                model.engine.set_dora(int(m.group(1)), m.group(2), np.asarray(a), np.asarray(b), np.asarray(mag), scale)
             n += 1
         if n == 0:
             logging.warning(f"No matching adapter parameters found in {adapter_path}")
