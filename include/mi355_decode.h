@@ -428,6 +428,37 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value);
 /* Blocks until the engine's stream is idle. */
 int mi_engine_sync(mi_engine* e);
 
+/* ---- merging an adapter into the base weights (the reference's tools/merge_lora.py is a stub) ------------------------
+ * Stateless and synchronous: device pointers on device `device`, row-major tensors in checkpoint layout, no engine needed
+ * (the caller's current device is restored).  T = dtype (MI_BF16 / MI_F16), W (N, K), A (K, rank) float32, B (rank, N) float32,
+ * m (N,) float32 or NULL for LoRA, s the adapter's scale.  quant_bits 0: w is W in T and scales / biases are ignored;
+ * 4 / 8: w is the MLX-packed uint32 (N, K bits / 32) with scales / biases (N, K / 64) in T, quant_group must be 64.
+ * Arithmetic, every sum float32, in a fixed order (the same inputs give the same bits):
+ *   Wd[n][k] = W[n][k], or T(scale q + bias) as ONE float32 multiply-add and one rounding
+ *   b'[n][j] = T(s B[j][n]);  a'[j][k] = T(A[k][j])
+ *   delta[n][k] = T(sum_j b'[n][j] a'[j][k])         an fmaf chain in ascending j from 0, one rounding at the end
+ *   Wm = T(Wd + delta)
+ *   with m: norm[n] = sqrt(sum_k Wm[n][k]^2) (a thread's k ascending in strides of 256, the wave sum, the four waves in
+ *           order), g[n] = m[n] / norm[n] in float32, W' = T(g[n] Wm[n][k]);  without m: W' = Wm
+ * requantize 0: out_w is W' in T (N, K), out_scales / out_biases are ignored -- also from a quantised input (a de-quantised
+ * merge).  requantize 1 (quantised input only): W' is quantised again with the input's bits and group by mi_quantize_mlx's
+ * kernel into out_w (packed) / out_scales / out_biases.  A linear bias is not an argument: merging leaves it as it is.
+ * These steps restate mlx-lm's LoRALinear.fuse, DoRALinear.fuse and QuantizedLinear.from_linear from their published code;
+ * they could not be run against mlx-lm.
+ * MI_ERR_UNSUPPORTED: dtype MI_F32; m together with a quantised input (mi_engine_set_dora refuses DoRA on quantised weights
+ * for the same reason); quant_group 32 or 128; K % 64 != 0 when quantised.  MI_ERR_INVALID: rank outside 1..64, a null or
+ * misaligned buffer, requantize with a dense input, an s or an m[n] that is not finite, a merged row whose norm is 0 or not
+ * finite (the message names the row).  A refused call writes nothing to the outputs. */
+int mi_lora_merge(int device, int N, int K, int rank, int dtype, int quant_bits, int quant_group, const void* w,
+                  const void* scales, const void* biases, const float* A, const float* B, const float* m, float s,
+                  int requantize, void* out_w, void* out_scales, void* out_biases);
+/* The quantiser alone: w (N, K) in T -> out_w uint32 (N, K bits / 32), out_scales / out_biases (N, K / 64) in T; bits 4 or 8,
+ * group 64 (32 / 128: MI_ERR_UNSUPPORTED, as K % 64 != 0 and dtype MI_F32).  mx.quantize as published: per group of 64,
+ * scale = max((max - min) / (2^bits - 1), 1e-7) signed towards the edge of larger magnitude, the edge snapped to a code, the
+ * codes from the unrounded float32 scale and bias (IEEE division, round half to even), then scale and bias rounded to T. */
+int mi_quantize_mlx(int device, int N, int K, int dtype, int bits, int group, const void* w, void* out_w, void* out_scales,
+                    void* out_biases);
+
 const char* mi_last_error(void);
 const char* mi_version(void);
 int mi_abi_version(void);                  /* MI_ABI_VERSION of the loaded library */

@@ -118,6 +118,9 @@ SIGNATURES = {
     "mi_profile_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "mi_engine_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "mi_engine_sync": (C.c_int, [_P]),
+    "mi_lora_merge": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float,
+                                C.c_int, _P, _P, _P]),
+    "mi_quantize_mlx": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mi_last_error": (C.c_char_p, []),
     "mi_version": (C.c_char_p, []),
     "mi_abi_version": (C.c_int, []),

@@ -39,6 +39,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lora-modules", nargs="+", default=None, metavar="NAME=PATH",
                    help="continuous scheduler: LoRA adapters that share the base model's weights and batch; a request whose "
                    "`model` is NAME runs on that adapter (not together with --lora-path).")
+    p.add_argument("--merge-lora", action="store_true", help="merge the --lora-path adapter into the base weights while they "
+                   "load: the server then runs a plain model, without the adapter's launches (not with --lora-modules).")
     p.add_argument("--max-batch-size", type=int, default=d.max_batch_size)
     p.add_argument("--batch-timeout", type=float, default=d.batch_timeout, help="Batching window in seconds.")
     p.add_argument("--request-timeout-seconds", type=float, default=d.request_timeout_seconds)
@@ -78,7 +80,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> ServerConfig:
     ns = parser.parse_args(argv)
     if ns.lora_path and ns.lora_modules:
         parser.error("--lora-path (one adapter for every request) and --lora-modules (an adapter per request) cannot be combined")
-    return ServerConfig(model_path=ns.model_path, host=ns.host, port=ns.port, lora_path=ns.lora_path,
+    if ns.merge_lora and ns.lora_modules:
+        parser.error("--merge-lora merges one adapter into the base weights; --lora-modules adapters need the unmerged base")
+    if ns.merge_lora and not ns.lora_path:
+        parser.error("--merge-lora needs --lora-path (the adapter to merge)")
+    return ServerConfig(model_path=ns.model_path, host=ns.host, port=ns.port, lora_path=ns.lora_path, merge_lora=bool(ns.merge_lora),
                         max_batch_size=ns.max_batch_size, batch_timeout=ns.batch_timeout,
                         request_timeout_seconds=ns.request_timeout_seconds,
                         max_concurrent_streams=ns.max_concurrent_streams, scheduler=ns.scheduler,

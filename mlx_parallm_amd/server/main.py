@@ -101,6 +101,7 @@ class ServerConfig:
     # continuous scheduler: name -> adapter directory.  Every adapter is resident in a slot of the engine's per-request table;
     # a request whose `model` is such a name runs on it, in the same steps as everybody else.  Not together with lora_path.
     lora_modules: Optional[Dict[str, str]] = None
+    merge_lora: bool = False                      # lora_path is merged into the base weights at load (utils.load merge_adapter)
 
     @classmethod
     def from_env(cls, base: Optional["ServerConfig"] = None) -> "ServerConfig":
@@ -746,11 +747,12 @@ def _load_initial_model(state: ServerState) -> None:
     model_registry[rec.id] = rec
     state.model_id = rec.id
     try:
+        merge = {"merge_adapter": True} if cfg.merge_lora else {}
         try:
             model, tokenizer = load(cfg.model_path, adapter_path=cfg.lora_path,
-                                    device=(cfg.devices[0] if cfg.devices else cfg.device))
+                                    device=(cfg.devices[0] if cfg.devices else cfg.device), **merge)
         except TypeError:
-            model, tokenizer = load(cfg.model_path, adapter_path=cfg.lora_path)
+            model, tokenizer = load(cfg.model_path, adapter_path=cfg.lora_path, **merge)
         rec.model_instance, rec.tokenizer_instance, rec.status = model, tokenizer, ModelStatus.LOADED
         log.info("loaded %s%s", rec.id, f" with adapter {cfg.lora_path}" if cfg.lora_path else "")
     except Exception as e:
@@ -804,6 +806,8 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
         config = ServerConfig.from_env(cli_args)
     if config.lora_path and config.lora_modules:
         raise ValueError("lora_path (one adapter for every request) and lora_modules (an adapter per request) cannot be combined")
+    if config.merge_lora and (config.lora_modules or not config.lora_path):
+        raise ValueError("merge_lora merges lora_path into the base weights: it needs lora_path and excludes lora_modules")
     state = ServerState(config)
 
     @asynccontextmanager
@@ -825,7 +829,8 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             from ..utils import load
 
             def more():
-                return [load(config.model_path, adapter_path=config.lora_path, device=d)[0] for d in config.devices[1:]]
+                return [load(config.model_path, adapter_path=config.lora_path, device=d, merge_adapter=config.merge_lora)[0]
+                        for d in config.devices[1:]]
             state.extra_replicas = await asyncio.get_running_loop().run_in_executor(None, more)
             if config.scheduler != "continuous":
                 log.info("%d devices: using the continuous scheduler", len(config.devices))

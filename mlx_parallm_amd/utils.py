@@ -377,14 +377,26 @@ def _checkpoint_dtype(weights: Dict[str, Any]) -> str:
 
 def load_model(model_path: Path, lazy: bool = False, model_config: dict = {}, *, device: int = 0,
                max_positions: Optional[int] = None, weights_from_rank: Optional[int] = None,
-               replicate_stats: Optional[Dict[str, float]] = None):
+               replicate_stats: Optional[Dict[str, float]] = None, adapter_path: Optional[str] = None,
+               merge_adapter: bool = False):
     """utils.py:630-708: config.json -> glob ``model*.safetensors`` -> Model(args) -> sanitize ->
     quantised modules are those with a ``.scales`` tensor -> unknown tensors filtered.
 
     ``weights_from_rank`` (keyword only; needs an initialised ``torch.distributed`` group): only that rank reads the
     safetensors files, the other ranks receive the tensors by bucketed broadcast straight into device memory
-    (``distributed.replicate_checkpoint``: RCCL over xGMI under backend "nccl") -- SURVEY 8e."""
+    (``distributed.replicate_checkpoint``: RCCL over xGMI under backend "nccl") -- SURVEY 8e.
+
+    ``adapter_path`` with ``merge_adapter=True`` (keyword only): the adapter is added into the checkpoint's tensors after
+    ``sanitize`` and before ``load_weights`` (``merge.merge_adapter_into_weights``; a quantised base is re-quantised), and the
+    model then loads and finalizes as ever: no ``set_lora`` call, no adapter table, exactly the launches of a plain model.  The
+    model records the directory as ``merged_adapter``; its base is no longer the base, so ``load_adapters``,
+    ``load_adapter_into`` and ``weight_updater.apply_lora_update`` refuse it."""
     from safetensors.torch import load_file
+
+    if merge_adapter and adapter_path is None:
+        raise ValueError("merge_adapter=True needs an adapter_path")
+    if adapter_path is not None and not merge_adapter:
+        raise ValueError("load_model takes an adapter_path only to merge it (merge_adapter=True); load() applies an unmerged one")
 
     model_path = Path(model_path)
     config = load_config(model_path)
@@ -418,12 +430,24 @@ def load_model(model_path: Path, lazy: bool = False, model_config: dict = {}, *,
     model = model_class(model_args, config=config, device=device, dtype=dtype, max_positions=max_positions)
     if hasattr(model, "sanitize"):
         weights = model.sanitize(weights)
+    if merge_adapter:
+        from .merge import merge_adapter_into_weights
+
+        merge_adapter_into_weights(weights, config, str(adapter_path), device=device)
     skipped = model.load_weights(list(weights.items()))
     if skipped > 0:
         logging.warning(f"Filtering out {skipped} unmatched weight tensors during load.")   # utils.py:696-698
     model.finalize()
     model.eval()
+    model.merged_adapter = str(adapter_path) if merge_adapter else None
     return model
+
+
+def _refuse_merged(model, what: str) -> None:
+    merged = getattr(model, "merged_adapter", None)
+    if merged is not None:
+        raise ValueError(f"{what}: the adapter {merged} was merged into this model's weights at load; "
+                         "its base is no longer the base an adapter was trained on")
 
 
 def _read_adapter(n_layers: int, adapter_path: str):
@@ -463,6 +487,7 @@ def load_adapters(model, adapter_path: str):
     ``adapters.safetensors`` (keys ``model.layers.<i>.<proj>.lora_a/lora_b``, for DoRA also ``.m``).  ``lora_parameters.keys``
     may name any of the seven linears of a block (lora_init.py:72,95-96); every key the file holds goes to the engine, in the
     config's order -- a DoRA entry through ``Engine.set_dora``, a LoRA entry through ``Engine.set_lora``."""
+    _refuse_merged(model, "load_adapters")
     for i, key, a, b, m, scale in list(_read_adapter(len(model.layers), adapter_path)):   # (a bad directory raises first)
         if m is None:
             model.engine.set_lora(i, key, a, b, scale)
@@ -475,6 +500,7 @@ def load_adapter_into(model, slot: int, adapter_path: str):
     """The same adapter directory into slot ``slot`` of the engine's per-request adapter table
     (``Engine.set_adapter_lora`` / ``set_adapter_dora``): rows that name the slot (``KVCache.set_row_adapter``) run it, the
     others do not.  Whatever the slot held before is cleared first, so the slot ends up holding exactly this adapter."""
+    _refuse_merged(model, "load_adapter_into")
     entries = list(_read_adapter(len(model.layers), adapter_path))       # (a bad directory raises before the slot is touched)
     model.engine.clear_adapter(slot)
     for i, key, a, b, m, scale in entries:
@@ -486,9 +512,13 @@ def load_adapter_into(model, slot: int, adapter_path: str):
 
 
 def load(path_or_hf_repo: str, tokenizer_config={}, model_config={}, adapter_path: Optional[str] = None,
-         lazy: bool = False, **engine_kwargs):
-    """utils.py:711-747 -> (model, tokenizer)."""
+         lazy: bool = False, merge_adapter: bool = False, **engine_kwargs):
+    """utils.py:711-747 -> (model, tokenizer).  ``merge_adapter=True`` (needs ``adapter_path``): the adapter is merged into the
+    weights while they load (``load_model``) instead of riding beside them."""
     model_path = get_model_path(path_or_hf_repo)
+    if merge_adapter:
+        model = load_model(model_path, lazy, model_config, adapter_path=adapter_path, merge_adapter=True, **engine_kwargs)
+        return model, load_tokenizer(model_path, tokenizer_config)
     model = load_model(model_path, lazy, model_config, **engine_kwargs)
     if adapter_path is not None:
         model = load_adapters(model, adapter_path)

@@ -45,7 +45,9 @@ def _load_adapter_arrays(path: str) -> Dict[str, Any]:
 
 def apply_lora_update(model, adapter_path: str, *, lock: Optional[RLock] = None, default_scale: float = 10.0) -> int:
     """Returns the number of (layer, projection) pairs updated."""
-    from .utils import load_adapters
+    from .utils import _refuse_merged, load_adapters
+
+    _refuse_merged(model, "apply_lora_update")
 
     def run() -> int:
         cfg_file = os.path.join(adapter_path, "adapter_config.json")
