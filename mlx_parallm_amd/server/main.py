@@ -1074,7 +1074,7 @@ async def _scheduled_response(state: ServerState, request: AnyRequest, tok: Toke
         text = prompt_text_of(request, tok)
     except Exception as e:
         raise HTTPException(status_code=500, detail=f"Error processing request: {e}")
-    group = state.scheduler.new_group() if n > 1 else None     # one per request: its choices share the prompt
+    group = state.scheduler.new_group(n) if n > 1 else None    # one per request: its choices share the prompt, queued together
     subs = [_submit(state, tok, text, request, choice=i, group=group) for i in range(n)]
     futs = [sub[0] for sub in subs]
     try:

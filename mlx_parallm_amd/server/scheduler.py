@@ -24,7 +24,8 @@ for -- a request does not wait for the running batch to finish -- and does it on
   * with ``fork_choices`` the ``n`` choices of one request (``submit(..., group=new_group())``) share one prompt prefill: the
     first member prefills, the others wait for it at the head of the queue and then get its row's first ``P - 1`` tokens
     (``KVCache.fork_row``: full blocks shared, the tail copied) and run the last prompt token themselves -- ``P + (n - 1)``
-    prompt tokens instead of ``n * P``;
+    prompt tokens instead of ``n * P``; a group that knows its size (``new_group(n)``) is queued whole, with its last member,
+    so that a first member cannot run to its end while its siblings are still being submitted;
   * while the row set is stable the next step is enqueued before the current one is read back, sampled tokens
     stay on the device (the same one-step-ahead pipelining as generate_step, utils.py:420-427); when a sequence
     finishes or a request is waiting, the step already in flight completes, its tokens for finished rows are
@@ -138,15 +139,20 @@ def check_stop(stop) -> List[str]:
 
 class Group:
     """What the sequences of one request's ``n`` choices share (``new_group()``, ``submit(..., group=g)``): a scheduler with
-    ``fork_choices`` prefills their common prompt once and forks the KV row for the others."""
-    __slots__ = ("replica",)
+    ``fork_choices`` prefills their common prompt once and forks the KV row for the others.  ``size``: how many members will
+    be submitted, where the caller knows; such a scheduler then holds them back and queues them together with the last one
+    (submitted one by one to a running scheduler, the first could finish and free its row before a sibling arrives, which
+    would then find no donor and prefill again)."""
+    __slots__ = ("replica", "size", "held")
 
-    def __init__(self):
+    def __init__(self, size: Optional[int] = None):
         self.replica = None            # ReplicaPool with fork_choices: the replica of the first member (a row is forked inside one cache)
+        self.size = None if size is None else int(size)
+        self.held: List["Sequence"] = []   # members submitted so far, not yet in `pending` (under the scheduler's cv)
 
 
-def new_group() -> Group:
-    return Group()
+def new_group(size: Optional[int] = None) -> Group:
+    return Group(size)
 
 
 class Sequence:
@@ -315,7 +321,14 @@ class ContinuousScheduler:
             raise ValueError(f"prompt ({len(seq.prompt)}) + max_tokens ({seq.max_tokens}) exceeds the engine's "
                              f"max_positions ({self.model.engine.max_positions})")
         with self.cv:
-            self.pending.append(seq)
+            if self.fork_choices and group is not None and group.size is not None:
+                group.held.append(seq)                # a sized group enters the queue whole: see Group
+                if len(group.held) < group.size:
+                    return seq
+                self.pending.extend(group.held)
+                group.held, group.size = [], None     # (a member beyond `size` is queued as it comes)
+            else:
+                self.pending.append(seq)
             self.cv.notify_all()
         return seq
 
@@ -437,8 +450,8 @@ class ContinuousScheduler:
             s.sample_steps += 1
         return sp
 
-    def new_group(self) -> Group:
-        return new_group()
+    def new_group(self, size: Optional[int] = None) -> Group:
+        return new_group(size)
 
     def _group_live(self, seq: Sequence) -> List[Sequence]:
         """The members of ``seq``'s group that hold a row and are still running, with the same prompt."""
@@ -723,8 +736,8 @@ class ReplicaPool:
                     group.replica = r
             return r.submit(prompt_ids, max_tokens, temp, top_p, sink, **controls)
 
-    def new_group(self) -> Group:
-        return new_group()
+    def new_group(self, size: Optional[int] = None) -> Group:
+        return new_group(size)
 
     @property
     def forks(self) -> int:

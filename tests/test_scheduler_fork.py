@@ -147,6 +147,38 @@ def test_later_siblings_fork_from_a_donor_that_is_already_decoding(tiny, tok, ch
     assert _prompt_tokens_fed(model.engine) == P + (N - 1)
 
 
+@pytest.mark.parametrize("fork", [True, False])
+def test_a_sized_group_reaches_a_running_scheduler_whole(tiny, tok, fork):
+    """Members submitted one by one to a scheduler that is already stepping: with ``new_group(N)`` none is queued before the
+    last one is in, so the first cannot finish (and free its row) while its siblings are on their way."""
+    model = _model(tiny)
+    sched = ContinuousScheduler(model, tok, max_slots=N, chunk_tokens=16, fork_choices=fork)
+    done, ev = [], threading.Event()
+
+    def sink(seq, delta, reason):
+        if reason is not None:
+            done.append(reason)
+            if len(done) == N:
+                ev.set()
+
+    sched.start()
+    g = sched.new_group(N)
+    seqs = [sched.submit(_prompt(tok), NEW, 0.0, 1.0, sink, group=g) for _ in range(N - 1)]
+    if fork:                                  # held back: nothing of the group has been queued or fed
+        assert g.held == seqs and not sched.pending and model.engine.fed == []
+    else:                                     # without the switch a group is inert
+        assert g.held == []
+    sched.submit(_prompt(tok), NEW, 0.0, 1.0, sink, group=g)
+    assert g.held == []
+    assert ev.wait(timeout=120), "a sequence never finished"
+    sched.stop()
+    assert done == ["length"] * N
+    if fork:
+        assert sched.forks == N - 1 and _prompt_tokens_fed(model.engine) == P + (N - 1)
+    else:
+        assert sched.forks == 0 and _prompt_tokens_fed(model.engine) == N * P
+
+
 def test_a_donor_cancelled_mid_prefill_leaves_the_others_to_normal_admission(tiny, tok):
     def hook(sched, seqs):
         # the donor goes away after its first chunk: cancel it from inside the engine, between two steps
