@@ -150,8 +150,11 @@ void mi_engine_destroy(mi_engine* e);
  * naming it), and the split names (q_proj, ..., up_proj) are unknown.  phi3.py has no linear biases and no tied head:
  * desc.attention_bias, mlp_bias or tie_word_embeddings set is MI_ERR_INVALID at mi_engine_create; rope_traditional and
  * rope_scale are those of MI_ARCH_LLAMA (phi3.py:73-81).
- * MI_ARCH_MIXTRAL (mixtral.py:95-119,198-215): dense 16-bit checkpoints only -- act_dtype MI_F32 or quant_bits != 0 is
- * MI_ERR_UNSUPPORTED at mi_engine_create naming the field, as are num_local_experts outside 1..16, num_experts_per_tok outside
+ * MI_ARCH_MIXTRAL (mixtral.py:95-119,198-215): 16-bit checkpoints, dense or quantised (quant_bits 4 / 8, quant_group_size 64:
+ * the ".weight" (uint32) / ".scales" / ".biases" triples of the experts in either name form -- [E][N][K bits / 32] and
+ * [E][N][K / 64], or 2-D per expert -- and of "block_sparse_moe.gate", the scales in the model dtype; the three expert tensors
+ * of a block all dense or all quantised).  act_dtype MI_F32, another group size, or quant_bits != 0 with a hidden_size or
+ * intermediate_size that is no multiple of 128 is MI_ERR_UNSUPPORTED at mi_engine_create naming the field, as are num_local_experts outside 1..16, num_experts_per_tok outside
  * {1, 2} (or above the expert count) and a hidden_size or intermediate_size that is no multiple of 64; tie_word_embeddings,
  * attention_bias or mlp_bias set is MI_ERR_INVALID.  The MLP of a block is "block_sparse_moe.gate.weight" [E][H] and either the
  * stacked tensors "block_sparse_moe.switch_mlp.{gate_proj,up_proj,down_proj}.weight" ([E][I][H], [E][I][H], [E][H][I]) or, per

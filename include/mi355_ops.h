@@ -26,6 +26,7 @@
  *   mi_op_sample_rowlp    ... and the per-row logprobs settings of mi_kv_set_row_logprobs (no counterpart)
  *   mi_op_moe_route / mi_op_moe_linear / mi_op_moe_mlp   MixtralSparseMoeBlock: mixtral.py:108-119 (gate, argpartition, softmax,
  *                     SwitchGLU, weighted sum)
+ *   mi_op_moe_linear_q / mi_op_moe_mlp_q   the same over quantised experts: QuantizedSwitchLinear, switch_layers.py:7-70
  */
 #ifndef MI355_OPS_H
 #define MI355_OPS_H
@@ -313,6 +314,22 @@ int mi_op_moe_linear(const void* x, int ldx, int x_rows, int x_shift, int act, i
 int mi_op_moe_mlp(const void* xn, int ldx, int R, int H, int I, int act, int rnd, int wdt, int E, int k, const void* w_gate,
                   const void* w_up, const void* w_down, const int32_t* meta, const int32_t* list, const void* score,
                   const void* resid, int ldr, void* out, int ldo, int iters, float* stage_ms);
+
+/* ---- the same two stages over MLX-affine QUANTISED experts (moe_q.hip; QuantizedSwitchLinear on mx.gather_qmm,
+ * switch_layers.py:7-70).  The experts arrive in checkpoint form -- w [E][N][K bits / 32] uint32, scales and biases
+ * [E][N][K / group] in `sdt` (MI_BF16 / MI_F16, equal to act unless act is MI_F32) -- and are repacked tile-major inside the
+ * call, untimed; every buffer 16-byte aligned.  W_hat = scale * q + bias stays in float32 (never rounded to 16 bits, no
+ * dequantised copy).  Served: bits 4 (K % 128 == 0) and 8 (K % 64 == 0), group 64, N % 16 == 0; anything else is
+ * MI_ERR_UNSUPPORTED.  Lists, iters and the timing outputs as in mi_op_moe_linear / mi_op_moe_mlp.  The arithmetic restates
+ * mx.quantize / gather_qmm from the reference's reading; it has not been checked against MLX itself. */
+int mi_op_moe_linear_q(const void* x, int ldx, int x_rows, int x_shift, int act, int rnd, const void* w, const void* scales,
+                       const void* biases, int sdt, int bits, int group, int E, int N, int K, const int32_t* meta,
+                       const int32_t* list, int pairs, void* out, int ldo, int iters, float* avg_ms);
+int mi_op_moe_mlp_q(const void* xn, int ldx, int R, int H, int I, int act, int rnd, int sdt, int bits, int group, int E, int k,
+                    const void* gate_w, const void* gate_scales, const void* gate_biases, const void* up_w, const void* up_scales,
+                    const void* up_biases, const void* down_w, const void* down_scales, const void* down_biases,
+                    const int32_t* meta, const int32_t* list, const void* score, const void* resid, int ldr, void* out, int ldo,
+                    int iters, float* stage_ms);
 
 #ifdef __cplusplus
 }

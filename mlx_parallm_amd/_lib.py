@@ -169,6 +169,9 @@ SIGNATURES = {
                                    C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mi_op_moe_mlp": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
                                 _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_moe_linear_q": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mi_op_moe_mlp_q": (C.c_int, [_P] + [C.c_int] * 11 + [_P] * 13 + [C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

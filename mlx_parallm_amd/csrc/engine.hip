@@ -112,9 +112,11 @@ int moe_block(mi_engine* e, LayerW& lw, size_t R, int act, bool w32) {
   const size_t es = dtype_size(act), P = R * k;
   hipStream_t st = e->stream;
   e->handover.valid = false;      // (o_proj's row sums describe h before this block adds to it: nothing here takes them)
+  // quantised experts: + the prepared rows of the linear in flight (moe_q.hip: xn for gate|up, then act for down)
+  const size_t prep = lw.moe_quant ? align256(std::max(moe_q_ws_bytes((int)R, H, act), moe_q_ws_bytes((int)P, I, act))) : 0;
   const size_t o_sel = 0, o_score = o_sel + align256(P * 4), o_meta = o_score + align256(P * es),
                o_list = o_meta + align256(2 * (size_t)E * 4), o_act = o_list + align256(P * 4), o_y = o_act + align256(P * I * es),
-               total = o_y + align256(P * H * es);
+               o_prep = o_y + align256(P * H * es), total = o_prep + prep;
   MI_TRY(grow(st, &e->moe_ws, &e->moe_ws_cap, total));
   char* ws = e->moe_ws;
   int32_t* sel = (int32_t*)(ws + o_sel); void* score = ws + o_score; int32_t* meta = (int32_t*)(ws + o_meta); int32_t* list = (int32_t*)(ws + o_list);
@@ -122,7 +124,20 @@ int moe_block(mi_engine* e, LayerW& lw, size_t R, int act, bool w32) {
   { Prof pr(e, "moe_route");
     MI_TRY(launch_rmsnorm_rows(e->h, H, w32 ? lw.post_norm32 : lw.post_norm, e->xn, H, (int)R, H, d.rms_norm_eps, act, st, true, RND_NONE));
     MoeRouteCall rc{e->xn, H, (int)R, H, act, RND_NONE, lw.moe_router, d.act_dtype, E, k, sel, score, meta, list};
+    if (lw.moe_router32 != nullptr) { rc.wg = lw.moe_router32; rc.wdt = MI_F32; }      // a router that arrived quantised
     MI_TRY(launch_moe_route(rc, st)); }
+  if (lw.moe_quant) {
+    { Prof pr(e, "moe_gate_up");
+      MoeLinearQCall c{e->xn, H, (int)R, k == 2 ? 1 : 0, act, RND_NONE, lw.moe_w[0], lw.moe_w[1], d.act_dtype, d.quant_bits, E, I, H, 1,
+                       meta, list, (int)P, acts, I, ws + o_prep};
+      MI_TRY(launch_moe_linear_q(c, st)); }
+    { Prof pr(e, "moe_down");
+      MoeLinearQCall c{acts, I, (int)P, 0, act, RND_NONE, lw.moe_w[2], nullptr, d.act_dtype, d.quant_bits, E, H, I, 0, meta, list, (int)P, y, H,
+                       ws + o_prep};
+      MI_TRY(launch_moe_linear_q(c, st)); }
+    Prof pr(e, "moe_combine");
+    return launch_moe_combine(y, score, k, e->h, H, e->h, H, (int)R, H, act, RND_NONE, st);
+  }
   { Prof pr(e, "moe_gate_up");
     MoeLinearCall c{e->xn, H, k == 2 ? 1 : 0, act, RND_NONE, lw.moe_w[0], lw.moe_w[1], d.act_dtype, E, I, H, 1, meta, list, acts, I};
     MI_TRY(launch_moe_linear(c, st)); }
@@ -530,7 +545,14 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     if (d.attention_bias || d.mlp_bias || d.tie_word_embeddings)
       return fail(MI_ERR_INVALID, "arch mixtral has neither linear biases nor a tied lm_head (attention_bias, mlp_bias, tie_word_embeddings must be 0)");
     if (d.act_dtype == MI_F32) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: act_dtype must be MI_BF16 or MI_F16 (float32 weights are not supported)");
-    if (d.quant_bits != 0) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits must be 0 (quantised experts are not supported yet)");
+    // quantised experts (moe_q.hip): MLX-affine int4 / int8 in groups of 64.  The engine takes them at widths that are whole
+    // 128-k blocks for both bit widths (every published Mixtral: 4096 / 14336, 6144 / 16384); the int8 kernel itself runs on
+    // 64-k blocks (mi_op_moe_linear_q)
+    if (d.quant_bits != 0 && d.quant_group_size != 64)
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits " + std::to_string(d.quant_bits) + " needs quant_group_size 64 (groups of 32 / 128 are not supported)");
+    if (d.quant_bits != 0 && (d.hidden_size % 128 || d.intermediate_size % 128))
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits " + std::to_string(d.quant_bits) +
+                                          " (quantization of the experts) needs hidden_size and intermediate_size to be multiples of 128");
     if (d.num_local_experts < 1 || d.num_local_experts > MOE_MAX_EXPERTS)
       return fail(MI_ERR_UNSUPPORTED, "arch mixtral: num_local_experts must be in [1, " + std::to_string(MOE_MAX_EXPERTS) + "]");
     if (d.num_experts_per_tok < 1 || d.num_experts_per_tok > 2 || d.num_experts_per_tok > d.num_local_experts)
@@ -553,7 +575,10 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     l.o.n_parts = 1; l.o.part_rows[0] = d.hidden_size;
     l.gate_up.n_parts = 2; l.gate_up.part_rows[0] = d.intermediate_size; l.gate_up.part_rows[1] = d.intermediate_size;
     l.down.n_parts = 1; l.down.part_rows[0] = d.hidden_size;
-    if (d.arch == MI_ARCH_MIXTRAL) for (auto& seen : l.moe_seen) seen.assign(d.num_local_experts, 0);
+    if (d.arch == MI_ARCH_MIXTRAL)
+      for (int t = 0; t < 3; ++t) {
+        l.moe_seen[t].assign(d.num_local_experts, 0); l.moe_seen_s[t].assign(d.num_local_experts, 0); l.moe_seen_b[t].assign(d.num_local_experts, 0);
+      }
   }
   e->embed.n_parts = 1; e->embed.part_rows[0] = d.vocab_size;
   e->lm_head.n_parts = 1; e->lm_head.part_rows[0] = d.vocab_size;
@@ -570,6 +595,9 @@ void mi_engine_destroy(mi_engine* e) {
     hipFree(l.in_norm); hipFree(l.post_norm); hipFree(l.q_norm); hipFree(l.k_norm);
     hipFree(l.in_norm32); hipFree(l.post_norm32); hipFree(l.q_norm32); hipFree(l.k_norm32);
     hipFree(l.moe_router); for (void* w : l.moe_w) hipFree(w);
+    hipFree(l.moe_router_s); hipFree(l.moe_router_b); hipFree(l.moe_router32);
+    for (void* w : l.moe_s) hipFree(w);
+    for (void* w : l.moe_b) hipFree(w);
   }
   hipFree(e->final_norm32); hipFree(e->xn); hipFree(e->xs); hipFree(e->gk_ws);
   free_linear(e->embed); free_linear(e->lm_head);

@@ -67,6 +67,17 @@ struct LayerW {
   // (0 gate, 1 up, 2 down) was set, by the stacked tensor or by the expert's own
   void* moe_router = nullptr; void* moe_w[3] = {nullptr, nullptr, nullptr};
   std::vector<char> moe_seen[3];
+  // Quantised experts (desc.quant_bits 4 / 8, group 64): until finalize moe_w[t] holds the packed codes [E][N][K bits / 32]
+  // and moe_s[t] / moe_b[t] the scales / biases [E][N][K / 64], row-major as loaded (moe_seen_s / moe_seen_b: the slots set);
+  // finalize repacks each stack tile-major into moe_w[t] as one [E N][K] matrix (moe_q.hip) and frees the three.  moe_kind[t]:
+  // -1 nothing loaded yet, 0 dense, 1 quantised -- a layer's three stacks must agree.  A router that arrives quantised keeps
+  // its triple in moe_router / moe_router_s / moe_router_b until finalize leaves the float32 table moe_router32.
+  void* moe_s[3] = {nullptr, nullptr, nullptr}; void* moe_b[3] = {nullptr, nullptr, nullptr};
+  std::vector<char> moe_seen_s[3], moe_seen_b[3];
+  int moe_kind[3] = {-1, -1, -1};
+  bool moe_quant = false;        // (set by finalize) moe_block runs the quantised launches
+  void* moe_router_s = nullptr; void* moe_router_b = nullptr; float* moe_router32 = nullptr;
+  int moe_router_kind = -1;
 };
 
 constexpr int NSLOT = 4;

@@ -207,18 +207,38 @@ bool find_proj(const mi_model_desc& d, LayerW& l, const std::string& sub, Proj* 
 
 // MI_ARCH_MIXTRAL: `sub` = "block_sparse_moe.<rest>" of block l.  gate: the router [E][H]; switch_mlp.{gate,up,down}_proj: all
 // experts stacked, 3-D; experts.<e>.{w1,w3,w2}: one expert, 2-D, into slot e (w1 = gate, w3 = up, w2 = down: mixtral.py:203).
+// kind 0 = .weight (dense in the model dtype, or packed uint32 with desc.quant_bits), 1 = .scales, 2 = .biases (the model dtype,
+// [..][rows][K / 64]): the quantised triples of QuantizedSwitchLinear (switch_layers.py:7-70), and of a router that
+// nn.quantize took along (utils.py:679-690).
 int set_moe_tensor(mi_engine* e, LayerW& l, const std::string& rest, int kind, const void* data, const int64_t* shape, int ndim,
                    int dtype, int on_device, const std::string& name) {
   const mi_model_desc& d = e->d;
   const int64_t E = d.num_local_experts, H = d.hidden_size, I = d.intermediate_size;
-  if (kind == 1 || kind == 2) return fail(MI_ERR_UNSUPPORTED, name + ": quantised experts are not supported");
-  if (kind != 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
-  if (dtype != d.act_dtype) return fail(MI_ERR_UNSUPPORTED, name + ": dense weight dtype differs from the model dtype");
+  if (kind < 0 || kind > 2) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
+  const bool packed = kind == 0 && dtype == MI_U32;
+  const bool qpart = kind != 0 || packed;                     // a member of a quantised triple
+  if (qpart) {
+    if (d.quant_bits == 0) return fail(MI_ERR_UNSUPPORTED, name + ": a quantised tensor, but this engine was created for dense experts (desc.quant_bits == 0)");
+    if (d.quant_group_size != 64) return fail(MI_ERR_UNSUPPORTED, name + ": quantised experts need groups of 64");
+    if (kind != 0 && dtype != d.act_dtype) return fail(MI_ERR_UNSUPPORTED, name + ": scale dtype differs from the model dtype");
+  } else if (dtype != d.act_dtype) {
+    return fail(MI_ERR_UNSUPPORTED, name + ": dense weight dtype differs from the model dtype");
+  }
   const size_t es = dtype_size(dtype);
+  // columns of a tensor over K inputs: dense K, codes K bits / 32, scales and biases K / 64
+  auto cols_of = [&](int64_t K) { return kind != 0 ? K / 64 : packed ? K * d.quant_bits / 32 : K; };
   if (rest == "gate") {
-    if (ndim != 2 || shape[0] != E || shape[1] != H) return fail(MI_ERR_INVALID, name + ": expected shape [num_local_experts][hidden_size]");
-    if (l.moe_router == nullptr) MI_HIP(hipMalloc(&l.moe_router, (size_t)(E * H) * es));
-    return copy_in(l.moe_router, data, (size_t)(E * H) * es, on_device, e->stream);
+    const int64_t cols = cols_of(H);
+    if (ndim != 2 || shape[0] != E || shape[1] != cols)
+      return fail(MI_ERR_INVALID, name + ": expected shape [" + std::to_string(E) + "][" + std::to_string(cols) + "]");
+    if (kind == 0) {
+      if (l.moe_router_kind >= 0 && l.moe_router_kind != (int)packed) return fail(MI_ERR_UNSUPPORTED, name + ": the router was set dense and quantised");
+      l.moe_router_kind = packed;
+    }
+    void*& dst = kind == 0 ? l.moe_router : kind == 1 ? l.moe_router_s : l.moe_router_b;
+    if (dst != nullptr) { hipFree(dst); dst = nullptr; }
+    MI_HIP(hipMalloc(&dst, (size_t)(E * cols) * es));
+    return copy_in(dst, data, (size_t)(E * cols) * es, on_device, e->stream);
   }
   int t = -1; int64_t slot = -1;                  // tensor (0 gate, 1 up, 2 down); expert slot, -1 = the stacked form
   if (rest == "switch_mlp.gate_proj") t = 0;
@@ -234,7 +254,8 @@ int set_moe_tensor(mi_engine* e, LayerW& l, const std::string& rest, int kind, c
     if (t >= 0 && slot >= E) return fail(MI_ERR_NOTFOUND, "expert index out of range: " + name);
   }
   if (t < 0) return fail(MI_ERR_NOTFOUND, "unknown tensor: " + name);
-  const int64_t rows = t == 2 ? H : I, cols = t == 2 ? I : H;
+  const int64_t rows = t == 2 ? H : I, K = t == 2 ? I : H, cols = cols_of(K);
+  if (qpart) MI_TRY(moe_q_check_shape(d.quant_bits, d.quant_group_size, (int)rows, (int)K, name));
   const size_t one = (size_t)(rows * cols) * es;
   if (slot < 0) {
     if (ndim != 3 || shape[0] != E || shape[1] != rows || shape[2] != cols)
@@ -242,14 +263,54 @@ int set_moe_tensor(mi_engine* e, LayerW& l, const std::string& rest, int kind, c
   } else if (ndim != 2 || shape[0] != rows || shape[1] != cols) {
     return fail(MI_ERR_INVALID, name + ": expected shape [" + std::to_string(rows) + "][" + std::to_string(cols) + "]");
   }
-  if (l.moe_w[t] == nullptr) MI_HIP(hipMalloc(&l.moe_w[t], one * (size_t)E));
-  if (slot < 0) {
-    MI_TRY(copy_in(l.moe_w[t], data, one * (size_t)E, on_device, e->stream));
-    std::fill(l.moe_seen[t].begin(), l.moe_seen[t].end(), 1);
-  } else {
-    MI_TRY(copy_in((char*)l.moe_w[t] + one * (size_t)slot, data, one, on_device, e->stream));
-    l.moe_seen[t][slot] = 1;
+  if (kind == 0) {
+    if (l.moe_kind[t] >= 0 && l.moe_kind[t] != (int)packed) return fail(MI_ERR_UNSUPPORTED, name + ": the experts of one tensor mix dense and quantised weights");
+    l.moe_kind[t] = packed;
   }
+  void*& dst = kind == 0 ? l.moe_w[t] : kind == 1 ? l.moe_s[t] : l.moe_b[t];
+  std::vector<char>& seen = kind == 0 ? l.moe_seen[t] : kind == 1 ? l.moe_seen_s[t] : l.moe_seen_b[t];
+  if (dst == nullptr) MI_HIP(hipMalloc(&dst, one * (size_t)E));
+  if (slot < 0) {
+    MI_TRY(copy_in(dst, data, one * (size_t)E, on_device, e->stream));
+    std::fill(seen.begin(), seen.end(), 1);
+  } else {
+    MI_TRY(copy_in((char*)dst + one * (size_t)slot, data, one, on_device, e->stream));
+    seen[slot] = 1;
+  }
+  return MI_OK;
+}
+
+// the quantised parts of a Mixtral block at finalize: the router's float32 table, the three stacks tile-major
+int finalize_moe_quant(mi_engine* e, LayerW& l, const std::string& p) {
+  const mi_model_desc& d = e->d;
+  const int E = d.num_local_experts, H = d.hidden_size, I = d.intermediate_size;
+  if (l.moe_router_kind == 1 && l.moe_router32 == nullptr) {
+    if (!l.moe_router_s || !l.moe_router_b) return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe.gate: scales/biases not set");
+    float* t32 = nullptr;
+    MI_HIP(hipMalloc(&t32, (size_t)E * H * sizeof(float)));
+    int rc = launch_moe_router_dequant(l.moe_router, l.moe_router_s, l.moe_router_b, d.act_dtype, d.quant_bits, E, H, t32, e->stream);
+    if (rc == MI_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MI_ERR_RUNTIME, p + ".block_sparse_moe.gate: dequantising the router failed");
+    if (rc != MI_OK) { hipFree(t32); return rc; }
+    l.moe_router32 = t32;
+    hipFree(l.moe_router); hipFree(l.moe_router_s); hipFree(l.moe_router_b);      // (the triple is never read again)
+    l.moe_router = l.moe_router_s = l.moe_router_b = nullptr;
+  }
+  if (l.moe_quant || l.moe_kind[0] != 1) return MI_OK;
+  for (int t = 0; t < 3; ++t) {
+    LinearW src;
+    src.wk = (d.quant_bits == 8 ? WK_Q8_F32 : WK_Q4_F32) + (d.act_dtype == MI_BF16 ? 1 : 2);
+    src.w = l.moe_w[t]; src.scales = l.moe_s[t]; src.biases = l.moe_b[t];
+    src.N = E * (t == 2 ? H : I); src.K = t == 2 ? I : H; src.group = 64; src.layout = 0;
+    void* dst = nullptr;
+    if (hipMalloc(&dst, tiled_bytes(src.wk, src.N, src.K)) != hipSuccess)
+      return fail(MI_ERR_RUNTIME, p + ".block_sparse_moe: out of device memory repacking the experts");
+    int rc = launch_repack_tiled(src, dst, e->stream);
+    if (rc == MI_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MI_ERR_RUNTIME, p + ".block_sparse_moe: repacking the experts failed");
+    if (rc != MI_OK) { hipFree(dst); return rc; }
+    hipFree(l.moe_w[t]); hipFree(l.moe_s[t]); hipFree(l.moe_b[t]);
+    l.moe_w[t] = dst; l.moe_s[t] = l.moe_b[t] = nullptr;
+  }
+  l.moe_quant = true;
   return MI_OK;
 }
 
@@ -547,14 +608,19 @@ int mi_engine_finalize(mi_engine* e) {
   for (int i = 0; d.arch == MI_ARCH_MIXTRAL && i < d.num_layers; ++i) {
     const LayerW& l = e->layers[i];
     const std::string p = "model.layers." + std::to_string(i);
-    if (l.moe_router == nullptr) return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe.gate.weight not set");
+    if (l.moe_router == nullptr && l.moe_router32 == nullptr) return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe.gate.weight not set");
     static const char* const stacked[3] = {"gate_proj", "up_proj", "down_proj"};
     static const char* const single[3] = {"w1", "w3", "w2"};
     for (int t = 0; t < 3; ++t)
-      for (int x = 0; x < d.num_local_experts; ++x)
+      for (int x = 0; x < d.num_local_experts; ++x) {
         if (!l.moe_seen[t][x])
           return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe: expert " + std::to_string(x) + " of switch_mlp." + stacked[t] + ".weight (experts." +
                                            std::to_string(x) + "." + single[t] + ".weight) not set");
+        if (l.moe_kind[t] == 1 && !l.moe_quant && (!l.moe_seen_s[t][x] || !l.moe_seen_b[t][x]))
+          return fail(MI_ERR_NOTFOUND, p + ".block_sparse_moe: expert " + std::to_string(x) + " of switch_mlp." + stacked[t] + ": scales/biases not set");
+      }
+    if (l.moe_kind[0] != l.moe_kind[1] || l.moe_kind[0] != l.moe_kind[2])
+      return fail(MI_ERR_UNSUPPORTED, p + ".block_sparse_moe.switch_mlp: gate_proj, up_proj and down_proj must be all dense or all quantised");
   }
   for (int i = 0; i < d.num_layers; ++i) {
     LayerW& l = e->layers[i];
@@ -571,6 +637,7 @@ int mi_engine_finalize(mi_engine* e) {
     if (d.rope_traditional) MI_TRY(permute_qk_heads(e, l.qkv));      // in front of the tile-major repack
     MI_TRY(finalize_linear(e, l.qkv, H, p + (d.arch == MI_ARCH_PHI3 ? ".self_attn.qkv_proj" : ".self_attn.{q,k,v}_proj")));
     MI_TRY(finalize_linear(e, l.o, QD, p + ".self_attn.o_proj"));
+    if (d.arch == MI_ARCH_MIXTRAL) MI_TRY(finalize_moe_quant(e, l, p));
     if (d.arch != MI_ARCH_MIXTRAL) {
       MI_TRY(finalize_linear(e, l.gate_up, H, p + (d.arch == MI_ARCH_PHI3 ? ".mlp.gate_up_proj" : ".mlp.{gate,up}_proj")));
       MI_TRY(finalize_linear(e, l.down, d.intermediate_size, p + ".mlp.down_proj"));

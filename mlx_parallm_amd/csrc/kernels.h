@@ -199,6 +199,25 @@ int launch_moe_linear(const MoeLinearCall& c, hipStream_t st);
 int launch_moe_combine(const void* y, const void* score, int k, const void* resid, int ldr, void* out, int ldo, int R, int H,
                        int act, int rnd, hipStream_t st);
 
+// ---- moe_q.hip: launch_moe_linear over MLX-affine quantised experts (group 64, 4 / 8 bits).  w, w2: the stacked [E][N][K]
+// tensor repacked tile-major as ONE [E N][K] matrix (launch_repack_tiled; tiled_bytes(wk, E N, K) bytes), scales and biases in
+// `sdt` (MI_BF16 / MI_F16, = act unless act is MI_F32).  x is prepared once per launch into `ws` (moe_q_ws_bytes(), 256-byte
+// aligned): all x_rows rows; `pairs` = the length of the list array.  N % 16 == 0; K % 128 == 0 (int4) / K % 64 == 0 (int8).
+struct MoeLinearQCall {
+  const void* x; int ldx, x_rows, x_shift, act, rnd;
+  const void* w; const void* w2; int sdt, bits, E, N, K, swiglu;
+  const int32_t* meta; const int32_t* list; int pairs;
+  void* out; int ldo;
+  void* ws;
+};
+size_t moe_q_ws_bytes(int x_rows, int K, int act);
+int moe_q_check_shape(int bits, int group, int N, int K, const std::string& who);
+int launch_moe_linear_q(const MoeLinearQCall& c, hipStream_t st);
+// a quantised router [E][H] -> float32 [E][H], s * q + b in float32 (the oracle's W_hat); launch_moe_route takes it with
+// wdt = MI_F32
+int launch_moe_router_dequant(const void* codes, const void* scales, const void* biases, int sdt, int bits, int E, int H, float* out,
+                              hipStream_t st);
+
 struct EmbedCall {
   const int32_t* tokens;  // device [rows]
   int rows;

@@ -57,7 +57,13 @@ __global__ __launch_bounds__(NTHR) void moe_gate_kernel(const T* xn, int ldx, in
     for (int e = 0; e < MOE_MAX_EXPERTS; ++e)
       if (e < E) {
         float wv[8];
-        widen8<W>(*(const u32x4*)(wg + (size_t)e * H + k0), wv);
+        if constexpr (sizeof(W) == 4) {                        // a router dequantised at load (moe_q.hip): float32 as it is
+          const f32x4 a = *(const f32x4*)(wg + (size_t)e * H + k0), b = *(const f32x4*)(wg + (size_t)e * H + k0 + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { wv[j] = a[j]; wv[4 + j] = b[j]; }
+        } else {
+          widen8<W>(*(const u32x4*)(wg + (size_t)e * H + k0), wv);
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[e] = fmaf(xv[j], wv[j], acc[e]);
       }
@@ -251,7 +257,8 @@ void with_types(int act, int wdt, F f) {
 }  // namespace
 
 int launch_moe_route(const MoeRouteCall& c, hipStream_t st) {
-  MI_TRY(check_types(c.act, c.wdt, "moe_route"));
+  if (c.wdt != MI_F32) MI_TRY(check_types(c.act, c.wdt, "moe_route"));
+  else if (c.act != MI_F32 && c.act != MI_BF16 && c.act != MI_F16) return fail(MI_ERR_INVALID, "moe_route: bad activation dtype");
   if (!c.xn || !c.wg || !c.sel || !c.score || !c.meta || !c.list || c.R < 1) return fail(MI_ERR_INVALID, "moe_route: bad argument");
   if (c.E < 1 || c.E > MOE_MAX_EXPERTS) return fail(MI_ERR_UNSUPPORTED, "moe_route: 1 to 16 experts");
   if (c.k < 1 || c.k > 2 || c.k > c.E) return fail(MI_ERR_UNSUPPORTED, "moe_route: 1 or 2 experts per token, at most the expert count");
@@ -259,7 +266,14 @@ int launch_moe_route(const MoeRouteCall& c, hipStream_t st) {
   if ((long long)c.R * c.k > (1LL << 30)) return fail(MI_ERR_UNSUPPORTED, "moe_route: too many rows");
   if ((uintptr_t)c.xn % 16 != 0 || (uintptr_t)c.wg % 16 != 0) return fail(MI_ERR_INVALID, "moe_route: misaligned buffer");
   const dim3 grid((c.R + NTHR / 64 - 1) / (NTHR / 64));
-  with_types(c.act, c.wdt, [&](auto t, auto w) {
+  if (c.wdt == MI_F32) {                                       // a float32 router table: any activation type
+    auto go = [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((moe_gate_kernel<T, float>), grid, dim3(NTHR), 0, st, (const T*)c.xn, c.ldx, c.R, c.H, c.rnd, (const float*)c.wg, c.E, c.k,
+                         c.sel, (T*)c.score);
+    };
+    if (c.act == MI_BF16) go(Tag<bf16>{}); else if (c.act == MI_F16) go(Tag<f16>{}); else go(Tag<float>{});
+  } else with_types(c.act, c.wdt, [&](auto t, auto w) {
     using T = typename decltype(t)::type; using W = typename decltype(w)::type;
     hipLaunchKernelGGL((moe_gate_kernel<T, W>), grid, dim3(NTHR), 0, st, (const T*)c.xn, c.ldx, c.R, c.H, c.rnd, (const W*)c.wg, c.E, c.k,
                        c.sel, (T*)c.score);

@@ -592,6 +592,8 @@ int mi_op_moe_route(const void* xn, int ldx, int R, int H, int act, int rnd, con
                     int32_t* sel, void* score, int32_t* meta, int32_t* list, int iters, float* avg_ms) {
   MI_TRY(ready());
   if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, "mi_op_moe_route: bad rounding mode");
+  // (the float32 table of a router dequantised at load is the engine's own: this op takes a router as a checkpoint stores it)
+  if (wdt != MI_BF16 && wdt != MI_F16) return fail(MI_ERR_UNSUPPORTED, "mi_op_moe_route: router weights must be bf16 or f16");
   const MoeRouteCall c{xn, ldx, R, H, act, rnd, wg, wdt, E, k, sel, score, meta, list};
   return run_timed([&] { return launch_moe_route(c, nullptr); }, iters, avg_ms);
 }
@@ -625,6 +627,85 @@ int mi_op_moe_mlp(const void* xn, int ldx, int R, int H, int I, int act, int rnd
   int rc = run_timed([&] { return launch_moe_linear(gu, nullptr); }, iters, stage_ms);
   if (rc == MI_OK) rc = run_timed([&] { return launch_moe_linear(dn, nullptr); }, iters, stage_ms ? stage_ms + 1 : nullptr);
   if (rc == MI_OK && resid == out && resid != nullptr && iters >= 1 && stage_ms) rc = fail(MI_ERR_INVALID, "mi_op_moe_mlp: a timed call cannot add into its own residual");
+  if (rc == MI_OK)
+    rc = run_timed([&] { return launch_moe_combine(y, score, k, resid, ldr, out, ldo, R, H, act, rnd, nullptr); }, iters, stage_ms ? stage_ms + 2 : nullptr);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- moe_q.hip on its own: the experts arrive in checkpoint form and are repacked inside the call, untimed -----------------
+namespace {
+struct QStack { const void* w; const void* scales; const void* biases; };
+// [E][N][K bits / 32] uint32 + [E][N][K / 64] x 2 -> one tile-major [E N][K] matrix (freed by the caller)
+int repack_stack(const QStack& s, int sdt, int bits, int E, int N, int K, void** out, const char* who) {
+  if (!s.w || !s.scales || !s.biases) return fail(MI_ERR_INVALID, std::string(who) + ": null argument");
+  if ((uintptr_t)s.w % 16 != 0 || (uintptr_t)s.scales % 16 != 0 || (uintptr_t)s.biases % 16 != 0)
+    return fail(MI_ERR_INVALID, std::string(who) + ": misaligned buffer");
+  LinearW src;
+  src.wk = (bits == 8 ? WK_Q8_F32 : WK_Q4_F32) + (sdt == MI_BF16 ? 1 : 2);
+  src.w = s.w; src.scales = s.scales; src.biases = s.biases; src.N = E * N; src.K = K; src.group = 64; src.layout = 0;
+  MI_HIP(hipMalloc(out, tiled_bytes(src.wk, src.N, src.K)));
+  MI_TRY(launch_repack_tiled(src, *out, nullptr));
+  MI_HIP(hipStreamSynchronize(nullptr));
+  return MI_OK;
+}
+int check_q_call(const char* who, int act, int rnd, int sdt, int E) {
+  if (rnd != RND_NONE && rnd != RND_BF16 && rnd != RND_F16) return fail(MI_ERR_INVALID, std::string(who) + ": bad rounding mode");
+  if (act != MI_F32 && act != MI_BF16 && act != MI_F16) return fail(MI_ERR_INVALID, std::string(who) + ": bad activation dtype");
+  if (sdt != MI_BF16 && sdt != MI_F16) return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": scales must be bf16 or f16");
+  if (act != MI_F32 && act != sdt) return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": 16-bit activations need scales of the same dtype");
+  if (E < 1 || E > MOE_MAX_EXPERTS) return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": 1 to 16 experts");
+  return MI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_op_moe_linear_q(const void* x, int ldx, int x_rows, int x_shift, int act, int rnd, const void* w, const void* scales,
+                       const void* biases, int sdt, int bits, int group, int E, int N, int K, const int32_t* meta,
+                       const int32_t* list, int pairs, void* out, int ldo, int iters, float* avg_ms) {
+  MI_TRY(ready());
+  MI_TRY(check_q_call("mi_op_moe_linear_q", act, rnd, sdt, E));
+  MI_TRY(moe_q_check_shape(bits, group, N, K, "mi_op_moe_linear_q"));
+  if (x_shift < 0 || x_shift > 1 || x_rows < 1) return fail(MI_ERR_INVALID, "mi_op_moe_linear_q: bad x_rows / x_shift");
+  if (!x || !out || (uintptr_t)x % 16 != 0) return fail(MI_ERR_INVALID, "mi_op_moe_linear_q: null or misaligned buffer");
+  MI_TRY(check_moe_lists(meta, list, E, pairs, x_rows, x_shift, "mi_op_moe_linear_q"));
+  void* tiled = nullptr; void* ws = nullptr;
+  FreeGuard g1{tiled}, g2{ws};
+  MI_TRY(repack_stack({w, scales, biases}, sdt, bits, E, N, K, &tiled, "mi_op_moe_linear_q"));
+  MI_HIP(hipMalloc(&ws, moe_q_ws_bytes(x_rows, K, act)));
+  const MoeLinearQCall c{x, ldx, x_rows, x_shift, act, rnd, tiled, nullptr, sdt, bits, E, N, K, 0, meta, list, pairs, out, ldo, ws};
+  return run_timed([&] { return launch_moe_linear_q(c, nullptr); }, iters, avg_ms);
+}
+
+int mi_op_moe_mlp_q(const void* xn, int ldx, int R, int H, int I, int act, int rnd, int sdt, int bits, int group, int E, int k,
+                    const void* gate_w, const void* gate_scales, const void* gate_biases, const void* up_w, const void* up_scales,
+                    const void* up_biases, const void* down_w, const void* down_scales, const void* down_biases,
+                    const int32_t* meta, const int32_t* list, const void* score, const void* resid, int ldr, void* out, int ldo,
+                    int iters, float* stage_ms) {
+  MI_TRY(ready());
+  MI_TRY(check_q_call("mi_op_moe_mlp_q", act, rnd, sdt, E));
+  if (R < 1 || k < 1 || k > 2 || (long long)R * k > (1LL << 30)) return fail(MI_ERR_INVALID, "mi_op_moe_mlp_q: bad shape");
+  MI_TRY(moe_q_check_shape(bits, group, I, H, "mi_op_moe_mlp_q (gate / up)"));
+  MI_TRY(moe_q_check_shape(bits, group, H, I, "mi_op_moe_mlp_q (down)"));
+  if (!xn || !out || !score || (uintptr_t)xn % 16 != 0) return fail(MI_ERR_INVALID, "mi_op_moe_mlp_q: null or misaligned buffer");
+  const int P = R * k;
+  MI_TRY(check_moe_lists(meta, list, E, P, R, k - 1, "mi_op_moe_mlp_q"));
+  const size_t es = dtype_size(act);
+  void* acts = nullptr; void* y = nullptr; void* tg = nullptr; void* tu = nullptr; void* td = nullptr; void* ws = nullptr;
+  FreeGuard g1{acts}, g2{y}, g3{tg}, g4{tu}, g5{td}, g6{ws};
+  MI_TRY(repack_stack({gate_w, gate_scales, gate_biases}, sdt, bits, E, I, H, &tg, "mi_op_moe_mlp_q"));
+  MI_TRY(repack_stack({up_w, up_scales, up_biases}, sdt, bits, E, I, H, &tu, "mi_op_moe_mlp_q"));
+  MI_TRY(repack_stack({down_w, down_scales, down_biases}, sdt, bits, E, H, I, &td, "mi_op_moe_mlp_q"));
+  MI_HIP(hipMalloc(&acts, (size_t)P * I * es));
+  MI_HIP(hipMalloc(&y, (size_t)P * H * es));
+  MI_HIP(hipMalloc(&ws, std::max(moe_q_ws_bytes(R, H, act), moe_q_ws_bytes(P, I, act))));
+  const MoeLinearQCall gu{xn, ldx, R, k - 1, act, rnd, tg, tu, sdt, bits, E, I, H, 1, meta, list, P, acts, I, ws};
+  const MoeLinearQCall dn{acts, I, P, 0, act, rnd, td, nullptr, sdt, bits, E, H, I, 0, meta, list, P, y, H, ws};
+  int rc = run_timed([&] { return launch_moe_linear_q(gu, nullptr); }, iters, stage_ms);
+  if (rc == MI_OK) rc = run_timed([&] { return launch_moe_linear_q(dn, nullptr); }, iters, stage_ms ? stage_ms + 1 : nullptr);
+  if (rc == MI_OK && resid == out && resid != nullptr && iters >= 1 && stage_ms) rc = fail(MI_ERR_INVALID, "mi_op_moe_mlp_q: a timed call cannot add into its own residual");
   if (rc == MI_OK)
     rc = run_timed([&] { return launch_moe_combine(y, score, k, resid, ldr, out, ldo, R, H, act, rnd, nullptr); }, iters, stage_ms ? stage_ms + 2 : nullptr);
   return rc;

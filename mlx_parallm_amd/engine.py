@@ -330,9 +330,9 @@ class Engine:
         d.tie_word_embeddings = int(bool(config.get("tie_word_embeddings", tie_default)))
         d.act_dtype = _DT_NAMES[act_dtype]
         q = config.get("quantization")
-        if q and mt == "mixtral":
-            raise NotImplementedError("quantization: quantised Mixtral checkpoints are not supported by the MI355X engine "
-                                      "(dense bfloat16 / float16 experts only)")
+        if q and mt == "mixtral" and (int(q["bits"]) not in (4, 8) or int(q["group_size"]) != 64):
+            raise NotImplementedError("quantization: a quantised Mixtral checkpoint runs with 4 or 8 bits in groups of 64 "
+                                      f"(csrc/moe_q.hip); got {dict(q)}")
         if mt == "mixtral":                                                         # mixtral.py:20,22
             d.num_local_experts = int(config.get("num_local_experts", 8))
             d.num_experts_per_tok = int(config.get("num_experts_per_tok", 2))

@@ -3,10 +3,16 @@
 The attention half of a block is Mistral's (RMSNorm, RoPE, SDPA, no linear biases, an untied ``lm_head``); the MLP half is
 the sparse mixture of experts of mixtral.py:95-119: a router picks ``num_experts_per_tok`` of ``num_local_experts`` SwiGLU
 experts per token and sums their outputs under the softmax of the picked router logits.  The engine runs it on the device
-(``MI_ARCH_MIXTRAL``, csrc/moe.hip); a tie between router logits goes to the lower expert index (``mx.argpartition`` leaves the
+(``MI_ARCH_MIXTRAL``, csrc/moe.hip, quantised experts csrc/moe_q.hip); a tie between router logits goes to the lower expert index (``mx.argpartition`` leaves the
 order open).
 
-Checkpoints: dense bfloat16 / float16 only, in either name form -- the stacked ``block_sparse_moe.switch_mlp.*`` tensors that
+Checkpoints: dense bfloat16 / float16, or MLX-affine int4 / int8 in groups of 64 (``QuantizedSwitchLinear``,
+switch_layers.py:7-70: ``.weight`` / ``.scales`` / ``.biases`` triples of the experts and of whatever else ``nn.quantize`` took
+along, the router included; the experts stay quantised on the device and are multiplied as they are, the router is
+dequantised once to a float32 table).  Refused: groups of 32 / 128, a quantised checkpoint whose hidden or intermediate size is no
+multiple of 128, a block whose three expert tensors are not all dense or all quantised, scales in another dtype than the
+model's.  The quantised arithmetic restates ``mx.quantize`` / ``gather_qmm`` from the reference's reading and has not been
+checked against MLX itself.  Either name form -- the stacked ``block_sparse_moe.switch_mlp.*`` tensors that
 the reference's ``sanitize`` produces, or the per-expert ``block_sparse_moe.experts.<e>.{w1,w3,w2}`` tensors of the original
 checkpoints, which the engine copies into their slots one by one (nothing is stacked on the host).  ``rope_scaling`` is
 ignored, as mixtral.py:57-61 ignores it; ``head_dim`` is ``hidden_size // num_attention_heads`` (mixtral.py:38).

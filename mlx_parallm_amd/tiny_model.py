@@ -142,10 +142,16 @@ def init_weights(cfg: Dict[str, Any], seed: int = 0, dtype: str = "float32", nor
 
 
 def quantize_weights(w: Dict[str, torch.Tensor], group_size: int, bits: int) -> Dict[str, torch.Tensor]:
-    """``nn.quantize``: every Linear and Embedding (2-D ``.weight``) becomes a packed triple."""
+    """``nn.quantize``: every Linear and Embedding (2-D ``.weight``) becomes a packed triple, and so does every 3-D expert
+    stack of a Mixtral block (``QuantizedSwitchLinear``: expert by expert, which is what quantising the stack row-wise is)."""
     out: Dict[str, torch.Tensor] = {}
     for k, t in w.items():
-        if k.endswith(".weight") and t.ndim == 2 and t.shape[1] % group_size == 0:
+        if k.endswith(".weight") and t.ndim == 3 and ".switch_mlp." in k and t.shape[2] % group_size == 0:
+            base = k[: -len(".weight")]
+            parts = [quantize(t[e], group_size, bits) for e in range(t.shape[0])]
+            for j, suf in enumerate((".weight", ".scales", ".biases")):
+                out[base + suf] = torch.stack([p[j] for p in parts])
+        elif k.endswith(".weight") and t.ndim == 2 and t.shape[1] % group_size == 0:
             base = k[: -len(".weight")]
             packed, scales, biases = quantize(t, group_size, bits)
             out[base + ".weight"] = packed
@@ -270,7 +276,8 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
 
     ``model_type="mixtral"``: ``num_local_experts`` experts of ``intermediate_size`` each, ``num_experts_per_tok`` of them per
     token; ``expert_names`` = "stacked" (``switch_mlp.*``, 3-D) or "per_expert" (``experts.<e>.{w1,w2,w3}``, the same numbers);
-    ``router_gain`` scales the router's weights.  Dense 16-bit only: pass ``quantize_model=False`` and a 16-bit ``dtype``."""
+    ``router_gain`` scales the router's weights.  A 16-bit ``dtype``; with ``quantize_model`` the experts (either name form) and
+    the router are quantised with everything else."""
     from safetensors.torch import save_file
 
     dst = Path(dst)
@@ -286,8 +293,11 @@ def build_tiny_model(dst, *, seed: int = 0, model_type: str = "llama", hidden_si
         model_type, head_dim = "llama", None
     mixtral = model_type == "mixtral"
     if mixtral:
-        if quantize_model or dtype == "float32":
-            raise ValueError("mixtral: dense bfloat16 / float16 checkpoints only (quantize_model=False, a 16-bit dtype)")
+        if dtype == "float32":
+            raise ValueError("mixtral: bfloat16 / float16 checkpoints only (a 16-bit dtype)")
+        if quantize_model and (q_bits not in (4, 8) or q_group_size != 64 or hidden_size % 128 or intermediate_size % 128):
+            raise ValueError("mixtral: a quantised checkpoint has 4 or 8 bits in groups of 64 and a hidden_size and "
+                             "intermediate_size that are multiples of 128 (what the engine loads)")
         if tie_word_embeddings or attention_bias or mlp_bias:
             raise ValueError("mixtral has neither a tied lm_head nor linear biases: pass tie_word_embeddings=False")
         if expert_names not in ("stacked", "per_expert"):

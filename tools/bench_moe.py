@@ -25,7 +25,14 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def moe_case(w, act, R, H, I, E, k, iters, seed):
+def quantize_stack(t, bits):
+    """[E][N][K] bf16 -> (packed, scales, biases) stacks of quant.quantize, expert by expert."""
+    from mlx_parallm_amd.quant import quantize
+    parts = [quantize(t[e], 64, bits) for e in range(t.shape[0])]
+    return [torch.stack([p[j] for p in parts]).contiguous() for j in range(3)]
+
+
+def moe_case(w, act, R, H, I, E, k, iters, seed, bits=0):
     g = torch.Generator(device=DEV).manual_seed(seed)
     xn = torch.randn((R, H), device=DEV, generator=g).to(TDT[act])
     sel = torch.zeros((R, k), dtype=torch.int32, device=DEV)
@@ -38,13 +45,18 @@ def moe_case(w, act, R, H, I, E, k, iters, seed):
     L.check(L.lib().mi_op_moe_route(_p(xn), H, R, H, MIDT[act], 0, _p(w["router"]), L.MI_BF16, E, k, _p(sel), _p(score), _p(meta),
                                     _p(lst), iters, C.byref(ms)))
     stage = (C.c_float * 3)()
-    L.check(L.lib().mi_op_moe_mlp(_p(xn), H, R, H, I, MIDT[act], 0, L.MI_BF16, E, k, _p(w["gate"]), _p(w["up"]), _p(w["down"]), _p(meta),
-                                  _p(lst), _p(score), None, H, _p(out), H, iters, stage))
+    if bits:
+        q = [_p(t) for name in ("gate", "up", "down") for t in w[name]]
+        L.check(L.lib().mi_op_moe_mlp_q(_p(xn), H, R, H, I, MIDT[act], 0, L.MI_BF16, bits, 64, E, k, *q, _p(meta), _p(lst), _p(score), None, H,
+                                        _p(out), H, iters, stage))
+    else:
+        L.check(L.lib().mi_op_moe_mlp(_p(xn), H, R, H, I, MIDT[act], 0, L.MI_BF16, E, k, _p(w["gate"]), _p(w["up"]), _p(w["down"]), _p(meta),
+                                      _p(lst), _p(score), None, H, _p(out), H, iters, stage))
     cnt = meta[:E].cpu().tolist()
     touched = sum(1 for c in cnt if c > 0)
-    one = I * H * 2                                          # bytes of one expert's matrix
+    one = I * H * (bits / 8 + 4 / 64 if bits else 2)         # bytes of one expert's matrix (quantised: codes + scale and bias per 64)
     us = {"route": ms.value * 1e3, "gate_up": stage[0] * 1e3, "down": stage[1] * 1e3, "combine": stage[2] * 1e3}
-    return {"act": act, "rows": R, "experts_touched": touched, "pairs_per_expert": cnt, "us": us,
+    return {"act": act, "rows": R, "bits": bits, "experts_touched": touched, "pairs_per_expert": cnt, "us": us,
             "gate_up_bytes_per_us": 2 * touched * one / us["gate_up"], "down_bytes_per_us": touched * one / us["down"]}
 
 
@@ -90,19 +102,23 @@ def main():
     ap.add_argument("--experts", type=int, default=8)
     ap.add_argument("--per-tok", type=int, default=2)
     ap.add_argument("--dense", type=int, default=1)
+    ap.add_argument("--bits", type=int, default=0, choices=(0, 4, 8), help="0: dense bf16 experts; 4 / 8: MLX-affine quantised experts (csrc/moe_q.hip)")
     ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
     args = ap.parse_args()
     H, I, E, k = args.hidden, args.intermediate, args.experts, args.per_tok
+    torch.manual_seed(0)                                     # the same router, hence the same routing, in every run and for every --bits
     w = {"router": (torch.randn((E, H), device=DEV) * 0.02).to(torch.bfloat16)}       # small logits: near-uniform random routing
     for name, shape in (("gate", (E, I, H)), ("up", (E, I, H)), ("down", (E, H, I))):
         w[name] = (torch.randn(shape, device=DEV, dtype=torch.bfloat16) * 0.02)
+        if args.bits:
+            w[name] = quantize_stack(w[name], args.bits)
     lines = []
     for act in args.acts.split(","):
         for R in (int(r) for r in args.rows.split(",")):
-            r = moe_case(w, act, R, H, I, E, k, args.iters if R <= 64 else max(2, args.iters // 4), seed=R)
+            r = moe_case(w, act, R, H, I, E, k, args.iters if R <= 64 else max(2, args.iters // 4), seed=R, bits=args.bits)
             lines.append({"moe": r})
             u = r["us"]
-            print(f"moe   {act:8s} rows {R:5d}  experts touched {r['experts_touched']}  route {u['route']:8.1f}  gate|up {u['gate_up']:9.1f}  "
+            print(f"moe{args.bits or '':<3} {act:8s} rows {R:5d}  experts touched {r['experts_touched']}  route {u['route']:8.1f}  gate|up {u['gate_up']:9.1f}  "
                   f"down {u['down']:9.1f}  combine {u['combine']:7.1f} us   gate|up {r['gate_up_bytes_per_us'] / 1e6:6.2f}  down "
                   f"{r['down_bytes_per_us'] / 1e6:6.2f} TB/s of distinct expert weights", flush=True)
     if args.dense:
