@@ -423,6 +423,12 @@ int mi_profile_read(mi_engine* e, int64_t* n_launches, double* total_ms);
  *   "short_prefill_skinny"    0: prefill calls of <= 128 rows in all through the tile GEMM like longer ones (default 1: the
  *                             weight-streaming split-K kernel of the decode steps, ~2x faster at that size)
  *   "tile_weights"            0: keep weights row-major (before mi_engine_finalize only; default 1)
+ *   "shared_prefix_attention" N > 0: a decode step on a paged cache (head_dim 64 / 128) whose rows hold a set of two or more rows
+ *                             that map the same blocks over at least N leading tokens (mi_kv_fork_row, mi_kv_prefix_attach) runs
+ *                             rope / append + ONE attention launch that reads each set's shared blocks once per group of
+ *                             16 / (Hq / Hkv) rows instead of once per row; every other step runs as with 0.  The sums are
+ *                             taken in another order than the fused launch's: close, not bit-identical.
+ *                             0: off (default).  A negative value: MI_ERR_INVALID, the option keeps its value.
  * Environment switches read per call by the library (reference paths for tests and A/B runs): MI_GEMM_DMA=0 (prefill:
  * the register-staged 256 x 256 tile instead of the LDS-DMA one), MI_GEMM_DMA_SPLITK=0 (no K split of the LDS-DMA tile),
  * MI_ATTN_PREFILL_DMA=0 (the register-staged prefill attention), MI_ATTN_PREFILL_F32_EXACT=1 (float32-KV prefill

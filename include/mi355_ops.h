@@ -220,6 +220,20 @@ int mi_op_rope_append(const mi_op_attn_shape* s, const void* qkv, void* q_out, v
                       const float* cos_tab, const float* sin_tab, int max_pos);
 int mi_op_attention(const mi_op_attn_shape* s, const void* q, const void* kcache, const void* vcache,
                     const int32_t* offsets, void* out, float scale, int nsplit, float* partial);
+/* shared-prefix decode attention (L == 1, attn_shared.hip) on a block-paged cache: arenas [block][Hkv][1 << bs_shift][D], token t
+ * of sequence b in block btab[b * bt_stride + (t >> bs_shift)] (device; block 0 must be mapped memory).  q [B][Hq*D] is normed and
+ * roped and the new key / value are in the cache already: sequence b attends to offsets[b] + 1 keys.  The sets (device arrays):
+ * set i = set_members[set_ptr[i] .. set_ptr[i + 1]) (sequence indices; every sequence in exactly one set, n_sets + 1 pointers)
+ * maps the same blocks over its first set_run[i] tokens (a multiple of the block size; 0: nothing shared).  The sets with a
+ * run come first: n_shared of them (the launch has prefix work for these only; a set behind them runs as run 0).  Host bounds:
+ * max_members = the largest set, max_run = the longest run, max_tail = the most keys a sequence has behind its set's run (the
+ * new key included).  partial: [B*Hq][16][D+2] floats; counters: [B*Hkv] zero-initialised ints, zero again afterwards.
+ * head_dim 64 / 128, bf16 / f16 / float32 with act == kv; anything else: MI_ERR_UNSUPPORTED.  iters > 1 repeats the launch
+ * (timing; avg_ms may be NULL). */
+int mi_op_attention_shared(const mi_op_attn_shape* s, const int32_t* btab, int bt_stride, int bs_shift, const void* q,
+                           const void* kcache, const void* vcache, const int32_t* offsets, const int32_t* set_ptr,
+                           const int32_t* set_members, const int32_t* set_run, int n_sets, int n_shared, int max_members,
+                           int max_run, int max_tail, void* out, float scale, float* partial, int32_t* counters, int iters, float* avg_ms);
 /* fused decode attention (L == 1): q/k norm + RoPE + append + split-KV attention + combine.
  * counters: [B*Hkv] zero-initialised ints.  variant 0: MFMA kernel where it applies (16-bit caches,
  * head_dim % 32 == 0; float32 caches, head_dim 64 / 128), 1: VALU kernel.  iters > 1 repeats the launch (timing; avg_ms

@@ -107,26 +107,6 @@ __device__ __forceinline__ void raw_to_f32(const uint32_t (&r)[NW32], float (&o)
 }
 
 
-// The last split's combine: (max, sum, O[d]) of every split for one (head, d).  The loads of four splits are issued
-// together (a loop over a run-time split count with the loads inside waits one L2 round trip per load: ~8 in a row
-// for 4 splits), then merged in split order -- deterministic whoever arrived last.
-template <int D>
-__device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int d) {
-  float mn = -1e30f, L = 0.f, O[1] = {0.f};
-  for (int i0 = 0; i0 < nsplit; i0 += 4) {
-    float mv[4], lv[4], ov[4][1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float* q = pp + (size_t)min(i0 + j, nsplit - 1) * (D + 2);
-      mv[j] = __hip_atomic_load(&q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      lv[j] = __hip_atomic_load(&q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ov[j][0] = __hip_atomic_load(&q[2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    merge_splits4<1>(mn, L, O, mv, lv, ov, nsplit - i0);
-  }
-  return merged_out(O[0], L);
-}
-
 // Cache row and KV length of batch entry b (wave-uniform).  The host knows both (it advances the lengths itself) and passes
 // them in the kernel arguments: n_host_off > 0.  On that path nothing may touch vector memory -- the first K/V load waits for
 // these two values.  Written as `cond ? c.host_row[b] : rows[b]`, hipcc selects between the two ADDRESSES and emits one
@@ -469,7 +449,6 @@ __host__ __device__ constexpr size_t attn_mfma_lds_total() {
 //     in register r.  Lane (c16, g4) loads V[key 4 g4 + r][64 h + 4 c16 .. + 3]: per instruction 256 contiguous bytes of
 //     each of 4 rows; element e of that load is row c16 of the A tile (h, e), so output tile (h, e) row c16' = 4 g4 + reg
 //     is d = 64 h + 4 c16' + e.  D/4 MFMAs per key tile for each product (32 + 32 at D = 128, 32 cycles each).
-__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 x 1 blocks, block = lane >> 2; acc[i] of lane 4 blk + j += a(lane 4 blk + i) * b(lane 4 blk + j)
 __device__ __forceinline__ f32x4 mfma_blk(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float row16_max(float v) {
@@ -479,12 +458,6 @@ __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, __builtin_amdgcn_update_dpp(v, v, 0x121, 0xf, 0xf, false));   // row_ror:1
   return v;
 }
-
-// A piece of a cached K / V row in the matrix-core kernel: one CU reads it once per step, and gigabytes of weights and other
-// rows pass before the next step reads it again, so it goes past the caches like the weight streams (gemv_f32.hip: load_w).
-// The KV append and the prologue's loads keep the default policy.
-template <typename V>
-__device__ __forceinline__ V load_kv(const void* p) { return __builtin_nontemporal_load((const V*)p); }
 
 // (a call, not an assignment: the address is computed before the value, which the epilogue's schedule depends on)
 template <typename T>

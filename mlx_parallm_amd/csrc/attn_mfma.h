@@ -28,4 +28,33 @@ __device__ __forceinline__ void pack2_split(float a, float b, uint32_t& hi, uint
   lo = __builtin_bit_cast(uint32_t, l);
 }
 
+// v_mfma_f32_16x16x4_f32: exact float32 products, one float per lane and operand (the float32 caches)
+__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// A piece of a cached K / V row in the matrix-core kernel: one CU reads it once per step, and gigabytes of weights and other
+// rows pass before the next step reads it again, so it goes past the caches like the weight streams (gemv_f32.hip: load_w).
+// The KV append and the prologue's loads keep the default policy.
+template <typename V>
+__device__ __forceinline__ V load_kv(const void* p) { return __builtin_nontemporal_load((const V*)p); }
+
+// The last split's combine: (max, sum, O[d]) of every split for one (head, d).  The loads of four splits are issued
+// together (a loop over a run-time split count with the loads inside waits one L2 round trip per load: ~8 in a row
+// for 4 splits), then merged in split order -- deterministic whoever arrived last.
+template <int D>
+__device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int d) {
+  float mn = -1e30f, L = 0.f, O[1] = {0.f};
+  for (int i0 = 0; i0 < nsplit; i0 += 4) {
+    float mv[4], lv[4], ov[4][1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float* q = pp + (size_t)min(i0 + j, nsplit - 1) * (D + 2);
+      mv[j] = __hip_atomic_load(&q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      lv[j] = __hip_atomic_load(&q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ov[j][0] = __hip_atomic_load(&q[2 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    merge_splits4<1>(mn, L, O, mv, lv, ov, nsplit - i0);
+  }
+  return merged_out(O[0], L);
+}
+
 }  // namespace mi

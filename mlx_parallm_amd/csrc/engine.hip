@@ -249,6 +249,27 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     if (nsplit[gi] > 1) MI_TRY(grow(st, &kv->partial, &kv->partial_cap, (size_t)kv->B * Hq * 16 * (D + 2) * sizeof(float)));
   }
 
+  // Shared-prefix attention (opt_shared_prefix > 0, a paged cache): the FIRST L == 1 group whose rows hold a set of two or more
+  // runs rope_append + one attn_shared launch over all its rows.  Decided here, ahead of the q|k|v linear, so that
+  // consumer_combine is not offered for such a step; every other step keeps its launches and its bits.
+  int shared_gi = -1, shared_tail = 1;
+  for (size_t gi = 0; gi < groups.size() && shared_gi < 0 && e->opt_shared_prefix > 0 && kv->paged; ++gi) {
+    const AttnGroup& g = groups[gi];
+    if (g.L != 1) continue;
+    AttnShape s{g.B, 1, Hq, Hkv, D, act, kv->dtype, RND_NONE, kv->cap, d_rows_of(g)};
+    kv_shape(kv, s);
+    if (!attention_shared_supported(s)) break;
+    std::vector<int32_t> grows(g.B);
+    for (int b = 0; b < g.B; ++b) grows[b] = row_of(g, b);
+    MI_TRY(kv_shared_sets(kv, grows.data(), g.B, e->opt_shared_prefix, st));
+    const KvBlocks::SharedSets& ss = kv->sets;
+    if (ss.max_members < 2) break;
+    shared_gi = (int)gi;
+    for (size_t si = 0; si + 1 < ss.ptr.size(); ++si)
+      for (int m = ss.ptr[si]; m < ss.ptr[si + 1]; ++m) shared_tail = std::max(shared_tail, kv->h_off[grows[ss.members[m]]] + 1 - ss.run[si]);
+    MI_TRY(grow(st, &kv->partial, &kv->partial_cap, (size_t)kv->B * Hq * 16 * (D + 2) * sizeof(float)));
+  }
+
   for (int li = 0; li < d.num_layers; ++li) {
     LayerW& lw = e->layers[li];
     const bool w32 = quirk && d.act_dtype != MI_F32;     // norm weights must match the activation storage type
@@ -260,7 +281,7 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
     // whose attention runs on the float32 MFMA kernel can add published K slices of q|k|v in its prologue
     bool cc_attn = false;
     int qkv_ks = 0;                              // > 0: this layer's q|k|v ran publish-only with that many K slices
-    if (e->opt_consumer_combine && e->opt_defer_norm && cur_L == 1 && rows == nullptr && groups.size() == 1 && groups[0].L == 1 && R <= 8 && act == MI_F32 &&
+    if (shared_gi < 0 && e->opt_consumer_combine && e->opt_defer_norm && cur_L == 1 && rows == nullptr && groups.size() == 1 && groups[0].L == 1 && R <= 8 && act == MI_F32 &&
         kv->dtype == MI_F32 && e->opt_fused_attn && e->opt_attn_mfma && D % 64 == 0 && D <= 128) {
       AttnShape s{groups[0].B, 1, Hq, Hkv, D, act, kv->dtype, rnd, kv->cap, nullptr};
       cc_attn = attention_decode_supported(s);
@@ -288,7 +309,18 @@ int forward(mi_engine* e, mi_kv* kv, const int32_t* rows, const std::vector<Attn
       const void* qkv_g = (const char*)e->qkv + g.tok0 * (size_t)nqkv * es;
       void* q_g = (char*)e->q + g.tok0 * (size_t)Hq * D * es;
       void* o_g = (char*)e->attn + g.tok0 * (size_t)Hq * D * es;
-      if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
+      if ((int)gi == shared_gi) {
+        { Prof pr(e, "rope_append");
+          RopeAppendCall rc{s, qkv_g, q_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps,
+                            e->cos_tab, e->sin_tab, d.max_positions};
+          MI_TRY(launch_rope_append(rc, st)); }
+        Prof pr(e, "attn_shared");
+        AttnShape sa = s; sa.rnd = RND_NONE;    // (as the unfused path below)
+        const KvBlocks::SharedSets& ss = kv->sets;
+        AttnSharedCall sc{sa, q_g, kc, vc, kv->d_off, o_g, 1.0f / sqrtf((float)D), kv->partial, kv->counters,
+                          kv->d_sets, kv->d_sets + g.B + 1, kv->d_sets + 2 * g.B + 1, (int)ss.run.size(), ss.max_members, ss.max_run, shared_tail, ss.n_shared};
+        MI_TRY(launch_attention_shared(sc, st));
+      } else if (g.L == 1 && e->opt_fused_attn && attention_decode_supported(s)) {
         // decode: norm + RoPE + append + attention + split combine in one launch
         AttnDecodeCall ac{s, qkv_g, kc, vc, kv->d_off, q_norm, k_norm, d.rms_norm_eps, e->cos_tab, e->sin_tab,
                           o_g, 1.0f / sqrtf((float)D), RND_NONE, nsplit[gi], kv->partial, kv->counters,
@@ -805,6 +837,11 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value) {
   if (k == "prefill_x_terms") { if (value != 2 && value != 3) return fail(MI_ERR_INVALID, "prefill_x_terms: 2 or 3"); e->opt_prefill_x_terms = (int)value; return MI_OK; }
   if (k == "short_prefill_skinny") { e->opt_short_prefill_skinny = value != 0; return MI_OK; }
   if (k == "decode_attention_mfma") { e->opt_attn_mfma = value != 0; return MI_OK; }
+  if (k == "shared_prefix_attention") {
+    if (value < 0) return fail(MI_ERR_INVALID, "shared_prefix_attention: 0 (off) or the least number of tokens a set shares");
+    e->opt_shared_prefix = (int)std::min<int64_t>(value, 1 << 30);
+    return MI_OK;
+  }
   if (k == "f16_hilo") { e->opt_f16_hilo = value != 0; return MI_OK; }
   if (k == "gate_up_interleave") { e->opt_gu8 = value != 0; return MI_OK; }
   if (k == "tile_weights") {

@@ -176,6 +176,8 @@ struct mi_engine {
   // the wide linears of a float32-KV decode step (gate|up, lm_head) at K <= 4096 on the resident form of gemv_f32.hip (x kept in
   // LDS; 0: the chunked kernel).  Bit-identical outputs; measurements: DESIGN §5, §8d
   int opt_resident_x = 1;
+  // > 0: decode steps read the blocks that rows share once per set (attn_shared.hip), for sets sharing at least that many tokens
+  int opt_shared_prefix = 0;
   float* cc_pub = nullptr; size_t cc_pub_cap = 0;      // the q|k|v seam: [guard][8 slices][8 rows][nqkv][guard][8 slices][8 rows][guard]
   float* d_sq = nullptr;        // [4096 tile groups][16 rows]
   mi::NormHandover handover;
@@ -225,6 +227,12 @@ struct mi_kv {
   bool paged = false;
   mi::KvBlocks blocks;
   int32_t* d_btab = nullptr;
+  // ---- shared-prefix attention: the sets of the last decode step that asked (kv_shared_sets), kept while the step's row list,
+  // the table (blocks.tab_version) and the threshold stay what they were; d_sets = [ptr: n + 1 | members: n | run: n]
+  mi::KvBlocks::SharedSets sets;
+  std::vector<int32_t> sets_rows;
+  uint64_t sets_version = 0; int sets_min = -1;
+  int32_t* d_sets = nullptr; size_t d_sets_cap = 0;
 };
 
 namespace mi {
@@ -255,6 +263,8 @@ float* cc_pub_sumsq(mi_engine* e, int nqkv);         // [8 slices][8 rows]
 int kv_ensure_blocks(mi_kv* kv, int row, int tokens);
 int kv_upload_table(mi_kv* kv, hipStream_t st);
 void kv_shape(const mi_kv* kv, AttnShape& s);
+// kv->sets / kv->d_sets describe the n cache rows `rows` of a decode step (after kv_ensure_blocks)
+int kv_shared_sets(mi_kv* kv, const int32_t* rows, int n, int min_tokens, hipStream_t st);
 size_t kv_layer_elems(const mi_kv* kv, const mi_model_desc& d);
 
 }  // namespace mi

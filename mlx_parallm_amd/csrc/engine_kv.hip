@@ -35,6 +35,31 @@ void kv_shape(const mi_kv* kv, AttnShape& s) {
   if (kv->paged) { s.btab = kv->d_btab; s.bt_stride = kv->blocks.bt_stride; s.bs_shift = kv->blocks.bs_shift; }
 }
 
+int kv_shared_sets(mi_kv* kv, const int32_t* rows, int n, int min_tokens, hipStream_t st) {
+  const KvBlocks& kb = kv->blocks;
+  if (kv->sets_min == min_tokens && kv->sets_version == kb.tab_version && kv->sets_rows.size() == (size_t)n &&
+      std::equal(rows, rows + n, kv->sets_rows.begin()))
+    return MI_OK;
+  kv->sets_min = -1;                             // (nothing is cached while this fails half way)
+  std::vector<int32_t> lens(n);
+  for (int i = 0; i < n; ++i) lens[i] = kv->h_off[rows[i]];
+  kv->sets = kb.shared_sets(rows, lens.data(), n, min_tokens);
+  const KvBlocks::SharedSets& ss = kv->sets;
+  kv->sets_rows.assign(rows, rows + n);
+  kv->sets_version = kb.tab_version;
+  if (ss.max_members < 2) { kv->sets_min = min_tokens; return MI_OK; }      // nobody shares: no launch reads d_sets, nothing is uploaded
+  std::vector<int32_t> img(ss.ptr);
+  img.resize(n + 1, (int32_t)n);
+  img.insert(img.end(), ss.members.begin(), ss.members.end());
+  img.insert(img.end(), ss.run.begin(), ss.run.end());
+  img.resize(3 * (size_t)n + 1, 0);
+  MI_TRY(grow(st, &kv->d_sets, &kv->d_sets_cap, img.size() * sizeof(int32_t)));
+  // (pageable host memory: staged by the runtime before the call returns, like the block table's upload)
+  MI_HIP(hipMemcpyAsync(kv->d_sets, img.data(), img.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  kv->sets_min = min_tokens;
+  return MI_OK;
+}
+
 size_t kv_layer_elems(const mi_kv* kv, const mi_model_desc& d) {
   return kv->paged ? ((size_t)kv->blocks.nblocks * d.num_kv_heads << kv->blocks.bs_shift) * d.head_dim
                    : (size_t)kv->B * d.num_kv_heads * kv->cap * d.head_dim;
@@ -187,7 +212,7 @@ void mi_kv_destroy(mi_kv* kv) {
   hipSetDevice(kv->e->device);
   hipStreamSynchronize(kv->e->stream);
   hipFree(kv->k); hipFree(kv->v); hipFree(kv->d_off); hipFree(kv->partial); hipFree(kv->counters); hipFree(kv->d_rows);
-  hipFree(kv->d_btab);
+  hipFree(kv->d_btab); hipFree(kv->d_sets);
   hipFree(kv->rb_block); hipFree(kv->lp_block);
   if (kv->rb_stage) hipHostFree(kv->rb_stage);
   for (hipEvent_t ev : kv->rb_ev) if (ev) hipEventDestroy(ev);

@@ -284,6 +284,30 @@ int launch_attention(const AttnCall& c, hipStream_t st);
 bool attention_prefill_supported(const AttnShape& s);
 int launch_attention_prefill(const AttnCall& c, hipStream_t st);
 
+// decode attention (L == 1) over a block-paged cache whose rows share leading blocks (attn_shared.hip): q is normed and roped
+// and the new key / value are appended already (launch_rope_append), so batch entry b attends to offsets[row of b] + 1 keys.
+// Every batch entry belongs to exactly one set; the members of a set map the same blocks over its first `run` tokens, which
+// one launch reads once per column group of 16 / (Hq/Hkv) members instead of once per row.
+struct AttnSharedCall {
+  AttnShape s;             // L == 1, btab set; s.rnd = logical rounding of the output
+  const void* q;           // [B][Hq*D]
+  const void* kcache;
+  const void* vcache;
+  const int32_t* offsets;  // device, by cache row: tokens in the cache BEFORE this step's append
+  void* out;               // [B][Hq*D]
+  float scale;
+  float* partial;          // [B*Hq][16][D+2]
+  int* counters;           // [B*Hkv] arrival tickets, zero between launches
+  const int32_t* set_ptr;      // device [n_sets + 1]: set i = set_members[set_ptr[i] .. set_ptr[i + 1])
+  const int32_t* set_members;  // device [B]: batch indices
+  const int32_t* set_run;      // device [n_sets]: tokens the set shares, a multiple of the block size (0: nothing)
+  int n_sets, max_members;     // host: the sets, the members of the largest
+  int max_run, max_tail;       // host: the longest run; the most keys a row has behind its run (the new key included)
+  int n_shared;                // host: the leading sets that have a run (every set behind them has run 0): prefix items cover these only
+};
+bool attention_shared_supported(const AttnShape& s);
+int launch_attention_shared(const AttnSharedCall& c, hipStream_t st);
+
 // fused decode step (L == 1): q/k norm + RoPE + KV append + split-KV attention + combine
 struct AttnDecodeCall {
   AttnShape s;             // s.rnd = logical rounding of q / k after norm and RoPE

@@ -9,6 +9,7 @@
 // exactly one row and is never in the prefix cache.  No shared block is ever written, because the kernels append at a row's
 // own length only -- behind its last full block, in a block of its own (ensure) or in the private copy that fork made.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <list>
@@ -25,6 +26,7 @@ struct KvBlocks {
   std::vector<int> refcnt;
   std::vector<int> free_blocks;
   bool btab_dirty = false;
+  uint64_t tab_version = 0;      // counts the changes of h_btab that can change what rows share: release, attach, fork
   // prefix cache: full blocks of prompts, keyed by the hash of ALL tokens up to and including the block; an entry keeps
   // the block's own tokens and its parent's key, so a hit is verified token by token (no reliance on the hash alone)
   struct PrefixEntry { int block; uint64_t parent; std::vector<int32_t> tokens; std::list<uint64_t>::iterator lru_it; };
@@ -51,7 +53,7 @@ struct KvBlocks {
       const int blk = take_block();
       if (blk < 0) return Ensure::EXHAUSTED;
       h_btab[(size_t)row * bt_stride + row_blocks[row]++] = blk;
-      btab_dirty = true;
+      btab_dirty = true;                         // (a fresh block of the row's own: no sharing changes, tab_version stays)
     }
     return Ensure::OK;
   }
@@ -61,7 +63,7 @@ struct KvBlocks {
       release_block(h_btab[(size_t)row * bt_stride + i]);
       h_btab[(size_t)row * bt_stride + i] = 0;
     }
-    if (row_blocks[row] > 0) btab_dirty = true;
+    if (row_blocks[row] > 0) table_changed();
     row_blocks[row] = 0;
   }
 
@@ -98,7 +100,7 @@ struct KvBlocks {
     lru_touch_chain(chain);
     stat_lookup_tokens += n;
     stat_hit_tokens += reused;
-    if (reused > 0) btab_dirty = true;
+    if (reused > 0) table_changed();
     return reused;
   }
 
@@ -143,8 +145,69 @@ struct KvBlocks {
     for (int i = 0; i < full; ++i) { d[i] = s[i]; ++refcnt[s[i]]; }
     if (tail) { d[full] = own; *src_tail_blk = s[full]; *dst_tail_blk = own; }
     row_blocks[dst] = full + (tail ? 1 : 0);
-    btab_dirty = true;
+    table_changed();
     return Ensure::OK;
+  }
+
+  // The rows of one decode step that map the same blocks in front (forked choices, rows attached to one published prefix), as
+  // the shared-prefix attention takes them.  rows[i] (i < n) holds lens[i] tokens before the step.
+  //   lcp(i, j) = the leading table indices at which both rows name the same non-zero block and both hold it fully;
+  //   best(i)   = the largest lcp(i, j) over the other rows.
+  // i and j are in one set iff lcp(i, j) == best(i) == best(j) > 0 -- one level: a row joins the rows it shares most with.  The
+  // block ids are compared index by index, never inferred from a later index: a row that published only the later blocks of
+  // a chain maps other physical blocks in front of them.  A set whose run (lcp x block size) is below min_tokens is not used:
+  // its members become sets of one with run 0, like every row that shares nothing.
+  // Every entry lands in exactly one set; the sets of two or more first, then the sets of one, each kind in the order of
+  // its first member; members ascending (entries, not rows).
+  struct SharedSets {
+    std::vector<int32_t> ptr, members, run;      // CSR: set s = members[ptr[s] .. ptr[s + 1]), run[s] tokens shared
+    int max_members = 0, max_run = 0;            // of the sets (max_members >= 2: some rows share)
+    int n_shared = 0;                            // the leading sets of two or more (run > 0); sets of one follow, run 0
+  };
+  // The result depends on the row list and the table alone once lens are the rows' true lengths: a block is shared only while
+  // full (the invariant above), and a row's block becomes full without a table change only while no other row maps it.  So a
+  // caller may keep it until the row list differs or tab_version has moved (ensure, which only appends fresh blocks of a row's
+  // own, does not move it: a large batch whose rows cross block boundaries on most steps keeps its result).
+  SharedSets shared_sets(const int32_t* rows, const int32_t* lens, int n, int min_tokens) const {
+    auto lcp = [&](int i, int j) {
+      const int32_t* a = &h_btab[(size_t)rows[i] * bt_stride];
+      const int32_t* b = &h_btab[(size_t)rows[j] * bt_stride];
+      if (a[0] == 0 || a[0] != b[0] || rows[i] == rows[j]) return 0;      // (nearly every pair of unrelated rows ends here)
+      const int full = std::min(std::min(lens[i], lens[j]) >> bs_shift, bt_stride);
+      int k = 0;
+      while (k < full && a[k] != 0 && a[k] == b[k]) ++k;
+      return k;
+    };
+    std::vector<int> best(n, 0);
+    for (int i = 0; i < n; ++i)
+      for (int j = i + 1; j < n; ++j) {
+        const int k = lcp(i, j);
+        if (k > best[i]) best[i] = k;
+        if (k > best[j]) best[j] = k;
+      }
+    std::vector<int> lead(n, -1), cnt(n, 0);     // the first member of i's set; members of the set that i leads
+    for (int i = 0; i < n; ++i) {
+      if (lead[i] >= 0) continue;
+      lead[i] = i; cnt[i] = 1;
+      if (best[i] > 0 && (best[i] << bs_shift) >= min_tokens)
+        for (int j = i + 1; j < n; ++j)
+          if (lead[j] < 0 && best[j] == best[i] && lcp(i, j) == best[i]) { lead[j] = i; ++cnt[i]; }
+    }
+    SharedSets out;
+    out.ptr.push_back(0);
+    for (int pass = 0; pass < 2; ++pass) {       // the sets that share first: the launch's prefix items cover the leading n_shared
+      for (int i = 0; i < n; ++i) {
+        if (lead[i] != i || (cnt[i] > 1) != (pass == 0)) continue;
+        for (int j = i; j < n; ++j) if (lead[j] == i) out.members.push_back(j);
+        const int run = pass == 0 ? best[i] << bs_shift : 0;
+        out.run.push_back(run);
+        out.ptr.push_back((int32_t)out.members.size());
+        if (cnt[i] > out.max_members) out.max_members = cnt[i];
+        if (run > out.max_run) out.max_run = run;
+      }
+      if (pass == 0) out.n_shared = (int)out.run.size();
+    }
+    return out;
   }
 
   void clear_prefix() {
@@ -164,6 +227,8 @@ struct KvBlocks {
   }
 
  private:
+  void table_changed() { btab_dirty = true; ++tab_version; }
+
   static uint64_t prefix_hash(uint64_t parent, const int32_t* toks, int n) {
     uint64_t h = parent ^ 0x9E3779B97F4A7C15ull;
     for (int i = 0; i < n; ++i) { h ^= (uint64_t)(uint32_t)toks[i] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xD6E8FEB86659FD93ull; }

@@ -428,6 +428,23 @@ int mi_op_attention(const mi_op_attn_shape* s, const void* q, const void* kcache
   return finish();
 }
 
+int mi_op_attention_shared(const mi_op_attn_shape* s, const int32_t* btab, int bt_stride, int bs_shift, const void* q,
+                           const void* kcache, const void* vcache, const int32_t* offsets, const int32_t* set_ptr,
+                           const int32_t* set_members, const int32_t* set_run, int n_sets, int n_shared, int max_members,
+                           int max_run, int max_tail, void* out, float scale, float* partial, int32_t* counters, int iters, float* avg_ms) {
+  if (!s) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  AttnShape sh = to_shape(s);
+  sh.btab = btab; sh.bt_stride = bt_stride; sh.bs_shift = bs_shift;
+  const AttnSharedCall sc{sh, q, kcache, vcache, offsets, out, scale, partial, (int*)counters,
+                          set_ptr, set_members, set_run, n_sets, max_members, max_run, max_tail, n_shared};
+  if (iters <= 1) {
+    MI_TRY(launch_attention_shared(sc, nullptr));
+    return finish();
+  }
+  return run_timed_strict([&] { return launch_attention_shared(sc, nullptr); }, iters, avg_ms);
+}
+
 // one launch, or iters back-to-back launches behind a warm-up one, timed into *avg_ms
 static int run_attention_decode(const AttnDecodeCall& ac, int iters, float* avg_ms) {
   if (iters <= 1) {

@@ -98,6 +98,7 @@ class ServerConfig:
     kv_blocks: Optional[int] = None
     prefix_cache: bool = True
     fork_choices: bool = False                    # the n choices of a request share one prompt prefill (KV rows are forked)
+    shared_prefix_attention: int = 0              # decode attention reads blocks shared by >= N tokens once per set of rows (0: off)
     # continuous scheduler: name -> adapter directory.  Every adapter is resident in a slot of the engine's per-request table;
     # a request whose `model` is such a name runs on it, in the same steps as everybody else.  Not together with lora_path.
     lora_modules: Optional[Dict[str, str]] = None
@@ -845,7 +846,8 @@ def create_app(config: Optional[ServerConfig] = None, *, model=None, tokenizer=N
             state.scheduler = ReplicaPool([rec.model_instance] + state.extra_replicas, rec.tokenizer_instance,
                                           max_slots=config.max_batch_size, metrics=state.metrics,
                                           chunk_tokens=config.chunk_tokens, kv_blocks=config.kv_blocks,
-                                          prefix_cache=config.prefix_cache, fork_choices=config.fork_choices)
+                                          prefix_cache=config.prefix_cache, fork_choices=config.fork_choices,
+                                          shared_prefix_tokens=config.shared_prefix_attention)
             state.scheduler.start()
             state.tasks = []
         else:

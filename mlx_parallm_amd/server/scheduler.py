@@ -209,7 +209,7 @@ class ContinuousScheduler:
     def __init__(self, model, tokenizer, max_slots: int = 8, kv_dtype: Optional[str] = None, capacity: int = 1024,
                  metrics=None, chunk_tokens: int = 256, paged: bool = True, block_tokens: int = 64,
                  kv_blocks: Optional[int] = None, prefix_cache: bool = True, step_rows: int = 256,
-                 fork_choices: bool = False):
+                 fork_choices: bool = False, shared_prefix_tokens: int = 0):
         from ..engine import SampleArgs      # noqa: F401  (fail early if the library is missing)
         from ..utils import DEFAULT_KV_DTYPE
 
@@ -228,6 +228,13 @@ class ContinuousScheduler:
         else:
             self.kv = eng.new_kv(self.max_slots, capacity=capacity, kv_dtype=kv_dtype or DEFAULT_KV_DTYPE)
         self.prefix_cache = bool(prefix_cache) and self.paged
+        # decode steps read the blocks that rows share (forked choices, a common prompt prefix) once per set of rows instead of
+        # once per row, for sets that share at least this many tokens (engine option "shared_prefix_attention"; 0: off)
+        self.shared_prefix_tokens = int(shared_prefix_tokens) if self.paged else 0
+        if self.shared_prefix_tokens < 0:
+            raise ValueError("shared_prefix_tokens must be >= 0")
+        if self.shared_prefix_tokens > 0:
+            eng.set_option("shared_prefix_attention", self.shared_prefix_tokens)
         self.prefix_hit_tokens = 0
         # the choices of one request (submit(..., group=)) share one prompt prefill: a member admitted while another one
         # holds the prompt in its row gets that row's first P - 1 tokens (KVCache.fork_row) and runs the last prompt token
