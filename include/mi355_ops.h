@@ -47,6 +47,24 @@ extern "C" {
 #define MI_WK_Q8_F32 6
 #define MI_WK_Q8_BF16 7
 #define MI_WK_Q8_F16 8
+/* MLX-affine 3- and 6-bit codes, group 64.  Row-major (layout 0) `w` is uint32 [N][K bits / 32]: code j of a row occupies bits
+ * [bits j, bits (j + 1)) of the row's little-endian byte stream (a code may straddle a dword).  Tile-major (layout 1, made by
+ * mi_op_repack_tiled; N % 16 == 0, K % 128 == 0) the matrix is one buffer of bit planes, block (row / 16, k / 128) at
+ * ((row / 16) (K / 128) + k / 128) x B bytes; lane l = 16 g + (row % 16) of a block owns the 32 codes k % 128 = 32 T + 8 g + e:
+ *   6 bits, B = 1664: [0, 1024) low nibbles -- dword T of the lane's 16 bytes holds e = 2 w at nibble w, e = 2 w + 1 at
+ *                     nibble w + 4; [1024, 1536) the two high bits -- dword T / 2 of the lane's 8 bytes, field
+ *                     2 (4 (T % 2) + w) (+ 16 for odd e); [1536, 1600) scales, row r -> 2 x 16 bit; [1600, 1664) biases
+ *   3 bits, B = 896:  [0, 512) the two low bits, laid out as the 6-bit high plane; [512, 768) the high bit -- bit 4 T + w
+ *                     (+ 16 for odd e) of the lane's dword; [768, 832) scales; [832, 896) biases
+ * mi_op_tiled_bytes is exactly N K bits / 8 + N (K / 64) 4: the resident copy stays packed and carries NO over-read padding.
+ * Over-read rule of these kinds: a kernel never reads past mi_op_tiled_bytes -- gemm_q36.hip addresses blocks of the matrix
+ * only and clamps its prefetch to the slice's last block; the caller provides a buffer of mi_op_tiled_bytes. */
+#define MI_WK_Q3_F32 9
+#define MI_WK_Q3_BF16 10
+#define MI_WK_Q3_F16 11
+#define MI_WK_Q6_F32 12
+#define MI_WK_Q6_BF16 13
+#define MI_WK_Q6_F16 14
 
 /* run-time logical rounding on top of the storage dtype */
 #define MI_RND_NONE 0

@@ -193,9 +193,16 @@ enum : int {
   WK_F32 = 0, WK_BF16 = 1, WK_F16 = 2,
   WK_Q4_F32 = 3, WK_Q4_BF16 = 4, WK_Q4_F16 = 5,
   WK_Q8_F32 = 6, WK_Q8_BF16 = 7, WK_Q8_F16 = 8,
+  WK_Q3_F32 = 9, WK_Q3_BF16 = 10, WK_Q3_F16 = 11,      // 3 / 6 bits: codes are a bit stream, not dword-aligned (quant.py)
+  WK_Q6_F32 = 12, WK_Q6_BF16 = 13, WK_Q6_F16 = 14,
 };
 inline bool wk_is_quant(int wk) { return wk >= WK_Q4_F32; }
-inline int wk_bits(int wk) { return wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0); }
+__host__ __device__ constexpr int wk_bits(int wk) {
+  return wk >= WK_Q6_F32 ? 6 : wk >= WK_Q3_F32 ? 3 : wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0);
+}
+inline bool wk_is_q36(int wk) { return wk >= WK_Q3_F32 && wk <= WK_Q6_F16; }
+// base kind of a bit width (+ 0 / 1 / 2 for float32 / bf16 / f16 scales); -1: a width the kernels do not read
+inline int wk_base_of_bits(int bits) { return bits == 4 ? WK_Q4_F32 : bits == 8 ? WK_Q8_F32 : bits == 3 ? WK_Q3_F32 : bits == 6 ? WK_Q6_F32 : -1; }
 inline int wk_scale_dtype(int wk) { return wk_is_quant(wk) ? (wk - 3) % 3 : wk; }
 
 }  // namespace mi

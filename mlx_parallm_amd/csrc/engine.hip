@@ -567,7 +567,12 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     return fail(MI_ERR_INVALID, "model dimensions must be positive");
   if (d.num_heads % d.num_kv_heads != 0) return fail(MI_ERR_INVALID, "num_heads must be a multiple of num_kv_heads");
   if (d.act_dtype != MI_F32 && d.act_dtype != MI_BF16 && d.act_dtype != MI_F16) return fail(MI_ERR_INVALID, "bad act_dtype");
-  if (d.quant_bits != 0 && d.quant_bits != 4 && d.quant_bits != 8) return fail(MI_ERR_UNSUPPORTED, "quant_bits must be 0, 4 or 8");
+  if (d.quant_bits != 0 && wk_base_of_bits(d.quant_bits) < 0)
+    return fail(MI_ERR_UNSUPPORTED, "quant_bits must be 0, 3, 4, 6 or 8 (2- and 5-bit checkpoints are not supported)");
+  if ((d.quant_bits == 3 || d.quant_bits == 6) && d.quant_group_size != 64)
+    return fail(MI_ERR_UNSUPPORTED, "quant_bits " + std::to_string(d.quant_bits) + " needs quant_group_size 64 (groups of 32 / 128 are served at 4 and 8 bits only)");
+  if ((d.quant_bits == 3 || d.quant_bits == 6) && (d.hidden_size % 32 || d.intermediate_size % 32 || (d.num_heads * d.head_dim) % 32))
+    return fail(MI_ERR_UNSUPPORTED, "quant_bits " + std::to_string(d.quant_bits) + " needs hidden, intermediate and attention widths that are multiples of 32 (whole dwords per row)");
   if (d.hidden_size % 8 || d.intermediate_size % 8 || (d.num_heads * d.head_dim) % 8)
     return fail(MI_ERR_UNSUPPORTED, "hidden / intermediate sizes must be multiples of 8");
   if (d.rope_traditional && d.arch == MI_ARCH_QWEN3)
@@ -580,6 +585,8 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     // quantised experts (moe_q.hip): MLX-affine int4 / int8 in groups of 64.  The engine takes them at widths that are whole
     // 128-k blocks for both bit widths (every published Mixtral: 4096 / 14336, 6144 / 16384); the int8 kernel itself runs on
     // 64-k blocks (mi_op_moe_linear_q)
+    if (d.quant_bits == 3 || d.quant_bits == 6)
+      return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits " + std::to_string(d.quant_bits) + " is not supported (the grouped expert kernels read int4 and int8 only)");
     if (d.quant_bits != 0 && d.quant_group_size != 64)
       return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_bits " + std::to_string(d.quant_bits) + " needs quant_group_size 64 (groups of 32 / 128 are not supported)");
     if (d.quant_bits != 0 && (d.hidden_size % 128 || d.intermediate_size % 128))

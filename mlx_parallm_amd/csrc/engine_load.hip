@@ -12,7 +12,7 @@ namespace {
 
 int kind_of(const FusedLinear& f, int bits) {
   if (!f.quant) return f.dense_dtype == MI_F32 ? WK_F32 : (f.dense_dtype == MI_BF16 ? WK_BF16 : WK_F16);
-  const int base = bits == 8 ? WK_Q8_F32 : WK_Q4_F32;
+  const int base = wk_base_of_bits(bits);                 // (mi_engine_create admits 3, 4, 6 and 8)
   return base + (f.scale_dtype == MI_F32 ? 0 : (f.scale_dtype == MI_BF16 ? 1 : 2));
 }
 

@@ -56,6 +56,27 @@ __device__ __forceinline__ void load8(const GemvParams& p, int row, int kb, floa
     const f16* h = (const f16*)&v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (float)h[j];
+  } else if constexpr (WK >= WK_Q3_F32) {
+    // 3 / 6 bits: the tile-major bit planes (repack.hip), or the checkpoint's bit stream, whose codes straddle dwords
+    constexpr int BITS = wk_bits(WK);
+    constexpr int SDT = (WK - 3) % 3;
+    float s, b;
+    if (SDT != 0 && p.layout) {
+      const uint8_t* blk = (const uint8_t*)p.w + tiled_block_q36(BITS, row, kb, p.K);
+      const int so = tiled_q36_scale_off(BITS, row, kb);
+      if constexpr (SDT == 1) { s = (float)*(const bf16*)(blk + so); b = (float)*(const bf16*)(blk + so + 64); }
+      else { s = (float)*(const f16*)(blk + so); b = (float)*(const f16*)(blk + so + 64); }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = mul_add_unfused((float)tiled_q36_code(BITS, blk, row, kb + j), s, b);
+    } else {
+      const size_t gi = (size_t)row * (p.K / p.group) + kb / p.group;
+      if constexpr (SDT == 0) { s = ((const float*)p.scales)[gi]; b = ((const float*)p.biases)[gi]; }
+      else if constexpr (SDT == 1) { s = (float)((const bf16*)p.scales)[gi]; b = (float)((const bf16*)p.biases)[gi]; }
+      else { s = (float)((const f16*)p.scales)[gi]; b = (float)((const f16*)p.biases)[gi]; }
+      const uint32_t* rw = (const uint32_t*)p.w + (size_t)row * (p.K * BITS / 32);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = mul_add_unfused((float)q36_stream_code(rw, BITS, kb + j), s, b);
+    }
   } else {
     constexpr int BITS = (WK >= WK_Q8_F32) ? 8 : 4;
     constexpr int SDT = (WK - 3) % 3;  // 0 f32, 1 bf16, 2 f16
@@ -276,6 +297,12 @@ int launch_wk(int wk, const GemvParams& p, hipStream_t st) {
     case WK_Q8_BF16: if constexpr (F32A || std::is_same<AT, bf16>::value) return launch_mt<AT, WK_Q8_BF16>(p, st); break;
     case WK_Q4_F16: if constexpr (F32A || std::is_same<AT, f16>::value) return launch_mt<AT, WK_Q4_F16>(p, st); break;
     case WK_Q8_F16: if constexpr (F32A || std::is_same<AT, f16>::value) return launch_mt<AT, WK_Q8_F16>(p, st); break;
+    case WK_Q3_F32: if constexpr (F32A) return launch_mt<AT, WK_Q3_F32>(p, st); break;
+    case WK_Q6_F32: if constexpr (F32A) return launch_mt<AT, WK_Q6_F32>(p, st); break;
+    case WK_Q3_BF16: if constexpr (F32A || std::is_same<AT, bf16>::value) return launch_mt<AT, WK_Q3_BF16>(p, st); break;
+    case WK_Q6_BF16: if constexpr (F32A || std::is_same<AT, bf16>::value) return launch_mt<AT, WK_Q6_BF16>(p, st); break;
+    case WK_Q3_F16: if constexpr (F32A || std::is_same<AT, f16>::value) return launch_mt<AT, WK_Q3_F16>(p, st); break;
+    case WK_Q6_F16: if constexpr (F32A || std::is_same<AT, f16>::value) return launch_mt<AT, WK_Q6_F16>(p, st); break;
   }
   return fail(MI_ERR_UNSUPPORTED, "gemv: weight kind / activation dtype combination not supported");
 }
@@ -298,6 +325,7 @@ int launch_gemv_v1(const LinearW& W, const GemvCall& c, hipStream_t st) {
   if (W.K % 8 != 0) return fail(MI_ERR_UNSUPPORTED, "gemv: K must be a multiple of 8");
   if (wk_is_quant(W.wk) && (W.group % 8 != 0 || W.K % W.group != 0))
     return fail(MI_ERR_UNSUPPORTED, "gemv: bad quantisation group size");
+  if (wk_is_q36(W.wk) && W.K % 32 != 0) return fail(MI_ERR_UNSUPPORTED, "gemv: 3- / 6-bit rows must be whole dwords (K % 32 == 0)");
   if (c.epi == EPI_SWIGLU && c.pair_offset * 2 != W.N) return fail(MI_ERR_INVALID, "gemv: swiglu needs N = 2*pair_offset");
   GemvParams p = make_params(W, c);
   switch (c.act) {

@@ -85,7 +85,7 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
 size_t split3_bytes(size_t rows, int K);
 int launch_split3_rows(const void* x, int ldx, const void* norm_w, float eps, void* out, int rows, int K, hipStream_t st,
                        int terms = 3);
-// int4 (tile-major) -> 16-bit tile-major [hi | lo], K' = 2K: the operand of the prefill GEMM for quantised weights
+// int4 / int8 / int3 / int6 (tile-major) -> 16-bit tile-major [hi | lo], K' = 2K: the operand of the prefill GEMM for quantised weights
 size_t dequant_hilo_bytes(int N, int K);
 int launch_dequant_q4_hilo(const LinearW& src, void* dst, hipStream_t st);
 // block_per_row: one workgroup per row, row in registers -- for the few rows of a decode step (default: one wave
@@ -165,6 +165,45 @@ __host__ __device__ inline int tiled_q8_code_off(size_t row, int k) {   // withi
   return (((k >> 4) & 3) * 16 + (int)(row & 15)) * 16 + (k & 15);
 }
 __host__ __device__ inline int tiled_q8_scale_off(size_t row) { return 1024 + (int)(row & 15) * 2; }   // + 32 for the bias
+
+// ---- 3- and 6-bit codes (group 64; include/mi355_ops.h has the two layouts)
+// row-major: code j of a row whose packed words start at `row_words` (a code may straddle two dwords; the last code of a row
+// ends on the row's last bit, so word d + 1 is read inside the row only)
+__host__ __device__ inline uint32_t q36_stream_code(const uint32_t* row_words, int bits, int j) {
+  const int bit = bits * j, d = bit >> 5, s = bit & 31;
+  uint32_t v = row_words[d] >> s;
+  if (s + bits > 32) v |= row_words[d + 1] << (32 - s);
+  return v & ((1u << bits) - 1u);
+}
+// tile-major: byte offset of the block of (row, k), the code of (row, k) inside it, the scale of (row, k) (+ 64: the bias)
+__host__ __device__ constexpr int q36_block_bytes(int bits) { return bits == 6 ? 1664 : 896; }
+__host__ __device__ inline size_t tiled_block_q36(int bits, size_t row, int k, int K) {
+  return ((row >> 4) * (size_t)(K / 128) + (size_t)(k >> 7)) * q36_block_bytes(bits);
+}
+__host__ __device__ inline uint32_t tiled_q36_code(int bits, const uint8_t* blk, size_t row, int k) {
+  const int T = (k >> 5) & 3, g = (k >> 3) & 3, w = (k >> 1) & 3, h = k & 1;
+  const int lane = g * 16 + (int)(row & 15), f = 2 * (4 * (T & 1) + w) + 16 * h;
+  if (bits == 6) {
+    const uint32_t nib = *(const uint32_t*)(blk + lane * 16 + T * 4);
+    const uint32_t hi2 = *(const uint32_t*)(blk + 1024 + lane * 8 + (T >> 1) * 4);
+    return ((nib >> (4 * w + 16 * h)) & 15u) | (((hi2 >> f) & 3u) << 4);
+  }
+  const uint32_t lo2 = *(const uint32_t*)(blk + lane * 8 + (T >> 1) * 4);
+  const uint32_t hi1 = *(const uint32_t*)(blk + 512 + lane * 4);
+  return ((lo2 >> f) & 3u) | (((hi1 >> (4 * T + w + 16 * h)) & 1u) << 2);
+}
+__host__ __device__ inline int tiled_q36_scale_off(int bits, size_t row, int k) {
+  return (bits == 6 ? 1536 : 768) + (int)(row & 15) * 4 + ((k >> 6) & 1) * 2;
+}
+
+// 3- / 6-bit (group 64, tile-major) weights, 1..128 rows of 16-bit activations (gemm_q36.hip): c.pro must be PRO_NONE
+// (normalise first); K split over workgroups through `ws` >= gemm_q36_ws_bytes() and `ctr` >= gemm_q36_groups() words that are
+// zero between launches (the kernel leaves them zero); ksplit = 0 lets the launcher choose.
+bool gemm_q36_supported(const LinearW& W, const GemvCall& c, size_t rows);
+int gemm_q36_ksplit(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+size_t gemm_q36_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+int gemm_q36_groups(const LinearW& W, const GemvCall& c, size_t rows);
+int launch_gemm_q36(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
 
 // ---- lora_rows.hip (the LoRA launches themselves: lora_rows.h)
 // out[m][n] = T(T(g * T(sigmoid(g))) * u) with g = x[m][n], u = x[m][I + n]: the SwiGLU of a gate|up output stored by an

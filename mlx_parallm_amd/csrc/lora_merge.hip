@@ -175,6 +175,8 @@ int check_quant_shape(const char* who, int N, int K, int dtype, int bits, int gr
   if (dtype == MI_F32) return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": float32 models are not supported (bf16 / f16 only)");
   if (dtype != MI_BF16 && dtype != MI_F16) return fail(MI_ERR_INVALID, std::string(who) + ": bad dtype");
   if (N < 1 || K < 1) return fail(MI_ERR_INVALID, std::string(who) + ": N and K must be positive");
+  if (bits == 6)
+    return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": a 6-bit base is not supported (the merge re-quantises at 4 and 8 bits only; keep the adapter beside the base)");
   if (bits != 4 && bits != 8) return fail(MI_ERR_INVALID, std::string(who) + ": quant_bits must be 4 or 8");
   if (group == 32 || group == 128) return fail(MI_ERR_UNSUPPORTED, std::string(who) + ": quantisation groups of 64 only");
   if (group != GROUP) return fail(MI_ERR_INVALID, std::string(who) + ": bad quantisation group");

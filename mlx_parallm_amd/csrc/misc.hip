@@ -49,7 +49,27 @@ __global__ __launch_bounds__(256) void embed_kernel(LinearW W, EmbedCall c) {
     else if constexpr (WK == WK_F16)
       v = W.layout ? (float)((const f16*)((const char*)W.w + tiled_piece_dense16(tok, k8, W.K)))[k & 7]
                    : (float)((const f16*)W.w)[(size_t)tok * W.K + k];
-    else {
+    else if constexpr (WK >= WK_Q3_F32) {
+      // 3 / 6 bits: 32 / BITS codes per word does not hold -- the tile-major bit planes, or the straddling bit stream
+      constexpr int BITS = wk_bits(WK);
+      constexpr int SDT = (WK - 3) % 3;
+      float s, b;
+      uint32_t q;
+      if (SDT != 0 && W.layout) {
+        const uint8_t* blk = (const uint8_t*)W.w + tiled_block_q36(BITS, tok, k, W.K);
+        const int so = tiled_q36_scale_off(BITS, tok, k);
+        if constexpr (SDT == 1) { s = (float)*(const bf16*)(blk + so); b = (float)*(const bf16*)(blk + so + 64); }
+        else { s = (float)*(const f16*)(blk + so); b = (float)*(const f16*)(blk + so + 64); }
+        q = tiled_q36_code(BITS, blk, tok, k);
+      } else {
+        const size_t gi = (size_t)tok * (W.K / W.group) + k / W.group;
+        if constexpr (SDT == 0) { s = ((const float*)W.scales)[gi]; b = ((const float*)W.biases)[gi]; }
+        else if constexpr (SDT == 1) { s = (float)((const bf16*)W.scales)[gi]; b = (float)((const bf16*)W.biases)[gi]; }
+        else { s = (float)((const f16*)W.scales)[gi]; b = (float)((const f16*)W.biases)[gi]; }
+        q = q36_stream_code((const uint32_t*)W.w + (size_t)tok * (W.K * BITS / 32), BITS, k);
+      }
+      v = mul_add_unfused((float)q, s, b);
+    } else {
       constexpr int BITS = (WK >= WK_Q8_F32) ? 8 : 4;
       constexpr int SDT = (WK - 3) % 3;
       constexpr int PER = 32 / BITS;
@@ -95,6 +115,12 @@ int launch_embed_wk(const LinearW& W, const EmbedCall& c, hipStream_t st) {
     case WK_Q8_F32: EK(WK_Q8_F32);
     case WK_Q8_BF16: EK(WK_Q8_BF16);
     case WK_Q8_F16: EK(WK_Q8_F16);
+    case WK_Q3_F32: EK(WK_Q3_F32);
+    case WK_Q3_BF16: EK(WK_Q3_BF16);
+    case WK_Q3_F16: EK(WK_Q3_F16);
+    case WK_Q6_F32: EK(WK_Q6_F32);
+    case WK_Q6_BF16: EK(WK_Q6_BF16);
+    case WK_Q6_F16: EK(WK_Q6_F16);
     default: return fail(MI_ERR_UNSUPPORTED, "embed: bad weight kind");
   }
 #undef EK

@@ -199,6 +199,18 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
     gemm_q4_force(-ksplit);
     if (!gemm_q4_supported(W, c, (size_t)c.M)) return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: ksplit < 0 forces gemm_q4, which does not take this call");
   }
+  if (wk_is_q36(W.wk)) {                         // 3 / 6 bits: gemm_q36.hip (ksplit > 0 forces its K slices)
+    if (ksplit < 0 || !gemm_q36_supported(W, c, (size_t)c.M) || c.pro != PRO_NONE)
+      return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: 3- / 6-bit weights take 1..128 rows of 16-bit activations in the scales' dtype, tile-major, no prologue");
+    const int ks = gemm_q36_ksplit(W, c, (size_t)c.M, ksplit), groups = gemm_q36_groups(W, c, (size_t)c.M);
+    void* ws = nullptr; void* ctr = nullptr;
+    FreeGuard g_ws{ws}, g_ctr{ctr};
+    MI_HIP(hipMalloc(&ws, std::max<size_t>(1024, gemm_q36_ws_bytes(W, c, (size_t)c.M, ksplit))));
+    MI_HIP(hipMalloc(&ctr, (size_t)groups * sizeof(unsigned)));
+    MI_HIP(hipMemset(ctr, 0, (size_t)groups * sizeof(unsigned)));
+    if (ksplit_used) *ksplit_used = ks;
+    return run_timed([&] { return launch_gemm_q36(W, c, (size_t)c.M, nullptr, ws, (unsigned*)ctr, ksplit); }, iters, avg_ms);
+  }
   if (!gemm_skinny_supported(W, c, (size_t)c.M) && !gemm_q4_supported(W, c, (size_t)c.M))
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: call not supported by this kernel");
   const int groups = std::max(1, gemm_skinny_groups(W, c, (size_t)c.M));
@@ -224,7 +236,7 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   if (c.act == MI_F32)
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: 16-bit activations only (float32 activations: mi_op_gemm_prefill_f32)");
   if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || (wk_is_quant(W.wk) && !gemm_prefill_supported(W, c, (size_t)c.M)))
-    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int4 or int8 (group 64) weights, 16-bit activations, no prologue");
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int3 / int4 / int6 / int8 (group 64) weights, 16-bit activations, no prologue");
   void* ws = nullptr; void* scratch = nullptr; size_t cap = 0;
   FreeGuard g_ws{ws}, g_scratch{scratch};
   if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, W.K)));

@@ -16,6 +16,10 @@
 //   int8 (g64):   block (i, j = k/64) at ((i * K/64 + j) * 1088) bytes:
 //                 [0,1024)    codes: lane l = g*16 + r owns the 16 codes W[16i+r][64j + 16g .. +16) (4 packed dwords)
 //                 [1024,1056) scales: row r -> one 16-bit value;  [1056,1088) biases.
+//   int6 / int3 (g64): bit planes per block (i, j = k/128) of 1664 / 896 bytes, exactly the codes' bits + scales + biases:
+//                 lane l = g*16 + r owns the codes k%128 = 32T + 8g + e in the order an MFMA B operand takes them (step T,
+//                 dword w = e/2, half e%2), so that the decode kernel's unpack is shift + and-or on whole dwords and never
+//                 crosses one (include/mi355_ops.h has the byte map; gemm_q36.hip the reasons).
 #include "kernels.h"
 
 namespace mi {
@@ -67,6 +71,42 @@ __global__ void repack_q8_kernel(const uint32_t* codes, const uint16_t* scales, 
     if (g == 0) {
       *(uint16_t*)(base + 1024 + r * 2) = scales[row * (K / 64) + j];
       *(uint16_t*)(base + 1056 + r * 2) = biases[row * (K / 64) + j];
+    }
+  }
+}
+
+// 3- / 6-bit codes: the checkpoint's bit stream (code j at bits [BITS j, BITS (j + 1)) of the row, straddling dwords) -> the
+// bit planes of the tile-major block.  One thread per (block, lane): its 32 codes, gathered one by one (this runs once).
+template <int BITS>
+__global__ void repack_q36_kernel(const uint32_t* codes, const uint16_t* scales, const uint16_t* biases, uint8_t* dst, int N, int K) {
+  const int nb = K / 128;
+  const size_t blocks = (size_t)(N / 16) * nb, row_words = (size_t)K * BITS / 32;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < blocks * 64; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / nb, j = blk % nb;
+    const size_t row = i * 16 + r;
+    const uint32_t* rw = codes + row * row_words;
+    uint8_t* base = dst + blk * q36_block_bytes(BITS);
+    uint32_t lo[4] = {0u, 0u, 0u, 0u}, mid[2] = {0u, 0u}, top = 0u;      // nibble image | 2-bit plane | 1-bit plane
+    for (int T = 0; T < 4; ++T)
+      for (int e = 0; e < 8; ++e) {
+        const uint32_t q = q36_stream_code(rw, BITS, (int)j * 128 + 32 * T + 8 * g + e);
+        const int w = e >> 1, h = e & 1, f = 2 * (4 * (T & 1) + w) + 16 * h;
+        if (BITS == 6) { lo[T] |= (q & 15u) << (4 * w + 16 * h); mid[T >> 1] |= (q >> 4) << f; }
+        else { mid[T >> 1] |= (q & 3u) << f; top |= (q >> 2) << (4 * T + w + 16 * h); }
+      }
+    if (BITS == 6) {
+      *(u32x4*)(base + lane * 16) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+      *(uint2*)(base + 1024 + lane * 8) = uint2{mid[0], mid[1]};
+    } else {
+      *(uint2*)(base + lane * 8) = uint2{mid[0], mid[1]};
+      *(uint32_t*)(base + 512 + lane * 4) = top;
+    }
+    if (g == 0) {
+      const int so = tiled_q36_scale_off(BITS, row, 0);
+      *(uint32_t*)(base + so) = *(const uint32_t*)(scales + row * (K / 64) + j * 2);
+      *(uint32_t*)(base + so + 64) = *(const uint32_t*)(biases + row * (K / 64) + j * 2);
     }
   }
 }
@@ -134,15 +174,55 @@ __global__ void dequant_q8_hilo_kernel(const uint8_t* src, T* dst, int N, int K)
   }
 }
 
+// the same for the bit planes of tile-major int3 / int6
+template <typename T, int BITS>
+__global__ void dequant_q36_hilo_kernel(const uint8_t* src, T* dst, int N, int K) {
+  const size_t pieces = (size_t)N * (K / 8);
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < pieces; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / (K / 32), j = blk % (K / 32);
+    const size_t row = i * 16 + r;
+    const int k = (int)j * 32 + g * 8;
+    const uint8_t* qb = src + tiled_block_q36(BITS, row, k, K);
+    const int so = tiled_q36_scale_off(BITS, row, k);
+    const float s = (float)*(const T*)(qb + so);
+    const float b = (float)*(const T*)(qb + so + 64);
+    T hi[8], lo[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float w = mul_add_unfused(s, (float)tiled_q36_code(BITS, qb, row, k + e), b);
+      hi[e] = (T)w;
+      lo[e] = (T)(w - (float)hi[e]);
+    }
+    const size_t kb2 = (size_t)(2 * K) / 32;
+    T* dh = dst + ((i * kb2 + j) * 64 + lane) * 8;
+    T* dl = dst + ((i * kb2 + (size_t)(K / 32) + j) * 64 + lane) * 8;
+    *(u32x4*)dh = *(const u32x4*)hi;
+    *(u32x4*)dl = *(const u32x4*)lo;
+  }
+}
+
 }  // namespace
 
 size_t dequant_hilo_bytes(int N, int K) { return (size_t)N * K * 2 * 2; }
 
 int launch_dequant_q4_hilo(const LinearW& src, void* dst, hipStream_t st) {
   const bool q4 = src.wk == WK_Q4_BF16 || src.wk == WK_Q4_F16, q8 = src.wk == WK_Q8_BF16 || src.wk == WK_Q8_F16;
-  if (src.layout != 1 || (!q4 && !q8) || src.group != 64 || src.K % (q4 ? 128 : 64) != 0 || src.N % 16 != 0)
-    return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major int4 / int8 (group 64) matrices only");
+  const bool q36 = wk_is_q36(src.wk) && wk_scale_dtype(src.wk) != MI_F32;
+  if (src.layout != 1 || (!q4 && !q8 && !q36) || src.group != 64 || src.K % (q8 ? 64 : 128) != 0 || src.N % 16 != 0)
+    return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major int3 / int4 / int6 / int8 (group 64) matrices only");
   const dim3 grid(4096), block(256);
+  if (q36) {
+#define DQ(T, BITS) hipLaunchKernelGGL((dequant_q36_hilo_kernel<T, BITS>), grid, block, 0, st, (const uint8_t*)src.w, (T*)dst, src.N, src.K)
+    if (src.wk == WK_Q3_BF16) DQ(bf16, 3);
+    else if (src.wk == WK_Q3_F16) DQ(f16, 3);
+    else if (src.wk == WK_Q6_BF16) DQ(bf16, 6);
+    else DQ(f16, 6);
+#undef DQ
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }
   if (src.wk == WK_Q4_BF16) hipLaunchKernelGGL(dequant_q4_hilo_kernel<bf16>, grid, block, 0, st, (const uint8_t*)src.w, (bf16*)dst, src.N, src.K);
   else if (src.wk == WK_Q4_F16) hipLaunchKernelGGL(dequant_q4_hilo_kernel<f16>, grid, block, 0, st, (const uint8_t*)src.w, (f16*)dst, src.N, src.K);
   else if (src.wk == WK_Q8_BF16) hipLaunchKernelGGL(dequant_q8_hilo_kernel<bf16>, grid, block, 0, st, (const uint8_t*)src.w, (bf16*)dst, src.N, src.K);
@@ -156,12 +236,15 @@ bool tiled_supported(int wk, int N, int K, int group) {
   if (wk == WK_BF16 || wk == WK_F16) return K % 32 == 0;
   if (wk == WK_Q4_BF16 || wk == WK_Q4_F16) return group == 64 && K % 128 == 0;
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return group == 64 && K % 64 == 0;
+  if (wk_is_q36(wk) && wk_scale_dtype(wk) != MI_F32) return group == 64 && K % 128 == 0;
   return false;
 }
 
 size_t tiled_bytes(int wk, int N, int K) {
   if (wk == WK_BF16 || wk == WK_F16) return (size_t)N * K * 2;
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return (size_t)(N / 16) * (K / 64) * 1088;
+  // (int3 / int6: the codes' bits + scales + biases and not a byte more -- gemm_q36.hip clamps its prefetch)
+  if (wk_is_q36(wk)) return (size_t)(N / 16) * (K / 128) * q36_block_bytes(wk_bits(wk));
   // (+ 64 KiB: gemm_q4.hip's weight stream is clamp-free -- its prefetch runs up to ~48 blocks past a slice's end, i.e. past
   // the last tile's end for the last workgroups; what it loads there is never multiplied)
   return (size_t)(N / 16) * (K / 128) * 1152 + ((size_t)64 << 10);
@@ -173,6 +256,12 @@ int launch_repack_tiled(const LinearW& src, void* dst, hipStream_t st) {
   const dim3 grid(2048), block(256);
   if (src.wk == WK_BF16 || src.wk == WK_F16)
     hipLaunchKernelGGL(repack_dense16_kernel, grid, block, 0, st, (const uint16_t*)src.w, (uint16_t*)dst, src.N, src.K);
+  else if (wk_is_q36(src.wk) && wk_bits(src.wk) == 3)
+    hipLaunchKernelGGL(repack_q36_kernel<3>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
+                       (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K);
+  else if (wk_is_q36(src.wk))
+    hipLaunchKernelGGL(repack_q36_kernel<6>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
+                       (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K);
   else if (src.wk == WK_Q8_BF16 || src.wk == WK_Q8_F16)
     hipLaunchKernelGGL(repack_q8_kernel, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
                        (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K);

@@ -63,6 +63,9 @@ def merge_adapter_into_weights(weights: Dict[str, "object"], config: dict, adapt
         sc, bi = weights.get(name + ".scales"), weights.get(name + ".biases")
         bits = int(quant.get("bits", 0)) if sc is not None else 0
         group = int(quant.get("group_size", 0)) if sc is not None else 0
+        if sc is not None and bits in (3, 6):
+            raise NotImplementedError(f"{name}: merging into a {bits}-bit base is not supported (mi_lora_merge re-quantises at 4 and "
+                                      "8 bits only); serve the adapter beside the base instead")
         if sc is not None and bits not in (4, 8):
             raise ValueError(f"{name}: a packed weight without a usable config.json quantization entry")
         n_rows = int(w.shape[0])

@@ -3,8 +3,11 @@ bits)`` step of ``scripts/build_tiny_model.py:150-151`` / ``utils.quantize_model
 producing the on-disk triple ``<p>.weight`` (uint32) / ``<p>.scales`` / ``<p>.biases``.
 
 Format (mlx 0.25.2 ``mx.quantize``): per group of ``group_size`` consecutive
-input features, ``w ~ scale * q + bias`` with ``q`` an unsigned ``bits``-bit code; 32/bits codes
-per uint32, code j at bits [bits*j, bits*(j+1)).
+input features, ``w ~ scale * q + bias`` with ``q`` an unsigned ``bits``-bit code; code j of a row
+occupies bits [bits*j, bits*(j+1)) of the row's little-endian byte stream, viewed as uint32 words.
+For 2, 4 and 8 bits that is 32/bits whole codes per word; for 3 and 6 bits every 3 bytes hold 8 or
+4 codes and a code may straddle a byte or word boundary (unpinned like the rest of the format:
+DESIGN §2).
 """
 from __future__ import annotations
 
@@ -18,8 +21,8 @@ def quantize(w: torch.Tensor, group_size: int = 64, bits: int = 4) -> Tuple[torc
     scales/biases come back in ``w.dtype``."""
     if w.ndim != 2 or w.shape[1] % group_size != 0:
         raise ValueError("quantize expects (N, K) with K divisible by group_size")
-    if bits not in (2, 4, 8):
-        raise ValueError("bits must be 2, 4 or 8")
+    if bits not in (2, 3, 4, 6, 8):
+        raise ValueError("bits must be 2, 3, 4, 6 or 8")
     dt = w.dtype
     n, k = w.shape
     g = w.to(torch.float32).reshape(n, k // group_size, group_size)
@@ -34,20 +37,40 @@ def quantize(w: torch.Tensor, group_size: int = 64, bits: int = 4) -> Tuple[torc
     scales = torch.where(q0 != 0, edge / q0, scales)
     biases = torch.where(q0 == 0, torch.zeros_like(edge), edge)
     q = torch.clamp(torch.round((g - biases) / scales), 0, n_bins).to(torch.int64)
-    per = 32 // bits
-    q = q.reshape(n, k // per, per)
-    shifts = (torch.arange(per, device=w.device, dtype=torch.int64) * bits)
-    packed = (q << shifts).sum(dim=-1)                       # < 2^32
-    packed = torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
-    return packed, scales.reshape(n, -1).to(dt), biases.reshape(n, -1).to(dt)
+    return pack_codes(q.reshape(n, k), bits), scales.reshape(n, -1).to(dt), biases.reshape(n, -1).to(dt)
+
+
+def pack_codes(q: torch.Tensor, bits: int) -> torch.Tensor:
+    """codes (N, K) integer in [0, 2^bits) -> the packed bit stream as int32 words (N, K*bits/32)."""
+    n, k = q.shape
+    if (k * bits) % 32 != 0:
+        raise ValueError("a packed row must be whole 32-bit words")
+    q = q.to(torch.int64)
+    if 32 % bits == 0:
+        per = 32 // bits
+        shifts = torch.arange(per, device=q.device, dtype=torch.int64) * bits
+        packed = (q.reshape(n, k // per, per) << shifts).sum(dim=-1)                       # < 2^32
+    else:                                                    # 3 / 6 bits: through the stream's single bits
+        bit = (q[..., None] >> torch.arange(bits, device=q.device, dtype=torch.int64)) & 1  # (N, K, bits), LSB first
+        shifts = torch.arange(32, device=q.device, dtype=torch.int64)
+        packed = (bit.reshape(n, k * bits // 32, 32) << shifts).sum(dim=-1)
+    return torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
+
+
+def unpack_codes(packed: torch.Tensor, bits: int) -> torch.Tensor:
+    """the inverse of pack_codes: int32 words (N, K*bits/32) -> codes (N, K) int64."""
+    p = packed.to(torch.int64) & 0xFFFFFFFF
+    n = packed.shape[0]
+    if 32 % bits == 0:
+        shifts = torch.arange(32 // bits, device=packed.device, dtype=torch.int64) * bits
+        return ((p[..., None] >> shifts) & ((1 << bits) - 1)).reshape(n, -1)
+    bit = ((p[..., None] >> torch.arange(32, device=packed.device, dtype=torch.int64)) & 1).reshape(n, -1, bits)
+    return (bit << torch.arange(bits, device=packed.device, dtype=torch.int64)).sum(dim=-1)
 
 
 def dequantize(packed: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, group_size: int = 64,
                bits: int = 4) -> torch.Tensor:
-    per = 32 // bits
-    p = packed.to(torch.int64) & 0xFFFFFFFF
-    shifts = (torch.arange(per, device=packed.device, dtype=torch.int64) * bits)
-    q = ((p[..., None] >> shifts) & ((1 << bits) - 1)).reshape(packed.shape[0], -1).to(torch.float32)
+    q = unpack_codes(packed, bits).to(torch.float32)
     n, k = q.shape
     q = q.reshape(n, k // group_size, group_size)
     w = q * scales.to(torch.float32)[..., None] + biases.to(torch.float32)[..., None]
