@@ -79,7 +79,8 @@ typedef struct mi_model_desc {
   int32_t tie_word_embeddings;
   int32_t act_dtype;         /* MI_F32 | MI_BF16 | MI_F16: dtype of the weights (dense) or scales (quantised) */
   int32_t quant_bits;        /* 0 = no quantised tensors; else 4 or 8 */
-  int32_t quant_group_size;  /* 64 (32 / 128 also accepted) */
+  int32_t quant_group_size;  /* 32, 64 or 128 at 4 / 8 bits, all on the matrix cores in the 16-bit mode (32 / 128: gemm_qg.hip; float32
+                              * activations: the generic kernel); 64 only at 3 / 6 bits and for Mixtral */
   int32_t max_positions;     /* RoPE table length = largest KV capacity a mi_kv may have */
   /* ABI 3 (llama.py:59-67,155-162,77-82); MI_ARCH_LLAMA */
   int32_t attention_bias;    /* q/k/v/o_proj carry a `.bias` tensor ([N], model dtype or float32) */

@@ -59,6 +59,15 @@ extern "C" {
  * mi_op_tiled_bytes is exactly N K bits / 8 + N (K / 64) 4: the resident copy stays packed and carries NO over-read padding.
  * Over-read rule of these kinds: a kernel never reads past mi_op_tiled_bytes -- gemm_q36.hip addresses blocks of the matrix
  * only and clamps its prefetch to the slice's last block; the caller provides a buffer of mi_op_tiled_bytes. */
+/* int4 / int8 kinds with 16-bit scales in quantisation groups of 32 or 128 (mi_op_linear.group): tile-major (N % 16 == 0,
+ * K % 128 == 0) block (row / 16, k / 128) at ((row / 16) (K / 128) + k / 128) x B bytes, NG = 128 / group, C = 1024 (int4) or
+ * 2048 (int8), B = C + 64 NG = 1280 / 1088 (int4, group 32 / 128) or 2304 / 2112 (int8); lane l = 16 g + (row % 16) owns the
+ * codes k % 128 = 32 T + 8 g + e:
+ *   [0, C)               int4: dword T of the lane's 16 bytes, e = 2 w at nibble w, e = 2 w + 1 at nibble w + 4;
+ *                        int8: bytes 8 (T % 2) + e of the lane's 16 in the half T / 2 (1 KiB each)
+ *   [C, C + 32 NG)       scales, row r -> NG x 16 bit in k order;   [C + 32 NG, C + 64 NG) biases, same shape
+ * mi_op_tiled_bytes is exactly N K bits / 8 + N (K / group) 4 and the over-read rule of the 3- / 6-bit kinds holds: gemm_qg.hip
+ * addresses blocks of the matrix only and clamps its prefetch.  Group 64 keeps the layouts above (int4: + 64 KiB over-read). */
 #define MI_WK_Q3_F32 9
 #define MI_WK_Q3_BF16 10
 #define MI_WK_Q3_F16 11
@@ -125,7 +134,8 @@ int mi_op_gemv_gu8(const mi_op_linear* w, const mi_op_gemv_args* a);
 /* launches the same call `iters` times back to back and returns the mean launch time (HIP events) */
 int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* the split-K weight-streaming GEMM the engine uses for decode steps of 9..128 rows (int4 / int8 weights: 1..128), on its own:
- * a->M in that range, a->pro = MI_PRO_NONE, tile-major 16-bit, int4 or int8 (group 64) weights.  ksplit 0 = the library's
+ * a->M in that range, a->pro = MI_PRO_NONE, tile-major 16-bit, int4 or int8 (group 64) weights; int4 / int8 in groups of 32 / 128 run gemm_qg.hip (1..128 rows, ksplit > 0
+ * forces its K slices, echoed in *ksplit_used, as for 3 / 6 bits).  ksplit 0 = the library's
  * cost model (returned in *ksplit_used); iters >= 1 also times that many back-to-back launches into *avg_ms.
  * int4 weights above 16 rows with ksplit <= 0 run the round-4 kernel (gemm_q4.hip: x prepared once per launch, K split
  * over the waves of a workgroup; a->pro may then be MI_PRO_NORM); ksplit < 0 forces its plan for tests and A/B runs:
@@ -151,14 +161,14 @@ int mi_op_gemv_f32_resident(const mi_op_linear* w, const mi_op_gemv_args* a, int
 /* gemm_prefill.hip on its own: the tile GEMM of the prefill call (generate_step's first model call, utils.py:243-262: every
  * nn.Linear over B x L rows at once).  a->M rows of 16-bit activations, tile-major dense 16-bit weights, a->pro =
  * MI_PRO_NONE; plain / residual / SwiGLU epilogues.  iters >= 1 also times that many back-to-back launches into *avg_ms.
- * Tile-major int4 / int8 (group 64) weights (nn.QuantizedLinear, llama.py:64-67) are taken too: their [hi | lo] 16-bit copy is
+ * Tile-major int4 / int8 (group 32, 64, 128) weights (nn.QuantizedLinear, llama.py:64-67) are taken too: their [hi | lo] 16-bit copy is
  * made in a scratch buffer inside the call, as the engine does.  Float32 activations are refused: mi_op_gemm_prefill_f32. */
 int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* the same tile GEMM on float32 activations, the PagedKVCache mode (base.py:111-112 promotes every activation behind layer 0
  * to float32; the linears are llama.py:64-67,93,143,160-165 again): a->x float32 rows, a->act = MI_F32, a->rnd = MI_RND_NONE,
  * float32 outputs and residual; a->pro may be MI_PRO_NORM with float32 norm weights (llama.py:187,189), applied inside the
  * split.  The call splits x exactly into x_terms bf16 terms (mi_op_split_rows) and runs the tile GEMM over that image, as the
- * engine's prefill does.  w is tile-major: dense bf16 (x_terms 2 or 3), int4-bf16 group 64 (x_terms 3; the [hi | lo] copy is
+ * engine's prefill does.  w is tile-major: dense bf16 (x_terms 2 or 3), int4-bf16 group 32 / 64 / 128 (x_terms 3; the [hi | lo] copy is
  * made inside), or dense f16 with K % 64 == 0 (x_terms 3; its exact [hi | lo] bf16 copy is made inside).  Anything the tile
  * GEMM does not take returns MI_ERR_UNSUPPORTED -- no other kernel runs.  iters >= 1 also times that many back-to-back
  * launches of the GEMM (without the split) into *avg_ms. */

@@ -162,6 +162,20 @@ int route_q36(const Lin& a) {
   return launch_gemm_q36(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
 }
 
+// 1c. int4 / int8 in quantisation groups of 32 / 128, up to 128 rows of 16-bit activations: the streaming kernel of those
+// groups (gemm_qg.hip), run as route 1b runs its kernel.  Longer calls fall through to the prefill GEMM ([hi | lo] copy per
+// call); float32 activations and matrices that are not tile-major (K % 128 != 0) to the generic kernel.
+int route_qg(const Lin& a) {
+  mi_engine* e = a.e;
+  if (!(e->opt_skinny_gemm && a.rows <= 128 && gemm_qg_supported(a.f.W, a.c, a.rows))) return NOT_TAKEN;
+  Prof pr(e, a.prof);
+  GemvCall c = a.c;
+  c.M = (int)a.rows;
+  if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, a.rows, a.KT(), c.rnd));
+  MI_TRY(ensure_skinny_ws(e, gemm_qg_ws_bytes(a.f.W, c, a.rows), gemm_qg_groups(a.f.W, c, a.rows)));
+  return launch_gemm_qg(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
+}
+
 // float32-KV decode step of <= 8 sequences: what routes 2 and 3 share
 bool f32_decode(const Lin& a) {
   return a.e->opt_skinny_gemm && a.e->cur_L == 1 && a.rows <= 8 && a.c.act == MI_F32 && a.c.rnd == RND_NONE && a.c.kx == 0;
@@ -339,6 +353,7 @@ int gemv_rows_on(const Lin& a) {
   int rc;
   if ((rc = route_two_slabs(a)) != NOT_TAKEN) return rc;
   if ((rc = route_q36(a)) != NOT_TAKEN) return rc;
+  if ((rc = route_qg(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_wide(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_whole(a)) != NOT_TAKEN) return rc;
   if ((rc = route_skinny(a)) != NOT_TAKEN) return rc;

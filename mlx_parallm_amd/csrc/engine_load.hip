@@ -162,7 +162,7 @@ int finalize_linear(mi_engine* e, FusedLinear& f, int K, const std::string& name
   // "repack weights": tile-major layout for the matrices the streaming kernels read (repack.hip)
   if (e->opt_tile_weights && tiled_supported(f.W.wk, f.W.N, f.W.K, f.W.group)) {
     void* dst = nullptr;
-    if (hipMalloc(&dst, tiled_bytes(f.W.wk, f.W.N, f.W.K)) != hipSuccess)
+    if (hipMalloc(&dst, tiled_bytes(f.W.wk, f.W.N, f.W.K, f.W.group)) != hipSuccess)
       return fail(MI_ERR_RUNTIME, name + ": out of device memory repacking weights");
     MI_TRY(launch_repack_tiled(f.W, dst, e->stream));
     MI_HIP(hipStreamSynchronize(e->stream));
@@ -302,7 +302,7 @@ int finalize_moe_quant(mi_engine* e, LayerW& l, const std::string& p) {
     src.w = l.moe_w[t]; src.scales = l.moe_s[t]; src.biases = l.moe_b[t];
     src.N = E * (t == 2 ? H : I); src.K = t == 2 ? I : H; src.group = 64; src.layout = 0;
     void* dst = nullptr;
-    if (hipMalloc(&dst, tiled_bytes(src.wk, src.N, src.K)) != hipSuccess)
+    if (hipMalloc(&dst, tiled_bytes(src.wk, src.N, src.K, src.group)) != hipSuccess)
       return fail(MI_ERR_RUNTIME, p + ".block_sparse_moe: out of device memory repacking the experts");
     int rc = launch_repack_tiled(src, dst, e->stream);
     if (rc == MI_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MI_ERR_RUNTIME, p + ".block_sparse_moe: repacking the experts failed");

@@ -873,14 +873,15 @@ bool gemm_prefill_supported(const LinearW& W, const GemvCall& c, size_t rows) {
   if (c.force_v1 || c.rnd != RND_NONE || W.layout != 1) return false;
   if (rows < 32) return false;
   const bool dense = (W.wk == WK_BF16 && c.act == MI_BF16) || (W.wk == WK_F16 && c.act == MI_F16);
-  const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.group == 64 &&
+  const bool qg = wk_is_qg(W.wk, W.group) && W.K % 128 == 0;     // groups of 32 / 128: blocks of their own, the same copy
+  const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && (W.group == 64 || qg) &&
                   W.K % 128 == 0;                       // through a [hi | lo] 16-bit copy (launch_dequant_q4_hilo)
-  const bool q8 = ((W.wk == WK_Q8_BF16 && c.act == MI_BF16) || (W.wk == WK_Q8_F16 && c.act == MI_F16)) && W.group == 64;
+  const bool q8 = ((W.wk == WK_Q8_BF16 && c.act == MI_BF16) || (W.wk == WK_Q8_F16 && c.act == MI_F16)) && (W.group == 64 || qg);
   // int3 / int6 bit planes: the same [hi | lo] copy (launch_dequant_q4_hilo reads them)
   const bool q36 = wk_is_q36(W.wk) && wk_scale_dtype(W.wk) == c.act && c.act != MI_F32 && W.group == 64 && W.K % 128 == 0;
   const bool q36_bf16 = (W.wk == WK_Q3_BF16 || W.wk == WK_Q6_BF16) && W.group == 64 && W.K % 128 == 0;
   // float32 activations on a bf16 model (PagedKVCache mode): x goes through launch_split3_rows first
-  const bool x32 = c.act == MI_F32 && (W.wk == WK_BF16 || (W.wk == WK_Q4_BF16 && W.group == 64 && W.K % 128 == 0) || q36_bf16) &&
+  const bool x32 = c.act == MI_F32 && (W.wk == WK_BF16 || (W.wk == WK_Q4_BF16 && (W.group == 64 || qg) && W.K % 128 == 0) || q36_bf16) &&
                    c.ldx % 4 == 0 && W.K % 4 == 0;
   if (!dense && !q4 && !q8 && !q36 && !x32) return false;
   if (W.K % BK != 0 || (!x32 && c.ldx % 8 != 0)) return false;

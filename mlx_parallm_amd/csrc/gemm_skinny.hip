@@ -54,18 +54,6 @@ constexpr int SK_NW = 8;      // waves (= tiles) per workgroup
 constexpr int SK_KC = 256;    // k per activation chunk
 constexpr int SQ_PARTS_MAX = 64;   // norm hand-over: tile groups of the producing linear (N <= 8192)
 
-// 8 int8 codes (two packed dwords) -> 8 16-bit floats: 0..255 are exact in bf16 and f16
-template <typename T>
-__device__ __forceinline__ u32x4 unpack_q8(uint32_t lo, uint32_t hi) {
-  T e[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    e[j] = (T)(float)((lo >> (8 * j)) & 255u);
-    e[4 + j] = (T)(float)((hi >> (8 * j)) & 255u);
-  }
-  return *(const u32x4*)e;
-}
-
 struct SkinnyParams {
   const void* x; int ldx; int M;
   const void* w; int N, K;

@@ -68,6 +68,18 @@ __device__ __forceinline__ u32x4 unpack_q4(uint32_t v) {
   return r;
 }
 
+// 8 int8 codes (two packed dwords) -> 8 16-bit floats: 0..255 are exact in bf16 and f16
+template <typename T>
+__device__ __forceinline__ u32x4 unpack_q8(uint32_t lo, uint32_t hi) {
+  T e[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    e[j] = (T)(float)((lo >> (8 * j)) & 255u);
+    e[4 + j] = (T)(float)((hi >> (8 * j)) & 255u);
+  }
+  return *(const u32x4*)e;
+}
+
 // ---- activation staging ---------------------------------------------------------------------
 // Dense: fragment for (k-block kb of 32, g) = x[m][32kb + 8g .. +8] at slot ((kb*4+g)*MB + m).
 // Int4:  128-wide block, quant group s (64 wide), step t, lane group g hold the 8 k's of packed

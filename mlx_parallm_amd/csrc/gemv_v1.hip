@@ -84,6 +84,15 @@ __device__ __forceinline__ void load8(const GemvParams& p, int row, int kb, floa
     const size_t gi = (size_t)row * ng + kb / p.group;
     float s, b;
     const char* blk = nullptr;
+    if (SDT != 0 && p.layout && p.group != 64) {   // tile-major groups of 32 / 128 (repack.hip): blocks of their own
+      const uint8_t* qb = (const uint8_t*)p.w + tiled_block_qg(BITS, p.group, row, kb, p.K);
+      const int so = tiled_qg_scale_off(BITS, p.group, row, kb), bo = so + tiled_qg_bias_step(p.group);
+      if constexpr (SDT == 1) { s = (float)*(const bf16*)(qb + so); b = (float)*(const bf16*)(qb + bo); }
+      else { s = (float)*(const f16*)(qb + so); b = (float)*(const f16*)(qb + bo); }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = mul_add_unfused((float)tiled_qg_code(BITS, qb, row, kb + j), s, b);
+      return;
+    }
     if (BITS == 4 && SDT != 0 && p.layout) {       // tile-major int4 (repack.hip): scales live in the block
       blk = (const char*)p.w + tiled_block_q4(row, kb, p.K);
       const int so = tiled_q4_scale_off(row, kb);

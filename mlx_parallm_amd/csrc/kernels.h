@@ -85,7 +85,7 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
 size_t split3_bytes(size_t rows, int K);
 int launch_split3_rows(const void* x, int ldx, const void* norm_w, float eps, void* out, int rows, int K, hipStream_t st,
                        int terms = 3);
-// int4 / int8 / int3 / int6 (tile-major) -> 16-bit tile-major [hi | lo], K' = 2K: the operand of the prefill GEMM for quantised weights
+// int4 / int8 (groups 32, 64, 128) / int3 / int6 (tile-major) -> 16-bit tile-major [hi | lo], K' = 2K: the operand of the prefill GEMM for quantised weights
 size_t dequant_hilo_bytes(int N, int K);
 int launch_dequant_q4_hilo(const LinearW& src, void* dst, hipStream_t st);
 // block_per_row: one workgroup per row, row in registers -- for the few rows of a decode step (default: one wave
@@ -134,7 +134,7 @@ int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t
 
 // tile-major weight layout (repack.hip)
 bool tiled_supported(int wk, int N, int K, int group);
-size_t tiled_bytes(int wk, int N, int K);
+size_t tiled_bytes(int wk, int N, int K, int group);
 int launch_repack_tiled(const LinearW& src_row_major, void* dst, hipStream_t st);
 // tile-major f16 (N x K) -> tile-major bf16 [hi | lo] (N x 2K), hi + lo == w exactly (repack.hip); dst: 2 x the source's bytes
 int launch_f16_to_hilo(const LinearW& tiled_f16, void* dst, hipStream_t st);
@@ -205,6 +205,39 @@ size_t gemm_q36_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int k
 int gemm_q36_groups(const LinearW& W, const GemvCall& c, size_t rows);
 int launch_gemm_q36(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
 
+// ---- int4 / int8 in groups of 32 and 128 (include/mi355_ops.h has the layout): block (row tile, k / 128) = codes, then
+// NG = 128 / group scales per row, then as many biases.  Lane l = 16 g + (row % 16) owns the codes k % 128 = 32 T + 8 g + e:
+// int4 -- dword T of the lane's 16 bytes, e = 2 w at nibble w and e = 2 w + 1 at nibble w + 4 (the order of unpack_q4);
+// int8 -- bytes 8 (T % 2) + e of the lane's 16 in the half T / 2 of the 2 KiB of codes.
+__host__ __device__ constexpr int qg_code_bytes(int bits) { return bits == 8 ? 2048 : 1024; }
+__host__ __device__ constexpr int qg_block_bytes(int bits, int group) { return qg_code_bytes(bits) + 16 * (128 / group) * 4; }
+__host__ __device__ inline size_t tiled_block_qg(int bits, int group, size_t row, int k, int K) {
+  return ((row >> 4) * (size_t)(K / 128) + (size_t)(k >> 7)) * qg_block_bytes(bits, group);
+}
+__host__ __device__ inline int tiled_qg_code_off(int bits, size_t row, int k) {     // int4: of the dword of codes k .. k + 8
+  const int T = (k >> 5) & 3, lane = ((k >> 3) & 3) * 16 + (int)(row & 15);
+  return bits == 8 ? (T >> 1) * 1024 + lane * 16 + (T & 1) * 8 + (k & 7) : lane * 16 + T * 4;
+}
+__host__ __device__ inline uint32_t tiled_qg_code(int bits, const uint8_t* blk, size_t row, int k) {
+  if (bits == 8) return blk[tiled_qg_code_off(8, row, k)];
+  const int e = k & 7;
+  return (*(const uint32_t*)(blk + tiled_qg_code_off(4, row, k)) >> (4 * ((e >> 1) + 4 * (e & 1)))) & 15u;
+}
+__host__ __device__ inline int tiled_qg_scale_off(int bits, int group, size_t row, int k) {    // + tiled_qg_bias_step: the bias
+  return qg_code_bytes(bits) + ((int)(row & 15) * (128 / group) + (k & 127) / group) * 2;
+}
+__host__ __device__ constexpr int tiled_qg_bias_step(int group) { return 16 * (128 / group) * 2; }
+inline bool wk_is_qg(int wk, int group) {      // the kinds these blocks hold: 16-bit scales, int4 / int8, group 32 / 128
+  return (wk == WK_Q4_BF16 || wk == WK_Q4_F16 || wk == WK_Q8_BF16 || wk == WK_Q8_F16) && (group == 32 || group == 128);
+}
+
+// int4 / int8 in groups of 32 / 128 (tile-major), 1..128 rows of 16-bit activations (gemm_qg.hip): the contract of gemm_q36
+bool gemm_qg_supported(const LinearW& W, const GemvCall& c, size_t rows);
+int gemm_qg_ksplit(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+size_t gemm_qg_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+int gemm_qg_groups(const LinearW& W, const GemvCall& c, size_t rows);
+int launch_gemm_qg(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
+
 // ---- lora_rows.hip (the LoRA launches themselves: lora_rows.h)
 // out[m][n] = T(T(g * T(sigmoid(g))) * u) with g = x[m][n], u = x[m][I + n]: the SwiGLU of a gate|up output stored by an
 // EPI_STORE launch (an adapted gate|up), rounding points of EPI_SWIGLU.  I % 8 == 0, ldx >= 2 I, ldo >= I, any M, one launch.
@@ -239,7 +272,7 @@ int launch_moe_combine(const void* y, const void* score, int k, const void* resi
                        int act, int rnd, hipStream_t st);
 
 // ---- moe_q.hip: launch_moe_linear over MLX-affine quantised experts (group 64, 4 / 8 bits).  w, w2: the stacked [E][N][K]
-// tensor repacked tile-major as ONE [E N][K] matrix (launch_repack_tiled; tiled_bytes(wk, E N, K) bytes), scales and biases in
+// tensor repacked tile-major as ONE [E N][K] matrix (launch_repack_tiled; tiled_bytes(wk, E N, K, 64) bytes), scales and biases in
 // `sdt` (MI_BF16 / MI_F16, = act unless act is MI_F32).  x is prepared once per launch into `ws` (moe_q_ws_bytes(), 256-byte
 // aligned): all x_rows rows; `pairs` = the length of the list array.  N % 16 == 0; K % 128 == 0 (int4) / K % 64 == 0 (int8).
 struct MoeLinearQCall {

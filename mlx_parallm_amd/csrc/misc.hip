@@ -76,7 +76,13 @@ __global__ __launch_bounds__(256) void embed_kernel(LinearW W, EmbedCall c) {
       const size_t gi = (size_t)tok * (W.K / W.group) + k / W.group;
       float s, b;
       uint32_t word;
-      if (BITS == 4 && SDT != 0 && W.layout) {     // tile-major int4 (repack.hip)
+      if (SDT != 0 && W.layout && W.group != 64) {     // tile-major groups of 32 / 128 (repack.hip)
+        const uint8_t* qb = (const uint8_t*)W.w + tiled_block_qg(BITS, W.group, tok, k, W.K);
+        const int so = tiled_qg_scale_off(BITS, W.group, tok, k), bo = so + tiled_qg_bias_step(W.group);
+        if constexpr (SDT == 1) { s = (float)*(const bf16*)(qb + so); b = (float)*(const bf16*)(qb + bo); }
+        else { s = (float)*(const f16*)(qb + so); b = (float)*(const f16*)(qb + bo); }
+        word = tiled_qg_code(BITS, qb, tok, k) << (BITS * (k % PER));
+      } else if (BITS == 4 && SDT != 0 && W.layout) {     // tile-major int4 (repack.hip)
         const char* blk = (const char*)W.w + tiled_block_q4(tok, k, W.K);
         const int so = tiled_q4_scale_off(tok, k);
         if constexpr (SDT == 1) { s = (float)*(const bf16*)(blk + so); b = (float)*(const bf16*)(blk + so + 64); }

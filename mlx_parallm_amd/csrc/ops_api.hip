@@ -211,6 +211,18 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
     if (ksplit_used) *ksplit_used = ks;
     return run_timed([&] { return launch_gemm_q36(W, c, (size_t)c.M, nullptr, ws, (unsigned*)ctr, ksplit); }, iters, avg_ms);
   }
+  if (wk_is_qg(W.wk, W.group)) {                 // int4 / int8 in groups of 32 / 128: gemm_qg.hip (ksplit > 0 forces its K slices)
+    if (ksplit < 0 || !gemm_qg_supported(W, c, (size_t)c.M) || c.pro != PRO_NONE)
+      return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: int4 / int8 in groups of 32 / 128 take 1..128 rows of 16-bit activations in the scales' dtype, tile-major, no prologue");
+    const int ks = gemm_qg_ksplit(W, c, (size_t)c.M, ksplit), groups = gemm_qg_groups(W, c, (size_t)c.M);
+    void* ws = nullptr; void* ctr = nullptr;
+    FreeGuard g_ws{ws}, g_ctr{ctr};
+    MI_HIP(hipMalloc(&ws, std::max<size_t>(1024, gemm_qg_ws_bytes(W, c, (size_t)c.M, ksplit))));
+    MI_HIP(hipMalloc(&ctr, (size_t)groups * sizeof(unsigned)));
+    MI_HIP(hipMemset(ctr, 0, (size_t)groups * sizeof(unsigned)));
+    if (ksplit_used) *ksplit_used = ks;
+    return run_timed([&] { return launch_gemm_qg(W, c, (size_t)c.M, nullptr, ws, (unsigned*)ctr, ksplit); }, iters, avg_ms);
+  }
   if (!gemm_skinny_supported(W, c, (size_t)c.M) && !gemm_q4_supported(W, c, (size_t)c.M))
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: call not supported by this kernel");
   const int groups = std::max(1, gemm_skinny_groups(W, c, (size_t)c.M));
@@ -236,7 +248,7 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   if (c.act == MI_F32)
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: 16-bit activations only (float32 activations: mi_op_gemm_prefill_f32)");
   if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || (wk_is_quant(W.wk) && !gemm_prefill_supported(W, c, (size_t)c.M)))
-    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int3 / int4 / int6 / int8 (group 64) weights, 16-bit activations, no prologue");
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int3 / int6 (group 64) or int4 / int8 (group 32, 64, 128) weights, 16-bit activations, no prologue");
   void* ws = nullptr; void* scratch = nullptr; size_t cap = 0;
   FreeGuard g_ws{ws}, g_scratch{scratch};
   if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, W.K)));
@@ -396,8 +408,9 @@ int mi_op_gemv_uses_mfma(const mi_op_linear* w, const mi_op_gemv_args* a) {
 }
 
 uint64_t mi_op_tiled_bytes(const mi_op_linear* w) {
-  if (!w || !tiled_supported(w->wk, w->N, w->K, w->group > 0 ? w->group : 64)) return 0;
-  return (uint64_t)tiled_bytes(w->wk, w->N, w->K);
+  const int group = w && w->group > 0 ? w->group : 64;
+  if (!w || !tiled_supported(w->wk, w->N, w->K, group)) return 0;
+  return (uint64_t)tiled_bytes(w->wk, w->N, w->K, group);
 }
 
 int mi_op_repack_tiled(const mi_op_linear* w, void* dst) {
@@ -674,7 +687,7 @@ int repack_stack(const QStack& s, int sdt, int bits, int E, int N, int K, void**
   LinearW src;
   src.wk = (bits == 8 ? WK_Q8_F32 : WK_Q4_F32) + (sdt == MI_BF16 ? 1 : 2);
   src.w = s.w; src.scales = s.scales; src.biases = s.biases; src.N = E * N; src.K = K; src.group = 64; src.layout = 0;
-  MI_HIP(hipMalloc(out, tiled_bytes(src.wk, src.N, src.K)));
+  MI_HIP(hipMalloc(out, tiled_bytes(src.wk, src.N, src.K, src.group)));
   MI_TRY(launch_repack_tiled(src, *out, nullptr));
   MI_HIP(hipStreamSynchronize(nullptr));
   return MI_OK;

@@ -20,6 +20,13 @@
 //                 lane l = g*16 + r owns the codes k%128 = 32T + 8g + e in the order an MFMA B operand takes them (step T,
 //                 dword w = e/2, half e%2), so that the decode kernel's unpack is shift + and-or on whole dwords and never
 //                 crosses one (include/mi355_ops.h has the byte map; gemm_q36.hip the reasons).
+//   int4 / int8 (g32, g128): block (i, j = k/128) of C + 16 NG 4 bytes, C = 1024 (int4) or 2048 (int8) bytes of codes and
+//                 NG = 128 / group -- 1280 / 1088 bytes at 4 bits, 2304 / 2112 at 8, exactly the codes + scales + biases:
+//                 [0,C)       codes: lane l = g*16 + r owns k%128 = 32T + 8g + e.  int4: dword T of its 16 bytes, e = 2w at
+//                             nibble w, e = 2w+1 at nibble w+4 (the order unpack_q4 produces: x needs no permutation);
+//                             int8: bytes 8 (T%2) + e of its 16 in the half T/2 of the 2 KiB.
+//                 [C, C + 32 NG)       scales: row r -> NG x 16-bit (the block's quantisation groups in k order)
+//                 [C + 32 NG, C + 64 NG) biases: same shape.   (kernels.h: tiled_*_qg; gemm_qg.hip reads them)
 #include "kernels.h"
 
 namespace mi {
@@ -108,6 +115,41 @@ __global__ void repack_q36_kernel(const uint32_t* codes, const uint16_t* scales,
       *(uint32_t*)(base + so) = *(const uint32_t*)(scales + row * (K / 64) + j * 2);
       *(uint32_t*)(base + so + 64) = *(const uint32_t*)(biases + row * (K / 64) + j * 2);
     }
+  }
+}
+
+// int4 / int8 in groups of 32 / 128: one thread per (block, lane); MLX packs code k of a row at bits [BITS k, BITS (k + 1))
+template <int BITS>
+__global__ void repack_qg_kernel(const uint32_t* codes, const uint16_t* scales, const uint16_t* biases, uint8_t* dst, int N, int K,
+                                 int group) {
+  const int nb = K / 128, ng = 128 / group;
+  const size_t blocks = (size_t)(N / 16) * nb;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < blocks * 64; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / nb, j = blk % nb;
+    const size_t row = i * 16 + r;
+    uint8_t* base = dst + blk * qg_block_bytes(BITS, group);
+    if (BITS == 4) {
+      uint32_t o[4];
+      for (int T = 0; T < 4; ++T) {
+        const uint32_t v = codes[row * (K / 8) + j * 16 + T * 4 + g];       // codes k = 128 j + 32 T + 8 g + e at nibble e
+        o[T] = 0u;
+        for (int e = 0; e < 8; ++e) o[T] |= ((v >> (4 * e)) & 15u) << (4 * ((e >> 1) + 4 * (e & 1)));
+      }
+      *(u32x4*)(base + lane * 16) = u32x4{o[0], o[1], o[2], o[3]};
+    } else {
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t* s0 = codes + row * (K / 4) + j * 32 + (2 * h) * 8 + g * 2;   // 8 codes of step T = two dwords
+        *(u32x4*)(base + h * 1024 + lane * 16) = u32x4{s0[0], s0[1], s0[8], s0[9]};
+      }
+    }
+    if (g == 0)
+      for (int q = 0; q < ng; ++q) {
+        const int so = tiled_qg_scale_off(BITS, group, row, q * group);
+        *(uint16_t*)(base + so) = scales[row * (K / group) + j * ng + q];
+        *(uint16_t*)(base + so + tiled_qg_bias_step(group)) = biases[row * (K / group) + j * ng + q];
+      }
   }
 }
 
@@ -203,6 +245,35 @@ __global__ void dequant_q36_hilo_kernel(const uint8_t* src, T* dst, int N, int K
   }
 }
 
+// the same for the blocks of int4 / int8 in groups of 32 / 128
+template <typename T, int BITS>
+__global__ void dequant_qg_hilo_kernel(const uint8_t* src, T* dst, int N, int K, int group) {
+  const size_t pieces = (size_t)N * (K / 8);
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < pieces; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / (K / 32), j = blk % (K / 32);
+    const size_t row = i * 16 + r;
+    const int k = (int)j * 32 + g * 8;
+    const uint8_t* qb = src + tiled_block_qg(BITS, group, row, k, K);
+    const int so = tiled_qg_scale_off(BITS, group, row, k);
+    const float s = (float)*(const T*)(qb + so);
+    const float b = (float)*(const T*)(qb + so + tiled_qg_bias_step(group));
+    T hi[8], lo[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float w = mul_add_unfused(s, (float)tiled_qg_code(BITS, qb, row, k + e), b);
+      hi[e] = (T)w;
+      lo[e] = (T)(w - (float)hi[e]);
+    }
+    const size_t kb2 = (size_t)(2 * K) / 32;
+    T* dh = dst + ((i * kb2 + j) * 64 + lane) * 8;
+    T* dl = dst + ((i * kb2 + (size_t)(K / 32) + j) * 64 + lane) * 8;
+    *(u32x4*)dh = *(const u32x4*)hi;
+    *(u32x4*)dl = *(const u32x4*)lo;
+  }
+}
+
 }  // namespace
 
 size_t dequant_hilo_bytes(int N, int K) { return (size_t)N * K * 2 * 2; }
@@ -210,9 +281,20 @@ size_t dequant_hilo_bytes(int N, int K) { return (size_t)N * K * 2 * 2; }
 int launch_dequant_q4_hilo(const LinearW& src, void* dst, hipStream_t st) {
   const bool q4 = src.wk == WK_Q4_BF16 || src.wk == WK_Q4_F16, q8 = src.wk == WK_Q8_BF16 || src.wk == WK_Q8_F16;
   const bool q36 = wk_is_q36(src.wk) && wk_scale_dtype(src.wk) != MI_F32;
-  if (src.layout != 1 || (!q4 && !q8 && !q36) || src.group != 64 || src.K % (q8 ? 64 : 128) != 0 || src.N % 16 != 0)
-    return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major int3 / int4 / int6 / int8 (group 64) matrices only");
+  const bool qg = wk_is_qg(src.wk, src.group);
+  if (src.layout != 1 || (!q4 && !q8 && !q36) || (src.group != 64 && !qg) || src.K % (q8 && !qg ? 64 : 128) != 0 || src.N % 16 != 0)
+    return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major int3 / int6 (group 64), int4 / int8 (group 32, 64, 128) matrices only");
   const dim3 grid(4096), block(256);
+  if (qg) {
+#define DQ(T, BITS) hipLaunchKernelGGL((dequant_qg_hilo_kernel<T, BITS>), grid, block, 0, st, (const uint8_t*)src.w, (T*)dst, src.N, src.K, src.group)
+    if (src.wk == WK_Q4_BF16) DQ(bf16, 4);
+    else if (src.wk == WK_Q4_F16) DQ(f16, 4);
+    else if (src.wk == WK_Q8_BF16) DQ(bf16, 8);
+    else DQ(f16, 8);
+#undef DQ
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }
   if (q36) {
 #define DQ(T, BITS) hipLaunchKernelGGL((dequant_q36_hilo_kernel<T, BITS>), grid, block, 0, st, (const uint8_t*)src.w, (T*)dst, src.N, src.K)
     if (src.wk == WK_Q3_BF16) DQ(bf16, 3);
@@ -234,14 +316,17 @@ int launch_dequant_q4_hilo(const LinearW& src, void* dst, hipStream_t st) {
 bool tiled_supported(int wk, int N, int K, int group) {
   if (N % 16 != 0) return false;
   if (wk == WK_BF16 || wk == WK_F16) return K % 32 == 0;
+  if (wk_is_qg(wk, group)) return K % 128 == 0;
   if (wk == WK_Q4_BF16 || wk == WK_Q4_F16) return group == 64 && K % 128 == 0;
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return group == 64 && K % 64 == 0;
   if (wk_is_q36(wk) && wk_scale_dtype(wk) != MI_F32) return group == 64 && K % 128 == 0;
   return false;
 }
 
-size_t tiled_bytes(int wk, int N, int K) {
+size_t tiled_bytes(int wk, int N, int K, int group) {
   if (wk == WK_BF16 || wk == WK_F16) return (size_t)N * K * 2;
+  // (groups of 32 / 128: packed, no padding -- gemm_qg.hip clamps its prefetch as gemm_q36.hip does)
+  if (wk_is_qg(wk, group)) return (size_t)(N / 16) * (K / 128) * qg_block_bytes(wk_bits(wk), group);
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return (size_t)(N / 16) * (K / 64) * 1088;
   // (int3 / int6: the codes' bits + scales + biases and not a byte more -- gemm_q36.hip clamps its prefetch)
   if (wk_is_q36(wk)) return (size_t)(N / 16) * (K / 128) * q36_block_bytes(wk_bits(wk));
@@ -256,6 +341,12 @@ int launch_repack_tiled(const LinearW& src, void* dst, hipStream_t st) {
   const dim3 grid(2048), block(256);
   if (src.wk == WK_BF16 || src.wk == WK_F16)
     hipLaunchKernelGGL(repack_dense16_kernel, grid, block, 0, st, (const uint16_t*)src.w, (uint16_t*)dst, src.N, src.K);
+  else if (wk_is_qg(src.wk, src.group) && wk_bits(src.wk) == 4)
+    hipLaunchKernelGGL(repack_qg_kernel<4>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
+                       (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K, src.group);
+  else if (wk_is_qg(src.wk, src.group))
+    hipLaunchKernelGGL(repack_qg_kernel<8>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
+                       (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K, src.group);
   else if (wk_is_q36(src.wk) && wk_bits(src.wk) == 3)
     hipLaunchKernelGGL(repack_q36_kernel<3>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
                        (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K);
