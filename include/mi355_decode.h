@@ -48,6 +48,7 @@ extern "C" {
 #define MI_BF16 1
 #define MI_F16 2
 #define MI_U32 3 /* MLX-packed quantised weights: 32/bits codes per word, little-endian */
+#define MI_U8 4  /* the E8M0 scale bytes of an mxfp4 linear (quant_mode 1): byte s means 2^(s - 127) */
 
 #define MI_ARCH_LLAMA 0 /* mlx_parallm/models/llama.py (also model_type "mistral": utils.py:33-36) */
 #define MI_ARCH_QWEN3 1 /* mlx_parallm/models/qwen3.py: + per-head q_norm/k_norm (qwen3.py:65-70) */
@@ -93,6 +94,18 @@ typedef struct mi_model_desc {
    * refuses a binding built against the shorter layout. */
   int32_t num_local_experts;   /* E in 1..16 */
   int32_t num_experts_per_tok; /* k in {1, 2}, k <= E */
+  /* config.json["quantization"]["mode"]; grown like the two fields above, struct_size guards it.
+   * 0 = MLX affine (scale * q + bias per group; `.weight` MI_U32, `.scales` and `.biases` in the model dtype).
+   * 1 = mxfp4, the OCP Microscaling FP4 format: `.weight` MI_U32 [N][K / 8], code j of a row at bits [4 j, 4 j + 4) of its
+   *     little-endian stream, bit 3 the sign and bits 0..2 one of {0, 0.5, 1, 1.5, 2, 3, 4, 6} (E2M1); `.scales` MI_U8
+   *     [N][K / 32], byte s = 2^(s - 127) (E8M0; byte 0 = 2^-127, byte 255 not special); NO `.biases` (giving one is
+   *     MI_ERR_INVALID).  Needs quant_bits 4, quant_group_size 32, act_dtype MI_BF16, hidden / intermediate / attention widths
+   *     that are multiples of 32 and an arch other than MI_ARCH_MIXTRAL: anything else is MI_ERR_UNSUPPORTED at mi_engine_create,
+   *     naming the field; so is rope_traditional with a hidden_size that is no multiple of 64 (mi_engine_finalize regroups
+   *     the q / k rows of scale bytes, hidden_size / 32 bytes each, in 16-bit units).  The embedding may be mxfp4 as well.  1..128 rows of the 16-bit mode run gemm_mx4.hip (K % 128 == 0),
+   *     longer calls the prefill GEMM over an exact bf16 copy, float32 activations and other K the generic kernel.
+   *     LoRA rides beside such a base; DoRA and mi_lora_merge refuse it like every quantised base they do not read. */
+  int32_t quant_mode;
 } mi_model_desc;
 
 /* arguments of the `sample` closure (utils.py:345-364) + top_p_sampling (sample_utils.py:3-38) */

@@ -74,6 +74,21 @@ extern "C" {
 #define MI_WK_Q6_F32 12
 #define MI_WK_Q6_BF16 13
 #define MI_WK_Q6_F16 14
+/* mxfp4 (OCP Microscaling FP4, mi_model_desc.quant_mode 1): group = 32, biases = NULL.  Row-major (layout 0) `w` is uint32
+ * [N][K / 8] with code j of a row at bits [4 j, 4 j + 4) (bit 3 the sign, bits 0..2 one of {0, 0.5, 1, 1.5, 2, 3, 4, 6}) and
+ * `scales` is uint8 [N][K / 32], byte s = 2^(s - 127).  The scales carry no dtype: _BF16 names a bf16 model (bf16 activations,
+ * or float32 ones as for the other _BF16 kinds), _F32 float32 activations only.  Tile-major (N % 16 == 0, K % 128 == 0) block
+ * (row / 16, k / 128) at ((row / 16) (K / 128) + k / 128) x 1088 bytes; lane l = 16 g + (row % 16) owns k % 128 = 32 T + 8 g + e:
+ *   [0, 1024)     codes: dword T of the lane's 16 bytes, code e at nibble e (NATURAL order, not the affine int4 interleave:
+ *                 v_cvt_scalef32_pk_bf16_fp4 with byte_sel 0..3 turns the dword into the eight values of an MFMA B operand)
+ *   [1024, 1088)  one dword per row r at 4 r: its four scale bytes in k order (byte T = the group of MFMA step T)
+ * mi_op_tiled_bytes is exactly N K / 2 + N K / 32 and the over-read rule of the 3- / 6-bit kinds holds: gemm_mx4.hip addresses
+ * blocks of the matrix only and clamps its prefetch.  Scale byte 0 (2^-127, a float32 subnormal) is exact in mi_op_gemv's
+ * generic kernel, mi_op_embed and the prefill copy (which rounds to bf16); gemm_mx4.hip hands the conversion s << 23, an
+ * exponent field of 0: the weights of such a group (all below 2^-124) are bf16 subnormals or zero there, whichever the
+ * instruction and the MFMA make of them -- NOT pinned, and no test relies on it. */
+#define MI_WK_MX4_BF16 15
+#define MI_WK_MX4_F32 16
 
 /* run-time logical rounding on top of the storage dtype */
 #define MI_RND_NONE 0

@@ -14,7 +14,7 @@ CSRC = Path(__file__).resolve().parent / "csrc"
 LIB_PATH = Path(os.environ.get("MLX_PARALLM_AMD_LIB") or (CSRC / "libmi355_decode.so"))   # (env: A/B another build)
 
 # dtype / enum constants (mirror of the headers)
-MI_F32, MI_BF16, MI_F16, MI_U32 = 0, 1, 2, 3
+MI_F32, MI_BF16, MI_F16, MI_U32, MI_U8 = 0, 1, 2, 3, 4
 MI_KV_MODEL = -1
 MI_ARCH_LLAMA, MI_ARCH_QWEN3, MI_ARCH_PHI3, MI_ARCH_MIXTRAL = 0, 1, 2, 3
 MI_MAX_TOP_LOGPROBS = 20
@@ -22,7 +22,8 @@ MI_MAX_ROW_LOGIT_BIAS = 1024
 MI_MAX_ADAPTERS = 16
 MI_ABI_VERSION = 4
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8,
-      "q3_f32": 9, "q3_bf16": 10, "q3_f16": 11, "q6_f32": 12, "q6_bf16": 13, "q6_f16": 14}
+      "q3_f32": 9, "q3_bf16": 10, "q3_f16": 11, "q6_f32": 12, "q6_bf16": 13, "q6_f16": 14,
+      "mx4_bf16": 15, "mx4_f32": 16}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
 PRO_NONE, PRO_NORM = 0, 1
 EPI_STORE, EPI_STORE_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3
@@ -40,7 +41,7 @@ class ModelDesc(C.Structure):
         ("rope_scale", C.c_float), ("tie_word_embeddings", C.c_int32), ("act_dtype", C.c_int32),
         ("quant_bits", C.c_int32), ("quant_group_size", C.c_int32), ("max_positions", C.c_int32),
         ("attention_bias", C.c_int32), ("mlp_bias", C.c_int32), ("rope_traditional", C.c_int32),
-        ("num_local_experts", C.c_int32), ("num_experts_per_tok", C.c_int32),
+        ("num_local_experts", C.c_int32), ("num_experts_per_tok", C.c_int32), ("quant_mode", C.c_int32),
     ]
 
 

@@ -51,6 +51,7 @@ inline size_t dtype_size(int dt) {
     case MI_BF16: return 2;
     case MI_F16: return 2;
     case MI_U32: return 4;
+    case MI_U8: return 1;
   }
   return 0;
 }
@@ -195,14 +196,31 @@ enum : int {
   WK_Q8_F32 = 6, WK_Q8_BF16 = 7, WK_Q8_F16 = 8,
   WK_Q3_F32 = 9, WK_Q3_BF16 = 10, WK_Q3_F16 = 11,      // 3 / 6 bits: codes are a bit stream, not dword-aligned (quant.py)
   WK_Q6_F32 = 12, WK_Q6_BF16 = 13, WK_Q6_F16 = 14,
+  // mxfp4 (OCP Microscaling: E2M1 codes, one E8M0 scale byte per 32, no bias).  The scales carry no dtype, so the suffix names
+  // the MODEL dtype: _BF16 runs with bf16 activations and, like the other _BF16 kinds, with float32 ones (PagedKVCache mode
+  // of a bf16 model); _F32 with float32 activations only
+  WK_MX4_BF16 = 15, WK_MX4_F32 = 16,
 };
 inline bool wk_is_quant(int wk) { return wk >= WK_Q4_F32; }
+__host__ __device__ constexpr bool wk_is_mx4(int wk) { return wk == WK_MX4_BF16 || wk == WK_MX4_F32; }
 __host__ __device__ constexpr int wk_bits(int wk) {
-  return wk >= WK_Q6_F32 ? 6 : wk >= WK_Q3_F32 ? 3 : wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0);
+  return wk >= WK_MX4_BF16 ? 4 : wk >= WK_Q6_F32 ? 6 : wk >= WK_Q3_F32 ? 3 : wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0);
 }
 inline bool wk_is_q36(int wk) { return wk >= WK_Q3_F32 && wk <= WK_Q6_F16; }
 // base kind of a bit width (+ 0 / 1 / 2 for float32 / bf16 / f16 scales); -1: a width the kernels do not read
 inline int wk_base_of_bits(int bits) { return bits == 4 ? WK_Q4_F32 : bits == 8 ? WK_Q8_F32 : bits == 3 ? WK_Q3_F32 : bits == 6 ? WK_Q6_F32 : -1; }
-inline int wk_scale_dtype(int wk) { return wk_is_quant(wk) ? (wk - 3) % 3 : wk; }
+inline int wk_scale_dtype(int wk) { return wk_is_mx4(wk) ? (wk == WK_MX4_BF16 ? MI_BF16 : MI_F32) : wk_is_quant(wk) ? (wk - 3) % 3 : wk; }
+
+// mxfp4 in plain arithmetic (the generic kernels, the embedding gather, the prefill copy; gemm_mx4.hip converts in hardware).
+// A code: bit 3 the sign, bits 0..2 select {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- E2M1, whose two subnormals are 0 and 0.5.
+// A scale byte s is 2^(s - 127): s << 23 as float32 bits for 1..254; byte 0 is the float32 subnormal 2^-127; byte 255
+// (E8M0's NaN) gets no special handling and becomes +inf.  code x scale is exact in float32 and, above 2^-126, in bf16.
+__host__ __device__ inline float mx4_code_value(uint32_t c) {
+  const uint32_t m = c & 7u;
+  const uint32_t mag = m < 2u ? (m ? 0x3f000000u : 0u) : (((126u + (m >> 1)) << 23) | ((m & 1u) << 22));
+  return __builtin_bit_cast(float, mag | ((c & 8u) << 28));
+}
+__host__ __device__ inline float mx4_scale_value(uint32_t s) { return __builtin_bit_cast(float, s ? s << 23 : 0x00400000u); }
+__host__ __device__ inline float mx4_weight(uint32_t c, uint32_t s) { return mx4_code_value(c) * mx4_scale_value(s); }
 
 }  // namespace mi

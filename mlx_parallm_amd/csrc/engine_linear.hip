@@ -176,6 +176,20 @@ int route_qg(const Lin& a) {
   return launch_gemm_qg(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
 }
 
+// 1d. mxfp4 weights, up to 128 rows of bf16 activations: the FP4 streaming kernel (gemm_mx4.hip), run as routes 1b and 1c run
+// theirs.  Longer calls fall through to the prefill GEMM (one exact bf16 copy per call); float32 activations and matrices that
+// are not tile-major (K % 128 != 0) to the generic kernel.
+int route_mx4(const Lin& a) {
+  mi_engine* e = a.e;
+  if (!(e->opt_skinny_gemm && a.rows <= 128 && gemm_mx4_supported(a.f.W, a.c, a.rows))) return NOT_TAKEN;
+  Prof pr(e, a.prof);
+  GemvCall c = a.c;
+  c.M = (int)a.rows;
+  if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, a.rows, a.KT(), c.rnd));
+  MI_TRY(ensure_skinny_ws(e, gemm_mx4_ws_bytes(a.f.W, c, a.rows), gemm_mx4_groups(a.f.W, c, a.rows)));
+  return launch_gemm_mx4(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
+}
+
 // float32-KV decode step of <= 8 sequences: what routes 2 and 3 share
 bool f32_decode(const Lin& a) {
   return a.e->opt_skinny_gemm && a.e->cur_L == 1 && a.rows <= 8 && a.c.act == MI_F32 && a.c.rnd == RND_NONE && a.c.kx == 0;
@@ -354,6 +368,7 @@ int gemv_rows_on(const Lin& a) {
   if ((rc = route_two_slabs(a)) != NOT_TAKEN) return rc;
   if ((rc = route_q36(a)) != NOT_TAKEN) return rc;
   if ((rc = route_qg(a)) != NOT_TAKEN) return rc;
+  if ((rc = route_mx4(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_wide(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_whole(a)) != NOT_TAKEN) return rc;
   if ((rc = route_skinny(a)) != NOT_TAKEN) return rc;

@@ -238,6 +238,34 @@ size_t gemm_qg_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int ks
 int gemm_qg_groups(const LinearW& W, const GemvCall& c, size_t rows);
 int launch_gemm_qg(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
 
+// ---- mxfp4 (include/mi355_ops.h has the layout): block (row tile, k / 128) = 1024 bytes of codes in natural nibble order,
+// then one dword of four scale bytes per row.  mx4_word / mx4_scale_byte read either layout (the generic kernels).
+constexpr int MX4_BLOCK = 1088;
+__host__ __device__ inline size_t tiled_block_mx4(size_t row, int k, int K) {
+  return ((row >> 4) * (size_t)(K / 128) + (size_t)(k >> 7)) * MX4_BLOCK;
+}
+__host__ __device__ inline int tiled_mx4_code_off(size_t row, int k) {      // of the dword of codes k .. k + 8 (k % 8 == 0)
+  return (((k >> 3) & 3) * 16 + (int)(row & 15)) * 16 + ((k >> 5) & 3) * 4;
+}
+__host__ __device__ inline int tiled_mx4_scale_off(size_t row, int k) { return 1024 + (int)(row & 15) * 4 + ((k >> 5) & 3); }
+__host__ __device__ inline uint32_t mx4_word(const void* w, int layout, size_t row, int k, int K) {   // codes k .. k + 8, k % 8 == 0
+  if (layout) return *(const uint32_t*)((const uint8_t*)w + tiled_block_mx4(row, k, K) + tiled_mx4_code_off(row, k));
+  return ((const uint32_t*)w)[row * (size_t)(K / 8) + (k >> 3)];
+}
+__host__ __device__ inline uint32_t mx4_scale_byte(const void* w, const void* scales, int layout, size_t row, int k, int K) {
+  if (layout) return ((const uint8_t*)w)[tiled_block_mx4(row, k, K) + tiled_mx4_scale_off(row, k)];
+  return ((const uint8_t*)scales)[row * (size_t)(K / 32) + (k >> 5)];
+}
+
+// mxfp4 weights (tile-major), 1..128 rows of bf16 activations (gemm_mx4.hip): the contract of gemm_q36
+bool gemm_mx4_supported(const LinearW& W, const GemvCall& c, size_t rows);
+int gemm_mx4_ksplit(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+size_t gemm_mx4_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+int gemm_mx4_groups(const LinearW& W, const GemvCall& c, size_t rows);
+int launch_gemm_mx4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
+// tile-major mxfp4 -> tile-major dense bf16 (N x K), exact: the prefill GEMM's operand (repack.hip); dst: N K 2 bytes
+int launch_dequant_mx4(const LinearW& src, void* dst, hipStream_t st);
+
 // ---- lora_rows.hip (the LoRA launches themselves: lora_rows.h)
 // out[m][n] = T(T(g * T(sigmoid(g))) * u) with g = x[m][n], u = x[m][I + n]: the SwiGLU of a gate|up output stored by an
 // EPI_STORE launch (an adapted gate|up), rounding points of EPI_SWIGLU.  I % 8 == 0, ldx >= 2 I, ldo >= I, any M, one launch.

@@ -29,13 +29,13 @@ def _tensor_info(t) -> Tuple[int, Tuple[int, ...], int, int, object]:
         if not t.is_contiguous():
             t = t.contiguous()
         dt = {torch.float32: L.MI_F32, torch.bfloat16: L.MI_BF16, torch.float16: L.MI_F16,
-              torch.uint32: L.MI_U32, torch.int32: L.MI_U32}.get(t.dtype)
+              torch.uint32: L.MI_U32, torch.int32: L.MI_U32, torch.uint8: L.MI_U8}.get(t.dtype)
         if dt is None:
             raise ValueError(f"unsupported tensor dtype {t.dtype}")
         return t.data_ptr(), tuple(t.shape), dt, int(t.is_cuda), t
     a = np.ascontiguousarray(t)
     dt = {np.dtype(np.float32): L.MI_F32, np.dtype(np.float16): L.MI_F16,
-          np.dtype(np.uint32): L.MI_U32, np.dtype(np.int32): L.MI_U32}.get(a.dtype)
+          np.dtype(np.uint32): L.MI_U32, np.dtype(np.int32): L.MI_U32, np.dtype(np.uint8): L.MI_U8}.get(a.dtype)
     if dt is None:
         raise ValueError(f"unsupported array dtype {a.dtype}")
     return a.ctypes.data, tuple(a.shape), dt, 0, a
@@ -338,6 +338,10 @@ class Engine:
             d.num_experts_per_tok = int(config.get("num_experts_per_tok", 2))
         d.quant_bits = int(q["bits"]) if q else 0
         d.quant_group_size = int(q["group_size"]) if q else 0
+        mode = q.get("mode", "affine") if q else "affine"                           # utils.py:679-690 hands the dict to nn.quantize
+        if mode not in ("affine", "mxfp4"):
+            raise NotImplementedError(f"quantization mode {mode!r} is not supported (affine and mxfp4 are)")
+        d.quant_mode = int(mode == "mxfp4")
         d.max_positions = int(max_positions or min(int(config.get("max_position_embeddings", 4096)), 32768))
         d.attention_bias = int(bool(config.get("attention_bias", False)))            # llama.py:59-67
         d.mlp_bias = int(bool(config.get("mlp_bias", False)))                        # llama.py:155-162

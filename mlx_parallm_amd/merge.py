@@ -46,6 +46,9 @@ def merge_adapter_into_weights(weights: Dict[str, "object"], config: dict, adapt
         raise ValueError(f"Model type {model_type} not supported.")
     entries = list(_read_adapter(int(config["num_hidden_layers"]), adapter_path))    # (a bad directory raises first)
     quant = config.get("quantization") or {}
+    if quant.get("mode", "affine") != "affine":
+        raise NotImplementedError(f"merging into a {quant['mode']} base is not supported (mi_lora_merge re-quantises MLX-affine "
+                                  "weights only); serve the adapter beside the base instead")
     for layer, key, *_ in entries:                                                    # (names are refused before any is merged)
         name = f"model.layers.{layer}.{key}"
         if key.startswith("block_sparse_moe."):

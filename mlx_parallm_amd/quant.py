@@ -68,6 +68,43 @@ def unpack_codes(packed: torch.Tensor, bits: int) -> torch.Tensor:
     return (bit << torch.arange(bits, device=packed.device, dtype=torch.int64)).sum(dim=-1)
 
 
+# ---- mode "mxfp4": the OCP Microscaling FP4 format (MX v1.0) in MLX's packing -- E2M1 codes, code j of a row at bits
+# [4j, 4j+4) like affine int4, one E8M0 scale byte (2^(s-127)) per 32 weights, no bias.  Restated from the published
+# definitions, not pinned against MLX.
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)     # bits 0..2 of a code; bit 3 is the sign
+
+
+def quantize_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w (N, K) float, K % 32 == 0 -> (packed int32 (N, K/8), scales uint8 (N, K/32)).  Scale = 2^(floor(log2 max|w|) - 2)
+    per group (E2M1's largest exponent is 2), clamped to E8M0's bytes 0..254; codes round to nearest, ties to the even
+    mantissa, onto the E2M1 grid and saturate at +-6."""
+    if w.ndim != 2 or w.shape[1] % 32 != 0:
+        raise ValueError("quantize_mxfp4 expects (N, K) with K divisible by 32")
+    n, k = w.shape
+    g = w.to(torch.float64).reshape(n, k // 32, 32)
+    amax = g.abs().amax(dim=-1, keepdim=True)
+    e = torch.where(amax > 0, torch.floor(torch.log2(torch.where(amax > 0, amax, torch.ones_like(amax)))) - 2, torch.full_like(amax, -127.0))
+    e = e.clamp(-127, 127)
+    v = (g / torch.exp2(e)).abs().clamp(max=6.0)
+    grid = torch.tensor(MXFP4_VALUES, dtype=torch.float64, device=w.device)
+    d = (v[..., None] - grid).abs()                           # (N, K/32, 32, 8); a tie sits between two neighbours:
+    lo = d.argmin(dim=-1)                                     # argmin takes the lower one, the even code wins it
+    tie = (lo < 7) & (d.gather(-1, lo[..., None]).squeeze(-1) == d.gather(-1, (lo + 1).clamp(max=7)[..., None]).squeeze(-1))
+    mag = torch.where(tie & (lo % 2 == 1), lo + 1, lo)
+    q = mag | ((g < 0) & (mag > 0)).to(torch.int64) << 3      # (no negative zero is written)
+    return pack_codes(q.reshape(n, k), 4), (e + 127).reshape(n, -1).to(torch.uint8)
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """-> (N, K) float32, code value x 2^(s - 127): exact in float32 and in bfloat16 (subnormals at scale byte 0)."""
+    q = unpack_codes(packed, 4)
+    n, k = q.shape
+    grid = torch.tensor(MXFP4_VALUES, dtype=torch.float64, device=packed.device)
+    v = grid[q & 7] * torch.where((q & 8) != 0, -1.0, 1.0)
+    s = torch.exp2(scales.to(torch.float64) - 127.0)
+    return (v.reshape(n, k // 32, 32) * s[..., None]).reshape(n, k).to(torch.float32)
+
+
 def dequantize(packed: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, group_size: int = 64,
                bits: int = 4) -> torch.Tensor:
     q = unpack_codes(packed, bits).to(torch.float32)

@@ -365,7 +365,7 @@ def _checkpoint_dtype(weights: Dict[str, Any]) -> str:
     import torch
 
     for k, t in weights.items():
-        if k.endswith(".scales"):
+        if k.endswith(".scales") and t.dtype != torch.uint8:      # (mxfp4 scale bytes say nothing about the model dtype)
             return {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}[t.dtype]
     for k, t in weights.items():
         if k.endswith(".bias") and t.ndim == 1:         # a linear bias keeps its own dtype through convert(): not the model's
