@@ -179,6 +179,14 @@ int mi_op_gemv_f32_resident(const mi_op_linear* w, const mi_op_gemv_args* a, int
  * Tile-major int4 / int8 (group 32, 64, 128) weights (nn.QuantizedLinear, llama.py:64-67) are taken too: their [hi | lo] 16-bit copy is
  * made in a scratch buffer inside the call, as the engine does.  Float32 activations are refused: mi_op_gemm_prefill_f32. */
 int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
+/* gemm_qtile.hip on its own: the prefill tile GEMM that reads PACKED quantised weights (nn.QuantizedLinear, llama.py:64-67) --
+ * tile-major int4 / int8 in groups of 64, a->M rows (any count) of 16-bit activations in the scales' dtype, a->pro =
+ * MI_PRO_NONE; store / float32 store / residual / SwiGLU epilogues, a linear bias as T(T(acc) + b).  No dequantised copy is
+ * made; per output element acc = sum over groups of (s_g sum q x + b_g sum x) in float32, deterministic, each row on its own.
+ * Anything else (float32 activations, row-major weights, other groups or bit widths, a prologue) returns MI_ERR_UNSUPPORTED
+ * with nothing launched and no output touched; mi_op_gemm_prefill keeps running the copy route.  iters >= 1 also times that
+ * many back-to-back launches (sums of x + GEMM) into *avg_ms. */
+int mi_op_gemm_prefill_q(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* the same tile GEMM on float32 activations, the PagedKVCache mode (base.py:111-112 promotes every activation behind layer 0
  * to float32; the linears are llama.py:64-67,93,143,160-165 again): a->x float32 rows, a->act = MI_F32, a->rnd = MI_RND_NONE,
  * float32 outputs and residual; a->pro may be MI_PRO_NORM with float32 norm weights (llama.py:187,189), applied inside the

@@ -653,7 +653,7 @@ void mi_engine_destroy(mi_engine* e) {
   free_linear(e->embed); free_linear(e->lm_head);
   hipFree(e->final_norm); hipFree(e->cos_tab); hipFree(e->sin_tab);
   hipFree(e->h); hipFree(e->qkv); hipFree(e->q); hipFree(e->attn); hipFree(e->act); hipFree(e->logits); hipFree(e->gu); hipFree(e->d_forced); hipFree(e->d_gather);
-  hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch);
+  hipFree(e->d_rowpar); hipFree(e->d_rowext); hipFree(e->deq_scratch); hipFree(e->qt_ws);
   hipFree(e->d_row_adapter); hipFree(e->lora_rt); hipFree(e->ys); hipFree(e->moe_ws);
   hipFree(e->sk_ws); hipFree(e->sk_ctr); hipFree(e->d_sq); hipFree(e->cc_pub);
   hipFree(e->d_tokens); hipFree(e->d_next); hipFree(e->d_rowstats);
@@ -854,6 +854,7 @@ int mi_engine_set_option(mi_engine* e, const char* key, int64_t value) {
   if (k == "defer_norm") { e->opt_defer_norm = value != 0; return MI_OK; }
   if (k == "prefill_x_terms") { if (value != 2 && value != 3) return fail(MI_ERR_INVALID, "prefill_x_terms: 2 or 3"); e->opt_prefill_x_terms = (int)value; return MI_OK; }
   if (k == "short_prefill_skinny") { e->opt_short_prefill_skinny = value != 0; return MI_OK; }
+  if (k == "quant_prefill_tile") { if (value != 0 && value != 1) return fail(MI_ERR_INVALID, "quant_prefill_tile: 0 or 1"); e->opt_quant_prefill_tile = (int)value; return MI_OK; }
   if (k == "decode_attention_mfma") { e->opt_attn_mfma = value != 0; return MI_OK; }
   if (k == "shared_prefix_attention") {
     if (value < 0) return fail(MI_ERR_INVALID, "shared_prefix_attention: 0 (off) or the least number of tokens a set shares");

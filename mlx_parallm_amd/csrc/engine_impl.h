@@ -145,6 +145,7 @@ struct mi_engine {
   int32_t* d_gather = nullptr;                            // token positions whose hidden state feeds the head (mixed steps)
   float* d_rowpar = nullptr; size_t d_rowpar_cap = 0;     // per-row temperature | top_p of the current step
   char* d_rowext = nullptr; size_t d_rowext_cap = 0;      // per-row seed | position (8 bytes each) | top_k | min_p
+  void* qt_ws = nullptr; size_t qt_cap = 0;               // gemm_qtile.hip: group sums of x + K-split partial tiles
   void* deq_scratch = nullptr; size_t deq_cap = 0;        // [hi | lo] 16-bit copy of one int4 matrix (prefill GEMM)
   void* sk_ws = nullptr; size_t sk_ws_cap = 0;            // split-K partial tiles of gemm_skinny.hip
   unsigned* sk_ctr = nullptr; size_t sk_ctr_cap = 0;      // its per-tile-group arrival counters (zero between launches)
@@ -169,6 +170,7 @@ struct mi_engine {
   int opt_norm_handover = 1;    // round 2 (partial sums read in ONE round trip): Mistral-7B int4 +3.2 %, int8 +2.9 %, bf16 B = 16 +3.7 %, Qwen3-14B int4 +0.6 %
   int opt_prefill_x_terms = 2;  // float32 activations, prefill tile GEMM on dense bf16 weights: 16-bit terms of x (2 or 3 = exact)
   int opt_defer_norm = 1;       // float32 activations: RMSNorm row scale applied in the split-K kernel's epilogue (no norm launch)
+  int opt_quant_prefill_tile = 1;     // int4 / int8 g64 prefill on the packed-weight tile GEMM instead of the [hi | lo] copy (gemv_rows)
   int opt_short_prefill_skinny = 1;   // short prefill / mixed calls on the weight-streaming kernel instead of the tile GEMM (gemv_rows)
   // the q|k|v linear of a float32-KV decode step publishes its K slices' partial rows and the decode attention's prologue
   // adds them (0: the linear's last arriver combines).  Bit-identical outputs; measurements and history: DESIGN §8e

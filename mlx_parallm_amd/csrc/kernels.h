@@ -132,6 +132,14 @@ int gemm_q4_ksplit(const LinearW& W, const GemvCall& c, size_t rows);
 void gemm_q4_force(int code);     // test / A-B hook: mt | TW << 3 | KW << 7 | ksplit << 11 | NS << 15 for this thread's next plans; 0 clears
 int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr);
 
+// int4 / int8 (group 64, tile-major) weights, many rows of 16-bit activations (gemm_qtile.hip): the prefill tile GEMM on the
+// PACKED matrix -- codes unpacked in registers, no [hi | lo] copy, one walk of K.  c.pro must be PRO_NONE (the caller normalises
+// first).  `ws` (ws_cap bytes, >= gemm_qtile_ws_bytes()) takes the per-group sums of x and, behind them, the float32 partial
+// tiles of a K split; with less room behind the sums the call splits less, or not at all.
+bool gemm_qtile_supported(const LinearW& W, const GemvCall& c, size_t rows);
+size_t gemm_qtile_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows);
+int launch_gemm_qtile(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, size_t ws_cap);
+
 // tile-major weight layout (repack.hip)
 bool tiled_supported(int wk, int N, int K, int group);
 size_t tiled_bytes(int wk, int N, int K, int group);

@@ -269,6 +269,22 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   return run_timed([&] { return launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap); }, iters, avg_ms);
 }
 
+// gemm_qtile.hip on its own: the tile GEMM on packed int4 / int8 (group 64) weights, and nothing else -- what it does not take
+// is refused before anything is launched or written
+int mi_op_gemm_prefill_q(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
+  if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
+  MI_TRY(ready());
+  const LinearW W = to_linear(w);
+  const GemvCall c = to_call(a);
+  if (c.M < 1 || !gemm_qtile_supported(W, c, (size_t)c.M))
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_q: tile-major int4 / int8 weights in groups of 64, 16-bit activations in the scales' dtype, no prologue");
+  void* ws = nullptr;
+  FreeGuard g_ws{ws};
+  const size_t cap = gemm_qtile_ws_bytes(W, c, (size_t)c.M);
+  MI_HIP(hipMalloc(&ws, cap));
+  return run_timed([&] { return launch_gemm_qtile(W, c, (size_t)c.M, nullptr, ws, cap); }, iters, avg_ms);
+}
+
 // gemm_prefill.hip on float32 activations, as gemv_rows_on (engine.hip) runs it: (norm +) launch_split3_rows into a buffer of
 // split3_bytes, then launch_gemm_prefill on that image with c.ldx = x_terms x K.  An f16 matrix is multiplied through its
 // [hi | lo] bf16 copy (launch_f16_to_hilo), presented as gemv_rows does: wk = WK_BF16, K = 2 K, c.kx = K.  Every buffer
