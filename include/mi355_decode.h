@@ -438,7 +438,8 @@ int mi_profile_read(mi_engine* e, int64_t* n_launches, double* total_ms);
  *                             weight-streaming split-K kernel of the decode steps, ~2x faster at that size)
  *   "quant_prefill_tile"      1 (default): prefill / mixed calls above the streaming kernels' row limits and up to 1024 rows on int4 /
  *                             int8 group-64 weights, 16-bit activations, run the tile GEMM that reads the packed matrix (gemm_qtile.hip);
- *                             0: the tile GEMM over a [hi | lo] 16-bit copy written per call.  Another summation order: close,
+ *                             mxfp4 weights with bf16 activations likewise, up to 1024 rows (a limit of its own measurement);
+ *                             0: the tile GEMM over a [hi | lo] 16-bit copy (mxfp4: a bf16 copy) written per call. Another summation order: close,
  *                             not bit-identical.  Any other value: MI_ERR_INVALID, the option keeps its value.
  *   "tile_weights"            0: keep weights row-major (before mi_engine_finalize only; default 1)
  *   "shared_prefix_attention" N > 0: a decode step on a paged cache (head_dim 64 / 128) whose rows hold a set of two or more rows

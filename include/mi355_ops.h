@@ -82,9 +82,9 @@ extern "C" {
  *   [0, 1024)     codes: dword T of the lane's 16 bytes, code e at nibble e (NATURAL order, not the affine int4 interleave:
  *                 v_cvt_scalef32_pk_bf16_fp4 with byte_sel 0..3 turns the dword into the eight values of an MFMA B operand)
  *   [1024, 1088)  one dword per row r at 4 r: its four scale bytes in k order (byte T = the group of MFMA step T)
- * mi_op_tiled_bytes is exactly N K / 2 + N K / 32 and the over-read rule of the 3- / 6-bit kinds holds: gemm_mx4.hip addresses
- * blocks of the matrix only and clamps its prefetch.  Scale byte 0 (2^-127, a float32 subnormal) is exact in mi_op_gemv's
- * generic kernel, mi_op_embed and the prefill copy (which rounds to bf16); gemm_mx4.hip hands the conversion s << 23, an
+ * mi_op_tiled_bytes is exactly N K / 2 + N K / 32 and the over-read rule of the 3- / 6-bit kinds holds: gemm_mx4.hip and the
+ * mxfp4 kernel of gemm_qtile.hip address blocks of the matrix only and clamp their prefetch. Scale byte 0 (2^-127, a float32 subnormal) is exact in mi_op_gemv's
+ * generic kernel, mi_op_embed and the prefill copy (which rounds to bf16); gemm_mx4.hip and gemm_qtile.hip hand the conversion s << 23, an
  * exponent field of 0: the weights of such a group (all below 2^-124) are bf16 subnormals or zero there, whichever the
  * instruction and the MFMA make of them -- NOT pinned, and no test relies on it. */
 #define MI_WK_MX4_BF16 15
@@ -183,7 +183,10 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
  * tile-major int4 / int8 in groups of 64, a->M rows (any count) of 16-bit activations in the scales' dtype, a->pro =
  * MI_PRO_NONE; store / float32 store / residual / SwiGLU epilogues, a linear bias as T(T(acc) + b).  No dequantised copy is
  * made; per output element acc = sum over groups of (s_g sum q x + b_g sum x) in float32, deterministic, each row on its own.
- * Anything else (float32 activations, row-major weights, other groups or bit widths, a prologue) returns MI_ERR_UNSUPPORTED
+ * Tile-major mxfp4 weights (MI_WK_MX4_BF16, group 32, K % 128 == 0, N % 16 == 0) with bf16 activations are taken as well, same
+ * epilogues: the FP4 codes are converted in registers (code x 2^(s - 127), exact in bf16) and every product is accumulated in
+ * float32 on the matrix cores; scale bytes 0 and 255 as for gemm_mx4.hip above.
+ * Anything else (float32 activations, MI_WK_MX4_F32, row-major weights, other groups or bit widths, a prologue) returns MI_ERR_UNSUPPORTED
  * with nothing launched and no output touched; mi_op_gemm_prefill keeps running the copy route.  iters >= 1 also times that
  * many back-to-back launches (sums of x + GEMM) into *avg_ms. */
 int mi_op_gemm_prefill_q(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);

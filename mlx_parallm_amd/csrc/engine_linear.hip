@@ -177,8 +177,8 @@ int route_qg(const Lin& a) {
 }
 
 // 1d. mxfp4 weights, up to 128 rows of bf16 activations: the FP4 streaming kernel (gemm_mx4.hip), run as routes 1b and 1c run
-// theirs.  Longer calls fall through to the prefill GEMM (one exact bf16 copy per call); float32 activations and matrices that
-// are not tile-major (K % 128 != 0) to the generic kernel.
+// theirs.  Longer calls fall through to route 4b (the tile GEMM on the packed matrix, up to 1024 rows) and from there to the prefill
+// GEMM (one exact bf16 copy per call); float32 activations and matrices that are not tile-major (K % 128 != 0) to the generic kernel.
 int route_mx4(const Lin& a) {
   mi_engine* e = a.e;
   if (!(e->opt_skinny_gemm && a.rows <= 128 && gemm_mx4_supported(a.f.W, a.c, a.rows))) return NOT_TAKEN;
@@ -282,10 +282,16 @@ int route_skinny(const Lin& a) {
 // ahead on all four through 1024 rows (gate|up 0.12 vs 0.32 ms at 256 rows, 0.42 vs 0.49 at 1024), behind on o_proj and
 // down_proj from 2048 rows and on all four at 4096 / 8192 (the kernel reaches ~0.6 PFLOP/s where the copy route's walk over
 // 2 K runs at ~1.3): longer calls stay on route 5.
+// mxfp4 (bf16 activations) goes the same way on qtile_mx4_kernel instead of route 5's bf16 copy per call + dense walk of K.  Its
+// limit is its own measurement ("mxfp4 prefill on packed weights"): ahead on all four linears through 1024 rows (gate|up
+// 0.065 vs 0.170 ms at 256 rows, 0.227 vs 0.272 at 1024), behind on down_proj at 2048 (0.239 vs 0.226; gate|up level)
+// and on all four at 8192 (the kernel reaches ~1.07 PFLOP/s, the dense walk ~1.4).  That the two limits are equal is a coincidence.
 constexpr size_t QTILE_MAX_ROWS = 1024;
+constexpr size_t QTILE_MX4_MAX_ROWS = 1024;
 int route_qtile(const Lin& a) {
   mi_engine* e = a.e; const FusedLinear& f = a.f; const size_t rows = a.rows;
-  if (!(e->opt_prefill_gemm && e->opt_quant_prefill_tile && a.quant() && a.c.act != MI_F32 && rows <= QTILE_MAX_ROWS)) return NOT_TAKEN;
+  const size_t max_rows = wk_is_mx4(f.W.wk) ? QTILE_MX4_MAX_ROWS : QTILE_MAX_ROWS;
+  if (!(e->opt_prefill_gemm && e->opt_quant_prefill_tile && a.quant() && a.c.act != MI_F32 && rows <= max_rows)) return NOT_TAKEN;
   GemvCall c = a.c;
   c.pro = PRO_NONE;                            // (the norm launch in front)
   if (!gemm_qtile_supported(f.W, c, rows)) return NOT_TAKEN;

@@ -30,6 +30,7 @@
 #include <atomic>
 
 #include "gemv_phase.h"
+#include "mx4_cvt.h"
 
 namespace mi {
 
@@ -53,18 +54,6 @@ struct MxParams {
 
 // a lane's share of one block: its 32 codes and the four scale bytes of its row of the tile
 struct MxRegs { u32x4 q; uint32_t sc; };
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// the B operand of one MFMA step: the eight codes of `dw` (code e at nibble e) times `scale`, as bf16
-__device__ __forceinline__ u32x4 mx_operand(uint32_t dw, float scale) {
-  u32x4 r;
-  r.x = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 0));
-  r.y = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 1));
-  r.z = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 2));
-  r.w = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 3));
-  return r;
-}
 
 template <int MT>
 __global__ __launch_bounds__(MX_NW * 64) void mx4_kernel(const MxParams p) {
@@ -126,7 +115,7 @@ __global__ __launch_bounds__(MX_NW * 64) void mx4_kernel(const MxParams p) {
     for (int T = 0; T < 4; ++T) {
       u32x4 wq[TN];
 #pragma unroll
-      for (int a = 0; a < TN; ++a) wq[a] = mx_operand(wr[a].q[T], __uint_as_float(((wr[a].sc >> (8 * T)) & 0xffu) << 23));
+      for (int a = 0; a < TN; ++a) wq[a] = mx_operand(wr[a].q[T], mx_scale(wr[a].sc, T));
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const u32x4 a0 = *(const u32x4*)(buf + ((T * MT + mt) * 64 + lane) * 16);

@@ -28,9 +28,13 @@
 //   * the group sums of x ride with the X tile: 128 floats per step, staged next to it.
 //   * few (M, N) blocks (a prompt of a few hundred rows): K is split over gridDim.z workgroups; slice z leaves a float32
 //     partial tile in ws[z][M][N] and qtile_splitk_kernel adds the slices in slice order and applies the epilogue.
+//
+// mxfp4 (MI_WK_MX4_BF16, bf16 activations) runs qtile_mx4_kernel: the same tiles, X staging, K split and epilogues around FP4
+// codes converted in registers by the hardware (mx4_cvt.h) and ONE accumulator chain per tile -- its notes stand at the kernel.
 #include <algorithm>
 
 #include "gemv_phase.h"
+#include "mx4_cvt.h"
 
 namespace mi {
 
@@ -133,6 +137,85 @@ __device__ __forceinline__ void qt_store_plain(const QtParams& p, int m, int n, 
   else { AT* h = (AT*)p.resid; h[(size_t)m * p.ldo + n] = (AT)((float)h[(size_t)m * p.ldo + n] + y); }
 }
 
+// ---- the X tile of one K step (128 rows x 64 k), shared by the tile kernels of this file: 128 rows x 8 chunks of 16 B, thread ->
+// chunks tid, tid + 256, ..; straight-line loads (rows past M read row M - 1 and are zeroed on the way into LDS)
+template <typename AT>
+struct QtXTile {
+  u32x4 areg[4];
+  const AT* arow[4];
+  int live;                        // rows of the tile inside the matrix
+  __device__ __forceinline__ QtXTile(const AT* x, int ldx, int M, int m0, int tid) : live(M - m0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i, row = c >> 3, kq = c & 7;
+      arow[i] = x + (size_t)min(m0 + row, M - 1) * ldx + kq * 8;
+    }
+  }
+  __device__ __forceinline__ void load(int s) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) areg[i] = *(const u32x4*)(arow[i] + s * QBK);
+  }
+  // PERM (int4): the 8 elements of a chunk go (e0 e1 | e2 e3 | e4 e5 | e6 e7) -> (e0 e4 | e1 e5 | e2 e6 | e3 e7)
+  template <bool PERM>
+  __device__ __forceinline__ void store(AT (*As)[QLDA], int tid) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i, row = c >> 3, kq = c & 7;
+      u32x4 v = row < live ? areg[i] : u32x4{0u, 0u, 0u, 0u};
+      if constexpr (PERM)
+        v = u32x4{(v.x & 0xffffu) | (v.z << 16), (v.x >> 16) | (v.z & 0xffff0000u), (v.y & 0xffffu) | (v.w << 16), (v.y >> 16) | (v.w & 0xffff0000u)};
+      *(u32x4*)&As[row][kq * 8] = v;
+    }
+  }
+};
+
+// ---- the end of a tile kernel: lane (c16, g) holds C[m = 4 g + r][n = c16] of every 16 x 16 tile of its wave's 64 x 64.
+// A K slice of a split leaves its float32 partial tile for qtile_splitk_kernel; otherwise the epilogue stores.
+template <typename AT, bool SWIGLU>
+__device__ __forceinline__ void qt_finish(const QtParams& p, const f32x4 (&acc)[4][4], int m0, int bn, int wm, int wn, int c16, int g) {
+  if constexpr (!SWIGLU) {
+    if (p.ksplit > 1) {
+      float* wz = p.ws + (size_t)blockIdx.z * p.M * p.N;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = m0 + wm * 64 + mt * 16 + 4 * g + r;
+          if (m >= p.M) continue;
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) {
+            const int n = bn * QBN + wn * 64 + nt * 16 + c16;
+            if (n < p.N) wz[(size_t)m * p.N + n] = acc[mt][nt][r];
+          }
+        }
+      return;
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m0 + wm * 64 + mt * 16 + 4 * g + r;
+      if (m >= p.M) continue;
+      if constexpr (SWIGLU) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int n = bn * 64 + wn * 32 + j * 16 + c16;
+          if (n >= p.pair_offset) continue;
+          const float gt = linear_value<AT>(acc[mt][j][r], p.bias != nullptr, p.bias, n, 1, RND_NONE);
+          const float up = linear_value<AT>(acc[mt][j + 2][r], p.bias != nullptr, p.bias, n + p.pair_offset, 1, RND_NONE);
+          ((AT*)p.out)[(size_t)m * p.ldo + n] = (AT)swiglu_value<AT>(gt, up, RND_NONE);
+        }
+      } else {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const int n = bn * QBN + wn * 64 + nt * 16 + c16;
+          if (n < p.N) qt_store_plain<AT>(p, m, n, acc[mt][nt][r]);
+        }
+      }
+    }
+}
+
 // grid: (m blocks, n blocks, K slices).  SWIGLU: a block covers 64 gate columns + the 64 matching up columns.
 template <typename AT, int BITS, bool SWIGLU>
 __global__ __launch_bounds__(256, 2) void qtile_kernel(QtParams p) {
@@ -168,33 +251,16 @@ __global__ __launch_bounds__(256, 2) void qtile_kernel(QtParams p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // ---- X tile: 128 rows x 8 chunks of 16 B, thread -> chunks tid, tid + 256, ..; straight-line loads (rows past M read
-  // row M - 1 and are zeroed on the way into LDS).  The tile's 128 group sums: one float per thread of the first two waves.
-  u32x4 areg[4];
+  // ---- X tile (QtXTile).  The tile's 128 group sums: one float per thread of the first two waves.
+  QtXTile<AT> xt(x, p.ldx, p.M, m0, tid);
   float sreg = 0.f;
-  const AT* arow[4];
-  bool aok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = tid + 256 * i, row = c >> 3, kq = c & 7;
-    aok[i] = m0 + row < p.M;
-    arow[i] = x + (size_t)min(m0 + row, p.M - 1) * p.ldx + kq * 8;
-  }
   const float* srow = p.sx + m0 + (tid & (QBM - 1));          // (m0 + 127 < Mpad)
   auto load_a = [&](int s) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) areg[i] = *(const u32x4*)(arow[i] + s * QBK);
+    xt.load(s);
     sreg = srow[(size_t)s * p.Mpad];
   };
   auto store_a = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i, row = c >> 3, kq = c & 7;
-      u32x4 v = aok[i] ? areg[i] : u32x4{0u, 0u, 0u, 0u};
-      if constexpr (BITS == 4)          // (e0 e1 | e2 e3 | e4 e5 | e6 e7) -> (e0 e4 | e1 e5 | e2 e6 | e3 e7)
-        v = u32x4{(v.x & 0xffffu) | (v.z << 16), (v.x >> 16) | (v.z & 0xffff0000u), (v.y & 0xffffu) | (v.w << 16), (v.y >> 16) | (v.w & 0xffff0000u)};
-      *(u32x4*)&As[buf][row][kq * 8] = v;
-    }
+    xt.template store<BITS == 4>(As[buf], tid);
     if (tid < QBM) Sx[buf][tid] = sreg;
   };
 
@@ -292,48 +358,126 @@ __global__ __launch_bounds__(256, 2) void qtile_kernel(QtParams p) {
     if (s + 1 < s1) step(s + 1, 1);
   }
 
-  // ---- lane (c16, g) holds C[m = 4 g + r][n = c16] of every 16 x 16 tile
-  if constexpr (!SWIGLU) {
-    if (p.ksplit > 1) {                            // this K slice's partial tile, float32, for qtile_splitk_kernel
-      float* wz = p.ws + (size_t)blockIdx.z * p.M * p.N;
+  qt_finish<AT, SWIGLU>(p, acc, m0, bn, wm, wn, c16, g);
+}
+
+// ---- mxfp4 (MI_WK_MX4_BF16, tile-major blocks of 16 rows x 128 k = 1088 bytes), bf16 activations.  Same grid, waves, tiles,
+// X staging and end as qtile_kernel; what differs is everything about W:
+//   * a lane's own 16 bytes of a block ARE its B operands of the block's four MFMA steps: dword T holds k = 32 T + 8 g + e, code
+//     e at nibble e, and mx_operand (four v_cvt_scalef32_pk_bf16_fp4) makes step T's eight dequantised bf16 values from it and
+//     scale byte T of the row's dword.  The k order is the natural one: lane group g of step t of an X tile reads chunk 4 t + g.
+//   * a step of 32 k is one MX group and there is no bias: nothing is folded outside the MFMA chain, acc = mfma(a, b, acc) over
+//     the whole K slice, 16 independent chains per wave and step.  No group sums of x, no workspace but the K split's.
+//   * the conversions are software-pipelined one MFMA step ahead, also across the block edge: while the 16 MFMAs of step T issue
+//     (four items of one row tile x four N tiles), item i converts N tile i's operand of step T + 1 into the other half of bq.
+//     After the prologue no MFMA waits for a conversion of its own step.  The order is pinned item by item.
+//   * two blocks of codes + scales are in registers: wq (being converted) and wqn (the block after it).  When step 3's operands
+//     are converted -- behind the items of step 2 -- wq takes wqn and the block after that is requested into wqn.  Nothing reads
+//     wqn before the next block's move; the first wait that covers its loads is the vmcnt(0) of the next X tile's store, whose
+//     own loads are younger: 48 MFMAs per wave after the request (read in the ISA; DESIGN 3 has what it took).  The stream is clamped to the slice's last block, the N tiles to the matrix's
+//     last tile: the kernel addresses nothing beyond mi_op_tiled_bytes.
+// K slices are whole blocks: slice z covers blocks [z nblk / ksplit, (z + 1) nblk / ksplit).  A trip of the loop is one block =
+// two X tiles of 64 k, LDS buffers 0 and 1 (37 KB; the choice against 128-k tiles: DESIGN 3).
+template <bool SWIGLU>
+__global__ __launch_bounds__(256, 2) void qtile_mx4_kernel(QtParams p) {
+  __shared__ __attribute__((aligned(16))) bf16 As[2][QBM][QLDA];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int c16 = lane & 15, g = lane >> 4;
+  const int bm = blockIdx.x, bn = blockIdx.y;
+  const int m0 = bm * QBM;
+  const int nblk = p.K / 128;
+  const int b0 = (int)(((long)blockIdx.z * nblk) / p.ksplit), b1 = (int)(((long)(blockIdx.z + 1) * nblk) / p.ksplit);
+  const int slast = 2 * b1 - 1;                        // the slice's last X tile
+
+  // the wave's four N tiles (wave-uniform); a tile past the matrix re-reads the last one and stores nothing
+  const int ntiles_w = p.N / 16;
+  const char* wbase[4];
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm * 64 + mt * 16 + 4 * g + r;
-          if (m >= p.M) continue;
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) {
-            const int n = bn * QBN + wn * 64 + nt * 16 + c16;
-            if (n < p.N) wz[(size_t)m * p.N + n] = acc[mt][nt][r];
-          }
-        }
-      return;
-    }
+  for (int nt = 0; nt < 4; ++nt) {
+    int t;
+    if constexpr (!SWIGLU) t = (bn * QBN + wn * 64 + nt * 16) / 16;
+    else t = (bn * 64 + wn * 32 + (nt & 1) * 16 + (nt >> 1) * p.pair_offset) / 16;
+    wbase[nt] = (const char*)p.w + (size_t)min(t, ntiles_w - 1) * nblk * MX4_BLOCK + lane * 16;
   }
+
+  f32x4 acc[4][4];
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + wm * 64 + mt * 16 + 4 * g + r;
-      if (m >= p.M) continue;
-      if constexpr (SWIGLU) {
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  QtXTile<bf16> xt((const bf16*)p.x, p.ldx, p.M, m0, tid);
+
+  u32x4 wq[4], wqn[4];            // codes: this block's, the next block's
+  uint32_t sc[4], scn[4];         // the four scale bytes of the lane's row of W
+  const int soff = 1024 + c16 * 4 - lane * 16;
+  auto load_w = [&](int b, u32x4 (&q)[4], uint32_t (&s)[4]) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int n = bn * 64 + wn * 32 + j * 16 + c16;
-          if (n >= p.pair_offset) continue;
-          const float gt = linear_value<AT>(acc[mt][j][r], p.bias != nullptr, p.bias, n, 1, RND_NONE);
-          const float up = linear_value<AT>(acc[mt][j + 2][r], p.bias != nullptr, p.bias, n + p.pair_offset, 1, RND_NONE);
-          ((AT*)p.out)[(size_t)m * p.ldo + n] = (AT)swiglu_value<AT>(gt, up, RND_NONE);
-        }
-      } else {
+    for (int nt = 0; nt < 4; ++nt) {
+      const char* blk = wbase[nt] + (size_t)b * MX4_BLOCK;
+      q[nt] = *(const u32x4*)blk;
+      s[nt] = *(const uint32_t*)(blk + soff);
+    }
+  };
+  u32x4 bq[2][4];                 // B operands: [step parity][N tile]
+  auto convert = [&](int T, int nt) {
+    u32x4 r = mx_operand(wq[nt][T], mx_scale(sc[nt], T));
+    // (an empty statement that holds the conversion where it is written: left alone, hipcc sank step 0's conversions of the next
+    // block out of step 3's items to behind the tile's barrier, where no MFMA covers them)
+    asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+    bq[T & 1][nt] = r;
+  };
+
+  // X tile s = half h of block b, out of LDS buffer h: MFMA steps T = 2 h, 2 h + 1 of the block
+  auto half = [&](int b, int h) {
+    const int s = 2 * b + h;
+    xt.load(min(s + 1, slast));
+    __builtin_amdgcn_sched_barrier(0);                 // the loads stay ahead of this tile's MFMAs
+    u32x4 af[2];
+    auto rd = [&](int it, int slot) {                  // item it = (step t, row tile mt): the A fragment, one item ahead
+      const int t = it >> 2, mt = it & 3;
+      af[slot] = *(const u32x4*)&As[h][wm * 64 + mt * 16 + c16][(4 * t + g) * 8];
+    };
+    rd(0, 0);
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int T = 2 * h + (it >> 2), mt = it & 3, sl = it & 1;
+      if (it + 1 < 8) rd(it + 1, sl ^ 1);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = mfma16<bf16>(af[sl], bq[T & 1][nt], acc[mt][nt]);
+      convert((T + 1) & 3, mt);                        // N tile mt's operand of the next step (step 3: the next block's step 0)
+      __builtin_amdgcn_sched_barrier(0);
+      if (T == 2 && mt == 3) {                         // wq is converted to its end: the next block moves up, the one after it is requested
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-          const int n = bn * QBN + wn * 64 + nt * 16 + c16;
-          if (n < p.N) qt_store_plain<AT>(p, m, n, acc[mt][nt][r]);
+          wq[nt] = wqn[nt]; sc[nt] = scn[nt];
+          // (holds the move HERE: left alone, hipcc loaded into fresh registers and moved them at the end of the same trip, behind
+          // a wait for loads that were ~16 MFMAs old)
+          asm volatile("" : "+v"(wq[nt].x), "+v"(wq[nt].y), "+v"(wq[nt].z), "+v"(wq[nt].w), "+v"(sc[nt]));
         }
+        load_w(min(b + 2, b1 - 1), wqn, scn);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
+    if (s < slast) {
+      xt.template store<false>(As[h ^ 1], tid);        // buffer h ^ 1 was last read one tile ago; that tile's barrier separates
+      __syncthreads();
+    }
+  };
+
+  xt.load(2 * b0);
+  load_w(b0, wq, sc);
+  load_w(min(b0 + 1, b1 - 1), wqn, scn);
+  xt.template store<false>(As[0], tid);
+  __syncthreads();
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) convert(0, nt);
+  for (int b = b0; b < b1; ++b) {
+    half(b, 0);
+    half(b, 1);
+  }
+  qt_finish<bf16, SWIGLU>(p, acc, m0, bn, wm, wn, c16, g);
 }
 
 // the K slices of qtile_kernel, added in slice order, + the epilogue (store / float32 store / residual); 4 columns per thread
@@ -350,13 +494,15 @@ __global__ __launch_bounds__(256) void qtile_splitk_kernel(QtParams p) {
   for (int j = 0; j < 4; ++j) qt_store_plain<AT>(p, m, n + j, a[j]);
 }
 
+// the front of the workspace: the group sums of x (mxfp4 has none: one unused line, so that no caller meets a size of zero)
 size_t qt_sx_bytes(const LinearW& W, size_t rows) {
+  if (wk_is_mx4(W.wk)) return 256;
   const size_t mpad = (rows + QBM - 1) / QBM * QBM;
   return ((size_t)(W.K / 64) * mpad * sizeof(float) + 255) & ~(size_t)255;
 }
 
-// K slices for a call whose (M, N) grid alone leaves CUs idle: ~512 workgroups in all (two per CU), at least 8 group steps
-// per slice, plain / float32 / residual epilogues (W.N % 4 == 0 for the reduce kernel), and the partial tiles within `cap`
+// K slices for a call whose (M, N) grid alone leaves CUs idle: ~512 workgroups in all (two per CU), at least 8 steps of 64 k
+// per slice (mxfp4: four blocks, its slices being whole blocks), plain / float32 / residual epilogues (W.N % 4 == 0 for the reduce kernel), and the partial tiles within `cap`
 int qt_ksplit(const LinearW& W, const GemvCall& c, size_t rows, size_t cap) {
   if (c.epi == EPI_SWIGLU || W.N % 4 != 0) return 1;
   const long blocks = (long)((rows + QBM - 1) / QBM) * ((W.N + QBN - 1) / QBN);
@@ -376,13 +522,14 @@ void qt_launch(const QtParams& p, bool sw, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
-// int4 / int8 (group 64, tile-major) weights, 16-bit activations in the scales' dtype, no prologue (the caller normalises
-// first), any row count; store / float32 store / residual / SwiGLU epilogues, linear bias
+// int4 / int8 (group 64, tile-major) weights, 16-bit activations in the scales' dtype, or mxfp4 (MI_WK_MX4_BF16, tile-major)
+// weights, bf16 activations; no prologue (the caller normalises first), any row count; store / float32 store / residual / SwiGLU epilogues, linear bias
 bool gemm_qtile_supported(const LinearW& W, const GemvCall& c, size_t rows) {
-  if (c.force_v1 || c.rnd != RND_NONE || W.layout != 1 || W.group != 64 || c.pro != PRO_NONE || c.kx != 0) return false;
-  const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.K % 128 == 0;
-  const bool q8 = ((W.wk == WK_Q8_BF16 && c.act == MI_BF16) || (W.wk == WK_Q8_F16 && c.act == MI_F16)) && W.K % 64 == 0;
-  if ((!q4 && !q8) || rows < 1 || W.K < 64 || c.ldx % 8 != 0) return false;
+  if (c.force_v1 || c.rnd != RND_NONE || W.layout != 1 || c.pro != PRO_NONE || c.kx != 0) return false;
+  const bool q4 = ((W.wk == WK_Q4_BF16 && c.act == MI_BF16) || (W.wk == WK_Q4_F16 && c.act == MI_F16)) && W.group == 64 && W.K % 128 == 0;
+  const bool q8 = ((W.wk == WK_Q8_BF16 && c.act == MI_BF16) || (W.wk == WK_Q8_F16 && c.act == MI_F16)) && W.group == 64 && W.K % 64 == 0;
+  const bool mx = W.wk == WK_MX4_BF16 && c.act == MI_BF16 && W.group == 32 && W.K % 128 == 0;
+  if ((!q4 && !q8 && !mx) || rows < 1 || W.K < 64 || c.ldx % 8 != 0) return false;
   if (c.epi != EPI_STORE && c.epi != EPI_STORE_F32 && c.epi != EPI_RESID && c.epi != EPI_SWIGLU) return false;
   // an adapted matrix: the caller adds the LoRA term to the stored output afterwards (launch_lora_up_add)
   if ((W.lora_b[0] != nullptr || W.lora_b[1] != nullptr) && c.epi != EPI_STORE) return false;
@@ -390,7 +537,7 @@ bool gemm_qtile_supported(const LinearW& W, const GemvCall& c, size_t rows) {
   return W.N % 16 == 0;
 }
 
-// the group sums of x, and behind them the partial tiles of the K split the call would like (at most 128 MiB of them)
+// the group sums of x (mxfp4: none), and behind them the partial tiles of the K split the call would like (at most 128 MiB of them)
 size_t gemm_qtile_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows) {
   const int ks = qt_ksplit(W, c, rows, (size_t)128 << 20);
   return qt_sx_bytes(W, rows) + (ks > 1 ? (size_t)ks * rows * W.N * sizeof(float) : 0);
@@ -407,14 +554,19 @@ int launch_gemm_qtile(const LinearW& W, const GemvCall& c, size_t rows, hipStrea
   p.bias = W.bias;
   p.ksplit = qt_ksplit(W, c, rows, ws_cap - sxb);
   p.ws = (float*)((char*)ws + sxb);
-  const bool b16 = c.act == MI_BF16, sw = c.epi == EPI_SWIGLU;
-  if (b16) hipLaunchKernelGGL(qtile_sums_kernel<bf16>, dim3(p.Mpad), dim3(256), 0, st, (const bf16*)c.x, c.ldx, p.M, p.Mpad, W.K, (float*)ws);
-  else hipLaunchKernelGGL(qtile_sums_kernel<f16>, dim3(p.Mpad), dim3(256), 0, st, (const f16*)c.x, c.ldx, p.M, p.Mpad, W.K, (float*)ws);
+  const bool b16 = c.act == MI_BF16, sw = c.epi == EPI_SWIGLU, mx = wk_is_mx4(W.wk);
+  if (!mx) {                                        // (mxfp4 has no bias term: no sums, p.sx is the unused line and is never read)
+    if (b16) hipLaunchKernelGGL(qtile_sums_kernel<bf16>, dim3(p.Mpad), dim3(256), 0, st, (const bf16*)c.x, c.ldx, p.M, p.Mpad, W.K, (float*)ws);
+    else hipLaunchKernelGGL(qtile_sums_kernel<f16>, dim3(p.Mpad), dim3(256), 0, st, (const f16*)c.x, c.ldx, p.M, p.Mpad, W.K, (float*)ws);
+  }
   MI_HIP(hipGetLastError());
   const int ncols = sw ? c.pair_offset : W.N, bnc = sw ? 64 : QBN;
   const dim3 grid((unsigned)(p.Mpad / QBM), (unsigned)((ncols + bnc - 1) / bnc), (unsigned)p.ksplit);
   const bool q4 = wk_bits(W.wk) == 4;
-  if (b16) { if (q4) qt_launch<bf16, 4>(p, sw, grid, st); else qt_launch<bf16, 8>(p, sw, grid, st); }
+  if (mx) {
+    if (sw) hipLaunchKernelGGL(qtile_mx4_kernel<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(qtile_mx4_kernel<false>, grid, dim3(256), 0, st, p);
+  } else if (b16) { if (q4) qt_launch<bf16, 4>(p, sw, grid, st); else qt_launch<bf16, 8>(p, sw, grid, st); }
   else { if (q4) qt_launch<f16, 4>(p, sw, grid, st); else qt_launch<f16, 8>(p, sw, grid, st); }
   MI_HIP(hipGetLastError());
   if (p.ksplit > 1) {

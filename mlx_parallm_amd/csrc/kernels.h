@@ -136,6 +136,8 @@ int launch_gemm_q4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t
 // PACKED matrix -- codes unpacked in registers, no [hi | lo] copy, one walk of K.  c.pro must be PRO_NONE (the caller normalises
 // first).  `ws` (ws_cap bytes, >= gemm_qtile_ws_bytes()) takes the per-group sums of x and, behind them, the float32 partial
 // tiles of a K split; with less room behind the sums the call splits less, or not at all.
+// mxfp4 (WK_MX4_BF16, group 32, tile-major) weights with bf16 activations go through the same three entry points: FP4 codes
+// converted in registers (mx4_cvt.h), no sums of x -- the front of `ws` is one unused line, never a size of zero.
 bool gemm_qtile_supported(const LinearW& W, const GemvCall& c, size_t rows);
 size_t gemm_qtile_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows);
 int launch_gemm_qtile(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, size_t ws_cap);

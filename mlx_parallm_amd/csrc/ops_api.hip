@@ -269,15 +269,15 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   return run_timed([&] { return launch_gemm_prefill(W, c, (size_t)c.M, nullptr, scratch, ws, cap); }, iters, avg_ms);
 }
 
-// gemm_qtile.hip on its own: the tile GEMM on packed int4 / int8 (group 64) weights, and nothing else -- what it does not take
-// is refused before anything is launched or written
+// gemm_qtile.hip on its own: the tile GEMM on packed int4 / int8 (group 64) or mxfp4 weights, and nothing else -- what it does
+// not take is refused before anything is launched or written
 int mi_op_gemm_prefill_q(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms) {
   if (!w || !a) return fail(MI_ERR_INVALID, "null argument");
   MI_TRY(ready());
   const LinearW W = to_linear(w);
   const GemvCall c = to_call(a);
   if (c.M < 1 || !gemm_qtile_supported(W, c, (size_t)c.M))
-    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_q: tile-major int4 / int8 weights in groups of 64, 16-bit activations in the scales' dtype, no prologue");
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill_q: tile-major int4 / int8 weights in groups of 64 with 16-bit activations in the scales' dtype, or mxfp4 (MI_WK_MX4_BF16) weights with bf16 activations; no prologue");
   void* ws = nullptr;
   FreeGuard g_ws{ws};
   const size_t cap = gemm_qtile_ws_bytes(W, c, (size_t)c.M);

@@ -7,7 +7,14 @@ ALTERNATING inside a round; reported: the median and the lowest / highest sample
 launches repeat on one matrix that stays in the last-level cache: cache rates, not HBM rates.
 
 --step: a Mistral-7B-shaped engine at batch 8, 16-bit KV 1024 -> 1100, on mxfp4 and on int4 group-32 weights (random codes and
-scales set directly, as a checkpoint would give them), bench.py's timing protocol, --rounds legs per engine, alternating."""
+scales set directly, as a checkpoint would give them), bench.py's timing protocol, --rounds legs per engine, alternating.
+
+--prefill: the four Mistral-7B linears with their epilogues (q|k|v store, o residual, gate|up SwiGLU, down residual) at 256 ..
+8192 rows of bf16 activations, per launch: mi_op_gemm_prefill_q on the packed mxfp4 matrix (qtile_mx4_kernel), mi_op_gemm_prefill
+on the same matrix (the bf16 copy written per call + the dense tile GEMM) and mi_op_gemm_prefill on a dense bf16 matrix of the
+same shape; the routes ALTERNATE inside a round, medians of --rounds samples.  A sample is at least --iters launches (default
+20 in this mode) and at least ~5 ms of work (counted at 1 PFLOP/s), so the small shapes repeat a few hundred times; the residual
+epilogues start every sample from a zeroed stream."""
 import argparse
 import ctypes as C
 import json
@@ -73,6 +80,47 @@ def kernels(args, emit):
                       "weight_GBps": round(lin[name][2] / (statistics.median(v) * 1e-6) / 1e9, 1)})
 
 
+PREFILL = {"qkv": (6144, 4096, "store"), "o": (4096, 4096, "resid"), "gate_up": (28672, 4096, "swiglu"), "down": (4096, 14336, "resid")}
+
+
+def prefill(args, emit):
+    lib = L.lib()
+    for shape, (N, K, epi) in PREFILL.items():
+        mx, mx_keep, _ = tiled("mx4_bf16", 32, N, K)
+        wd = (torch.randn((N, K), generator=torch.Generator().manual_seed(N), dtype=torch.float32) * 0.02).to(torch.bfloat16).cuda()
+        dn = L.OpLinear()
+        dn.wk, dn.N, dn.K, dn.group, dn.w = L.WK["bf16"], N, K, 64, wd.data_ptr()
+        dt = torch.zeros(int(lib.mi_op_tiled_bytes(C.byref(dn))), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        L.check(lib.mi_op_repack_tiled(C.byref(dn), C.c_void_p(dt.data_ptr())))
+        dn.w, dn.layout = dt.data_ptr(), 1
+        routes = {"tile_mx4": (lib.mi_op_gemm_prefill_q, mx), "copy_mx4": (lib.mi_op_gemm_prefill, mx), "dense_bf16": (lib.mi_op_gemm_prefill, dn)}
+        for M in (int(r) for r in args.rows.split(",")):
+            x = torch.randn((M, K), dtype=torch.bfloat16, device="cuda")
+            No = N // 2 if epi == "swiglu" else N
+            out = torch.zeros((M, No), dtype=torch.bfloat16, device="cuda")
+            a = L.OpGemvArgs()
+            a.x, a.ldx, a.M, a.act, a.ldo = x.data_ptr(), K, M, L.MI_BF16, No
+            a.epi = {"store": L.EPI_STORE, "resid": L.EPI_RESID, "swiglu": L.EPI_SWIGLU}[epi]
+            a.pair_offset = No if epi == "swiglu" else 0
+            if epi == "resid":
+                a.resid = out.data_ptr()
+            else:
+                a.out = out.data_ptr()
+            iters = max(args.iters, int(5e-3 / (2.0 * M * N * K / 1e15)))
+            us = {name: [] for name in routes}
+            for _ in range(args.rounds):
+                for name, (fn, ol) in routes.items():
+                    ms = C.c_float(0.0)
+                    out.zero_()
+                    torch.cuda.synchronize()
+                    L.check(fn(C.byref(ol), C.byref(a), iters, C.byref(ms)))
+                    us[name].append(ms.value * 1e3)
+            for name, v in us.items():
+                emit({"prefill": shape, "route": name, "rows": M, "iters": iters, "us": spread(v),
+                      "TFLOPs": round(2.0 * M * N * K / (statistics.median(v) * 1e-6) / 1e12, 1)})
+
+
 def engine_with(kind, group, cap):
     cfg = dict(bench.SHAPES["mistral-7b"], quantization=dict({"group_size": group, "bits": 4}, **({"mode": "mxfp4"} if kind.startswith("mx4") else {})))
     eng = Engine(cfg, device=0, max_positions=max(cap, 2048), act_dtype="bfloat16")
@@ -114,19 +162,22 @@ def step(args, emit):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", action="store_true")
-    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--prefill", action="store_true")
+    ap.add_argument("--iters", type=int, default=None, help="launches per sample (default 200; --prefill: 20)")
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--rows", default="1,8,64")
+    ap.add_argument("--rows", default=None, help="default 1,8,64; --prefill: 256,512,1024,2048,4096,8192")
     ap.add_argument("--steps", type=int, default=76)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--out", default=None, help="also write the results as JSON lines to this file")
     args = ap.parse_args()
+    args.iters = args.iters or (20 if args.prefill else 200)
+    args.rows = args.rows or ("256,512,1024,2048,4096,8192" if args.prefill else "1,8,64")
     lines = []
 
     def emit(r):
         lines.append(r)
         print(json.dumps(r), flush=True)
-    (step if args.step else kernels)(args, emit)
+    (step if args.step else prefill if args.prefill else kernels)(args, emit)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text("\n".join(json.dumps(x) for x in lines) + "\n")
