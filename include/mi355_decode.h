@@ -48,7 +48,7 @@ extern "C" {
 #define MI_BF16 1
 #define MI_F16 2
 #define MI_U32 3 /* MLX-packed quantised weights: 32/bits codes per word, little-endian */
-#define MI_U8 4  /* the E8M0 scale bytes of an mxfp4 linear (quant_mode 1): byte s means 2^(s - 127) */
+#define MI_U8 4  /* the E8M0 scale bytes of an mxfp4 / mxfp8 linear (quant_mode 1 / 2): byte s means 2^(s - 127) */
 
 #define MI_ARCH_LLAMA 0 /* mlx_parallm/models/llama.py (also model_type "mistral": utils.py:33-36) */
 #define MI_ARCH_QWEN3 1 /* mlx_parallm/models/qwen3.py: + per-head q_norm/k_norm (qwen3.py:65-70) */
@@ -104,7 +104,15 @@ typedef struct mi_model_desc {
    *     naming the field; so is rope_traditional with a hidden_size that is no multiple of 64 (mi_engine_finalize regroups
    *     the q / k rows of scale bytes, hidden_size / 32 bytes each, in 16-bit units).  The embedding may be mxfp4 as well.  1..128 rows of the 16-bit mode run gemm_mx4.hip (K % 128 == 0),
    *     longer calls the prefill GEMM over an exact bf16 copy, float32 activations and other K the generic kernel.
-   *     LoRA rides beside such a base; DoRA and mi_lora_merge refuse it like every quantised base they do not read. */
+   *     LoRA rides beside such a base; DoRA and mi_lora_merge refuse it like every quantised base they do not read.
+   * 2 = mxfp8, the OCP Microscaling FP8 format: `.weight` MI_U32 [N][K / 4], code j of a row at byte j of its little-endian
+   *     stream, a code being OCP E4M3 ("fn": bit 7 the sign, four exponent bits with bias 7, three mantissa bits, subnormals,
+   *     largest value 448, 0x7f / 0xff NaN); `.scales` MI_U8 [N][K / 32] as for mxfp4; NO `.biases` (MI_ERR_INVALID).  Needs
+   *     quant_bits 8 and otherwise what mode 1 needs (quant_group_size 32, act_dtype MI_BF16, widths that are multiples of 32,
+   *     no MI_ARCH_MIXTRAL, hidden_size % 64 == 0 with rope_traditional).  The embedding may be mxfp8 as well.  1..128 rows of
+   *     the 16-bit mode run gemm_mx8.hip (K % 128 == 0), longer calls the prefill GEMM over an exact bf16 copy, float32
+   *     activations and other K the generic kernel.  On gemm_mx8.hip scale bytes 0..9 and 247..255 (products outside bf16's
+   *     normal range) and NaN codes are NOT pinned (include/mi355_ops.h).  LoRA, DoRA and mi_lora_merge as for mode 1. */
   int32_t quant_mode;
 } mi_model_desc;
 

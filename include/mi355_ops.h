@@ -89,6 +89,23 @@ extern "C" {
  * instruction and the MFMA make of them -- NOT pinned, and no test relies on it. */
 #define MI_WK_MX4_BF16 15
 #define MI_WK_MX4_F32 16
+/* mxfp8 (OCP Microscaling FP8, mi_model_desc.quant_mode 2): group = 32, biases = NULL.  Row-major (layout 0) `w` is uint32
+ * [N][K / 4] with code j of a row at byte j of the row's little-endian stream and `scales` is uint8 [N][K / 32], byte s =
+ * 2^(s - 127).  A code is OCP E4M3 ("fn"): bit 7 the sign, bits 3..6 the exponent (bias 7), bits 0..2 the mantissa, exponent
+ * field 0 subnormal (m x 2^-9), largest value 448, 0x7f / 0xff NaN.  _BF16 / _F32 as for mxfp4.  Tile-major (N % 16 == 0,
+ * K % 128 == 0) block (row / 16, k / 128) at ((row / 16) (K / 128) + k / 128) x 2112 bytes; lane l = 16 g + (row % 16) owns
+ * k % 128 = 32 T + 8 g + e:
+ *   [0, 2048)     codes, two halves of 1024: half T / 2 holds, at 16 l, the lane's 16 bytes, code e at byte 8 (T % 2) + e (the
+ *                 int8 layout of the group-32 / 128 kinds; a lane's two loads are 16-byte and lane-linear, and the two dwords of
+ *                 step T go through v_cvt_scalef32_pk_bf16_fp8, low and high word, into the eight values of an MFMA B operand)
+ *   [2048, 2112)  one dword per row r at 4 r: its four scale bytes in k order (byte T = the group of MFMA step T)
+ * mi_op_tiled_bytes is exactly N K + N K / 32 and the over-read rule of the mxfp4 kind holds: gemm_mx8.hip addresses blocks of
+ * the matrix only and clamps its prefetch.  mi_op_gemv's generic kernel, mi_op_embed and the prefill copy compute code x scale
+ * in float32 arithmetic, exact for every finite code (subnormal codes included).  NOT pinned on gemm_mx8.hip, which hands the
+ * conversion s << 23: scale bytes 0..9 and 247..255 (products leave bf16's normal range), and the NaN codes anywhere (the plain
+ * arithmetic reads them as +-480).  MI_WK_MX8_F32 runs on the generic kernels only. */
+#define MI_WK_MX8_BF16 17
+#define MI_WK_MX8_F32 18
 
 /* run-time logical rounding on top of the storage dtype */
 #define MI_RND_NONE 0
@@ -150,7 +167,9 @@ int mi_op_gemv_gu8(const mi_op_linear* w, const mi_op_gemv_args* a);
 int mi_op_gemv_bench(const mi_op_linear* w, const mi_op_gemv_args* a, int iters, float* avg_ms);
 /* the split-K weight-streaming GEMM the engine uses for decode steps of 9..128 rows (int4 / int8 weights: 1..128), on its own:
  * a->M in that range, a->pro = MI_PRO_NONE, tile-major 16-bit, int4 or int8 (group 64) weights; int4 / int8 in groups of 32 / 128 run gemm_qg.hip (1..128 rows, ksplit > 0
- * forces its K slices, echoed in *ksplit_used, as for 3 / 6 bits).  ksplit 0 = the library's
+ * forces its K slices, echoed in *ksplit_used, as for 3 / 6 bits); MI_WK_MX4_BF16 / MI_WK_MX8_BF16 (tile-major, group 32, bf16
+ * activations, 1..128 rows) run gemm_mx4.hip / gemm_mx8.hip under the same ksplit rule, anything else of those kinds is
+ * MI_ERR_UNSUPPORTED.  ksplit 0 = the library's
  * cost model (returned in *ksplit_used); iters >= 1 also times that many back-to-back launches into *avg_ms.
  * int4 weights above 16 rows with ksplit <= 0 run the round-4 kernel (gemm_q4.hip: x prepared once per launch, K split
  * over the waves of a workgroup; a->pro may then be MI_PRO_NORM); ksplit < 0 forces its plan for tests and A/B runs:

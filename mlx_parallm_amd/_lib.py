@@ -23,7 +23,7 @@ MI_MAX_ADAPTERS = 16
 MI_ABI_VERSION = 4
 WK = {"f32": 0, "bf16": 1, "f16": 2, "q4_f32": 3, "q4_bf16": 4, "q4_f16": 5, "q8_f32": 6, "q8_bf16": 7, "q8_f16": 8,
       "q3_f32": 9, "q3_bf16": 10, "q3_f16": 11, "q6_f32": 12, "q6_bf16": 13, "q6_f16": 14,
-      "mx4_bf16": 15, "mx4_f32": 16}
+      "mx4_bf16": 15, "mx4_f32": 16, "mx8_bf16": 17, "mx8_f32": 18}
 RND_NONE, RND_BF16, RND_F16 = 0, 1, 2
 PRO_NONE, PRO_NORM = 0, 1
 EPI_STORE, EPI_STORE_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3

@@ -107,6 +107,8 @@ def dequantize_model(weights: Dict[str, torch.Tensor], config: dict) -> Tuple[Di
     q = config.get("quantization")
     if not q:
         return dict(weights), copy.deepcopy(config)
+    if q.get("mode", "affine") != "affine":               # (mxfp4 / mxfp8 hold scale bytes and no biases: refused by name, not by a KeyError)
+        raise NotImplementedError(f"convert: a {q['mode']} checkpoint is not supported (MLX-affine triples only)")
     out: Dict[str, torch.Tensor] = {}
     for k, t in weights.items():
         if k.endswith(".scales") or k.endswith(".biases"):

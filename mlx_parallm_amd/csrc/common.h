@@ -200,16 +200,20 @@ enum : int {
   // the MODEL dtype: _BF16 runs with bf16 activations and, like the other _BF16 kinds, with float32 ones (PagedKVCache mode
   // of a bf16 model); _F32 with float32 activations only
   WK_MX4_BF16 = 15, WK_MX4_F32 = 16,
+  // mxfp8 (OCP Microscaling FP8: one E4M3 code byte per weight, the same scale bytes, no bias); suffixes as for mxfp4
+  WK_MX8_BF16 = 17, WK_MX8_F32 = 18,
 };
 inline bool wk_is_quant(int wk) { return wk >= WK_Q4_F32; }
 __host__ __device__ constexpr bool wk_is_mx4(int wk) { return wk == WK_MX4_BF16 || wk == WK_MX4_F32; }
+__host__ __device__ constexpr bool wk_is_mx8(int wk) { return wk == WK_MX8_BF16 || wk == WK_MX8_F32; }
+__host__ __device__ constexpr bool wk_is_mx(int wk) { return wk_is_mx4(wk) || wk_is_mx8(wk); }      // E8M0 scale bytes, no biases
 __host__ __device__ constexpr int wk_bits(int wk) {
-  return wk >= WK_MX4_BF16 ? 4 : wk >= WK_Q6_F32 ? 6 : wk >= WK_Q3_F32 ? 3 : wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0);
+  return wk >= WK_MX8_BF16 ? 8 : wk >= WK_MX4_BF16 ? 4 : wk >= WK_Q6_F32 ? 6 : wk >= WK_Q3_F32 ? 3 : wk >= WK_Q8_F32 ? 8 : (wk >= WK_Q4_F32 ? 4 : 0);
 }
 inline bool wk_is_q36(int wk) { return wk >= WK_Q3_F32 && wk <= WK_Q6_F16; }
 // base kind of a bit width (+ 0 / 1 / 2 for float32 / bf16 / f16 scales); -1: a width the kernels do not read
 inline int wk_base_of_bits(int bits) { return bits == 4 ? WK_Q4_F32 : bits == 8 ? WK_Q8_F32 : bits == 3 ? WK_Q3_F32 : bits == 6 ? WK_Q6_F32 : -1; }
-inline int wk_scale_dtype(int wk) { return wk_is_mx4(wk) ? (wk == WK_MX4_BF16 ? MI_BF16 : MI_F32) : wk_is_quant(wk) ? (wk - 3) % 3 : wk; }
+inline int wk_scale_dtype(int wk) { return wk_is_mx(wk) ? (wk == WK_MX4_BF16 || wk == WK_MX8_BF16 ? MI_BF16 : MI_F32) : wk_is_quant(wk) ? (wk - 3) % 3 : wk; }
 
 // mxfp4 in plain arithmetic (the generic kernels, the embedding gather, the prefill copy; gemm_mx4.hip converts in hardware).
 // A code: bit 3 the sign, bits 0..2 select {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- E2M1, whose two subnormals are 0 and 0.5.
@@ -222,5 +226,16 @@ __host__ __device__ inline float mx4_code_value(uint32_t c) {
 }
 __host__ __device__ inline float mx4_scale_value(uint32_t s) { return __builtin_bit_cast(float, s ? s << 23 : 0x00400000u); }
 __host__ __device__ inline float mx4_weight(uint32_t c, uint32_t s) { return mx4_code_value(c) * mx4_scale_value(s); }
+
+// mxfp8 likewise (gemm_mx8.hip converts in hardware).  A code byte is OCP E4M3 ("fn"): bit 7 the sign, bits 3..6 the exponent
+// (bias 7), bits 0..2 the mantissa; exponent field 0 is subnormal, m x 2^-9; the largest value is 448.  0x7f / 0xff (NaN) get no
+// special handling and read as +-480.  Four significant bits times a power of two: exact in float32 (down to 2^-136, a float32
+// subnormal, at scale byte 0) and, above 2^-126, in bf16.
+__host__ __device__ inline float mx8_code_value(uint32_t c) {
+  const uint32_t e = (c >> 3) & 15u, m = c & 7u;
+  const float mag = e ? __builtin_bit_cast(float, ((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+  return (c & 0x80u) ? -mag : mag;
+}
+__host__ __device__ inline float mx8_weight(uint32_t c, uint32_t s) { return mx8_code_value(c) * mx4_scale_value(s); }
 
 }  // namespace mi

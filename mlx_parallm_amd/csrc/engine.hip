@@ -573,16 +573,18 @@ int mi_engine_create(const mi_model_desc* desc, int device, mi_engine** out) {
     return fail(MI_ERR_UNSUPPORTED, "quant_bits " + std::to_string(d.quant_bits) + " needs quant_group_size 64 (groups of 32 / 128 are served at 4 and 8 bits only)");
   if ((d.quant_bits == 3 || d.quant_bits == 6) && (d.hidden_size % 32 || d.intermediate_size % 32 || (d.num_heads * d.head_dim) % 32))
     return fail(MI_ERR_UNSUPPORTED, "quant_bits " + std::to_string(d.quant_bits) + " needs hidden, intermediate and attention widths that are multiples of 32 (whole dwords per row)");
-  if (d.quant_mode != 0 && d.quant_mode != 1) return fail(MI_ERR_UNSUPPORTED, "quant_mode must be 0 (affine) or 1 (mxfp4)");
-  if (d.quant_mode == 1) {      // mxfp4: E2M1 codes, one E8M0 scale byte per 32, no biases (gemm_mx4.hip; the header has the format)
-    if (d.quant_bits != 4) return fail(MI_ERR_UNSUPPORTED, "quant_mode 1 (mxfp4) needs quant_bits 4");
-    if (d.quant_group_size != 32) return fail(MI_ERR_UNSUPPORTED, "quant_mode 1 (mxfp4) needs quant_group_size 32");
-    if (d.act_dtype != MI_BF16) return fail(MI_ERR_UNSUPPORTED, "quant_mode 1 (mxfp4) needs act_dtype MI_BF16 (the dequantised weights are bf16 values)");
-    if (d.arch == MI_ARCH_MIXTRAL) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: quant_mode 1 (mxfp4) is not supported (the grouped expert kernels read affine int4 and int8 only)");
+  if (d.quant_mode < 0 || d.quant_mode > 2) return fail(MI_ERR_UNSUPPORTED, "quant_mode must be 0 (affine), 1 (mxfp4) or 2 (mxfp8)");
+  if (d.quant_mode != 0) {      // mxfp4 / mxfp8: E2M1 / E4M3 codes, one E8M0 scale byte per 32, no biases (gemm_mx4.hip, gemm_mx8.hip; the header has the formats)
+    const std::string mode = d.quant_mode == 1 ? "quant_mode 1 (mxfp4)" : "quant_mode 2 (mxfp8)";
+    const int bits = d.quant_mode == 1 ? 4 : 8;
+    if (d.quant_bits != bits) return fail(MI_ERR_UNSUPPORTED, mode + " needs quant_bits " + std::to_string(bits));
+    if (d.quant_group_size != 32) return fail(MI_ERR_UNSUPPORTED, mode + " needs quant_group_size 32");
+    if (d.act_dtype != MI_BF16) return fail(MI_ERR_UNSUPPORTED, mode + " needs act_dtype MI_BF16 (the dequantised weights are bf16 values)");
+    if (d.arch == MI_ARCH_MIXTRAL) return fail(MI_ERR_UNSUPPORTED, "arch mixtral: " + mode + " is not supported (the grouped expert kernels read affine int4 and int8 only)");
     if (d.hidden_size % 32 || d.intermediate_size % 32 || (d.num_heads * d.head_dim) % 32)
-      return fail(MI_ERR_UNSUPPORTED, "quant_mode 1 (mxfp4) needs hidden_size, intermediate_size and num_heads x head_dim to be multiples of 32 (whole groups per row)");
+      return fail(MI_ERR_UNSUPPORTED, mode + " needs hidden_size, intermediate_size and num_heads x head_dim to be multiples of 32 (whole groups per row)");
     if (d.rope_traditional && d.hidden_size % 64)
-      return fail(MI_ERR_UNSUPPORTED, "quant_mode 1 (mxfp4) with rope_traditional needs hidden_size to be a multiple of 64 (the q / k scale rows are regrouped in 16-bit units)");
+      return fail(MI_ERR_UNSUPPORTED, mode + " with rope_traditional needs hidden_size to be a multiple of 64 (the q / k scale rows are regrouped in 16-bit units)");
   }
   if (d.hidden_size % 8 || d.intermediate_size % 8 || (d.num_heads * d.head_dim) % 8)
     return fail(MI_ERR_UNSUPPORTED, "hidden / intermediate sizes must be multiples of 8");

@@ -190,6 +190,19 @@ int route_mx4(const Lin& a) {
   return launch_gemm_mx4(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
 }
 
+// 1e. mxfp8 weights likewise: the FP8 streaming kernel (gemm_mx8.hip).  Every call of more than 128 rows goes to the prefill
+// GEMM over the bf16 copy (there is no packed mxfp8 tile in gemm_qtile.hip).
+int route_mx8(const Lin& a) {
+  mi_engine* e = a.e;
+  if (!(e->opt_skinny_gemm && a.rows <= 128 && gemm_mx8_supported(a.f.W, a.c, a.rows))) return NOT_TAKEN;
+  Prof pr(e, a.prof);
+  GemvCall c = a.c;
+  c.M = (int)a.rows;
+  if (c.pro == PRO_NORM) MI_TRY(norm_into_xn(e, c, a.rows, a.KT(), c.rnd));
+  MI_TRY(ensure_skinny_ws(e, gemm_mx8_ws_bytes(a.f.W, c, a.rows), gemm_mx8_groups(a.f.W, c, a.rows)));
+  return launch_gemm_mx8(a.f.W, c, a.rows, e->stream, e->sk_ws, e->sk_ctr);
+}
+
 // float32-KV decode step of <= 8 sequences: what routes 2 and 3 share
 bool f32_decode(const Lin& a) {
   return a.e->opt_skinny_gemm && a.e->cur_L == 1 && a.rows <= 8 && a.c.act == MI_F32 && a.c.rnd == RND_NONE && a.c.kx == 0;
@@ -395,6 +408,7 @@ int gemv_rows_on(const Lin& a) {
   if ((rc = route_q36(a)) != NOT_TAKEN) return rc;
   if ((rc = route_qg(a)) != NOT_TAKEN) return rc;
   if ((rc = route_mx4(a)) != NOT_TAKEN) return rc;
+  if ((rc = route_mx8(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_wide(a)) != NOT_TAKEN) return rc;
   if ((rc = route_f32_whole(a)) != NOT_TAKEN) return rc;
   if ((rc = route_skinny(a)) != NOT_TAKEN) return rc;

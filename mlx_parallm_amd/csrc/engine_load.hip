@@ -48,12 +48,12 @@ int set_linear(mi_engine* e, FusedLinear& f, int part, int K, int kind, const vo
     f.seen_w[part] = 1;
   } else {
     if (d.quant_bits == 0) return fail(MI_ERR_INVALID, name + ": scales/biases but desc.quant_bits == 0");
-    if (d.quant_mode == 1 && kind == 2) return fail(MI_ERR_INVALID, name + ": an mxfp4 linear (quant_mode 1) has no biases");
+    if (d.quant_mode != 0 && kind == 2) return fail(MI_ERR_INVALID, name + ": an mxfp4 / mxfp8 linear (quant_mode 1 / 2) has no biases");
     if (K % d.quant_group_size != 0) return fail(MI_ERR_INVALID, name + ": K not divisible by the group size");
     const int64_t cols = K / d.quant_group_size;
     if (shape[1] != cols) return fail(MI_ERR_INVALID, name + ": wrong number of groups");
-    if (d.quant_mode == 1 ? dtype != MI_U8 : (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16))
-      return fail(MI_ERR_INVALID, name + (d.quant_mode == 1 ? ": mxfp4 scales are MI_U8 (one E8M0 byte per group)" : ": bad dtype"));
+    if (d.quant_mode != 0 ? dtype != MI_U8 : (dtype != MI_F32 && dtype != MI_BF16 && dtype != MI_F16))
+      return fail(MI_ERR_INVALID, name + (d.quant_mode != 0 ? ": mxfp4 / mxfp8 scales are MI_U8 (one E8M0 byte per group)" : ": bad dtype"));
     if (f.scale_dtype >= 0 && f.scale_dtype != dtype) return fail(MI_ERR_UNSUPPORTED, name + ": mixed scale dtypes");
     f.scale_dtype = dtype;
     const size_t row_bytes = (size_t)cols * dtype_size(dtype);
@@ -139,7 +139,7 @@ int permute_qk_heads(mi_engine* e, FusedLinear& f) {
   const size_t nrows = (size_t)f.part_rows[0] + f.part_rows[1];
   const int D = e->d.head_dim;
   MI_TRY(head_perm_inplace(e, f.w, nrows, D, f.w_bytes / total));
-  if (f.quant && f.scales != nullptr && (f.biases != nullptr || e->d.quant_mode == 1)) {      // (mxfp4: scale bytes, no biases)
+  if (f.quant && f.scales != nullptr && (f.biases != nullptr || e->d.quant_mode != 0)) {      // (mxfp4 / mxfp8: scale bytes, no biases)
     MI_TRY(head_perm_inplace(e, f.scales, nrows, D, f.s_bytes / total));
     if (f.biases != nullptr) MI_TRY(head_perm_inplace(e, f.biases, nrows, D, f.s_bytes / total));
   }
@@ -153,12 +153,12 @@ int finalize_linear(mi_engine* e, FusedLinear& f, int K, const std::string& name
   for (int i = 0; i < f.n_parts; ++i) {
     total += f.part_rows[i];
     if (!f.seen_w[i]) return fail(MI_ERR_NOTFOUND, name + ": weight not set");
-    const bool mx4 = e->d.quant_mode == 1;                 // (mxfp4 has no biases to ask for)
+    const bool mx4 = e->d.quant_mode != 0;                 // (mxfp4 / mxfp8 have no biases to ask for)
     if (f.quant && (!f.seen_s[i] || (!mx4 && !f.seen_b[i]))) return fail(MI_ERR_NOTFOUND, name + (mx4 ? ": scales not set" : ": scales/biases not set"));
   }
-  if (f.quant && e->d.quant_mode != 1 && f.scale_dtype != e->d.act_dtype)
+  if (f.quant && e->d.quant_mode == 0 && f.scale_dtype != e->d.act_dtype)
     return fail(MI_ERR_UNSUPPORTED, name + ": scale dtype differs from the model dtype");
-  f.W.wk = f.quant && e->d.quant_mode == 1 ? WK_MX4_BF16 : kind_of(f, e->d.quant_bits);      // (mi_engine_create: a bf16 model)
+  f.W.wk = f.quant && e->d.quant_mode == 1 ? WK_MX4_BF16 : f.quant && e->d.quant_mode == 2 ? WK_MX8_BF16 : kind_of(f, e->d.quant_bits);      // (mi_engine_create: a bf16 model)
   f.W.w = f.w; f.W.scales = f.scales; f.W.biases = f.biases;
   f.W.N = total; f.W.K = K; f.W.group = e->d.quant_group_size > 0 ? e->d.quant_group_size : 64;
   f.W.bias = f.bias;

@@ -883,10 +883,10 @@ bool gemm_prefill_supported(const LinearW& W, const GemvCall& c, size_t rows) {
   // float32 activations on a bf16 model (PagedKVCache mode): x goes through launch_split3_rows first
   const bool x32 = c.act == MI_F32 && (W.wk == WK_BF16 || (W.wk == WK_Q4_BF16 && (W.group == 64 || qg) && W.K % 128 == 0) || q36_bf16) &&
                    c.ldx % 4 == 0 && W.K % 4 == 0;
-  // mxfp4: through an exact ONE-term bf16 copy (launch_dequant_mx4): the GEMM then sees a dense bf16 matrix, K not 2 K;
-  // float32 activations keep their exact three-term split
-  const bool mx4 = wk_is_mx4(W.wk) && W.group == 32 && W.K % 128 == 0 &&
-                   ((W.wk == WK_MX4_BF16 && c.act == MI_BF16) || (c.act == MI_F32 && c.ldx % 4 == 0));
+  // mxfp4 / mxfp8: through an exact ONE-term bf16 copy (launch_dequant_mx4 / _mx8): the GEMM then sees a dense bf16 matrix,
+  // K not 2 K; float32 activations keep their exact three-term split
+  const bool mx4 = wk_is_mx(W.wk) && W.group == 32 && W.K % 128 == 0 &&
+                   ((wk_scale_dtype(W.wk) == MI_BF16 && c.act == MI_BF16) || (c.act == MI_F32 && c.ldx % 4 == 0));
   if (!dense && !q4 && !q8 && !q36 && !x32 && !mx4) return false;
   if (W.K % BK != 0 || (c.act != MI_F32 && c.ldx % 8 != 0)) return false;
   // a [hi | lo] copy of an f16 matrix: the x terms are kx wide each and the walk wraps at whole K tiles of them (the engine
@@ -942,11 +942,11 @@ int launch_gemm_prefill(const LinearW& W, const GemvCall& c, size_t rows, hipStr
   GemmParams p{};
   p.ksplit = 1;
   p.x = c.x; p.ldx = c.ldx; p.M = (int)rows; p.w = W.w; p.N = W.N; p.K = W.K; p.ka = W.K; p.kw = W.K;
-  const bool mx4 = wk_is_mx4(W.wk);
+  const bool mx4 = wk_is_mx(W.wk);         // (mxfp8 as well)
   if (wk_is_quant(W.wk)) {
     if (scratch == nullptr) return fail(MI_ERR_INVALID, "gemm_prefill: int4 weights need a dequantisation scratch buffer");
     if (mx4) {                               // one exact bf16 term: a dense matrix of W.K columns from here on
-      MI_TRY(launch_dequant_mx4(W, scratch, st));
+      MI_TRY(wk_is_mx8(W.wk) ? launch_dequant_mx8(W, scratch, st) : launch_dequant_mx4(W, scratch, st));
       p.w = scratch;
     } else {
       MI_TRY(launch_dequant_q4_hilo(W, scratch, st));

@@ -61,6 +61,12 @@ __device__ __forceinline__ void load8(const GemvParams& p, int row, int kb, floa
     const uint32_t v = mx4_word(p.w, p.layout, row, kb, p.K), s = mx4_scale_byte(p.w, p.scales, p.layout, row, kb, p.K);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = mx4_weight(v >> (4 * j), s);
+  } else if constexpr (WK == WK_MX8_BF16 || WK == WK_MX8_F32) {
+    // mxfp8, either layout: E4M3 code x 2^(s - 127) in plain float32, exact (subnormal codes included)
+    const uint32_t v[2] = {mx8_word(p.w, p.layout, row, kb, p.K), mx8_word(p.w, p.layout, row, kb + 4, p.K)};
+    const uint32_t s = mx8_scale_byte(p.w, p.scales, p.layout, row, kb, p.K);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = mx8_weight((v[j >> 2] >> (8 * (j & 3))) & 0xffu, s);
   } else if constexpr (WK >= WK_Q3_F32) {
     // 3 / 6 bits: the tile-major bit planes (repack.hip), or the checkpoint's bit stream, whose codes straddle dwords
     constexpr int BITS = wk_bits(WK);
@@ -319,6 +325,8 @@ int launch_wk(int wk, const GemvParams& p, hipStream_t st) {
     case WK_Q6_F16: if constexpr (F32A || std::is_same<AT, f16>::value) return launch_mt<AT, WK_Q6_F16>(p, st); break;
     case WK_MX4_BF16: if constexpr (F32A || std::is_same<AT, bf16>::value) return launch_mt<AT, WK_MX4_BF16>(p, st); break;
     case WK_MX4_F32: if constexpr (F32A) return launch_mt<AT, WK_MX4_F32>(p, st); break;
+    case WK_MX8_BF16: if constexpr (F32A || std::is_same<AT, bf16>::value) return launch_mt<AT, WK_MX8_BF16>(p, st); break;
+    case WK_MX8_F32: if constexpr (F32A) return launch_mt<AT, WK_MX8_F32>(p, st); break;
   }
   return fail(MI_ERR_UNSUPPORTED, "gemv: weight kind / activation dtype combination not supported");
 }
@@ -341,7 +349,7 @@ int launch_gemv_v1(const LinearW& W, const GemvCall& c, hipStream_t st) {
   if (W.K % 8 != 0) return fail(MI_ERR_UNSUPPORTED, "gemv: K must be a multiple of 8");
   if (wk_is_quant(W.wk) && (W.group % 8 != 0 || W.K % W.group != 0))
     return fail(MI_ERR_UNSUPPORTED, "gemv: bad quantisation group size");
-  if (wk_is_mx4(W.wk) && (W.group != 32 || W.biases != nullptr)) return fail(MI_ERR_INVALID, "gemv: mxfp4 weights have groups of 32 and no biases");
+  if (wk_is_mx(W.wk) && (W.group != 32 || W.biases != nullptr)) return fail(MI_ERR_INVALID, "gemv: mxfp4 / mxfp8 weights have groups of 32 and no biases");
   if (wk_is_q36(W.wk) && W.K % 32 != 0) return fail(MI_ERR_UNSUPPORTED, "gemv: 3- / 6-bit rows must be whole dwords (K % 32 == 0)");
   if (c.epi == EPI_SWIGLU && c.pair_offset * 2 != W.N) return fail(MI_ERR_INVALID, "gemv: swiglu needs N = 2*pair_offset");
   GemvParams p = make_params(W, c);

@@ -276,6 +276,36 @@ int launch_gemm_mx4(const LinearW& W, const GemvCall& c, size_t rows, hipStream_
 // tile-major mxfp4 -> tile-major dense bf16 (N x K), exact: the prefill GEMM's operand (repack.hip); dst: N K 2 bytes
 int launch_dequant_mx4(const LinearW& src, void* dst, hipStream_t st);
 
+// ---- mxfp8 (include/mi355_ops.h has the layout): block (row tile, k / 128) = 2048 bytes of E4M3 codes in the two halves of the
+// int8 blocks above (half T / 2, bytes 8 (T % 2) + e of the lane's 16), then one dword of four scale bytes per row.
+// mx8_word (the codes k .. k + 4, k % 4 == 0, code e at byte e) / mx8_scale_byte read either layout (the generic kernels).
+constexpr int MX8_BLOCK = 2112;
+__host__ __device__ inline size_t tiled_block_mx8(size_t row, int k, int K) {
+  return ((row >> 4) * (size_t)(K / 128) + (size_t)(k >> 7)) * MX8_BLOCK;
+}
+__host__ __device__ inline int tiled_mx8_code_off(size_t row, int k) {      // of the code byte of (row, k)
+  const int T = (k >> 5) & 3, lane = ((k >> 3) & 3) * 16 + (int)(row & 15);
+  return (T >> 1) * 1024 + lane * 16 + (T & 1) * 8 + (k & 7);
+}
+__host__ __device__ inline int tiled_mx8_scale_off(size_t row, int k) { return 2048 + (int)(row & 15) * 4 + ((k >> 5) & 3); }
+__host__ __device__ inline uint32_t mx8_word(const void* w, int layout, size_t row, int k, int K) {
+  if (layout) return *(const uint32_t*)((const uint8_t*)w + tiled_block_mx8(row, k, K) + tiled_mx8_code_off(row, k));
+  return ((const uint32_t*)w)[row * (size_t)(K / 4) + (k >> 2)];
+}
+__host__ __device__ inline uint32_t mx8_scale_byte(const void* w, const void* scales, int layout, size_t row, int k, int K) {
+  if (layout) return ((const uint8_t*)w)[tiled_block_mx8(row, k, K) + tiled_mx8_scale_off(row, k)];
+  return ((const uint8_t*)scales)[row * (size_t)(K / 32) + (k >> 5)];
+}
+
+// mxfp8 weights (tile-major), 1..128 rows of bf16 activations (gemm_mx8.hip): the contract of gemm_mx4
+bool gemm_mx8_supported(const LinearW& W, const GemvCall& c, size_t rows);
+int gemm_mx8_ksplit(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+size_t gemm_mx8_ws_bytes(const LinearW& W, const GemvCall& c, size_t rows, int ksplit = 0);
+int gemm_mx8_groups(const LinearW& W, const GemvCall& c, size_t rows);
+int launch_gemm_mx8(const LinearW& W, const GemvCall& c, size_t rows, hipStream_t st, void* ws, unsigned* ctr, int ksplit = 0);
+// tile-major mxfp8 -> tile-major dense bf16 (N x K), exact: the prefill GEMM's operand above 128 rows (repack.hip); dst: N K 2 bytes
+int launch_dequant_mx8(const LinearW& src, void* dst, hipStream_t st);
+
 // ---- lora_rows.hip (the LoRA launches themselves: lora_rows.h)
 // out[m][n] = T(T(g * T(sigmoid(g))) * u) with g = x[m][n], u = x[m][I + n]: the SwiGLU of a gate|up output stored by an
 // EPI_STORE launch (an adapted gate|up), rounding points of EPI_SWIGLU.  I % 8 == 0, ldx >= 2 I, ldo >= I, any M, one launch.

@@ -51,6 +51,8 @@ __global__ __launch_bounds__(256) void embed_kernel(LinearW W, EmbedCall c) {
                    : (float)((const f16*)W.w)[(size_t)tok * W.K + k];
     else if constexpr (WK == WK_MX4_BF16 || WK == WK_MX4_F32)      // mxfp4, either layout: code x 2^(s - 127), exact
       v = mx4_weight(mx4_word(W.w, W.layout, tok, k8, W.K) >> (4 * (k & 7)), mx4_scale_byte(W.w, W.scales, W.layout, tok, k, W.K));
+    else if constexpr (WK == WK_MX8_BF16 || WK == WK_MX8_F32)      // mxfp8, either layout: E4M3 code x 2^(s - 127), exact
+      v = mx8_weight((mx8_word(W.w, W.layout, tok, k & ~3, W.K) >> (8 * (k & 3))) & 0xffu, mx8_scale_byte(W.w, W.scales, W.layout, tok, k, W.K));
     else if constexpr (WK >= WK_Q3_F32) {
       // 3 / 6 bits: 32 / BITS codes per word does not hold -- the tile-major bit planes, or the straddling bit stream
       constexpr int BITS = wk_bits(WK);
@@ -131,6 +133,8 @@ int launch_embed_wk(const LinearW& W, const EmbedCall& c, hipStream_t st) {
     case WK_Q6_F16: EK(WK_Q6_F16);
     case WK_MX4_BF16: EK(WK_MX4_BF16);
     case WK_MX4_F32: EK(WK_MX4_F32);
+    case WK_MX8_BF16: EK(WK_MX8_BF16);
+    case WK_MX8_F32: EK(WK_MX8_F32);
     default: return fail(MI_ERR_UNSUPPORTED, "embed: bad weight kind");
   }
 #undef EK

@@ -1,4 +1,5 @@
-// mx4_cvt.h -- the FP4 (E2M1) -> bf16 conversion that the mxfp4 kernels share (gemm_mx4.hip: 1..128 rows; gemm_qtile.hip: prefill).
+// mx4_cvt.h -- the conversions of MX codes to bf16 that the Microscaling kernels share: FP4 (E2M1) for gemm_mx4.hip (1..128 rows)
+// and gemm_qtile.hip (prefill), FP8 (E4M3) for gemm_mx8.hip.
 #pragma once
 
 #include "mfma16.h"
@@ -15,6 +16,17 @@ __device__ __forceinline__ u32x4 mx_operand(uint32_t dw, float scale) {
   r.y = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 1));
   r.z = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 2));
   r.w = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 3));
+  return r;
+}
+
+// the same operand from E4M3 codes: the eight code bytes of `lo` (e = 0..3) and `hi` (e = 4..7), code e at byte e % 4 -- four
+// v_cvt_scalef32_pk_bf16_fp8, the low and the high word of each dword
+__device__ __forceinline__ u32x4 mx8_operand(uint32_t lo, uint32_t hi, float scale) {
+  u32x4 r;
+  r.x = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, false));
+  r.y = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, true));
+  r.z = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, false));
+  r.w = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, true));
   return r;
 }
 

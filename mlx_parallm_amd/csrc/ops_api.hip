@@ -235,6 +235,18 @@ int mi_op_gemm_skinny(const mi_op_linear* w, const mi_op_gemv_args* a, int kspli
     if (ksplit_used) *ksplit_used = ks;
     return run_timed([&] { return launch_gemm_mx4(W, c, (size_t)c.M, nullptr, ws, (unsigned*)ctr, ksplit); }, iters, avg_ms);
   }
+  if (wk_is_mx8(W.wk)) {                         // mxfp8: gemm_mx8.hip (ksplit > 0 forces its K slices)
+    if (ksplit < 0 || !gemm_mx8_supported(W, c, (size_t)c.M) || c.pro != PRO_NONE)
+      return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: mxfp8 weights (MI_WK_MX8_BF16, group 32) take 1..128 rows of bf16 activations, tile-major, no prologue");
+    const int ks = gemm_mx8_ksplit(W, c, (size_t)c.M, ksplit), groups = gemm_mx8_groups(W, c, (size_t)c.M);
+    void* ws = nullptr; void* ctr = nullptr;
+    FreeGuard g_ws{ws}, g_ctr{ctr};
+    MI_HIP(hipMalloc(&ws, std::max<size_t>(1024, gemm_mx8_ws_bytes(W, c, (size_t)c.M, ksplit))));
+    MI_HIP(hipMalloc(&ctr, (size_t)groups * sizeof(unsigned)));
+    MI_HIP(hipMemset(ctr, 0, (size_t)groups * sizeof(unsigned)));
+    if (ksplit_used) *ksplit_used = ks;
+    return run_timed([&] { return launch_gemm_mx8(W, c, (size_t)c.M, nullptr, ws, (unsigned*)ctr, ksplit); }, iters, avg_ms);
+  }
   if (!gemm_skinny_supported(W, c, (size_t)c.M) && !gemm_q4_supported(W, c, (size_t)c.M))
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_skinny: call not supported by this kernel");
   const int groups = std::max(1, gemm_skinny_groups(W, c, (size_t)c.M));
@@ -260,7 +272,7 @@ int mi_op_gemm_prefill(const mi_op_linear* w, const mi_op_gemv_args* a, int iter
   if (c.act == MI_F32)
     return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: 16-bit activations only (float32 activations: mi_op_gemm_prefill_f32)");
   if (c.M < 1 || c.pro != PRO_NONE || W.layout != 1 || (wk_is_quant(W.wk) && !gemm_prefill_supported(W, c, (size_t)c.M)))
-    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int3 / int6 (group 64), int4 / int8 (group 32, 64, 128) or mxfp4 weights, 16-bit activations, no prologue");
+    return fail(MI_ERR_UNSUPPORTED, "mi_op_gemm_prefill: tile-major dense 16-bit, int3 / int6 (group 64), int4 / int8 (group 32, 64, 128), mxfp4 or mxfp8 weights, 16-bit activations, no prologue");
   void* ws = nullptr; void* scratch = nullptr; size_t cap = 0;
   FreeGuard g_ws{ws}, g_scratch{scratch};
   if (wk_is_quant(W.wk)) MI_HIP(hipMalloc(&scratch, dequant_hilo_bytes(W.N, W.K)));

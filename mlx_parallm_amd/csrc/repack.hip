@@ -30,6 +30,9 @@
 //   mxfp4:        block (i, j = k/128) of 1088 bytes: [0,1024) codes, lane l = g*16 + r owns k%128 = 32T + 8g + e in dword T of
 //                 its 16 bytes with code e at nibble e (the checkpoint's order); [1024,1088) row r -> its four E8M0 scale bytes in
 //                 k order.  No biases.   (kernels.h: tiled_*_mx4; gemm_mx4.hip reads them)
+//   mxfp8:        block (i, j = k/128) of 2112 bytes: [0,2048) E4M3 codes as the int8 codes above (lane l = g*16 + r, bytes
+//                 8 (T%2) + e of its 16 in the half T/2, e in the checkpoint's byte order); [2048,2112) row r -> its four E8M0
+//                 scale bytes in k order.  No biases.   (kernels.h: tiled_*_mx8; gemm_mx8.hip reads them)
 #include "kernels.h"
 
 namespace mi {
@@ -313,6 +316,44 @@ __global__ void dequant_mx4_kernel(const uint8_t* src, __bf16* dst, int N, int K
   }
 }
 
+// mxfp8: one thread per (block, lane).  The checkpoint's dwords (row, k / 4) hold code e at byte e, the order in which
+// v_cvt_scalef32_pk_bf16_fp8 takes the low and the high word of a dword, so the codes move as whole dwords: the two of MFMA step
+// T (k = 128 j + 32 T + 8 g + 0..7) go to bytes 8 (T % 2) .. + 8 of the lane's 16 in half T / 2.  Scale bytes as for mxfp4.
+__global__ void repack_mx8_kernel(const uint32_t* codes, const uint8_t* scales, uint8_t* dst, int N, int K) {
+  const int nb = K / 128;
+  const size_t blocks = (size_t)(N / 16) * nb;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < blocks * 64; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / nb, j = blk % nb;
+    const size_t row = i * 16 + r;
+    uint8_t* base = dst + blk * MX8_BLOCK;
+    const uint32_t* s0 = codes + row * (K / 4) + j * 32 + g * 2;          // dwords 8 T, 8 T + 1 = codes k = 128 j + 32 T + 8 g + e
+    *(u32x4*)(base + lane * 16) = u32x4{s0[0], s0[1], s0[8], s0[9]};
+    *(u32x4*)(base + 1024 + lane * 16) = u32x4{s0[16], s0[17], s0[24], s0[25]};
+    if (g == 0) *(uint32_t*)(base + 2048 + r * 4) = *(const uint32_t*)(scales + row * (K / 32) + j * 4);
+  }
+}
+
+// tile-major mxfp8 -> tile-major dense bf16, the sibling of dequant_mx4_kernel: an E4M3 code has four significant bits, so ONE
+// bf16 term is the exact weight here as well
+__global__ void dequant_mx8_kernel(const uint8_t* src, __bf16* dst, int N, int K) {
+  const size_t pieces = (size_t)N * (K / 8);
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < pieces; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t blk = idx >> 6;
+    const int lane = (int)(idx & 63), r = lane & 15, g = lane >> 4;
+    const size_t i = blk / (K / 32), j = blk % (K / 32);
+    const size_t row = i * 16 + r;
+    const int k = (int)j * 32 + g * 8;
+    const uint32_t v[2] = {mx8_word(src, 1, row, k, K), mx8_word(src, 1, row, k + 4, K)};
+    const uint32_t s = mx8_scale_byte(src, nullptr, 1, row, k, K);
+    __bf16 o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (__bf16)mx8_weight((v[e >> 2] >> (8 * (e & 3))) & 0xffu, s);
+    *(u32x4*)(dst + idx * 8) = *(const u32x4*)o;
+  }
+}
+
 }  // namespace
 
 size_t dequant_hilo_bytes(int N, int K) { return (size_t)N * K * 2 * 2; }
@@ -321,6 +362,14 @@ int launch_dequant_mx4(const LinearW& src, void* dst, hipStream_t st) {
   if (src.layout != 1 || !wk_is_mx4(src.wk) || src.group != 32 || src.K % 128 != 0 || src.N % 16 != 0)
     return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major mxfp4 matrices (group 32) only");
   hipLaunchKernelGGL(dequant_mx4_kernel, dim3(4096), dim3(256), 0, st, (const uint8_t*)src.w, (__bf16*)dst, src.N, src.K);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int launch_dequant_mx8(const LinearW& src, void* dst, hipStream_t st) {
+  if (src.layout != 1 || !wk_is_mx8(src.wk) || src.group != 32 || src.K % 128 != 0 || src.N % 16 != 0)
+    return fail(MI_ERR_UNSUPPORTED, "dequant: tile-major mxfp8 matrices (group 32) only");
+  hipLaunchKernelGGL(dequant_mx8_kernel, dim3(4096), dim3(256), 0, st, (const uint8_t*)src.w, (__bf16*)dst, src.N, src.K);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
@@ -364,7 +413,7 @@ bool tiled_supported(int wk, int N, int K, int group) {
   if (N % 16 != 0) return false;
   if (wk == WK_BF16 || wk == WK_F16) return K % 32 == 0;
   if (wk_is_qg(wk, group)) return K % 128 == 0;
-  if (wk_is_mx4(wk)) return group == 32 && K % 128 == 0;
+  if (wk_is_mx(wk)) return group == 32 && K % 128 == 0;
   if (wk == WK_Q4_BF16 || wk == WK_Q4_F16) return group == 64 && K % 128 == 0;
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return group == 64 && K % 64 == 0;
   if (wk_is_q36(wk) && wk_scale_dtype(wk) != MI_F32) return group == 64 && K % 128 == 0;
@@ -376,6 +425,7 @@ size_t tiled_bytes(int wk, int N, int K, int group) {
   // (groups of 32 / 128: packed, no padding -- gemm_qg.hip clamps its prefetch as gemm_q36.hip does)
   if (wk_is_qg(wk, group)) return (size_t)(N / 16) * (K / 128) * qg_block_bytes(wk_bits(wk), group);
   if (wk_is_mx4(wk)) return (size_t)(N / 16) * (K / 128) * MX4_BLOCK;      // (N K / 2 + N K / 32: gemm_mx4.hip clamps as well)
+  if (wk_is_mx8(wk)) return (size_t)(N / 16) * (K / 128) * MX8_BLOCK;      // (N K + N K / 32: gemm_mx8.hip clamps as well)
   if (wk == WK_Q8_BF16 || wk == WK_Q8_F16) return (size_t)(N / 16) * (K / 64) * 1088;
   // (int3 / int6: the codes' bits + scales + biases and not a byte more -- gemm_q36.hip clamps its prefetch)
   if (wk_is_q36(wk)) return (size_t)(N / 16) * (K / 128) * q36_block_bytes(wk_bits(wk));
@@ -392,6 +442,8 @@ int launch_repack_tiled(const LinearW& src, void* dst, hipStream_t st) {
     hipLaunchKernelGGL(repack_dense16_kernel, grid, block, 0, st, (const uint16_t*)src.w, (uint16_t*)dst, src.N, src.K);
   else if (wk_is_mx4(src.wk))
     hipLaunchKernelGGL(repack_mx4_kernel, grid, block, 0, st, (const uint32_t*)src.w, (const uint8_t*)src.scales, (uint8_t*)dst, src.N, src.K);
+  else if (wk_is_mx8(src.wk))
+    hipLaunchKernelGGL(repack_mx8_kernel, grid, block, 0, st, (const uint32_t*)src.w, (const uint8_t*)src.scales, (uint8_t*)dst, src.N, src.K);
   else if (wk_is_qg(src.wk, src.group) && wk_bits(src.wk) == 4)
     hipLaunchKernelGGL(repack_qg_kernel<4>, grid, block, 0, st, (const uint32_t*)src.w, (const uint16_t*)src.scales,
                        (const uint16_t*)src.biases, (uint8_t*)dst, src.N, src.K, src.group);

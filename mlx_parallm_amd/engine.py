@@ -339,9 +339,11 @@ class Engine:
         d.quant_bits = int(q["bits"]) if q else 0
         d.quant_group_size = int(q["group_size"]) if q else 0
         mode = q.get("mode", "affine") if q else "affine"                           # utils.py:679-690 hands the dict to nn.quantize
-        if mode not in ("affine", "mxfp4"):
-            raise NotImplementedError(f"quantization mode {mode!r} is not supported (affine and mxfp4 are)")
-        d.quant_mode = int(mode == "mxfp4")
+        if mode not in ("affine", "mxfp4", "mxfp8"):
+            raise NotImplementedError(f"quantization mode {mode!r} is not supported (affine, mxfp4 and mxfp8 are)")
+        if mode != "affine" and d.quant_bits != {"mxfp4": 4, "mxfp8": 8}[mode]:
+            raise NotImplementedError(f"quantization mode {mode!r} needs bits {4 if mode == 'mxfp4' else 8}, got {d.quant_bits}")
+        d.quant_mode = {"affine": 0, "mxfp4": 1, "mxfp8": 2}[mode]
         d.max_positions = int(max_positions or min(int(config.get("max_position_embeddings", 4096)), 32768))
         d.attention_bias = int(bool(config.get("attention_bias", False)))            # llama.py:59-67
         d.mlp_bias = int(bool(config.get("mlp_bias", False)))                        # llama.py:155-162

@@ -105,6 +105,44 @@ def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor
     return (v.reshape(n, k // 32, 32) * s[..., None]).reshape(n, k).to(torch.float32)
 
 
+# ---- mode "mxfp8": OCP Microscaling FP8 -- one E4M3 ("fn") code byte per weight (sign, four exponent bits with bias 7, three
+# mantissa bits, subnormals m x 2^-9, largest value 448, 0x7f / 0xff NaN), code j of a row at byte j like affine int8, the same
+# E8M0 scale bytes, no bias.
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e in float64 for integer e in float64's normal range, exactly (torch.exp2 is not exact everywhere)"""
+    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def quantize_mxfp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w (N, K) float, K % 32 == 0 -> (packed int32 (N, K/4), scales uint8 (N, K/32)).  Scale = 2^(floor(log2 max|w|) - 8) per
+    group (E4M3's largest exponent is 8), clamped to E8M0's bytes 0..254; codes round to nearest, ties to the even mantissa,
+    onto the E4M3 grid and saturate at +-448 (clamped in float64, before any code is formed: no NaN code and no negative zero
+    is written).  The scale rule restates the MX specification; it could not be checked against MLX."""
+    if w.ndim != 2 or w.shape[1] % 32 != 0:
+        raise ValueError("quantize_mxfp8 expects (N, K) with K divisible by 32")
+    n, k = w.shape
+    g = w.to(torch.float64).reshape(n, k // 32, 32)
+    amax = g.abs().amax(dim=-1, keepdim=True)
+    e = torch.where(amax > 0, torch.frexp(amax)[1].to(torch.int64) - 1 - 8, torch.full_like(amax, -127, dtype=torch.int64)).clamp(-127, 127)
+    v = (g * _pow2(-e)).abs().clamp(max=448.0)
+    ex = (torch.frexp(v)[1].to(torch.int64) - 1).clamp(min=-6)         # floor(log2 v); below 2^-6 the grid is the subnormals' 2^-9
+    a = (torch.round(v * _pow2(3 - ex)) * _pow2(ex - 3)).clamp(max=448.0)      # (torch.round: ties to even)
+    ea = torch.frexp(a)[1].to(torch.int64) - 1                # (a may have carried into the next binade)
+    q = torch.where(a < 2.0 ** -6, (a * 512.0).to(torch.int64), ((ea + 7) << 3) | ((a * _pow2(-ea) - 1.0) * 8.0).to(torch.int64))
+    q = q | ((g < 0) & (q > 0)).to(torch.int64) << 7
+    return pack_codes(q.reshape(n, k), 8), (e + 127).reshape(n, -1).to(torch.uint8)
+
+
+def dequantize_mxfp8(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """-> (N, K) float32, code value x 2^(s - 127): exact in float32 and in bfloat16 (four significant bits)."""
+    q = unpack_codes(packed, 8)
+    n, k = q.shape
+    ef, m = ((q >> 3) & 15).to(torch.float64), (q & 7).to(torch.float64)
+    v = torch.where(ef == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * _pow2(ef - 7)) * torch.where((q & 128) != 0, -1.0, 1.0)
+    s = _pow2(scales.to(torch.int64) - 127)
+    return (v.reshape(n, k // 32, 32) * s[..., None]).reshape(n, k).to(torch.float32)
+
+
 def dequantize(packed: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, group_size: int = 64,
                bits: int = 4) -> torch.Tensor:
     q = unpack_codes(packed, bits).to(torch.float32)

@@ -14,7 +14,10 @@ scales set directly, as a checkpoint would give them), bench.py's timing protoco
 on the same matrix (the bf16 copy written per call + the dense tile GEMM) and mi_op_gemm_prefill on a dense bf16 matrix of the
 same shape; the routes ALTERNATE inside a round, medians of --rounds samples.  A sample is at least --iters launches (default
 20 in this mode) and at least ~5 ms of work (counted at 1 PFLOP/s), so the small shapes repeat a few hundred times; the residual
-epilogues start every sample from a zeroed stream."""
+epilogues start every sample from a zeroed stream.
+
+--fp8: the 8-bit family instead -- mxfp8 (gemm_mx8.hip) against affine int8 in groups of 32 (gemm_qg.hip) and 64
+(gemm_skinny.hip), in the kernel mode (with the o shape added) and in --step."""
 import argparse
 import ctypes as C
 import json
@@ -32,15 +35,25 @@ from mlx_parallm_amd.engine import Engine, SampleArgs
 
 SHAPES = {"qkv": (6144, 4096), "gate_up": (28672, 4096), "down": (4096, 14336)}
 KINDS = {"mxfp4": ("mx4_bf16", 32), "int4_g32": ("q4_bf16", 32), "int4_g64": ("q4_bf16", 64)}
+SHAPES8 = dict(SHAPES, o=(4096, 4096))
+KINDS8 = {"mxfp8": ("mx8_bf16", 32), "int8_g32": ("q8_bf16", 32), "int8_g64": ("q8_bf16", 64)}
+
+
+def bits_of(kind):
+    return 8 if kind[:3] in ("mx8", "q8_") else 4
 
 
 def random_linear(kind, group, N, K, gen):
     """-> [codes, scales(, biases)] as a checkpoint holds them (weights of about N(0, 0.02^2)), on the device"""
-    t = [torch.randint(-2 ** 31, 2 ** 31 - 1, (N, K // 8), dtype=torch.int32, generator=gen).cuda()]
+    bits = bits_of(kind)
+    t = [torch.randint(-2 ** 31, 2 ** 31 - 1, (N, K * bits // 32), dtype=torch.int32, generator=gen).cuda()]
+    if kind.startswith("mx8"):
+        t[0] &= -16843010                                    # 0xfefefefe: no byte is a NaN code (0x7f / 0xff)
+        return t + [torch.randint(111, 114, (N, K // 32), dtype=torch.uint8, generator=gen).cuda()]
     if kind.startswith("mx4"):
         return t + [torch.randint(117, 120, (N, K // 32), dtype=torch.uint8, generator=gen).cuda()]
-    s = (torch.rand((N, K // group), generator=gen) * 0.004 + 0.004).to(torch.bfloat16)
-    return t + [s.cuda(), (s * -7.5).cuda()]
+    s = (torch.rand((N, K // group), generator=gen) * 0.004 + 0.004).to(torch.bfloat16) / (16 if bits == 8 else 1)
+    return t + [s.cuda(), (s * -(2 ** (bits - 1) - 0.5)).cuda()]
 
 
 def tiled(kind, group, N, K):
@@ -53,7 +66,7 @@ def tiled(kind, group, N, K):
     torch.cuda.synchronize()
     L.check(L.lib().mi_op_repack_tiled(C.byref(ol), C.c_void_p(dst.data_ptr())))
     ol.w, ol.scales, ol.biases, ol.layout = dst.data_ptr(), 0, 0, 1
-    return ol, dst, N * K // 2 + N * (K // group) * (1 if kind.startswith("mx4") else 4)
+    return ol, dst, N * K * bits_of(kind) // 8 + N * (K // group) * (1 if kind.startswith("mx") else 4)
 
 
 def spread(v):
@@ -61,8 +74,8 @@ def spread(v):
 
 
 def kernels(args, emit):
-    for shape, (N, K) in SHAPES.items():
-        lin = {name: tiled(kind, group, N, K) for name, (kind, group) in KINDS.items()}
+    for shape, (N, K) in (SHAPES8 if args.fp8 else SHAPES).items():
+        lin = {name: tiled(kind, group, N, K) for name, (kind, group) in (KINDS8 if args.fp8 else KINDS).items()}
         for M in (int(r) for r in args.rows.split(",")):
             x = torch.randn((M, K), dtype=torch.bfloat16, device="cuda")
             out = torch.zeros((M, N), dtype=torch.bfloat16, device="cuda")
@@ -122,7 +135,8 @@ def prefill(args, emit):
 
 
 def engine_with(kind, group, cap):
-    cfg = dict(bench.SHAPES["mistral-7b"], quantization=dict({"group_size": group, "bits": 4}, **({"mode": "mxfp4"} if kind.startswith("mx4") else {})))
+    mode = {"mode": "mxfp4" if kind.startswith("mx4") else "mxfp8"} if kind.startswith("mx") else {}
+    cfg = dict(bench.SHAPES["mistral-7b"], quantization=dict({"group_size": group, "bits": bits_of(kind)}, **mode))
     eng = Engine(cfg, device=0, max_positions=max(cap, 2048), act_dtype="bfloat16")
     H, I, V, D = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"], cfg["hidden_size"] // cfg["num_attention_heads"]
     KV, gen, ones = cfg["num_key_value_heads"] * D, torch.Generator().manual_seed(1), torch.ones(H, dtype=torch.bfloat16)
@@ -146,13 +160,14 @@ def step(args, emit):
     cap = ctx + 2 * (K + W) + 136
     a = bench.parse_args(["--gpus", "1", "--steps", str(K), "--warmup", str(W)])
     a.batch, a.no_prefill_timing, a.profile_kernel = B, True, "gemv_gate_up"
-    engines = {name: engine_with(*KINDS[name], cap) for name in ("mxfp4", "int4_g32")}
+    kinds = KINDS8 if args.fp8 else {n: KINDS[n] for n in ("mxfp4", "int4_g32")}
+    engines = {name: engine_with(*kg, cap) for name, kg in kinds.items()}
     prompts = np.random.default_rng(23).integers(0, 32000, size=(B, ctx)).astype(np.int32)
     ms, gu = {n: [] for n in engines}, {n: [] for n in engines}
     for _ in range(args.rounds):
         for name, (eng, cfg) in engines.items():
             leg = bench.decode_leg(eng, cfg, a, "model", prompts, SampleArgs(temp=0.0), None, 1, cap, instrument=True)
-            n = bench.numbers(cfg, 4, B, K, W, ctx, leg, "model", "gemv_gate_up", 1)
+            n = bench.numbers(cfg, 8 if args.fp8 else 4, B, K, W, ctx, leg, "model", "gemv_gate_up", 1)
             ms[name].append(n["ms_per_step"]); gu[name].append(n["avg_ms"] * 1e3)
     for name in engines:
         emit({"step": name, "ms_per_step": spread(ms[name]), "tokens_per_s": round(B / statistics.median(ms[name]) * 1e3, 1),
@@ -163,6 +178,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--prefill", action="store_true")
+    ap.add_argument("--fp8", action="store_true", help="mxfp8 against int8 (kernel mode and --step)")
     ap.add_argument("--iters", type=int, default=None, help="launches per sample (default 200; --prefill: 20)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--rows", default=None, help="default 1,8,64; --prefill: 256,512,1024,2048,4096,8192")
